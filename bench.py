@@ -14,11 +14,13 @@ Workload at N=1: BASELINE.json configs[2] (= configs[1] with phasing on): 100k C
 N > 1 (`value`): reference windows shard independently — one 3 kb window x 100k reads per rank and batch (weak
 scaling), the only exchange is the RCCL all-gather of the variant table, which rides with each launch as one device
 operation (jl_group_exchange_bind; JL_BENCH_EXCHANGE=worker: the communicator's worker-thread form).
-Every N also times BASELINE.json configs[3] as stated — ONE 10 kb reference whose 1M reads span all windows, split
+With `--full`, every N also times BASELINE.json configs[3] as stated — ONE 10 kb reference whose 1M reads span all windows, split
 into N column windows (strong scaling): call per window with the global Bonferroni factor, all-gather of the table,
 the variant columns broadcast by their owners, phasing across windows — reported as `config3_strong` in the same line.
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task brief), including
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times `--steps` steps and reports the headline figure (`value`
+reads/s, `ms_per_step`) with the configuration; `--dump-outputs DIR` writes what the last timed step gave (dump_outputs).
+`--full` adds the legs below, each a run of its own after the timed steps (the CLI leg before them):
   roofline     the dominant kernel (pileup) against the 8 TB/s HBM peak: algorithmic bytes = reads x columns x 3 / 8 — every
                cell of the resident matrix read exactly once, 3 bits per cell (seven symbols; the bit planes are THE resident
                format since round 4, DESIGN.md "Data layout") — so `frac` is physical: what crosses the HBM over the kernel's
@@ -142,6 +144,35 @@ def same(sig, out):
             and ph["summary"] == sig["summary"])
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, res):
+    """`--dump-outputs DIR`: what the last timed step gave its caller — that window's variant table (one file per field) and
+    its phasing result (summary in SUMMARY_FIELDS order, positions, haplotype counts / patterns / hits, co-occurrence, the
+    per-read haplotype ids) — as DIR/<name>.npy.  Counts and p-values are float64 (exact); the per-read ids are 16-bit and
+    go as float32 (exact).  Should everything exceed DUMP_MAX_BYTES, the ids are a fixed sample (seed 0, sorted indices in
+    phase_read_hap_index.npy)."""
+    from minorseq_amd import capi
+    os.makedirs(path, exist_ok=True)
+    v, ph = res["variants"], res["phase"]
+    arrays = {f"variants_{f}": np.asarray(v[f], dtype=np.float64) for f in capi.VARIANT.names if f != "pad_"}
+    arrays["phase_summary"] = np.array([ph["summary"][k] for k in capi.SUMMARY_FIELDS], dtype=np.float64)
+    for k in ("pos_cols", "hap_count", "hap_pattern", "hit", "cooc"):
+        if ph.get(k) is not None:
+            arrays[f"phase_{k}"] = np.asarray(ph[k], dtype=np.float64)
+    if ph.get("read_hap") is not None:
+        ids = np.asarray(ph["read_hap"]).astype(np.float32)
+        room = DUMP_MAX_BYTES - sum(a.nbytes for a in arrays.values())
+        if ids.nbytes > room:
+            idx = np.sort(np.random.default_rng(0).choice(len(ids), room // 12, replace=False))
+            arrays["phase_read_hap_index"] = idx.astype(np.float64)
+            ids = ids[idx]
+        arrays["phase_read_hap"] = ids
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def subprocess_errors():
     import subprocess
     return subprocess.SubprocessError
@@ -237,7 +268,14 @@ def main():
     ap.add_argument("--e2e-reads", type=int, default=0, help="a second end_to_end size (reads x 3 kb), e.g. 1000000: the decode-bound regime")
     ap.add_argument("--run-timeout", type=float, default=900.0,
                     help="N > 1: seconds the whole run may take; then rank 0 writes the line with what was measured and every rank exits 3")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: end_to_end, latencies, roofline, once_through(_qv), "
+                         "configs[3]/[4], CPU baselines (the --no-* options above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the results of the last timed step as DIR/<name>.npy (float64 / float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around us: be the launcher (decided before torch is imported or any GPU call is made)
         sys.exit(launch_ranks(args, sys.argv[1:]))
@@ -250,7 +288,7 @@ def main():
 
     # the CLI leg first: `juliet` is a process of its own with its own GPU context — before this process opens one
     e2e = e2e_big = None
-    if (int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_end_to_end and (args.reads, args.cols) == (N_READS, N_COLS)
+    if (args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_end_to_end and (args.reads, args.cols) == (N_READS, N_COLS)
             and os.environ.get("JL_BENCH_FORCE_DIST") != "1"):
         try:
             e2e = end_to_end(args.reads, args.cols, 1000, 2)
@@ -299,7 +337,7 @@ def main():
         if not left.acquire(blocking=False):
             return               # (another timer is already writing the line)
         out["error"] = f"{reason} (rank {rank}, at: {stage['at']})"
-        if not args.no_config3:
+        if args.full and not args.no_config3:
             out.setdefault("config3_strong", {"error": reason, "scaling": "strong", "n_gpus": world})
             out.setdefault("config4_strong", {"error": reason, "scaling": "strong", "n_gpus": world})
         if rank == 0:
@@ -640,113 +678,117 @@ def main():
     out.update({"metric": "aligned CCS reads/sec through juliet call+phase" + (" (weak scaling: independent windows per GPU; strong scaling "
                                                                                   "of one reference: config3_strong, config4_strong)" if world > 1 else ""),
                 "value": world * n / (ms_per_step * 1e-3), "ms_per_step": ms_per_step})
-    stage["at"] = "latency legs"
-
-    # latency of ONE batch through the path (its own graph, nothing else on the GPU), for the record
-    def one_batch():
-        jl.run_async(genes, refseq, prm, None, True, 10, True)
-        return jl.run_view()
-    for _ in range(3):
-        one_batch()
-    fence()
-    t1 = time.perf_counter()
-    for _ in range(20):
-        one_batch()
-    fence()
-    latency_ms = 1000.0 * (time.perf_counter() - t1) / 20
-    # ... and the same loop inside the library (jl_time_run: launch -> completion word -> run view -> next launch, host clock):
-    # what a C or C++ caller sees; the figure above has this interpreter between the runs (4-6 us: ctypes, the numpy views)
-    latency_c_ms = jl.time_run(genes, refseq, prm, None, True, 10, True, reps=40)
-
-    # the same for a window with SIXTEEN variant positions (the reference's own screenshots show 9-13 and more,
-    # doc/JULIET.md:350, 362): beyond ten positions a pattern takes two key words — the two-word fused launch
-    many_ms = many_c_ms = None
-    if world == 1 and (n, l) == (N_READS, N_COLS):
-        from minorseq_amd import msa
-        mp = capi.Juliet(local_rank)
-        rows = msa.unpack_columns(jl.download_columns(), n)
-        rng = np.random.default_rng(3)
-        for k in range(11):                       # eleven more edited codons, about 3 % of the reads each
-            who = rng.choice(n, n // 30, replace=False)
-            c0 = 3 * (100 + 61 * k)
-            rows[who, c0:c0 + 3] = (rows[who, c0:c0 + 3] + 1 + k % 3) % 4
-        mp.upload_rows(rows, win_begin=win_begin)
-        del rows
-
-        def many():
-            mp.run_async(genes, refseq, prm, None, True, 10, True)
-            return mp.run_view() or mp.run_fetch(True, True, cap_var=64)
-        for _ in range(4):
-            mv = many()
-        fence()
-        t2 = time.perf_counter()
-        for _ in range(20):
-            mv = many()
-        fence()
-        many_ms = 1000.0 * (time.perf_counter() - t2) / 20
-        many_c_ms = mp.time_run(genes, refseq, prm, None, True, 10, True, reps=40)
-        many_positions = int(mv["phase"]["summary"]["n_positions"])
-        mp.close()
-
-    # dominant kernel alone: HIP events on the stream it is launched on, around back-to-back launches that rotate
-    # over the resident batches (no launch finds its windows in the 256 MiB Infinity Cache).  rocprofv3 sees exactly
-    # these launches when bench.py runs with --kernel-only (profiles/README.md).
-    if G > 1:
-        run_steps(n_units * G)   # the timing hook reads each group's argument table: every group has run
-        fence()
-        t_pileup_ms, alg_bytes = capi.time_pileup_groups(groups, reps=max(20, args.steps // G))
-        # (round 6: the launch the runs make — the pileup with the Fisher stage of its codons in the epilogue; JL_NO_FOLD_CALL=1: the plain one)
-        kernel_name = "pileup_planes_group_kernel" if os.environ.get("JL_NO_FOLD_CALL") else "pileup_fold_group_kernel"
-    else:
-        alg_bytes = n * l * 3.0 / 8.0
-        kernel_name = jl.lib.jl_pileup_kernel_name().decode()
-        try:
-            t_pileup_ms = capi.time_pileup_set(ctxs, reps=max(20, args.steps))
-        except capi.JulietError:   # launch shapes that need zeroed counters (long columns): one launch per event pair
-            t_pileup_ms = jl.time_pileup(reps=max(10, args.steps))
-    achieved = alg_bytes / (t_pileup_ms * 1e-3) / 1e9
-    traffic = None
-    tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(tpath) and (n, l) == (N_READS, N_COLS):   # the PMC passes were taken on the default workload
-        try:
-            tj = json.load(open(tpath))
-            if tj.get("windows_per_launch", 1) == G:
-                traffic = tj.get("pileup_kernel_hbm_bytes_per_launch")
-        except Exception:
-            traffic = None
-
-    step_bytes = n * l * 3.0 / 8.0
+    if args.dump_outputs and rank == 0:   # (before anything else runs on the contexts: `last` views their result blocks)
+        dump_outputs(args.dump_outputs, last)
     # at N > 1 `value` is WEAK scaling (one independent 100k x 3kb window per GPU and batch); ONE reference split over
-    # the GPUs (strong scaling) is config3_strong / config4_strong in the same line
-    out.update({
-        "config": {"workload": f"configs[2]: {n} CCS reads x {l} bp reference per GPU, pileup + Fisher-exact + phasing "
-                               "(96% major + four 1% minor haplotypes, sub 1.75e-4, del 1.3e-3, N 2e-2); every resident "
-                               "batch holds different reads",
-                   "reads_per_gpu": n, "ref_columns_per_gpu": l,
-                   "parallelism": f"window-sharded x{world}, {exchange}" if distributed
-                   else "single GPU",
-                   "rccl_ranks": rccl_ranks, "exchange_form": exchange_form,
-                   "batches_per_launch": G, "launches_in_flight": n_flight, "resident_batches": len(ctxs),
-                   "one_batch_latency_ms": latency_ms, "one_batch_latency_c_abi_ms": latency_c_ms,
-                   "many_positions_latency_ms": many_ms, "many_positions_latency_c_abi_ms": many_c_ms, "many_positions": many_positions if many_ms is not None else None,
-                   "variants_called": state["gathered_rows"] if comm is not None else len(table),
-                   "haplotypes": ph["summary"]["n_haplotypes"],
-                   "windows_verified_in_loop": state["checked"]},
-        "roofline": {"bound": "hbm", "kernel": kernel_name, "achieved": achieved,
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     "traffic_source": "profiles/pmc_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                                       "command (a separate run; counters cannot be read from inside bench.py)" if traffic else None,
-                     "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": t_pileup_ms,
-                     "algorithmic_unit": "3 bits per cell (reads x columns x 3 / 8 bytes): every cell of the resident bit planes read once",
-                     "layout": "bit planes, 3 bits per cell: the one resident format, written directly by every producer",
-                     # the same time against SURVEY 8d's original 4-bit cell (what rounds 1-3 called `frac`)
-                     "frac_in_nibble_units": alg_bytes * (4.0 / 3.0) / (t_pileup_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                     # the same bytes over the whole step (launch gaps, Fisher, phasing, results on the host included)
-                     # one window alone through the whole path (what `juliet in.bam out.json` does): its bytes over its latency
-                     "one_batch_frac": step_bytes / (latency_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                     "step_achieved": step_bytes / (ms_per_step * 1e-3) / 1e9,
-                     "step_frac": step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS},
-    })
+    # the GPUs (strong scaling) is config3_strong / config4_strong in the same line (--full)
+    config = {"workload": f"configs[2]: {n} CCS reads x {l} bp reference per GPU, pileup + Fisher-exact + phasing "
+                          "(96% major + four 1% minor haplotypes, sub 1.75e-4, del 1.3e-3, N 2e-2); every resident "
+                          "batch holds different reads",
+              "reads_per_gpu": n, "ref_columns_per_gpu": l,
+              "parallelism": f"window-sharded x{world}, {exchange}" if distributed
+              else "single GPU",
+              "rccl_ranks": rccl_ranks, "exchange_form": exchange_form,
+              "batches_per_launch": G, "launches_in_flight": n_flight, "resident_batches": len(ctxs),
+              "variants_called": state["gathered_rows"] if comm is not None else len(table),
+              "haplotypes": ph["summary"]["n_haplotypes"],
+              "windows_verified_in_loop": state["checked"]}
+    out["config"] = config
+    if args.full:
+        stage["at"] = "latency legs"
+
+        # latency of ONE batch through the path (its own graph, nothing else on the GPU), for the record
+        def one_batch():
+            jl.run_async(genes, refseq, prm, None, True, 10, True)
+            return jl.run_view()
+        for _ in range(3):
+            one_batch()
+        fence()
+        t1 = time.perf_counter()
+        for _ in range(20):
+            one_batch()
+        fence()
+        latency_ms = 1000.0 * (time.perf_counter() - t1) / 20
+        # ... and the same loop inside the library (jl_time_run: launch -> completion word -> run view -> next launch, host clock):
+        # what a C or C++ caller sees; the figure above has this interpreter between the runs (4-6 us: ctypes, the numpy views)
+        latency_c_ms = jl.time_run(genes, refseq, prm, None, True, 10, True, reps=40)
+
+        # the same for a window with SIXTEEN variant positions (the reference's own screenshots show 9-13 and more,
+        # doc/JULIET.md:350, 362): beyond ten positions a pattern takes two key words — the two-word fused launch
+        many_ms = many_c_ms = None
+        if world == 1 and (n, l) == (N_READS, N_COLS):
+            from minorseq_amd import msa
+            mp = capi.Juliet(local_rank)
+            rows = msa.unpack_columns(jl.download_columns(), n)
+            rng = np.random.default_rng(3)
+            for k in range(11):                       # eleven more edited codons, about 3 % of the reads each
+                who = rng.choice(n, n // 30, replace=False)
+                c0 = 3 * (100 + 61 * k)
+                rows[who, c0:c0 + 3] = (rows[who, c0:c0 + 3] + 1 + k % 3) % 4
+            mp.upload_rows(rows, win_begin=win_begin)
+            del rows
+
+            def many():
+                mp.run_async(genes, refseq, prm, None, True, 10, True)
+                return mp.run_view() or mp.run_fetch(True, True, cap_var=64)
+            for _ in range(4):
+                mv = many()
+            fence()
+            t2 = time.perf_counter()
+            for _ in range(20):
+                mv = many()
+            fence()
+            many_ms = 1000.0 * (time.perf_counter() - t2) / 20
+            many_c_ms = mp.time_run(genes, refseq, prm, None, True, 10, True, reps=40)
+            many_positions = int(mv["phase"]["summary"]["n_positions"])
+            mp.close()
+
+        # dominant kernel alone: HIP events on the stream it is launched on, around back-to-back launches that rotate
+        # over the resident batches (no launch finds its windows in the 256 MiB Infinity Cache).  rocprofv3 sees exactly
+        # these launches when bench.py runs with --kernel-only (profiles/README.md).
+        if G > 1:
+            run_steps(n_units * G)   # the timing hook reads each group's argument table: every group has run
+            fence()
+            t_pileup_ms, alg_bytes = capi.time_pileup_groups(groups, reps=max(20, args.steps // G))
+            # (round 6: the launch the runs make — the pileup with the Fisher stage of its codons in the epilogue; JL_NO_FOLD_CALL=1: the plain one)
+            kernel_name = "pileup_planes_group_kernel" if os.environ.get("JL_NO_FOLD_CALL") else "pileup_fold_group_kernel"
+        else:
+            alg_bytes = n * l * 3.0 / 8.0
+            kernel_name = jl.lib.jl_pileup_kernel_name().decode()
+            try:
+                t_pileup_ms = capi.time_pileup_set(ctxs, reps=max(20, args.steps))
+            except capi.JulietError:   # launch shapes that need zeroed counters (long columns): one launch per event pair
+                t_pileup_ms = jl.time_pileup(reps=max(10, args.steps))
+        achieved = alg_bytes / (t_pileup_ms * 1e-3) / 1e9
+        traffic = None
+        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+        if os.path.exists(tpath) and (n, l) == (N_READS, N_COLS):   # the PMC passes were taken on the default workload
+            try:
+                tj = json.load(open(tpath))
+                if tj.get("windows_per_launch", 1) == G:
+                    traffic = tj.get("pileup_kernel_hbm_bytes_per_launch")
+            except Exception:
+                traffic = None
+
+        step_bytes = n * l * 3.0 / 8.0
+        config.update({"one_batch_latency_ms": latency_ms, "one_batch_latency_c_abi_ms": latency_c_ms,
+                       "many_positions_latency_ms": many_ms, "many_positions_latency_c_abi_ms": many_c_ms,
+                       "many_positions": many_positions if many_ms is not None else None})
+        out["roofline"] = {
+            "bound": "hbm", "kernel": kernel_name, "achieved": achieved,
+            "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+            "traffic_source": "profiles/pmc_traffic.json: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
+                              "command (a separate run; counters cannot be read from inside bench.py)" if traffic else None,
+            "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": t_pileup_ms,
+            "algorithmic_unit": "3 bits per cell (reads x columns x 3 / 8 bytes): every cell of the resident bit planes read once",
+            "layout": "bit planes, 3 bits per cell: the one resident format, written directly by every producer",
+            # the same time against SURVEY 8d's original 4-bit cell (what rounds 1-3 called `frac`)
+            "frac_in_nibble_units": alg_bytes * (4.0 / 3.0) / (t_pileup_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            # the same bytes over the whole step (launch gaps, Fisher, phasing, results on the host included)
+            # one window alone through the whole path (what `juliet in.bam out.json` does): its bytes over its latency
+            "one_batch_frac": step_bytes / (latency_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            "step_achieved": step_bytes / (ms_per_step * 1e-3) / 1e9,
+            "step_frac": step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS}
     for g in (groups or []) + list(partial_groups.values()):
         g.close()
     if e2e is not None:
@@ -754,7 +796,7 @@ def main():
         out["end_to_end"] = e2e
         if e2e_big is not None:
             out["end_to_end_big"] = e2e_big
-    if not args.no_once_through and (n, l) == (N_READS, N_COLS):
+    if args.full and not args.no_once_through and (n, l) == (N_READS, N_COLS):
         try:
             out["once_through"] = once_through(capi, synth, torch, jl, genes, refseq, prm, expected[id(jl)], rank, local_rank, n, l,
                                                win_begin, args.once_steps)
@@ -765,7 +807,7 @@ def main():
                                                   win_begin, args.once_steps, qv=True)
         except (OSError, capi.JulietError) as exc:
             out["once_through_qv"] = {"error": repr(exc)}
-    if not args.no_config3:
+    if args.full and not args.no_config3:
         # The weak-scaling measurement above is complete.  The strong-scaling form adds two exchanges that have only ever
         # run with one rank on hardware: should it fail or stall on some rank, every rank leaves after
         # `--config3-timeout` seconds and the line still goes out with what was measured, the failure named in it.
@@ -787,7 +829,7 @@ def main():
                 raise
             leave(f"rank {rank}: {exc!r}")
         watchdog.cancel()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"], rows_host = cpu_baseline(jl, genes, refseq, expected[id(jl)])
         ncores = usable_cores()
         if ncores > 1:

@@ -19,7 +19,7 @@ for part in "$@"; do
 case $part in
 a)
   cd /tmp; rm -rf $O/a
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/a -o a -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/a_bench_line.json 2> $O/a.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/a -o a -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/a_bench_line.json 2> $O/a.err
   ;;
 b)
   cd /tmp; rm -rf $O/b $O/pf $O/pw
@@ -28,7 +28,7 @@ b)
   rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pw -o pw -- python3 $R/profiles/isolated_pileup.py 25 > /dev/null 2> $O/pw.err
   ;;
 c)
-  cd $R; python3 bench.py > $O/c_bench_line.json 2> $O/c.err
+  cd $R; python3 bench.py --full > $O/c_bench_line.json 2> $O/c.err
   ;;
 e)
   cd $R

@@ -7,8 +7,8 @@ mkdir -p $O
 for i in $(seq 1 $N); do
   for v in fold nofold; do
     if [ $v = nofold ]; then export JL_NO_FOLD_CALL=1; else unset JL_NO_FOLD_CALL; fi
-    python3 $R/bench.py --steps 20 --warmup 5 --no-config3 --no-cpu-baseline --no-once-through --no-end-to-end > $O/${v}_20_$i.json 2>/dev/null
-    python3 $R/bench.py --no-config3 --no-cpu-baseline --no-once-through --no-end-to-end > $O/${v}_long_$i.json 2>/dev/null
+    python3 $R/bench.py --steps 20 --warmup 5 --full --no-config3 --no-cpu-baseline --no-once-through --no-end-to-end > $O/${v}_20_$i.json 2>/dev/null
+    python3 $R/bench.py --full --no-config3 --no-cpu-baseline --no-once-through --no-end-to-end > $O/${v}_long_$i.json 2>/dev/null
   done
 done
 unset JL_NO_FOLD_CALL
