@@ -2,11 +2,13 @@
 // rendering of it) out.  Keeps the documented surface of the reference tool:
 //   juliet [--config/-c CFG] [--mode-phasing/-p] [--region/-r B-E] [--min-perc X] [--max-perc X] [--drm-only]
 //          in.align.bam out.{json,html} [out2.{json,html}]
+//   juliet [options] --batch samples.tsv   (many per-barcode BAMs in one process: BatchRunner below)
 // (doc/JULIET.md:62-66, 121, 160-163, 195, 270-271, 342-344, 352-354, 370).  Everything the reference text
 // leaves open is an explicit flag with the docs/SPEC.md default.  All compute happens on the GPU through
 // the C ABI; without a gfx950 device the tool exits with status 3.
 #include <unistd.h>
 
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -17,7 +19,9 @@
 #include <ctime>
 #include <filesystem>
 #include <fstream>
+#include <functional>
 #include <iostream>
+#include <map>
 #include <memory>
 
 #include "config.hpp"
@@ -56,6 +60,9 @@ struct Options {
     uint32_t ins_min_distance = 10;  // ... and the previous included insertion lies at least this many columns back (UNPINNED)
     bool timing = false;
     std::string exchange;            // --exchange rccl|inproc: how the rank threads exchange (default: rccl, inproc when a device repeats)
+    std::string batch;               // --batch samples.tsv: one `in.bam<TAB>out1[<TAB>out2]` per line, every other option for all of them
+    struct BatchLine { unsigned line; std::string bam; std::vector<std::string> outputs; };
+    std::vector<BatchLine> batch_lines;
 };
 
 [[noreturn]] void usage(int code)
@@ -63,6 +70,7 @@ struct Options {
     std::cerr <<
         "juliet " << kVersion << "\n"
         "usage: juliet [options] in.align.bam out.json|out.html [second output]\n"
+        "       juliet [options] --batch samples.tsv\n"
         "  -c, --config <HIV|ABL1|file.json>   target config (doc/JULIET.md:109-180)\n"
         "  -p, --mode-phasing                  cluster reads into haplotypes (doc/JULIET.md:192-211)\n"
         "  -r, --region <begin-end>            1-based [begin,end) window of the config to call\n"
@@ -82,9 +90,67 @@ struct Options {
         "      --consensus <out.fasta>         also write the window's consensus as `fuse` would (doc/FUSE.md:17-20):\n"
         "                                      majority base, major deletions removed, in-frame majority insertions kept\n"
         "      --ins-min-frac 0.5  --ins-min-distance 10   when an insertion enters the consensus\n"
+        "      --batch <samples.tsv>           many samples in one process: one `in.bam<TAB>out1[<TAB>out2]` per line (blank lines\n"
+        "                                      and lines starting with # skipped); every other option applies to every sample and\n"
+        "                                      each sample gets the files a single run would write.  A sample that fails is named\n"
+        "                                      on stderr and the others go on (exit status 2 if any failed); a GPU error stops\n"
+        "                                      the batch (3).  Not with --windows, --devices a,b, --consensus or --dump-*\n"
         "      --timing                        wall time of each stage on stderr\n"
         "  diagnostics (no GPU needed): --dump-msa <file>  --dump-config <file>\n";
     std::exit(code);
+}
+
+bool output_kind_ok(const std::string &out)   // the outputs are told apart by their extension (doc/JULIET.md:61-66)
+{
+    return out.size() > 5 && (out.substr(out.size() - 5) == ".json" || out.substr(out.size() - 5) == ".html");
+}
+
+// The --batch list: `in.bam<TAB>out1[<TAB>out2 ...]` per line; blank lines and lines starting with # are skipped.  Anything
+// wrong with it ends the process with status 1 before any BAM is read.
+std::vector<Options::BatchLine> read_batch_list(const std::string &path)
+{
+    auto bad = [&](unsigned line, const std::string &why) {
+        std::cerr << "juliet: --batch " << path;
+        if (line) std::cerr << " line " << line;
+        std::cerr << ": " << why << "\n";
+        std::exit(1);
+    };
+    std::error_code ec;
+    if (std::filesystem::is_directory(path, ec)) bad(0, "is a directory");
+    std::ifstream f(path);
+    if (!f) bad(0, "cannot be read");
+    std::vector<Options::BatchLine> lines;
+    std::map<std::string, unsigned> written;   // output path (absolute, normalised) -> the line that names it
+    std::string text;
+    unsigned no = 0;
+    while (std::getline(f, text)) {
+        ++no;
+        if (!text.empty() && text.back() == '\r') text.pop_back();
+        if (text.find_first_not_of(" \t") == std::string::npos || text[0] == '#') continue;
+        std::vector<std::string> fields;
+        for (size_t b = 0;;) {
+            const size_t e = text.find('\t', b);
+            fields.push_back(text.substr(b, e == std::string::npos ? std::string::npos : e - b));
+            if (e == std::string::npos) break;
+            b = e + 1;
+        }
+        if (fields.size() < 2) bad(no, "wants an input BAM and at least one output, separated by tabs");
+        for (const std::string &fld : fields)
+            if (fld.empty()) bad(no, "has an empty field");
+        Options::BatchLine l{no, fields[0], std::vector<std::string>(fields.begin() + 1, fields.end())};
+        for (const std::string &out : l.outputs) {
+            if (!output_kind_ok(out)) bad(no, "output '" + out + "' must end in .json or .html (doc/JULIET.md:61-66)");
+            const std::string key = std::filesystem::absolute(out, ec).lexically_normal().string();
+            const auto it = written.find(key);
+            if (it != written.end())
+                bad(no, "output '" + out + "' is also written by line " + std::to_string(it->second) + " (every output once)");
+            written.emplace(key, no);
+        }
+        lines.push_back(std::move(l));
+    }
+    if (f.bad()) bad(0, "cannot be read");
+    if (lines.empty()) bad(0, "names no sample");
+    return lines;
 }
 
 Options parse(int argc, char **argv)
@@ -151,14 +217,29 @@ Options parse(int argc, char **argv)
         else if (a == "--dump-msa") o.dump_msa = need(i);
         else if (a == "--dump-config") o.dump_config = need(i);
         else if (a == "--timing") o.timing = true;
+        else if (a == "--batch") o.batch = need(i);
         else if (!a.empty() && a[0] == '-') { std::cerr << "juliet: unknown option " << a << "\n"; usage(1); }
         else pos.push_back(a);
     }
+    const std::string prog = argv[0];
+    const size_t slash = prog.find_last_of('/');
+    const bool as_fuse = (slash == std::string::npos ? prog : prog.substr(slash + 1)) == "fuse";
+    if (!o.batch.empty()) {   // everything a batch cannot do is refused here, before any file is read or any GPU work
+        auto refuse = [](const char *why) { std::cerr << "juliet: --batch " << why << "\n"; std::exit(1); };
+        if (as_fuse) refuse("is not an option of fuse");
+        if (!pos.empty()) refuse("takes no input BAM or outputs on the command line: they are the lines of the list");
+        if (o.windows > 1) refuse("runs one window per sample (drop --windows)");
+        if (o.devices.size() > 1) refuse("runs on one device (--device, not a --devices list)");
+        if (!o.consensus.empty()) refuse("writes no consensus (drop --consensus)");
+        if (!o.dump_msa.empty() || !o.dump_config.empty()) refuse("does not combine with --dump-msa or --dump-config");
+        if (!o.devices.empty()) o.device = o.devices[0];
+        o.devices.assign(1, o.device);
+        o.batch_lines = read_batch_list(o.batch);
+        return o;
+    }
     if (!o.dump_config.empty() && pos.empty()) { if (o.devices.empty()) o.devices.push_back(o.device); return o; }
     {   // `fuse in.bam out.fasta` (doc/FUSE.md:26-31): the same front end, asked for the consensus only
-        const std::string prog = argv[0];
-        const size_t slash = prog.find_last_of('/');
-        if ((slash == std::string::npos ? prog : prog.substr(slash + 1)) == "fuse") {
+        if (as_fuse) {
             if (pos.size() != 2) { std::cerr << "fuse: usage: fuse in.align.bam out.fasta\n"; std::exit(1); }
             o.bam = pos[0];
             o.consensus = pos[1];
@@ -180,8 +261,7 @@ Options parse(int argc, char **argv)
     o.bam = pos[0];
     o.outputs.assign(pos.begin() + 1, pos.end());
     for (const std::string &out : o.outputs) {
-        const bool ok = (out.size() > 5 && out.substr(out.size() - 5) == ".json") || (out.size() > 5 && out.substr(out.size() - 5) == ".html");
-        if (!ok) { std::cerr << "juliet: output '" << out << "' must end in .json or .html (doc/JULIET.md:61-66)\n"; usage(1); }
+        if (!output_kind_ok(out)) { std::cerr << "juliet: output '" << out << "' must end in .json or .html (doc/JULIET.md:61-66)\n"; usage(1); }
     }
     return o;
 }
@@ -713,6 +793,672 @@ static void run_rank_local(RankJob &job, const DeviceStageInput &in, const std::
     }
 }
 
+// ---------------------------------------------------------------- one sample, step by step
+// What `juliet in.bam out...` does to its file, cut into the steps that a batch (--batch) runs for each of its samples too:
+// decode and upload, the sample's setup, the fetch of its results, its outputs.  Both paths call these, so a sample of a
+// batch gets what a single run of the same file gets.
+
+uint64_t file_bytes(const std::string &path)
+{
+    std::error_code ec;
+    const uintmax_t n = std::filesystem::file_size(path, ec);
+    return ec ? 0 : (uint64_t)n;
+}
+
+struct Decoded {
+    ReadExtent ext;
+    std::vector<BamRef> refs;
+    std::string header_text;
+};
+
+// ONE pass over the file: records as decoded from BAM (cigar expansion, QV masking and the transpose run on the device) and
+// the extent they cover.  With a device behind it (`uploader`): the pipelined reader — inflate and record parsing on every
+// core, chunks to the uploader in file order; the GPU-free diagnostics and non-BGZF files take the sequential one (into `rec`).
+Decoded decode_bam(const std::string &bam, const IngestOptions &io, RecordUploader *uploader, RecordArrays &rec)
+{
+    Decoded d;
+    RecordSink sink;
+    if (uploader) sink.give = [uploader](RecordArrays &c) { uploader->give(c); };
+    const bool want_qual = io.min_qv > 0;
+    d.ext = (uploader && PipelinedBamReader::is_bgzf(bam))
+                ? PipelinedBamReader::run(bam, io, io.ref_id, want_qual, sink, &d.refs, &d.header_text)
+                : collect_records(bam, io, io.ref_id, want_qual, rec, &d.refs, &d.header_text, uploader ? &sink : nullptr);
+    return d;
+}
+
+// Everything a sample's device stage and outputs are derived from, besides its reads.
+struct SampleSetup {
+    TargetConfig cfg;                // the config, or the ORF "unknown" over the sample's reads
+    uint32_t win_begin = 0, n_cols = 0;
+    std::string chem;
+    jl_params prm = {};
+    std::vector<jl_gene> genes;
+    std::vector<uint8_t> refcodes;
+    const uint8_t *refp() const { return refcodes.empty() ? nullptr : refcodes.data(); }
+};
+
+// The genes and the window of one sample: 0, or 1 when --region leaves no gene of the config (message printed).
+int sample_window(const Options &opt, const TargetConfig &config, const Decoded &d, SampleSetup &s)
+{
+    s.cfg = config;
+    TargetConfig &cfg = s.cfg;
+    int64_t ref_len = std::numeric_limits<int64_t>::max();
+    if (d.ext.ref_id >= 0 && (size_t)d.ext.ref_id < d.refs.size()) ref_len = d.refs[(size_t)d.ext.ref_id].length;
+
+    const bool have_cfg = !cfg.genes.empty();
+    if (!have_cfg) {
+        // no target config: one ORF over the covered window, labelled "unknown" (doc/JULIET.md:182-188);
+        // --region marks the reading frame
+        GeneCfg g;
+        g.name = "unknown";
+        g.begin = g.begin_eff = opt.have_region ? opt.region_b : (uint32_t)d.ext.min_pos + 1;
+        g.end = g.end_eff = opt.have_region ? opt.region_e : (uint32_t)d.ext.max_end + 1;
+        cfg.genes.push_back(g);
+    } else if (opt.have_region) {
+        cfg.apply_region(opt.region_b, opt.region_e);
+        if (cfg.genes.empty()) { std::cerr << "juliet: --region leaves no gene of the config\n"; return 1; }
+    }
+    // window: the called genes plus the -3..+5 context columns (doc/JULIET.md:99-100), inside the reference
+    int64_t gb = std::numeric_limits<int64_t>::max(), ge = 0;
+    for (const GeneCfg &g : cfg.genes) { gb = std::min<int64_t>(gb, (int64_t)g.begin_eff - 1); ge = std::max<int64_t>(ge, (int64_t)g.end_eff - 1); }
+    const int64_t wb = std::max<int64_t>(0, gb - 3);
+    const int64_t we = std::max<int64_t>(wb + 1, std::min<int64_t>(ref_len, ge + 5));
+    s.win_begin = (uint32_t)wb;
+    s.n_cols = (uint32_t)(we - wb);
+    return 0;
+}
+
+// Chemistry (from the sample's own @RG header with --chemistry auto), parameters, genes and reference codes of one sample.
+void sample_params(const Options &opt, const Decoded &d, SampleSetup &s)
+{
+    std::string chem = opt.chemistry;
+    if (chem == "auto") {
+        // chemistry-keyed rates with a permissive fallback (doc/JULIET.md:221-225); the key here is the
+        // platform model in the @RG line
+        chem = (d.header_text.find("SEQUEL") != std::string::npos || d.header_text.find("S/P") != std::string::npos) ? "sequel" : "permissive";
+        if (chem == "permissive") std::cerr << "juliet: chemistry not recognised, permissive mode is active (doc/JULIET.md:221-225)\n";
+    }
+    s.chem = chem;
+    jl_params &prm = s.prm;
+    prm.alpha = opt.alpha;
+    prm.n_tests = opt.n_tests;
+    if (chem == "sequel") prm.err = {0.998826, 5.8e-5, 1.0e-3};
+    else prm.err = {0.99764, 1.2e-4, 2.0e-3};
+    if (opt.match > 0) prm.err.match = opt.match;
+    if (opt.substitution >= 0) prm.err.substitution = opt.substitution;
+    prm.expected_round = opt.expected_round;
+    prm.tail = opt.fisher_tail;
+    prm.min_perc = opt.min_perc;
+    prm.max_perc = opt.max_perc;
+
+    s.genes.clear();
+    for (const GeneCfg &g : s.cfg.genes) s.genes.push_back({g.begin_eff, g.end_eff});
+    s.refcodes.clear();
+    if (!s.cfg.reference_sequence.empty())
+        for (char ch : s.cfg.reference_sequence) s.refcodes.push_back(base_code(ch));
+}
+
+using Tick = std::function<void(const char *)>;
+
+// The variant table (unless `calls` is off: the pileup alone ran) and the column counts of the run last enqueued on `ctx`,
+// whether it ran alone or in a group.  R.col_counts holds n_cols * 6 entries.  nullptr, or the step that failed.
+const char *fetch_calls(jl_ctx *ctx, bool calls, Results &R, const Tick &tick)
+{
+    R.var.resize(4096);
+    uint32_t nv = 0;
+    if (calls && jl_call_fetch(ctx, R.var.data(), 4096, &nv) != JL_OK) return "call fetch";
+    R.var.resize(nv);
+    tick("  wait for the run + table");
+    if (jl_pileup_fetch(ctx, R.col_counts.data(), nullptr, nullptr, nullptr, nullptr, nullptr) != JL_OK) return "pileup fetch";
+    tick("  column counts");
+    return nullptr;
+}
+
+// The haplotypes and the per-read ids of a phasing run, after fetch_calls.
+const char *fetch_phase(jl_ctx *ctx, uint64_t n_reads, Results &R)
+{
+    const uint32_t cap_var = std::max<uint32_t>(1, (uint32_t)R.var.size());
+    R.pos_cols.resize(cap_var);
+    R.hap_count.resize(JL_MAX_HAPLOTYPES);
+    R.hap_pattern.resize((size_t)JL_MAX_HAPLOTYPES * cap_var);
+    R.hit.resize((size_t)cap_var * JL_MAX_HAPLOTYPES);
+    R.read_hap.resize(n_reads);
+    R.pat_stride = cap_var;
+    R.hit_stride = JL_MAX_HAPLOTYPES;
+    if (jl_phase_fetch(ctx, &R.ps, R.pos_cols.data(), R.hap_count.data(), R.hap_pattern.data(), R.hit.data(), R.read_hap.data(), nullptr, cap_var) != JL_OK)
+        return "phase fetch";
+    return nullptr;
+}
+
+// The JSON document of one sample (doc/JULIET.md:61-107, 207-211); the HTML output is its rendering.
+Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam, const std::string &cmdline,
+                const std::vector<std::string> &names, uint64_t n_reads, const Results &R)
+{
+    const TargetConfig &cfg = s.cfg;
+    const uint32_t win_begin = s.win_begin, n_cols = s.n_cols;
+    const std::string &chem = s.chem;
+    const std::vector<jl_variant> &var = R.var;
+    const std::vector<uint32_t> &col_counts = R.col_counts;
+    const jl_phase_summary &ps = R.ps;
+    const std::vector<uint32_t> &pos_cols = R.pos_cols, &hap_count = R.hap_count;
+    const std::vector<uint8_t> &hap_pattern = R.hap_pattern, &hit = R.hit;
+    const std::vector<uint16_t> &read_hap = R.read_hap;
+
+    Json root = Json::object();
+    root.set("input", Json::object()
+                          .set("timestamp", Json::of(iso_now()))
+                          .set("input_file", Json::of(bam))
+                          .set("command_line", Json::of(cmdline))
+                          .set("juliet_version", Json::of(kVersion)));
+    Json tc = cfg.echo();
+    tc.set("n_reads", Json::of((int64_t)n_reads));
+    tc.set("window_begin", Json::of(win_begin + 1)).set("window_end", Json::of(win_begin + n_cols + 1));
+    tc.set("chemistry_model", Json::of(chem));
+    root.set("target_config", tc);
+
+    Json genes_json = Json::array();
+    const uint32_t H = ps.n_haplotypes;
+    for (size_t g = 0; g < cfg.genes.size(); ++g) {
+        Json gj = Json::object();
+        gj.set("name", Json::of(cfg.genes[g].name));
+        Json vps = Json::array();
+        size_t v = 0;
+        while (v < var.size()) {
+            if (var[v].gene != g) { ++v; continue; }
+            size_t e = v;
+            while (e < var.size() && var[e].gene == g && var[e].codon_pos == var[v].codon_pos) ++e;
+            const jl_variant &f = var[v];
+            Json vp = Json::object();
+            vp.set("ref_codon", Json::of(codon_string(f.ref_codon)));
+            vp.set("ref_amino_acid", Json::of(std::string(1, translate(f.ref_codon))));
+            const uint32_t aa_pos = f.codon_pos + cfg.genes[g].first_codon;
+            vp.set("ref_position", Json::of(aa_pos));
+            vp.set("coverage", Json::of(f.coverage));
+            // variant codons grouped by amino acid (position 223 with two rows)
+            Json aas = Json::array();
+            std::vector<char> order;
+            for (size_t k = v; k < e; ++k) {
+                const char aa = translate(var[k].codon);
+                if (std::find(order.begin(), order.end(), aa) == order.end()) order.push_back(aa);
+            }
+            // amino acids in alphabetical order: juliet_abl-nohaplotype.png prints "A GCC" above "P CCA" at ABL1 223
+            std::sort(order.begin(), order.end());
+            for (char aa : order) {
+                Json aj = Json::object();
+                aj.set("amino_acid", Json::of(std::string(1, aa)));
+                Json cods = Json::array();
+                for (size_t k = v; k < e; ++k) {
+                    if (translate(var[k].codon) != aa) continue;
+                    Json cj = Json::object();
+                    cj.set("codon", Json::of(codon_string(var[k].codon)));
+                    cj.set("frequency", Json::of((double)var[k].count / (double)var[k].coverage));
+                    cj.set("count", Json::of(var[k].count));
+                    cj.set("expected", Json::of(var[k].expected));
+                    cj.set("pValue", Json::of(var[k].p_value));
+                    cj.set("log_pValue", Json::of(var[k].log_p));
+                    cj.set("known_drm", Json::of(cfg.known_drms(g, aa_pos, aa)));
+                    if (opt.phasing) {
+                        Json hh = Json::array();
+                        for (uint32_t h = 0; h < H; ++h) hh.push(Json::of(hit[(size_t)k * R.hit_stride + h] != 0));
+                        cj.set("haplotype_hit", hh);  // doc/JULIET.md:207-209
+                    }
+                    cods.push(cj);
+                }
+                aj.set("variant_codons", cods);
+                aas.push(aj);
+            }
+            vp.set("variant_amino_acids", aas);
+            // MSA context: -3 .. +5 around the codon's first base (doc/JULIET.md:99-100)
+            Json msa = Json::array();
+            for (int rel = -3; rel <= 5; ++rel) {
+                const int64_t c = (int64_t)f.col + rel;
+                if (c < 0 || c >= (int64_t)n_cols) continue;
+                const uint32_t *cc = &col_counts[(size_t)c * 6];
+                Json mj = Json::object();
+                mj.set("rel_pos", Json::of((int64_t)rel)).set("abs_pos", Json::of((int64_t)(win_begin + c + 1)));
+                static const char *sym[6] = {"A", "C", "G", "T", "-", "N"};
+                for (int s = 0; s < 6; ++s) mj.set(sym[s], Json::of(cc[s]));
+                const size_t r = (size_t)win_begin + (size_t)c;
+                if (r < cfg.reference_sequence.size()) mj.set("wt", Json::of(std::string(1, (char)std::toupper((unsigned char)cfg.reference_sequence[r]))));
+                msa.push(mj);
+            }
+            vp.set("msa", msa);
+            vps.push(vp);
+            v = e;
+        }
+        gj.set("variant_positions", vps);
+        genes_json.push(gj);
+    }
+    root.set("genes", genes_json);
+
+    // Section 4, drug summaries: variants grouped by annotated drug (doc/JULIET.md:104-107)
+    {
+        std::vector<std::pair<std::string, Json>> by_drug;
+        for (const jl_variant &f : var) {
+            const GeneCfg &g = cfg.genes[f.gene];
+            const uint32_t aa_pos = f.codon_pos + g.first_codon;
+            const char aa = translate(f.codon);
+            for (const Drm &d : g.drms) {
+                bool hit_drm = false;
+                for (const DrmPosition &dp : d.positions) hit_drm = hit_drm || dp.matches(aa_pos, aa);
+                if (!hit_drm) continue;
+                Json e = Json::object();
+                e.set("gene", Json::of(g.name));
+                e.set("mutation", Json::of(std::string(1, translate(f.ref_codon)) + std::to_string(aa_pos) + std::string(1, aa)));
+                e.set("codon", Json::of(codon_string(f.codon)));
+                e.set("frequency", Json::of((double)f.count / (double)f.coverage));
+                auto it = std::find_if(by_drug.begin(), by_drug.end(), [&](const std::pair<std::string, Json> &kv) { return kv.first == d.name; });
+                if (it == by_drug.end()) { by_drug.emplace_back(d.name, Json::array()); it = by_drug.end() - 1; }
+                it->second.push(e);
+            }
+        }
+        Json ds = Json::array();
+        for (auto &kv : by_drug) ds.push(Json::object().set("drug", Json::of(kv.first)).set("variants", kv.second));
+        root.set("drug_summaries", ds);
+    }
+
+    if (opt.phasing) {  // root `haplotype` block: counts and read names, same order as haplotype_hit (doc/JULIET.md:209-211)
+        Json hb = Json::object();
+        hb.set("reported_reads", Json::of(ps.reported_reads)).set("insufficient_coverage_reads", Json::of(ps.insufficient_reads));
+        hb.set("damaged_reads", Json::of(ps.damaged_reads)).set("marginal_gaps", Json::of(ps.marginal_gap));
+        hb.set("marginal_heteroduplexes", Json::of(ps.marginal_heteroduplex)).set("marginal_partial", Json::of(ps.marginal_partial));
+        std::vector<std::vector<uint32_t>> members(H);
+        for (uint64_t i = 0; i < n_reads; ++i)
+            if (read_hap[i] < H) members[read_hap[i]].push_back((uint32_t)i);
+        Json hs = Json::array();
+        for (uint32_t h = 0; h < H; ++h) {
+            Json hj = Json::object();
+            hj.set("name", Json::of(haplotype_name(h))).set("reads", Json::of(hap_count[h]));
+            hj.set("frequency", Json::of(ps.reported_reads ? (double)hap_count[h] / (double)ps.reported_reads : 0.0));
+            Json cods = Json::array();
+            for (uint32_t p = 0; p < ps.n_positions; ++p) cods.push(Json::of(codon_string(hap_pattern[(size_t)h * R.pat_stride + p])));
+            hj.set("codons", std::move(cods));
+            Json rn = Json::array();      // (moved on, level by level: a copy of this list per level was most of the stage at a million reads)
+            rn.arr.reserve(members[h].size());
+            for (uint32_t i : members[h]) rn.push(Json::of(names[i]));
+            hj.set("read_names", std::move(rn));
+            hs.push(std::move(hj));
+        }
+        hb.set("haplotypes", std::move(hs));
+        Json pc = Json::array();
+        for (uint32_t p = 0; p < ps.n_positions; ++p) pc.push(Json::of(win_begin + pos_cols[p] + 1));
+        hb.set("variant_positions_abs", std::move(pc));
+        root.set("haplotype", std::move(hb));
+    }
+    return root;
+}
+
+// Every output of one run — the JSON text, or its HTML rendering, by extension — each file closed and its stream checked:
+// a short write or a full disk is a failed output, not a quiet success.  "" or the first output that failed.
+std::string write_outputs(const std::vector<std::string> &outputs, const Json &root)
+{
+    std::string text;
+    root.write(text);
+    text += "\n";
+    for (const std::string &out : outputs) {
+        std::ofstream f(out);
+        if (!f) return out;
+        if (out.substr(out.size() - 5) == ".json") f << text;
+        else f << render_html(root);
+        f.close();
+        if (!f) return out;
+    }
+    return "";
+}
+
+// ---------------------------------------------------------------- --batch: many samples in one process
+// One device and ONE pool of contexts, made once and refilled sample after sample (jl_records_begin drops what a context held
+// before), so the runtime start and the contexts are paid once per list instead of once per file.  A decoding thread takes the
+// list in order: decode + upload into a free context of the pool (the first context comes up while the first file decodes, as
+// in a single run), the sample's setup, the device ingest, the --drm-only masks; the sample is then READY.  The main thread
+// runs the ready samples: those that share a group key (genes, reference codes, parameters, window, drm masks or none) up to
+// eight at a time through one group run (one launch per stage for all of them), any other alone (jl_run_async); a group that
+// refuses its windows (pileup chunk widths, a window that needs the two- or multi-word phasing pipeline) runs them alone too.
+// Each sample's results are fetched with the calls of a single run, its context goes back to the pool and its outputs are
+// written while the next samples decode.  The pool bounds what is resident: at most kPool samples, whatever the list's length.
+class BatchRunner {
+public:
+    BatchRunner(const Options &opt, const TargetConfig &cfg, const std::string &cmdline) : opt_(opt), cfg_(cfg), cmdline_(cmdline) {}
+
+    int run()
+    {
+        const auto t_start = std::chrono::steady_clock::now();
+        const size_t n_pool = std::min<size_t>(kPool, opt_.batch_lines.size());
+        const int dev = opt_.device;
+        first_ = std::async(std::launch::async, [dev]() {
+                     jl_ctx *c = nullptr;
+                     const int rc = jl_ctx_create(dev, nullptr, &c);
+                     return std::make_pair(rc, c);
+                 }).share();
+        std::thread creator([this, n_pool] { create_pool(n_pool); });
+        std::thread producer([this] { produce(); });
+        for (;;) {
+            std::vector<std::unique_ptr<Sample>> take;
+            {
+                // what is ready runs once a whole group is, or when nothing more comes soon: the list is through, or the decoding
+                // thread waits for a context that only this thread can give back (the whole pool exists and is taken)
+                std::unique_lock<std::mutex> lk(m_);
+                cv_.wait(lk, [&] {
+                    return ready_.size() >= kGroupMax || producer_done_ || (producer_waiting_ && created_ + 1 >= n_pool && !ready_.empty());
+                });
+                if (ready_.empty() && producer_done_) break;
+                while (!ready_.empty()) {
+                    take.push_back(std::move(ready_.front()));
+                    ready_.pop_front();
+                }
+            }
+            dispatch(take);
+        }
+        producer.join();
+        creator.join();
+        const unsigned failed = n_failed_.load();
+        if (opt_.timing)
+            fprintf(stderr, "juliet: timing batch total  %zu samples  %u failed  %.1f ms\n", opt_.batch_lines.size(), failed,
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count());
+        // every output is written, closed and checked: the same fast end as a single run (JL_SLOW_EXIT=1: the long way)
+        if (!getenv("JL_SLOW_EXIT")) {
+            std::cout.flush();
+            std::cerr.flush();
+            fflush(nullptr);
+            _exit(failed ? 2 : 0);
+        }
+        for (auto &g : groups_) jl_group_destroy(g.second);
+        for (jl_ctx *c : pool_) jl_ctx_destroy(c);
+        return failed ? 2 : 0;
+    }
+
+private:
+    static constexpr size_t kPool = 16;       // contexts, i.e. samples resident at once
+    static constexpr size_t kGroupMax = 8;    // samples per group run (one launch per stage for the eight)
+    static constexpr size_t kGroupCache = 16;
+
+    struct Sample {
+        const Options::BatchLine *line = nullptr;
+        jl_ctx *ctx = nullptr;
+        SampleSetup s;
+        std::vector<std::string> names;
+        uint64_t n_reads = 0;
+        bool drm_only = false;
+        std::vector<uint64_t> drm_masks;
+        Results R;
+        // what the run gets, as in a single run (empty masks — no evaluated position — are none)
+        const uint64_t *masks() const { return drm_only ? drm_masks.data() : nullptr; }
+    };
+
+    // A GPU error is no failure of one sample: the batch stops here and writes nothing more (an output being written is finished
+    // first, so that none is left half written).
+    [[noreturn]] void gpu_error(const std::string &what)
+    {
+        std::lock_guard<std::mutex> lk(io_m_);
+        std::cerr << "juliet: batch stopped by a GPU error: " << what << "\n";
+        std::cerr.flush();
+        fflush(nullptr);
+        _exit(3);
+    }
+    void sample_failed(const Options::BatchLine &l, const std::string &why)
+    {
+        const std::string msg = "juliet: batch line " + std::to_string(l.line) + " (" + l.bam + "): " + why + "\n";
+        fputs(msg.c_str(), stderr);
+        ++n_failed_;
+    }
+
+    // ---- the pool
+    void create_pool(size_t n)   // contexts 1 .. n-1, once the first is up (the runtime starts once)
+    {
+        if (first_.get().first != JL_OK) return;   // (the decoding thread reports it)
+        for (size_t k = 1; k < n; ++k) {
+            jl_ctx *c = nullptr;
+            if (jl_ctx_create(opt_.device, nullptr, &c) != JL_OK) gpu_error(std::string("context: ") + jl_last_error(c));
+            {
+                std::lock_guard<std::mutex> lk(m_);
+                pool_.push_back(c);
+                free_.push_back(c);
+                ++created_;
+            }
+            cv_.notify_all();
+        }
+    }
+    jl_ctx *acquire()
+    {
+        std::unique_lock<std::mutex> lk(m_);
+        producer_waiting_ = true;
+        cv_.notify_all();
+        cv_.wait(lk, [&] { return !free_.empty(); });
+        producer_waiting_ = false;
+        jl_ctx *c = free_.front();
+        free_.pop_front();
+        return c;
+    }
+    void release(jl_ctx *c)
+    {
+        {
+            std::lock_guard<std::mutex> lk(m_);
+            free_.push_back(c);
+        }
+        cv_.notify_all();
+    }
+
+    // ---- the decoding thread
+    void produce()
+    {
+        for (size_t i = 0; i < opt_.batch_lines.size(); ++i) {
+            std::unique_ptr<Sample> smp(new Sample);
+            smp->line = &opt_.batch_lines[i];
+            smp->drm_only = opt_.drm_only;
+            std::shared_future<std::pair<int, jl_ctx *>> up;
+            if (i == 0) {
+                up = first_;
+            } else {
+                std::promise<std::pair<int, jl_ctx *>> p;
+                p.set_value(std::make_pair((int)JL_OK, acquire()));
+                up = p.get_future().share();
+            }
+            const std::string why = prepare(*smp, up);
+            if (!smp->ctx) smp->ctx = context_of(up);   // (a sample that failed before it asked for its context)
+            if (i == 0) {
+                std::lock_guard<std::mutex> lk(m_);
+                pool_.push_back(smp->ctx);
+            }
+            if (!why.empty()) {
+                sample_failed(*smp->line, why);
+                release(smp->ctx);
+                continue;
+            }
+            {
+                std::lock_guard<std::mutex> lk(m_);
+                ready_.push_back(std::move(smp));
+            }
+            cv_.notify_all();
+        }
+        {
+            std::lock_guard<std::mutex> lk(m_);
+            producer_done_ = true;
+        }
+        cv_.notify_all();
+    }
+    jl_ctx *context_of(const std::shared_future<std::pair<int, jl_ctx *>> &up)
+    {
+        const auto r = up.get();
+        if (r.first != JL_OK) gpu_error("no usable GPU (this tool has no CPU fallback)");
+        return r.second;
+    }
+    // Decode + upload, setup, device ingest and masks of one sample: "" (ready), or why the sample failed.
+    std::string prepare(Sample &smp, const std::shared_future<std::pair<int, jl_ctx *>> &up)
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        const Options::BatchLine &l = *smp.line;
+        IngestOptions io;
+        io.min_qv = opt_.min_qv;
+        io.min_rq = opt_.min_rq;
+        std::unique_ptr<RecordUploader> uploader(new RecordUploader({up}, file_bytes(l.bam), opt_.min_qv > 0));
+        Decoded dec;
+        try {
+            RecordArrays rec;
+            dec = decode_bam(l.bam, io, uploader.get(), rec);
+        } catch (const std::exception &e) {
+            return e.what();
+        }
+        smp.ctx = context_of(up);
+        if (const int rc = uploader->finish()) {
+            jl_ctx *c = uploader->failed() ? uploader->failed() : smp.ctx;
+            if (rc == JL_ERR_ARG) return std::string("record upload: ") + jl_last_error(c);   // (the records, not the device)
+            gpu_error(std::string("record upload: ") + jl_last_error(c));
+        }
+        if (dec.ext.n_reads == 0) return "no primary or supplementary alignments";
+        if (uploader->n_reads != dec.ext.n_reads) gpu_error("record upload lost reads");
+        smp.names.swap(uploader->names);
+        uploader.reset();   // (its threads and its gathered arrays)
+        smp.n_reads = dec.ext.n_reads;
+        if (sample_window(opt_, cfg_, dec, smp.s)) return "--region leaves no gene of the config";
+        sample_params(opt_, dec, smp.s);
+        const int rc = jl_records_finish(smp.ctx, smp.s.n_cols, smp.s.win_begin, opt_.min_qv);
+        if (rc == JL_ERR_ARG || rc == JL_ERR_STATE) return std::string("ingest: ") + jl_last_error(smp.ctx);   // (a malformed record)
+        if (rc != JL_OK) gpu_error(std::string("ingest: ") + jl_last_error(smp.ctx));
+        if (opt_.drm_only) {
+            const DeviceStageInput in{&opt_, &smp.s.cfg, &smp.s.genes, &smp.s.refcodes, smp.s.prm, smp.s.win_begin, smp.s.n_cols, smp.n_reads};
+            if (drm_masks_of(smp.ctx, in, smp.drm_masks)) gpu_error(std::string("pileup: ") + jl_last_error(smp.ctx));
+        }
+        if (opt_.timing)
+            fprintf(stderr, "juliet: timing batch decode  line %u  %llu reads  %.1f ms\n", l.line, (unsigned long long)smp.n_reads,
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        return "";
+    }
+
+    // ---- the device stage, on the main thread
+    static bool same_key(const Sample &a, const Sample &b)
+    {
+        const SampleSetup &x = a.s, &y = b.s;
+        if (x.win_begin != y.win_begin || x.n_cols != y.n_cols || x.genes.size() != y.genes.size() || x.refcodes != y.refcodes ||
+            (a.masks() == nullptr) != (b.masks() == nullptr))
+            return false;
+        for (size_t g = 0; g < x.genes.size(); ++g)
+            if (x.genes[g].begin != y.genes[g].begin || x.genes[g].end != y.genes[g].end) return false;
+        return memcmp(&x.prm, &y.prm, sizeof(jl_params)) == 0;
+    }
+    void dispatch(std::vector<std::unique_ptr<Sample>> &take)
+    {
+        std::vector<std::vector<Sample *>> classes;   // samples of one group key, in list order
+        for (auto &p : take) {
+            auto it = std::find_if(classes.begin(), classes.end(), [&](const std::vector<Sample *> &c) { return same_key(*c[0], *p); });
+            if (it == classes.end()) classes.push_back({p.get()});
+            else it->push_back(p.get());
+        }
+        for (const std::vector<Sample *> &c : classes)
+            for (size_t o = 0; o < c.size(); o += kGroupMax)
+                run_chunk(std::vector<Sample *>(c.begin() + (ptrdiff_t)o, c.begin() + (ptrdiff_t)std::min(c.size(), o + kGroupMax)));
+        for (auto &p : take) write(*p);
+        take.clear();
+    }
+    void run_chunk(std::vector<Sample *> chunk)
+    {
+        auto t0 = std::chrono::steady_clock::now();
+        if (chunk.size() >= 2) {
+            // the contexts in one order whatever the samples' order: a group of the same contexts is used again
+            std::sort(chunk.begin(), chunk.end(), [](const Sample *a, const Sample *b) { return std::less<jl_ctx *>()(a->ctx, b->ctx); });
+            jl_group *g = group_of(chunk);
+            const SampleSetup &s = chunk[0]->s;
+            std::vector<const uint64_t *> masks;
+            for (const Sample *x : chunk) masks.push_back(x->masks());
+            const int rc = jl_group_run_masked_async(g, s.genes.data(), (uint32_t)s.genes.size(), s.refp(), (uint32_t)s.refcodes.size(), &s.prm,
+                                                     masks.data(), opt_.phasing, opt_.min_reads, opt_.phasing);
+            if (rc == JL_OK) {
+                for (const Sample *x : chunk) last_group_[x->ctx] = g;
+                fetch(chunk);
+                timing_line("group ", chunk, t0);
+                return;
+            }
+            // JL_ERR_ARG: the group refuses these windows together; each runs alone (a refusal never fails a sample)
+            if (rc != JL_ERR_ARG) gpu_error(std::string("group run: ") + jl_group_last_error(g));
+            if (opt_.timing) fprintf(stderr, "juliet: timing batch refused  %zu samples: %s\n", chunk.size(), jl_group_last_error(g));
+        }
+        for (Sample *x : chunk) {
+            if (x != chunk[0]) t0 = std::chrono::steady_clock::now();
+            const SampleSetup &s = x->s;
+            if (jl_run_async(x->ctx, s.genes.data(), (uint32_t)s.genes.size(), s.refp(), (uint32_t)s.refcodes.size(), &s.prm, x->masks(),
+                             opt_.phasing, opt_.min_reads, opt_.phasing) != JL_OK)
+                gpu_error(std::string("run: ") + jl_last_error(x->ctx));
+            last_group_[x->ctx] = nullptr;
+            fetch({x});
+            timing_line("single", {x}, t0);
+        }
+    }
+    // the results of each sample with the fetch calls of a single run; then its context goes back to the pool
+    void fetch(const std::vector<Sample *> &chunk)
+    {
+        const Tick quiet = [](const char *) {};
+        for (Sample *x : chunk) {
+            x->R.col_counts.assign((size_t)x->s.n_cols * 6, 0);
+            const char *what = fetch_calls(x->ctx, true, x->R, quiet);
+            if (!what && opt_.phasing) what = fetch_phase(x->ctx, x->n_reads, x->R);
+            if (!what && jl_sync(x->ctx) != JL_OK) what = "sync";   // (the group's stream too: nothing of the run is left on the device)
+            if (what) gpu_error(std::string(what) + ": " + jl_last_error(x->ctx));
+            release(x->ctx);
+        }
+    }
+    void timing_line(const char *kind, const std::vector<Sample *> &chunk, std::chrono::steady_clock::time_point t0)
+    {
+        if (!opt_.timing) return;
+        std::string lines;
+        for (const Sample *x : chunk) lines += (lines.empty() ? "" : ",") + std::to_string(x->line->line);
+        fprintf(stderr, "juliet: timing batch %s %2zu samples  lines %s  run + fetch %.2f ms\n", kind, chunk.size(), lines.c_str(),
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    }
+    // A group of exactly these contexts, made once and kept.  When the cache is full, one goes that is no context's last group
+    // run (a context's next run waits for the stream of its last group run, which must still exist).
+    jl_group *group_of(const std::vector<Sample *> &chunk)
+    {
+        std::vector<jl_ctx *> ctxs;
+        for (const Sample *x : chunk) ctxs.push_back(x->ctx);
+        for (auto &e : groups_)
+            if (e.first == ctxs) return e.second;
+        if (groups_.size() >= kGroupCache)
+            for (auto it = groups_.begin(); it != groups_.end(); ++it) {
+                bool in_use = false;
+                for (const auto &lg : last_group_) in_use = in_use || lg.second == it->second;
+                if (in_use) continue;
+                jl_group_destroy(it->second);
+                groups_.erase(it);
+                break;
+            }
+        jl_group *g = nullptr;
+        if (jl_group_create(ctxs.data(), (uint32_t)ctxs.size(), &g) != JL_OK) gpu_error("cannot create a group of " + std::to_string(ctxs.size()) + " contexts");
+        groups_.emplace_back(ctxs, g);
+        return g;
+    }
+    void write(Sample &x)
+    {
+        try {
+            const Json root = build_json(opt_, x.s, x.line->bam, cmdline_, x.names, x.n_reads, x.R);
+            std::lock_guard<std::mutex> lk(io_m_);
+            const std::string failed = write_outputs(x.line->outputs, root);
+            if (!failed.empty()) sample_failed(*x.line, "cannot write " + failed);
+        } catch (const std::exception &e) {
+            sample_failed(*x.line, e.what());
+        }
+    }
+
+    const Options &opt_;
+    const TargetConfig &cfg_;
+    const std::string &cmdline_;
+    std::shared_future<std::pair<int, jl_ctx *>> first_;
+    std::mutex m_, io_m_;
+    std::condition_variable cv_;
+    std::vector<jl_ctx *> pool_;           // every context of the pool
+    std::deque<jl_ctx *> free_;
+    size_t created_ = 0;                   // contexts the pool thread made (the first is not counted)
+    bool producer_waiting_ = false, producer_done_ = false;
+    std::deque<std::unique_ptr<Sample>> ready_;
+    std::atomic<unsigned> n_failed_{0};
+    std::vector<std::pair<std::vector<jl_ctx *>, jl_group *>> groups_;   // main thread only
+    std::map<jl_ctx *, jl_group *> last_group_;                          // main thread only
+};
+
+int run_batch(const Options &opt, const TargetConfig &cfg, const std::string &cmdline)
+{
+    BatchRunner b(opt, cfg, cmdline);
+    return b.run();
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -727,7 +1473,7 @@ int main(int argc, char **argv)
         opt = parse(argc, argv);
         const auto t_start = std::chrono::steady_clock::now();
         auto t_last = t_start;
-        auto tick = [&](const char *what) {
+        const Tick tick = [&](const char *what) {
             if (!opt.timing) return;
             const auto now = std::chrono::steady_clock::now();
             fprintf(stderr, "juliet: timing %-26s %9.1f ms  (at %9.1f ms)\n", what,
@@ -738,6 +1484,7 @@ int main(int argc, char **argv)
         // ---------------------------------------------------------------- target config
         TargetConfig cfg;
         if (!opt.config.empty()) cfg = TargetConfig::load(opt.config);
+        if (!opt.batch.empty()) return run_batch(opt, cfg, cmdline);
         if (!opt.dump_config.empty() && opt.bam.empty()) {
             if (opt.have_region) cfg.apply_region(opt.region_b, opt.region_e);
             Json j = cfg.echo();
@@ -758,7 +1505,6 @@ int main(int argc, char **argv)
         const bool need_gpu = !opt.outputs.empty() || opt.fuse_only;
         std::vector<std::shared_future<std::pair<int, jl_ctx *>>> ctx_ups;
         std::unique_ptr<RecordUploader> uploader;
-        RecordSink sink;
         if (need_gpu) {
             for (int dev : opt.devices)
                 ctx_ups.push_back(std::async(std::launch::async, [dev]() {
@@ -766,46 +1512,17 @@ int main(int argc, char **argv)
                     const int rc = jl_ctx_create(dev, nullptr, &c);
                     return std::make_pair(rc, c);
                 }).share());
-            std::error_code ec;
-            const uintmax_t fsz = std::filesystem::file_size(opt.bam, ec);
-            uploader.reset(new RecordUploader(ctx_ups, ec ? 0 : (uint64_t)fsz, opt.min_qv > 0));
-            sink.give = [&uploader](RecordArrays &c) { uploader->give(c); };
+            uploader.reset(new RecordUploader(ctx_ups, file_bytes(opt.bam), opt.min_qv > 0));
         }
-        // ONE pass over the file: records as decoded from BAM (cigar expansion, QV masking and the transpose run on
-        // the device) and the extent they cover
         RecordArrays rec;
-        std::vector<BamRef> bam_refs;
-        std::string header_text;
-        // (with a device behind it: the pipelined reader — inflate and record parsing on every core, chunks to the uploader
-        // in file order; the GPU-free diagnostics and non-BGZF files take the sequential one)
-        const ReadExtent ext = (uploader && PipelinedBamReader::is_bgzf(opt.bam))
-                                   ? PipelinedBamReader::run(opt.bam, io, io.ref_id, opt.min_qv > 0, sink, &bam_refs, &header_text)
-                                   : collect_records(opt.bam, io, io.ref_id, opt.min_qv > 0, rec, &bam_refs, &header_text,
-                                                     uploader ? &sink : nullptr);
+        const Decoded dec = decode_bam(opt.bam, io, uploader.get(), rec);
+        const ReadExtent &ext = dec.ext;
         tick("bam decode");
         if (ext.n_reads == 0) { std::cerr << "juliet: no primary or supplementary alignments in " << opt.bam << "\n"; return 2; }
-        int64_t ref_len = std::numeric_limits<int64_t>::max();
-        if (ext.ref_id >= 0 && (size_t)ext.ref_id < bam_refs.size()) ref_len = bam_refs[(size_t)ext.ref_id].length;
 
-        const bool have_cfg = !cfg.genes.empty();
-        if (!have_cfg) {
-            // no target config: one ORF over the covered window, labelled "unknown" (doc/JULIET.md:182-188);
-            // --region marks the reading frame
-            GeneCfg g;
-            g.name = "unknown";
-            g.begin = g.begin_eff = opt.have_region ? opt.region_b : (uint32_t)ext.min_pos + 1;
-            g.end = g.end_eff = opt.have_region ? opt.region_e : (uint32_t)ext.max_end + 1;
-            cfg.genes.push_back(g);
-        } else if (opt.have_region) {
-            cfg.apply_region(opt.region_b, opt.region_e);
-            if (cfg.genes.empty()) { std::cerr << "juliet: --region leaves no gene of the config\n"; return 1; }
-        }
-        // window: the called genes plus the -3..+5 context columns (doc/JULIET.md:99-100), inside the reference
-        int64_t gb = std::numeric_limits<int64_t>::max(), ge = 0;
-        for (const GeneCfg &g : cfg.genes) { gb = std::min<int64_t>(gb, (int64_t)g.begin_eff - 1); ge = std::max<int64_t>(ge, (int64_t)g.end_eff - 1); }
-        const int64_t wb = std::max<int64_t>(0, gb - 3);
-        const int64_t we = std::max<int64_t>(wb + 1, std::min<int64_t>(ref_len, ge + 5));
-        const uint32_t win_begin = (uint32_t)wb, n_cols = (uint32_t)(we - wb);
+        SampleSetup smp;
+        if (sample_window(opt, cfg, dec, smp)) return 1;
+        const uint32_t win_begin = smp.win_begin, n_cols = smp.n_cols;
 
         std::vector<std::string> names;
         uint64_t n_reads = 0;
@@ -821,30 +1538,9 @@ int main(int argc, char **argv)
         n_reads = ext.n_reads;
 
         // ---------------------------------------------------------------- parameters
-        std::string chem = opt.chemistry;
-        if (chem == "auto") {
-            // chemistry-keyed rates with a permissive fallback (doc/JULIET.md:221-225); the key here is the
-            // platform model in the @RG line
-            chem = (header_text.find("SEQUEL") != std::string::npos || header_text.find("S/P") != std::string::npos) ? "sequel" : "permissive";
-            if (chem == "permissive") std::cerr << "juliet: chemistry not recognised, permissive mode is active (doc/JULIET.md:221-225)\n";
-        }
-        jl_params prm;
-        prm.alpha = opt.alpha;
-        prm.n_tests = opt.n_tests;
-        if (chem == "sequel") prm.err = {0.998826, 5.8e-5, 1.0e-3};
-        else prm.err = {0.99764, 1.2e-4, 2.0e-3};
-        if (opt.match > 0) prm.err.match = opt.match;
-        if (opt.substitution >= 0) prm.err.substitution = opt.substitution;
-        prm.expected_round = opt.expected_round;
-        prm.tail = opt.fisher_tail;
-        prm.min_perc = opt.min_perc;
-        prm.max_perc = opt.max_perc;
-
-        std::vector<jl_gene> genes;
-        for (const GeneCfg &g : cfg.genes) genes.push_back({g.begin_eff, g.end_eff});
-        std::vector<uint8_t> refcodes;
-        if (!cfg.reference_sequence.empty())
-            for (char ch : cfg.reference_sequence) refcodes.push_back(base_code(ch));
+        sample_params(opt, dec, smp);
+        const std::vector<jl_gene> &genes = smp.genes;
+        const std::vector<uint8_t> &refcodes = smp.refcodes;
 
         // ---------------------------------------------------------------- device
         jl_ctx *ctx = nullptr;
@@ -861,10 +1557,10 @@ int main(int argc, char **argv)
         if (opt.timing)
             fprintf(stderr, "juliet: timing   uploader thread: gather %.1f ms, begin %.1f ms, %u appends %.1f ms (longest %.1f), names %.1f ms\n",
                     uploader->ms_gather, uploader->ms_begin, uploader->n_appends, uploader->ms_append, uploader->ms_append_max, uploader->ms_names);
-        const uint8_t *refp = refcodes.empty() ? nullptr : refcodes.data();
+        const uint8_t *refp = smp.refp();
         Results R;
         R.col_counts.assign((size_t)n_cols * 6, 0);
-        DeviceStageInput in{&opt, &cfg, &genes, &refcodes, prm, win_begin, n_cols, n_reads};
+        DeviceStageInput in{&opt, &smp.cfg, &genes, &refcodes, smp.prm, win_begin, n_cols, n_reads};
         const size_t n_ranks = opt.devices.size();
         if (opt.windows > 1 || n_ranks > 1) {
             // ---- K column windows over R devices (doc/JULIET.md:261-264: each gene is treated separately, so the split
@@ -952,18 +1648,12 @@ int main(int argc, char **argv)
         if (opt.drm_only && drm_masks_of(ctx, in, drm_masks)) die_jl(ctx, "pileup");
         if (opt.fuse_only) {   // the column pileup is all a consensus needs
             if (jl_pileup_async(ctx, genes.data(), (uint32_t)genes.size(), refp, (uint32_t)refcodes.size()) != JL_OK) die_jl(ctx, "pileup");
-        } else if (jl_run_async(ctx, genes.data(), (uint32_t)genes.size(), refp, (uint32_t)refcodes.size(), &prm,
+        } else if (jl_run_async(ctx, genes.data(), (uint32_t)genes.size(), refp, (uint32_t)refcodes.size(), &smp.prm,
                                 opt.drm_only ? drm_masks.data() : nullptr, opt.phasing, opt.min_reads, opt.phasing) != JL_OK)
             die_jl(ctx, "run");
         tick("plan + enqueue");
 
-        R.var.resize(4096);
-        uint32_t nv = 0;
-        if (!opt.fuse_only && jl_call_fetch(ctx, R.var.data(), 4096, &nv) != JL_OK) die_jl(ctx, "call fetch");
-        R.var.resize(nv);
-        tick("  wait for the run + table");
-        if (jl_pileup_fetch(ctx, R.col_counts.data(), nullptr, nullptr, nullptr, nullptr, nullptr) != JL_OK) die_jl(ctx, "pileup fetch");
-        tick("  column counts");
+        if (const char *what = fetch_calls(ctx, !opt.fuse_only, R, tick)) die_jl(ctx, what);
 
         if (!opt.consensus.empty()) {  // what `fuse` writes for this window (doc/FUSE.md:17-24)
             std::vector<uint32_t> len_hist((size_t)n_cols * 32), base_counts((size_t)n_cols * 120);
@@ -979,181 +1669,16 @@ int main(int argc, char **argv)
             jl_ctx_destroy(ctx);
             return 0;
         }
-        const uint32_t cap_var = std::max<uint32_t>(1, nv);
-        if (opt.phasing) {
-            R.pos_cols.resize(cap_var);
-            R.hap_count.resize(JL_MAX_HAPLOTYPES);
-            R.hap_pattern.resize((size_t)JL_MAX_HAPLOTYPES * cap_var);
-            R.hit.resize((size_t)cap_var * JL_MAX_HAPLOTYPES);
-            R.read_hap.resize(n_reads);
-            R.pat_stride = cap_var;
-            R.hit_stride = JL_MAX_HAPLOTYPES;
-            if (jl_phase_fetch(ctx, &R.ps, R.pos_cols.data(), R.hap_count.data(), R.hap_pattern.data(), R.hit.data(), R.read_hap.data(), nullptr, cap_var) != JL_OK)
-                die_jl(ctx, "phase fetch");
-        }
+        if (opt.phasing)
+            if (const char *what = fetch_phase(ctx, n_reads, R)) die_jl(ctx, what);
         tick("  haplotypes + ids");
         // (the context is not torn down: the process is about to end, and freeing two dozen device buffers one by one took
         // 4-6 ms of a 0.1 s run)
         }
-        const std::vector<jl_variant> &var = R.var;
-        const std::vector<uint32_t> &col_counts = R.col_counts;
-        const jl_phase_summary &ps = R.ps;
-        const std::vector<uint32_t> &pos_cols = R.pos_cols, &hap_count = R.hap_count;
-        const std::vector<uint8_t> &hap_pattern = R.hap_pattern, &hit = R.hit;
-        const std::vector<uint16_t> &read_hap = R.read_hap;
-
-        // ---------------------------------------------------------------- JSON (doc/JULIET.md:61-107, 207-211)
-        Json root = Json::object();
-        root.set("input", Json::object()
-                              .set("timestamp", Json::of(iso_now()))
-                              .set("input_file", Json::of(opt.bam))
-                              .set("command_line", Json::of(cmdline))
-                              .set("juliet_version", Json::of(kVersion)));
-        Json tc = cfg.echo();
-        tc.set("n_reads", Json::of((int64_t)n_reads));
-        tc.set("window_begin", Json::of(win_begin + 1)).set("window_end", Json::of(win_begin + n_cols + 1));
-        tc.set("chemistry_model", Json::of(chem));
-        root.set("target_config", tc);
-
-        Json genes_json = Json::array();
-        const uint32_t H = ps.n_haplotypes;
-        for (size_t g = 0; g < cfg.genes.size(); ++g) {
-            Json gj = Json::object();
-            gj.set("name", Json::of(cfg.genes[g].name));
-            Json vps = Json::array();
-            size_t v = 0;
-            while (v < var.size()) {
-                if (var[v].gene != g) { ++v; continue; }
-                size_t e = v;
-                while (e < var.size() && var[e].gene == g && var[e].codon_pos == var[v].codon_pos) ++e;
-                const jl_variant &f = var[v];
-                Json vp = Json::object();
-                vp.set("ref_codon", Json::of(codon_string(f.ref_codon)));
-                vp.set("ref_amino_acid", Json::of(std::string(1, translate(f.ref_codon))));
-                const uint32_t aa_pos = f.codon_pos + cfg.genes[g].first_codon;
-                vp.set("ref_position", Json::of(aa_pos));
-                vp.set("coverage", Json::of(f.coverage));
-                // variant codons grouped by amino acid (position 223 with two rows)
-                Json aas = Json::array();
-                std::vector<char> order;
-                for (size_t k = v; k < e; ++k) {
-                    const char aa = translate(var[k].codon);
-                    if (std::find(order.begin(), order.end(), aa) == order.end()) order.push_back(aa);
-                }
-                // amino acids in alphabetical order: juliet_abl-nohaplotype.png prints "A GCC" above "P CCA" at ABL1 223
-                std::sort(order.begin(), order.end());
-                for (char aa : order) {
-                    Json aj = Json::object();
-                    aj.set("amino_acid", Json::of(std::string(1, aa)));
-                    Json cods = Json::array();
-                    for (size_t k = v; k < e; ++k) {
-                        if (translate(var[k].codon) != aa) continue;
-                        Json cj = Json::object();
-                        cj.set("codon", Json::of(codon_string(var[k].codon)));
-                        cj.set("frequency", Json::of((double)var[k].count / (double)var[k].coverage));
-                        cj.set("count", Json::of(var[k].count));
-                        cj.set("expected", Json::of(var[k].expected));
-                        cj.set("pValue", Json::of(var[k].p_value));
-                        cj.set("log_pValue", Json::of(var[k].log_p));
-                        cj.set("known_drm", Json::of(cfg.known_drms(g, aa_pos, aa)));
-                        if (opt.phasing) {
-                            Json hh = Json::array();
-                            for (uint32_t h = 0; h < H; ++h) hh.push(Json::of(hit[(size_t)k * R.hit_stride + h] != 0));
-                            cj.set("haplotype_hit", hh);  // doc/JULIET.md:207-209
-                        }
-                        cods.push(cj);
-                    }
-                    aj.set("variant_codons", cods);
-                    aas.push(aj);
-                }
-                vp.set("variant_amino_acids", aas);
-                // MSA context: -3 .. +5 around the codon's first base (doc/JULIET.md:99-100)
-                Json msa = Json::array();
-                for (int rel = -3; rel <= 5; ++rel) {
-                    const int64_t c = (int64_t)f.col + rel;
-                    if (c < 0 || c >= (int64_t)n_cols) continue;
-                    const uint32_t *cc = &col_counts[(size_t)c * 6];
-                    Json mj = Json::object();
-                    mj.set("rel_pos", Json::of((int64_t)rel)).set("abs_pos", Json::of((int64_t)(win_begin + c + 1)));
-                    static const char *sym[6] = {"A", "C", "G", "T", "-", "N"};
-                    for (int s = 0; s < 6; ++s) mj.set(sym[s], Json::of(cc[s]));
-                    const size_t r = (size_t)win_begin + (size_t)c;
-                    if (r < cfg.reference_sequence.size()) mj.set("wt", Json::of(std::string(1, (char)std::toupper((unsigned char)cfg.reference_sequence[r]))));
-                    msa.push(mj);
-                }
-                vp.set("msa", msa);
-                vps.push(vp);
-                v = e;
-            }
-            gj.set("variant_positions", vps);
-            genes_json.push(gj);
-        }
-        root.set("genes", genes_json);
-
-        // Section 4, drug summaries: variants grouped by annotated drug (doc/JULIET.md:104-107)
-        {
-            std::vector<std::pair<std::string, Json>> by_drug;
-            for (const jl_variant &f : var) {
-                const GeneCfg &g = cfg.genes[f.gene];
-                const uint32_t aa_pos = f.codon_pos + g.first_codon;
-                const char aa = translate(f.codon);
-                for (const Drm &d : g.drms) {
-                    bool hit_drm = false;
-                    for (const DrmPosition &dp : d.positions) hit_drm = hit_drm || dp.matches(aa_pos, aa);
-                    if (!hit_drm) continue;
-                    Json e = Json::object();
-                    e.set("gene", Json::of(g.name));
-                    e.set("mutation", Json::of(std::string(1, translate(f.ref_codon)) + std::to_string(aa_pos) + std::string(1, aa)));
-                    e.set("codon", Json::of(codon_string(f.codon)));
-                    e.set("frequency", Json::of((double)f.count / (double)f.coverage));
-                    auto it = std::find_if(by_drug.begin(), by_drug.end(), [&](const std::pair<std::string, Json> &kv) { return kv.first == d.name; });
-                    if (it == by_drug.end()) { by_drug.emplace_back(d.name, Json::array()); it = by_drug.end() - 1; }
-                    it->second.push(e);
-                }
-            }
-            Json ds = Json::array();
-            for (auto &kv : by_drug) ds.push(Json::object().set("drug", Json::of(kv.first)).set("variants", kv.second));
-            root.set("drug_summaries", ds);
-        }
-
-        if (opt.phasing) {  // root `haplotype` block: counts and read names, same order as haplotype_hit (doc/JULIET.md:209-211)
-            Json hb = Json::object();
-            hb.set("reported_reads", Json::of(ps.reported_reads)).set("insufficient_coverage_reads", Json::of(ps.insufficient_reads));
-            hb.set("damaged_reads", Json::of(ps.damaged_reads)).set("marginal_gaps", Json::of(ps.marginal_gap));
-            hb.set("marginal_heteroduplexes", Json::of(ps.marginal_heteroduplex)).set("marginal_partial", Json::of(ps.marginal_partial));
-            std::vector<std::vector<uint32_t>> members(H);
-            for (uint64_t i = 0; i < n_reads; ++i)
-                if (read_hap[i] < H) members[read_hap[i]].push_back((uint32_t)i);
-            Json hs = Json::array();
-            for (uint32_t h = 0; h < H; ++h) {
-                Json hj = Json::object();
-                hj.set("name", Json::of(haplotype_name(h))).set("reads", Json::of(hap_count[h]));
-                hj.set("frequency", Json::of(ps.reported_reads ? (double)hap_count[h] / (double)ps.reported_reads : 0.0));
-                Json cods = Json::array();
-                for (uint32_t p = 0; p < ps.n_positions; ++p) cods.push(Json::of(codon_string(hap_pattern[(size_t)h * R.pat_stride + p])));
-                hj.set("codons", std::move(cods));
-                Json rn = Json::array();      // (moved on, level by level: a copy of this list per level was most of the stage at a million reads)
-                rn.arr.reserve(members[h].size());
-                for (uint32_t i : members[h]) rn.push(Json::of(names[i]));
-                hj.set("read_names", std::move(rn));
-                hs.push(std::move(hj));
-            }
-            hb.set("haplotypes", std::move(hs));
-            Json pc = Json::array();
-            for (uint32_t p = 0; p < ps.n_positions; ++p) pc.push(Json::of(win_begin + pos_cols[p] + 1));
-            hb.set("variant_positions_abs", std::move(pc));
-            root.set("haplotype", std::move(hb));
-        }
-
-        std::string text;
-        root.write(text);
-        text += "\n";
-        for (const std::string &out : opt.outputs) {
-            std::ofstream f(out);
-            if (!f) { std::cerr << "juliet: cannot write " << out << "\n"; return 2; }
-            if (out.substr(out.size() - 5) == ".json") f << text;
-            else f << render_html(root);
-        }
+        // ---------------------------------------------------------------- JSON / HTML (doc/JULIET.md:61-107, 207-211)
+        const Json root = build_json(opt, smp, opt.bam, cmdline, names, n_reads, R);
+        const std::string failed = write_outputs(opt.outputs, root);
+        if (!failed.empty()) { std::cerr << "juliet: cannot write " << failed << "\n"; return 2; }
         tick("json / html");
         // Everything is written and closed.  What a `return` would still do — free a gigabyte of record arrays page by page, take down
         // the uploader and the decode pool, destroy the GPU contexts and the HIP runtime's own state — the operating system does at
