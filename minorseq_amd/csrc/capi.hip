@@ -12,13 +12,6 @@
 
 #include "jl_internal.h"
 
-// 1: a small window's last launch stores the completion word itself (every workgroup that wrote host memory releases
-// it at system scope first); 0: always a one-thread node of its own behind the last stage.  Measured equal on one
-// window alone (74.1 vs 74.4 us) and no faster in the pipelined loop: the node of its own is the default.
-#ifndef JL_SIGNAL_IN_KERNEL
-#define JL_SIGNAL_IN_KERNEL 0
-#endif
-
 static thread_local std::string g_create_error;
 
 // (The library does not touch the process environment.  A host that keeps several launches in flight beside an exchange
@@ -79,43 +72,22 @@ int jl_device_count(void)
 
 const char *jl_last_error(const jl_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
-#ifdef JL_TUNING
-// JL_CTX_TIMES=1: where jl_ctx_create spends its time (tools_tuning/ctx_create_cost.py)
-#define JL_CTX_MARK(what)                                                                                              \
-    do {                                                                                                               \
-        if (ctx_times) {                                                                                               \
-            const auto now_ = std::chrono::steady_clock::now();                                                        \
-            fprintf(stderr, "  jl_ctx_create: %-28s %7.2f ms\n", what, std::chrono::duration<double, std::milli>(now_ - mark_).count()); \
-            mark_ = now_;                                                                                              \
-        }                                                                                                              \
-    } while (0)
-#else
-#define JL_CTX_MARK(what) do { } while (0)
-#endif
-
 int jl_ctx_create(int device, void *stream, jl_ctx **out)
 {
     if (!out) return JL_ERR_ARG;
     *out = nullptr;
-#ifdef JL_TUNING
-    const bool ctx_times = getenv("JL_CTX_TIMES") != nullptr;
-    auto mark_ = std::chrono::steady_clock::now();
-#endif
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
         return jl_fail(nullptr, JL_ERR_DEVICE, "no HIP device visible; this library has no CPU fallback");
     if (device < 0 || device >= n) return jl_fail(nullptr, JL_ERR_ARG, "device %d out of range (%d visible)", device, n);
-    JL_CTX_MARK("hipGetDeviceCount");
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) != hipSuccess) return jl_fail(nullptr, JL_ERR_DEVICE, "hipGetDeviceProperties failed");
-    JL_CTX_MARK("hipGetDeviceProperties");
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return jl_fail(nullptr, JL_ERR_DEVICE, "device %d is %s; kernels are built for gfx950 only", device, prop.gcnArchName);
     jl_ctx *ctx = new (std::nothrow) jl_ctx();
     if (!ctx) return JL_ERR_MEMORY;
     ctx->device = device;
     if (hipSetDevice(device) != hipSuccess) { delete ctx; return jl_fail(nullptr, JL_ERR_DEVICE, "hipSetDevice failed"); }
-    JL_CTX_MARK("hipSetDevice");
     if (stream) {
         ctx->stream = (hipStream_t)stream;
     } else {
@@ -125,10 +97,8 @@ int jl_ctx_create(int device, void *stream, jl_ctx **out)
         }
         ctx->own_stream = true;
     }
-    JL_CTX_MARK("stream");
     hipEventCreate(&ctx->ev0);
     hipEventCreate(&ctx->ev1);
-    JL_CTX_MARK("two events");
 
     bool ok = hipMalloc(&ctx->d_variants, sizeof(jl_variant) * JL_VARIANT_CAP) == hipSuccess &&
               hipMalloc(&ctx->d_nvar, 2 * sizeof(uint32_t)) == hipSuccess &&
@@ -140,18 +110,15 @@ int jl_ctx_create(int device, void *stream, jl_ctx **out)
               hipMalloc(&ctx->d_cooc, sizeof(uint32_t) * ctx->cooc_cap * ctx->cooc_cap) == hipSuccess &&
               hipMalloc(&ctx->d_pack, 2 * sizeof(jl_pack)) == hipSuccess &&
               hipMalloc(&ctx->d_sync, 16 * sizeof(uint32_t)) == hipSuccess;
-    JL_CTX_MARK("ten hipMalloc");
     ok = ok && hipHostMalloc(&ctx->h_pack, sizeof(jl_pack), hipHostMallocDefault) == hipSuccess &&
               hipHostMalloc((void **)&ctx->h_seq, 64, hipHostMallocDefault) == hipSuccess &&
               hipHostMalloc(&ctx->h_scratch, (size_t)1 << 20, hipHostMallocDefault) == hipSuccess;
-    JL_CTX_MARK("three hipHostMalloc");
     if (ok) ctx->h_scratch_cap = (size_t)1 << 20;
     if (!ok) { jl_ctx_destroy(ctx); return jl_fail(nullptr, JL_ERR_MEMORY, "context allocation failed"); }
     hipMemsetAsync(ctx->d_nvar, 0, 2 * sizeof(uint32_t), ctx->stream);
     hipMemsetAsync(ctx->d_meta, 0, sizeof(jl_phase_meta), ctx->stream);
     hipMemsetAsync(ctx->d_sync, 0, 16 * sizeof(uint32_t), ctx->stream);
     for (int k = 0; k < 16; ++k) ctx->h_seq[k] = 0;
-    JL_CTX_MARK("three hipMemsetAsync");
     *out = ctx;
     return JL_OK;
 }
@@ -186,7 +153,7 @@ void jl_ctx_destroy(jl_ctx *ctx)
                     ctx->d_counts, ctx->d_called, ctx->d_staged, ctx->d_drm, ctx->d_variants, ctx->d_nvar, ctx->d_meta, ctx->d_vpcols,
                     ctx->d_col2pos, ctx->d_varcol, ctx->d_keys, ctx->d_flagw, ctx->d_read_slot, ctx->d_read_hap,
                     ctx->d_slot_rep, ctx->d_slot_count, ctx->d_slot_key, ctx->d_slot_hap, ctx->d_occupied, ctx->d_hap_count,
-                    ctx->d_hap_pattern, ctx->d_hit, ctx->d_cooc, ctx->d_pack, ctx->d_sync, ctx->d_timeline,
+                    ctx->d_hap_pattern, ctx->d_hit, ctx->d_cooc, ctx->d_pack, ctx->d_sync,
                     ctx->d_ins_len, ctx->d_ins_base, ctx->d_ing_runs, ctx->d_ing_nruns, ctx->d_ing_desc, ctx->d_ing_count, ctx->d_ing_slow,
                     ctx->d_exp_count,
                     ctx->d_exp_pattern, ctx->d_exp_hap, ctx->d_blockcat, ctx->d_slot_key_a, ctx->d_slot_key_b, ctx->d_occ_a, ctx->d_occ_b};
@@ -393,19 +360,21 @@ int jl_records_append(jl_ctx *ctx, uint64_t n_reads, const int32_t *pos, const u
     const uint64_t first = R.n_reads;
     // a chunk that fails validation ends the stream (jl_records_begin starts over).  Here: the offsets, which the uploads
     // below follow; what the cigars say — an 'M', more bases than the record holds — is checked where they are walked, on
-    // the device (cigar_runs_kernel), and reported by the build (jl_records_finish / jl_records_window): the loop over
-    // twelve million cigar words was most of an append on the host.
+    // the device (cigar_walk_kernel, cigar_runs_kernel for long reads), and reported by the build (jl_records_finish /
+    // jl_records_window): the loop over twelve million cigar words was most of an append on the host.
     auto bad = [&](uint64_t r, const char *what, uint64_t v) {
         records_drop(ctx);
         return jl_fail(ctx, JL_ERR_ARG, what, (unsigned long long)(first + r), (unsigned long long)v);
     };
+    for (uint64_t r = 0; r < n_reads; ++r)
+        if (cig_off[r + 1] < cig_off[r] || seq_off[r + 1] < seq_off[r] || (qual && qual_off[r + 1] < qual_off[r]))
+            return bad(r, "record %llu: offsets must not decrease", 0);
     // ... and whether a read needs the ingest's launch for long reads: only a read with more ops than entries fit can, and a CCS
-    // sample has few of those — their cigars are looked at here, a word per read of the chunk at most (then: "maybe")
+    // sample has few of those — their cigars are looked at here, a word per read of the chunk at most (then: "maybe").  Only
+    // behind the check of EVERY offset: then each read's cigar lies within [cig_off[0], cig_off[n_reads]), the caller's array.
     const uint64_t short_ops = jl_ingest_short_ops();
     uint64_t looked = 0;
     for (uint64_t r = 0; r < n_reads; ++r) {
-        if (cig_off[r + 1] < cig_off[r] || seq_off[r + 1] < seq_off[r] || (qual && qual_off[r + 1] < qual_off[r]))
-            return bad(r, "record %llu: offsets must not decrease", 0);
         const uint64_t n_ops = cig_off[r + 1] - cig_off[r];
         if (n_ops > short_ops && !R.maybe_long) {
             looked += n_ops;
@@ -482,37 +451,6 @@ int jl_ingest_verdict(jl_ctx *ctx)
     ctx->ing_check_pending = false;
     // (through the context's pinned block: a process's first pageable device-to-host copy costs the runtime milliseconds)
     unsigned long long both[2] = {0, ~0ull};     // (the counters, the verdict: kernels_ingest.hip jl_launch_ingest)
-#ifdef JL_TUNING
-    {   // the address checks of the tuning build's ingest kernels (kernels_ingest.hip JL_ING_CHECK)
-        uint32_t w[16] = {0};
-        if (int rc = jl_fetch_to_host(ctx, ctx->d_ing_count, 64, w, 64)) return rc;
-        for (int c = 1; c < 5; ++c)
-            if (w[4 + c]) fprintf(stderr, "ingest check %d failed %u times (a value: %u)\n", c, w[4 + c], w[9 + c]);
-        if (getenv("JL_ING_STAMPS") && ctx->d_ing_slow) {   // phase stamps of the sampled workgroups (kernels_ingest.hip JL_ING_STAMP)
-            std::vector<unsigned long long> t(160 * 4 * 12);
-            hipMemcpy(t.data(), ctx->d_ing_slow, t.size() * 8, hipMemcpyDeviceToHost);
-            double sum[4][12] = {{0}};
-            int n = 0;
-            for (int g = 0; g < 160; ++g) {
-                const unsigned long long *q = &t[(size_t)g * 48];
-                if (!q[0] || !q[10]) continue;
-                ++n;
-                for (int wv = 0; wv < 4; ++wv)
-                    for (int k = 1; k <= 10; ++k)
-                        if (q[wv * 12 + k] && q[wv * 12 + k - 1]) sum[wv][k] += 0.01 * (double)(q[wv * 12 + k] - q[wv * 12 + k - 1]);
-                        else if (q[wv * 12 + k] && k >= 2 && q[wv * 12 + k - 2]) sum[wv][k] += 0.01 * (double)(q[wv * 12 + k] - q[wv * 12 + k - 2]);
-            }
-            if (n) {
-                fprintf(stderr, "ingest stamps, %d workgroups, us per step (desc, prologue, barrier, fetch+fill, pieces, stage, barrier, general, barrier, transpose):\n", n);
-                for (int wv = 0; wv < 4; ++wv) {
-                    fprintf(stderr, "  wave %d:", wv);
-                    for (int k = 1; k <= 10; ++k) fprintf(stderr, " %6.2f", sum[wv][k] / n);
-                    fprintf(stderr, "\n");
-                }
-            }
-        }
-    }
-#endif
     if (int rc = jl_fetch_to_host(ctx, ctx->d_ing_count, 16, both, 64)) return rc;
     const unsigned long long w = both[1];
     if (w == ~0ull) return JL_OK;
@@ -580,7 +518,7 @@ static int records_build(jl_ctx *src, jl_ctx *dst, uint32_t n_cols, uint32_t win
     if (e == hipSuccess) {
         jl_launch_ingest(dst, R.d_pos, R.d_cig, R.d_co, R.d_seq, R.d_so, R.have_qual ? R.d_qual : nullptr,
                          R.have_qual ? R.d_qo : nullptr, min_qv, dst->d_ing_runs, dst->d_ing_nruns, dst->d_ing_desc, dst->d_ing_count,
-                         dst->d_ing_slow, R.maybe_long, R.n_seq, R.n_cig + 3 * nr + 8);
+                         dst->d_ing_slow, R.maybe_long);
         e = hipGetLastError();
         dst->ing_check_pending = e == hipSuccess;
         if (e == hipSuccess && wait) e = hipStreamSynchronize(st);
@@ -758,10 +696,6 @@ static void build_chunks(jl_ctx *ctx, const std::vector<uint8_t> &colflag, std::
     for (uint32_t c = 0; c + 2 < L; ++c)
         if ((colflag[c] & 1) && ((colflag[c + 1] & 1) || (colflag[c + 2] & 1))) ++crowded;
     uint32_t W = (total && crowded * 4 > total) ? 6u : 3u;
-#ifdef JL_TUNING
-    if (const char *env_w = getenv("JL_PILEUP_W"))
-        if (*env_w) W = (uint32_t)atoi(env_w) % 100u;
-#endif
     if (W != 3 && W != 6) W = 3;   // the kernels exist for these two widths
     (void)major;
     ctx->pileup_w = W;
@@ -1464,7 +1398,6 @@ static void enqueue_path(jl_ctx *ctx, const jl_params *prm, double n_tests, bool
     (void)want_read_hap;   // no copy nodes: results are stored straight into pinned host memory (ctx->pack_mirror / read_hap_out)
     if (jl_pileup_needs_zero(ctx)) hipMemsetAsync(ctx->d_counts, 0, ctx->counts_words * sizeof(uint32_t), st);
     if (!ctx->have_ref) jl_launch_guess(ctx, st);
-    jl_launch_stamp(ctx, 0);
     if (ctx->pileup_clock) jl_launch_clock(ctx, st, 0);
     if (jl_pileup_can_fold(ctx)) {
         // every chunk is counted by ONE workgroup: it tests its codon from the histogram still in LDS (kernels_pileup.hip) —
@@ -1478,7 +1411,6 @@ static void enqueue_path(jl_ctx *ctx, const jl_params *prm, double n_tests, bool
         if (ctx->pileup_clock) jl_launch_clock(ctx, st, 1);
         jl_launch_call(ctx, st, prm, n_tests, use_drm, phasing);
     }
-    jl_launch_stamp(ctx, 1);
     // The completion word (jl_run_wait) is stored by a one-thread node of its own behind the last stage: the end of
     // that stage's kernel is what pushes the results every compute die wrote for the host out of the dies' L2s.
     bool signaled = false;
@@ -1489,12 +1421,12 @@ static void enqueue_path(jl_ctx *ctx, const jl_params *prm, double n_tests, bool
         signaled = true;
     } else if (ctx->phase_generic) {
         jl_launch_compact(ctx, st, true, false, false);
-        jl_launch_stamp(ctx, 2);
         jl_launch_phase(ctx, st, min_reads, true, false, false);
     } else {
-        signaled = jl_launch_phase(ctx, st, min_reads, true, true, JL_SIGNAL_IN_KERNEL != 0);
+        // (the completion word by a node of its own here too: the fused launch storing it itself measured equal on one window
+        // alone, 74.1 against 74.4 us, and no faster in the pipelined loop)
+        signaled = jl_launch_phase(ctx, st, min_reads, true, true, false);
     }
-    jl_launch_stamp(ctx, 3);
     if (!signaled) jl_launch_done(ctx);
 }
 
@@ -1534,13 +1466,6 @@ int jl_run_prepare(jl_ctx *ctx, const jl_gene *genes, uint32_t n_genes, const ui
             ctx->h_read_hap_cap = (size_t)ctx->col_stride * 2;
         }
     }
-#ifdef JL_TUNING
-    if (!ctx->d_timeline && getenv("JL_TIMELINE")) {   // tuning aid, see stamp_kernel
-        JL_HIP(ctx, hipMalloc(&ctx->d_timeline, (size_t)JL_TIMELINE_ROWS * JL_TIMELINE_SLOTS * 8));
-        JL_HIP(ctx, hipMemset(ctx->d_timeline, 0, (size_t)JL_TIMELINE_ROWS * JL_TIMELINE_SLOTS * 8));
-        ctx->alloc_version++;
-    }
-#endif
     *n_tests_out = prm->n_tests > 0.0 ? prm->n_tests : ctx->default_n_tests;
     ctx->last_min_reads = min_reads;
     jl_prepare_pileup(ctx);
@@ -1576,7 +1501,7 @@ int jl_run_async(jl_ctx *ctx, const jl_gene *genes, uint32_t n_genes, const uint
     memset(&sig, 0, sizeof sig);
     sig.alloc = ctx->alloc_version; sig.plan = ctx->plan_version; sig.prm = *prm; sig.n_tests = n_tests;
     sig.drm = drm_masks != nullptr; sig.phasing = phasing != 0; sig.min_reads = min_reads; sig.rh = want_read_hap != 0; sig.generic = (ctx->phase_generic ? 1u : 0u) | (ctx->phase_two ? 2u : 0u); sig.pad = (uint32_t)(uintptr_t)ctx->read_hap_out;
-    static const bool graphs_on = !getenv("JL_NO_GRAPH");   // read once; eager launches are a debugging aid
+    const bool graphs_on = !jl_env().no_graph;   // (eager launches are a debugging aid)
     bool launched = false;
     // A graph replay reaches the queue 10-16 us after the call, a plain launch 3-5 us (MI355X guide, graph-replay-floor);
     // the remaining launches of an eager run are enqueued while the first kernel runs.  For a window whose counting
@@ -1701,19 +1626,6 @@ int jl_run_wait_seq_quiet(jl_ctx *ctx, uint32_t want, hipStream_t stream)
 }
 
 extern "C" {
-
-#ifdef JL_TUNING
-// tuning aid, not part of the ABI header (tools_tuning/timeline.py): the device-clock stamps of the last
-// JL_TIMELINE_ROWS runs of this context (JL_TIMELINE=1), 100 MHz ticks
-__attribute__((visibility("default"))) int jl_debug_timeline(jl_ctx *ctx, uint64_t *out)
-{
-    if (!ctx || !out) return JL_ERR_ARG;
-    if (!ctx->d_timeline) return jl_fail(ctx, JL_ERR_STATE, "run with JL_TIMELINE=1");
-    JL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    JL_HIP(ctx, hipMemcpy(out, ctx->d_timeline, (size_t)JL_TIMELINE_ROWS * JL_TIMELINE_SLOTS * 8, hipMemcpyDeviceToHost));
-    return JL_OK;
-}
-#endif
 
 int jl_run_wait(jl_ctx *ctx)
 {

@@ -335,10 +335,9 @@ void jl_comm_direct_wait_begin(jl_comm *c)
 int jl_comm_host_gather(jl_comm *c)
 {
     if (c->host_gather >= 0) return c->host_gather;
-    static const char *forced = getenv("JL_EXCHANGE_STAGED");   // tuning / tests: take the staged form
     const size_t kPart = 64;
     uint8_t *t = nullptr;
-    bool ok = !(forced && forced[0] == '1') && hipHostMalloc(&t, kPart * (size_t)c->world, hipHostMallocDefault) == hipSuccess;
+    bool ok = !jl_env().exchange_staged && hipHostMalloc(&t, kPart * (size_t)c->world, hipHostMallocDefault) == hipSuccess;
     jl_comm_direct_wait_begin(c);
     if (ok) {
         memset(t, 0, kPart * (size_t)c->world);

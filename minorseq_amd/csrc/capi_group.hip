@@ -319,7 +319,7 @@ int jl_group_run_masked_async(jl_group *g, const jl_gene *genes, uint32_t n_gene
         g->h_phase[k].S.xhead = xh;
         g->h_compact[k].xhead = xh;
     }
-    static const bool graphs_on = !getenv("JL_NO_GRAPH");
+    const bool graphs_on = !jl_env().no_graph;
     if (graphs_on && !g->graph_exec[par] && !g->graph_tried[par]) {
         g->graph_tried[par] = true;
         if (hipStreamBeginCapture(g->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {

@@ -10,12 +10,17 @@
 #include "../../include/juliet_hip.h"
 #include "jl_synth.h"
 
-// Tuning builds (make EXTRA=-DJL_TUNING; -DJL_PILEUP_TUNING implies it) compile in the probes of tools_tuning/:
-// environment switches for launch shapes, device-clock stamps between the stages, wrong-by-design kernel variants.
-// The shipped library has none of them and reads no environment variable on its launch paths.
-#if defined(JL_PILEUP_TUNING) && !defined(JL_TUNING)
-#define JL_TUNING 1
-#endif
+// The environment: the library reads these four switches and no other, each once (jl_env, kernels_util.hip).
+//   JL_NO_FOLD_CALL        the separate call launch instead of the Fisher stage folded into the pileup: A/B of the fold
+//                          (bench.py picks the kernel it times by it)
+//   JL_NO_GRAPH            eager launches, no captured graphs: a debugging aid
+//   JL_EXCHANGE_STAGED=1   the all-gather's staged form (tests/test_gpu_parity.py)
+//   JL_FORCE_FOLD_TIMEOUT  test hook of the -DJL_TUNING build (tools_tuning/build_tuning_lib.sh): a folded phase launch gives up
+//                          waiting at once (test_fold_timeout_is_rerun_unfolded).  JL_TUNING means nothing else.
+struct jl_env_switches {
+    bool no_fold_call, no_graph, exchange_staged, force_fold_timeout;
+};
+const jl_env_switches &jl_env();
 
 #define JL_VARIANT_CAP 4096u      // rows of the resident variant table (all-gather stride)
 #define JL_CAND_CAP 4096u         // haplotype candidates (groups with >= min_reads) the selector can rank
@@ -26,14 +31,9 @@
 #ifndef JL_FOLD_MAX_BLOCKS
 #define JL_FOLD_MAX_BLOCKS 128u
 #endif
-#define JL_TIMELINE_ROWS 4096u
-#define JL_TIMELINE_SLOTS 8u
 #define JL_INS_LEN_BINS 32u        // insertion lengths 0..30 by value, 31 = longer
 #define JL_INS_MAX_BASES 30u       // inserted bases tracked per insertion
 #define JL_GUESS_PAD 32u           // zero bytes after the last column's seed base
-#ifndef JL_INGEST_SWEEP
-#define JL_INGEST_SWEEP 256u        // columns a workgroup of the record ingest expands at a time (kernels_ingest.hip)
-#endif
 
 
 // resolved reference codon per position
@@ -457,7 +457,6 @@ struct jl_ctx {
     hipStream_t run_stream = nullptr;  // where the last run was enqueued (the ctx stream, or a group's)
     bool pileup_clock = false;        // jl_run_pileup_clock: clock nodes around the pileup of a run -> h_seq[8..11] (two 64-bit stamps)
     uint32_t clock_run = 0;           // value of runs_launched of the run those stamps belong to (0: none)
-    uint64_t *d_timeline = nullptr;   // JL_TIMELINE=1 only: [JL_TIMELINE_ROWS][JL_TIMELINE_SLOTS] device clock stamps
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     std::vector<uint8_t> graph_sig;
@@ -519,7 +518,6 @@ void jl_launch_done_on(jl_ctx *ctx, hipStream_t st);
 // on the run's stream; blocks until it is done.  The call stage's results are still resident.
 extern "C" int jl_phase_rerun_unfolded(jl_ctx *ctx);
 void jl_launch_done_group(const jl_done_ent *d_ents, uint32_t n, hipStream_t st);
-void jl_launch_stamp(jl_ctx *ctx, uint32_t slot);
 extern "C" int jl_run_prepare(jl_ctx *ctx, const jl_gene *genes, uint32_t n_genes, const uint8_t *refseq, uint32_t ref_len,
                               const jl_params *prm, const uint64_t *drm_masks, int phasing, uint32_t min_reads,
                               int want_read_hap, double *n_tests_out);
@@ -533,7 +531,7 @@ bool jl_ingest_read_is_long(const uint32_t *cigar, uint64_t n_ops);
 void jl_launch_ingest(jl_ctx *ctx, const int32_t *d_pos, const uint32_t *d_cigar, const uint64_t *d_cig_off,
                       const uint8_t *d_seq4, const uint64_t *d_seq_off, const uint8_t *d_qual,
                       const uint64_t *d_qual_off, uint32_t min_qv, uint2 *d_runs, uint32_t *d_nruns, uint4 *d_desc,
-                      uint32_t *d_slow_count, uint2 *d_slow, bool maybe_long, uint64_t seq_bytes, uint64_t n_entries);
+                      uint32_t *d_slow_count, uint2 *d_slow, bool maybe_long);
 uint32_t jl_ingest_sweeps(uint32_t n_cols);
 size_t jl_ingest_slow_room(const jl_ctx *ctx);
 extern "C" int jl_ingest_verdict(jl_ctx *ctx);

@@ -5,9 +5,9 @@
 // outside a read's span are 'not covered' (code 6).
 //
 // Four launches at most, three for a CCS sample (the upload looks at the cigars of the few reads that could be long ones —
-// jl_ingest_read_is_long — and cigar_runs_kernel is launched only if there may be one; the planes kernel's second size finds nothing
+// jl_ingest_read_is_long — and the long-read launch is made only if there may be one; the planes kernel's second size finds nothing
 // to do on CCS reads); no by-row scratch in HBM:
-//   cigar_walk_kernel   (round 6) a workgroup takes 64 reads.  One thread a read walks its cigar, sixteen ops a step in registers ->
+//   cigar_walk_kernel   every read: a workgroup takes 64 reads.  One thread a read walks its cigar, sixteen ops a step in registers ->
 //                       the read's RUNS in WINDOW columns (stretches of '=' / 'X' merge into one run of aligned bases; D and N are
 //                       runs of their own; I / S / H / P only end a run), 8 bytes each, between a leading 'not covered from column
 //                       0' entry and two trailing ones (the read's end; 'never'), so that every column of the window lies in exactly
@@ -16,8 +16,8 @@
 //                       the sweep needs begins on, how many pieces, the query offset of that piece — everything
 //                       ingest_planes_kernel needs to ask for its input in one round trip.  Reads of more than 192 ops or 37 runs
 //                       are left to
-//   cigar_runs_kernel   a row of sixteen lanes a read, prefix sums over the cigar, 512 entries a read in LDS and what is beyond
-//                       read back from HBM (rounds 4-5: also the first launch, with 64 entries a read).
+//   cigar_runs_kernel   the long-read launch: the reads cigar_walk_kernel left to it, a row of sixteen lanes a read, prefix sums
+//                       over the cigar, 512 entries a read in LDS and what is beyond read back from HBM.
 //   ingest_planes_kernel  a workgroup = 128 reads x one sweep of 256 columns.  One request per read (the descriptor), then
 //                       the entries and the pieces together.  The pieces become nibbles in QUERY order in LDS with plain
 //                       16-byte stores — no run search, no masks.  Meanwhile a thread per read fills a table: for every block
@@ -39,7 +39,6 @@
 //                       and tile, 7 x 10^6 a window — the stores were 34 us of the launch's 111, 70 of 184 with qualities).
 //                       (Rounds 1-3 expanded every read into a by-row matrix in HBM: 870 MB moved for the 316 MB needed;
 //                       round 4 scattered the codes into a by-row LDS tile with masked, shifted XORs: 137 us.)
-#include <stdlib.h>
 
 #include <algorithm>
 
@@ -50,12 +49,9 @@ namespace {
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
 
-constexpr uint32_t kSweep = JL_INGEST_SWEEP;        // columns per workgroup
+constexpr uint32_t kSweep = 256u;                   // columns per workgroup (448-column sweeps: 144 us against 140, round 4)
 constexpr uint32_t kBlocks = kSweep / 8u;           // blocks of 8 columns = dwords of 8 codes
-#ifndef JL_INGEST_TILE
-#define JL_INGEST_TILE 128
-#endif
-constexpr uint32_t kTileReads = JL_INGEST_TILE;     // reads per workgroup
+constexpr uint32_t kTileReads = 128u;               // reads per workgroup (64-read tiles: 182 us against 176, round 5)
 constexpr uint32_t kTileGroups = kTileReads / 32u;  // groups of 32 reads = dwords of a plane the tile writes per column
 constexpr uint32_t kSubTiles = 1024u / kTileReads;  // tiles that share the 128-byte lines of the planes
 constexpr uint32_t kThreads = 2u * kTileReads;      // a thread per read in the prologue, two in the table fill
@@ -81,17 +77,11 @@ __device__ __forceinline__ uint32_t wave_scan(uint32_t v)
 // Entry 0 = {0, nothing}; entries 1 .. n_runs the read's runs, columns clamped to [0, n_cols] (a run that begins before the
 // window begins at column 0 with its query offset moved along); entry n_runs + 1 = the read's end {column, nothing, query
 // length}; entry n_runs + 2 = {kRunMask, nothing}: never reached.  The columns never decrease.
-constexpr uint32_t kRunsReadsPerWave = 4u;   // a wave takes four reads a turn
-// entries of a read kept in LDS for the descriptors: 64 — 8 KB a workgroup — in the launch that takes every read (a CCS read has
-// a dozen), which lists the reads with more; 512 — 64 KB, two workgroups a CU — in the launch that takes those (and reads
-// what is beyond even that back from HBM, a trip an entry: 1 ms instead of 0.12 for 100k reads with 1 % of indels, 236 ops
-// a read, when they all did)
-#ifndef JL_RUNS_LDS_SMALL
-#define JL_RUNS_LDS_SMALL 64u
-#endif
-constexpr uint32_t kRunsLdsLarge = 512u;
-constexpr uint32_t kRunsDeferred = 0xFFFFFFFFu;   // nruns[r] of a read the first launch (cigar_walk_kernel) leaves to the second
-constexpr uint32_t kRunsLongGrid = 1024u;     // workgroups of the second launch at most: its waves take 64 reads at a time, in turns
+// entries of a long read kept in LDS for the descriptors: 512 — 64 KB, two workgroups a CU (what is beyond is read back from HBM,
+// a trip an entry: 1 ms instead of 0.12 for 100k reads with 1 % of indels, 236 ops a read, when they all did)
+constexpr uint32_t kRunsLds = 512u;
+constexpr uint32_t kRunsDeferred = 0xFFFFFFFFu;   // nruns[r] of a read cigar_walk_kernel leaves to the long-read launch
+constexpr uint32_t kRunsLongGrid = 1024u;     // workgroups of the long-read launch at most: its waves take 64 reads at a time, in turns
 constexpr uint32_t kDescSweeps = 15u;       // sweeps a row of sixteen lanes describes per pass (it needs sixteen bounds)
 constexpr uint32_t kDescMax = 255u;         // "more than the planes kernel takes": pieces or entries of a (read, sweep)
 
@@ -109,14 +99,9 @@ constexpr uint32_t kDescMax = 255u;         // "more than the planes kernel take
 // of (read << 8 | code), code 1 'M', 2 bases, 3 qualities, 4 span (5: see cigar_walk_kernel) — and the read is treated as covering nothing, so no later
 // kernel follows its offsets anywhere.  Lengths add up in 64 bits (a step that holds an op of 2^24 bases or more is summed
 // exactly, lane by lane), so no crafted cigar wraps a sum back into range.
-#ifndef JL_RUNS_WAVES
-#define JL_RUNS_WAVES 1
-#endif
-// The first launch takes every read, four a wave, with room for kRunsLdsSmall entries each in LDS; a read with more gets its
-// entries and its count there, but not its descriptors.  The second launch (LONG) takes those reads — it finds them by their
-// counts, sixty-four reads a wave at a time — with room for kRunsLdsLarge.
-template <uint32_t kRunsLds, bool LONG>
-__global__ __launch_bounds__(256, JL_RUNS_WAVES) void cigar_runs_kernel(uint64_t n_reads, const int32_t *__restrict__ pos, const uint32_t *__restrict__ cigar,
+// The long-read launch takes the reads cigar_walk_kernel left to it (nruns[r] = kRunsDeferred): a wave finds them among
+// sixty-four reads at a time and takes them four at a time, with room for kRunsLds entries each in LDS.
+__global__ __launch_bounds__(256) void cigar_runs_kernel(uint64_t n_reads, const int32_t *__restrict__ pos, const uint32_t *__restrict__ cigar,
                                                          const uint64_t *__restrict__ cig_off, const uint64_t *__restrict__ seq_off,
                                                          const uint64_t *__restrict__ qual_off, uint32_t win_begin, uint32_t n_cols,
                                                          uint32_t n_sweeps, uint2 *__restrict__ runs, uint32_t *__restrict__ nruns,
@@ -128,7 +113,7 @@ __global__ __launch_bounds__(256, JL_RUNS_WAVES) void cigar_runs_kernel(uint64_t
     // time over the whole wave, two ops a lane, was 450 wave instructions a read; the scans, the ballots and the bookkeeping
     // per step are now shared by four reads and eight ops a lane.  Several batches of four a wave, the next one's words asked
     // for ahead, measured slower: 63 against 51 us.)
-    __shared__ uint2 s_run_all[4][kRunsReadsPerWave][kRunsLds];
+    __shared__ uint2 s_run_all[4][4][kRunsLds];      // [wave][its four reads]
     const uint32_t wid = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     uint2 (*s_run)[kRunsLds] = s_run_all[wid];
     const uint32_t q = lane >> 4, sl = lane & 15u;
@@ -151,23 +136,19 @@ __global__ __launch_bounds__(256, JL_RUNS_WAVES) void cigar_runs_kernel(uint64_t
         wa = k < n ? *reinterpret_cast<const u32x4a4 *>(cigar + h.cb + k) : z;           // (words past the read's ops are masked where they are used)
         wb = k + 4u < n ? *reinterpret_cast<const u32x4a4 *>(cigar + h.cb + k + 4u) : z;
     };
-    const uint64_t turn = (uint64_t)gridDim.x * 4u * (LONG ? 64u : kRunsReadsPerWave);
-    for (uint64_t i0 = ((uint64_t)blockIdx.x * 4u + wid) * (LONG ? 64u : kRunsReadsPerWave); i0 < n_reads; i0 += turn) {
-    // LONG: which of the sixty-four reads from i0 on are long ones, taken four at a time
-    uint64_t todo = 1;
-    if (LONG) todo = __ballot(i0 + lane < n_reads && nruns[min(i0 + lane, n_reads - 1u)] == kRunsDeferred);   // (left to this launch by cigar_walk_kernel)
+    const uint64_t turn = (uint64_t)gridDim.x * 4u * 64u;
+    for (uint64_t i0 = ((uint64_t)blockIdx.x * 4u + wid) * 64u; i0 < n_reads; i0 += turn) {
+    // which of the sixty-four reads from i0 on are long ones, taken four at a time
+    uint64_t todo = __ballot(i0 + lane < n_reads && nruns[min(i0 + lane, n_reads - 1u)] == kRunsDeferred);   // (left to this launch by cigar_walk_kernel)
     while (todo) {
-    uint64_t r = i0 + q;
-    if (LONG) {
-        uint32_t at[4];
+    uint32_t at[4];
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            at[t] = todo ? (uint32_t)__builtin_ctzll(todo) : 64u;
-            todo &= todo - 1u;
-        }
-        const uint32_t mine = q == 0u ? at[0] : q == 1u ? at[1] : q == 2u ? at[2] : at[3];
-        r = mine < 64u ? i0 + mine : n_reads;
-    } else todo = 0;
+    for (int t = 0; t < 4; ++t) {
+        at[t] = todo ? (uint32_t)__builtin_ctzll(todo) : 64u;
+        todo &= todo - 1u;
+    }
+    const uint32_t mine = q == 0u ? at[0] : q == 1u ? at[1] : q == 2u ? at[2] : at[3];
+    const uint64_t r = mine < 64u ? i0 + mine : n_reads;
     const bool live = r < n_reads;
     const head_t h = ask_head(r);
     u32x4a4 wa_first, wb_first;
@@ -256,12 +237,7 @@ __global__ __launch_bounds__(256, JL_RUNS_WAVES) void cigar_runs_kernel(uint64_t
 #pragma unroll
         for (uint32_t t = 0; t < 8u; ++t) {
             const uint32_t op = w8[t] & 15u, len = k + t < n_ops ? w8[t] >> 4 : 0u;
-#if defined(JL_RUNS_PROBE) && JL_RUNS_PROBE >= 2     // (tuning: ... and without the entries)
-            if (false)
-#else
-            if ((starts >> (2u * t)) & 1u)
-#endif
-            {
+            if ((starts >> (2u * t)) & 1u) {
                 uint32_t bf;
                 const uint32_t w = window_col(ref_at, bf);
                 put(idx, make_uint2(w | (((kinds >> (2u * t)) & 3u) << 30), (uint32_t)q_at + bf));
@@ -292,24 +268,18 @@ __global__ __launch_bounds__(256, JL_RUNS_WAVES) void cigar_runs_kernel(uint64_t
         uint32_t bf;
         end_col = window_col(ref_total, bf);
     }
-    // a read with more entries than the LDS copy holds: for the second launch (its entries are written here all the same)
-    const bool is_long = !LONG && live && n_runs + 3u > kRunsLds;
     if (live && sl < 3u) {
         const uint32_t idx = sl == 0u ? 0u : n_runs + sl;
         const uint2 e = sl == 0u ? make_uint2(3u << 30, 0u) : sl == 1u ? make_uint2(end_col | (3u << 30), (uint32_t)q_total) : make_uint2(kRunMask | (3u << 30), 0u);
         put(idx, e);
         if (sl == 0u) nruns[r] = n_runs;
     }
-#if defined(JL_RUNS_PROBE) && JL_RUNS_PROBE >= 1     // (tuning: the kernel without its descriptors — wrong results by design)
-    if (n_reads) continue;
-#endif
     // ---- the descriptors: a lane per sweep (fifteen sweeps a pass: a sweep needs the bound of the next one too).  Entries
     // beyond the LDS copy are read back from HBM: past this wave's own stores.
-    const uint32_t n_mine = is_long ? 0u : n_runs;
-    uint32_t n_max = n_mine;
+    uint32_t n_max = n_runs;
 #pragma unroll
-    for (int t = 0; t < 4; ++t) n_max = max(n_max, (uint32_t)__builtin_amdgcn_readlane((int)n_mine, 16 * t));
-    if (LONG && n_max + 3u > kRunsLds) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    for (int t = 0; t < 4; ++t) n_max = max(n_max, (uint32_t)__builtin_amdgcn_readlane((int)n_runs, 16 * t));
+    if (n_max + 3u > kRunsLds) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     __builtin_amdgcn_wave_barrier();
     const uint32_t n_ent_all = n_runs + 3u;          // entries of this lane's read
     uint32_t top = 1u;                         // the highest power of two not above the longest list
@@ -328,10 +298,10 @@ __global__ __launch_bounds__(256, JL_RUNS_WAVES) void cigar_runs_kernel(uint64_t
             uint32_t f = 0;
             for (uint32_t step = top; step; step >>= 1) {
                 const uint32_t t = f + step;
-                if (live && !is_long && t <= n_ent_all && (entry(t - 1u).x & kRunMask) <= X_bound) f = t;
+                if (live && t <= n_ent_all && (entry(t - 1u).x & kRunMask) <= X_bound) f = t;
             }
             const uint32_t f_next = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)f, 0x101, 0xF, 0xF, false);   // row_shl:1
-            if (!live || is_long || sl == kDescSweeps || s >= n_sweeps) continue;
+            if (!live || sl == kDescSweeps || s >= n_sweeps) continue;
             const uint32_t Xend = min(n_cols, X + kSweep);
             const uint32_t lo = f - 1u;
             uint32_t n_ent = f_next - f + 2u;
@@ -383,7 +353,7 @@ __global__ __launch_bounds__(256, JL_RUNS_WAVES) void cigar_runs_kernel(uint64_t
         }
     };
     const uint2 *s_mine = s_run[q];
-    if (!LONG || n_max + 3u <= kRunsLds) describe([&](uint32_t i) -> uint2 { return s_mine[i]; });
+    if (n_max + 3u <= kRunsLds) describe([&](uint32_t i) -> uint2 { return s_mine[i]; });
     else
         describe([&](uint32_t i) -> uint2 {
             if (i < kRunsLds) return s_mine[i];
@@ -392,12 +362,11 @@ __global__ __launch_bounds__(256, JL_RUNS_WAVES) void cigar_runs_kernel(uint64_t
         });
     __builtin_amdgcn_wave_barrier();      // (the next four reads write the LDS copy these ones' descriptors were made from)
     }
-    if (!LONG) break;                     // (the first launch has a wave for every four reads)
     }
 }
 
 // ---------------------------------------------------------------------------------------- runs, a thread a read
-// The first launch of a build (round 6; it replaces cigar_runs_kernel<64, false>, which gave a row of sixteen lanes to every read:
+// The first launch of a build (round 6; it replaced a first launch of cigar_runs_kernel, which gave a row of sixteen lanes to every read:
 // 24 x 10^6 wave instructions and 47-50 us for 100k reads of 127 ops, 36 us for the ten ops of a `ccs --richQVs` read — the scans,
 // the LDS copy of the entries and a binary search per sweep done by every row, for lists a dozen entries long).  A workgroup takes
 // 64 reads:
@@ -410,16 +379,13 @@ __global__ __launch_bounds__(256, JL_RUNS_WAVES) void cigar_runs_kernel(uint64_t
 //      first that begins behind its last column.  Then the entries go out.
 // (One thread a read for BOTH passes — a dozen descriptors one after the other — was 25 us for ten ops: a wave is alone on its
 // SIMD then, 1563 waves for 1024 SIMDs, and the length of the dependent chain is all that counts.)
-// A read with more than kWalkOps ops or more than kWalkEnt entries is left, whole, to the launch with a row of lanes a read:
+// A read with more than kWalkOps ops or more than kWalkEnt entries is left, whole, to the long-read launch (cigar_runs_kernel):
 // nruns[r] = kRunsDeferred.
 constexpr uint32_t kWalkOps = 192u;
-#ifndef JL_WALK_ENT
-#define JL_WALK_ENT 40
-#endif
 // entries of a read in LDS: a CCS read has a dozen.  With 24 two reads in a thousand went to the other launch; with 32 two in 100 000
 // (fifteen deletions) — enough for the upload to have to ask for that launch in every build; with 40 none of a CCS sample does
 // (48: 26 KB of LDS a workgroup, six a CU — not all 1563 of a 100k-read build at once: 28 us instead of 22)
-constexpr uint32_t kWalkEnt = JL_WALK_ENT;
+constexpr uint32_t kWalkEnt = 40u;
 constexpr uint32_t kWalkReads = 64u;    // reads of a workgroup
 
 __global__ __launch_bounds__(256) void cigar_walk_kernel(uint64_t n_reads, const int32_t *__restrict__ pos, const uint32_t *__restrict__ cigar,
@@ -667,29 +633,7 @@ struct ingest_args {
     uint32_t *big_list;          // the units (block numbers) handed on to the kernel's second size; their number in slow_count[1]
     uint8_t *msa;
     uint64_t plane_stride;
-    uint64_t seq_bytes, n_entries;   // (tuning builds check every address a descriptor leads to against these and report in dbg[])
-    uint32_t *dbg;
-    unsigned long long *stamps;  // (tuning builds)
-    uint32_t skip;               // tuning builds: bit 0 no bases, bit 1 no table, bit 2 no stores, bit 3 no general pass, bit 4 no transposing, bit 6 no conversion
 };
-#ifdef JL_TUNING
-#define JL_ING_SKIP(a, bit) (((a).skip >> (bit)) & 1u)
-// an address that would leave its array: counted in dbg[code], the offending value kept in dbg[5 + code]; the access is redirected
-#define JL_ING_CHECK(a, ok, code, value, fix) \
-    if (!(ok)) {                               \
-        atomicAdd(&(a).dbg[code], 1u);         \
-        (a).dbg[5 + (code)] = (uint32_t)(value); \
-        fix;                                   \
-    }
-// wall-clock stamps (10 ns) of every 61st workgroup's waves at the phase boundaries, in the (empty) slow list's memory
-#define JL_ING_STAMP(a, k)                                                                                        \
-    if ((a).stamps && blockIdx.x % 61u == 0u && blockIdx.x / 61u < 160u && (threadIdx.x & 63u) == 0u)           \
-        (a).stamps[((blockIdx.x / 61u) * 4u + (threadIdx.x >> 6)) * 12u + (k)] = wall_clock64();
-#else
-#define JL_ING_SKIP(a, bit) 0u
-#define JL_ING_CHECK(a, ok, code, value, fix)
-#define JL_ING_STAMP(a, k)
-#endif
 
 // LDS of a planes workgroup.  The staging area holds dwords of eight codes; a NIBBLE address into it fits 16 bits:
 //   dwords 0-1 'not covered' twice, 2-3 '-' twice (what a table entry of a block nothing / a deletion covers points at),
@@ -697,35 +641,20 @@ struct ingest_args {
 //   kRowBase ..        the reads' codes in query order: a row of kRowPieces 16-byte pieces per read — a sweep's bases from a
 //                      16-byte boundary on, + 8 dwords between the 32-read groups, so that the four reads a wave gathers from
 //                      at a time lie 8 banks apart.
-#ifndef JL_INGEST_ENT_PER_READ
-#define JL_INGEST_ENT_PER_READ 4
-#endif
-#ifndef JL_INGEST_ENT_PER_READ_BIG
-#define JL_INGEST_ENT_PER_READ_BIG 16
-#endif
 constexpr uint32_t kReadWaves = kTileReads / 64u;     // waves of read threads, with a part of the entry area each
-#ifndef JL_INGEST_MIN_WGS
-#define JL_INGEST_MIN_WGS 4               // workgroups a CU must be able to hold: 128 registers for the first size (two tiles a workgroup with qualities: 129 without the bound)
-#endif
-#ifndef JL_INGEST_NT
-#define JL_INGEST_NT 1                    // sibling tiles a workgroup of the planes kernel's first size takes (1, 2, 4); with qualities:
-#endif
-#ifndef JL_INGEST_NT_QV
-#define JL_INGEST_NT_QV 2
-#endif
-#ifndef JL_INGEST_QUAL_AHEAD
-#define JL_INGEST_QUAL_AHEAD 3            // pieces whose qualities a thread has asked for ahead of their turn (8 registers each; with all
-                                          // seven ahead one tile a workgroup is 5 us faster, two tiles a workgroup 11 us slower)
-#endif
-#ifndef JL_INGEST_ROW_EXTRA
-#define JL_INGEST_ROW_EXTRA 0             // pieces of a row beyond a sweep's own (room for inserted bases: 32 a piece)
-#endif
-constexpr uint32_t kRowPieces = (kSweep + 31u) / 32u + 1u + JL_INGEST_ROW_EXTRA, kRowDw = 4u * kRowPieces, kGroupPadDw = 8u;
+constexpr uint32_t kMinWgs = 4u;      // workgroups a CU must be able to hold: 128 registers for the first size (two tiles a workgroup with qualities: 129 without the bound)
+// pieces whose qualities a thread has asked for ahead of their turn (8 registers each; with all seven ahead one tile a workgroup is
+// 5 us faster, two tiles a workgroup 11 us slower)
+constexpr uint32_t kQualAhead = 3u;
+// a row: a sweep's pieces and one more — its first piece may begin seven bases before the sweep, which leaves room for 25 inserted
+// bases (a read with more of them in a sweep goes to slow_pair)
+constexpr uint32_t kRowPieces = (kSweep + 31u) / 32u + 1u, kRowDw = 4u * kRowPieces, kGroupPadDw = 8u;
 // The kernel comes in two sizes of its entry area (entries of the reads that need them, 4 bytes each in LDS: column - sweep's first
 // (0..256: 9 bits) | kind << 9 | (query offset there - the row's first) << 11): four entries a read on average — a CCS read has 4
 // in a sweep with an indel — with five workgroups to a CU, and sixteen, with three: for the (tile, sweep) units whose reads have
 // more (an indel every 50 columns), which the first size hands on (ingest_args::big_list) instead of leaving read after read
 // to the column-by-column kernel (7 ms for 100k reads with 1 % of indels).
+constexpr uint32_t kEntPerRead = 4u, kEntPerReadBig = 16u;
 template <uint32_t EPR>
 struct planes_shape {
     static constexpr uint32_t kEntCap = EPR * kTileReads, kEntCapWave = kEntCap / kReadWaves;
@@ -781,13 +710,6 @@ __device__ __forceinline__ piece_quals ask_quals(const ingest_args &a, int Q, ui
     typedef uint32_t u32x4a1 __attribute__((ext_vector_type(4), aligned(1)));
     const uint8_t *qp = a.qual + (int64_t)qual_base + (int64_t)Q;
     piece_quals q;
-#ifdef JL_TUNING
-    if (JL_ING_SKIP(a, 10)) {      // (probe: streaming loads)
-        q.a = __builtin_nontemporal_load(reinterpret_cast<const u32x4a1 *>(qp));
-        q.b = __builtin_nontemporal_load(reinterpret_cast<const u32x4a1 *>(qp + 16));
-        return q;
-    }
-#endif
     q.a = *reinterpret_cast<const u32x4a1 *>(qp);
     q.b = *reinterpret_cast<const u32x4a1 *>(qp + 16);
     return q;
@@ -890,10 +812,7 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
 {
     using shape = planes_shape<EPR>;
     constexpr uint32_t kEntCap = shape::kEntCap, kEntCapWave = shape::kEntCapWave, kRowBase = shape::kRowBase, kStageDw = shape::kStageDw;
-#ifndef JL_INGEST_LDS_PAD
-#define JL_INGEST_LDS_PAD 0               // (tuning: bytes of LDS a workgroup holds on top of what it uses — fewer workgroups per CU)
-#endif
-    __shared__ __attribute__((aligned(16))) uint32_t s_stage[kStageDw + JL_INGEST_LDS_PAD / 4];
+    __shared__ __attribute__((aligned(16))) uint32_t s_stage[kStageDw];
     __shared__ __attribute__((aligned(16))) uint16_t s_tab[kTabSize];
     __shared__ uint32_t s_ent[kEntCap];           // the entries of the reads with several in the sweep, a half per read wave
     __shared__ uint8_t s_own[kEntCap];            // whose: the read | 0x80 for its last one
@@ -917,7 +836,6 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
     const uint32_t X = sweep * kSweep, Xend = min(a.n_cols, X + kSweep), width = Xend - X;
     const uint4 *desc = a.desc + (uint64_t)sweep * a.n_reads;
     const uint64_t r0 = (uint64_t)tile * kTileReads;
-    JL_ING_STAMP(a, 0)
 
     // the pieces p0, p0 + 128, ... (K of them): the descriptors of their reads, then the pieces, all of a thread's requests in
     // flight together; a piece that is not there (the read has fewer) asks for the read's first one again — the same number of
@@ -952,13 +870,8 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
             const uint32_t p = p0 + kTileReads * k, j = p / kRowPieces, i = p - kRowPieces * j;
             uint32_t np = (d[k].w >> 16) & 0xFFu;
             if (np > kRowPieces || (d[k].w >> 24) == kDescMax) np = 0;      // (slow_pair's)
-            uint64_t at = ((((uint64_t)d[k].w & 0xFFu) << 32) | d[k].x) + (i < np ? 4u * i : 0u);     // (in dwords)
-            JL_ING_CHECK(a, 4u * at + 16u <= a.seq_bytes + 64u, 1, at, at = 0)
+            const uint64_t at = ((((uint64_t)d[k].w & 0xFFu) << 32) | d[k].x) + (i < np ? 4u * i : 0u);     // (in dwords)
             // (plain loads: neighbouring lanes' pieces share lines, and so do the sweeps of a read)
-#ifdef JL_TUNING
-            if (JL_ING_SKIP(a, 9)) pc[k].v = __builtin_nontemporal_load(reinterpret_cast<const u32x4a4 *>(a.seq4 + 4u * at));   // (probe)
-            else
-#endif
             pc[k].v = *reinterpret_cast<const u32x4a4 *>(a.seq4 + 4u * at);
             pc[k].dst = i < np ? shape::row_dw(j) + 4u * i : 0u;
             pc[k].Q = (int32_t)d[k].z + (i < np ? 32 * (int32_t)i : 0);      // (a piece that is not there: its read's first one's qualities)
@@ -968,7 +881,6 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
     // (QV: a piece's qualities are asked for kQualAhead pieces ahead of its turn, outside any branch — the loads of a piece that is
     // not there ask for its read's first piece's again.  Asked for inside the piece's own turn, as round 5 had it, every piece
     // of a thread waited for its own trip to HBM, seven in a row: 184 us against 111 without qualities.)
-    constexpr uint32_t kQualAhead = JL_INGEST_QUAL_AHEAD;
     auto stage_pieces = [&](uint32_t K, const piece_t (&pc)[kPieceRoundsB]) {
         piece_quals pq[kPieceRoundsB];
         if (QV) {
@@ -982,8 +894,7 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
             if (QV && k + kQualAhead < K && k + kQualAhead < kPieceRoundsB) pq[k + kQualAhead] = ask_quals(a, pc[k + kQualAhead].Q, pc[k + kQualAhead].qb);
             if (pc[k].dst) {
                 uint32_t S[4];
-                if (JL_ING_SKIP(a, 6)) { S[0] = pc[k].v.x; S[1] = pc[k].v.y; S[2] = pc[k].v.z; S[3] = pc[k].v.w; }
-                else piece_bases<QV>(a, pc[k].v, pq[k], S);
+                piece_bases<QV>(a, pc[k].v, pq[k], S);
                 u32x4 o = {S[0], S[1], S[2], S[3]};
                 *reinterpret_cast<u32x4 *>(&s_stage[pc[k].dst]) = o;
             }
@@ -997,12 +908,9 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
     // launch 110-113 -> 100-107 us, a whole build 171 -> 164 us on one stream and 159 -> 152 with two builds overlapping.  With
     // qualities the launch alone gains 3 us of 169 and the build LOSES 3-7 (two streams: 191 -> 198; in bench.py's once_through_qv
     // 185 -> 202): its raised waves also go before the waves of whatever else is on the device — the next build's cigar walk, the
-    // pileup and the phasing of the windows before — so there it stays off.  (JL_INGEST_PRIO=0 for A/B.  Raised only until the loads
-    // are out: the same; raised for the transposing instead: 116 / 176.)
-#ifndef JL_INGEST_PRIO
-#define JL_INGEST_PRIO 1
-#endif
-    constexpr bool kPrio = JL_INGEST_PRIO && !QV;
+    // pileup and the phasing of the windows before — so there it stays off.  (Raised only until the loads are out: the same;
+    // raised for the transposing instead: 116 / 176.)
+    constexpr bool kPrio = !QV;
     if (kPrio) __builtin_amdgcn_s_setprio(3);
     if (tid >= kTileReads) {
         // ---- waves 2, 3: pieces
@@ -1012,9 +920,7 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
         const uint32_t p0 = tid - kTileReads;
         ask_descs(p0, kPieceRoundsB, d, qo);
         ask_pieces(p0, kPieceRoundsB, d, qo, pc);
-        JL_ING_STAMP(a, 3)
-        if (!JL_ING_SKIP(a, 0)) stage_pieces(kPieceRoundsB, pc);
-        JL_ING_STAMP(a, 6)
+        stage_pieces(kPieceRoundsB, pc);
     } else {
         // ---- waves 0, 1: a thread per read
         typedef uint32_t u32x4a8 __attribute__((ext_vector_type(4), aligned(8)));
@@ -1026,9 +932,6 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
         uint4 d = make_uint4(0, 0, 0, 3u << 8 | 1u << 24);   // (no read: one entry of nothing)
         if (r < a.n_reads) d = desc[r];
         ask_descs(p0, kPieceRoundsA, dp, qo);
-#ifdef JL_TUNING
-        if (a.stamps) { asm volatile("" ::"v"(d.w)); JL_ING_STAMP(a, 1) }   // (the descriptor has arrived)
-#endif
         if (tid < 4u) s_stage[tid] = tid < 2u ? 0x66666666u : 0x44444444u;
         if (tid == 4u) s_nslow = 0;
         if (lane == 0) s_nent[wid] = 0, s_nent[kReadWaves + wid] = 0;
@@ -1052,14 +955,12 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
             s_nent[kReadWaves + wid] = 1u;
             slow = false;
         }
-        JL_ING_CHECK(a, !slow || r < a.n_reads, 3, r, slow = false)
         slow_read = slow;
         off_e += wid * kEntCapWave;
         // the sweep's entries of this read: the first eight in four 16-byte requests that go out together (entries past the
         // read's own belong to the next read or to the array's slack) — two deletions in a sweep are six entries, and a
         // wave in which ONE read needs a ninth makes another trip for it
-        uint64_t src_at = n_ent ? ((((uint64_t)(d.w >> 8) & 0xFFu) << 32) | d.y) : 0u;
-        JL_ING_CHECK(a, src_at + (n_ent > 4u ? max(n_ent, 8u) : 4u) <= a.n_entries, 2, src_at, src_at = 0)
+        const uint64_t src_at = n_ent ? ((((uint64_t)(d.w >> 8) & 0xFFu) << 32) | d.y) : 0u;
         const uint2 *src = a.runs + src_at;
         u32x4a8 e01 = {0, 0, 0, 0}, e23 = e01, e45 = e01, e67 = e01;
         if (n_ent) {
@@ -1087,7 +988,6 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
                 hi += step;
             }
         }
-        JL_ING_STAMP(a, 2)
         // several entries: -> LDS, four bytes each, with their owner; everybody makes table rows of them behind the barrier
         if (n_ent) {
             auto pack = [&](uint32_t x, uint32_t y) -> uint32_t {
@@ -1114,12 +1014,9 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
             }
             atomicMax(&s_nent[wid], off_e - wid * kEntCapWave + n_ent);
         }
-        JL_ING_STAMP(a, 4)
-        if (!JL_ING_SKIP(a, 0)) stage_pieces(kPieceRoundsA, pc);
-        JL_ING_STAMP(a, 6)
+        stage_pieces(kPieceRoundsA, pc);
     }
     __syncthreads();
-    JL_ING_STAMP(a, 7)
     if (!BIG) {
         uint32_t handed = 0;
 #pragma unroll
@@ -1136,93 +1033,89 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
     // it: the blocks that lie WHOLLY inside are the entry's — addresses that rise by eight codes a block, or the dword of '-' /
     // of 'not covered' — and every block is wholly inside one entry or has an entry that begins inside it; those are put
     // together, by the thread of the first such entry, in that entry's side dword.  No list, no search, no loop per block.
-    if (!JL_ING_SKIP(a, 1)) {
-        uint32_t n_e = 0;
+    uint32_t n_e = 0;
 #pragma unroll
-        for (uint32_t w = 0; w < kReadWaves; ++w) n_e += s_nent[w];
-        for (uint32_t si = tid; si < n_e; si += kThreads) {
-            uint32_t slot = 0, rem = si;      // the si-th entry of the parts one behind the other
-            bool found = false;
+    for (uint32_t w = 0; w < kReadWaves; ++w) n_e += s_nent[w];
+    for (uint32_t si = tid; si < n_e; si += kThreads) {
+        uint32_t slot = 0, rem = si;      // the si-th entry of the parts one behind the other
+        bool found = false;
 #pragma unroll
-            for (uint32_t w = 0; w < kReadWaves; ++w) {
-                const uint32_t nw = s_nent[w];
-                if (!found && rem < nw) {
-                    slot = w * kEntCapWave + rem;
-                    found = true;
-                }
-                if (!found) rem -= nw;
+        for (uint32_t w = 0; w < kReadWaves; ++w) {
+            const uint32_t nw = s_nent[w];
+            if (!found && rem < nw) {
+                slot = w * kEntCapWave + rem;
+                found = true;
             }
-            const uint32_t own = s_own[slot], e = s_ent[slot], nx = s_ent[slot + 1u];
-            const uint32_t wr = ent_col(e);
-            if ((own & 0x80u) || wr >= width) continue;
-            const uint32_t row8 = 8u * shape::row_dw(own);
-            // (a) the entry's whole blocks [bf, be): singly up to a multiple of four, four a store, singly again
-            const uint32_t wn = ent_col(nx);
-            const uint32_t be = wn >= width ? kBlocks : wn >> 3;
-            uint32_t bf = (wr + 7u) >> 3;
-            if (bf < be) {
-                const uint32_t st = ent_kind(e) == 1u ? 8u : 0u;
-                uint32_t av = ent_addr(e, row8, 8u * bf);
-#pragma unroll
-                for (uint32_t k = 0; k < 3u; ++k)
-                    if ((bf & 3u) && bf < be) {
-                        s_tab[tab_at(own, bf)] = (uint16_t)av;
-                        av += st;
-                        ++bf;
-                    }
-                uint32_t p01 = av | ((av + st) << 16);
-                const uint32_t p_st = st | st << 16;
-                for (; bf + 4u <= be; bf += 4u) {
-                    *reinterpret_cast<uint2 *>(s_tab + tab_at(own, bf)) = make_uint2(p01, p01 + 2u * p_st);
-                    p01 += 4u * p_st;
-                }
-                av = p01 & 0xFFFFu;
-#pragma unroll
-                for (uint32_t k = 0; k < 3u; ++k)
-                    if (bf < be) {
-                        s_tab[tab_at(own, bf)] = (uint16_t)av;
-                        av += st;
-                        ++bf;
-                    }
-            }
-            // (b) the block it begins inside, if it is the first entry to do so
-            const uint32_t bb = wr >> 3;
-            if (!(wr & 7u) || JL_ING_SKIP(a, 3)) continue;
-            uint32_t ee = s_ent[slot - 1u];        // (an entry that begins inside a block is not its read's first)
-            if (ent_col(ee) > 8u * bb) continue;
-            const uint32_t c0 = 8u * bb, c1 = c0 + 8u;
-            uint32_t bases = 0, m_al = 0, m_del = 0;      // the block's aligned bases (BAM's codes), where they are, where a deletion is
-            for (uint32_t kk = slot;; ++kk) {
-                const uint32_t nn = s_ent[kk];
-                const uint32_t W = ent_col(ee), Wn = ent_col(nn);
-                const uint32_t ca = max(W, c0), cb = min(Wn, c1);
-                const uint32_t kind = ent_kind(ee);
-                if (ca < cb && kind != 3u) {
-                    const uint32_t m = (cb - ca == 8u ? 0xFFFFFFFFu : ((1u << (4u * (cb - ca))) - 1u)) << (4u * (ca - c0));
-                    if (kind == 1u) {
-                        const uint32_t A = ent_addr(ee, row8, ca);
-                        bases |= (__builtin_amdgcn_alignbit(s_stage[(A >> 3) + 1u], s_stage[A >> 3], 4u * (A & 7u)) << (4u * (ca - c0))) & m;
-                        m_al |= m;
-                    } else m_del |= m;
-                }
-                if (Wn >= c1 || (s_own[kk] & 0x80u)) break;     // (the read's last entry is nothing: 'not covered' stays)
-                ee = nn;
-            }
-            const uint32_t R = (codes_of_bases8(bases) & m_al) | (0x44444444u & m_del) | (0x66666666u & ~(m_al | m_del));
-            s_stage[4u + slot] = R;
-            s_tab[tab_at(own, bb)] = (uint16_t)(8u * (4u + slot));
+            if (!found) rem -= nw;
         }
+        const uint32_t own = s_own[slot], e = s_ent[slot], nx = s_ent[slot + 1u];
+        const uint32_t wr = ent_col(e);
+        if ((own & 0x80u) || wr >= width) continue;
+        const uint32_t row8 = 8u * shape::row_dw(own);
+        // (a) the entry's whole blocks [bf, be): singly up to a multiple of four, four a store, singly again
+        const uint32_t wn = ent_col(nx);
+        const uint32_t be = wn >= width ? kBlocks : wn >> 3;
+        uint32_t bf = (wr + 7u) >> 3;
+        if (bf < be) {
+            const uint32_t st = ent_kind(e) == 1u ? 8u : 0u;
+            uint32_t av = ent_addr(e, row8, 8u * bf);
+#pragma unroll
+            for (uint32_t k = 0; k < 3u; ++k)
+                if ((bf & 3u) && bf < be) {
+                    s_tab[tab_at(own, bf)] = (uint16_t)av;
+                    av += st;
+                    ++bf;
+                }
+            uint32_t p01 = av | ((av + st) << 16);
+            const uint32_t p_st = st | st << 16;
+            for (; bf + 4u <= be; bf += 4u) {
+                *reinterpret_cast<uint2 *>(s_tab + tab_at(own, bf)) = make_uint2(p01, p01 + 2u * p_st);
+                p01 += 4u * p_st;
+            }
+            av = p01 & 0xFFFFu;
+#pragma unroll
+            for (uint32_t k = 0; k < 3u; ++k)
+                if (bf < be) {
+                    s_tab[tab_at(own, bf)] = (uint16_t)av;
+                    av += st;
+                    ++bf;
+                }
+        }
+        // (b) the block it begins inside, if it is the first entry to do so
+        const uint32_t bb = wr >> 3;
+        if (!(wr & 7u)) continue;
+        uint32_t ee = s_ent[slot - 1u];        // (an entry that begins inside a block is not its read's first)
+        if (ent_col(ee) > 8u * bb) continue;
+        const uint32_t c0 = 8u * bb, c1 = c0 + 8u;
+        uint32_t bases = 0, m_al = 0, m_del = 0;      // the block's aligned bases (BAM's codes), where they are, where a deletion is
+        for (uint32_t kk = slot;; ++kk) {
+            const uint32_t nn = s_ent[kk];
+            const uint32_t W = ent_col(ee), Wn = ent_col(nn);
+            const uint32_t ca = max(W, c0), cb = min(Wn, c1);
+            const uint32_t kind = ent_kind(ee);
+            if (ca < cb && kind != 3u) {
+                const uint32_t m = (cb - ca == 8u ? 0xFFFFFFFFu : ((1u << (4u * (cb - ca))) - 1u)) << (4u * (ca - c0));
+                if (kind == 1u) {
+                    const uint32_t A = ent_addr(ee, row8, ca);
+                    bases |= (__builtin_amdgcn_alignbit(s_stage[(A >> 3) + 1u], s_stage[A >> 3], 4u * (A & 7u)) << (4u * (ca - c0))) & m;
+                    m_al |= m;
+                } else m_del |= m;
+            }
+            if (Wn >= c1 || (s_own[kk] & 0x80u)) break;     // (the read's last entry is nothing: 'not covered' stays)
+            ee = nn;
+        }
+        const uint32_t R = (codes_of_bases8(bases) & m_al) | (0x44444444u & m_del) | (0x66666666u & ~(m_al | m_del));
+        s_stage[4u + slot] = R;
+        s_tab[tab_at(own, bb)] = (uint16_t)(8u * (4u + slot));
     }
-    JL_ING_STAMP(a, 8)
     __syncthreads();
-    JL_ING_STAMP(a, 9)
     const uint32_t n_slow = s_nslow;
 
     // ---- gather at the transpose: thread = 32 reads x 8 columns; neighbouring lanes write consecutive dwords of a plane
     if (kPrio) __builtin_amdgcn_s_setprio(0);
     {
         const uint32_t G = tid % kTileGroups, blk = tid / kTileGroups;
-        const bool act = blk < kBlocks && 8u * blk < width && !JL_ING_SKIP(a, 4);
+        const bool act = blk < kBlocks && 8u * blk < width;
         uint32_t out[8][3];
         if (act) {
             // (the dwords in front of the reads' rows — 'not covered', '-', the boundary blocks — hold symbol codes already; `codes`
@@ -1247,25 +1140,7 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
                 for (uint32_t k = 0; k < 3u; ++k) keep[jj][k] = out[jj][k];
         } else if (act) {
             const uint64_t byte = (uint64_t)tile * (kTileReads / 8u) + (uint64_t)G * 4u;
-#ifdef JL_TUNING
-            if (JL_ING_SKIP(a, 7) || JL_ING_SKIP(a, 8)) {   // (probes, wrong data by design: 7 the same bytes in 16-byte stores, a quarter of the requests; 8 non-temporal stores)
-                uint8_t *row = a.msa + (uint64_t)((X + 8u * blk) * 3u) * a.plane_stride + (uint64_t)tile * (kTileReads / 8u) + (JL_ING_SKIP(a, 8) ? (uint64_t)G * 4u : 0u);
-                for (uint32_t jj = 0; jj < 8u; ++jj)
-                    for (uint32_t k = 0; k < 3u; ++k) {
-                        if (JL_ING_SKIP(a, 8)) __builtin_nontemporal_store(out[jj][k], reinterpret_cast<uint32_t *>(row));
-                        else if (G == 0) { u32x4 o = {out[jj][k], out[jj][0], out[jj][1], out[jj][2]}; *reinterpret_cast<u32x4 *>(row) = o; }
-                        row += a.plane_stride;
-                    }
-            } else if (JL_ING_SKIP(a, 11)) {   // (probe, wrong data by design: the same bytes as 64-byte requests — a quarter of the rows, four tiles wide)
-                uint8_t *row = a.msa + (uint64_t)((X + 8u * blk) * 3u) * a.plane_stride + (uint64_t)(tile & ~3u) * (kTileReads / 8u) + (uint64_t)G * 16u;
-                for (uint32_t jj = 0; jj < 8u; ++jj)
-                    for (uint32_t k = 0; k < 3u; ++k) {
-                        if (((jj * 3u + k) & 3u) == (sub & 3u)) { u32x4 o = {out[jj][k], out[jj][0], out[jj][1], out[jj][2]}; *reinterpret_cast<u32x4 *>(row) = o; }
-                        row += a.plane_stride;
-                    }
-            } else
-#endif
-            if (byte < a.plane_stride && (!JL_ING_SKIP(a, 2) || out[0][0] == 0x12345u)) {
+            if (byte < a.plane_stride) {
                 // (one 64-bit multiply for the first plane row, then a stride at a time; a block of eight whole columns — all but
                 // the window's last — stores without a question per column: a predicate per store was a sixth of this phase)
                 uint8_t *row = a.msa + (uint64_t)((X + 8u * blk) * 3u) * a.plane_stride + byte;
@@ -1287,7 +1162,6 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
             }
         }
     }
-    JL_ING_STAMP(a, 10)
     // ---- the reads left out (none, in a CCS sample): column by column behind the workgroup's own stores, a wave a read
     if (!DEFER && n_slow) {       // (the same in every thread)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1302,22 +1176,23 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
 constexpr uint32_t kBigGrid = 768u;
 // NT (the first size): sibling tiles a workgroup takes one after the other, their plane words kept in registers and stored
 // TOGETHER at the end — NT x 16 bytes of a line a request instead of 16.  The L2 takes a write request per (row, tile): 7 x 10^6 a
-// window, more than all its read requests; the same bytes as 64-byte requests (a probe: JL_ING_SKIP bit 11) took 19 us off the
+// window, more than all its read requests; the same bytes as 64-byte requests (a probe, round 6) took 19 us off the
 // launch's 113 and 29 off the 180 with qualities.  The tiles' words change places between the lanes of a DPP row (16 lanes = four
-// blocks of 8 columns x four 32-read groups): the lane at position u of a run of NT blocks ends up with tile u's words of all NT
-// blocks (log2 NT rounds of two DPP moves a word), and 4 NT neighbouring lanes write NT x 16 contiguous bytes of a row.
+// blocks of 8 columns x four 32-read groups): the lane at position u of a pair of blocks ends up with tile u's words of both
+// blocks (two DPP moves a word), and 4 NT neighbouring lanes write NT x 16 contiguous bytes of a row.  (Four tiles a workgroup
+// were slower: see jl_launch_ingest.)
 template <bool QV, uint32_t EPR, bool BIG, uint32_t NT = 1u>
-__global__ __launch_bounds__(kThreads, (BIG ? 1 : JL_INGEST_MIN_WGS)) void ingest_planes_kernel(ingest_args a)
+__global__ __launch_bounds__(kThreads, (BIG ? 1 : kMinWgs)) void ingest_planes_kernel(ingest_args a)
 {
-    static_assert(NT == 1u || NT == 2u || NT == 4u, "a DPP row holds four blocks");
-    if (BIG) {
+    static_assert(NT == 1u || NT == 2u, "one tile a workgroup, or two");
+    if constexpr (BIG) {
         uint32_t none[8][3];
         const uint32_t n = a.slow_count[1];
         for (uint32_t u = blockIdx.x; u < n; u += gridDim.x) {
             planes_unit<QV, EPR, true>(a, a.big_list[u], none);
             __syncthreads();      // (the next unit's LDS)
         }
-    } else if (NT == 1u) {
+    } else if constexpr (NT == 1u) {
         uint32_t none[8][3];
         planes_unit<QV, EPR, false>(a, blockIdx.x, none);
     } else {
@@ -1343,30 +1218,16 @@ __global__ __launch_bounds__(kThreads, (BIG ? 1 : JL_INGEST_MIN_WGS)) void inges
         const uint32_t tid = threadIdx.x;
         if (tid >= kTileGroups * kBlocks) return;           // (the transposing threads)
         const uint32_t G = tid % kTileGroups, blk = tid / kTileGroups, u = blk & (NT - 1u);
-        // ---- the tiles' words change places: round s swaps, between blocks 2^s apart, the words of the tiles whose bit s differs
+        // ---- the two tiles' words change places between neighbouring blocks: lanes of an even block take the partner's (4 lanes
+        // up) tile-0 words into slot 1, the others the partner's tile-1 words into slot 0 (bank = block within the row)
 #pragma unroll
-        for (uint32_t sft = 0; (1u << sft) < NT; ++sft) {
+        for (uint32_t jj = 0; jj < 8u; ++jj)
 #pragma unroll
-            for (uint32_t t0 = 0; t0 < NT; ++t0) {
-                if (t0 & (1u << sft)) continue;
-                const uint32_t t1 = t0 | (1u << sft);
-#pragma unroll
-                for (uint32_t jj = 0; jj < 8u; ++jj)
-#pragma unroll
-                    for (uint32_t k = 0; k < 3u; ++k) {
-                        const int x0 = (int)D[t0][jj][k], x1 = (int)D[t1][jj][k];
-                        // lanes whose block has bit s clear take the partner's (4 << s lanes up) tile-t0 words into slot t1,
-                        // the others the partner's tile-t1 words into slot t0 (bank = block within the row)
-                        if (sft == 0u) {
-                            D[t1][jj][k] = (uint32_t)__builtin_amdgcn_update_dpp(x1, x0, 0x104, 0xF, 0x5, false);   // row_shl:4, banks 0 2
-                            D[t0][jj][k] = (uint32_t)__builtin_amdgcn_update_dpp(x0, x1, 0x114, 0xF, 0xA, false);   // row_shr:4, banks 1 3
-                        } else {
-                            D[t1][jj][k] = (uint32_t)__builtin_amdgcn_update_dpp(x1, x0, 0x108, 0xF, 0x3, false);   // row_shl:8, banks 0 1
-                            D[t0][jj][k] = (uint32_t)__builtin_amdgcn_update_dpp(x0, x1, 0x118, 0xF, 0xC, false);   // row_shr:8, banks 2 3
-                        }
-                    }
+            for (uint32_t k = 0; k < 3u; ++k) {
+                const int x0 = (int)D[0][jj][k], x1 = (int)D[1][jj][k];
+                D[1][jj][k] = (uint32_t)__builtin_amdgcn_update_dpp(x1, x0, 0x104, 0xF, 0x5, false);   // row_shl:4, banks 0 2
+                D[0][jj][k] = (uint32_t)__builtin_amdgcn_update_dpp(x0, x1, 0x114, 0xF, 0xA, false);   // row_shr:4, banks 1 3
             }
-        }
         // ---- D[p] = this lane's tile's (tile u of the NT) words of block (blk & ~(NT - 1)) + p: NT x 4 lanes a row
         if (!((ok >> u) & 1u)) return;                      // (this lane's tile was handed on)
         const uint32_t sub0 = NT * h, group = xcd + 8u * (qq / a.n_sweeps), sweep = qq % a.n_sweeps;
@@ -1417,11 +1278,10 @@ static uint32_t planes_units(const jl_ctx *ctx)
     return (groups + 7u) / 8u * jl_ingest_sweeps(ctx->n_cols) * 8u * kSubTiles;
 }
 
-// pairs (8 bytes) of d_slow: the tuning build's stamps, and behind them the units handed on (a word each)
-constexpr uint32_t kStampPairs = 160u * 4u * 12u;
-size_t jl_ingest_slow_room(const jl_ctx *ctx) { return (size_t)kStampPairs + planes_units(ctx) / 2u + 8u; }
+// pairs (8 bytes) of d_slow: the units handed on (a word each)
+size_t jl_ingest_slow_room(const jl_ctx *ctx) { return (size_t)planes_units(ctx) / 2u + 8u; }
 
-// The host's copy of cigar_walk_kernel's rule — which reads it leaves to the second launch (more than kWalkOps ops, or more entries
+// The host's copy of cigar_walk_kernel's rule — which reads it leaves to the long-read launch (more than kWalkOps ops, or more entries
 // than a read has room for in its LDS) — for the upload (jl_records_append), which looks at the few reads of a CCS sample with more
 // ops than a read has entries: when it finds none, jl_launch_ingest does not make that launch.
 uint32_t jl_ingest_short_ops() { return kWalkEnt - 3u; }      // a read of so many ops at most cannot be a long one
@@ -1442,12 +1302,12 @@ bool jl_ingest_read_is_long(const uint32_t *cigar, uint64_t n_ops)
 // d_runs: n_cig + 3 n_reads + 8 entries; d_nruns: n_reads; d_desc: n_reads x sweeps descriptors; d_slow: jl_ingest_slow_room() pairs.
 // d_slow_count, 64 bytes: [0] pairs listed, [1] units handed on — zeroed by the build's first launch; [2..3] the 64-bit word of the
 // first malformed record (all ones: none — so it is allocated, and so jl_ingest_verdict leaves it when it has read one; a build
-// whose predecessor's word has not been read yet folds its own into it, atomicMin); [4..15] the tuning build's checks.
+// whose predecessor's word has not been read yet folds its own into it, atomicMin).
 // Everything is enqueued on ctx->stream; nothing waits.
 void jl_launch_ingest(jl_ctx *ctx, const int32_t *d_pos, const uint32_t *d_cigar, const uint64_t *d_cig_off,
                       const uint8_t *d_seq4, const uint64_t *d_seq_off, const uint8_t *d_qual,
                       const uint64_t *d_qual_off, uint32_t min_qv, uint2 *d_runs, uint32_t *d_nruns, uint4 *d_desc,
-                      uint32_t *d_slow_count, uint2 *d_slow, bool maybe_long, uint64_t seq_bytes, uint64_t n_entries)
+                      uint32_t *d_slow_count, uint2 *d_slow, bool maybe_long)
 {
     hipStream_t st = ctx->stream;
     const uint32_t ns = jl_ingest_sweeps(ctx->n_cols);
@@ -1455,20 +1315,15 @@ void jl_launch_ingest(jl_ctx *ctx, const int32_t *d_pos, const uint32_t *d_cigar
     // whenever a verdict has been read (jl_ingest_verdict): a build whose predecessor's verdict is still unread folds its own into it.
     if (!ctx->n_reads) hipLaunchKernelGGL(ingest_init_kernel, dim3(1), dim3(64), 0, st, d_slow_count, 0u);
     if (ctx->n_reads) {
-        const uint32_t per_wg = 4u * kRunsReadsPerWave;
         unsigned long long *bad = reinterpret_cast<unsigned long long *>(d_slow_count + 2);
         const uint64_t *qo = d_qual ? d_qual_off : nullptr;
-        (void)per_wg;
         hipLaunchKernelGGL(cigar_walk_kernel, dim3((uint32_t)((ctx->n_reads + kWalkReads - 1u) / kWalkReads)), dim3(256), 0, st,
                            ctx->n_reads, d_pos, d_cigar, d_cig_off, d_seq_off, qo, ctx->win_begin, ctx->n_cols, ns, d_runs, d_nruns, d_desc, bad, d_slow_count, maybe_long ? 1u : 0u);
         // (the launch for the long reads: not when the upload has looked and found none — every CCS sample: 6 us of a build)
         if (maybe_long)
-            hipLaunchKernelGGL((cigar_runs_kernel<kRunsLdsLarge, true>), dim3((uint32_t)std::min<uint64_t>(kRunsLongGrid, (ctx->n_reads + 255u) / 256u)), dim3(256), 0, st,
+            hipLaunchKernelGGL(cigar_runs_kernel, dim3((uint32_t)std::min<uint64_t>(kRunsLongGrid, (ctx->n_reads + 255u) / 256u)), dim3(256), 0, st,
                                ctx->n_reads, d_pos, d_cigar, d_cig_off, d_seq_off, qo, ctx->win_begin, ctx->n_cols, ns, d_runs, d_nruns, d_desc, bad);
     }
-#ifdef JL_TUNING
-    if (getenv("JL_ING_ONLY_RUNS")) return;     // (probe builds of cigar_runs leave descriptors nobody may follow)
-#endif
     ingest_args a;
     a.n_reads = ctx->n_reads;
     a.n_cols = ctx->n_cols;
@@ -1486,31 +1341,18 @@ void jl_launch_ingest(jl_ctx *ctx, const int32_t *d_pos, const uint32_t *d_cigar
     a.nruns = d_nruns;
     a.desc = d_desc;
     a.slow_count = d_slow_count;
-    a.big_list = reinterpret_cast<uint32_t *>(d_slow + kStampPairs);
+    a.big_list = reinterpret_cast<uint32_t *>(d_slow);
     a.msa = ctx->d_msa;
     a.plane_stride = ctx->plane_stride;
-    a.seq_bytes = seq_bytes;
-    a.n_entries = n_entries;
-    a.dbg = d_slow_count + 4;    // (twelve spare words of the 64-byte block)
-    a.skip = 0;
-    a.stamps = nullptr;
-#ifdef JL_TUNING
-    if (getenv("JL_ING_STAMPS")) {
-        a.stamps = reinterpret_cast<unsigned long long *>(d_slow);
-        hipMemsetAsync(d_slow, 0, kStampPairs * 8u, st);
-    }
-    hipMemsetAsync(d_slow_count + 4, 0, 48, st);
-    if (const char *e = getenv("JL_ING_SKIP")) a.skip = (uint32_t)atoi(e);
-#endif
     const uint32_t grid = planes_units(ctx);
-    constexpr uint32_t E = JL_INGEST_ENT_PER_READ, EB = JL_INGEST_ENT_PER_READ_BIG;
-    // (sibling tiles a workgroup, tools_tuning/nt_probe.sh: with qualities two — 170 us against 179 with one, 213-219 with four (the
-    // registers leave two workgroups a CU); without qualities one: 111-113 with one or two, 132 with four)
+    // sibling tiles a workgroup (round 6): with qualities two — 170 us against 179 with one, 213-219 with four (the registers leave two
+    // workgroups a CU); without qualities one: 111-113 with one or two, 132 with four
+    constexpr uint32_t kNt = 1u, kNtQv = 2u;
     if (qv) {
-        hipLaunchKernelGGL((ingest_planes_kernel<true, E, false, JL_INGEST_NT_QV>), dim3(grid / JL_INGEST_NT_QV), dim3(kThreads), 0, st, a);
-        hipLaunchKernelGGL((ingest_planes_kernel<true, EB, true>), dim3(kBigGrid), dim3(kThreads), 0, st, a);
+        hipLaunchKernelGGL((ingest_planes_kernel<true, kEntPerRead, false, kNtQv>), dim3(grid / kNtQv), dim3(kThreads), 0, st, a);
+        hipLaunchKernelGGL((ingest_planes_kernel<true, kEntPerReadBig, true>), dim3(kBigGrid), dim3(kThreads), 0, st, a);
     } else {
-        hipLaunchKernelGGL((ingest_planes_kernel<false, E, false, JL_INGEST_NT>), dim3(grid / JL_INGEST_NT), dim3(kThreads), 0, st, a);
-        hipLaunchKernelGGL((ingest_planes_kernel<false, EB, true>), dim3(kBigGrid), dim3(kThreads), 0, st, a);
+        hipLaunchKernelGGL((ingest_planes_kernel<false, kEntPerRead, false, kNt>), dim3(grid / kNt), dim3(kThreads), 0, st, a);
+        hipLaunchKernelGGL((ingest_planes_kernel<false, kEntPerReadBig, true>), dim3(kBigGrid), dim3(kThreads), 0, st, a);
     }
 }

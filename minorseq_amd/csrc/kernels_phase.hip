@@ -545,15 +545,6 @@ typedef jl_select_args select_args;
 //   3. the remaining clean reads go through an LDS table (CAS on the 64-bit key), which is then flushed
 //      with one global insert per distinct key per block.
 // Global atomics on the hot slot drop from one per wave to one per 2048 reads.
-#ifdef JL_EXP_STAMPS   // experiment builds only: device-clock stamps (100 MHz) of one workgroup's way through the fused launch
-__device__ unsigned long long g_stamps[64];
-#define JL_STAMP(k) do { if (threadIdx.x == 0 && (blockIdx.x == 0 || (k) >= 8)) g_stamps[(k)] = wall_clock64(); } while (0)
-#define JL_STAMP_ON 1
-#else
-#define JL_STAMP(k) do { } while (0)
-#define JL_STAMP_ON 0
-__device__ unsigned long long g_stamps[32];   // (never written in this build: the stores sit behind JL_STAMP_ON)
-#endif
 constexpr uint32_t kLdsSlots = 1024;
 constexpr uint64_t kNoKey = ~0ull;
 constexpr uint32_t kPlanList = 256;   // called positions a workgroup can rank in LDS; more take the multi-word pipeline
@@ -756,7 +747,6 @@ __device__ __forceinline__ bool phase_select_lds(const jl_win_phase &w, const pl
         T.vpos[v] = e;
     }
     __syncthreads();
-    JL_STAMP(13);
     const uint32_t H = T.ncand;
     if (T.bail || nv * H > JL_SEL_HIT_BYTES) return false;
     if (KW == 2) {   // the candidates' two words, from the half-key tables
@@ -767,7 +757,6 @@ __device__ __forceinline__ bool phase_select_lds(const jl_win_phase &w, const pl
         }
         __syncthreads();
     }
-    JL_STAMP(23);
     // Nothing below gives the run back to the general routine, and nothing reads the tables again: they are left empty for
     // the next run now (only the slots this run touched) — stores that go out beside the ranking instead of behind it.
     // (the first 1024 groups' slots are still in registers from the scan: stores only)
@@ -825,7 +814,6 @@ __device__ __forceinline__ bool phase_select_lds(const jl_win_phase &w, const pl
         }
     }
     __syncthreads();
-    JL_STAMP(24);
     {   // (H <= 128: the threads that hold my_rank)
         uint32_t ca = 0;
         if (tid < H) {
@@ -842,7 +830,6 @@ __device__ __forceinline__ bool phase_select_lds(const jl_win_phase &w, const pl
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the table's stores, the scan's among them, are performed)
     __syncthreads();
-    JL_STAMP(25);
     ranked(id_bits_for(H));
     // hit[v][h] and, per variant, the set of haplotypes that carry it as bits: a lane per haplotype (its pattern words in
     // registers), a wave per variant (no division per element; the set makes the co-occurrence sums a walk over a few
@@ -872,7 +859,6 @@ __device__ __forceinline__ bool phase_select_lds(const jl_win_phase &w, const pl
     __syncthreads();
     const uint32_t bits = id_bits_for(H);
     *id_bits_out = bits;   // (every thread: a register of the caller)
-    JL_STAMP(14);
     const uint32_t nvc = nv < S.cooc_cap ? nv : S.cooc_cap;
     const bool cooc_fits = nv <= JL_PACK_COOC_N;
     // ---- outputs.  The resident arrays are what the stage-API fetches read; a whole-path run whose results fit the result
@@ -886,7 +872,6 @@ __device__ __forceinline__ bool phase_select_lds(const jl_win_phase &w, const pl
         for (uint32_t v = tid >> 6; v < nv; v += nt >> 6)
             for (uint32_t h = tid & 63u; h < H; h += 64u) S.hit[(uint64_t)v * JL_MAX_HAPLOTYPES + h] = T.hit[v * H + h];
     }
-    JL_STAMP(26);
     jl_pack *pk = S.pk + (seq_pre & 1u);
     jl_pack *dsts[2] = {pk, S.mirror};
     // Co-occurrence C[v][x] = sum over the haplotypes that carry both of their read counts.  The counts are cut into bit
@@ -930,7 +915,6 @@ __device__ __forceinline__ bool phase_select_lds(const jl_win_phase &w, const pl
             for (int t = 0; t < 2; ++t)
                 if (dsts[t]) { dsts[t]->cooc[v * nv + x] = sum; dsts[t]->cooc[x * nv + v] = sum; }
     }
-    JL_STAMP(15);
     // ... and the result block, device copy (all-gather source) and pinned host mirror, straight from LDS, eight bytes a store
     if (tid == 0) {
         jl_phase_summary sm;
@@ -979,9 +963,6 @@ __device__ __forceinline__ bool phase_select_lds(const jl_win_phase &w, const pl
             for (uint32_t i = tid; i < n_hit8; i += nt) reinterpret_cast<unsigned long long *>(o->hit)[i] = hit8[i];
         }
     }
-    JL_STAMP(16);
-    JL_STAMP(17);
-    if (tid == 0 && JL_STAMP_ON) g_stamps[18] = n_occ;
     return true;
 }
 
@@ -1118,7 +1099,6 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
     // whole-path runs launch one workgroup more than the reads need: it compacts the called rows meanwhile
     const uint32_t n_arrive = w.n_blocks + (from_called ? 1u : 0u);
     const bool plan_block = from_called && blockIdx.x == w.n_blocks;
-    JL_STAMP(0);
 
     // ---- 0. the plan
     uint32_t vp, n_rows;
@@ -1167,7 +1147,6 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
     }
     const uint64_t t = (uint64_t)blockIdx.x * 256u + tid;  // dword index within a column = 8 reads
     const bool live = t * 4u < col_stride;                 // never for the extra workgroup
-    JL_STAMP(1);
     uint32_t clean_keep = 0;   // bit 4r: read r of this lane is clean
     uint32_t gslot[8];         // global table slot of each clean read
 #pragma unroll
@@ -1243,7 +1222,6 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
         for (int r = 0; r < 8; ++r)
             if (t * 8u + r < n_reads) valid |= 1u << (4 * r);
     }
-    JL_STAMP(2);
     gap &= valid; het &= valid; par &= valid;
     const uint32_t dirty = gap | het | par;
     const uint32_t cleanm = valid & ~dirty;  // bit 4r: read r is clean
@@ -1317,7 +1295,6 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
             const uint32_t c = wave_sum_all(__popc(isdom[z]));
             if ((tid & 63u) == 0 && c) atomicAdd(&s_domcnt[z], c);
         }
-        JL_STAMP(3);
         // ---- 3. everything else through the LDS table
         uint32_t myslot[N][8];
 #pragma unroll
@@ -1346,7 +1323,6 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
             }
         }
         __syncthreads();
-        JL_STAMP(4);
         // One global insert per distinct key of the block, ALL AT ONCE: the keys are listed densely first, so thread i takes
         // the i-th (a sweep over the 1024 table slots, four per thread, made the thread that owned two occupied slots — and
         // thread 0, which also had the dominant key — do its inserts one after the other: 8.7 us of a 25 us launch at a
@@ -1416,7 +1392,6 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
         for (int r = 0; r < 8; ++r)
             if ((cleanm >> (4 * r)) & 1u) read_slot[t * 8u + r] = gslot[r];
     }
-    JL_STAMP(5);
     clean_keep = cleanm;
     }  // work
     if (!S.run) return;  // the generic pipeline has its own select launch
@@ -1438,7 +1413,6 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
     // list, the read-category counters, the compacted rows): no release fence — an L2 write-back per block serialises
     // in the L2.  Every wave drains its stores -> block barrier -> one lane: the arrival add; the last arriver reads
     // with agent-scope loads (past its L1).  The counter is zero before the first launch and the last arriver leaves it zero.
-    JL_STAMP(6);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0) {
@@ -1452,11 +1426,9 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
         s_last = last;
     }
     __syncthreads();
-    JL_STAMP(7);
     const bool last = s_last != 0;
     if (!last && !S.fold) return;
     if (last) {
-        JL_STAMP(8);
         uint32_t nv = 0, seq_before = 0;
         const bool fast_export = work && S.exp_count != nullptr;
         // the selection's first loads go out beside those of the read categories (the list entry is used below the count only)
@@ -1493,17 +1465,13 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
                 __hip_atomic_store(&meta->summary.marginal_partial, s_cat[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
-        JL_STAMP(9);
         if (fast_export) {
             phase_export_fast<KW>(w, vp, s_cat, &s_running, tw);
-            JL_STAMP(10);
             // every wave's stores (the groups may lie in host memory) are performed; ONE system-scope release, carried by
             // the completion word's store, pushes them out in front of it: data and word leave the same workgroup
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
-            JL_STAMP(11);
             if (S.seq_host && tid == 0) jl_signal_done_from(seq_before, S.seq_dev, S.seq_host);
-            JL_STAMP(12);
             return;
         }
         bool done = false;
@@ -1513,7 +1481,6 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
                                         &sel_bits, [&](uint32_t bits) {
                                             if (!S.fold) return;
                                             if (tid == 0) __hip_atomic_store(S.flag, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                            JL_STAMP(19);
                                             write_ids(bits);
                                             ids_written = true;
                                         });
@@ -1572,7 +1539,6 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
             s_idbits = bits;
             if (!ids_written) {     // (the selection out of LDS released them as soon as it had ranked)
                 __hip_atomic_store(S.flag, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                JL_STAMP(19);
             }
         }
         __syncthreads();
@@ -1601,7 +1567,6 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
 #endif
             s_idbits = bits;   // 0: timed out
         }
-        JL_STAMP(20);
         __syncthreads();
     }
     // ---- per-read haplotype ids of this workgroup's own reads, straight from the slots still in registers
@@ -1610,7 +1575,6 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
     // counter) for the next launch and, when this launch ends a run, stores the completion word behind all the ids.
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    JL_STAMP(21);
     if (tid == 0) {
         if (S.seq_host) __threadfence_system();   // this workgroup's ids leave its die's L2 before it arrives (see above)
         const uint32_t prev = __hip_atomic_fetch_add(S.arrive2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1626,7 +1590,6 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
                 __hip_atomic_store(&pk->magic, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             if (S.seq_host) signal_done(S.seq_dev, S.seq_host);
-            JL_STAMP(22);
         }
     }
 }
@@ -1689,22 +1652,12 @@ __global__ __launch_bounds__(256) void phase_assign_group_kernel(jl_phase_group_
 
 }  // namespace
 
-#ifdef JL_EXP_STAMPS
-extern "C" __attribute__((visibility("default"))) int jl_debug_stamps(unsigned long long *out)
-{
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_stamps), sizeof(g_stamps)) == hipSuccess ? 0 : -2;
-}
-#endif
-
-#ifndef JL_ASSIGN_HOST_BLOCKS
-#define JL_ASSIGN_HOST_BLOCKS 128u
-#endif
 // workgroups per window of a launch that writes per-read ids (see jl_launch_assign_group)
 static uint32_t jl_assign_blocks(uint32_t n_win, uint32_t max_read_blocks, bool to_host)
 {
     if (!to_host) return max_read_blocks;   // ids that stay in HBM: one workgroup per 2048 reads
-    // to pinned host memory: JL_ASSIGN_HOST_BLOCKS workgroups in all (see jl_launch_assign_group)
-    const uint32_t cap = std::max(1u, JL_ASSIGN_HOST_BLOCKS / std::max(1u, n_win));
+    // to pinned host memory: 128 workgroups in all (see jl_launch_assign_group)
+    const uint32_t cap = std::max(1u, 128u / std::max(1u, n_win));
     return std::min<uint32_t>(cap, max_read_blocks);
 }
 
@@ -1749,7 +1702,7 @@ bool jl_fill_win_phase(jl_ctx *ctx, uint32_t min_reads, bool signal, uint32_t fo
     S.fold = fold ? 1u : 0u;
 #ifdef JL_TUNING
     // tests of the re-run: the waiting workgroups of a folded launch give up at once (as if they had not been resident together)
-    if (fold && getenv("JL_FORCE_FOLD_TIMEOUT")) S.fold = 2u;
+    if (fold && jl_env().force_fold_timeout) S.fold = 2u;
 #endif
     S.flag = ctx->d_sync + 4; S.arrive2 = ctx->d_sync + 3;
     S.read_hap = ctx->read_hap_out ? ctx->read_hap_out : ctx->d_read_hap;

@@ -374,18 +374,6 @@ __global__ __launch_bounds__(64) void guess_kernel(const uint8_t *__restrict__ p
     }
 }
 
-// Launch-shape switches exist for tuning builds only (make EXTRA=-DJL_TUNING); the shipped library reads no
-// environment variable on its launch paths.
-#ifdef JL_TUNING
-int env_int(const char *name, int dflt)
-{
-    const char *s = getenv(name);
-    return s && *s ? atoi(s) : dflt;
-}
-#else
-constexpr int env_int(const char *, int dflt) { return dflt; }
-#endif
-
 }  // namespace
 
 const char *jl_pileup_kernel_name(void) { return "pileup_planes_kernel"; }   // rocprofv3 prints the template arguments behind it
@@ -428,10 +416,8 @@ uint32_t jl_pileup_rsplit(jl_ctx *ctx)
     const uint32_t n_tiles = planes_tiles(ctx, false);
     const int per_cu = ctx->pileup_blocks_per_cu[planes_slot(ctx)];
     // long columns: several blocks per slot smooth the tail; short ones: exactly one resident wave of blocks
-    const uint32_t target = 256u * (uint32_t)per_cu * (uint32_t)env_int("JL_PILEUP_WAVES", n_tiles >= 64 ? 4 : 1);
+    const uint32_t target = 256u * (uint32_t)per_cu * (n_tiles >= 64 ? 4u : 1u);
     uint32_t rsplit = target / n_chunks;  // never more blocks than resident slots: a second wave costs more than it balances
-    const int forced = env_int("JL_PILEUP_RSPLIT", 0);
-    if (forced > 0) rsplit = (uint32_t)forced;
     if (rsplit > n_tiles) rsplit = n_tiles;
     if (rsplit < 1) rsplit = 1;
     if (rsplit > 65535u) rsplit = 65535u;
@@ -454,12 +440,8 @@ void jl_launch_pileup(jl_ctx *ctx, hipStream_t st)
 #undef JL_LAUNCH_PLANES
 }
 
-// (JL_NO_FOLD_CALL: the separate call launch instead, for A/B measurements; read once, like JL_NO_GRAPH)
-bool jl_fold_enabled(void)
-{
-    static const bool on = !getenv("JL_NO_FOLD_CALL");
-    return on;
-}
+// (JL_NO_FOLD_CALL, one of the four environment switches of jl_internal.h: the separate call launch instead, for A/B measurements)
+bool jl_fold_enabled(void) { return !jl_env().no_fold_call; }
 bool jl_pileup_can_fold(jl_ctx *ctx) { return jl_fold_enabled() && ctx->P != 0 && jl_pileup_rsplit(ctx) == 1u; }
 
 void jl_fill_win_fold(jl_ctx *ctx, const jl_win_call *call, jl_win_fold *f)

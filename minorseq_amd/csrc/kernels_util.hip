@@ -4,6 +4,7 @@
 //   pack_rows_kernel          by-row uint8 codes (jl_msa_pack_rows)
 //   nibbles_to_planes_kernel  the interchange format of jl_msa_upload, validated on the way (planes_to_nibbles_kernel: jl_msa_download)
 //   (aligned BAM records: kernels_ingest.hip)
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -279,21 +280,21 @@ void jl_launch_clock(jl_ctx *ctx, hipStream_t st, uint32_t which)
     hipLaunchKernelGGL(clock_kernel, dim3(1), dim3(1), 0, st, reinterpret_cast<volatile unsigned long long *>(const_cast<uint32_t *>(ctx->h_seq) + 8u + 2u * which));
 }
 
+const jl_env_switches &jl_env()
+{
+    static const jl_env_switches e = [] {
+        jl_env_switches v = {};
+        v.no_fold_call = getenv("JL_NO_FOLD_CALL") != nullptr;
+        v.no_graph = getenv("JL_NO_GRAPH") != nullptr;
+        const char *staged = getenv("JL_EXCHANGE_STAGED");
+        v.exchange_staged = staged && staged[0] == '1';
 #ifdef JL_TUNING
-// tuning aid (JL_TIMELINE=1): a one-thread node that records the device's constant-rate clock between the stages of
-// a run, row = runs completed so far; read back with jl_debug_timeline (tools_tuning/timeline.py)
-__global__ void stamp_kernel(const uint32_t *__restrict__ seq_dev, uint64_t *__restrict__ tl, uint32_t slot)
-{
-    tl[(uint64_t)(*seq_dev % JL_TIMELINE_ROWS) * JL_TIMELINE_SLOTS + slot] = wall_clock64();
-}
-void jl_launch_stamp(jl_ctx *ctx, uint32_t slot)
-{
-    if (!ctx->d_timeline) return;
-    hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_sync, ctx->d_timeline, slot);
-}
-#else
-void jl_launch_stamp(jl_ctx *, uint32_t) {}
+        v.force_fold_timeout = getenv("JL_FORCE_FOLD_TIMEOUT") != nullptr;
 #endif
+        return v;
+    }();
+    return e;
+}
 
 void jl_launch_consensus(jl_ctx *ctx, uint8_t *d_out)
 {

@@ -1239,6 +1239,41 @@ def test_device_ingest_in_chunks(jl, chunk, hints):
     assert (msa.unpack_columns(jl.download_columns(), n) == rows).all()
 
 
+def test_records_append_checks_every_offset_before_reading_cigars(jl):
+    """A chunk whose last offset decreases is refused before any cigar is read: read 0 claims 100 ops (enough for the host's
+    long-read scan to look at them) while the cigar array ends at cig_off[2] = 10 words, right in front of a page that may not
+    be read.  The scan reading read 0's ops before the offsets behind them were checked would fault here."""
+    import ctypes as C
+    import mmap
+    libc = C.CDLL(None, use_errno=True)
+    libc.mmap.restype = C.c_void_p
+    libc.mmap.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_long]
+    libc.mprotect.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
+    libc.munmap.argtypes = [C.c_void_p, C.c_size_t]
+    ps = mmap.PAGESIZE
+    base = libc.mmap(None, 2 * ps, mmap.PROT_READ | mmap.PROT_WRITE, mmap.MAP_PRIVATE | mmap.MAP_ANONYMOUS, -1, 0)
+    assert base not in (None, C.c_void_p(-1).value)
+    try:
+        assert libc.mprotect(base + ps, ps, 0) == 0          # PROT_NONE
+        n_words = 10
+        cigar = np.ctypeslib.as_array((C.c_uint32 * n_words).from_address(base + ps - 4 * n_words))
+        cigar[:] = (5 << 4) | 7                                  # 5 '=' each
+        cig_off = np.array([0, 100, n_words], dtype=np.uint64)   # read 0: 100 ops; read 1 ends in front of where it begins
+        pos = np.zeros(2, dtype=np.int32)
+        seq4 = np.full(64, 0x12, dtype=np.uint8)
+        seq_off = np.array([0, 25, 50], dtype=np.uint64)
+        jl._chk(jl.lib.jl_records_begin(jl.h, 2, n_words, 64, 0))
+        with pytest.raises(capi.JulietError) as err:
+            jl._chk(jl.lib.jl_records_append(jl.h, 2, capi._p(pos), C.c_void_p(base + ps - 4 * n_words), capi._p(cig_off),
+                                             capi._p(seq4), capi._p(seq_off), None, None))
+        assert err.value.status == -1 and "record 1: offsets must not decrease" in str(err.value)      # JL_ERR_ARG
+    finally:
+        libc.munmap(base, 2 * ps)
+    with pytest.raises(capi.JulietError) as err:      # a refused append ends the stream: nothing to finish
+        jl._chk(jl.lib.jl_records_finish(jl.h, 10, 0, 0))
+    assert "before jl_records_begin" in str(err.value)
+
+
 def test_device_ingest_refuses_cigars_whose_lengths_wrap(jl):
     """Untrusted records through the C ABI: four insertions of 2^28 - 1 bases, a hundred matches and twelve more
     insertions sum to 84 modulo 2^32 — below the hundred bases the record holds — while the run of matches sits at query offset

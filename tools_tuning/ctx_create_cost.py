@@ -1,5 +1,5 @@
 """jl_ctx_create behind an initialised runtime (torch has created its context; no host-to-device copy yet): its own time, then the
-first large pageable upload.  With JL_LIB = a -DJL_TUNING build and JL_CTX_TIMES=1 the library prints its steps."""
+first large pageable upload."""
 import os
 import sys
 import time

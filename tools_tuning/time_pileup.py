@@ -1,4 +1,4 @@
-"""Time the pileup kernel alone (HIP events, jl_time_pileup) for a window shape; env JL_PILEUP_* select variants."""
+"""Time the pileup kernel alone (HIP events, jl_time_pileup) for a window shape."""
 import os
 import sys
 
