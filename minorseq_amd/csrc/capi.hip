@@ -986,8 +986,19 @@ int jl_variant_table_device(jl_ctx *ctx, void **d_rows, void **d_count, uint32_t
 
 /* ---------------------------------------------------------------- phase */
 
-static int reserve_phase(jl_ctx *ctx, uint32_t kwords_needed)
+// The form phasing vp positions needs, from `from` on (never a smaller one): up to 10 positions keep it; 11..20 take the
+// two-word fused launch when coming from the one-word one and `two_word_ok`; anything else the multi-word pipeline.
+static jl_phase_form phase_form_for(jl_phase_form from, uint32_t vp, bool two_word_ok)
 {
+    if (vp <= JL_POS_PER_WORD) return from;
+    if (vp <= 2u * JL_POS_PER_WORD && from == jl_phase_form::one_word && two_word_ok) return jl_phase_form::two_word;
+    return jl_phase_form::multi_word;
+}
+
+// the buffers of phasing in `form` (which the context takes on) with key words for kwords_needed * 10 positions
+static int reserve_phase(jl_ctx *ctx, jl_phase_form form, uint32_t kwords_needed)
+{
+    ctx->phase_form = form;
     const size_t reads_pad = (size_t)ctx->col_stride * 2;
     int rc;
     if (ctx->reads_capacity < reads_pad) {
@@ -1011,7 +1022,7 @@ static int reserve_phase(jl_ctx *ctx, uint32_t kwords_needed)
         ctx->reads_capacity = reads_pad;
         ctx->keys_capacity = 0;
     }
-    if (ctx->phase_two && ctx->two_slots != ctx->table_slots) {   // the two-word fused launch numbers its half keys here
+    if (form == jl_phase_form::two_word && ctx->two_slots != ctx->table_slots) {   // the two-word fused launch numbers its half keys here
         void *old[] = {ctx->d_slot_key_a, ctx->d_slot_key_b, ctx->d_occ_a, ctx->d_occ_b};
         for (void *p : old)
             if (p) hipFree(p);
@@ -1086,7 +1097,7 @@ static int phase_async_impl(jl_ctx *ctx, const jl_variant *variants, uint32_t n_
         kwords = ctx->keys_words > 4 ? ctx->keys_words : 4;
     }
     if (kwords == 0) kwords = 1;
-    int rc = reserve_phase(ctx, kwords);
+    int rc = reserve_phase(ctx, ctx->phase_form, kwords);
     if (rc) return rc;
     if (exporting && (rc = reserve_export(ctx, kwords))) return rc;
     ctx->phase_export = exporting;
@@ -1097,7 +1108,7 @@ static int phase_async_impl(jl_ctx *ctx, const jl_variant *variants, uint32_t n_
     ctx->last_min_reads = min_reads;
     ctx->pack_mirror = nullptr;
     ctx->read_hap_out = nullptr;
-    jl_launch_phase(ctx, ctx->stream, min_reads, false, false, false);
+    jl_launch_phase(ctx, ctx->stream, min_reads, jl_phase_plan::plan_kernel, false);
     JL_HIP(ctx, hipGetLastError());
     ctx->phase_done = true;
     ctx->pack_valid = false;
@@ -1155,6 +1166,9 @@ static int fetch_ids(jl_ctx *ctx, uint32_t bits, uint16_t *read_hap)
     return JL_OK;
 }
 
+// a folded phase launch of this context timed out: it stays unfolded, and its captured graphs, which fold, are stale
+static void phase_unfold(jl_ctx *ctx) { ctx->no_fold = true; ctx->fold_reruns++; ctx->alloc_version++; }
+
 // Waits for the last phase launch and reads its scalars; a launch that found more variant positions than its kernels
 // or its key buffer cover is run again with what it needs (the variant table is resident).
 static int phase_settle(jl_ctx *ctx, jl_phase_meta *out)
@@ -1164,37 +1178,23 @@ static int phase_settle(jl_ctx *ctx, jl_phase_meta *out)
     jl_phase_meta meta;
     JL_HIP(ctx, hipMemcpyAsync(&meta, ctx->d_meta, sizeof meta, hipMemcpyDeviceToHost, st));
     JL_HIP(ctx, hipStreamSynchronize(st));
-    if (meta.overflow & 12u) {
-        // more variant positions than the fused launch in use (bit 3) or the resident key buffer (bit 2) covers: up to 20
-        // positions take the two-word fused launch, more — or a result beyond its selection — the multi-word pipeline;
-        // grow the buffer if need be and run phasing again (the variant table is resident)
-        for (int attempt = 0; attempt < 3 && (meta.overflow & 12u); ++attempt) {
-            if (meta.vp_true > JL_POS_PER_WORD) {
-                if (meta.vp_true <= 2u * JL_POS_PER_WORD && !ctx->phase_two && !ctx->phase_generic && !ctx->phase_export) ctx->phase_two = true;
-                else ctx->phase_generic = true;
-            }
-            const uint32_t kw = (meta.vp_true + JL_POS_PER_WORD - 1) / JL_POS_PER_WORD;
-            int rc = reserve_phase(ctx, kw);
-            if (rc == JL_OK && ctx->phase_export) rc = reserve_export(ctx, kw);
-            if (rc) return rc;
-            jl_launch_phase(ctx, st, ctx->last_min_reads, false, false, false);
-            JL_HIP(ctx, hipGetLastError());
-            JL_HIP(ctx, hipMemcpyAsync(&meta, ctx->d_meta, sizeof meta, hipMemcpyDeviceToHost, st));
-            JL_HIP(ctx, hipStreamSynchronize(st));
-        }
-    }
-    if (meta.overflow & 32u) {
-        // A workgroup of the folded launch gave up waiting for the selection (the launch's workgroups were not resident
-        // together): some reads have no id.  The stage runs again with the ids in a launch of their own — transparently;
-        // this context stays unfolded from now on.
-        ctx->no_fold = true;
-        ctx->fold_reruns++;
-        ctx->alloc_version++;
-        jl_launch_phase(ctx, st, ctx->last_min_reads, false, false, false);
+    for (int attempt = 0; attempt < 3 && (meta.overflow & (JL_PHASE_OVF_FORM | JL_PHASE_OVF_KEY_WORDS)); ++attempt) {
+        const uint32_t kw = (meta.vp_true + JL_POS_PER_WORD - 1) / JL_POS_PER_WORD;
+        int rc = reserve_phase(ctx, phase_form_for(ctx->phase_form, meta.vp_true, !ctx->phase_export), kw);
+        if (rc == JL_OK && ctx->phase_export) rc = reserve_export(ctx, kw);
+        if (rc) return rc;
+        jl_launch_phase(ctx, st, ctx->last_min_reads, jl_phase_plan::plan_kernel, false);
         JL_HIP(ctx, hipGetLastError());
         JL_HIP(ctx, hipMemcpyAsync(&meta, ctx->d_meta, sizeof meta, hipMemcpyDeviceToHost, st));
         JL_HIP(ctx, hipStreamSynchronize(st));
-        if (meta.overflow & 32u) return jl_fail(ctx, JL_ERR_DEVICE, "the unfolded phase launch reports a time-out");
+    }
+    if (meta.overflow & JL_PHASE_OVF_FOLD_TIMEOUT) {
+        phase_unfold(ctx);   // the stage again, transparently, the ids in a launch of their own
+        jl_launch_phase(ctx, st, ctx->last_min_reads, jl_phase_plan::plan_kernel, false);
+        JL_HIP(ctx, hipGetLastError());
+        JL_HIP(ctx, hipMemcpyAsync(&meta, ctx->d_meta, sizeof meta, hipMemcpyDeviceToHost, st));
+        JL_HIP(ctx, hipStreamSynchronize(st));
+        if (meta.overflow & JL_PHASE_OVF_FOLD_TIMEOUT) return jl_fail(ctx, JL_ERR_DEVICE, "the unfolded phase launch reports a time-out");
     }
     *out = meta;
     return JL_OK;
@@ -1255,7 +1255,7 @@ int jl_phase_fetch(jl_ctx *ctx, jl_phase_summary *summary, uint32_t *pos_cols, u
     }
     JL_HIP(ctx, hipStreamSynchronize(st));
     for (uint32_t h = 0; h < H && !flat_pat.empty(); ++h) memcpy(hap_pattern + (size_t)h * cap_var, flat_pat.data() + (size_t)h * JL_VARIANT_CAP, vp);
-    if (meta.overflow & 1u) return jl_fail(ctx, JL_ERR_OVERFLOW, "more than %u haplotype candidates", JL_CAND_CAP);
+    if (meta.overflow & JL_PHASE_OVF_CANDIDATES) return jl_fail(ctx, JL_ERR_OVERFLOW, "more than %u haplotype candidates", JL_CAND_CAP);
     return JL_OK;
 }
 
@@ -1270,7 +1270,7 @@ int jl_phase_groups_fetch(jl_ctx *ctx, uint8_t *patterns, uint32_t pattern_strid
     if (!ctx->phase_done || !ctx->phase_export) return jl_fail(ctx, JL_ERR_STATE, "jl_phase_groups_fetch needs jl_phase_groups_async first");
     jl_phase_meta meta;
     if (int rc = phase_settle(ctx, &meta)) return rc;
-    if (meta.overflow & 16u)
+    if (meta.overflow & JL_PHASE_OVF_EXPORT)
         return jl_fail(ctx, JL_ERR_OVERFLOW, "%u groups of reads, the export holds %u", meta.n_occupied, ctx->exp_cap);
     const uint32_t vp = meta.vp, ng = vp ? meta.n_occupied : 0u;
     *n_groups = ng;
@@ -1334,12 +1334,8 @@ int jl_phase_groups_prepare(jl_ctx *ctx, uint32_t vp)
     JL_HIP(ctx, hipSetDevice(ctx->device));
     int rc = reserve_columns(ctx);
     if (rc) return rc;
-    uint32_t kwords = (vp + JL_POS_PER_WORD - 1) / JL_POS_PER_WORD;
-    if (kwords == 0) kwords = 1;
-    // up to 10 positions one key word, up to 20 the two-word fused launch, more the multi-word pipeline
-    ctx->phase_two = vp > JL_POS_PER_WORD && vp <= 2u * JL_POS_PER_WORD;
-    ctx->phase_generic = vp > 2u * JL_POS_PER_WORD;
-    if ((rc = reserve_phase(ctx, kwords))) return rc;
+    const uint32_t kwords = std::max(1u, (vp + JL_POS_PER_WORD - 1) / JL_POS_PER_WORD);
+    if ((rc = reserve_phase(ctx, phase_form_for(jl_phase_form::one_word, vp, true), kwords))) return rc;
     ctx->direct.on = 0;
     ctx->phase_export = true;
     ctx->exp_known = false;
@@ -1419,13 +1415,13 @@ static void enqueue_path(jl_ctx *ctx, const jl_params *prm, double n_tests, bool
         // drained stores and a system-scope fence (no other die has written anything the host reads)
         jl_launch_compact(ctx, st, false, true, true);
         signaled = true;
-    } else if (ctx->phase_generic) {
+    } else if (ctx->phase_form == jl_phase_form::multi_word) {
         jl_launch_compact(ctx, st, true, false, false);
-        jl_launch_phase(ctx, st, min_reads, true, false, false);
+        jl_launch_phase(ctx, st, min_reads, jl_phase_plan::resident, false);
     } else {
         // (the completion word by a node of its own here too: the fused launch storing it itself measured equal on one window
         // alone, 74.1 against 74.4 us, and no faster in the pipelined loop)
-        signaled = jl_launch_phase(ctx, st, min_reads, true, true, false);
+        signaled = jl_launch_phase(ctx, st, min_reads, jl_phase_plan::call_masks, false);
     }
     if (!signaled) jl_launch_done(ctx);
 }
@@ -1457,7 +1453,7 @@ int jl_run_prepare(jl_ctx *ctx, const jl_gene *genes, uint32_t n_genes, const ui
         JL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (phasing) {
-        if ((rc = reserve_phase(ctx, ctx->keys_words > 4 ? ctx->keys_words : 4))) return rc;   // (with the half-key tables once the context is in two-word mode)
+        if ((rc = reserve_phase(ctx, ctx->phase_form, ctx->keys_words > 4 ? ctx->keys_words : 4))) return rc;
         if (want_read_hap && ctx->h_read_hap_cap < (size_t)ctx->col_stride * 2) {
             if (ctx->h_read_hap) hipHostFree(ctx->h_read_hap);
             ctx->h_read_hap = nullptr;
@@ -1497,10 +1493,10 @@ int jl_run_async(jl_ctx *ctx, const jl_gene *genes, uint32_t n_genes, const uint
     }
 
     // signature of everything a captured graph bakes in
-    struct { uint64_t alloc, plan; jl_params prm; double n_tests; uint32_t drm, phasing, min_reads, rh, generic, pad; } sig;
+    struct { uint64_t alloc, plan; jl_params prm; double n_tests; uint32_t drm, phasing, min_reads, rh, form, pad; } sig;
     memset(&sig, 0, sizeof sig);
     sig.alloc = ctx->alloc_version; sig.plan = ctx->plan_version; sig.prm = *prm; sig.n_tests = n_tests;
-    sig.drm = drm_masks != nullptr; sig.phasing = phasing != 0; sig.min_reads = min_reads; sig.rh = want_read_hap != 0; sig.generic = (ctx->phase_generic ? 1u : 0u) | (ctx->phase_two ? 2u : 0u); sig.pad = (uint32_t)(uintptr_t)ctx->read_hap_out;
+    sig.drm = drm_masks != nullptr; sig.phasing = phasing != 0; sig.min_reads = min_reads; sig.rh = want_read_hap != 0; sig.form = (uint32_t)ctx->phase_form; sig.pad = (uint32_t)(uintptr_t)ctx->read_hap_out;
     const bool graphs_on = !jl_env().no_graph;   // (eager launches are a debugging aid)
     bool launched = false;
     // A graph replay reaches the queue 10-16 us after the call, a plain launch 3-5 us (MI355X guide, graph-replay-floor);
@@ -1538,12 +1534,8 @@ int jl_run_async(jl_ctx *ctx, const jl_gene *genes, uint32_t n_genes, const uint
         enqueue_path(ctx, prm, n_tests, drm_masks != nullptr, phasing != 0, min_reads, want_read_hap != 0);
         JL_HIP(ctx, hipGetLastError());
     }
-    ctx->runs_launched++;
+    jl_run_finish(ctx, phasing, want_read_hap);
     ctx->clock_run = ctx->pileup_clock ? ctx->runs_launched : 0u;   // (the run whose pileup the two clock nodes bracket)
-    ctx->pileup_done = ctx->call_done = true;
-    ctx->phase_done = phasing != 0;
-    ctx->pack_valid = true;
-    ctx->run_read_hap = phasing && want_read_hap;
     return JL_OK;
 }
 
@@ -1589,15 +1581,13 @@ int jl_phase_rerun_unfolded(jl_ctx *ctx)
     uint32_t ovf = 0;
     JL_HIP(ctx, hipMemcpyAsync(&ovf, &ctx->d_meta->overflow, 4, hipMemcpyDeviceToHost, st));
     JL_HIP(ctx, hipStreamSynchronize(st));
-    if (!(ovf & 32u)) return jl_fail(ctx, JL_ERR_DEVICE, "the run's result block was not written (no folded launch timed out)");
-    ctx->no_fold = true;
-    ctx->fold_reruns++;
-    ctx->alloc_version++;   // captured graphs of this context folded
+    if (!(ovf & JL_PHASE_OVF_FOLD_TIMEOUT)) return jl_fail(ctx, JL_ERR_DEVICE, "the run's result block was not written (no folded launch timed out)");
+    phase_unfold(ctx);
     // the Fisher stage's masks and rows are resident: the plan comes out of them again, the ids from phase_assign_kernel,
     // the completion word from a node of its own (only the fused launches fold, so the run is one of theirs).  The run
     // counters are the Fisher launch's to zero (call_kernel): here a memset stands in for it.
     JL_HIP(ctx, hipMemsetAsync(ctx->d_meta, 0, sizeof(jl_phase_meta), st));
-    jl_launch_phase(ctx, st, ctx->last_min_reads, true, true, false);
+    jl_launch_phase(ctx, st, ctx->last_min_reads, jl_phase_plan::call_masks, false);
     jl_launch_done_on(ctx, st);
     JL_HIP(ctx, hipGetLastError());
     ctx->runs_launched++;

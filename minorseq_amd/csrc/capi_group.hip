@@ -247,7 +247,7 @@ int jl_group_run_masked_async(jl_group *g, const jl_gene *genes, uint32_t n_gene
         if (rc) return group_fail(g, rc, jl_last_error(c));
         // a group run reads what the window's own stream wrote (uploads, ingest): that stream must be idle
         if (hipStreamSynchronize(c->stream) != hipSuccess) return group_fail(g, JL_ERR_DEVICE, "context stream failed");
-        if (phasing && (c->phase_generic || c->phase_two))
+        if (phasing && c->phase_form != jl_phase_form::one_word)
             return group_fail(g, JL_ERR_ARG, "a window needs the two-word or the multi-word phasing pipeline: run it with jl_run_async");
     }
     // signature: anything that changes an argument block or the launch shapes
@@ -293,7 +293,7 @@ int jl_group_run_masked_async(jl_group *g, const jl_gene *genes, uint32_t n_gene
                 jl_fill_win_call(x, prm, n_tests[k], drm_masks && drm_masks[k], phasing != 0, &g->h_call[k]);
                 jl_fill_win_fold(x, &g->h_call[k], &g->h_fold[k]);
                 jl_fill_win_compact(x, false, true, false, &g->h_compact[k]);
-                jl_fill_win_phase(x, min_reads, false, c.fold ? 0xFFFFFFFFu : 0u, true, &g->h_phase[k]);
+                jl_fill_win_phase(x, min_reads, false, c.fold ? 0xFFFFFFFFu : 0u, jl_phase_plan::call_masks, &g->h_phase[k]);
                 c.max_chunks = std::max(c.max_chunks, g->h_pile[k].n_chunks);
                 c.max_call_blocks = std::max(c.max_call_blocks, g->h_call[k].n_blocks);
                 c.max_phase_blocks = std::max(c.max_phase_blocks, g->h_phase[k].n_blocks);

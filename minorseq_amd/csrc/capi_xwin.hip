@@ -769,7 +769,7 @@ int jl_xwin_phase_sharded(jl_xwin *x, uint32_t min_reads, jl_xwin_result *out)
         if (x->n_mine) {
             // the selection of this launch ends a "run" of pc when nothing else follows on the device (no gather): its
             // last workgroup stores the completion word behind the exported block
-            jl_launch_phase(pc, pc->stream, 0xFFFFFFFFu, true, false, !collective);
+            jl_launch_phase(pc, pc->stream, 0xFFFFFFFFu, jl_phase_plan::resident, !collective);
             if (hipGetLastError() != hipSuccess) return xs_fail(x, JL_ERR_DEVICE, "phase launch failed");
             if (!collective) {
                 pc->runs_launched++;

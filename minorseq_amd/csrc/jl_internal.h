@@ -40,13 +40,18 @@ const jl_env_switches &jl_env();
 #define JL_REF_MAJORITY 0xFFu
 #define JL_REF_SKIP 0xFEu
 
+constexpr uint32_t JL_PHASE_OVF_CANDIDATES = 1u;     // more than JL_CAND_CAP haplotype candidates
+constexpr uint32_t JL_PHASE_OVF_HAPLOTYPES = 2u;     // more than JL_MAX_HAPLOTYPES qualified
+constexpr uint32_t JL_PHASE_OVF_KEY_WORDS = 4u;      // the key buffer was too small for vp_true positions
+constexpr uint32_t JL_PHASE_OVF_FORM = 8u;           // more positions, or a larger result, than the fused launch in use covers
+constexpr uint32_t JL_PHASE_OVF_EXPORT = 16u;        // an exporting run found more groups than its block holds
+constexpr uint32_t JL_PHASE_OVF_FOLD_TIMEOUT = 32u;  // a workgroup of a folded launch gave up waiting: some reads have no id
 struct jl_phase_meta {  // device-resident scalars of one phasing run
     uint32_t n_var;     // rows used
     uint32_t vp;        // distinct variant columns
     uint32_t kwords;    // 64-bit words per read key
     uint32_t n_occupied;
-    uint32_t overflow;  // bit0: more than JL_CAND_CAP candidates; bit1: more than JL_MAX_HAPLOTYPES qualified;
-                        // bit2: the key buffer was too small for vp_true positions (phasing skipped, host re-runs)
+    uint32_t overflow;  // JL_PHASE_OVF_* (KEY_WORDS, FORM: phasing was skipped, the fetch calls re-run it with what it needs)
     uint32_t vp_true;   // distinct variant columns before the capacity check
     uint32_t id_bits;   // width of the per-read ids the run wrote: 4, 8 or 16 (see JL_ID_* below)
     uint32_t pad_;
@@ -307,6 +312,17 @@ struct jl_records {
     bool maybe_long = false;
 };
 
+enum class jl_phase_form : uint32_t {   // the pipeline that phases a context; the value is the plan's fast_only (phase_plan.h)
+    multi_word = 0,   // more than 20 positions, or a result beyond the fused selection: keys, group, select, assign launches
+    one_word = 1,     // up to 10 positions: phase_fused1_kernel (phase_group_run_kernel in a group run)
+    two_word = 2,     // 11..20 positions: phase_fused2_kernel (jl_two_word)
+};
+enum class jl_phase_plan {   // where jl_launch_phase finds the plan (meta, vpcols)
+    plan_kernel,   // the stand-alone plan kernel runs first, from the resident variant table (stage API, re-runs)
+    resident,      // a compact launch or the cross-window session wrote it already
+    call_masks,    // the fused launch derives it from the Fisher stage's call masks (whole-path runs)
+};
+
 struct jl_ctx {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -427,12 +443,10 @@ struct jl_ctx {
     uint32_t *d_cooc = nullptr;        // [cooc_cap][cooc_cap]
     uint32_t cooc_cap = 256;
     bool phase_done = false;
-    bool no_fold = false;        // a folded phase launch of this context timed out once (its workgroups were not resident together):
-                                 // from then on the per-read ids come from a launch of their own (jl_phase_rerun_unfolded)
+    bool no_fold = false;        // a folded phase launch of this context timed out once: the ids take a launch of their own
     uint32_t fold_reruns = 0;    // how often that happened
-    bool phase_generic = false;  // multi-word pipeline selected (more than 20 positions, or results beyond the fused selection)
-    bool phase_two = false;      // 11..20 positions: the two-word fused launch (jl_two_word)
-    uint64_t *d_slot_key_a = nullptr, *d_slot_key_b = nullptr;   // its half-key tables [table slots]
+    jl_phase_form phase_form = jl_phase_form::one_word;   // only grows, except where a session sets it (jl_phase_groups_prepare)
+    uint64_t *d_slot_key_a = nullptr, *d_slot_key_b = nullptr;   // half-key tables of the two-word launch [table slots]
     uint32_t *d_occ_a = nullptr, *d_occ_b = nullptr;             // [reads_pad]
     uint64_t two_slots = 0;                                      // table size the half-key tables were made for
 
@@ -494,14 +508,14 @@ bool jl_pileup_needs_zero(jl_ctx *ctx);
 void jl_prepare_pileup(jl_ctx *ctx);
 void jl_launch_call(jl_ctx *ctx, hipStream_t st, const jl_params *prm, double n_tests, bool use_drm, bool with_meta);
 void jl_launch_compact(jl_ctx *ctx, hipStream_t st, bool plan, bool pack, bool signal);
-bool jl_launch_phase(jl_ctx *ctx, hipStream_t st, uint32_t min_reads, bool planned, bool from_called, bool signal);
+bool jl_launch_phase(jl_ctx *ctx, hipStream_t st, uint32_t min_reads, jl_phase_plan plan, bool signal);
 void jl_fill_call_args(jl_ctx *ctx, const jl_params *prm, double n_tests, jl_call_args *A);
 // group runs: fill one window's argument block / launch a stage once for `n_win` <= JL_GROUP_MAX windows (the blocks
 // travel by value in the kernel arguments)
 void jl_fill_win_pileup(jl_ctx *ctx, jl_win_pileup *w);
 void jl_fill_win_call(jl_ctx *ctx, const jl_params *prm, double n_tests, bool use_drm, bool with_meta, jl_win_call *w);
 void jl_fill_win_compact(jl_ctx *ctx, bool plan, bool pack, bool signal, jl_win_compact *w);
-bool jl_fill_win_phase(jl_ctx *ctx, uint32_t min_reads, bool signal, uint32_t fold_budget, bool from_called, jl_win_phase *w);
+bool jl_fill_win_phase(jl_ctx *ctx, uint32_t min_reads, bool signal, uint32_t fold_budget, jl_phase_plan plan, jl_win_phase *w);
 int jl_launch_pileup_group(jl_ctx *const *ctxs, uint32_t n_win, const jl_win_pileup *h_wins, uint32_t max_chunks, hipStream_t st);
 void jl_launch_call_group(const jl_win_call *h_wins, uint32_t n_win, uint32_t max_blocks, hipStream_t st);
 void jl_launch_compact_group(const jl_win_compact *h_wins, uint32_t n_win, hipStream_t st);
@@ -514,7 +528,7 @@ void jl_launch_nibbles_to_planes(jl_ctx *ctx, const uint8_t *d_nib, uint64_t nib
 void jl_launch_planes_to_nibbles(jl_ctx *ctx, uint8_t *d_nib, uint64_t nib_stride, uint32_t c0, uint32_t n);
 void jl_launch_done(jl_ctx *ctx);
 void jl_launch_done_on(jl_ctx *ctx, hipStream_t st);
-// a run whose folded phase launch gave up waiting (meta.overflow & 32): the phasing stage again, unfolded, behind everything
+// a run whose folded phase launch gave up waiting (JL_PHASE_OVF_FOLD_TIMEOUT): the phasing stage again, unfolded, behind everything
 // on the run's stream; blocks until it is done.  The call stage's results are still resident.
 extern "C" int jl_phase_rerun_unfolded(jl_ctx *ctx);
 void jl_launch_done_group(const jl_done_ent *d_ents, uint32_t n, hipStream_t st);

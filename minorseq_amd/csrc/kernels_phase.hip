@@ -289,7 +289,7 @@ __device__ __forceinline__ void phase_select_block(uint32_t min_reads, uint64_t 
         }
         __syncthreads();
         if (tid == 0) {
-            if (n_occ > exp_cap) meta->overflow |= 16u;
+            if (n_occ > exp_cap) meta->overflow |= JL_PHASE_OVF_EXPORT;
             meta->summary.reported_reads = 0;
             meta->summary.insufficient_reads = s_insufficient;   // clean reads: the merge decides which are reported
             meta->summary.n_haplotypes = 0;
@@ -319,7 +319,7 @@ __device__ __forceinline__ void phase_select_block(uint32_t min_reads, uint64_t 
     __syncthreads();
     uint32_t ncand = s_ncand;
     if (ncand > JL_CAND_CAP) {
-        if (tid == 0) meta->overflow |= 1u;
+        if (tid == 0) meta->overflow |= JL_PHASE_OVF_CANDIDATES;
         ncand = JL_CAND_CAP;
     }
     // `cache` (2 * JL_CAND_CAP words of LDS, the general launch has them): every candidate's count and representative
@@ -417,7 +417,7 @@ __device__ __forceinline__ void phase_select_block(uint32_t min_reads, uint64_t 
     __syncthreads();
     const uint32_t H = s_nhap;
     if (tid == 0) {
-        if (ncand > JL_MAX_HAPLOTYPES) meta->overflow |= 2u;
+        if (ncand > JL_MAX_HAPLOTYPES) meta->overflow |= JL_PHASE_OVF_HAPLOTYPES;
         meta->summary.reported_reads = s_reported;
         meta->summary.insufficient_reads = s_insufficient;
         meta->summary.n_haplotypes = H;
@@ -1022,7 +1022,7 @@ __device__ __forceinline__ void phase_export_fast(const jl_win_phase &w, uint32_
             S.exp_head[7] = total_clean;
         }
         // the run's scalars for the stage API (jl_phase_groups_fetch reads them from here)
-        if (n_occ > S.exp_cap) atomicOr(&meta->overflow, 16u);
+        if (n_occ > S.exp_cap) atomicOr(&meta->overflow, JL_PHASE_OVF_EXPORT);
         meta->summary.reported_reads = 0;
         meta->summary.insufficient_reads = total_clean;   // clean reads: the merge decides which are reported
         meta->summary.damaged_reads = cat[0];
@@ -1122,7 +1122,7 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
                 __hip_atomic_store(S.n_rows_out, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 const uint32_t need_kw = (vpt + JL_POS_PER_WORD - 1u) / JL_POS_PER_WORD;
                 uint32_t ovf = 0;
-                if (!work && (vpt != 0u || s_plan.ovf)) ovf = (s_plan.ovf || need_kw <= S.kwords_cap) ? 8u : 4u;
+                if (!work && (vpt != 0u || s_plan.ovf)) ovf = (s_plan.ovf || need_kw <= S.kwords_cap) ? JL_PHASE_OVF_FORM : JL_PHASE_OVF_KEY_WORDS;
                 __hip_atomic_store(&meta->n_var, n < S.cap ? n : S.cap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(&meta->vp_true, s_plan.ovf ? JL_POS_PER_WORD + 1u : vpt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(&meta->vp, vp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1499,7 +1499,7 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
                 }
                 two_word_cleanup(*tw);
                 if (tid == 0) {
-                    __hip_atomic_store(&meta->overflow, 8u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(&meta->overflow, JL_PHASE_OVF_FORM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     __hip_atomic_store(&meta->vp_true, 2u * JL_POS_PER_WORD + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     __hip_atomic_store(&meta->vp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     __hip_atomic_store(&meta->kwords, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1553,14 +1553,14 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
             while ((bits = __hip_atomic_load(S.flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0u) {
                 __builtin_amdgcn_s_sleep(8);
                 if (++spins > (1u << 23)) {
-                    atomicOr(&meta->overflow, 32u);
+                    atomicOr(&meta->overflow, JL_PHASE_OVF_FOLD_TIMEOUT);
                     if (S.mirror) __hip_atomic_store(&S.mirror->magic, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                     break;
                 }
             }
 #ifdef JL_TUNING
             if (S.fold == 2u && bits != 0u) {   // forced: behave as if the wait had run out just before the selection arrived
-                atomicOr(&meta->overflow, 32u);
+                atomicOr(&meta->overflow, JL_PHASE_OVF_FOLD_TIMEOUT);
                 if (S.mirror) __hip_atomic_store(&S.mirror->magic, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 bits = 0u;
             }
@@ -1584,7 +1584,7 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
             // A workgroup that gave up waiting marked the run failed; a selection that was only LATE has since written a
             // valid result block over that mark.  The mark in the run's scalars is the lasting one: whoever arrives last
             // makes the blocks say so again, just before the completion word.
-            if (ld_coherent(&meta->overflow) & 32u) {
+            if (ld_coherent(&meta->overflow) & JL_PHASE_OVF_FOLD_TIMEOUT) {
                 if (S.mirror) __hip_atomic_store(&S.mirror->magic, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 jl_pack *pk = S.pk + (__hip_atomic_load(S.seq_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1u);
                 __hip_atomic_store(&pk->magic, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1661,14 +1661,13 @@ static uint32_t jl_assign_blocks(uint32_t n_win, uint32_t max_read_blocks, bool 
     return std::min<uint32_t>(cap, max_read_blocks);
 }
 
-// Argument block of the fused phase launch for one window.  `from_called`: the plan comes out of the call masks of
-// the Fisher stage (whole-path runs); otherwise meta / vpcols hold it already.  `fold_budget`: workgroups that may
-// still be added to a launch whose members all wait for each other (the per-read ids are then written by the same
-// launch); returns whether this window folds.
-bool jl_fill_win_phase(jl_ctx *ctx, uint32_t min_reads, bool signal, uint32_t fold_budget, bool from_called, jl_win_phase *w)
+// Argument block of the fused phase launch for one window.  `plan`: call_masks, or the plan is in meta / vpcols already.
+// `fold_budget`: workgroups that may still be added to a launch whose members all wait for each other (the per-read ids
+// are then written by the same launch); returns whether this window folds.
+bool jl_fill_win_phase(jl_ctx *ctx, uint32_t min_reads, bool signal, uint32_t fold_budget, jl_phase_plan plan, jl_win_phase *w)
 {
     memset(w, 0, sizeof *w);
-    const bool generic = ctx->phase_generic;
+    const bool generic = ctx->phase_form == jl_phase_form::multi_word;
     const bool ids_to_host = ctx->read_hap_out != nullptr;
     const bool signal_select = signal && !ids_to_host;   // no ids wanted on the host: the selection ends the run
     const uint32_t n_dwords = (uint32_t)(ctx->col_stride / 4u);
@@ -1707,7 +1706,7 @@ bool jl_fill_win_phase(jl_ctx *ctx, uint32_t min_reads, bool signal, uint32_t fo
     S.flag = ctx->d_sync + 4; S.arrive2 = ctx->d_sync + 3;
     S.read_hap = ctx->read_hap_out ? ctx->read_hap_out : ctx->d_read_hap;
     S.seq_host = (fold ? signal : signal_select) ? ctx->h_seq : nullptr;
-    if (from_called && !generic) {
+    if (plan == jl_phase_plan::call_masks) {
         S.called = ctx->d_called; S.staged = ctx->d_staged; S.pos_col = ctx->d_pos_col; S.rows = ctx->d_variants;
         S.n_rows_out = ctx->d_nvar; S.vpcols_out = ctx->d_vpcols; S.col2pos_out = ctx->d_col2pos;
         S.P = ctx->P; S.cap = JL_VARIANT_CAP; S.kwords_cap = ctx->keys_words;
@@ -1715,50 +1714,46 @@ bool jl_fill_win_phase(jl_ctx *ctx, uint32_t min_reads, bool signal, uint32_t fo
     return fold;
 }
 
-// The phasing launches behind a plan.  `from_called`: whole-path run, the Fisher stage left call masks (ignored by the
-// multi-word pipeline, whose plan a compact launch made); otherwise the stand-alone plan kernel runs here when
-// `planned` is false.  ctx->phase_generic selects the multi-word pipeline; the default runs only the single-word
-// (Vp <= 10) kernel, whose last block also does the selection, and flags inputs that need more (jl_phase_fetch then
-// switches and re-runs).  `signal`: this launch ends a jl_run_async — its last kernel stores the completion word.
-// Returns whether the launches store the run's completion word themselves (otherwise the caller adds done_kernel).
-bool jl_launch_phase(jl_ctx *ctx, hipStream_t st, uint32_t min_reads, bool planned, bool from_called, bool signal)
+// The phasing launches of ctx->phase_form (the fused ones flag inputs that need a larger form: JL_PHASE_OVF_FORM).  `signal`:
+// this launch ends a jl_run_async.  Returns whether the launches store the run's completion word themselves (otherwise the
+// caller adds done_kernel).
+bool jl_launch_phase(jl_ctx *ctx, hipStream_t st, uint32_t min_reads, jl_phase_plan plan, bool signal)
 {
     const uint64_t reads_pad = ctx->col_stride * 2u;
-    const bool generic = ctx->phase_generic;
+    const bool generic = ctx->phase_form == jl_phase_form::multi_word;
     const bool ids_to_host = ctx->read_hap_out != nullptr;
     const bool signal_select = signal && !ids_to_host;
-    const bool two = ctx->phase_two && !generic;
-    if (!planned && !(from_called && !generic))
+    // only the fused launches read call masks: behind them the multi-word pipeline finds the plan its compact launch wrote
+    if (generic && plan == jl_phase_plan::call_masks) plan = jl_phase_plan::resident;
+    if (plan == jl_phase_plan::plan_kernel)
         hipLaunchKernelGGL(phase_plan_kernel, dim3(1), dim3(1024), 0, st, ctx->d_variants, ctx->d_nvar, JL_VARIANT_CAP,
                            ctx->n_cols, ctx->d_varcol, ctx->d_vpcols, ctx->d_col2pos, ctx->keys_words,
-                           generic ? 0u : (two ? 2u : 1u), ctx->d_meta);
+                           (uint32_t)ctx->phase_form, ctx->d_meta);
     const uint32_t n_dwords = (uint32_t)(ctx->col_stride / 4u);
-    const uint32_t rblocks = (uint32_t)((ctx->n_reads + 255u) / 256u);
-    if (generic)
+    jl_win_phase w;
+    const bool fold = jl_fill_win_phase(ctx, min_reads, signal, JL_FOLD_MAX_BLOCKS, plan, &w);
+    if (generic) {
         hipLaunchKernelGGL(phase_keys_kernel, dim3((n_dwords + 255u) / 256u), dim3(256), 0, st, ctx->d_msa,
                            ctx->plane_stride, ctx->n_reads, reads_pad, ctx->d_vpcols, ctx->d_meta, ctx->d_keys,
                            ctx->d_flagw);
-    jl_win_phase w;
-    const bool fold = jl_fill_win_phase(ctx, min_reads, signal, JL_FOLD_MAX_BLOCKS, from_called, &w);
-    // (the multi-word pipeline has its own keys / grouping / selection launches: the fused launch would find nothing to do)
-    if (!generic && ctx->direct.on && !w.S.called)
-        hipLaunchKernelGGL(phase_fused1_direct_kernel, dim3(w.n_blocks), dim3(256), 0, st, w, ctx->direct);
-    else if (two) {
-        jl_two_word tw;
-        tw.key_a = (unsigned long long *)ctx->d_slot_key_a; tw.key_b = (unsigned long long *)ctx->d_slot_key_b;
-        tw.occ_a = ctx->d_occ_a; tw.occ_b = ctx->d_occ_b; tw.n_occ = ctx->d_sync + 10;
-        hipLaunchKernelGGL(phase_fused2_kernel, dim3(w.n_blocks + (w.S.called ? 1u : 0u)), dim3(256), 0, st, w, tw);
-    } else if (!generic) hipLaunchKernelGGL(phase_fused1_kernel, dim3(w.n_blocks + (w.S.called ? 1u : 0u)), dim3(256), 0, st, w);
-    if (generic) {
-        hipLaunchKernelGGL(phase_group_kernel, dim3(rblocks), dim3(256), 0, st, ctx->n_reads, reads_pad, ctx->d_keys,
-                           ctx->d_flagw, ctx->d_meta, ctx->table_slots - 1u, ctx->d_slot_rep, ctx->d_slot_count,
-                           ctx->d_occupied, ctx->d_read_slot);
+        hipLaunchKernelGGL(phase_group_kernel, dim3((uint32_t)((ctx->n_reads + 255u) / 256u)), dim3(256), 0, st, ctx->n_reads,
+                           reads_pad, ctx->d_keys, ctx->d_flagw, ctx->d_meta, ctx->table_slots - 1u, ctx->d_slot_rep,
+                           ctx->d_slot_count, ctx->d_occupied, ctx->d_read_slot);
         hipLaunchKernelGGL(phase_select_kernel, dim3(1), dim3(1024), 0, st, min_reads, reads_pad, ctx->d_keys,
                            ctx->d_meta, ctx->d_slot_rep, ctx->d_slot_count, ctx->d_occupied, ctx->d_slot_hap,
                            ctx->d_variants, ctx->d_col2pos, ctx->n_cols, ctx->d_hap_count, ctx->d_hap_pattern, ctx->d_hit,
                            ctx->d_nvar, ctx->d_vpcols, ctx->d_cooc, ctx->cooc_cap, ctx->d_pack, ctx->pack_mirror,
                            (unsigned long long *)ctx->d_slot_key, ctx->d_sync, signal_select ? ctx->h_seq : nullptr,
                            w.S.exp_count, w.S.exp_pattern, w.S.exp_cap, w.S.exp_stride, w.S.exp_head);
+    } else if (ctx->direct.on && !w.S.called) {
+        hipLaunchKernelGGL(phase_fused1_direct_kernel, dim3(w.n_blocks), dim3(256), 0, st, w, ctx->direct);
+    } else if (ctx->phase_form == jl_phase_form::two_word) {
+        jl_two_word tw;
+        tw.key_a = (unsigned long long *)ctx->d_slot_key_a; tw.key_b = (unsigned long long *)ctx->d_slot_key_b;
+        tw.occ_a = ctx->d_occ_a; tw.occ_b = ctx->d_occ_b; tw.n_occ = ctx->d_sync + 10;
+        hipLaunchKernelGGL(phase_fused2_kernel, dim3(w.n_blocks + (w.S.called ? 1u : 0u)), dim3(256), 0, st, w, tw);
+    } else {
+        hipLaunchKernelGGL(phase_fused1_kernel, dim3(w.n_blocks + (w.S.called ? 1u : 0u)), dim3(256), 0, st, w);
     }
     if (fold) return signal;
     if (ctx->phase_export) return false;   // the ids wait for the merge (jl_phase_regroup)
