@@ -314,7 +314,8 @@ int jl_expand_read_hap(const void *packed, uint32_t bits, uint64_t n_reads, uint
 
 /*
  * Group runs: the whole path for SEVERAL (at most 32) resident windows (one context each, same device) in a few launches —
- * per stage ONE launch for up to eight windows (blockIdx.z = window): counting, the Fisher stage, phasing, per-read ids.  A 150 MB window is too short a stream to hide a launch's ramp and drain, and its phasing stage
+ * per stage ONE launch for up to eight windows (blockIdx.z = window): counting, the Fisher stage (in the counting launch's epilogue
+ * or as a launch of its own, chosen per run from what else the device has in flight: same results), phasing, per-read ids.  A 150 MB window is too short a stream to hide a launch's ramp and drain, and its phasing stage
  * is a latency chain that occupies a hardware queue while doing little; grouped, the pileup runs at the rate of one long
  * stream and the latency chains of all windows overlap.  Groups of more than eight windows are pipelined inside the
  * launch: the counting of the next eight runs beside the phasing of the previous eight.
@@ -337,13 +338,14 @@ int jl_group_run_async(jl_group *group, const jl_gene *genes, uint32_t n_genes, 
 int jl_group_run_masked_async(jl_group *group, const jl_gene *genes, uint32_t n_genes, const uint8_t *refseq,
                               uint32_t ref_len, const jl_params *prm, const uint64_t *const *drm_masks, int phasing,
                               uint32_t min_reads, int want_read_hap);
-/* Timing hook (bench): average device time in ms of the grouped pileup launch alone, `reps` back-to-back launches
- * rotating over `groups` (each must have run once); `bytes_per_launch` = algorithmic bytes of one launch of groups[0]: 3 bits per cell,
- * every cell read once. */
 /* The results of the last group run, one view per window (the group's context order): jl_run_view_get on every context in
  * ONE call — waits for each window's completion word in turn.  out[cap]; *n = the group's windows.  A window whose view
  * fails ends the call with its status (jl_group_last_error names it). */
 int jl_group_views(jl_group *group, jl_run_view *out, uint32_t cap, uint32_t *n);
+/* Timing hook (bench): average device time in ms of the grouped pileup launch alone — the plain counting kernel, without the
+ * Fisher stage a run may carry in its epilogue — `reps` back-to-back launches rotating over `groups` (each must have run once);
+ * `bytes_per_launch` = algorithmic bytes of one launch of groups[0]: 3 bits per cell, every cell read once.  No side effect on
+ * the groups' last runs: their results stay complete and fetchable. */
 int jl_group_time_pileup(jl_group *const *groups, uint32_t n_groups, uint32_t reps, float *ms_avg, uint64_t *bytes_per_launch);
 
 /* ---------------------------------------------------------------- numerics self-check */

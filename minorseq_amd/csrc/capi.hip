@@ -139,6 +139,7 @@ void *jl_ctx_stream(const jl_ctx *ctx) { return ctx ? (void *)ctx->stream : null
 void jl_ctx_destroy(jl_ctx *ctx)
 {
     if (!ctx) return;
+    jl_group_forget_ctx(ctx);   // (live groups read their windows' completion words: capi_group.hip)
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
     if (ctx->graph_exec) hipGraphExecDestroy(ctx->graph_exec);

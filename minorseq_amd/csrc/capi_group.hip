@@ -4,8 +4,8 @@
 // reaches 0.61 of the HBM peak, a 1.2 GB stream 0.77), and its phasing stage is a chain of dependent memory round
 // trips that keeps a hardware queue busy for tens of microseconds while doing almost nothing.  A group run gives each
 // stage ONE launch for up to JL_GROUP_MAX windows (blockIdx.z = window, per-window argument blocks by value):
-//   counting            pileup_planes_group_kernel (up to JL_GROUP_WINDOWS_MAX windows)
-//   Fisher              call_group_kernel
+//   counting            pileup_planes_group_kernel, or pileup_fold_group_kernel: the same with the Fisher stage in its epilogue
+//   Fisher              call_group_kernel, in the unfolded form only (see "Two forms" below)
 //   phasing             phase_group_run_kernel (plan out of the call masks, keys, grouping, selection, result block)
 //   per-read ids        phase_assign_group_kernel (small groups fold them into the phasing launch)
 //   completion words    done_group_kernel
@@ -15,9 +15,18 @@
 //
 // Results are per window, exactly those of jl_run_async on each context: every context keeps its own result block,
 // per-read ids and completion word, so jl_run_wait / jl_run_view_get / jl_call_fetch / jl_phase_fetch work unchanged.
+//
+// Two forms, chosen per launch (group_pick_form).  FOLDED: the Fisher stage rides in the pileup launch's epilogue — one launch
+// and one read-back of the histograms less in the tail, which is what a launch whose tail is exposed gains from.  UNFOLDED: plain
+// pileup + call_group_kernel — the pileup's workgroups leave as soon as they have counted, which is what a launch gains from
+// whose tail runs beside other launches' pileups anyway (the epilogue then only holds workgroup slots those pileups want).
+// Which of the two a tail is going to be is read off the completion words of the device's other group launches at enqueue
+// time: a few loads from pinned host memory, no HIP call.  Both forms share call_eval.h and give the same bits; a group
+// captures a graph per form (and exchange parity): both with the first launch of a configuration where both can be taken.
 #include <string.h>
 
 #include <algorithm>
+#include <mutex>
 #include <new>
 #include <string>
 #include <vector>
@@ -31,6 +40,12 @@
 #ifndef JL_COMM_TIMEOUT_S
 #define JL_COMM_TIMEOUT_S 60
 #endif
+// A group launch is FOLDED while fewer than this many other group launches of its device are incomplete at enqueue time
+// (0: never, a large value: always).  Measured, not guessed: the sweep is in profiles/ (DESIGN.md "What bounds a step").
+#ifndef JL_GROUP_FOLD_BELOW
+#define JL_GROUP_FOLD_BELOW 3u
+#endif
+enum { JL_FORM_FOLDED = 0, JL_FORM_UNFOLDED = 1 };
 
 struct jl_group {
     int device = -1;
@@ -49,11 +64,14 @@ struct jl_group {
     struct chunk_t { uint32_t first, n, max_chunks, max_call_blocks, max_phase_blocks; bool fold; };
     std::vector<chunk_t> chunks;
     bool phasing = true;
-    // one captured graph per parity of a bound exchange (the heads' destination is baked in); unbound: [0] only
-    hipGraph_t graph[2] = {nullptr, nullptr};
-    hipGraphExec_t graph_exec[2] = {nullptr, nullptr};
-    bool graph_tried[2] = {false, false};
-    std::vector<uint8_t> sig;   // everything the captured graph and the tables bake in
+    // one captured graph per parity of a bound exchange (the heads' destination is baked in; unbound: [0] only) and per form
+    hipGraph_t graph[2][2] = {};
+    hipGraphExec_t graph_exec[2][2] = {};
+    bool graph_tried[2][2] = {};
+    std::vector<uint8_t> sig;   // everything the captured graphs and the tables bake in (the form is the graphs' second index)
+    // the last launch, for the other groups' choice of form (under g_live_mu): each window's runs_launched behind it
+    bool fl_busy = false;
+    uint32_t fl_seq[JL_GROUP_WINDOWS_MAX];
     std::string err;
     // ---- bound exchange (jl_group_exchange_bind): every run carries the all-gather of its windows' table heads
     jl_comm *xc = nullptr;
@@ -72,11 +90,59 @@ struct jl_group {
 
 static void group_drop_graphs(jl_group *g)
 {
-    for (int p = 0; p < 2; ++p) {
-        if (g->graph_exec[p]) { hipGraphExecDestroy(g->graph_exec[p]); g->graph_exec[p] = nullptr; }
-        if (g->graph[p]) { hipGraphDestroy(g->graph[p]); g->graph[p] = nullptr; }
-        g->graph_tried[p] = false;
+    for (int p = 0; p < 2; ++p)
+        for (int f = 0; f < 2; ++f) {
+            if (g->graph_exec[p][f]) { hipGraphExecDestroy(g->graph_exec[p][f]); g->graph_exec[p][f] = nullptr; }
+            if (g->graph[p][f]) { hipGraphDestroy(g->graph[p][f]); g->graph[p][f] = nullptr; }
+            g->graph_tried[p][f] = false;
+        }
+}
+
+// ---- the live groups of the process, for the choice of form.  A group is in the list from jl_group_create to
+// jl_group_destroy; a context that is destroyed first takes the groups it is a window of out (jl_group_forget_ctx): nothing
+// here reads a completion word that has been freed.
+// (never destroyed: a context or a group may be closed while the process exits, after static destructors have run)
+static std::mutex &g_live_mu = *new std::mutex();
+static std::vector<jl_group *> &g_live = *new std::vector<jl_group *>();
+#ifdef JL_TUNING
+static uint64_t g_form_taken[2] = {0, 0};
+#endif
+
+// Group launches of g's device, other than g's own, that were incomplete a moment ago.  A launch is complete when every window's
+// pinned completion word has reached the run number the launch gave it.
+static uint32_t group_others_in_flight(const jl_group *g)
+{
+    uint32_t busy = 0;
+    for (jl_group *o : g_live) {
+        if (o == g || o->device != g->device || !o->fl_busy) continue;
+        bool done = true;
+        for (size_t k = 0; k < o->ctxs.size() && done; ++k)
+            done = (int32_t)(*o->ctxs[k]->h_seq - o->fl_seq[k]) >= 0;
+        if (done) o->fl_busy = false;
+        else ++busy;
     }
+    return busy;
+}
+
+// FOLDED while this launch's tail is likely to be exposed: few other launches to run beside.  JL_NO_FOLD_CALL: never.
+// *other_reachable: the form not taken now is one a later launch of this group can take (enough other groups on the device).
+static int group_pick_form(const jl_group *g, bool *other_reachable)
+{
+    *other_reachable = false;
+    if (!jl_fold_enabled()) return JL_FORM_UNFOLDED;
+    std::lock_guard<std::mutex> lk(g_live_mu);
+    uint32_t others = 0;
+    for (const jl_group *o : g_live) others += o != g && o->device == g->device;
+    *other_reachable = JL_GROUP_FOLD_BELOW > 0u && others >= JL_GROUP_FOLD_BELOW;
+    return group_others_in_flight(g) < JL_GROUP_FOLD_BELOW ? JL_FORM_FOLDED : JL_FORM_UNFOLDED;
+}
+
+void jl_group_forget_ctx(const jl_ctx *ctx)
+{
+    std::lock_guard<std::mutex> lk(g_live_mu);
+    for (size_t i = 0; i < g_live.size();)
+        if (std::find(g_live[i]->ctxs.begin(), g_live[i]->ctxs.end(), ctx) != g_live[i]->ctxs.end()) g_live.erase(g_live.begin() + i);
+        else ++i;
 }
 
 static int group_fail(jl_group *g, int status, const char *msg)
@@ -86,10 +152,11 @@ static int group_fail(jl_group *g, int status, const char *msg)
 }
 
 // the latency-bound stages of one chunk, on `st`
-static void chunk_tail(jl_group *g, const jl_group::chunk_t &c, hipStream_t st)
+static void chunk_tail(jl_group *g, const jl_group::chunk_t &c, int form, hipStream_t st)
 {
-    // (the Fisher stage ran in the pileup launch's epilogue: kernels_pileup.hip FOLD)
-    if (!jl_fold_enabled()) jl_launch_call_group(g->h_call.data() + c.first, c.n, c.max_call_blocks, st);
+    // (folded form: the Fisher stage ran in the pileup launch's epilogue, kernels_pileup.hip FOLD.  Whichever of the two runs
+    // first zeroes the window's run counters — the epilogue's block 0 or call_kernel's first block, never both)
+    if (form == JL_FORM_UNFOLDED) jl_launch_call_group(g->h_call.data() + c.first, c.n, c.max_call_blocks, st);
     if (!g->phasing) {
         jl_launch_compact_group(g->h_compact.data() + c.first, c.n, st);
     } else {
@@ -104,7 +171,7 @@ static void chunk_tail(jl_group *g, const jl_group::chunk_t &c, hipStream_t st)
     jl_launch_done_group(g->d_done + c.first, c.n, st);
 }
 
-static int group_enqueue(jl_group *g)
+static int group_enqueue(jl_group *g, int form)
 {
     for (jl_ctx *c : g->ctxs)
         if (!c->have_ref) jl_launch_guess(c, g->stream);   // majority-codon mode: seed bases per window
@@ -112,17 +179,17 @@ static int group_enqueue(jl_group *g)
     bool side_used[JL_GROUP_SIDE_STREAMS] = {false, false};
     for (size_t k = 0; k < nc; ++k) {
         const jl_group::chunk_t &c = g->chunks[k];
-        int rc = jl_fold_enabled() ? jl_launch_pileup_fold_group(g->ctxs.data() + c.first, c.n, g->h_pile.data() + c.first, g->h_fold.data() + c.first, c.max_chunks, g->stream)
+        int rc = form == JL_FORM_FOLDED ? jl_launch_pileup_fold_group(g->ctxs.data() + c.first, c.n, g->h_pile.data() + c.first, g->h_fold.data() + c.first, c.max_chunks, g->stream)
                                    : jl_launch_pileup_group(g->ctxs.data() + c.first, c.n, g->h_pile.data() + c.first, c.max_chunks, g->stream);
         if (rc) return rc;
         if (k + 1 < nc) {   // the tail runs beside the next chunk's pileup
             hipStream_t st = g->side[k % JL_GROUP_SIDE_STREAMS];
             if (hipEventRecord(g->ev_fork[k], g->stream) != hipSuccess || hipStreamWaitEvent(st, g->ev_fork[k], 0) != hipSuccess)
                 return JL_ERR_DEVICE;
-            chunk_tail(g, c, st);
+            chunk_tail(g, c, form, st);
             side_used[k % JL_GROUP_SIDE_STREAMS] = true;
         } else {
-            chunk_tail(g, c, g->stream);
+            chunk_tail(g, c, form, g->stream);
         }
     }
     for (int i = 0; i < JL_GROUP_SIDE_STREAMS; ++i)
@@ -167,6 +234,10 @@ int jl_group_create(jl_ctx *const *ctxs, uint32_t n_ctx, jl_group **out)
         jl_group_destroy(g);
         return JL_ERR_MEMORY;
     }
+    {
+        std::lock_guard<std::mutex> lk(g_live_mu);
+        g_live.push_back(g);
+    }
     *out = g;
     return JL_OK;
 }
@@ -174,6 +245,10 @@ int jl_group_create(jl_ctx *const *ctxs, uint32_t n_ctx, jl_group **out)
 void jl_group_destroy(jl_group *g)
 {
     if (!g) return;
+    {
+        std::lock_guard<std::mutex> lk(g_live_mu);
+        g_live.erase(std::remove(g_live.begin(), g_live.end(), g), g_live.end());
+    }
     hipSetDevice(g->device);
     if (g->stream) hipStreamSynchronize(g->stream);
     group_drop_graphs(g);
@@ -319,25 +394,37 @@ int jl_group_run_masked_async(jl_group *g, const jl_gene *genes, uint32_t n_gene
         g->h_phase[k].S.xhead = xh;
         g->h_compact[k].xhead = xh;
     }
+    // the form of THIS launch, from what is in flight now (the argument blocks above hold both forms' arguments)
+    bool other_reachable = false;
+    const int form = group_pick_form(g, &other_reachable);
+#ifdef JL_TUNING
+    __atomic_fetch_add(&g_form_taken[form], 1, __ATOMIC_RELAXED);
+#endif
     const bool graphs_on = !jl_env().no_graph;
-    if (graphs_on && !g->graph_exec[par] && !g->graph_tried[par]) {
-        g->graph_tried[par] = true;
+    auto ensure_graph = [&](int f) {
+        if (!graphs_on || g->graph_exec[par][f] || g->graph_tried[par][f]) return;
+        g->graph_tried[par][f] = true;
         if (hipStreamBeginCapture(g->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            const int erc = group_enqueue(g);
+            const int erc = group_enqueue(g, f);
             hipGraph_t gr = nullptr;
             if (hipStreamEndCapture(g->stream, &gr) == hipSuccess && gr && erc == JL_OK &&
-                hipGraphInstantiate(&g->graph_exec[par], gr, nullptr, nullptr, 0) == hipSuccess) {
-                g->graph[par] = gr;
+                hipGraphInstantiate(&g->graph_exec[par][f], gr, nullptr, nullptr, 0) == hipSuccess) {
+                g->graph[par][f] = gr;
             } else {
                 if (gr) hipGraphDestroy(gr);
-                g->graph_exec[par] = nullptr;
+                g->graph_exec[par][f] = nullptr;
             }
             (void)hipGetLastError();
         }
-    }
-    bool launched = g->graph_exec[par] && hipGraphLaunch(g->graph_exec[par], g->stream) == hipSuccess;
+    };
+    ensure_graph(form);
+    // The other form's graph too, with the first launch of a configuration rather than in the middle of a stream of launches
+    // (a capture and its instantiation cost milliseconds) — where this group can ever take that form: the unfolded one needs
+    // JL_GROUP_FOLD_BELOW other groups on the device.  A group whose neighbours are created later captures it at first use.
+    if (other_reachable) ensure_graph(form ^ 1);
+    bool launched = g->graph_exec[par][form] && hipGraphLaunch(g->graph_exec[par][form], g->stream) == hipSuccess;
     if (!launched) {
-        const int erc = group_enqueue(g);
+        const int erc = group_enqueue(g, form);
         if (erc != JL_OK || hipGetLastError() != hipSuccess) return group_fail(g, erc ? erc : JL_ERR_DEVICE, "group launch failed");
     }
     return JL_OK;
@@ -366,11 +453,16 @@ int jl_group_run_masked_async(jl_group *g, const jl_gene *genes, uint32_t n_gene
         hipEventRecord(g->ev_end, g->stream);
     }
     if (run_rc != JL_OK) return run_rc;   // (its message stands; the exchange, if any, went out with empty heads and is pending)
-    for (uint32_t k = 0; k < n; ++k) {
-        jl_ctx *c = g->ctxs[k];
-        jl_run_finish(c, phasing, want_read_hap);
-        c->run_stream = g->stream;
-        if (g->xc) g->x_run_seq[par][k] = c->runs_launched;
+    {
+        std::lock_guard<std::mutex> lk(g_live_mu);   // (fl_seq / fl_busy are read by the other groups' threads)
+        for (uint32_t k = 0; k < n; ++k) {
+            jl_ctx *c = g->ctxs[k];
+            jl_run_finish(c, phasing, want_read_hap);
+            c->run_stream = g->stream;
+            if (g->xc) g->x_run_seq[par][k] = c->runs_launched;
+            g->fl_seq[k] = c->runs_launched;
+        }
+        g->fl_busy = true;
     }
     if (xrc != JL_OK) return group_fail(g, xrc, xrc == JL_ERR_COMM ? g->xc->tp_error.c_str() : "the run's exchange could not be enqueued");
     return JL_OK;
@@ -471,10 +563,12 @@ int jl_group_exchange_collect(jl_group *g, jl_variant *all_rows, uint32_t *all_c
     return JL_OK;
 }
 
-// Average device time in ms of the grouped pileup launch alone (the launch of a group's FIRST chunk, with the Fisher
-// stage in its epilogue as in a run): `reps` back-to-back launches rotating over the given groups (all on the first
-// group's stream), one pair of HIP events around them.  Every group must have run at least once (its argument
-// tables are what the launch reads).
+// Average device time in ms of the grouped pileup launch alone — pileup_planes_group_kernel, the plain kernel of the unfolded
+// form, over the launch of a group's FIRST chunk: the bytes the roofline counts against the kernel that only moves them.
+// `reps` back-to-back launches rotating over the given groups (all on the first group's stream), one pair of HIP events
+// around them.  Every group must have run at least once (its argument tables are what the launch reads).  The launch
+// rewrites the windows' column counts and codon histograms with the values they hold already (the matrix has not
+// changed) and touches nothing else: the last run's tables, run counters and results stay as they are and stay fetchable.
 int jl_group_time_pileup(jl_group *const *groups, uint32_t n_groups, uint32_t reps, float *ms_avg, uint64_t *bytes_per_launch)
 {
     if (!groups || n_groups == 0 || !ms_avg || reps == 0) return JL_ERR_ARG;
@@ -489,9 +583,7 @@ int jl_group_time_pileup(jl_group *const *groups, uint32_t n_groups, uint32_t re
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return group_fail(g0, JL_ERR_DEVICE, "events");
     auto launch = [&](jl_group *g) {
         const jl_group::chunk_t &c = g->chunks[0];
-        // (the launch the group's runs make: the pileup with the Fisher stage in its epilogue)
-        if (!jl_fold_enabled()) return jl_launch_pileup_group(g->ctxs.data() + c.first, c.n, g->h_pile.data() + c.first, c.max_chunks, g0->stream);
-        return jl_launch_pileup_fold_group(g->ctxs.data() + c.first, c.n, g->h_pile.data() + c.first, g->h_fold.data() + c.first, c.max_chunks, g0->stream);
+        return jl_launch_pileup_group(g->ctxs.data() + c.first, c.n, g->h_pile.data() + c.first, c.max_chunks, g0->stream);
     };
     int rc = JL_OK;
     for (uint32_t k = 0; k < n_groups && rc == JL_OK; ++k) rc = launch(groups[k]);   // warm-up, once per group
@@ -510,13 +602,29 @@ int jl_group_time_pileup(jl_group *const *groups, uint32_t n_groups, uint32_t re
         for (uint32_t k = c.first; k < c.first + c.n; ++k) b += (uint64_t)g0->ctxs[k]->n_reads * g0->ctxs[k]->n_cols * 3u / 8u;   // 3 bits per cell
         *bytes_per_launch = b;
     }
-    for (uint32_t k = 0; k < n_groups; ++k)
-        for (jl_ctx *c : groups[k]->ctxs) {
-            c->pileup_done = true;
-            c->call_done = c->phase_done = false;
-            c->pack_valid = false;
-        }
     return JL_OK;
 }
+
+#ifdef JL_TUNING
+// test hook of the -DJL_TUNING build: group launches of this process that took the folded / the unfolded form
+__attribute__((visibility("default"))) void jl_tuning_group_forms(uint64_t *folded, uint64_t *unfolded)
+{
+    if (folded) *folded = __atomic_load_n(&g_form_taken[JL_FORM_FOLDED], __ATOMIC_RELAXED);
+    if (unfolded) *unfolded = __atomic_load_n(&g_form_taken[JL_FORM_UNFOLDED], __ATOMIC_RELAXED);
+}
+// ... and the device-resident scalars of a context's last phasing run (jl_phase_meta: run counters, overflow bits, summary) as
+// bytes, behind everything on the run's stream: what a test compares before and after a call that must not touch them.
+// Returns the number of bytes written, or a negative status.
+__attribute__((visibility("default"))) int jl_tuning_ctx_meta(jl_ctx *ctx, void *out, uint32_t cap)
+{
+    if (!ctx || !out || cap < sizeof(jl_phase_meta)) return JL_ERR_ARG;
+    hipStream_t st = ctx->run_stream ? ctx->run_stream : ctx->stream;
+    if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
+        hipMemcpyAsync(out, ctx->d_meta, sizeof(jl_phase_meta), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return JL_ERR_DEVICE;
+    return (int)sizeof(jl_phase_meta);
+}
+#endif
 
 }  // extern "C"

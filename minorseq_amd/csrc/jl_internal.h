@@ -11,12 +11,13 @@
 #include "jl_synth.h"
 
 // The environment: the library reads these four switches and no other, each once (jl_env, kernels_util.hip).
-//   JL_NO_FOLD_CALL        the separate call launch instead of the Fisher stage folded into the pileup: A/B of the fold
-//                          (bench.py picks the kernel it times by it)
+//   JL_NO_FOLD_CALL        the separate call launch always, never the Fisher stage folded into the pileup: A/B of the fold
+//                          (group runs choose between the two per launch otherwise: capi_group.hip)
 //   JL_NO_GRAPH            eager launches, no captured graphs: a debugging aid
 //   JL_EXCHANGE_STAGED=1   the all-gather's staged form (tests/test_gpu_parity.py)
 //   JL_FORCE_FOLD_TIMEOUT  test hook of the -DJL_TUNING build (tools_tuning/build_tuning_lib.sh): a folded phase launch gives up
-//                          waiting at once (test_fold_timeout_is_rerun_unfolded).  JL_TUNING means nothing else.
+//                          waiting at once (test_fold_timeout_is_rerun_unfolded).  JL_TUNING adds one more thing, a
+//                          counter of the forms group launches took (jl_tuning_group_forms, capi_group.hip), and nothing else.
 struct jl_env_switches {
     bool no_fold_call, no_graph, exchange_staged, force_fold_timeout;
 };
@@ -532,6 +533,8 @@ void jl_launch_done_on(jl_ctx *ctx, hipStream_t st);
 // on the run's stream; blocks until it is done.  The call stage's results are still resident.
 extern "C" int jl_phase_rerun_unfolded(jl_ctx *ctx);
 void jl_launch_done_group(const jl_done_ent *d_ents, uint32_t n, hipStream_t st);
+// capi_group.hip: `ctx` is about to be destroyed — the groups it is a window of stop being counted as launches in flight
+void jl_group_forget_ctx(const jl_ctx *ctx);
 extern "C" int jl_run_prepare(jl_ctx *ctx, const jl_gene *genes, uint32_t n_genes, const uint8_t *refseq, uint32_t ref_len,
                               const jl_params *prm, const uint64_t *drm_masks, int phasing, uint32_t min_reads,
                               int want_read_hap, double *n_tests_out);

@@ -227,6 +227,8 @@ __device__ __forceinline__ void pileup_planes_stream(const uint8_t JL_AS1 *plane
 // tail exposes).  Only where ONE workgroup counts a chunk (gridDim.y = 1).  Wave j & 3 takes the codon that begins at the chunk's
 // column j — the positions at that column from the host's lists (jl_win_fold) — behind the kernel's last barrier: the other
 // waves store the histogram and leave, so what the evaluation holds for its 2-3 us is one wave's registers, not the workgroup's.
+// A single run (jl_run_async) always takes this form where it can.  A group run takes it per launch, only while its tail is
+// likely to be exposed (capi_group.hip "Two forms"): in a steady stream of group launches the epilogue cost 2.7 % of a step.
 template <int W, int NQ, bool FOLD>
 __device__ __forceinline__ void pileup_planes_body(const uint8_t JL_AS1 *planes, uint64_t plane_stride, uint32_t n_cols, uint32_t n_tiles,
                                                    const uint2 JL_AS1 *chunks, const uint32_t JL_AS1 *guess32, uint32_t JL_AS1 *counts,
@@ -440,7 +442,7 @@ void jl_launch_pileup(jl_ctx *ctx, hipStream_t st)
 #undef JL_LAUNCH_PLANES
 }
 
-// (JL_NO_FOLD_CALL, one of the four environment switches of jl_internal.h: the separate call launch instead, for A/B measurements)
+// (JL_NO_FOLD_CALL, one of the four environment switches of jl_internal.h: the separate call launch always, for A/B measurements)
 bool jl_fold_enabled(void) { return !jl_env().no_fold_call; }
 bool jl_pileup_can_fold(jl_ctx *ctx) { return jl_fold_enabled() && ctx->P != 0 && jl_pileup_rsplit(ctx) == 1u; }
 
