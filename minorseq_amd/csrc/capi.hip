@@ -1167,8 +1167,16 @@ static int fetch_ids(jl_ctx *ctx, uint32_t bits, uint16_t *read_hap)
     return JL_OK;
 }
 
-// a folded phase launch of this context timed out: it stays unfolded, and its captured graphs, which fold, are stale
-static void phase_unfold(jl_ctx *ctx) { ctx->no_fold = true; ctx->fold_reruns++; ctx->alloc_version++; }
+// a phase launch of this context with inline ids timed out: its ids stay separate, and its captured graphs, which have them inline, are stale
+static void phase_ids_go_separate(jl_ctx *ctx) { ctx->ids_separate = true; ctx->alloc_version++; }
+
+// the scalars of the context's last phasing run, behind everything on `st`; blocks until they are there
+static int read_phase_meta(jl_ctx *ctx, hipStream_t st, jl_phase_meta *out)
+{
+    JL_HIP(ctx, hipMemcpyAsync(out, ctx->d_meta, sizeof *out, hipMemcpyDeviceToHost, st));
+    JL_HIP(ctx, hipStreamSynchronize(st));
+    return JL_OK;
+}
 
 // Waits for the last phase launch and reads its scalars; a launch that found more variant positions than its kernels
 // or its key buffer cover is run again with what it needs (the variant table is resident).
@@ -1177,8 +1185,7 @@ static int phase_settle(jl_ctx *ctx, jl_phase_meta *out)
     hipStream_t st = ctx->stream;
     if (ctx->run_stream && ctx->run_stream != st) JL_HIP(ctx, hipStreamSynchronize(ctx->run_stream));
     jl_phase_meta meta;
-    JL_HIP(ctx, hipMemcpyAsync(&meta, ctx->d_meta, sizeof meta, hipMemcpyDeviceToHost, st));
-    JL_HIP(ctx, hipStreamSynchronize(st));
+    if (int rc = read_phase_meta(ctx, st, &meta)) return rc;
     for (int attempt = 0; attempt < 3 && (meta.overflow & (JL_PHASE_OVF_FORM | JL_PHASE_OVF_KEY_WORDS)); ++attempt) {
         const uint32_t kw = (meta.vp_true + JL_POS_PER_WORD - 1) / JL_POS_PER_WORD;
         int rc = reserve_phase(ctx, phase_form_for(ctx->phase_form, meta.vp_true, !ctx->phase_export), kw);
@@ -1186,16 +1193,14 @@ static int phase_settle(jl_ctx *ctx, jl_phase_meta *out)
         if (rc) return rc;
         jl_launch_phase(ctx, st, ctx->last_min_reads, jl_phase_plan::plan_kernel, false);
         JL_HIP(ctx, hipGetLastError());
-        JL_HIP(ctx, hipMemcpyAsync(&meta, ctx->d_meta, sizeof meta, hipMemcpyDeviceToHost, st));
-        JL_HIP(ctx, hipStreamSynchronize(st));
+        if ((rc = read_phase_meta(ctx, st, &meta))) return rc;
     }
-    if (meta.overflow & JL_PHASE_OVF_FOLD_TIMEOUT) {
-        phase_unfold(ctx);   // the stage again, transparently, the ids in a launch of their own
+    if (meta.overflow & JL_PHASE_OVF_IDS_WAIT_TIMEOUT) {
+        phase_ids_go_separate(ctx);   // the stage again, transparently, the ids in a launch of their own
         jl_launch_phase(ctx, st, ctx->last_min_reads, jl_phase_plan::plan_kernel, false);
         JL_HIP(ctx, hipGetLastError());
-        JL_HIP(ctx, hipMemcpyAsync(&meta, ctx->d_meta, sizeof meta, hipMemcpyDeviceToHost, st));
-        JL_HIP(ctx, hipStreamSynchronize(st));
-        if (meta.overflow & JL_PHASE_OVF_FOLD_TIMEOUT) return jl_fail(ctx, JL_ERR_DEVICE, "the unfolded phase launch reports a time-out");
+        if (int rc = read_phase_meta(ctx, st, &meta)) return rc;
+        if (meta.overflow & JL_PHASE_OVF_IDS_WAIT_TIMEOUT) return jl_fail(ctx, JL_ERR_DEVICE, "a phase launch with a separate ids launch reports a time-out");
     }
     *out = meta;
     return JL_OK;
@@ -1515,19 +1520,10 @@ int jl_run_async(jl_ctx *ctx, const jl_gene *genes, uint32_t n_genes, const uint
             if (ctx->graph) { hipGraphDestroy(ctx->graph); ctx->graph = nullptr; }
             ctx->graph_sig.clear();
             if (!seen) ctx->graph_seen.assign((const uint8_t *)&sig, (const uint8_t *)&sig + sizeof sig);
-            else if (hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                enqueue_path(ctx, prm, n_tests, drm_masks != nullptr, phasing != 0, min_reads, want_read_hap != 0);
-                hipGraph_t g = nullptr;
-                if (hipStreamEndCapture(ctx->stream, &g) == hipSuccess && g &&
-                    hipGraphInstantiate(&ctx->graph_exec, g, nullptr, nullptr, 0) == hipSuccess) {
-                    ctx->graph = g;
-                    ctx->graph_sig.assign((const uint8_t *)&sig, (const uint8_t *)&sig + sizeof sig);
-                } else {
-                    if (g) hipGraphDestroy(g);
-                    ctx->graph_exec = nullptr;
-                }
-            }
-            (void)hipGetLastError();
+            else if (jl_capture_graph(ctx->stream, &ctx->graph, &ctx->graph_exec,
+                                      [&] { enqueue_path(ctx, prm, n_tests, drm_masks != nullptr, phasing != 0, min_reads, want_read_hap != 0); return JL_OK; }))
+                ctx->graph_sig.assign((const uint8_t *)&sig, (const uint8_t *)&sig + sizeof sig);
+            (void)hipGetLastError();   // (of a capture that could not begin)
         }
         if (ctx->graph_exec && hipGraphLaunch(ctx->graph_exec, ctx->stream) == hipSuccess) launched = true;
     }
@@ -1546,9 +1542,9 @@ int jl_run_wait_impl(jl_ctx *ctx)
 {
     int rc = jl_run_wait_seq(ctx, ctx->runs_launched);
     if (rc == JL_OK && ctx->ing_check_pending) rc = jl_ingest_verdict(ctx);   // the run read a matrix an enqueued ingest made
-    // a result block without its magic behind a phasing run: the folded launch timed out (see jl_phase_rerun_unfolded)
-    if (rc == JL_OK && ctx->pack_valid && ctx->phase_done && ctx->h_pack && ctx->h_pack->magic != JL_PACK_MAGIC && !ctx->no_fold)
-        rc = jl_phase_rerun_unfolded(ctx);
+    // a result block without its magic behind a phasing run: a launch with inline ids timed out (see jl_phase_rerun_ids_separate)
+    if (rc == JL_OK && ctx->pack_valid && ctx->phase_done && ctx->h_pack && ctx->h_pack->magic != JL_PACK_MAGIC && !ctx->ids_separate)
+        rc = jl_phase_rerun_ids_separate(ctx);
     return rc;
 }
 
@@ -1574,18 +1570,16 @@ static int run_wait_word(volatile uint32_t *p, uint32_t want, hipStream_t stream
     return 0;
 }
 
-int jl_phase_rerun_unfolded(jl_ctx *ctx)
+int jl_phase_rerun_ids_separate(jl_ctx *ctx)
 {
     hipStream_t st = ctx->run_stream ? ctx->run_stream : ctx->stream;
     JL_HIP(ctx, hipSetDevice(ctx->device));
-    JL_HIP(ctx, hipStreamSynchronize(st));
-    uint32_t ovf = 0;
-    JL_HIP(ctx, hipMemcpyAsync(&ovf, &ctx->d_meta->overflow, 4, hipMemcpyDeviceToHost, st));
-    JL_HIP(ctx, hipStreamSynchronize(st));
-    if (!(ovf & JL_PHASE_OVF_FOLD_TIMEOUT)) return jl_fail(ctx, JL_ERR_DEVICE, "the run's result block was not written (no folded launch timed out)");
-    phase_unfold(ctx);
+    jl_phase_meta meta;
+    if (int rc = read_phase_meta(ctx, st, &meta)) return rc;   // (behind the run: same stream)
+    if (!(meta.overflow & JL_PHASE_OVF_IDS_WAIT_TIMEOUT)) return jl_fail(ctx, JL_ERR_DEVICE, "the run's result block was not written (no launch with inline ids timed out)");
+    phase_ids_go_separate(ctx);
     // the Fisher stage's masks and rows are resident: the plan comes out of them again, the ids from phase_assign_kernel,
-    // the completion word from a node of its own (only the fused launches fold, so the run is one of theirs).  The run
+    // the completion word from a node of its own (only the fused launches take inline ids, so the run is one of theirs).  The run
     // counters are the Fisher launch's to zero (call_kernel): here a memset stands in for it.
     JL_HIP(ctx, hipMemsetAsync(ctx->d_meta, 0, sizeof(jl_phase_meta), st));
     jl_launch_phase(ctx, st, ctx->last_min_reads, jl_phase_plan::call_masks, false);
@@ -1594,7 +1588,7 @@ int jl_phase_rerun_unfolded(jl_ctx *ctx)
     ctx->runs_launched++;
     int rc = jl_run_wait_seq(ctx, ctx->runs_launched);
     if (rc) return rc;
-    if (ctx->h_pack->magic != JL_PACK_MAGIC) return jl_fail(ctx, JL_ERR_DEVICE, "the unfolded phase launch left no result block either");
+    if (ctx->h_pack->magic != JL_PACK_MAGIC) return jl_fail(ctx, JL_ERR_DEVICE, "the re-run with a separate ids launch left no result block either");
     return JL_OK;
 }
 

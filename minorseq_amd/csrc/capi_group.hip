@@ -7,7 +7,7 @@
 //   counting            pileup_planes_group_kernel, or pileup_fold_group_kernel: the same with the Fisher stage in its epilogue
 //   Fisher              call_group_kernel, in the unfolded form only (see "Two forms" below)
 //   phasing             phase_group_run_kernel (plan out of the call masks, keys, grouping, selection, result block)
-//   per-read ids        phase_assign_group_kernel (small groups fold them into the phasing launch)
+//   per-read ids        phase_assign_group_kernel (small chunks have them inline, written by the phasing launch: jl_phase_ids_inline)
 //   completion words    done_group_kernel
 // A group of more windows is cut into chunks of JL_GROUP_MAX that are PIPELINED inside one captured graph: the
 // pileups of consecutive chunks run back to back on the group's stream, each chunk's latency-bound tail runs on a
@@ -61,7 +61,7 @@ struct jl_group {
     std::vector<jl_win_fold> h_fold;      // the Fisher stage as the pileup launch's epilogue (every chunk is counted by one workgroup)
     std::vector<jl_win_compact> h_compact;
     std::vector<jl_win_phase> h_phase;
-    struct chunk_t { uint32_t first, n, max_chunks, max_call_blocks, max_phase_blocks; bool fold; };
+    struct chunk_t { uint32_t first, n, max_chunks, max_call_blocks, max_phase_blocks; bool ids_inline; };
     std::vector<chunk_t> chunks;
     bool phasing = true;
     // one captured graph per parity of a bound exchange (the heads' destination is baked in; unbound: [0] only) and per form
@@ -161,7 +161,7 @@ static void chunk_tail(jl_group *g, const jl_group::chunk_t &c, int form, hipStr
         jl_launch_compact_group(g->h_compact.data() + c.first, c.n, st);
     } else {
         jl_launch_phase_group(g->h_phase.data() + c.first, c.n, c.max_phase_blocks, st);
-        if (!c.fold) {
+        if (!c.ids_inline) {
             bool to_host = false;
             for (uint32_t k = 0; k < c.n; ++k) to_host = to_host || g->ctxs[c.first + k]->read_hap_out != nullptr;
             jl_launch_assign_group(g->h_phase.data() + c.first, c.n, c.max_phase_blocks, to_host, st);
@@ -356,19 +356,15 @@ int jl_group_run_masked_async(jl_group *g, const jl_gene *genes, uint32_t n_gene
             memset(&c, 0, sizeof c);
             c.first = o;
             c.n = std::min<uint32_t>(JL_GROUP_MAX, n - o);
-            // The phase launch writes the per-read ids itself when ALL its workgroups can wait for each other, i.e.
-            // are resident at once — also while more such launches run: at most JL_FOLD_MAX_BLOCKS per launch against
-            // 1536 places (six 75-register blocks per CU).  Larger chunks take a separate launch for the ids.
-            uint32_t total_blocks = 0;
-            for (uint32_t k = o; k < o + c.n; ++k) total_blocks += (uint32_t)((g->ctxs[k]->col_stride / 4u + 255u) / 256u) + 1u;
-            c.fold = total_blocks <= JL_FOLD_MAX_BLOCKS;
+            // who writes the chunk's per-read ids: decided once, for the argument blocks below and for chunk_tail
+            c.ids_inline = jl_phase_ids_inline(g->ctxs.data() + o, c.n);
             for (uint32_t k = o; k < o + c.n; ++k) {
                 jl_ctx *x = g->ctxs[k];
                 jl_fill_win_pileup(x, &g->h_pile[k]);
                 jl_fill_win_call(x, prm, n_tests[k], drm_masks && drm_masks[k], phasing != 0, &g->h_call[k]);
                 jl_fill_win_fold(x, &g->h_call[k], &g->h_fold[k]);
                 jl_fill_win_compact(x, false, true, false, &g->h_compact[k]);
-                jl_fill_win_phase(x, min_reads, false, c.fold ? 0xFFFFFFFFu : 0u, jl_phase_plan::call_masks, &g->h_phase[k]);
+                jl_fill_win_phase(x, min_reads, false, c.ids_inline, jl_phase_plan::call_masks, &g->h_phase[k]);
                 c.max_chunks = std::max(c.max_chunks, g->h_pile[k].n_chunks);
                 c.max_call_blocks = std::max(c.max_call_blocks, g->h_call[k].n_blocks);
                 c.max_phase_blocks = std::max(c.max_phase_blocks, g->h_phase[k].n_blocks);
@@ -404,18 +400,7 @@ int jl_group_run_masked_async(jl_group *g, const jl_gene *genes, uint32_t n_gene
     auto ensure_graph = [&](int f) {
         if (!graphs_on || g->graph_exec[par][f] || g->graph_tried[par][f]) return;
         g->graph_tried[par][f] = true;
-        if (hipStreamBeginCapture(g->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            const int erc = group_enqueue(g, f);
-            hipGraph_t gr = nullptr;
-            if (hipStreamEndCapture(g->stream, &gr) == hipSuccess && gr && erc == JL_OK &&
-                hipGraphInstantiate(&g->graph_exec[par][f], gr, nullptr, nullptr, 0) == hipSuccess) {
-                g->graph[par][f] = gr;
-            } else {
-                if (gr) hipGraphDestroy(gr);
-                g->graph_exec[par][f] = nullptr;
-            }
-            (void)hipGetLastError();
-        }
+        jl_capture_graph(g->stream, &g->graph[par][f], &g->graph_exec[par][f], [&] { return group_enqueue(g, f); });
     };
     ensure_graph(form);
     // The other form's graph too, with the first launch of a configuration rather than in the middle of a stream of launches

@@ -11,15 +11,16 @@
 #include "jl_synth.h"
 
 // The environment: the library reads these four switches and no other, each once (jl_env, kernels_util.hip).
-//   JL_NO_FOLD_CALL        the separate call launch always, never the Fisher stage folded into the pileup: A/B of the fold
-//                          (group runs choose between the two per launch otherwise: capi_group.hip)
-//   JL_NO_GRAPH            eager launches, no captured graphs: a debugging aid
-//   JL_EXCHANGE_STAGED=1   the all-gather's staged form (tests/test_gpu_parity.py)
-//   JL_FORCE_FOLD_TIMEOUT  test hook of the -DJL_TUNING build (tools_tuning/build_tuning_lib.sh): a folded phase launch gives up
-//                          waiting at once (test_fold_timeout_is_rerun_unfolded).  JL_TUNING adds one more thing, a
-//                          counter of the forms group launches took (jl_tuning_group_forms, capi_group.hip), and nothing else.
+//   JL_NO_GRAPH                eager launches, no captured graphs: a debugging aid
+//   JL_EXCHANGE_STAGED=1       the all-gather's staged form (tests/test_gpu_parity.py)
+// The fold = the Fisher stage in the pileup launch's epilogue ("fold", "folded", "unfolded" mean nothing else in the library):
+//   JL_NO_FOLD_CALL            the separate call launch always, never the folded Fisher stage: A/B of the fold
+//                              (group runs choose between the two per launch otherwise: capi_group.hip)
+// Inline ids = the phasing launch writing the per-read ids itself (JL_INLINE_IDS_MAX_BLOCKS below):
+//   JL_FORCE_IDS_WAIT_TIMEOUT  test hook of the -DJL_TUNING build (tools_tuning/build_tuning_lib.sh): such a launch gives up waiting at
+//                              once (test_fold_timeout_is_rerun_unfolded).  JL_TUNING adds two read-outs besides (capi_group.hip), nothing else.
 struct jl_env_switches {
-    bool no_fold_call, no_graph, exchange_staged, force_fold_timeout;
+    bool no_fold_call, no_graph, exchange_staged, force_ids_wait_timeout;
 };
 const jl_env_switches &jl_env();
 
@@ -27,10 +28,10 @@ const jl_env_switches &jl_env();
 #define JL_CAND_CAP 4096u         // haplotype candidates (groups with >= min_reads) the selector can rank
 #define JL_POS_PER_WORD 10u       // variant positions per 64-bit key word (6 bits each)
 // Largest phase launch whose workgroups may wait for each other inside the launch (the per-read ids are then written by
-// the same launch): all of them must be resident at once, next to as many more such launches as queues run at a time.
+// the same launch, "inline ids"): all of them must be resident at once, next to as many more such launches as queues run at a time.
 // 1536 places on the chip (75 VGPRs, 20.5 KB LDS per block); 128 leaves room for eight concurrent launches and more.
-#ifndef JL_FOLD_MAX_BLOCKS
-#define JL_FOLD_MAX_BLOCKS 128u
+#ifndef JL_INLINE_IDS_MAX_BLOCKS
+#define JL_INLINE_IDS_MAX_BLOCKS 128u
 #endif
 #define JL_INS_LEN_BINS 32u        // insertion lengths 0..30 by value, 31 = longer
 #define JL_INS_MAX_BASES 30u       // inserted bases tracked per insertion
@@ -46,7 +47,7 @@ constexpr uint32_t JL_PHASE_OVF_HAPLOTYPES = 2u;     // more than JL_MAX_HAPLOTY
 constexpr uint32_t JL_PHASE_OVF_KEY_WORDS = 4u;      // the key buffer was too small for vp_true positions
 constexpr uint32_t JL_PHASE_OVF_FORM = 8u;           // more positions, or a larger result, than the fused launch in use covers
 constexpr uint32_t JL_PHASE_OVF_EXPORT = 16u;        // an exporting run found more groups than its block holds
-constexpr uint32_t JL_PHASE_OVF_FOLD_TIMEOUT = 32u;  // a workgroup of a folded launch gave up waiting: some reads have no id
+constexpr uint32_t JL_PHASE_OVF_IDS_WAIT_TIMEOUT = 32u;  // a workgroup of a launch with inline ids gave up waiting: some reads have no id
 struct jl_phase_meta {  // device-resident scalars of one phasing run
     uint32_t n_var;     // rows used
     uint32_t vp;        // distinct variant columns
@@ -155,6 +156,11 @@ struct jl_win_compact {
     uint8_t *xhead;                  // bound exchange: see jl_select_args
 };
 
+constexpr uint32_t JL_IDS_SEPARATE = 0u;   // jl_select_args::ids_mode: a launch of their own (phase_assign(_group)_kernel) writes the ids
+constexpr uint32_t JL_IDS_INLINE = 1u;     // this launch does
+#ifdef JL_TUNING
+constexpr uint32_t JL_IDS_INLINE_GIVE_UP = 2u;   // ... and its waiting workgroups give up at once (JL_FORCE_IDS_WAIT_TIMEOUT)
+#endif
 // what the last block of the fused phase launch needs to run the selection (and to end the run)
 struct jl_select_args {
     uint32_t run;  // 0: the generic (multi-word) pipeline follows with its own select launch
@@ -171,9 +177,9 @@ struct jl_select_args {
     uint32_t *arrive;
     uint32_t *seq_dev;
     volatile uint32_t *seq_host;
-    // fold != 0: the per-read ids are written by this launch too (all its workgroups are resident together): the
+    // not JL_IDS_SEPARATE: the per-read ids are written by this launch too (all its workgroups are resident together): the
     // other workgroups wait for the selection on `flag`, then map their own reads
-    uint32_t fold, pad_;
+    uint32_t ids_mode, pad_;
     uint32_t *flag, *arrive2;
     uint16_t *read_hap;
     // plan from the call masks (whole-path runs): every workgroup derives the variant columns itself, one extra
@@ -444,8 +450,7 @@ struct jl_ctx {
     uint32_t *d_cooc = nullptr;        // [cooc_cap][cooc_cap]
     uint32_t cooc_cap = 256;
     bool phase_done = false;
-    bool no_fold = false;        // a folded phase launch of this context timed out once: the ids take a launch of their own
-    uint32_t fold_reruns = 0;    // how often that happened
+    bool ids_separate = false;   // a phase launch of this context with inline ids timed out once: the ids take a launch of their own
     jl_phase_form phase_form = jl_phase_form::one_word;   // only grows, except where a session sets it (jl_phase_groups_prepare)
     uint64_t *d_slot_key_a = nullptr, *d_slot_key_b = nullptr;   // half-key tables of the two-word launch [table slots]
     uint32_t *d_occ_a = nullptr, *d_occ_b = nullptr;             // [reads_pad]
@@ -494,6 +499,20 @@ int jl_fail(jl_ctx *ctx, int status, const char *fmt, ...);
                            #expr, hipGetErrorString(e_));                                            \
     } while (0)
 
+// What `enqueue` (a callable returning a status) puts on `st`, captured and instantiated.  False: both stay null, the caller launches eagerly.
+template <class F>
+static inline bool jl_capture_graph(hipStream_t st, hipGraph_t *graph, hipGraphExec_t *exec, F &&enqueue)
+{
+    if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) return false;
+    const int rc = enqueue();
+    hipGraph_t g = nullptr;
+    const bool ok = hipStreamEndCapture(st, &g) == hipSuccess && g && rc == JL_OK && hipGraphInstantiate(exec, g, nullptr, nullptr, 0) == hipSuccess;
+    if (ok) *graph = g;
+    else { if (g) hipGraphDestroy(g); *exec = nullptr; }
+    (void)hipGetLastError();
+    return ok;
+}
+
 // kernel launchers (defined in the .hip files) -------------------------------------------------
 void jl_launch_guess(jl_ctx *ctx, hipStream_t st);
 void jl_launch_pileup(jl_ctx *ctx, hipStream_t st);
@@ -516,7 +535,10 @@ void jl_fill_call_args(jl_ctx *ctx, const jl_params *prm, double n_tests, jl_cal
 void jl_fill_win_pileup(jl_ctx *ctx, jl_win_pileup *w);
 void jl_fill_win_call(jl_ctx *ctx, const jl_params *prm, double n_tests, bool use_drm, bool with_meta, jl_win_call *w);
 void jl_fill_win_compact(jl_ctx *ctx, bool plan, bool pack, bool signal, jl_win_compact *w);
-bool jl_fill_win_phase(jl_ctx *ctx, uint32_t min_reads, bool signal, uint32_t fold_budget, jl_phase_plan plan, jl_win_phase *w);
+// jl_phase_ids_inline decides who writes a launch's per-read ids: true goes into every window's block (`ids_inline`), false adds the ids launch
+uint32_t jl_phase_grid_blocks(const jl_ctx *ctx);
+bool jl_phase_ids_inline(jl_ctx *const *ctxs, uint32_t n_win);
+void jl_fill_win_phase(jl_ctx *ctx, uint32_t min_reads, bool signal, bool ids_inline, jl_phase_plan plan, jl_win_phase *w);
 int jl_launch_pileup_group(jl_ctx *const *ctxs, uint32_t n_win, const jl_win_pileup *h_wins, uint32_t max_chunks, hipStream_t st);
 void jl_launch_call_group(const jl_win_call *h_wins, uint32_t n_win, uint32_t max_blocks, hipStream_t st);
 void jl_launch_compact_group(const jl_win_compact *h_wins, uint32_t n_win, hipStream_t st);
@@ -529,9 +551,9 @@ void jl_launch_nibbles_to_planes(jl_ctx *ctx, const uint8_t *d_nib, uint64_t nib
 void jl_launch_planes_to_nibbles(jl_ctx *ctx, uint8_t *d_nib, uint64_t nib_stride, uint32_t c0, uint32_t n);
 void jl_launch_done(jl_ctx *ctx);
 void jl_launch_done_on(jl_ctx *ctx, hipStream_t st);
-// a run whose folded phase launch gave up waiting (JL_PHASE_OVF_FOLD_TIMEOUT): the phasing stage again, unfolded, behind everything
-// on the run's stream; blocks until it is done.  The call stage's results are still resident.
-extern "C" int jl_phase_rerun_unfolded(jl_ctx *ctx);
+// a run whose phase launch gave up waiting to write its ids (JL_PHASE_OVF_IDS_WAIT_TIMEOUT): the phasing stage again, the ids separate,
+// behind everything on the run's stream; blocks until it is done.  The call stage's results are still resident.
+extern "C" int jl_phase_rerun_ids_separate(jl_ctx *ctx);
 void jl_launch_done_group(const jl_done_ent *d_ents, uint32_t n, hipStream_t st);
 // capi_group.hip: `ctx` is about to be destroyed — the groups it is a window of stop being counted as launches in flight
 void jl_group_forget_ctx(const jl_ctx *ctx);

@@ -14,8 +14,8 @@
 //   assign  per-read haplotype id
 // Vp <= 10 (one key word): ONE launch — phase_fused1_kernel (a window) / phase_group_run_kernel (several windows,
 // blockIdx.z): keys + grouping in every block, the selection by the block that arrives last, and — when all
-// workgroups of the launch are resident together (<= JL_FOLD_MAX_BLOCKS) — the per-read ids by every block from the slots still
-// in its registers (the others wait on a flag); larger launches leave the ids to phase_assign(_group)_kernel.
+// workgroups of the launch are resident together (<= JL_INLINE_IDS_MAX_BLOCKS) — the per-read ids ("inline ids") by every block from the slots still
+// in its registers (the others wait on a flag); larger launches leave the ids to a separate launch, phase_assign(_group)_kernel.
 // Vp > 10: phase_keys_kernel, phase_group_kernel, phase_select_kernel, phase_assign_kernel.
 #include <string.h>
 
@@ -1225,7 +1225,7 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
     gap &= valid; het &= valid; par &= valid;
     const uint32_t dirty = gap | het | par;
     const uint32_t cleanm = valid & ~dirty;  // bit 4r: read r is clean
-    if (live && !S.fold) {
+    if (live && S.ids_mode == JL_IDS_SEPARATE) {
         // the flags and slots of every read are only needed by a later launch that writes the ids
         flagw[t] = gap | (het << 1) | (par << 2) | ((valid ^ kM1) << 3);
     }
@@ -1387,7 +1387,7 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
     // up (four atomics per workgroup on ONE cache line were the longest queue of the launch at a million reads)
     if (tid >= 64u && tid < 68u)
         __hip_atomic_store(&w.blockcat[blockIdx.x * 4u + (tid - 64u)], s_cat[tid - 64u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (!S.fold) {
+    if (S.ids_mode == JL_IDS_SEPARATE) {
 #pragma unroll
         for (int r = 0; r < 8; ++r)
             if ((cleanm >> (4 * r)) & 1u) read_slot[t * 8u + r] = gslot[r];
@@ -1427,7 +1427,7 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
     }
     __syncthreads();
     const bool last = s_last != 0;
-    if (!last && !S.fold) return;
+    if (!last && S.ids_mode == JL_IDS_SEPARATE) return;
     if (last) {
         uint32_t nv = 0, seq_before = 0;
         const bool fast_export = work && S.exp_count != nullptr;
@@ -1479,7 +1479,7 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
         if (work && !S.exp_count)
             done = phase_select_lds<KW>(w, s_plan, vp, nv, n_rows, *reinterpret_cast<sel_lds *>(s_tables[0]), tw, n_occ_pre, occ_pre, s_cat,
                                         &sel_bits, [&](uint32_t bits) {
-                                            if (!S.fold) return;
+                                            if (S.ids_mode == JL_IDS_SEPARATE) return;
                                             if (tid == 0) __hip_atomic_store(S.flag, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                                             write_ids(bits);
                                             ids_written = true;
@@ -1528,7 +1528,7 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
         // out of this die's L2 first — without it the host now and then saw the word before the block's header
         // (new per-read ids and variant rows beside the previous run's read categories: one group run in ten).
         if (tid == 0) __threadfence_system();
-        if (!S.fold) {
+        if (S.ids_mode == JL_IDS_SEPARATE) {
             if (S.seq_host && tid == 0) signal_done(S.seq_dev, S.seq_host);  // no per-read ids wanted: the run ends here
             return;
         }
@@ -1543,7 +1543,7 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
         }
         __syncthreads();
     } else {
-        // wait for the selection.  Every workgroup of this launch is resident (the host folds only small grids), so
+        // wait for the selection.  Every workgroup of this launch is resident (the host asks only small grids for inline ids), so
         // the flag does arrive; the bound turns a broken invariant into a loud failure, not a hang — and not a fault
         // either (a trap can take the device down for every tenant): the run is marked failed where both ways of reading
         // it look (the phase scalars for jl_phase_fetch, the pinned block's magic for jl_run_view_get), this workgroup
@@ -1553,14 +1553,14 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
             while ((bits = __hip_atomic_load(S.flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0u) {
                 __builtin_amdgcn_s_sleep(8);
                 if (++spins > (1u << 23)) {
-                    atomicOr(&meta->overflow, JL_PHASE_OVF_FOLD_TIMEOUT);
+                    atomicOr(&meta->overflow, JL_PHASE_OVF_IDS_WAIT_TIMEOUT);
                     if (S.mirror) __hip_atomic_store(&S.mirror->magic, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                     break;
                 }
             }
 #ifdef JL_TUNING
-            if (S.fold == 2u && bits != 0u) {   // forced: behave as if the wait had run out just before the selection arrived
-                atomicOr(&meta->overflow, JL_PHASE_OVF_FOLD_TIMEOUT);
+            if (S.ids_mode == JL_IDS_INLINE_GIVE_UP && bits != 0u) {   // forced: behave as if the wait had run out just before the selection arrived
+                atomicOr(&meta->overflow, JL_PHASE_OVF_IDS_WAIT_TIMEOUT);
                 if (S.mirror) __hip_atomic_store(&S.mirror->magic, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 bits = 0u;
             }
@@ -1584,7 +1584,7 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
             // A workgroup that gave up waiting marked the run failed; a selection that was only LATE has since written a
             // valid result block over that mark.  The mark in the run's scalars is the lasting one: whoever arrives last
             // makes the blocks say so again, just before the completion word.
-            if (ld_coherent(&meta->overflow) & JL_PHASE_OVF_FOLD_TIMEOUT) {
+            if (ld_coherent(&meta->overflow) & JL_PHASE_OVF_IDS_WAIT_TIMEOUT) {
                 if (S.mirror) __hip_atomic_store(&S.mirror->magic, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 jl_pack *pk = S.pk + (__hip_atomic_load(S.seq_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1u);
                 __hip_atomic_store(&pk->magic, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1661,32 +1661,41 @@ static uint32_t jl_assign_blocks(uint32_t n_win, uint32_t max_read_blocks, bool 
     return std::min<uint32_t>(cap, max_read_blocks);
 }
 
+// a window's phasing grid: a workgroup per 2048 reads + the one that compacts the rows
+uint32_t jl_phase_grid_blocks(const jl_ctx *ctx) { return (uint32_t)((ctx->col_stride / 4u + 255u) / 256u) + 1u; }
+// this context may take inline ids: a fused launch that selects (an exporting run keeps every read's flags and slot:
+// jl_phase_regroup maps them once the merge is known) and has never timed out waiting
+static bool phase_ids_inline_ok(const jl_ctx *ctx) { return ctx->phase_form != jl_phase_form::multi_word && !ctx->phase_export && !ctx->ids_separate; }
+// A launch over these windows (a single run: one) writes the per-read ids itself when every window may take them and ALL its
+// workgroups are resident at once, so that they can wait for each other — also while more such launches run: at most
+// JL_INLINE_IDS_MAX_BLOCKS per launch against 1536 places (six 75-register blocks per CU).
+bool jl_phase_ids_inline(jl_ctx *const *ctxs, uint32_t n_win)
+{
+    uint32_t total_blocks = 0;
+    for (uint32_t k = 0; k < n_win; ++k) total_blocks += jl_phase_grid_blocks(ctxs[k]);
+    return total_blocks <= JL_INLINE_IDS_MAX_BLOCKS && std::all_of(ctxs, ctxs + n_win, phase_ids_inline_ok);
+}
+
 // Argument block of the fused phase launch for one window.  `plan`: call_masks, or the plan is in meta / vpcols already.
-// `fold_budget`: workgroups that may still be added to a launch whose members all wait for each other (the per-read ids
-// are then written by the same launch); returns whether this window folds.
-bool jl_fill_win_phase(jl_ctx *ctx, uint32_t min_reads, bool signal, uint32_t fold_budget, jl_phase_plan plan, jl_win_phase *w)
+void jl_fill_win_phase(jl_ctx *ctx, uint32_t min_reads, bool signal, bool ids_inline, jl_phase_plan plan, jl_win_phase *w)
 {
     memset(w, 0, sizeof *w);
-    const bool generic = ctx->phase_form == jl_phase_form::multi_word;
     const bool ids_to_host = ctx->read_hap_out != nullptr;
     const bool signal_select = signal && !ids_to_host;   // no ids wanted on the host: the selection ends the run
-    const uint32_t n_dwords = (uint32_t)(ctx->col_stride / 4u);
-    const uint32_t fblocks = (n_dwords + 255u) / 256u;
     w->msa = ctx->d_msa; w->col_stride = ctx->col_stride; w->n_reads = ctx->n_reads; w->reads_pad = ctx->col_stride * 2u;
     w->vpcols = ctx->d_vpcols; w->meta = ctx->d_meta; w->keys = ctx->d_keys; w->flagw = ctx->d_flagw;
     w->slots_mask = ctx->table_slots - 1u; w->slot_key = (unsigned long long *)ctx->d_slot_key;
     w->slot_rep = ctx->d_slot_rep; w->slot_count = ctx->d_slot_count; w->occupied = ctx->d_occupied;
     w->read_slot = ctx->d_read_slot;
     w->blockcat = ctx->d_blockcat;
-    w->n_blocks = fblocks;
+    w->n_blocks = jl_phase_grid_blocks(ctx) - 1u;   // (the arrival counters do not count the compacting workgroup)
     select_args &S = w->S;
-    S.run = generic ? 0u : 1u;
+    S.run = ctx->phase_form == jl_phase_form::multi_word ? 0u : 1u;
     S.min_reads = min_reads; S.n_cols = ctx->n_cols; S.cooc_cap = ctx->cooc_cap;
     S.slot_hap = ctx->d_slot_hap; S.variants = ctx->d_variants; S.col2pos = ctx->d_col2pos;
     S.hap_count = ctx->d_hap_count; S.hap_pattern = ctx->d_hap_pattern; S.hit = ctx->d_hit; S.n_rows = ctx->d_nvar;
     S.cooc = ctx->d_cooc; S.pk = ctx->d_pack; S.mirror = ctx->pack_mirror;
     S.arrive = ctx->d_sync + 2; S.seq_dev = ctx->d_sync;
-    // a launch of at most JL_FOLD_MAX_BLOCKS workgroups in all also writes the per-read ids: one launch less
     if (ctx->phase_export) {
         if (ctx->exp_ext_count) {   // a session's block (pinned host memory, or the send buffer of the all-gather)
             S.exp_count = ctx->exp_ext_count; S.exp_pattern = ctx->exp_ext_pattern; S.exp_head = ctx->exp_ext_head;
@@ -1696,22 +1705,19 @@ bool jl_fill_win_phase(jl_ctx *ctx, uint32_t min_reads, bool signal, uint32_t fo
             S.exp_cap = ctx->exp_cap; S.exp_stride = ctx->exp_stride;
         }
     }
-    // (an exporting run keeps every read's flags and slot: jl_phase_regroup maps them once the merge is known)
-    const bool fold = !generic && !ctx->phase_export && !ctx->no_fold && fblocks + 1u <= fold_budget;
-    S.fold = fold ? 1u : 0u;
+    S.ids_mode = ids_inline ? JL_IDS_INLINE : JL_IDS_SEPARATE;   // one launch less
 #ifdef JL_TUNING
-    // tests of the re-run: the waiting workgroups of a folded launch give up at once (as if they had not been resident together)
-    if (fold && jl_env().force_fold_timeout) S.fold = 2u;
+    // tests of the re-run: the waiting workgroups give up at once (as if they had not been resident together)
+    if (ids_inline && jl_env().force_ids_wait_timeout) S.ids_mode = JL_IDS_INLINE_GIVE_UP;
 #endif
     S.flag = ctx->d_sync + 4; S.arrive2 = ctx->d_sync + 3;
     S.read_hap = ctx->read_hap_out ? ctx->read_hap_out : ctx->d_read_hap;
-    S.seq_host = (fold ? signal : signal_select) ? ctx->h_seq : nullptr;
+    S.seq_host = (ids_inline ? signal : signal_select) ? ctx->h_seq : nullptr;
     if (plan == jl_phase_plan::call_masks) {
         S.called = ctx->d_called; S.staged = ctx->d_staged; S.pos_col = ctx->d_pos_col; S.rows = ctx->d_variants;
         S.n_rows_out = ctx->d_nvar; S.vpcols_out = ctx->d_vpcols; S.col2pos_out = ctx->d_col2pos;
         S.P = ctx->P; S.cap = JL_VARIANT_CAP; S.kwords_cap = ctx->keys_words;
     }
-    return fold;
 }
 
 // The phasing launches of ctx->phase_form (the fused ones flag inputs that need a larger form: JL_PHASE_OVF_FORM).  `signal`:
@@ -1731,7 +1737,8 @@ bool jl_launch_phase(jl_ctx *ctx, hipStream_t st, uint32_t min_reads, jl_phase_p
                            (uint32_t)ctx->phase_form, ctx->d_meta);
     const uint32_t n_dwords = (uint32_t)(ctx->col_stride / 4u);
     jl_win_phase w;
-    const bool fold = jl_fill_win_phase(ctx, min_reads, signal, JL_FOLD_MAX_BLOCKS, plan, &w);
+    const bool ids_inline = jl_phase_ids_inline(&ctx, 1);   // a chunk of one window
+    jl_fill_win_phase(ctx, min_reads, signal, ids_inline, plan, &w);
     if (generic) {
         hipLaunchKernelGGL(phase_keys_kernel, dim3((n_dwords + 255u) / 256u), dim3(256), 0, st, ctx->d_msa,
                            ctx->plane_stride, ctx->n_reads, reads_pad, ctx->d_vpcols, ctx->d_meta, ctx->d_keys,
@@ -1755,7 +1762,7 @@ bool jl_launch_phase(jl_ctx *ctx, hipStream_t st, uint32_t min_reads, jl_phase_p
     } else {
         hipLaunchKernelGGL(phase_fused1_kernel, dim3(w.n_blocks + (w.S.called ? 1u : 0u)), dim3(256), 0, st, w);
     }
-    if (fold) return signal;
+    if (ids_inline) return signal;
     if (ctx->phase_export) return false;   // the ids wait for the merge (jl_phase_regroup)
     hipLaunchKernelGGL(phase_assign_kernel, dim3(jl_assign_blocks(1, w.n_blocks, ids_to_host)), dim3(256), 0, st,
                        (uint64_t)n_dwords, ctx->d_flagw, ctx->d_meta, ctx->d_read_slot, ctx->d_slot_hap,

@@ -289,7 +289,7 @@ const jl_env_switches &jl_env()
         const char *staged = getenv("JL_EXCHANGE_STAGED");
         v.exchange_staged = staged && staged[0] == '1';
 #ifdef JL_TUNING
-        v.force_fold_timeout = getenv("JL_FORCE_FOLD_TIMEOUT") != nullptr;
+        v.force_ids_wait_timeout = getenv("JL_FORCE_IDS_WAIT_TIMEOUT") != nullptr;
 #endif
         return v;
     }();

@@ -53,6 +53,6 @@ def test_form_switch_between_launches():
 def test_timing_hook_leaves_the_run_alone():
     """jl_group_time_pileup times the plain grouped pileup kernel and has no side effect: after it, jl_group_views, the
     run views and jl_call_fetch + jl_phase_fetch of every window still return the run's results (against single runs and
-    the oracle), and the device's run counters — n_occupied, the overflow bits jl_phase_rerun_unfolded looks at, the
+    the oracle), and the device's run counters — n_occupied, the overflow bits jl_phase_rerun_ids_separate looks at, the
     summary — are byte for byte what the run left (read through the tuning build's jl_tuning_ctx_meta)."""
     assert "HOOK-OK" in run_child("hook")

@@ -483,16 +483,16 @@ def test_run_view_and_completion_word(jl, oracle):
         j.close()
 
 
-@pytest.mark.parametrize("fold", [True, False])
-def test_group_run_equals_single_runs_and_oracle(jl, oracle, fold):
+@pytest.mark.parametrize("inline_ids", [True, False])
+def test_group_run_equals_single_runs_and_oracle(jl, oracle, inline_ids):
     """jl_group_run_async: several windows through the path in three launches (blockIdx.z = window).  Windows of
     different depth and noise, the same genes: every window's results must equal the oracle's (and so a single
     run's), over graph replays, after new reads were generated into the same buffers, and in majority-codon mode.
-    fold = False: windows deep enough that the phasing launch has more workgroups than may wait for each other (128):
+    inline_ids = False: windows deep enough that the phasing launch has more workgroups than may wait for each other (128):
     the layout large groups use (per-read ids from a launch of their own, nothing waits in a launch)."""
     l = 300
     genes = np.array([(1, l + 1)], dtype=capi.GENE)
-    k_ = 1 if fold else 15
+    k_ = 1 if inline_ids else 15
     shapes = [(9000 * k_, 0.05), (5000 * k_, 0.0), (12345 * k_, 0.2), (2048 * k_, 0.1)]
     ref = synth.reference(90, l)
     ctxs = []
@@ -586,17 +586,17 @@ def test_bench_configuration_group_of_eight_full_size_windows(oracle):
             j.close()
 
 
-@pytest.mark.parametrize("fold", [True, False])
-def test_group_run_with_more_windows_than_a_stage_launch_takes(oracle, fold):
+@pytest.mark.parametrize("inline_ids", [True, False])
+def test_group_run_with_more_windows_than_a_stage_launch_takes(oracle, inline_ids):
     """A group of 19 windows = chunks of 8 + 8 + 3 pipelined inside one captured graph (the counting of a chunk beside
     the phasing of the previous one, side streams forked and joined by events).  Every window against the oracle, over
-    graph replays.  fold = False: deeper windows, the per-read ids come from a launch of their own."""
+    graph replays.  inline_ids = False: deeper windows, the per-read ids come from a launch of their own."""
     l = 150
     genes = np.array([(1, l + 1)], dtype=capi.GENE)
     ref = synth.reference(41, l)
     ctxs, exp = [], []
     for k in range(19):
-        n = (1500 + 433 * k) * (1 if fold else 12)
+        n = (1500 + 433 * k) * (1 if inline_ids else 12)
         j = capi.Juliet(0)
         j.alloc(n, l)
         j.synth_fill(synth.SynthParams(seed=41 + k, minor_permille=(60, 50, 40, 30), partial_rate=0.02 * k), ref)

@@ -423,11 +423,12 @@ def test_result_block_holds_a_sixteen_position_window(oracle):
 
 
 def test_fold_timeout_is_rerun_unfolded(tmp_path):
-    """A folded phase launch whose waiting workgroups give up (they were not resident together) marks the run failed on
-    the device; the host then runs the phasing stage again with the ids in a launch of their own — transparently: the
-    caller gets the right answer, the context stays unfolded.  The time-out is forced in a -DJL_TUNING build
-    (tools_tuning/build_tuning_lib.sh; JL_FORCE_FOLD_TIMEOUT), in a child process (the test process holds the shipped
-    library)."""
+    """A phase launch with inline ids (it writes the per-read ids itself) whose waiting workgroups give up (they were not
+    resident together) marks the run failed on the device; the host then runs the phasing stage again with a separate ids
+    launch — transparently: the caller gets the right answer, the context keeps the separate ids launch from then on.  A
+    group's later runs must then launch it too: the second group run below, on other reads, would keep the first run's
+    ids otherwise.  The time-out is forced in a -DJL_TUNING build (tools_tuning/build_tuning_lib.sh;
+    JL_FORCE_IDS_WAIT_TIMEOUT), in a child process (the test process holds the shipped library)."""
     import subprocess
     import sys
     lib = os.path.join(ROOT, "tools_tuning", "lib_exp", "libjuliet_hip.so")
@@ -450,7 +451,7 @@ ev = orc.call(rows, genes, refseq=ref)
 ep = orc.phase(rows, ev)
 jl = capi.Juliet(0)
 jl.upload_rows(rows)
-for rep in range(3):      # the first run times out and is run again; the next ones are unfolded from the start
+for rep in range(3):      # the first run times out and is run again; the next ones have a separate ids launch from the start
     out = jl.run(genes, ref)
     assert (out["variants"]["count"] == ev["count"]).all()
     assert out["phase"]["summary"] == ep["summary"] and (out["phase"]["read_hap"] == ep["read_hap"]).all(), rep
@@ -461,6 +462,13 @@ g = capi.Group([a, b])
 g.run_async(genes, ref, capi.default_params(), True, 10, True)
 va = a.run_view(); vb = b.run_view()
 assert (va["phase"]["read_hap"] == ep["read_hap"]).all() and (vb["phase"]["read_hap"] == ep["read_hap"][::-1]).all()
+# the group again with the windows' reads swapped: each window's ids are those of the reads it holds NOW (after a time-out
+# both contexts take a separate ids launch, which the group has to make)
+a.upload_rows(rows[::-1].copy()); b.upload_rows(rows)
+g.run_async(genes, ref, capi.default_params(), True, 10, True)
+va = a.run_view(); vb = b.run_view()
+assert (va["phase"]["read_hap"] == ep["read_hap"][::-1]).all(), "window a: ids of the reads it holds now"
+assert (vb["phase"]["read_hap"] == ep["read_hap"]).all(), "window b: ids of the reads it holds now"
 # the stage API
 c = capi.Juliet(0)
 c.upload_rows(rows)
@@ -469,10 +477,10 @@ ph = c.phase_fetch()
 assert ph["summary"] == ep["summary"] and (ph["read_hap"] == ep["read_hap"]).all()
 print("RERUN-OK")
 '''
-    env = dict(os.environ, JL_LIB=lib, JL_ROOT=ROOT, JL_FORCE_FOLD_TIMEOUT="1")
+    env = dict(os.environ, JL_LIB=lib, JL_ROOT=ROOT, JL_FORCE_IDS_WAIT_TIMEOUT="1")
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "RERUN-OK" in out.stdout, out.stdout + out.stderr
-    # ... and without the forced time-out the same build folds and needs no second run
-    env.pop("JL_FORCE_FOLD_TIMEOUT")
+    # ... and without the forced time-out the same build writes the ids inline and needs no second run
+    env.pop("JL_FORCE_IDS_WAIT_TIMEOUT")
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "RERUN-OK" in out.stdout, out.stdout + out.stderr

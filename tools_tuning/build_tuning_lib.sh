@@ -1,4 +1,4 @@
-# builds the library with -DJL_TUNING (its test hooks: JL_FORCE_FOLD_TIMEOUT) and the extra flags $1 into tools_tuning/lib_exp/${2:-libjuliet_hip.so};
+# builds the library with -DJL_TUNING (its test hooks: JL_FORCE_IDS_WAIT_TIMEOUT) and the extra flags $1 into tools_tuning/lib_exp/${2:-libjuliet_hip.so};
 # JL_LIB points tools at it
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
