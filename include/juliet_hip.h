@@ -190,6 +190,35 @@ int jl_records_window(jl_ctx *records, jl_ctx *window, uint32_t n_cols, uint32_t
 int jl_records_window_async(jl_ctx *records, jl_ctx *window, uint32_t n_cols, uint32_t win_begin, uint32_t min_qv);
 int jl_records_drop(jl_ctx *records);
 /*
+ * The QV filter decided by the caller: one bit per base in place of one quality byte and a threshold.  A set bit makes the
+ * base N, exactly as qual < min_qv && qual != 0xFF does in the byte form; a caller with its own policy (per-track
+ * thresholds, a precomputed mask) sets whatever bits it likes.
+ * LAYOUT of `qmask`: parallel to the chunk's seq4, one bit per 4-bit base in the bases' own (query) order.  Base q of read
+ * r of the chunk is bit i = 2 * (seq_off[r] - seq_off[0]) + q, stored in bit (i & 7) of byte (i >> 3): the first base of a
+ * seq4 byte (its high nibble) has the even bit, and the bit of the spare low nibble of an odd-length read is ignored.  The
+ * mask has no offsets of its own and begins at the chunk's first base whatever seq_off[0] is; it holds
+ * jl_qmask_bytes(seq_off[n_reads] - seq_off[0]) bytes.
+ * A stream is masked (every chunk through jl_records_append_masked), or carries qualities, or neither: a chunk of another
+ * form, or a NULL mask, fails with JL_ERR_ARG and drops the stream.  The chunks need no alignment of their own (the
+ * library starts each on a 16-byte boundary of its resident arrays).  A masked stream has no quality count to check a
+ * cigar against; every other rule is jl_records_append's.  jl_records_finish / _window / _window_async: min_qv == 0 builds
+ * without the filter, any other value applies the mask — one upload feeds filtered and unfiltered windows.
+ */
+int jl_records_append_masked(jl_ctx *ctx, uint64_t n_reads, const int32_t *pos, const uint32_t *cigar,
+                             const uint64_t *cig_off, const uint8_t *seq4, const uint64_t *seq_off, const uint8_t *qmask);
+/* jl_records_begin + one jl_records_append_masked + jl_records_finish. */
+int jl_msa_ingest_records_masked(jl_ctx *ctx, uint64_t n_reads, uint32_t n_cols, uint32_t win_begin, const int32_t *pos,
+                                 const uint32_t *cigar, const uint64_t *cig_off, const uint8_t *seq4,
+                                 const uint64_t *seq_off, const uint8_t *qmask, uint32_t min_qv);
+/* Host only (no device, no context).  Bytes of the mask of seq_bytes bytes of packed bases: ceil(seq_bytes / 4). */
+uint64_t jl_qmask_bytes(uint64_t seq_bytes);
+/* The byte form's rule as a mask in the layout above: read r has qual_off[r+1] - qual_off[r] bases (at most two per byte
+ * of its seq4), min_qv is taken as at most 127, 0xFF never masks; every other bit of the first
+ * jl_qmask_bytes(seq_off[n_reads] - seq_off[0]) bytes is cleared (all qmask_bytes are written).  JL_ERR_ARG when
+ * qmask_bytes is less than that, or the offsets decrease. */
+int jl_qmask_from_quals(uint64_t n_reads, const uint64_t *seq_off, const uint8_t *qual, const uint64_t *qual_off,
+                        uint32_t min_qv, uint8_t *qmask, uint64_t qmask_bytes);
+/*
  * Insertions are not part of the matrix (J:26-27) but `fuse` "includes in-frame insertions with a certain distance to
  * each other" (doc/FUSE.md:19): with tracking on, jl_msa_ingest_records also counts them per window column — an
  * insertion sits BEFORE the column of the next reference base.  len_hist[n_cols][32]: insertions by length (31 = longer

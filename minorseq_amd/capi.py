@@ -30,7 +30,7 @@ SUMMARY = np.dtype([(n, "<u4") for n in SUMMARY_FIELDS])
 # every symbol include/juliet_hip.h declares (checked by tests/test_capi_exports.py)
 EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", "jl_ctx_destroy", "jl_last_error",
            "jl_sync", "jl_col_stride", "jl_plane_stride", "jl_msa_upload", "jl_msa_alloc", "jl_msa_adopt", "jl_msa_pack_rows",
-           "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_download", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
+           "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_download", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
            "jl_consensus_fetch", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_phase_async", "jl_phase_fetch",
            "jl_ctx_stream", "jl_run_async", "jl_run_wait", "jl_run_done", "jl_run_view_get", "jl_group_create", "jl_group_destroy",
            "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
@@ -173,6 +173,11 @@ def load_library(path=LIB_PATH):
     lib.jl_records_window.argtypes = [vp, vp, u32, u32, u32]
     lib.jl_records_window_async.argtypes = [vp, vp, u32, u32, u32]
     lib.jl_records_drop.argtypes = [vp]
+    lib.jl_records_append_masked.argtypes = [vp, u64] + [vp] * 6
+    lib.jl_msa_ingest_records_masked.argtypes = [vp, u64, u32, u32] + [vp] * 6 + [u32]
+    lib.jl_qmask_bytes.restype = u64
+    lib.jl_qmask_bytes.argtypes = [u64]
+    lib.jl_qmask_from_quals.argtypes = [u64, vp, vp, vp, u32, vp, u64]
     lib.jl_msa_track_insertions.argtypes = [vp, C.c_int]
     lib.jl_insertions_fetch.argtypes = [vp, vp, vp]
     lib.jl_msa_download.argtypes = [vp, vp, u64]
@@ -334,8 +339,9 @@ class Juliet:
         self._chk(self.lib.jl_msa_pack_rows(self.h, _p(rows), n, l, win_begin))
         self._shape(n, l)
 
-    def ingest_records(self, n_cols, win_begin, pos, cigar, cig_off, seq4, seq_off, qual=None, qual_off=None, min_qv=0):
-        """Aligned records (BAM-decoded arrays) -> resident matrix, cigar expansion on the device."""
+    def ingest_records(self, n_cols, win_begin, pos, cigar, cig_off, seq4, seq_off, qual=None, qual_off=None, min_qv=0, qmask=None):
+        """Aligned records (BAM-decoded arrays) -> resident matrix, cigar expansion on the device.  `qmask`: the filter as one
+        bit per base (jl_msa_ingest_records_masked, layout in include/juliet_hip.h) instead of qualities."""
         pos = np.ascontiguousarray(pos, dtype=np.int32)
         cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
         cig_off = np.ascontiguousarray(cig_off, dtype=np.uint64)
@@ -345,14 +351,25 @@ class Juliet:
             qual = np.ascontiguousarray(qual, dtype=np.uint8)
             qual_off = np.ascontiguousarray(qual_off, dtype=np.uint64)
         n = len(pos)
+        if qmask is not None:
+            if qual is not None:
+                raise ValueError("records carry qualities or a mask, not both")
+            qmask = np.ascontiguousarray(qmask, dtype=np.uint8)
+            self._chk(self.lib.jl_msa_ingest_records_masked(self.h, n, n_cols, win_begin, _p(pos), _p(cigar), _p(cig_off), _p(seq4),
+                                                            _p(seq_off), _p(qmask), min_qv))
+            self._shape(n, n_cols)
+            return
         self._chk(self.lib.jl_msa_ingest_records(self.h, n, n_cols, win_begin, _p(pos), _p(cigar), _p(cig_off), _p(seq4),
                                                  _p(seq_off), _p(qual), _p(qual_off), min_qv))
         self._shape(n, n_cols)
 
     def ingest_records_chunked(self, n_cols, win_begin, pos, cigar, cig_off, seq4, seq_off, qual=None, qual_off=None,
-                               min_qv=0, chunk_reads=1000, hints=(0, 0, 0, 0)):
+                               min_qv=0, chunk_reads=1000, hints=(0, 0, 0, 0), qmask=None):
         """The same through jl_records_begin / _append / _finish, `chunk_reads` records per append; every chunk passes
-        slices of the caller's arrays with offsets that do not start at 0 (the library rebases them)."""
+        slices of the caller's arrays with offsets that do not start at 0 (the library rebases them).  `qmask` (for the whole
+        arrays, relative to seq_off[0]): every chunk's mask is cut out of it, re-based to the chunk's first base."""
+        if qmask is not None and qual is not None:
+            raise ValueError("records carry qualities or a mask, not both")
         pos = np.ascontiguousarray(pos, dtype=np.int32)
         cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
         cig_off = np.ascontiguousarray(cig_off, dtype=np.uint64)
@@ -368,14 +385,21 @@ class Juliet:
             b = min(n, a + chunk_reads)
             co, so = np.ascontiguousarray(cig_off[a:b + 1]), np.ascontiguousarray(seq_off[a:b + 1])
             qo = np.ascontiguousarray(qual_off[a:b + 1]) if qual is not None else None
+            if qmask is not None:
+                qm = qmask_slice(qmask, int(so[0]) - int(seq_off[0]), int(so[-1]) - int(so[0]))
+                self._chk(self.lib.jl_records_append_masked(self.h, b - a, _p(np.ascontiguousarray(pos[a:b])), _p(cigar), _p(co),
+                                                            _p(seq4), _p(so), _p(qm)))
+                continue
             self._chk(self.lib.jl_records_append(self.h, b - a, _p(np.ascontiguousarray(pos[a:b])), _p(cigar), _p(co), _p(seq4),
                                                  _p(so), _p(qual), _p(qo)))
         self._chk(self.lib.jl_records_finish(self.h, n_cols, win_begin, min_qv))
         self._shape(n, n_cols)
 
-    def records_upload(self, pos, cigar, cig_off, seq4, seq_off, qual=None, qual_off=None):
+    def records_upload(self, pos, cigar, cig_off, seq4, seq_off, qual=None, qual_off=None, qmask=None):
         """jl_records_begin + one jl_records_append: the records stay resident on this context (for records_window /
-        records_window_async on other contexts of the device) until records_drop."""
+        records_window_async on other contexts of the device) until records_drop.  `qmask`: jl_records_append_masked."""
+        if qmask is not None and qual is not None:
+            raise ValueError("records carry qualities or a mask, not both")
         pos = np.ascontiguousarray(pos, dtype=np.int32)
         cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
         cig_off = np.ascontiguousarray(cig_off, dtype=np.uint64)
@@ -386,7 +410,11 @@ class Juliet:
             qual_off = np.ascontiguousarray(qual_off, dtype=np.uint64)
         n = len(pos)
         self._chk(self.lib.jl_records_begin(self.h, n, len(cigar), len(seq4), len(qual) if qual is not None else 0))
-        self._chk(self.lib.jl_records_append(self.h, n, _p(pos), _p(cigar), _p(cig_off), _p(seq4), _p(seq_off), _p(qual), _p(qual_off)))
+        if qmask is not None:
+            qmask = np.ascontiguousarray(qmask, dtype=np.uint8)
+            self._chk(self.lib.jl_records_append_masked(self.h, n, _p(pos), _p(cigar), _p(cig_off), _p(seq4), _p(seq_off), _p(qmask)))
+        else:
+            self._chk(self.lib.jl_records_append(self.h, n, _p(pos), _p(cigar), _p(cig_off), _p(seq4), _p(seq_off), _p(qual), _p(qual_off)))
         self._n_records = n
 
     def records_window(self, records, n_cols, win_begin=0, min_qv=0, wait=True):
@@ -757,6 +785,28 @@ def xwin_plan(win_begins, win_ncols, merged):
     if rc:
         raise JulietError(rc, "jl_xwin_plan")
     return remapped[: len(merged)].copy(), pos[: vp.value].copy(), owner[: vp.value].copy()
+
+
+def qmask_from_quals(seq_off, qual, qual_off, min_qv):
+    """jl_qmask_from_quals (host only): the byte form's filter — qual < min(min_qv, 127) and not 0xFF — as one bit per base,
+    bit 2 * (seq_off[r] - seq_off[0]) + q for base q of read r (include/juliet_hip.h)."""
+    lib = load_library()
+    seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
+    qual_off = np.ascontiguousarray(qual_off, dtype=np.uint64)
+    qual = np.ascontiguousarray(qual, dtype=np.uint8)
+    n = len(seq_off) - 1
+    out = np.zeros(int(lib.jl_qmask_bytes(int(seq_off[-1] - seq_off[0]))), dtype=np.uint8)
+    rc = lib.jl_qmask_from_quals(n, _p(seq_off), _p(qual), _p(qual_off), min_qv, _p(out), len(out))
+    if rc != 0:
+        raise JulietError(rc, "jl_qmask_from_quals")
+    return out
+
+
+def qmask_slice(qmask, seq_byte, seq_bytes):
+    """The mask of the `seq_bytes` bytes of packed bases from byte `seq_byte` on, out of a mask of the whole array: two bits per
+    byte, moved down to bit 0."""
+    bits = np.unpackbits(np.ascontiguousarray(qmask, dtype=np.uint8), bitorder="little")[2 * seq_byte:2 * (seq_byte + seq_bytes)]
+    return np.packbits(bits, bitorder="little") if len(bits) else np.zeros(1, dtype=np.uint8)
 
 
 def merge_tables(tables, win_begins):

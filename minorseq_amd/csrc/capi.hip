@@ -299,7 +299,7 @@ int jl_msa_pack_rows(jl_ctx *ctx, const uint8_t *rows, uint64_t n_reads, uint32_
 static void records_drop(jl_ctx *ctx)
 {
     jl_records &r = ctx->rec;
-    void *tmp[] = {r.d_seq, r.d_cig, r.d_co, r.d_so, r.d_pos, r.d_qual, r.d_qo};
+    void *tmp[] = {r.d_seq, r.d_cig, r.d_co, r.d_so, r.d_pos, r.d_qual, r.d_qo, r.d_mask};
     for (void *p : tmp)
         if (p) hipFree(p);
     r = jl_records();
@@ -347,12 +347,47 @@ int jl_records_begin(jl_ctx *ctx, uint64_t reads_hint, uint64_t cigar_words_hint
     return JL_OK;
 }
 
-int jl_records_append(jl_ctx *ctx, uint64_t n_reads, const int32_t *pos, const uint32_t *cigar, const uint64_t *cig_off,
-                      const uint8_t *seq4, const uint64_t *seq_off, const uint8_t *qual, const uint64_t *qual_off)
+// bytes of a mask of `seq_bytes` bytes of packed bases: a bit per nibble
+uint64_t jl_qmask_bytes(uint64_t seq_bytes) { return (seq_bytes + 3u) / 4u; }
+
+// The byte form's rule (kernels_ingest.hip mask_low_quals, slow_pair) on the host: bit 2 (seq_off[r] - seq_off[0]) + q is set when
+// base q of read r has a quality below min_qv (at most 127) that is not 0xFF.
+int jl_qmask_from_quals(uint64_t n_reads, const uint64_t *seq_off, const uint8_t *qual, const uint64_t *qual_off, uint32_t min_qv,
+                        uint8_t *qmask, uint64_t qmask_bytes)
 {
-    if (!ctx || !pos || !cigar || !cig_off || !seq4 || !seq_off || (qual && !qual_off)) return JL_ERR_ARG;
+    if (!seq_off || !qual_off || (!qmask && qmask_bytes)) return JL_ERR_ARG;
+    for (uint64_t r = 0; r < n_reads; ++r)
+        if (seq_off[r + 1] < seq_off[r] || qual_off[r + 1] < qual_off[r]) return JL_ERR_ARG;
+    if (qmask_bytes < jl_qmask_bytes(seq_off[n_reads] - seq_off[0])) return JL_ERR_ARG;
+    for (uint64_t r = 0; r < n_reads; ++r)      // (a read's bits lie inside its own bytes of the bases: two a byte)
+        if (qual_off[r + 1] - qual_off[r] > 2u * (seq_off[r + 1] - seq_off[r])) return JL_ERR_ARG;
+    if (qmask_bytes) memset(qmask, 0, (size_t)qmask_bytes);
+    if (n_reads && !qual && qual_off[n_reads] != qual_off[0]) return JL_ERR_ARG;
+    const uint32_t t = std::min<uint32_t>(min_qv, 127u);
+    for (uint64_t r = 0; r < n_reads; ++r) {
+        const uint8_t *q = qual + qual_off[r];
+        const uint64_t n = qual_off[r + 1] - qual_off[r], i0 = 2u * (seq_off[r] - seq_off[0]);
+        for (uint64_t b = 0; b < n; ++b)
+            if (q[b] < t && q[b] != 0xFFu) qmask[(i0 + b) >> 3] |= (uint8_t)(1u << ((i0 + b) & 7u));
+    }
+    return JL_OK;
+}
+
+// jl_records_append (qmask null, masked false) and jl_records_append_masked (no qualities, masked true)
+static int records_append(jl_ctx *ctx, uint64_t n_reads, const int32_t *pos, const uint32_t *cigar, const uint64_t *cig_off,
+                          const uint8_t *seq4, const uint64_t *seq_off, const uint8_t *qual, const uint64_t *qual_off,
+                          const uint8_t *qmask, bool masked)
+{
     jl_records &R = ctx->rec;
     if (!R.open) return jl_fail(ctx, JL_ERR_STATE, "jl_records_append before jl_records_begin");
+    if (masked && !qmask) {
+        records_drop(ctx);
+        return jl_fail(ctx, JL_ERR_ARG, "jl_records_append_masked: no mask (a stream without a filter takes jl_records_append without qualities)");
+    }
+    if (R.n_reads && masked != R.masked) {
+        records_drop(ctx);
+        return jl_fail(ctx, JL_ERR_ARG, "records: either every chunk carries a mask (jl_records_append_masked) or none does");
+    }
     if (R.n_reads && (qual != nullptr) != R.have_qual) {
         records_drop(ctx);
         return jl_fail(ctx, JL_ERR_ARG, "records: either every chunk carries qualities or none does");
@@ -389,23 +424,34 @@ int jl_records_append(jl_ctx *ctx, uint64_t n_reads, const int32_t *pos, const u
     const size_t n_cig = (size_t)(cig_off[n_reads] - c0), n_seq = (size_t)(seq_off[n_reads] - s0),
                  n_q = qual ? (size_t)(qual_off[n_reads] - q0) : 0;
     const size_t nr = (size_t)R.n_reads;
+    // A masked stream's chunks begin on 16 bytes of the resident bases (offsets may leave gaps: nobody's bases), so that the chunk's
+    // mask — a bit per nibble, relative to the chunk's first base — begins on a dword of the resident mask, at a quarter of the
+    // bases' offset: bit 2 x byte + nibble, for every read of the stream, which is where the kernels look.
+    const uint64_t seq_at = masked ? (R.n_seq + 15u) & ~(uint64_t)15u : R.n_seq;
+    const size_t n_mask = masked ? (size_t)jl_qmask_bytes(n_seq) : 0;
     hipError_t e = records_room(ctx, R.d_pos, R.cap_pos, nr, nr + n_reads, 0);
     if (e == hipSuccess) e = records_room(ctx, R.d_co, R.cap_co, nr + 1, nr + n_reads + 1, 0);
     if (e == hipSuccess) e = records_room(ctx, R.d_so, R.cap_so, nr + 1, nr + n_reads + 1, 0);
     if (e == hipSuccess) e = records_room(ctx, R.d_cig, R.cap_cig, (size_t)R.n_cig, (size_t)R.n_cig + n_cig, 64);
     // the kernel reads the bases in aligned 32-byte pieces: padding behind them
-    if (e == hipSuccess) e = records_room(ctx, R.d_seq, R.cap_seq, (size_t)R.n_seq, (size_t)R.n_seq + n_seq, 64);
+    if (e == hipSuccess) e = records_room(ctx, R.d_seq, R.cap_seq, (size_t)R.n_seq, (size_t)seq_at + n_seq, 64);
+    // (the mask's share of those 64 bytes: a piece's dword of flags lies inside the allocation wherever the piece does)
+    // (its first allocation follows the bases' — the hint of jl_records_begin — so that it grows when they do, not chunk after chunk)
+    if (e == hipSuccess && masked)
+        e = records_room(ctx, R.d_mask, R.cap_mask, (size_t)jl_qmask_bytes(R.n_seq),
+                         std::max((size_t)(seq_at / 4u) + n_mask, R.d_mask ? (size_t)0 : R.cap_seq / 4u), 16);
     if (e == hipSuccess && qual) e = records_room(ctx, R.d_qual, R.cap_qual, (size_t)R.n_qual, (size_t)R.n_qual + n_q, 64);
     if (e == hipSuccess && qual) e = records_room(ctx, R.d_qo, R.cap_qo, nr + 1, nr + n_reads + 1, 0);
     std::vector<uint64_t> off((size_t)(n_reads + 1) * (qual ? 3 : 2));
     uint64_t *co = off.data(), *so = co + n_reads + 1, *qo = so + n_reads + 1;
     for (uint64_t r = 0; r <= n_reads; ++r) {
         co[r] = cig_off[r] - c0 + R.n_cig;
-        so[r] = seq_off[r] - s0 + R.n_seq;
+        so[r] = seq_off[r] - s0 + seq_at;
         if (qual) qo[r] = qual_off[r] - q0 + R.n_qual;
     }
     const size_t off_bytes = (size_t)(n_reads + 1) * 8;
-    if (e == hipSuccess && n_seq) e = hipMemcpyAsync(R.d_seq + R.n_seq, seq4 + s0, n_seq, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && n_seq) e = hipMemcpyAsync(R.d_seq + seq_at, seq4 + s0, n_seq, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && n_mask) e = hipMemcpyAsync(R.d_mask + seq_at / 4u, qmask, n_mask, hipMemcpyHostToDevice, st);
     if (e == hipSuccess && n_cig) e = hipMemcpyAsync(R.d_cig + R.n_cig, cigar + c0, n_cig * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(R.d_co + nr, co, off_bytes, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(R.d_so + nr, so, off_bytes, hipMemcpyHostToDevice, st);
@@ -419,11 +465,26 @@ int jl_records_append(jl_ctx *ctx, uint64_t n_reads, const int32_t *pos, const u
         return jl_fail(ctx, e == hipErrorOutOfMemory ? JL_ERR_MEMORY : JL_ERR_DEVICE, "records: %s", hipGetErrorString(e));
     }
     R.have_qual = qual != nullptr;
+    R.masked = masked;
     R.n_reads += n_reads;
     R.n_cig += n_cig;
-    R.n_seq += n_seq;
+    R.n_seq = seq_at + n_seq;
     R.n_qual += n_q;
     return JL_OK;
+}
+
+int jl_records_append(jl_ctx *ctx, uint64_t n_reads, const int32_t *pos, const uint32_t *cigar, const uint64_t *cig_off,
+                      const uint8_t *seq4, const uint64_t *seq_off, const uint8_t *qual, const uint64_t *qual_off)
+{
+    if (!ctx || !pos || !cigar || !cig_off || !seq4 || !seq_off || (qual && !qual_off)) return JL_ERR_ARG;
+    return records_append(ctx, n_reads, pos, cigar, cig_off, seq4, seq_off, qual, qual_off, nullptr, false);
+}
+
+int jl_records_append_masked(jl_ctx *ctx, uint64_t n_reads, const int32_t *pos, const uint32_t *cigar, const uint64_t *cig_off,
+                             const uint8_t *seq4, const uint64_t *seq_off, const uint8_t *qmask)
+{
+    if (!ctx || !pos || !cigar || !cig_off || !seq4 || !seq_off) return JL_ERR_ARG;
+    return records_append(ctx, n_reads, pos, cigar, cig_off, seq4, seq_off, nullptr, nullptr, qmask, true);
 }
 
 // room for `n` elements of `elem` bytes in one of the ingest's scratch arrays of `ctx` (grow-only; the old contents are not kept)
@@ -518,7 +579,7 @@ static int records_build(jl_ctx *src, jl_ctx *dst, uint32_t n_cols, uint32_t win
     }
     if (e == hipSuccess) {
         jl_launch_ingest(dst, R.d_pos, R.d_cig, R.d_co, R.d_seq, R.d_so, R.have_qual ? R.d_qual : nullptr,
-                         R.have_qual ? R.d_qo : nullptr, min_qv, dst->d_ing_runs, dst->d_ing_nruns, dst->d_ing_desc, dst->d_ing_count,
+                         R.have_qual ? R.d_qo : nullptr, R.masked ? R.d_mask : nullptr, min_qv, dst->d_ing_runs, dst->d_ing_nruns, dst->d_ing_desc, dst->d_ing_count,
                          dst->d_ing_slow, R.maybe_long);
         e = hipGetLastError();
         dst->ing_check_pending = e == hipSuccess;
@@ -575,6 +636,18 @@ int jl_msa_ingest_records(jl_ctx *ctx, uint64_t n_reads, uint32_t n_cols, uint32
     int rc = jl_records_begin(ctx, n_reads, cig_off[n_reads] - cig_off[0], seq_off[n_reads] - seq_off[0],
                               qual ? std::max<uint64_t>(qual_off[n_reads] - qual_off[0], 1) : 0);
     if (rc == JL_OK) rc = jl_records_append(ctx, n_reads, pos, cigar, cig_off, seq4, seq_off, qual, qual_off);
+    if (rc == JL_OK) rc = jl_records_finish(ctx, n_cols, win_begin, min_qv);
+    else if (ctx->rec.open) records_drop(ctx);
+    return rc;
+}
+
+int jl_msa_ingest_records_masked(jl_ctx *ctx, uint64_t n_reads, uint32_t n_cols, uint32_t win_begin, const int32_t *pos,
+                                 const uint32_t *cigar, const uint64_t *cig_off, const uint8_t *seq4, const uint64_t *seq_off,
+                                 const uint8_t *qmask, uint32_t min_qv)
+{
+    if (!ctx || !pos || !cigar || !cig_off || !seq4 || !seq_off) return JL_ERR_ARG;
+    int rc = jl_records_begin(ctx, n_reads, cig_off[n_reads] - cig_off[0], seq_off[n_reads] - seq_off[0], 0);
+    if (rc == JL_OK) rc = jl_records_append_masked(ctx, n_reads, pos, cigar, cig_off, seq4, seq_off, qmask);
     if (rc == JL_OK) rc = jl_records_finish(ctx, n_cols, win_begin, min_qv);
     else if (ctx->rec.open) records_drop(ctx);
     return rc;

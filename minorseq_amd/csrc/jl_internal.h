@@ -308,7 +308,9 @@ void jl_launch_xw_fetch(const void *d_src, void *h_dst, uint64_t bytes, uint32_t
 // Records uploaded so far by jl_records_append: one run of device arrays, offsets rebased to it.
 struct jl_records {
     bool open = false, have_qual = false;
-    uint8_t *d_seq = nullptr, *d_qual = nullptr;
+    bool masked = false;     // a masked stream (jl_records_append_masked): d_mask holds a bit per nibble of d_seq, every chunk begins on 16 bytes of d_seq
+    uint8_t *d_seq = nullptr, *d_qual = nullptr, *d_mask = nullptr;
+    size_t cap_mask = 0;
     uint32_t *d_cig = nullptr;
     uint64_t *d_co = nullptr, *d_so = nullptr, *d_qo = nullptr;
     int32_t *d_pos = nullptr;
@@ -569,7 +571,7 @@ uint32_t jl_ingest_short_ops();
 bool jl_ingest_read_is_long(const uint32_t *cigar, uint64_t n_ops);
 void jl_launch_ingest(jl_ctx *ctx, const int32_t *d_pos, const uint32_t *d_cigar, const uint64_t *d_cig_off,
                       const uint8_t *d_seq4, const uint64_t *d_seq_off, const uint8_t *d_qual,
-                      const uint64_t *d_qual_off, uint32_t min_qv, uint2 *d_runs, uint32_t *d_nruns, uint4 *d_desc,
+                      const uint64_t *d_qual_off, const uint8_t *d_qmask, uint32_t min_qv, uint2 *d_runs, uint32_t *d_nruns, uint4 *d_desc,
                       uint32_t *d_slow_count, uint2 *d_slow, bool maybe_long);
 uint32_t jl_ingest_sweeps(uint32_t n_cols);
 size_t jl_ingest_slow_room(const jl_ctx *ctx);

@@ -37,12 +37,20 @@
 //                       With qualities a workgroup of the first size takes TWO sibling tiles one after the other and stores
 //                       their plane words together, 32 bytes of a line a request (round 6: the L2 takes a write request per row
 //                       and tile, 7 x 10^6 a window — the stores were 34 us of the launch's 111, 70 of 184 with qualities).
+//                       The QV filter comes in two forms: qualities, a byte a base, compared with min_qv here (two unaligned 16-byte
+//                       loads a piece, eight registers), or the caller's decision, a BIT a base (jl_records_append_masked): the mask is
+//                       laid out by the resident bases, bit 2 x byte + nibble, so the 32 flags of a piece are the four bytes at a
+//                       quarter of the piece's byte offset — one register a piece, asked for with the piece.
 //                       (Rounds 1-3 expanded every read into a by-row matrix in HBM: 870 MB moved for the 316 MB needed;
 //                       round 4 scattered the codes into a by-row LDS tile with masked, shifted XORs: 137 us.)
 
 #include <algorithm>
 
 #include "jl_internal.h"
+
+#ifndef JL_NT_QM      // sibling tiles a workgroup of the planes kernel's mask mode (jl_launch_ingest): 1 or 2
+#define JL_NT_QM 2
+#endif
 
 namespace {
 
@@ -626,6 +634,7 @@ struct ingest_args {
     const uint64_t *seq_off;     // (slow_pair)
     const uint8_t *qual;         // null: no QV masking
     const uint64_t *qual_off;
+    const uint8_t *qmask;        // the filter as one bit a base (jl_records_append_masked), bit 2 x seq byte + base of the byte; null: none
     const uint2 *runs;
     const uint32_t *nruns;
     const uint4 *desc;
@@ -643,6 +652,8 @@ struct ingest_args {
 //                      at a time lie 8 banks apart.
 constexpr uint32_t kReadWaves = kTileReads / 64u;     // waves of read threads, with a part of the entry area each
 constexpr uint32_t kMinWgs = 4u;      // workgroups a CU must be able to hold: 128 registers for the first size (two tiles a workgroup with qualities: 129 without the bound)
+// (the mask mode with two tiles a workgroup takes 126 under the same bound; bounded to the five workgroups the LDS leaves room for —
+// 96 registers — it spills 88 bytes a lane: the kept plane words of the first tile are 48 of them.  With one tile: 75, five by itself.)
 // pieces whose qualities a thread has asked for ahead of their turn (8 registers each; with all seven ahead one tile a workgroup is
 // 5 us faster, two tiles a workgroup 11 us slower)
 constexpr uint32_t kQualAhead = 3u;
@@ -734,13 +745,33 @@ __device__ __forceinline__ void mask_low_quals(const ingest_args &a, const piece
     }
 }
 
-template <bool QV>
-__device__ __forceinline__ void piece_bases(const ingest_args &a, const u32x4 &v, const piece_quals &pq, uint32_t (&S)[4])
+// The input modes of the planes kernel: no filter; qualities, a byte a base, compared with min_qv here; the filter made by the
+// caller, a bit a base (jl_records_append_masked).
+constexpr uint32_t kQvNone = 0u, kQvBytes = 1u, kQvMask = 2u;
+
+// The filter of a piece's 32 bases as the caller made it, flag b = base b of the piece: byte k of `fl` goes onto the nibbles of S[k]
+// (flag 8 k + j -> nibble j), 15 (N) where it is set — three masked shifts spread eight bits to the low bit of eight nibbles,
+// and x 15 fills the nibble: nine instructions for eight bases, against mask_low_quals' thirteen and its eight registers of input.
+__device__ __forceinline__ void mask_flagged(uint32_t fl, uint32_t (&S)[4])
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        uint32_t t = (fl >> (8 * k)) & 0xFFu;
+        t = (t | (t << 12)) & 0x000F000Fu;      // flags 0-3 in bits 0-3, 4-7 in bits 16-19
+        t = (t | (t << 6)) & 0x03030303u;       // two a byte
+        t = (t | (t << 3)) & 0x11111111u;       // one a nibble
+        S[k] |= t * 15u;
+    }
+}
+
+template <uint32_t QV>
+__device__ __forceinline__ void piece_bases(const ingest_args &a, const u32x4 &v, const piece_quals &pq, uint32_t fl, uint32_t (&S)[4])
 {
     const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
     for (int k = 0; k < 4; ++k) S[k] = ((w4[k] >> 4) & 0x0F0F0F0Fu) | ((w4[k] & 0x0F0F0F0Fu) << 4);
-    if (QV) mask_low_quals(a, pq, S);
+    if (QV == kQvBytes) mask_low_quals(a, pq, S);
+    if (QV == kQvMask) mask_flagged(fl, S);
 }
 
 __device__ __forceinline__ uint32_t ent_col(uint32_t e) { return e & 511u; }
@@ -783,6 +814,10 @@ __device__ __forceinline__ void slow_pair(const ingest_args &a, uint64_t r, uint
                 const uint32_t qv = a.qual[qo + q];
                 if (qv != 0xFFu && qv < a.min_qv) sym = JL_SYM_MASK;
             }
+            if (a.qmask) {
+                const uint64_t i = 2u * so + q;      // (the mask is laid out by the resident bases: a bit a nibble)
+                if ((a.qmask[i >> 3] >> (uint32_t)(i & 7u)) & 1u) sym = JL_SYM_MASK;
+            }
         }
         const uint32_t flip = sym ^ 6u;
         const uint32_t bit = 1u << (uint32_t)(r & 31u);
@@ -807,7 +842,7 @@ __device__ __forceinline__ void slow_pair(const ingest_args &a, uint64_t r, uint
 // DEFER (the first size, several sibling tiles a workgroup: ingest_planes_kernel): the unit's plane words are handed back in `keep`
 // instead of being stored — returns whether the unit made any (false: outside the window's groups, or handed on) — and a read
 // the workgroup has no room for hands the unit on instead of going through slow_pair (whose bit flips need the stores done).
-template <bool QV, uint32_t EPR, bool BIG, bool DEFER = false>
+template <uint32_t QV, uint32_t EPR, bool BIG, bool DEFER = false>
 __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t b, uint32_t (&keep)[8][3])
 {
     using shape = planes_shape<EPR>;
@@ -840,7 +875,7 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
     // the pieces p0, p0 + 128, ... (K of them): the descriptors of their reads, then the pieces, all of a thread's requests in
     // flight together; a piece that is not there (the read has fewer) asks for the read's first one again — the same number of
     // requests in every lane, so that a wait for something asked earlier does not wait for these
-    struct piece_t { u32x4 v; uint32_t dst; int32_t Q; uint64_t qb; };    // dst: dword in the staging area, 0 = none
+    struct piece_t { u32x4 v; uint32_t dst; int32_t Q; uint64_t qb; uint32_t fl; };    // dst: dword in the staging area, 0 = none; fl: the piece's 32 flags (kQvMask)
     // (every load is asked for whatever the read's number — a read past the last asks for the first one's, and is set to nothing
     // afterwards: loads inside a branch made the compiler wait for each before it asked for the next)
     auto ask_descs = [&](uint32_t p0, uint32_t K, uint4 (&d)[kPieceRoundsB], uint64_t (&qo)[kPieceRoundsB]) {
@@ -852,7 +887,7 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
             in[k] = r0 + j < a.n_reads;
             const uint64_t at = in[k] ? r0 + j : 0u;
             d[k] = desc[at];
-            qo[k] = QV ? a.qual_off[at] : 0u;
+            qo[k] = QV == kQvBytes ? a.qual_off[at] : 0u;
         }
 #pragma unroll
         for (uint32_t k = 0; k < kPieceRoundsB; ++k) {
@@ -863,6 +898,7 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
             }
         }
     };
+    typedef uint32_t u32a1 __attribute__((aligned(1)));
     auto ask_pieces = [&](uint32_t p0, uint32_t K, const uint4 (&d)[kPieceRoundsB], const uint64_t (&qo)[kPieceRoundsB], piece_t (&pc)[kPieceRoundsB]) {
 #pragma unroll
         for (uint32_t k = 0; k < kPieceRoundsB; ++k) {
@@ -873,6 +909,9 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
             const uint64_t at = ((((uint64_t)d[k].w & 0xFFu) << 32) | d[k].x) + (i < np ? 4u * i : 0u);     // (in dwords)
             // (plain loads: neighbouring lanes' pieces share lines, and so do the sweeps of a read)
             pc[k].v = *reinterpret_cast<const u32x4a4 *>(a.seq4 + 4u * at);
+            // (kQvMask: the piece begins at byte 4 at of the bases = bit 8 at of the mask, its 32 flags are the four bytes from byte
+            // `at` on — one register a piece, asked for WITH the piece: all of a thread's requests are out before the first is used)
+            if (QV == kQvMask) pc[k].fl = *reinterpret_cast<const u32a1 *>(a.qmask + at);
             pc[k].dst = i < np ? shape::row_dw(j) + 4u * i : 0u;
             pc[k].Q = (int32_t)d[k].z + (i < np ? 32 * (int32_t)i : 0);      // (a piece that is not there: its read's first one's qualities)
             pc[k].qb = qo[k];
@@ -883,7 +922,7 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
     // of a thread waited for its own trip to HBM, seven in a row: 184 us against 111 without qualities.)
     auto stage_pieces = [&](uint32_t K, const piece_t (&pc)[kPieceRoundsB]) {
         piece_quals pq[kPieceRoundsB];
-        if (QV) {
+        if (QV == kQvBytes) {
 #pragma unroll
             for (uint32_t k = 0; k < kPieceRoundsB; ++k)
                 if (k < K && k < kQualAhead) pq[k] = ask_quals(a, pc[k].Q, pc[k].qb);
@@ -891,10 +930,10 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
 #pragma unroll
         for (uint32_t k = 0; k < kPieceRoundsB; ++k) {
             if (k >= K) break;
-            if (QV && k + kQualAhead < K && k + kQualAhead < kPieceRoundsB) pq[k + kQualAhead] = ask_quals(a, pc[k + kQualAhead].Q, pc[k + kQualAhead].qb);
+            if (QV == kQvBytes && k + kQualAhead < K && k + kQualAhead < kPieceRoundsB) pq[k + kQualAhead] = ask_quals(a, pc[k + kQualAhead].Q, pc[k + kQualAhead].qb);
             if (pc[k].dst) {
                 uint32_t S[4];
-                piece_bases<QV>(a, pc[k].v, pq[k], S);
+                piece_bases<QV>(a, pc[k].v, pq[k], pc[k].fl, S);
                 u32x4 o = {S[0], S[1], S[2], S[3]};
                 *reinterpret_cast<u32x4 *>(&s_stage[pc[k].dst]) = o;
             }
@@ -910,7 +949,7 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
     // 185 -> 202): its raised waves also go before the waves of whatever else is on the device — the next build's cigar walk, the
     // pileup and the phasing of the windows before — so there it stays off.  (Raised only until the loads are out: the same;
     // raised for the transposing instead: 116 / 176.)
-    constexpr bool kPrio = !QV;
+    constexpr bool kPrio = QV == kQvNone;
     if (kPrio) __builtin_amdgcn_s_setprio(3);
     if (tid >= kTileReads) {
         // ---- waves 2, 3: pieces
@@ -1181,7 +1220,7 @@ constexpr uint32_t kBigGrid = 768u;
 // blocks of 8 columns x four 32-read groups): the lane at position u of a pair of blocks ends up with tile u's words of both
 // blocks (two DPP moves a word), and 4 NT neighbouring lanes write NT x 16 contiguous bytes of a row.  (Four tiles a workgroup
 // were slower: see jl_launch_ingest.)
-template <bool QV, uint32_t EPR, bool BIG, uint32_t NT = 1u>
+template <uint32_t QV, uint32_t EPR, bool BIG, uint32_t NT = 1u>
 __global__ __launch_bounds__(kThreads, (BIG ? 1 : kMinWgs)) void ingest_planes_kernel(ingest_args a)
 {
     static_assert(NT == 1u || NT == 2u, "one tile a workgroup, or two");
@@ -1306,7 +1345,7 @@ bool jl_ingest_read_is_long(const uint32_t *cigar, uint64_t n_ops)
 // Everything is enqueued on ctx->stream; nothing waits.
 void jl_launch_ingest(jl_ctx *ctx, const int32_t *d_pos, const uint32_t *d_cigar, const uint64_t *d_cig_off,
                       const uint8_t *d_seq4, const uint64_t *d_seq_off, const uint8_t *d_qual,
-                      const uint64_t *d_qual_off, uint32_t min_qv, uint2 *d_runs, uint32_t *d_nruns, uint4 *d_desc,
+                      const uint64_t *d_qual_off, const uint8_t *d_qmask, uint32_t min_qv, uint2 *d_runs, uint32_t *d_nruns, uint4 *d_desc,
                       uint32_t *d_slow_count, uint2 *d_slow, bool maybe_long)
 {
     hipStream_t st = ctx->stream;
@@ -1337,6 +1376,9 @@ void jl_launch_ingest(jl_ctx *ctx, const int32_t *d_pos, const uint32_t *d_cigar
     const bool qv = d_qual != nullptr && min_qv != 0u;
     a.qual = qv ? d_qual : nullptr;
     a.qual_off = qv ? d_qual_off : nullptr;
+    // (a masked stream — jl_records_append_masked — has no qualities: d_qual is null then, and min_qv only switches the filter on)
+    const bool qm = d_qmask != nullptr && min_qv != 0u;
+    a.qmask = qm ? d_qmask : nullptr;
     a.runs = d_runs;
     a.nruns = d_nruns;
     a.desc = d_desc;
@@ -1347,12 +1389,17 @@ void jl_launch_ingest(jl_ctx *ctx, const int32_t *d_pos, const uint32_t *d_cigar
     const uint32_t grid = planes_units(ctx);
     // sibling tiles a workgroup (round 6): with qualities two — 170 us against 179 with one, 213-219 with four (the registers leave two
     // workgroups a CU); without qualities one: 111-113 with one or two, 132 with four
-    constexpr uint32_t kNt = 1u, kNtQv = 2u;
+    // (the mask mode: two — a whole build 140.7 us at the median, 137.5 at best, against 144.2 / 142.5 with one, the byte mode 193-195 in
+    // the same runs: profiles/qmask_ingest_ab.txt; -DJL_NT_QM=1 through tools_tuning/build_tuning_lib.sh builds the other)
+    constexpr uint32_t kNt = 1u, kNtQv = 2u, kNtQm = JL_NT_QM;
     if (qv) {
-        hipLaunchKernelGGL((ingest_planes_kernel<true, kEntPerRead, false, kNtQv>), dim3(grid / kNtQv), dim3(kThreads), 0, st, a);
-        hipLaunchKernelGGL((ingest_planes_kernel<true, kEntPerReadBig, true>), dim3(kBigGrid), dim3(kThreads), 0, st, a);
+        hipLaunchKernelGGL((ingest_planes_kernel<kQvBytes, kEntPerRead, false, kNtQv>), dim3(grid / kNtQv), dim3(kThreads), 0, st, a);
+        hipLaunchKernelGGL((ingest_planes_kernel<kQvBytes, kEntPerReadBig, true>), dim3(kBigGrid), dim3(kThreads), 0, st, a);
+    } else if (qm) {
+        hipLaunchKernelGGL((ingest_planes_kernel<kQvMask, kEntPerRead, false, kNtQm>), dim3(grid / kNtQm), dim3(kThreads), 0, st, a);
+        hipLaunchKernelGGL((ingest_planes_kernel<kQvMask, kEntPerReadBig, true>), dim3(kBigGrid), dim3(kThreads), 0, st, a);
     } else {
-        hipLaunchKernelGGL((ingest_planes_kernel<false, kEntPerRead, false, kNt>), dim3(grid / kNt), dim3(kThreads), 0, st, a);
-        hipLaunchKernelGGL((ingest_planes_kernel<false, kEntPerReadBig, true>), dim3(kBigGrid), dim3(kThreads), 0, st, a);
+        hipLaunchKernelGGL((ingest_planes_kernel<kQvNone, kEntPerRead, false, kNt>), dim3(grid / kNt), dim3(kThreads), 0, st, a);
+        hipLaunchKernelGGL((ingest_planes_kernel<kQvNone, kEntPerReadBig, true>), dim3(kBigGrid), dim3(kThreads), 0, st, a);
     }
 }

@@ -50,6 +50,7 @@ struct Options {
     int expected_round = 0;
     int fisher_tail = 0;             // --fisher-tail greater|two-sided (doc/JULIET.md:38-42 leaves the sidedness open)
     uint32_t min_reads = 10, min_qv = 0;
+    bool qv_upload_mask = false;     // --qv-upload mask|bytes: what --min-qv sends to the device (bytes: DESIGN.md, the record ingest)
     double min_rq = 0.0;
     int device = 0;
     uint32_t windows = 1;            // column windows the reference is cut into (doc/JULIET.md:261-264: the split never shows)
@@ -81,6 +82,9 @@ struct Options {
         "      --match-rate <r> --substitution-rate <r> --expected-round ceil|floor|nearest\n"
         "      --fisher-tail greater|two-sided  sidedness of Fisher's exact test (default greater: an excess of observed codons)\n"
         "      --min-reads 10  --min-qv 0  --min-rq 0  --device 0\n"
+        "      --qv-upload mask|bytes          what --min-qv sends to the device: the filter decided while decoding, one bit per\n"
+        "                                      base, or the folded qualities, one byte per base, and the threshold (default);\n"
+        "                                      the same output\n"
         "      --windows K [--devices a,b,...] cut the reference into K column windows (2-column overlap, global Bonferroni\n"
         "                                      factor), consecutive windows per device; phasing runs across the windows with\n"
         "                                      the reads sharded over the devices.  The output is that of one window.\n"
@@ -195,6 +199,11 @@ Options parse(int argc, char **argv)
         }
         else if (a == "--min-reads") o.min_reads = (uint32_t)std::stoul(need(i));
         else if (a == "--min-qv") o.min_qv = (uint32_t)std::stoul(need(i));
+        else if (a == "--qv-upload") {
+            const std::string v = need(i);
+            if (v != "mask" && v != "bytes") { std::cerr << "juliet: --qv-upload takes mask or bytes\n"; usage(1); }
+            o.qv_upload_mask = v == "mask";
+        }
         else if (a == "--min-rq") o.min_rq = std::stod(need(i));
         else if (a == "--device") o.device = std::stoi(need(i));
         else if (a == "--windows") o.windows = (uint32_t)std::stoul(need(i));
@@ -363,8 +372,9 @@ private:
 class RecordUploader {
 public:
     // one records context per device: every chunk goes to each of them (one rank per device reads its windows out of it)
-    RecordUploader(std::vector<std::shared_future<std::pair<int, jl_ctx *>>> ctx_up, uint64_t file_bytes, bool want_qual)
-        : ctx_up_(std::move(ctx_up)), file_bytes_(file_bytes), want_qual_(want_qual), th_([this] { run(); })
+    // want_qual: the chunks carry the folded quality bytes; qv_mask: the filter as one bit per base instead (IngestOptions::qv_mask)
+    RecordUploader(std::vector<std::shared_future<std::pair<int, jl_ctx *>>> ctx_up, uint64_t file_bytes, bool want_qual, bool qv_mask = false)
+        : ctx_up_(std::move(ctx_up)), file_bytes_(file_bytes), want_qual_(want_qual && !qv_mask), qv_mask_(want_qual && qv_mask), th_([this] { run(); })
     {
     }
     ~RecordUploader() { finish(); }
@@ -439,6 +449,14 @@ private:
     void gather(const RecordArrays &c)
     {
         const size_t n = c.pos.size();
+        if (qv_mask_ && (big_.seq4.size() & 3u)) {
+            // a chunk's mask begins at its first base: every chunk begins on four bytes of the gathered bases, a whole byte of the
+            // gathered mask (the read before ends where the gap does: offsets may leave gaps)
+            const size_t padded = (big_.seq4.size() + 3u) & ~(size_t)3u;
+            if (padded > big_.seq4.capacity()) crew_.wait();      // (it moves: nobody may be copying into the old place)
+            big_.seq4.resize(padded, 0);
+            big_.seq_off.back() = big_.seq4.size();
+        }
         const uint64_t cb = big_.cigar.size(), sb = big_.seq4.size(), qb = big_.qual.size();
         big_.pos.insert(big_.pos.end(), c.pos.begin(), c.pos.end());
         gather_array(big_.cigar, c.cigar);
@@ -447,12 +465,13 @@ private:
             big_.cig_off.push_back(cb + c.cig_off[i] - c.cig_off[0]);
             big_.seq_off.push_back(sb + c.seq_off[i] - c.seq_off[0]);
         }
+        if (qv_mask_) gather_array(big_.qmask, c.qmask);
         if (want_qual_) {
             gather_array(big_.qual, c.qual);
             for (size_t i = 1; i <= n; ++i) big_.qual_off.push_back(qb + c.qual_off[i] - c.qual_off[0]);
         }
     }
-    size_t gathered_bytes() const { return big_.seq4.size() + big_.qual.size() + 4 * big_.cigar.size(); }
+    size_t gathered_bytes() const { return big_.seq4.size() + big_.qual.size() + big_.qmask.size() + 4 * big_.cigar.size(); }
     bool contexts_ready() const
     {
         for (const auto &f : ctx_up_)
@@ -485,9 +504,13 @@ private:
         const auto t = std::chrono::steady_clock::now();
         for (jl_ctx *dst : ctxs_) {
             if (rc_ != JL_OK) break;
-            rc_ = jl_records_append(dst, big_.pos.size(), big_.pos.data(), big_.cigar.data(), big_.cig_off.data(), big_.seq4.data(),
-                                    big_.seq_off.data(), want_qual_ ? big_.qual.data() : nullptr,
-                                    want_qual_ ? big_.qual_off.data() : nullptr);
+            if (qv_mask_)
+                rc_ = jl_records_append_masked(dst, big_.pos.size(), big_.pos.data(), big_.cigar.data(), big_.cig_off.data(),
+                                               big_.seq4.data(), big_.seq_off.data(), big_.qmask.data());
+            else
+                rc_ = jl_records_append(dst, big_.pos.size(), big_.pos.data(), big_.cigar.data(), big_.cig_off.data(), big_.seq4.data(),
+                                        big_.seq_off.data(), want_qual_ ? big_.qual.data() : nullptr,
+                                        want_qual_ ? big_.qual_off.data() : nullptr);
             if (rc_ != JL_OK) failed_ = dst;
         }
         const double ms = ms_since(t);
@@ -505,6 +528,7 @@ private:
             big_.seq4.reserve(seq_hint);
             big_.cigar.reserve(seq_hint / 8);
             if (want_qual_) big_.qual.reserve(2 * seq_hint);
+            if (qv_mask_) big_.qmask.reserve(seq_hint / 4 + 64);
         }
         for (;;) {
             std::deque<RecordArrays> got;
@@ -549,7 +573,7 @@ private:
     }
     std::vector<std::shared_future<std::pair<int, jl_ctx *>>> ctx_up_;
     uint64_t file_bytes_;
-    bool want_qual_;
+    bool want_qual_, qv_mask_;
     std::mutex m_;
     std::condition_variable cv_;
     std::deque<RecordArrays> q_;
@@ -1290,7 +1314,8 @@ private:
         IngestOptions io;
         io.min_qv = opt_.min_qv;
         io.min_rq = opt_.min_rq;
-        std::unique_ptr<RecordUploader> uploader(new RecordUploader({up}, file_bytes(l.bam), opt_.min_qv > 0));
+        io.qv_mask = opt_.qv_upload_mask;
+        std::unique_ptr<RecordUploader> uploader(new RecordUploader({up}, file_bytes(l.bam), opt_.min_qv > 0, io.qv_mask));
         Decoded dec;
         try {
             RecordArrays rec;
@@ -1501,6 +1526,7 @@ int main(int argc, char **argv)
         IngestOptions io;
         io.min_qv = opt.min_qv;
         io.min_rq = opt.min_rq;
+        io.qv_mask = opt.qv_upload_mask;
         // the GPU context comes up (runtime start, stream, pinned blocks) while the host reads the BAM
         const bool need_gpu = !opt.outputs.empty() || opt.fuse_only;
         std::vector<std::shared_future<std::pair<int, jl_ctx *>>> ctx_ups;
@@ -1512,7 +1538,7 @@ int main(int argc, char **argv)
                     const int rc = jl_ctx_create(dev, nullptr, &c);
                     return std::make_pair(rc, c);
                 }).share());
-            uploader.reset(new RecordUploader(ctx_ups, file_bytes(opt.bam), opt.min_qv > 0));
+            uploader.reset(new RecordUploader(ctx_ups, file_bytes(opt.bam), opt.min_qv > 0, io.qv_mask));
         }
         RecordArrays rec;
         const Decoded dec = decode_bam(opt.bam, io, uploader.get(), rec);

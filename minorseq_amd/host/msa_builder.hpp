@@ -20,6 +20,8 @@ struct IngestOptions {
     uint32_t min_qv = 0;    // bases whose lowest QV (QUAL and the rich-QV tracks dq/iq/sq when present) is below this
                             // become N (doc/JULIET.md:256-259; threshold UNPINNED); 0 = off
     double min_rq = 0.0;    // skip reads with a lower rq tag; 0 = off (doc/JULIET.md:56 leaves this to the user)
+    bool qv_mask = false;   // the record decoder hands the filter on as one bit per base (RecordArrays::qmask) instead of the folded
+                            // quality bytes: the device's mask form (jl_records_append_masked)
 };
 
 // dst[i] = min(dst[i], track[i] - 33) over n bases, as unsigned bytes: a rich-QV track (phred + 33, a character per base) folded into
@@ -40,6 +42,32 @@ inline void min_with_track(uint8_t *dst, const char *track, size_t n)
     for (; i < n; ++i) {
         const uint8_t v = (uint8_t)(track[i] - 33);
         if (v < dst[i]) dst[i] = v;
+    }
+}
+
+// The filter of n bases as bits: bit `bit` + i of `mask` is set when q[i] < t (t <= 127, so 0xFF — nothing known — never is), sixteen
+// bases a compare.  The bits are ORed in: bytes that a read before has begun keep theirs, new bytes come cleared.
+inline void mask_low_quals(uint8_t *mask, uint64_t bit, const uint8_t *q, size_t n, uint8_t t)
+{
+    auto put = [&](uint32_t m, size_t nbits) {      // nbits <= 16 flags at `bit`
+        const uint32_t v = m << (bit & 7u);
+        uint8_t *b = mask + (bit >> 3);
+        for (size_t k = 0, nb = ((bit & 7u) + nbits + 7u) / 8u; k < nb; ++k) b[k] |= (uint8_t)(v >> (8u * k));
+        bit += nbits;
+    };
+    size_t i = 0;
+#if defined(__SSE2__)
+    const __m128i tv = _mm_set1_epi8((char)t);
+    for (; i + 16 <= n; i += 16) {
+        const __m128i v = _mm_loadu_si128(reinterpret_cast<const __m128i *>(q + i));
+        put(~(uint32_t)_mm_movemask_epi8(_mm_cmpeq_epi8(_mm_max_epu8(v, tv), v)) & 0xFFFFu, 16);      // (max(v, t) == v: v >= t)
+    }
+#endif
+    for (; i < n; i += 16) {
+        const size_t nb = std::min<size_t>(16, n - i);
+        uint32_t m = 0;
+        for (size_t k = 0; k < nb; ++k) m |= (q[i + k] < t ? 1u : 0u) << k;
+        put(m, nb);
     }
 }
 
@@ -179,10 +207,13 @@ struct RecordArrays {
     std::vector<uint32_t, HugeAlloc<uint32_t>> cigar;
     std::vector<uint64_t> cig_off{0}, seq_off{0}, qual_off{0};
     std::vector<uint8_t, HugeAlloc<uint8_t>> seq4, qual;
+    // IngestOptions::qv_mask: the filter as one bit per base, bit 2 * (byte of seq4) + (base of the byte), (seq4.size() + 3) / 4
+    // bytes — the layout of jl_records_append_masked for arrays whose seq_off[0] is 0; `qual` is scratch then, `qual_off` unused
+    std::vector<uint8_t, HugeAlloc<uint8_t>> qmask;
     std::vector<std::string> names;
     void clear()   // keeps the capacity: chunks are recycled
     {
-        pos.clear(); cigar.clear(); seq4.clear(); qual.clear(); names.clear();
+        pos.clear(); cigar.clear(); seq4.clear(); qual.clear(); qmask.clear(); names.clear();
         cig_off.assign(1, 0); seq_off.assign(1, 0); qual_off.assign(1, 0);
     }
 };
@@ -248,7 +279,17 @@ inline bool parse_record(const uint8_t *p, size_t len, const IngestOptions &opt,
     out.seq4.resize(s_at + (o_qual - o_seq));
     memcpy(out.seq4.data() + s_at, p + o_seq, o_qual - o_seq);
     out.seq_off.push_back(out.seq4.size());
-    if (want_qual) {
+    if (want_qual && opt.qv_mask) {
+        // the effective qualities of this read only, folded as below, then one compare per sixteen bases: its bits of the mask
+        out.qual.resize(l_seq);
+        memcpy(out.qual.data(), p + o_qual, l_seq);
+        for (int k = 0; k < 3; ++k) min_with_track(out.qual.data(), aux.track[k], std::min<size_t>(aux.len[k], l_seq));
+        const size_t m_at = out.qmask.size(), m_end = (out.seq4.size() + 3) / 4;
+        out.qmask.resize(m_end);
+        memset(out.qmask.data() + m_at, 0, m_end - m_at);
+        mask_low_quals(out.qmask.data(), 2 * (uint64_t)s_at, out.qual.data(), l_seq, (uint8_t)std::min<uint32_t>(opt.min_qv, 127u));
+        out.qual.clear();
+    } else if (want_qual) {
         const size_t q_at = out.qual.size();
         out.qual.resize(q_at + l_seq);
         memcpy(out.qual.data() + q_at, p + o_qual, l_seq);
