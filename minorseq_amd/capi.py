@@ -257,6 +257,16 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _record_arrays(pos, cigar, cig_off, seq4, seq_off, qual, qual_off, qmask):
+    """The arrays of aligned records as the library takes them (qual, qual_off: None without qualities); qualities or a mask, not both."""
+    if qmask is not None and qual is not None:
+        raise ValueError("records carry qualities or a mask, not both")
+    if qual is not None:
+        qual, qual_off = np.ascontiguousarray(qual, dtype=np.uint8), np.ascontiguousarray(qual_off, dtype=np.uint64)
+    return (np.ascontiguousarray(pos, dtype=np.int32), np.ascontiguousarray(cigar, dtype=np.uint32), np.ascontiguousarray(cig_off, dtype=np.uint64),
+            np.ascontiguousarray(seq4, dtype=np.uint8), np.ascontiguousarray(seq_off, dtype=np.uint64), qual, qual_off)
+
+
 class _LazyIds:
     """The per-read ids of a run view: packed bytes in pinned memory + their width; expands to uint16 on first use
     (a step loop that only reads the small results never touches them)."""
@@ -342,18 +352,9 @@ class Juliet:
     def ingest_records(self, n_cols, win_begin, pos, cigar, cig_off, seq4, seq_off, qual=None, qual_off=None, min_qv=0, qmask=None):
         """Aligned records (BAM-decoded arrays) -> resident matrix, cigar expansion on the device.  `qmask`: the filter as one
         bit per base (jl_msa_ingest_records_masked, layout in include/juliet_hip.h) instead of qualities."""
-        pos = np.ascontiguousarray(pos, dtype=np.int32)
-        cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
-        cig_off = np.ascontiguousarray(cig_off, dtype=np.uint64)
-        seq4 = np.ascontiguousarray(seq4, dtype=np.uint8)
-        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
-        if qual is not None:
-            qual = np.ascontiguousarray(qual, dtype=np.uint8)
-            qual_off = np.ascontiguousarray(qual_off, dtype=np.uint64)
+        pos, cigar, cig_off, seq4, seq_off, qual, qual_off = _record_arrays(pos, cigar, cig_off, seq4, seq_off, qual, qual_off, qmask)
         n = len(pos)
         if qmask is not None:
-            if qual is not None:
-                raise ValueError("records carry qualities or a mask, not both")
             qmask = np.ascontiguousarray(qmask, dtype=np.uint8)
             self._chk(self.lib.jl_msa_ingest_records_masked(self.h, n, n_cols, win_begin, _p(pos), _p(cigar), _p(cig_off), _p(seq4),
                                                             _p(seq_off), _p(qmask), min_qv))
@@ -368,16 +369,7 @@ class Juliet:
         """The same through jl_records_begin / _append / _finish, `chunk_reads` records per append; every chunk passes
         slices of the caller's arrays with offsets that do not start at 0 (the library rebases them).  `qmask` (for the whole
         arrays, relative to seq_off[0]): every chunk's mask is cut out of it, re-based to the chunk's first base."""
-        if qmask is not None and qual is not None:
-            raise ValueError("records carry qualities or a mask, not both")
-        pos = np.ascontiguousarray(pos, dtype=np.int32)
-        cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
-        cig_off = np.ascontiguousarray(cig_off, dtype=np.uint64)
-        seq4 = np.ascontiguousarray(seq4, dtype=np.uint8)
-        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
-        if qual is not None:
-            qual = np.ascontiguousarray(qual, dtype=np.uint8)
-            qual_off = np.ascontiguousarray(qual_off, dtype=np.uint64)
+        pos, cigar, cig_off, seq4, seq_off, qual, qual_off = _record_arrays(pos, cigar, cig_off, seq4, seq_off, qual, qual_off, qmask)
         n = len(pos)
         hq = hints[3] if qual is not None else 0
         self._chk(self.lib.jl_records_begin(self.h, hints[0], hints[1], hints[2], hq))
@@ -398,16 +390,7 @@ class Juliet:
     def records_upload(self, pos, cigar, cig_off, seq4, seq_off, qual=None, qual_off=None, qmask=None):
         """jl_records_begin + one jl_records_append: the records stay resident on this context (for records_window /
         records_window_async on other contexts of the device) until records_drop.  `qmask`: jl_records_append_masked."""
-        if qmask is not None and qual is not None:
-            raise ValueError("records carry qualities or a mask, not both")
-        pos = np.ascontiguousarray(pos, dtype=np.int32)
-        cigar = np.ascontiguousarray(cigar, dtype=np.uint32)
-        cig_off = np.ascontiguousarray(cig_off, dtype=np.uint64)
-        seq4 = np.ascontiguousarray(seq4, dtype=np.uint8)
-        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64)
-        if qual is not None:
-            qual = np.ascontiguousarray(qual, dtype=np.uint8)
-            qual_off = np.ascontiguousarray(qual_off, dtype=np.uint64)
+        pos, cigar, cig_off, seq4, seq_off, qual, qual_off = _record_arrays(pos, cigar, cig_off, seq4, seq_off, qual, qual_off, qmask)
         n = len(pos)
         self._chk(self.lib.jl_records_begin(self.h, n, len(cigar), len(seq4), len(qual) if qual is not None else 0))
         if qmask is not None:

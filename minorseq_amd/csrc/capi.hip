@@ -1,4 +1,4 @@
-// capi.hip — the C ABI of include/juliet_hip.h: context, residency, planning, launches, copies.
+// capi.hip — the C ABI of include/juliet_hip.h: context, residency, planning, launches, copies (the record stream: capi_records.hip).
 // No compute happens on the host here and there is no CPU fallback: every entry point needs a gfx950 device.
 #include <stdarg.h>
 #include <stddef.h>
@@ -132,8 +132,6 @@ static void free_msa(jl_ctx *ctx)
     ctx->msa_capacity = 0;
 }
 
-static void records_drop(jl_ctx *ctx);
-
 void *jl_ctx_stream(const jl_ctx *ctx) { return ctx ? (void *)ctx->stream : nullptr; }
 
 void jl_ctx_destroy(jl_ctx *ctx)
@@ -149,13 +147,13 @@ void jl_ctx_destroy(jl_ctx *ctx)
     if (ctx->h_read_hap) hipHostFree(ctx->h_read_hap);
     if (ctx->h_scratch) hipHostFree(ctx->h_scratch);
     free_msa(ctx);
-    records_drop(ctx);
+    jl_records_release(ctx);
     void *ptrs[] = {ctx->d_pos_gene, ctx->d_pos_codon, ctx->d_pos_col, ctx->d_pos_refcfg, ctx->d_col_head, ctx->d_pos_next, ctx->d_guess, ctx->d_chunks,
                     ctx->d_counts, ctx->d_called, ctx->d_staged, ctx->d_drm, ctx->d_variants, ctx->d_nvar, ctx->d_meta, ctx->d_vpcols,
                     ctx->d_col2pos, ctx->d_varcol, ctx->d_keys, ctx->d_flagw, ctx->d_read_slot, ctx->d_read_hap,
                     ctx->d_slot_rep, ctx->d_slot_count, ctx->d_slot_key, ctx->d_slot_hap, ctx->d_occupied, ctx->d_hap_count,
                     ctx->d_hap_pattern, ctx->d_hit, ctx->d_cooc, ctx->d_pack, ctx->d_sync,
-                    ctx->d_ins_len, ctx->d_ins_base, ctx->d_ing_runs, ctx->d_ing_nruns, ctx->d_ing_desc, ctx->d_ing_count, ctx->d_ing_slow,
+                    ctx->d_ins_len, ctx->d_ins_base,
                     ctx->d_exp_count,
                     ctx->d_exp_pattern, ctx->d_exp_hap, ctx->d_blockcat, ctx->d_slot_key_a, ctx->d_slot_key_b, ctx->d_occ_a, ctx->d_occ_b};
     for (void *p : ptrs)
@@ -288,386 +286,6 @@ int jl_msa_pack_rows(jl_ctx *ctx, const uint8_t *rows, uint64_t n_reads, uint32_
     }
     hipFree(d_rows);
     if (e != hipSuccess) return jl_fail(ctx, JL_ERR_DEVICE, "pack_rows: %s", hipGetErrorString(e));
-    return JL_OK;
-}
-
-// Aligned records straight to the resident layout: cigar expansion, QV masking and the transpose all run
-// on the device.  Arrays are what a BAM decoder holds: per read its leftmost position, its
-// cigar words (len << 4 | op), its 4-bit packed bases exactly as stored in BAM, optionally its qualities.
-// Streamed form: jl_records_begin / jl_records_append (any number of chunks, e.g. one per inflated BGZF batch,
-// so the upload hides under the decode of the next chunk) / jl_records_finish (alloc + kernels).
-static void records_drop(jl_ctx *ctx)
-{
-    jl_records &r = ctx->rec;
-    void *tmp[] = {r.d_seq, r.d_cig, r.d_co, r.d_so, r.d_pos, r.d_qual, r.d_qo, r.d_mask};
-    for (void *p : tmp)
-        if (p) hipFree(p);
-    r = jl_records();
-}
-
-// room for `need` elements of `elem` bytes (+pad bytes behind them); what is already there moves along
-static hipError_t records_room_bytes(jl_ctx *ctx, void **d, size_t *cap, size_t elem, size_t used, size_t need, size_t pad_bytes)
-{
-    if (*d && need <= *cap) return hipSuccess;
-    const size_t ncap = std::max<size_t>({need, *cap + *cap / 2, (size_t)1024});
-    void *nd = nullptr;
-    hipError_t e = hipMalloc(&nd, ncap * elem + pad_bytes);
-    if (e != hipSuccess) return e;
-    if (*d && used) e = hipMemcpyAsync(nd, *d, used * elem, hipMemcpyDeviceToDevice, ctx->stream);
-    if (*d) {
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        hipFree(*d);
-    }
-    *d = nd;
-    *cap = ncap;
-    return e;
-}
-#define records_room(ctx, d, cap, used, need, pad) records_room_bytes(ctx, (void **)&(d), &(cap), sizeof(*(d)), used, need, pad)
-
-int jl_records_begin(jl_ctx *ctx, uint64_t reads_hint, uint64_t cigar_words_hint, uint64_t seq_bytes_hint, uint64_t qual_bytes_hint)
-{
-    if (!ctx) return JL_ERR_ARG;
-    JL_HIP(ctx, hipSetDevice(ctx->device));
-    records_drop(ctx);
-    jl_records &r = ctx->rec;
-    r.open = true;
-    hipError_t e = records_room(ctx, r.d_pos, r.cap_pos, 0, (size_t)reads_hint, 0);
-    if (e == hipSuccess) e = records_room(ctx, r.d_co, r.cap_co, 0, (size_t)reads_hint + 1, 0);
-    if (e == hipSuccess) e = records_room(ctx, r.d_so, r.cap_so, 0, (size_t)reads_hint + 1, 0);
-    if (e == hipSuccess) e = records_room(ctx, r.d_cig, r.cap_cig, 0, (size_t)cigar_words_hint, 64);
-    if (e == hipSuccess) e = records_room(ctx, r.d_seq, r.cap_seq, 0, (size_t)seq_bytes_hint, 64);
-    // (the qualities begin 16 bytes into their array: the ingest reads a piece's 32 qualities from up to six bytes before a read's first)
-    r.n_qual = 16;
-    if (e == hipSuccess && qual_bytes_hint) e = records_room(ctx, r.d_qual, r.cap_qual, 0, (size_t)qual_bytes_hint + 16, 64);
-    if (e == hipSuccess && qual_bytes_hint) e = records_room(ctx, r.d_qo, r.cap_qo, 0, (size_t)reads_hint + 1, 0);
-    if (e != hipSuccess) {
-        records_drop(ctx);
-        return jl_fail(ctx, e == hipErrorOutOfMemory ? JL_ERR_MEMORY : JL_ERR_DEVICE, "records: %s", hipGetErrorString(e));
-    }
-    return JL_OK;
-}
-
-// bytes of a mask of `seq_bytes` bytes of packed bases: a bit per nibble
-uint64_t jl_qmask_bytes(uint64_t seq_bytes) { return (seq_bytes + 3u) / 4u; }
-
-// The byte form's rule (kernels_ingest.hip mask_low_quals, slow_pair) on the host: bit 2 (seq_off[r] - seq_off[0]) + q is set when
-// base q of read r has a quality below min_qv (at most 127) that is not 0xFF.
-int jl_qmask_from_quals(uint64_t n_reads, const uint64_t *seq_off, const uint8_t *qual, const uint64_t *qual_off, uint32_t min_qv,
-                        uint8_t *qmask, uint64_t qmask_bytes)
-{
-    if (!seq_off || !qual_off || (!qmask && qmask_bytes)) return JL_ERR_ARG;
-    for (uint64_t r = 0; r < n_reads; ++r)
-        if (seq_off[r + 1] < seq_off[r] || qual_off[r + 1] < qual_off[r]) return JL_ERR_ARG;
-    if (qmask_bytes < jl_qmask_bytes(seq_off[n_reads] - seq_off[0])) return JL_ERR_ARG;
-    for (uint64_t r = 0; r < n_reads; ++r)      // (a read's bits lie inside its own bytes of the bases: two a byte)
-        if (qual_off[r + 1] - qual_off[r] > 2u * (seq_off[r + 1] - seq_off[r])) return JL_ERR_ARG;
-    if (qmask_bytes) memset(qmask, 0, (size_t)qmask_bytes);
-    if (n_reads && !qual && qual_off[n_reads] != qual_off[0]) return JL_ERR_ARG;
-    const uint32_t t = std::min<uint32_t>(min_qv, 127u);
-    for (uint64_t r = 0; r < n_reads; ++r) {
-        const uint8_t *q = qual + qual_off[r];
-        const uint64_t n = qual_off[r + 1] - qual_off[r], i0 = 2u * (seq_off[r] - seq_off[0]);
-        for (uint64_t b = 0; b < n; ++b)
-            if (q[b] < t && q[b] != 0xFFu) qmask[(i0 + b) >> 3] |= (uint8_t)(1u << ((i0 + b) & 7u));
-    }
-    return JL_OK;
-}
-
-// jl_records_append (qmask null, masked false) and jl_records_append_masked (no qualities, masked true)
-static int records_append(jl_ctx *ctx, uint64_t n_reads, const int32_t *pos, const uint32_t *cigar, const uint64_t *cig_off,
-                          const uint8_t *seq4, const uint64_t *seq_off, const uint8_t *qual, const uint64_t *qual_off,
-                          const uint8_t *qmask, bool masked)
-{
-    jl_records &R = ctx->rec;
-    if (!R.open) return jl_fail(ctx, JL_ERR_STATE, "jl_records_append before jl_records_begin");
-    if (masked && !qmask) {
-        records_drop(ctx);
-        return jl_fail(ctx, JL_ERR_ARG, "jl_records_append_masked: no mask (a stream without a filter takes jl_records_append without qualities)");
-    }
-    if (R.n_reads && masked != R.masked) {
-        records_drop(ctx);
-        return jl_fail(ctx, JL_ERR_ARG, "records: either every chunk carries a mask (jl_records_append_masked) or none does");
-    }
-    if (R.n_reads && (qual != nullptr) != R.have_qual) {
-        records_drop(ctx);
-        return jl_fail(ctx, JL_ERR_ARG, "records: either every chunk carries qualities or none does");
-    }
-    if (!n_reads) return JL_OK;
-    const uint64_t first = R.n_reads;
-    // a chunk that fails validation ends the stream (jl_records_begin starts over).  Here: the offsets, which the uploads
-    // below follow; what the cigars say — an 'M', more bases than the record holds — is checked where they are walked, on
-    // the device (cigar_walk_kernel, cigar_runs_kernel for long reads), and reported by the build (jl_records_finish /
-    // jl_records_window): the loop over twelve million cigar words was most of an append on the host.
-    auto bad = [&](uint64_t r, const char *what, uint64_t v) {
-        records_drop(ctx);
-        return jl_fail(ctx, JL_ERR_ARG, what, (unsigned long long)(first + r), (unsigned long long)v);
-    };
-    for (uint64_t r = 0; r < n_reads; ++r)
-        if (cig_off[r + 1] < cig_off[r] || seq_off[r + 1] < seq_off[r] || (qual && qual_off[r + 1] < qual_off[r]))
-            return bad(r, "record %llu: offsets must not decrease", 0);
-    // ... and whether a read needs the ingest's launch for long reads: only a read with more ops than entries fit can, and a CCS
-    // sample has few of those — their cigars are looked at here, a word per read of the chunk at most (then: "maybe").  Only
-    // behind the check of EVERY offset: then each read's cigar lies within [cig_off[0], cig_off[n_reads]), the caller's array.
-    const uint64_t short_ops = jl_ingest_short_ops();
-    uint64_t looked = 0;
-    for (uint64_t r = 0; r < n_reads; ++r) {
-        const uint64_t n_ops = cig_off[r + 1] - cig_off[r];
-        if (n_ops > short_ops && !R.maybe_long) {
-            looked += n_ops;
-            R.maybe_long = looked > n_reads + 4096u || jl_ingest_read_is_long(cigar + cig_off[r], n_ops);
-        }
-    }
-    JL_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    // the chunk's arrays start wherever its offsets say; on the device everything is one run of arrays
-    const uint64_t c0 = cig_off[0], s0 = seq_off[0], q0 = qual ? qual_off[0] : 0;
-    const size_t n_cig = (size_t)(cig_off[n_reads] - c0), n_seq = (size_t)(seq_off[n_reads] - s0),
-                 n_q = qual ? (size_t)(qual_off[n_reads] - q0) : 0;
-    const size_t nr = (size_t)R.n_reads;
-    // A masked stream's chunks begin on 16 bytes of the resident bases (offsets may leave gaps: nobody's bases), so that the chunk's
-    // mask — a bit per nibble, relative to the chunk's first base — begins on a dword of the resident mask, at a quarter of the
-    // bases' offset: bit 2 x byte + nibble, for every read of the stream, which is where the kernels look.
-    const uint64_t seq_at = masked ? (R.n_seq + 15u) & ~(uint64_t)15u : R.n_seq;
-    const size_t n_mask = masked ? (size_t)jl_qmask_bytes(n_seq) : 0;
-    hipError_t e = records_room(ctx, R.d_pos, R.cap_pos, nr, nr + n_reads, 0);
-    if (e == hipSuccess) e = records_room(ctx, R.d_co, R.cap_co, nr + 1, nr + n_reads + 1, 0);
-    if (e == hipSuccess) e = records_room(ctx, R.d_so, R.cap_so, nr + 1, nr + n_reads + 1, 0);
-    if (e == hipSuccess) e = records_room(ctx, R.d_cig, R.cap_cig, (size_t)R.n_cig, (size_t)R.n_cig + n_cig, 64);
-    // the kernel reads the bases in aligned 32-byte pieces: padding behind them
-    if (e == hipSuccess) e = records_room(ctx, R.d_seq, R.cap_seq, (size_t)R.n_seq, (size_t)seq_at + n_seq, 64);
-    // (the mask's share of those 64 bytes: a piece's dword of flags lies inside the allocation wherever the piece does)
-    // (its first allocation follows the bases' — the hint of jl_records_begin — so that it grows when they do, not chunk after chunk)
-    if (e == hipSuccess && masked)
-        e = records_room(ctx, R.d_mask, R.cap_mask, (size_t)jl_qmask_bytes(R.n_seq),
-                         std::max((size_t)(seq_at / 4u) + n_mask, R.d_mask ? (size_t)0 : R.cap_seq / 4u), 16);
-    if (e == hipSuccess && qual) e = records_room(ctx, R.d_qual, R.cap_qual, (size_t)R.n_qual, (size_t)R.n_qual + n_q, 64);
-    if (e == hipSuccess && qual) e = records_room(ctx, R.d_qo, R.cap_qo, nr + 1, nr + n_reads + 1, 0);
-    std::vector<uint64_t> off((size_t)(n_reads + 1) * (qual ? 3 : 2));
-    uint64_t *co = off.data(), *so = co + n_reads + 1, *qo = so + n_reads + 1;
-    for (uint64_t r = 0; r <= n_reads; ++r) {
-        co[r] = cig_off[r] - c0 + R.n_cig;
-        so[r] = seq_off[r] - s0 + seq_at;
-        if (qual) qo[r] = qual_off[r] - q0 + R.n_qual;
-    }
-    const size_t off_bytes = (size_t)(n_reads + 1) * 8;
-    if (e == hipSuccess && n_seq) e = hipMemcpyAsync(R.d_seq + seq_at, seq4 + s0, n_seq, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && n_mask) e = hipMemcpyAsync(R.d_mask + seq_at / 4u, qmask, n_mask, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && n_cig) e = hipMemcpyAsync(R.d_cig + R.n_cig, cigar + c0, n_cig * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(R.d_co + nr, co, off_bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(R.d_so + nr, so, off_bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(R.d_pos + nr, pos, (size_t)n_reads * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && qual && n_q) e = hipMemcpyAsync(R.d_qual + R.n_qual, qual + q0, n_q, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && qual) e = hipMemcpyAsync(R.d_qo + nr, qo, off_bytes, hipMemcpyHostToDevice, st);
-    // the caller may reuse its chunk buffers (and `off` goes away) as soon as this returns
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        records_drop(ctx);
-        return jl_fail(ctx, e == hipErrorOutOfMemory ? JL_ERR_MEMORY : JL_ERR_DEVICE, "records: %s", hipGetErrorString(e));
-    }
-    R.have_qual = qual != nullptr;
-    R.masked = masked;
-    R.n_reads += n_reads;
-    R.n_cig += n_cig;
-    R.n_seq = seq_at + n_seq;
-    R.n_qual += n_q;
-    return JL_OK;
-}
-
-int jl_records_append(jl_ctx *ctx, uint64_t n_reads, const int32_t *pos, const uint32_t *cigar, const uint64_t *cig_off,
-                      const uint8_t *seq4, const uint64_t *seq_off, const uint8_t *qual, const uint64_t *qual_off)
-{
-    if (!ctx || !pos || !cigar || !cig_off || !seq4 || !seq_off || (qual && !qual_off)) return JL_ERR_ARG;
-    return records_append(ctx, n_reads, pos, cigar, cig_off, seq4, seq_off, qual, qual_off, nullptr, false);
-}
-
-int jl_records_append_masked(jl_ctx *ctx, uint64_t n_reads, const int32_t *pos, const uint32_t *cigar, const uint64_t *cig_off,
-                             const uint8_t *seq4, const uint64_t *seq_off, const uint8_t *qmask)
-{
-    if (!ctx || !pos || !cigar || !cig_off || !seq4 || !seq_off) return JL_ERR_ARG;
-    return records_append(ctx, n_reads, pos, cigar, cig_off, seq4, seq_off, nullptr, nullptr, qmask, true);
-}
-
-// room for `n` elements of `elem` bytes in one of the ingest's scratch arrays of `ctx` (grow-only; the old contents are not kept)
-static hipError_t ingest_room_bytes(jl_ctx *ctx, void **d, size_t *cap, size_t elem, size_t n)
-{
-    if (*d && *cap >= n) return hipSuccess;
-    if (*d) {
-        hipError_t e = hipStreamSynchronize(ctx->stream);   // an earlier build may still read it
-        if (e != hipSuccess) return e;
-        hipFree(*d);
-    }
-    *d = nullptr;
-    *cap = 0;
-    const size_t want = n + n / 8 + 64;
-    hipError_t e = hipMalloc(d, want * elem);
-    if (e == hipSuccess) *cap = want;
-    return e;
-}
-#define ingest_room(ctx, d, cap, n) ingest_room_bytes(ctx, (void **)(d), cap, sizeof(**(d)), n)
-
-// What the last record ingest into `ctx` found wrong with the records (its kernels have run): the first malformed read.
-// Called by the blocking builds, and by the first blocking call behind an enqueued one (jl_sync, jl_run_wait, the fetches).
-int jl_ingest_verdict(jl_ctx *ctx)
-{
-    if (!ctx->ing_check_pending) return JL_OK;
-    ctx->ing_check_pending = false;
-    // (through the context's pinned block: a process's first pageable device-to-host copy costs the runtime milliseconds)
-    unsigned long long both[2] = {0, ~0ull};     // (the counters, the verdict: kernels_ingest.hip jl_launch_ingest)
-    if (int rc = jl_fetch_to_host(ctx, ctx->d_ing_count, 16, both, 64)) return rc;
-    const unsigned long long w = both[1];
-    if (w == ~0ull) return JL_OK;
-    // (read: the word is all ones again for the builds to come — behind whatever this context has enqueued)
-    JL_HIP(ctx, hipMemsetAsync(ctx->d_ing_count + 2, 0xFF, 8, ctx->stream));
-    const unsigned long long r = w >> 8;
-    const unsigned code = (unsigned)(w & 0xFFu);
-    ctx->pileup_done = ctx->call_done = ctx->phase_done = false;
-    if (code == 1u) return jl_fail(ctx, JL_ERR_ARG, "record %llu: cigar M is forbidden in PacBio-compliant BAM (doc/JULIET.md:53)", r);
-    if (code == 4u) return jl_fail(ctx, JL_ERR_ARG, "record %llu: its cigar spans 2^30 reference bases or more", r);
-    if (code == 5u) return jl_fail(ctx, JL_ERR_STATE, "record %llu: a long cigar the upload had not seen (jl_ingest_read_is_long and cigar_walk_kernel disagree)", r);
-    return jl_fail(ctx, JL_ERR_ARG, "record %llu: its cigar consumes more %s than the record holds", r, code == 2u ? "bases" : "qualities");
-}
-
-// The resident matrix of `dst` from the records uploaded to `src` (the same context for jl_records_finish; another one of
-// the same device when one upload feeds several column windows).  The records stay.  Everything is ENQUEUED on dst's
-// stream (three launches + the insertion counters when asked for); `wait`: return when it has run.
-static int records_build(jl_ctx *src, jl_ctx *dst, uint32_t n_cols, uint32_t win_begin, uint32_t min_qv, bool wait)
-{
-    jl_records &R = src->rec;
-    int rc = jl_msa_alloc(dst, R.n_reads, n_cols, win_begin);
-    if (rc) return rc;
-    hipStream_t st = dst->stream;
-    hipError_t e = hipSuccess;
-    if (!R.n_reads) {   // nothing was appended: the offset arrays still need their first entry
-        e = records_room(src, R.d_co, R.cap_co, 0, 1, 0);
-        if (e == hipSuccess) e = records_room(src, R.d_so, R.cap_so, 0, 1, 0);
-        if (e == hipSuccess) e = records_room(src, R.d_pos, R.cap_pos, 0, 1, 0);
-        if (e == hipSuccess) e = records_room(src, R.d_cig, R.cap_cig, 0, 1, 64);
-        if (e == hipSuccess) e = records_room(src, R.d_seq, R.cap_seq, 0, 1, 64);
-        if (e == hipSuccess) e = hipMemsetAsync(R.d_co, 0, 8, st);
-        if (e == hipSuccess) e = hipMemsetAsync(R.d_so, 0, 8, st);
-    }
-    const uint32_t ns = jl_ingest_sweeps(n_cols);
-    const size_t nr = (size_t)R.n_reads;
-    if (e == hipSuccess) e = ingest_room(dst, &dst->d_ing_runs, &dst->ing_cap_runs, (size_t)R.n_cig + 3 * nr + 8);   // (three entries around a read's runs; + 8: the planes kernel reads entries four and eight at a time)
-    if (e == hipSuccess) e = ingest_room(dst, &dst->d_ing_nruns, &dst->ing_cap_reads, nr + 1);
-    if (e == hipSuccess) e = ingest_room(dst, &dst->d_ing_desc, &dst->ing_cap_desc, (nr + 1) * ns);
-    if (e == hipSuccess) e = ingest_room(dst, &dst->d_ing_slow, &dst->ing_cap_slow, jl_ingest_slow_room(dst));
-    if (e == hipSuccess && !dst->d_ing_count) {
-        e = hipMalloc(&dst->d_ing_count, 64);
-        // (counters zero, the verdict word — [2..3] — all ones: no malformed record seen; kernels_ingest.hip jl_launch_ingest)
-        if (e == hipSuccess) e = hipMemsetAsync(dst->d_ing_count, 0, 64, st);
-        if (e == hipSuccess) e = hipMemsetAsync(dst->d_ing_count + 2, 0xFF, 8, st);
-    }
-    dst->ins_valid = false;
-    if (e == hipSuccess && dst->track_insertions) {
-        if (dst->ins_capacity < n_cols) {
-            if (dst->d_ins_len) hipFree(dst->d_ins_len);
-            if (dst->d_ins_base) hipFree(dst->d_ins_base);
-            dst->d_ins_len = dst->d_ins_base = nullptr;
-            dst->ins_capacity = 0;
-            e = hipMalloc(&dst->d_ins_len, (size_t)n_cols * JL_INS_LEN_BINS * 4);
-            if (e == hipSuccess) e = hipMalloc(&dst->d_ins_base, (size_t)n_cols * JL_INS_MAX_BASES * 16);
-            if (e == hipSuccess) dst->ins_capacity = n_cols;
-        }
-        if (e == hipSuccess) e = hipMemsetAsync(dst->d_ins_len, 0, (size_t)n_cols * JL_INS_LEN_BINS * 4, st);
-        if (e == hipSuccess) e = hipMemsetAsync(dst->d_ins_base, 0, (size_t)n_cols * JL_INS_MAX_BASES * 16, st);
-        if (e == hipSuccess) {
-            jl_launch_insertions(dst, R.d_pos, R.d_cig, R.d_co, R.d_seq, R.d_so);
-            e = hipGetLastError();
-            dst->ins_valid = e == hipSuccess;
-        }
-    }
-    if (e == hipSuccess) {
-        jl_launch_ingest(dst, R.d_pos, R.d_cig, R.d_co, R.d_seq, R.d_so, R.have_qual ? R.d_qual : nullptr,
-                         R.have_qual ? R.d_qo : nullptr, R.masked ? R.d_mask : nullptr, min_qv, dst->d_ing_runs, dst->d_ing_nruns, dst->d_ing_desc, dst->d_ing_count,
-                         dst->d_ing_slow, R.maybe_long);
-        e = hipGetLastError();
-        dst->ing_check_pending = e == hipSuccess;
-        if (e == hipSuccess && wait) e = hipStreamSynchronize(st);
-    }
-    if (e != hipSuccess) return jl_fail(dst, e == hipErrorOutOfMemory ? JL_ERR_MEMORY : JL_ERR_DEVICE, "ingest: %s", hipGetErrorString(e));
-    return wait ? jl_ingest_verdict(dst) : JL_OK;
-}
-
-int jl_records_finish(jl_ctx *ctx, uint32_t n_cols, uint32_t win_begin, uint32_t min_qv)
-{
-    if (!ctx) return JL_ERR_ARG;
-    if (!ctx->rec.open) return jl_fail(ctx, JL_ERR_STATE, "jl_records_finish before jl_records_begin");
-    JL_HIP(ctx, hipSetDevice(ctx->device));
-    const int rc = records_build(ctx, ctx, n_cols, win_begin, min_qv, true);
-    records_drop(ctx);
-    return rc;
-}
-
-int jl_records_window(jl_ctx *records, jl_ctx *window, uint32_t n_cols, uint32_t win_begin, uint32_t min_qv)
-{
-    if (!records || !window) return JL_ERR_ARG;
-    if (!records->rec.open) return jl_fail(window, JL_ERR_STATE, "jl_records_window: no records uploaded (jl_records_begin / _append)");
-    if (records->device != window->device) return jl_fail(window, JL_ERR_ARG, "records and window are on different devices");
-    JL_HIP(window, hipSetDevice(window->device));
-    JL_HIP(window, hipStreamSynchronize(records->stream));   // the uploads are complete
-    return records_build(records, window, n_cols, win_begin, min_qv, true);
-}
-
-// The same, enqueued only: the window's matrix is complete when the window's stream reaches this point — a run enqueued
-// behind it on that stream (jl_run_async) reads it.  No allocation once a window of this shape has been built on `window`.
-int jl_records_window_async(jl_ctx *records, jl_ctx *window, uint32_t n_cols, uint32_t win_begin, uint32_t min_qv)
-{
-    if (!records || !window) return JL_ERR_ARG;
-    if (!records->rec.open) return jl_fail(window, JL_ERR_STATE, "jl_records_window_async: no records uploaded (jl_records_begin / _append)");
-    if (records->device != window->device) return jl_fail(window, JL_ERR_ARG, "records and window are on different devices");
-    JL_HIP(window, hipSetDevice(window->device));
-    return records_build(records, window, n_cols, win_begin, min_qv, false);
-}
-
-int jl_records_drop(jl_ctx *ctx)
-{
-    if (!ctx) return JL_ERR_ARG;
-    JL_HIP(ctx, hipSetDevice(ctx->device));
-    records_drop(ctx);
-    return JL_OK;
-}
-
-int jl_msa_ingest_records(jl_ctx *ctx, uint64_t n_reads, uint32_t n_cols, uint32_t win_begin, const int32_t *pos,
-                          const uint32_t *cigar, const uint64_t *cig_off, const uint8_t *seq4, const uint64_t *seq_off,
-                          const uint8_t *qual, const uint64_t *qual_off, uint32_t min_qv)
-{
-    if (!ctx || !pos || !cigar || !cig_off || !seq4 || !seq_off || (qual && !qual_off)) return JL_ERR_ARG;
-    int rc = jl_records_begin(ctx, n_reads, cig_off[n_reads] - cig_off[0], seq_off[n_reads] - seq_off[0],
-                              qual ? std::max<uint64_t>(qual_off[n_reads] - qual_off[0], 1) : 0);
-    if (rc == JL_OK) rc = jl_records_append(ctx, n_reads, pos, cigar, cig_off, seq4, seq_off, qual, qual_off);
-    if (rc == JL_OK) rc = jl_records_finish(ctx, n_cols, win_begin, min_qv);
-    else if (ctx->rec.open) records_drop(ctx);
-    return rc;
-}
-
-int jl_msa_ingest_records_masked(jl_ctx *ctx, uint64_t n_reads, uint32_t n_cols, uint32_t win_begin, const int32_t *pos,
-                                 const uint32_t *cigar, const uint64_t *cig_off, const uint8_t *seq4, const uint64_t *seq_off,
-                                 const uint8_t *qmask, uint32_t min_qv)
-{
-    if (!ctx || !pos || !cigar || !cig_off || !seq4 || !seq_off) return JL_ERR_ARG;
-    int rc = jl_records_begin(ctx, n_reads, cig_off[n_reads] - cig_off[0], seq_off[n_reads] - seq_off[0], 0);
-    if (rc == JL_OK) rc = jl_records_append_masked(ctx, n_reads, pos, cigar, cig_off, seq4, seq_off, qmask);
-    if (rc == JL_OK) rc = jl_records_finish(ctx, n_cols, win_begin, min_qv);
-    else if (ctx->rec.open) records_drop(ctx);
-    return rc;
-}
-
-int jl_msa_track_insertions(jl_ctx *ctx, int on)
-{
-    if (!ctx) return JL_ERR_ARG;
-    ctx->track_insertions = on != 0;
-    return JL_OK;
-}
-
-int jl_insertions_fetch(jl_ctx *ctx, uint32_t *len_hist, uint32_t *base_counts)
-{
-    if (!ctx) return JL_ERR_ARG;
-    if (!ctx->ins_valid) return jl_fail(ctx, JL_ERR_STATE, "no insertion counts: jl_msa_track_insertions(ctx, 1) before jl_msa_ingest_records");
-    JL_HIP(ctx, hipSetDevice(ctx->device));
-    if (len_hist) JL_HIP(ctx, hipMemcpyAsync(len_hist, ctx->d_ins_len, (size_t)ctx->n_cols * JL_INS_LEN_BINS * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (base_counts) JL_HIP(ctx, hipMemcpyAsync(base_counts, ctx->d_ins_base, (size_t)ctx->n_cols * JL_INS_MAX_BASES * 16, hipMemcpyDeviceToHost, ctx->stream));
-    JL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return JL_OK;
 }
 
@@ -1614,7 +1232,7 @@ int jl_run_async(jl_ctx *ctx, const jl_gene *genes, uint32_t n_genes, const uint
 int jl_run_wait_impl(jl_ctx *ctx)
 {
     int rc = jl_run_wait_seq(ctx, ctx->runs_launched);
-    if (rc == JL_OK && ctx->ing_check_pending) rc = jl_ingest_verdict(ctx);   // the run read a matrix an enqueued ingest made
+    if (rc == JL_OK && ctx->ing.check_pending) rc = jl_ingest_verdict(ctx);   // the run read a matrix an enqueued ingest made
     // a result block without its magic behind a phasing run: a launch with inline ids timed out (see jl_phase_rerun_ids_separate)
     if (rc == JL_OK && ctx->pack_valid && ctx->phase_done && ctx->h_pack && ctx->h_pack->magic != JL_PACK_MAGIC && !ctx->ids_separate)
         rc = jl_phase_rerun_ids_separate(ctx);

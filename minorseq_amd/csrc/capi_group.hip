@@ -507,7 +507,7 @@ int jl_group_exchange_collect(jl_group *g, jl_variant *all_rows, uint32_t *all_c
     // a window whose matrix an enqueued record ingest made: what that ingest found wrong with the records is reported before
     // tables computed from it are handed out (the run is over: the verdict word is final)
     for (jl_ctx *ctx : g->ctxs)
-        if (ctx->ing_check_pending)
+        if (ctx->ing.check_pending)
             if (int vrc = jl_ingest_verdict(ctx)) return group_fail(g, vrc, ctx->err.c_str());
     const uint32_t n = (uint32_t)g->ctxs.size();
     const uint8_t *base = g->x_host + g->x_region() * par;

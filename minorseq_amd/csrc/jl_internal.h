@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -305,20 +306,89 @@ void jl_launch_xw_assign(const jl_xw_assign_args *a, const uint16_t *host_tab, c
 void jl_launch_xw_fetch(const void *d_src, void *h_dst, uint64_t bytes, uint32_t *arrive, uint32_t *seq_dev, volatile uint32_t *seq_host,
                         hipStream_t st);
 
-// Records uploaded so far by jl_records_append: one run of device arrays, offsets rebased to it.
+inline int jl_hip_status(hipError_t e) { return e == hipErrorOutOfMemory ? JL_ERR_MEMORY : JL_ERR_DEVICE; }
+
+// A device array that grows: `cap` elements at `d`.  Making room returns HIP's error (jl_hip_status: the status it becomes).
+template <typename T>
+struct jl_dev_array {
+    T *d = nullptr;
+    size_t cap = 0;
+    // room for `need` elements (+ pad_bytes behind them); the first `used` move along, on `st`
+    hipError_t grow_keep(hipStream_t st, size_t used, size_t need, size_t pad_bytes)
+    {
+        if (d && need <= cap) return hipSuccess;
+        const size_t ncap = std::max<size_t>({need, cap + cap / 2, (size_t)1024});
+        T *nd = nullptr;
+        hipError_t e = hipMalloc(&nd, ncap * sizeof(T) + pad_bytes);
+        if (e != hipSuccess) return e;
+        if (d && used) e = hipMemcpyAsync(nd, d, used * sizeof(T), hipMemcpyDeviceToDevice, st);
+        if (d) {
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            hipFree(d);
+        }
+        d = nd;
+        cap = ncap;
+        return e;
+    }
+    // room for `n` elements, grow-only; the old contents are not kept
+    hipError_t grow_discard(hipStream_t st, size_t n)
+    {
+        if (d && cap >= n) return hipSuccess;
+        hipError_t e = d ? hipStreamSynchronize(st) : hipSuccess;   // what is enqueued on `st` may still read it
+        if (e != hipSuccess) return e;
+        release();
+        const size_t want = n + n / 8 + 64;
+        e = hipMalloc(&d, want * sizeof(T));
+        if (e == hipSuccess) cap = want;
+        return e;
+    }
+    void release()
+    {
+        if (d) hipFree(d);
+        d = nullptr, cap = 0;
+    }
+};
+
+// Records uploaded so far by jl_records_append: one run of device arrays, offsets rebased to it (capi_records.hip).
 struct jl_records {
     bool open = false, have_qual = false;
-    bool masked = false;     // a masked stream (jl_records_append_masked): d_mask holds a bit per nibble of d_seq, every chunk begins on 16 bytes of d_seq
-    uint8_t *d_seq = nullptr, *d_qual = nullptr, *d_mask = nullptr;
-    size_t cap_mask = 0;
-    uint32_t *d_cig = nullptr;
-    uint64_t *d_co = nullptr, *d_so = nullptr, *d_qo = nullptr;
-    int32_t *d_pos = nullptr;
-    size_t cap_seq = 0, cap_qual = 0, cap_cig = 0, cap_co = 0, cap_so = 0, cap_qo = 0, cap_pos = 0;
+    bool masked = false;     // a masked stream (jl_records_append_masked): `mask` holds a bit per nibble of `seq`, every chunk begins on 16 bytes of `seq`
+    jl_dev_array<uint8_t> seq, qual, mask;
+    jl_dev_array<uint32_t> cig;
+    jl_dev_array<uint64_t> co, so, qo;   // the reads' offsets into cig, seq, qual
+    jl_dev_array<int32_t> pos;
     uint64_t n_reads = 0, n_cig = 0, n_seq = 0, n_qual = 0;
     // does any read need the ingest's launch for long reads (kernels_ingest.hip jl_ingest_read_is_long)?  Found out at the upload for
     // the few reads a CCS sample has with more ops than entries fit; `true` as soon as looking would cost more than the launch
     bool maybe_long = false;
+    void release() { seq.release(), qual.release(), mask.release(), cig.release(), co.release(), so.release(), qo.release(), pos.release(); }
+};
+
+// How a build takes the QV filter: the planes kernel's template argument (kernels_ingest.hip kQvNone, kQvBytes, kQvMask).
+enum jl_qv_mode : uint32_t {
+    JL_QV_NONE = 0,    // no filter: min_qv 0, or a stream with neither qualities nor a mask
+    JL_QV_BYTES = 1,   // a quality byte per base against min_qv
+    JL_QV_MASK = 2,    // a bit per base (a masked stream; min_qv only switches the filter on)
+};
+inline jl_qv_mode jl_qv_mode_of(bool have_qual, bool masked, uint32_t min_qv)
+{
+    return min_qv == 0u ? JL_QV_NONE : have_qual ? JL_QV_BYTES : masked ? JL_QV_MASK : JL_QV_NONE;
+}
+
+// Scratch of the record ingest INTO a context (kernels_ingest.hip), kept between builds.
+struct jl_ingest_scratch {
+    jl_dev_array<uint2> runs;       // the reads' runs
+    jl_dev_array<uint32_t> nruns;
+    jl_dev_array<uint4> desc;       // one descriptor per (sweep, read): the run at every sweep's first column
+    jl_dev_array<uint2> slow;       // the units handed on to the planes kernel's second size
+    uint32_t *d_count = nullptr;    // 64 bytes: the counters of a build and the verdict word (jl_launch_ingest)
+    bool check_pending = false;     // an ingest ran (or is enqueued) whose verdict on the records has not been read yet
+    void release()
+    {
+        runs.release(), nruns.release(), desc.release(), slow.release();
+        if (d_count) hipFree(d_count);
+        d_count = nullptr;
+    }
 };
 
 enum class jl_phase_form : uint32_t {   // the pipeline that phases a context; the value is the plan's fast_only (phase_plan.h)
@@ -363,14 +433,7 @@ struct jl_ctx {
 
     // ---- aligned records on their way in (jl_records_begin / _append / _finish)
     jl_records rec;
-    // scratch of the record ingest INTO this context (kernels_ingest.hip), kept between builds: the reads' runs, the run at
-    // every sweep's first column, the units handed on to the planes kernel's second size
-    uint2 *d_ing_runs = nullptr;
-    uint32_t *d_ing_nruns = nullptr, *d_ing_count = nullptr;
-    uint4 *d_ing_desc = nullptr;      // one descriptor per (sweep, read): kernels_ingest.hip
-    uint2 *d_ing_slow = nullptr;
-    size_t ing_cap_runs = 0, ing_cap_reads = 0, ing_cap_desc = 0, ing_cap_slow = 0;
-    bool ing_check_pending = false;   // an ingest ran (or is enqueued) whose verdict on the records has not been read yet
+    jl_ingest_scratch ing;            // ... and of the builds into this context's matrix
 
     // ---- phasing sharded by reads: the groups of this matrix exported for the merge (jl_phase_groups_async / _fetch)
     bool phase_export = false;        // the phase launch in flight / last run exported instead of selecting
@@ -497,8 +560,7 @@ int jl_fail(jl_ctx *ctx, int status, const char *fmt, ...);
     do {                                                                                             \
         hipError_t e_ = (expr);                                                                      \
         if (e_ != hipSuccess)                                                                        \
-            return jl_fail(ctx, e_ == hipErrorOutOfMemory ? JL_ERR_MEMORY : JL_ERR_DEVICE, "%s: %s", \
-                           #expr, hipGetErrorString(e_));                                            \
+            return jl_fail(ctx, jl_hip_status(e_), "%s: %s", #expr, hipGetErrorString(e_));          \
     } while (0)
 
 // What `enqueue` (a callable returning a status) puts on `st`, captured and instantiated.  False: both stay null, the caller launches eagerly.
@@ -569,16 +631,15 @@ void jl_launch_consensus(jl_ctx *ctx, uint8_t *d_out);
 void jl_launch_clock(jl_ctx *ctx, hipStream_t st, uint32_t which);   // h_seq[8 + 2 which ..] = the device's 100 MHz clock
 uint32_t jl_ingest_short_ops();
 bool jl_ingest_read_is_long(const uint32_t *cigar, uint64_t n_ops);
-void jl_launch_ingest(jl_ctx *ctx, const int32_t *d_pos, const uint32_t *d_cigar, const uint64_t *d_cig_off,
-                      const uint8_t *d_seq4, const uint64_t *d_seq_off, const uint8_t *d_qual,
-                      const uint64_t *d_qual_off, const uint8_t *d_qmask, uint32_t min_qv, uint2 *d_runs, uint32_t *d_nruns, uint4 *d_desc,
-                      uint32_t *d_slow_count, uint2 *d_slow, bool maybe_long);
+// the matrix of `dst` (allocated, at least one read) from the records R, with the scratch of `dst` (made by the caller: capi_records.hip records_build)
+void jl_launch_ingest(jl_ctx *dst, const jl_records &R, uint32_t min_qv);
 uint32_t jl_ingest_sweeps(uint32_t n_cols);
 size_t jl_ingest_slow_room(const jl_ctx *ctx);
 extern "C" int jl_ingest_verdict(jl_ctx *ctx);
+// capi_records.hip: frees the records uploaded to `ctx` and the scratch of the builds into it (jl_ctx_destroy)
+void jl_records_release(jl_ctx *ctx);
 void jl_launch_regroup(jl_ctx *ctx, const uint16_t *d_hap_of_group, uint32_t n_groups, uint32_t n_haplotypes, bool phased);
-void jl_launch_insertions(jl_ctx *ctx, const int32_t *d_pos, const uint32_t *d_cigar, const uint64_t *d_cig_off,
-                          const uint8_t *d_seq4, const uint64_t *d_seq_off);
+void jl_launch_insertions(jl_ctx *dst, const jl_records &R);
 void jl_launch_fisher_eval(jl_ctx *ctx, uint32_t n, const uint32_t *a, const uint32_t *c, const uint32_t *cov, int tail,
                            double *p, double *lp);
 // per-read ids in their packed form (4 / 8 / 16 bits, see JL_ID4_MAX_H) expanded to 16-bit ids on the host

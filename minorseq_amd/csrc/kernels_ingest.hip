@@ -747,7 +747,7 @@ __device__ __forceinline__ void mask_low_quals(const ingest_args &a, const piece
 
 // The input modes of the planes kernel: no filter; qualities, a byte a base, compared with min_qv here; the filter made by the
 // caller, a bit a base (jl_records_append_masked).
-constexpr uint32_t kQvNone = 0u, kQvBytes = 1u, kQvMask = 2u;
+constexpr uint32_t kQvNone = JL_QV_NONE, kQvBytes = JL_QV_BYTES, kQvMask = JL_QV_MASK;   // (jl_internal.h jl_qv_mode)
 
 // The filter of a piece's 32 bases as the caller made it, flag b = base b of the piece: byte k of `fl` goes onto the nibbles of S[k]
 // (flag 8 k + j -> nibble j), 15 (N) where it is set — three masked shifts spread eight bits to the low bit of eight nibbles,
@@ -1298,14 +1298,6 @@ __global__ __launch_bounds__(kThreads, (BIG ? 1 : kMinWgs)) void ingest_planes_k
     }
 }
 
-// the counters of a build: [0] pairs listed, [1] units handed on = 0; [2..3] the verdict word = all ones unless an earlier build's is still unread
-__global__ void ingest_init_kernel(uint32_t *count, uint32_t fresh_verdict)
-{
-    const uint32_t t = threadIdx.x;
-    if (t < 2u) count[t] = 0u;
-    else if (t < 4u && fresh_verdict) count[t] = 0xFFFFFFFFu;
-}
-
 }  // namespace
 
 uint32_t jl_ingest_sweeps(uint32_t n_cols) { return (n_cols + kSweep - 1u) / kSweep; }
@@ -1338,68 +1330,66 @@ bool jl_ingest_read_is_long(const uint32_t *cigar, uint64_t n_ops)
     return n_runs + 3u > kWalkEnt;
 }
 
-// d_runs: n_cig + 3 n_reads + 8 entries; d_nruns: n_reads; d_desc: n_reads x sweeps descriptors; d_slow: jl_ingest_slow_room() pairs.
-// d_slow_count, 64 bytes: [0] pairs listed, [1] units handed on — zeroed by the build's first launch; [2..3] the 64-bit word of the
-// first malformed record (all ones: none — so it is allocated, and so jl_ingest_verdict leaves it when it has read one; a build
-// whose predecessor's word has not been read yet folds its own into it, atomicMin).
-// Everything is enqueued on ctx->stream; nothing waits.
-void jl_launch_ingest(jl_ctx *ctx, const int32_t *d_pos, const uint32_t *d_cigar, const uint64_t *d_cig_off,
-                      const uint8_t *d_seq4, const uint64_t *d_seq_off, const uint8_t *d_qual,
-                      const uint64_t *d_qual_off, const uint8_t *d_qmask, uint32_t min_qv, uint2 *d_runs, uint32_t *d_nruns, uint4 *d_desc,
-                      uint32_t *d_slow_count, uint2 *d_slow, bool maybe_long)
+// The scratch of `dst` (capi_records.hip records_build): runs, n_cig + 3 n_reads + 8 entries; nruns, n_reads; desc, n_reads x sweeps
+// descriptors; slow, jl_ingest_slow_room() pairs.
+// d_count, 64 bytes: [0] pairs listed, [1] units handed on — zeroed by the first block of the build's first launch (cigar_walk_kernel);
+// [2..3] the 64-bit word of the first malformed record (all ones: none — so it is set when the block is allocated, and again by
+// jl_ingest_verdict when it has read one; a build whose predecessor's word has not been read yet folds its own into it, atomicMin).
+// Everything is enqueued on dst->stream; nothing waits.  dst->n_reads is not zero: the matrix has been allocated.
+void jl_launch_ingest(jl_ctx *dst, const jl_records &R, uint32_t min_qv)
 {
-    hipStream_t st = ctx->stream;
-    const uint32_t ns = jl_ingest_sweeps(ctx->n_cols);
-    // The counters are zeroed by the first launch (cigar_walk_kernel); the verdict word is all ones from its allocation on and again
-    // whenever a verdict has been read (jl_ingest_verdict): a build whose predecessor's verdict is still unread folds its own into it.
-    if (!ctx->n_reads) hipLaunchKernelGGL(ingest_init_kernel, dim3(1), dim3(64), 0, st, d_slow_count, 0u);
-    if (ctx->n_reads) {
-        unsigned long long *bad = reinterpret_cast<unsigned long long *>(d_slow_count + 2);
-        const uint64_t *qo = d_qual ? d_qual_off : nullptr;
-        hipLaunchKernelGGL(cigar_walk_kernel, dim3((uint32_t)((ctx->n_reads + kWalkReads - 1u) / kWalkReads)), dim3(256), 0, st,
-                           ctx->n_reads, d_pos, d_cigar, d_cig_off, d_seq_off, qo, ctx->win_begin, ctx->n_cols, ns, d_runs, d_nruns, d_desc, bad, d_slow_count, maybe_long ? 1u : 0u);
-        // (the launch for the long reads: not when the upload has looked and found none — every CCS sample: 6 us of a build)
-        if (maybe_long)
-            hipLaunchKernelGGL(cigar_runs_kernel, dim3((uint32_t)std::min<uint64_t>(kRunsLongGrid, (ctx->n_reads + 255u) / 256u)), dim3(256), 0, st,
-                               ctx->n_reads, d_pos, d_cigar, d_cig_off, d_seq_off, qo, ctx->win_begin, ctx->n_cols, ns, d_runs, d_nruns, d_desc, bad);
-    }
+    hipStream_t st = dst->stream;
+    const jl_ingest_scratch &S = dst->ing;
+    const uint32_t ns = jl_ingest_sweeps(dst->n_cols);
+    const jl_qv_mode mode = jl_qv_mode_of(R.have_qual, R.masked, min_qv);
+    unsigned long long *bad = reinterpret_cast<unsigned long long *>(S.d_count + 2);
+    // (the cigar kernels check a read's quality COUNT: the offsets whenever the stream has qualities, whatever min_qv is)
+    const uint64_t *qo = R.have_qual ? R.qo.d : nullptr;
+    hipLaunchKernelGGL(cigar_walk_kernel, dim3((uint32_t)((dst->n_reads + kWalkReads - 1u) / kWalkReads)), dim3(256), 0, st,
+                       dst->n_reads, R.pos.d, R.cig.d, R.co.d, R.so.d, qo, dst->win_begin, dst->n_cols, ns, S.runs.d, S.nruns.d, S.desc.d, bad, S.d_count, R.maybe_long ? 1u : 0u);
+    // (the launch for the long reads: not when the upload has looked and found none — every CCS sample: 6 us of a build)
+    if (R.maybe_long)
+        hipLaunchKernelGGL(cigar_runs_kernel, dim3((uint32_t)std::min<uint64_t>(kRunsLongGrid, (dst->n_reads + 255u) / 256u)), dim3(256), 0, st,
+                           dst->n_reads, R.pos.d, R.cig.d, R.co.d, R.so.d, qo, dst->win_begin, dst->n_cols, ns, S.runs.d, S.nruns.d, S.desc.d, bad);
     ingest_args a;
-    a.n_reads = ctx->n_reads;
-    a.n_cols = ctx->n_cols;
+    a.n_reads = dst->n_reads;
+    a.n_cols = dst->n_cols;
     a.n_sweeps = ns;
-    const uint64_t reads_pad = ctx->plane_stride * 8u;                 // a multiple of 1024: whole line groups of tiles
+    const uint64_t reads_pad = dst->plane_stride * 8u;                 // a multiple of 1024: whole line groups of tiles
     a.n_groups = (uint32_t)(reads_pad / 1024u);
     a.min_qv = std::min<uint32_t>(min_qv, 127u);   // (the byte-parallel compare of the QV path; BAM qualities end at 93)
-    a.cig_off = d_cig_off;
-    a.seq4 = d_seq4;
-    a.seq_off = d_seq_off;
-    const bool qv = d_qual != nullptr && min_qv != 0u;
-    a.qual = qv ? d_qual : nullptr;
-    a.qual_off = qv ? d_qual_off : nullptr;
-    // (a masked stream — jl_records_append_masked — has no qualities: d_qual is null then, and min_qv only switches the filter on)
-    const bool qm = d_qmask != nullptr && min_qv != 0u;
-    a.qmask = qm ? d_qmask : nullptr;
-    a.runs = d_runs;
-    a.nruns = d_nruns;
-    a.desc = d_desc;
-    a.slow_count = d_slow_count;
-    a.big_list = reinterpret_cast<uint32_t *>(d_slow);
-    a.msa = ctx->d_msa;
-    a.plane_stride = ctx->plane_stride;
-    const uint32_t grid = planes_units(ctx);
+    a.cig_off = R.co.d;
+    a.seq4 = R.seq.d;
+    a.seq_off = R.so.d;
+    // (null unless the mode is theirs: slow_pair tests these pointers)
+    a.qual = mode == JL_QV_BYTES ? R.qual.d : nullptr;
+    a.qual_off = mode == JL_QV_BYTES ? R.qo.d : nullptr;
+    a.qmask = mode == JL_QV_MASK ? R.mask.d : nullptr;
+    a.runs = S.runs.d;
+    a.nruns = S.nruns.d;
+    a.desc = S.desc.d;
+    a.slow_count = S.d_count;
+    a.big_list = reinterpret_cast<uint32_t *>(S.slow.d);
+    a.msa = dst->d_msa;
+    a.plane_stride = dst->plane_stride;
+    const uint32_t grid = planes_units(dst);
     // sibling tiles a workgroup (round 6): with qualities two — 170 us against 179 with one, 213-219 with four (the registers leave two
     // workgroups a CU); without qualities one: 111-113 with one or two, 132 with four
     // (the mask mode: two — a whole build 140.7 us at the median, 137.5 at best, against 144.2 / 142.5 with one, the byte mode 193-195 in
     // the same runs: profiles/qmask_ingest_ab.txt; -DJL_NT_QM=1 through tools_tuning/build_tuning_lib.sh builds the other)
     constexpr uint32_t kNt = 1u, kNtQv = 2u, kNtQm = JL_NT_QM;
-    if (qv) {
+    switch (mode) {
+    case JL_QV_BYTES:
         hipLaunchKernelGGL((ingest_planes_kernel<kQvBytes, kEntPerRead, false, kNtQv>), dim3(grid / kNtQv), dim3(kThreads), 0, st, a);
         hipLaunchKernelGGL((ingest_planes_kernel<kQvBytes, kEntPerReadBig, true>), dim3(kBigGrid), dim3(kThreads), 0, st, a);
-    } else if (qm) {
+        break;
+    case JL_QV_MASK:
         hipLaunchKernelGGL((ingest_planes_kernel<kQvMask, kEntPerRead, false, kNtQm>), dim3(grid / kNtQm), dim3(kThreads), 0, st, a);
         hipLaunchKernelGGL((ingest_planes_kernel<kQvMask, kEntPerReadBig, true>), dim3(kBigGrid), dim3(kThreads), 0, st, a);
-    } else {
+        break;
+    case JL_QV_NONE:
         hipLaunchKernelGGL((ingest_planes_kernel<kQvNone, kEntPerRead, false, kNt>), dim3(grid / kNt), dim3(kThreads), 0, st, a);
         hipLaunchKernelGGL((ingest_planes_kernel<kQvNone, kEntPerReadBig, true>), dim3(kBigGrid), dim3(kThreads), 0, st, a);
+        break;
     }
 }

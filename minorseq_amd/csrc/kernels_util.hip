@@ -316,11 +316,10 @@ void jl_launch_planes_to_nibbles(jl_ctx *ctx, uint8_t *d_nib, uint64_t nib_strid
                        ctx->plane_stride, c0, d_nib, nib_stride);
 }
 
-void jl_launch_insertions(jl_ctx *ctx, const int32_t *d_pos, const uint32_t *d_cigar, const uint64_t *d_cig_off,
-                          const uint8_t *d_seq4, const uint64_t *d_seq_off)
+void jl_launch_insertions(jl_ctx *dst, const jl_records &R)
 {
-    hipLaunchKernelGGL(insertions_kernel, dim3((uint32_t)((ctx->n_reads + 255u) / 256u)), dim3(256), 0, ctx->stream, ctx->n_reads,
-                       ctx->n_cols, ctx->win_begin, d_pos, d_cigar, d_cig_off, d_seq4, d_seq_off, ctx->d_ins_len, ctx->d_ins_base);
+    hipLaunchKernelGGL(insertions_kernel, dim3((uint32_t)((dst->n_reads + 255u) / 256u)), dim3(256), 0, dst->stream, dst->n_reads,
+                       dst->n_cols, dst->win_begin, R.pos.d, R.cig.d, R.co.d, R.seq.d, R.so.d, dst->d_ins_len, dst->d_ins_base);
 }
 
 void jl_launch_synth(jl_ctx *ctx, const jl_synth_plan *plan, const uint8_t *d_ref, uint32_t col0)

@@ -241,6 +241,72 @@ def test_insertion_counters_do_not_depend_on_the_form(ctxs):
     assert lh_m.sum() > 0 and (lh_m == lh_b).all() and (bc_m == bc_b).all()
 
 
+def test_empty_stream_is_refused_and_the_contexts_go_on(ctxs):
+    """A stream nothing was appended to builds no matrix: jl_records_finish, jl_records_window and jl_records_window_async refuse
+    it as an "empty matrix" (the matrix is allocated first, so the ingest's launches never see zero reads).  The contexts take a
+    plain ingest afterwards — 300 reads: three tiles, the last one partial."""
+    jl, w = ctxs
+    lib = jl.lib
+    rec, _ = records(300, 600, RICH)
+    exp = records_expand.expand(rec, 600, 0, 0)
+
+    def refused(ctx, rc):
+        assert rc == JL_ERR_ARG
+        assert "empty matrix" in lib.jl_last_error(ctx.h).decode(), lib.jl_last_error(ctx.h)
+
+    def plain(ctx):
+        ctx.ingest_records(600, 0, *five(rec))
+        assert (matrix(ctx, 300) == exp).all()
+
+    assert lib.jl_records_begin(jl.h, 0, 0, 0, 0) == 0
+    refused(jl, lib.jl_records_finish(jl.h, 600, 0, MIN_QV))
+    plain(jl)
+    for window in (lib.jl_records_window, lib.jl_records_window_async):
+        assert lib.jl_records_begin(jl.h, 0, 0, 0, 0) == 0
+        refused(w, window(jl.h, w.h, 600, 0, MIN_QV))
+        plain(jl)
+        plain(w)
+
+
+_noisy_window = {}
+
+
+def noisy_window(min_qv):
+    """records(300, 600, NOISY) in the window (37, 560)"""
+    if min_qv not in _noisy_window:
+        _noisy_window[min_qv] = records_expand.expand(records(300, 600, NOISY)[0], 560, 37, min_qv)
+    return _noisy_window[min_qv]
+
+
+@pytest.mark.parametrize("kind", ["none", "bytes", "mask"])
+def test_one_resident_stream_mode_chosen_per_build(ctxs, kind):
+    """One upload, the window built with min_qv 0, 20 and 0 again: the filter is on or off per build, whatever form the stream
+    carries it in; a stream without qualities is never filtered.  The quality COUNT of a stream with quality bytes is checked
+    at min_qv 0 too (the cigar kernels get the quality offsets whenever the stream has qualities)."""
+    jl, w = ctxs
+    rec, mask = records(300, 600, NOISY)
+    more = {"none": {}, "bytes": {"qual": rec["qual"], "qual_off": rec["qual_off"]}, "mask": {"qmask": mask}}[kind]
+    jl.records_upload(*five(rec), **more)
+    try:
+        for min_qv in (0, MIN_QV, 0):
+            w.records_window(jl, 560, 37, min_qv)
+            assert (matrix(w, 300) == noisy_window(0 if kind == "none" else min_qv)).all(), min_qv
+    finally:
+        jl.records_drop()
+    if kind != "bytes":
+        return
+    short = rec["qual_off"].copy()       # read 7: one quality fewer than its cigar consumes
+    assert short[8] - short[7] > 1
+    short[8:] -= 1
+    jl.records_upload(*five(rec), rec["qual"], short)
+    try:
+        with pytest.raises(capi.JulietError) as err:
+            w.records_window(jl, 560, 37, 0)
+        assert "record 7: its cigar consumes more qualities than the record holds" in str(err.value)
+    finally:
+        jl.records_drop()
+
+
 # --------------------------------------------------------------------------------------------- the command line
 def _norm(path):
     j = json.load(open(path))

@@ -10,7 +10,7 @@ O = sys.argv[1]
 
 
 def short(n):
-    for k in ("ingest_planes_kernel", "cigar_runs_kernel", "cigar_walk_kernel", "ingest_init_kernel"):
+    for k in ("ingest_planes_kernel", "cigar_runs_kernel", "cigar_walk_kernel"):
         if k in n:
             rest = n[n.index(k) + len(k):]      # (the template arguments of the kernel itself, not of its parameters' types)
             return k + rest[:rest.index(">") + 1] if rest.startswith("<") else k
