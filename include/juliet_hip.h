@@ -226,6 +226,41 @@ int jl_qmask_from_quals(uint64_t n_reads, const uint64_t *seq_off, const uint8_t
  */
 int jl_msa_track_insertions(jl_ctx *ctx, int on);
 int jl_insertions_fetch(jl_ctx *ctx, uint32_t *len_hist, uint32_t *base_counts);
+/*
+ * Take reads: the resident matrix of `dst` made of chosen reads of other resident matrices of the same device — a downsample
+ * ("downsample it to 6000x", doc/JULIETFLOW.md:23-25; doc/JULIET.md:244-251), a mixture of clones at a given ratio and coverage
+ * (doc/MIXDATA.md), a bootstrap resample — without another decode, upload or ingest: a read is one bit position in the three
+ * planes of a column, so this is a bit gather over planes that are in HBM already (docs/SPEC.md §12).
+ * Destination reads are the parts one after the other, in argument order; within a part read j is read idx[j] of the part's
+ * source.  idx may be in any order and may repeat.  `dst` becomes a resident window of sum(n) reads with the sources' n_cols and
+ * win_begin, owned by `dst` (plane stride jl_plane_stride(sum n)), padded with code 6; whatever `dst` held, and its stage
+ * results and insertion counters, are gone.  Every stage accepts it as any other window.  The index arrays may be reused on return.
+ * JL_ERR_ARG (jl_last_error(dst) says which): no parts, more than JL_TAKE_MAX_PARTS, sum(n) = 0 or above 2^31 - 1; an index at or
+ * beyond its source's reads; sources of different n_cols or win_begin, or on another device than `dst`; `dst` among the sources.
+ * JL_ERR_STATE: a source without a resident matrix.  A call refused with either leaves `dst` as it was.
+ * jl_msa_take waits for the sources' streams, enqueues on dst's and waits for it; jl_msa_take_async only enqueues on dst's
+ * stream, as jl_records_window_async does (one upload of the indices and one launch; the sources must be complete when dst's
+ * stream gets there — e.g. they share the stream — and stay unchanged until it has).
+ */
+enum { JL_TAKE_MAX_PARTS = 16 };
+typedef struct {
+    jl_ctx *src;          /* a context with a resident matrix */
+    const uint32_t *idx;  /* [n] reads of src */
+    uint64_t n;
+} jl_take_part;
+int jl_msa_take(jl_ctx *dst, const jl_take_part *parts, uint32_t n_parts);
+int jl_msa_take_async(jl_ctx *dst, const jl_take_part *parts, uint32_t n_parts);
+/* Host only (no device, no context), docs/SPEC.md §12.  Which k of n_reads reads a downsample keeps: read i has the key
+ * splitmix64(seed + i) (the generator of the synthetic reads), kept are the k reads with the smallest (key, i), written to
+ * idx in ascending i; *n_out = min(k, n_reads) of them (idx has room for that many; k >= n_reads keeps every read).  Samples
+ * of one seed are nested — the sample of k reads contains the sample of every smaller k — and no device has a say in them.
+ * JL_ERR_ARG: n_reads above 2^32 - 1 (an index is 32 bits). */
+int jl_sample_reads(uint64_t n_reads, uint64_t k, uint64_t seed, uint32_t *idx, uint64_t *n_out);
+/* Host only.  Reads per source of a mixture of `coverage` reads in which every minor clone has `percentage` percent
+ * (doc/MIXDATA.md:10-22): counts[1 .. n_sources) = floor(coverage * percentage / 100), counts[0] — the major clone — the rest,
+ * so that the counts sum to `coverage` exactly.  JL_ERR_ARG: no source, a percentage outside (0, 100), or minors that
+ * alone exceed the coverage. */
+int jl_mix_counts(uint32_t n_sources, uint64_t coverage, double percentage, uint64_t *counts);
 /* The resident matrix back on the host in the interchange format, [n_cols][jl_col_stride(n_reads)] nibbles (tests). */
 int jl_msa_download(jl_ctx *ctx, uint8_t *colpacked, uint64_t bytes);
 /* Fill the resident matrix with synthetic reads, on the device. `ref` = n_cols base codes (host). */

@@ -30,7 +30,7 @@ SUMMARY = np.dtype([(n, "<u4") for n in SUMMARY_FIELDS])
 # every symbol include/juliet_hip.h declares (checked by tests/test_capi_exports.py)
 EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", "jl_ctx_destroy", "jl_last_error",
            "jl_sync", "jl_col_stride", "jl_plane_stride", "jl_msa_upload", "jl_msa_alloc", "jl_msa_adopt", "jl_msa_pack_rows",
-           "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_download", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
+           "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_take", "jl_msa_take_async", "jl_sample_reads", "jl_mix_counts", "jl_msa_download", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
            "jl_consensus_fetch", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_phase_async", "jl_phase_fetch",
            "jl_ctx_stream", "jl_run_async", "jl_run_wait", "jl_run_done", "jl_run_view_get", "jl_group_create", "jl_group_destroy",
            "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
@@ -57,6 +57,14 @@ class SynthParams(C.Structure):
 
 class PhaseSummary(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in SUMMARY_FIELDS]
+
+
+class TakePart(C.Structure):
+    """jl_take_part: `n` reads `idx` of the resident matrix of `src` (include/juliet_hip.h)."""
+    _fields_ = [("src", C.c_void_p), ("idx", C.c_void_p), ("n", C.c_uint64)]
+
+
+TAKE_MAX_PARTS = 16
 
 
 class XwinOp(C.Structure):
@@ -181,6 +189,10 @@ def load_library(path=LIB_PATH):
     lib.jl_msa_track_insertions.argtypes = [vp, C.c_int]
     lib.jl_insertions_fetch.argtypes = [vp, vp, vp]
     lib.jl_msa_download.argtypes = [vp, vp, u64]
+    lib.jl_msa_take.argtypes = [vp, vp, u32]
+    lib.jl_msa_take_async.argtypes = [vp, vp, u32]
+    lib.jl_sample_reads.argtypes = [u64, u64, u64, vp, C.POINTER(u64)]
+    lib.jl_mix_counts.argtypes = [u32, u64, C.c_double, vp]
     lib.jl_synth_fill.argtypes = [vp, C.POINTER(SynthParams), vp]
     lib.jl_synth_fill_window.argtypes = [vp, C.POINTER(SynthParams), vp, u32]
     lib.jl_pileup_async.argtypes = [vp, vp, u32, vp, u32]
@@ -429,6 +441,19 @@ class Juliet:
         self._chk(self.lib.jl_msa_adopt(self.h, C.c_void_p(device_ptr), n_reads, n_cols, plane_stride, win_begin))
         self._shape(n_reads, n_cols, plane_stride)
         self._keep = keep_alive
+
+    def take(self, parts, wait=True):
+        """jl_msa_take: this context's resident matrix from chosen reads of other contexts' — parts = [(source, idx), ...],
+        destination reads = the parts one after the other, read j of a part = read idx[j] of its source (any order, repeats
+        allowed).  wait=False only enqueues on this context's stream (jl_msa_take_async)."""
+        keep = [np.ascontiguousarray(idx, dtype=np.uint32) for _, idx in parts]
+        arr = (TakePart * max(1, len(parts)))()
+        for k, ((src, _), idx) in enumerate(zip(parts, keep)):
+            arr[k] = TakePart(src.h, idx.ctypes.data if len(idx) else None, len(idx))
+        fn = self.lib.jl_msa_take if wait else self.lib.jl_msa_take_async
+        self._chk(fn(self.h, arr, len(parts)))
+        self._shape(sum(len(idx) for idx in keep), parts[0][0].n_cols)
+        self._keep = None
 
     def synth_fill(self, sp, ref):
         """sp: minorseq_amd.synth.SynthParams; fills the resident matrix on the device."""
@@ -768,6 +793,29 @@ def xwin_plan(win_begins, win_ncols, merged):
     if rc:
         raise JulietError(rc, "jl_xwin_plan")
     return remapped[: len(merged)].copy(), pos[: vp.value].copy(), owner[: vp.value].copy()
+
+
+def sample_reads(n_reads, k, seed=0):
+    """jl_sample_reads (host only, docs/SPEC.md §12): the min(k, n_reads) reads a downsample keeps — the smallest
+    (splitmix64(seed + i), i) — as ascending uint32 indices.  Samples of one seed are nested."""
+    lib = load_library()
+    out = np.zeros(max(1, min(int(k), int(n_reads))), dtype=np.uint32)
+    n = C.c_uint64()
+    rc = lib.jl_sample_reads(int(n_reads), int(k), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(out), C.byref(n))
+    if rc:
+        raise JulietError(rc, "jl_sample_reads")
+    return out[: n.value].copy()
+
+
+def mix_counts(n_sources, coverage, percentage):
+    """jl_mix_counts (host only, doc/MIXDATA.md:10-22): reads per source of a mixture — every minor
+    floor(coverage * percentage / 100), the first source the rest."""
+    lib = load_library()
+    out = np.zeros(max(1, int(n_sources)), dtype=np.uint64)
+    rc = lib.jl_mix_counts(int(n_sources), int(coverage), float(percentage), _p(out))
+    if rc:
+        raise JulietError(rc, "jl_mix_counts")
+    return out[: int(n_sources)].copy()
 
 
 def qmask_from_quals(seq_off, qual, qual_off, min_qv):

@@ -306,6 +306,23 @@ void jl_launch_xw_assign(const jl_xw_assign_args *a, const uint16_t *host_tab, c
 void jl_launch_xw_fetch(const void *d_src, void *h_dst, uint64_t bytes, uint32_t *arrive, uint32_t *seq_dev, volatile uint32_t *seq_host,
                         hipStream_t st);
 
+// ---- a matrix of chosen reads of other matrices (kernels_take.hip, capi_take.hip)
+struct jl_take_src {
+    const uint8_t *base;   // the source's planes
+    uint32_t stride;       // ... and its plane stride (its own: an adopted matrix may have any)
+    uint32_t pad_;
+    uint64_t begin;        // the part's first destination read
+};
+struct jl_take_args {
+    jl_take_src part[JL_TAKE_MAX_PARTS];
+    uint32_t n_parts, n_cols;
+    uint64_t n_total;      // destination reads: the parts' sum
+    const uint32_t *idx;   // [n_total] the parts' indices one after the other, each into its own source
+    uint8_t *dst;
+    uint64_t dst_stride;   // whole 128-byte lines: jl_plane_stride(n_total)
+};
+void jl_launch_take(const jl_take_args *a, hipStream_t st);
+
 inline int jl_hip_status(hipError_t e) { return e == hipErrorOutOfMemory ? JL_ERR_MEMORY : JL_ERR_DEVICE; }
 
 // A device array that grows: `cap` elements at `d`.  Making room returns HIP's error (jl_hip_status: the status it becomes).
@@ -434,6 +451,12 @@ struct jl_ctx {
     // ---- aligned records on their way in (jl_records_begin / _append / _finish)
     jl_records rec;
     jl_ingest_scratch ing;            // ... and of the builds into this context's matrix
+
+    // ---- jl_msa_take INTO this context: the parts' indices on their way to the device (capi_take.hip)
+    jl_dev_array<uint32_t> take_idx;
+    uint32_t *h_take_idx = nullptr;   // pinned staging of the same
+    size_t h_take_cap = 0;            // ... in indices
+    hipEvent_t take_ev = nullptr;     // behind the last upload out of the staging: it may be refilled then
 
     // ---- phasing sharded by reads: the groups of this matrix exported for the merge (jl_phase_groups_async / _fetch)
     bool phase_export = false;        // the phase launch in flight / last run exported instead of selecting
@@ -638,6 +661,8 @@ size_t jl_ingest_slow_room(const jl_ctx *ctx);
 extern "C" int jl_ingest_verdict(jl_ctx *ctx);
 // capi_records.hip: frees the records uploaded to `ctx` and the scratch of the builds into it (jl_ctx_destroy)
 void jl_records_release(jl_ctx *ctx);
+// capi_take.hip: frees the index buffers of the takes into `ctx` (jl_ctx_destroy)
+void jl_take_release(jl_ctx *ctx);
 void jl_launch_regroup(jl_ctx *ctx, const uint16_t *d_hap_of_group, uint32_t n_groups, uint32_t n_haplotypes, bool phased);
 void jl_launch_insertions(jl_ctx *dst, const jl_records &R);
 void jl_launch_fisher_eval(jl_ctx *ctx, uint32_t n, const uint32_t *a, const uint32_t *c, const uint32_t *cov, int tail,

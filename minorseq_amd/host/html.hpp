@@ -49,8 +49,19 @@ inline std::string render_html(const Json &root)
     // ---- 1. Input data (doc/JULIET.md:73-79)
     if (const Json *in = root.get("input")) {
         h += "<details open id=\"input\"><summary>Input data</summary><table id=\"input-table\">\n";
-        for (auto &kv : in->obj) h += "<tr><th>" + html_escape(kv.first) + "</th>" + td(num_str(&kv.second)) + "</tr>\n";
-        h += "</table></details>\n";
+        for (auto &kv : in->obj)
+            if (kv.first != "sampling") h += "<tr><th>" + html_escape(kv.first) + "</th>" + td(num_str(&kv.second)) + "</tr>\n";
+        h += "</table>\n";
+        // --downsample / --mix: the seed and, per source, its file, its reads and how many of them were kept (docs/SPEC.md section 12)
+        if (const Json *sp = in->get("sampling")) {
+            h += "<table id=\"sampling-table\" data-seed=\"" + num_str(sp->get("seed")) + "\">\n<tr><th>sampling (seed " + num_str(sp->get("seed")) +
+                 ")</th><th>reads</th><th>kept</th></tr>\n";
+            if (const Json *srcs = sp->get("sources"))
+                for (const Json &x : srcs->arr)
+                    h += "<tr>" + td(x.get_str("file")) + td(num_str(x.get("reads"))) + td(num_str(x.get("kept"))) + "</tr>\n";
+            h += "</table>\n";
+        }
+        h += "</details>\n";
     }
     // ---- 2. Target config (doc/JULIET.md:83-88)
     if (const Json *tc = root.get("target_config")) {

@@ -61,6 +61,13 @@ struct Options {
     uint32_t ins_min_distance = 10;  // ... and the previous included insertion lies at least this many columns back (UNPINNED)
     bool timing = false;
     std::string exchange;            // --exchange rccl|inproc: how the rank threads exchange (default: rccl, inproc when a device repeats)
+    // Sampling (docs/SPEC.md §12): the window is ingested whole, then replaced by chosen reads of it on the device (jl_msa_take)
+    bool have_downsample = false;
+    uint64_t downsample = 0;         // --downsample N: keep N reads (with --mix: the mixture's coverage, default 3000 as mixdata's COVERAGE)
+    uint64_t sample_seed = 0;        // --sample-seed S (source m of a mixture is sampled with S + m)
+    std::vector<std::string> mix;    // --mix b.bam[,c.bam...]: the minor clones; the positional BAM is the major one (doc/MIXDATA.md)
+    double mix_perc = 1.0;           // --mix-perc P: percent of the mixture each minor clone gets
+    bool sampling() const { return have_downsample || !mix.empty(); }
     std::string batch;               // --batch samples.tsv: one `in.bam<TAB>out1[<TAB>out2]` per line, every other option for all of them
     struct BatchLine { unsigned line; std::string bam; std::vector<std::string> outputs; };
     std::vector<BatchLine> batch_lines;
@@ -94,6 +101,14 @@ struct Options {
         "      --consensus <out.fasta>         also write the window's consensus as `fuse` would (doc/FUSE.md:17-20):\n"
         "                                      majority base, major deletions removed, in-frame majority insertions kept\n"
         "      --ins-min-frac 0.5  --ins-min-distance 10   when an insertion enters the consensus\n"
+        "      --downsample N [--sample-seed S]  call on N reads of the sample (\"downsample it to 6000x\", doc/JULIETFLOW.md:23-25):\n"
+        "                                      the reads are chosen by docs/SPEC.md section 12 (seed default 0; samples of one seed are\n"
+        "                                      nested) and gathered on the device; N at or above the read count changes nothing.\n"
+        "                                      With --batch: every sample.  Not with --windows, --devices a,b or --consensus\n"
+        "      --mix b.bam[,c.bam...] [--mix-perc P]  a mixture as mixdata makes it (doc/MIXDATA.md): in.bam is the major clone, every\n"
+        "                                      listed BAM a minor clone with P percent (default 1) of --downsample C reads (default\n"
+        "                                      3000); source m is sampled with seed S + m.  A source with too few reads is an input\n"
+        "                                      error (2).  Not with --batch, --windows, --devices a,b or --consensus\n"
         "      --batch <samples.tsv>           many samples in one process: one `in.bam<TAB>out1[<TAB>out2]` per line (blank lines\n"
         "                                      and lines starting with # skipped); every other option applies to every sample and\n"
         "                                      each sample gets the files a single run would write.  A sample that fails is named\n"
@@ -227,12 +242,38 @@ Options parse(int argc, char **argv)
         else if (a == "--dump-config") o.dump_config = need(i);
         else if (a == "--timing") o.timing = true;
         else if (a == "--batch") o.batch = need(i);
+        else if (a == "--downsample") { o.downsample = std::stoull(need(i)); o.have_downsample = true; }
+        else if (a == "--sample-seed") o.sample_seed = std::stoull(need(i));
+        else if (a == "--mix") {
+            const std::string v = need(i);
+            for (size_t b = 0; b <= v.size();) {
+                const size_t e = std::min(v.find(',', b), v.size());
+                if (e > b) o.mix.push_back(v.substr(b, e - b));
+                b = e + 1;
+            }
+            if (o.mix.empty()) { std::cerr << "juliet: --mix names no BAM\n"; std::exit(1); }
+        }
+        else if (a == "--mix-perc") o.mix_perc = std::stod(need(i));
         else if (!a.empty() && a[0] == '-') { std::cerr << "juliet: unknown option " << a << "\n"; usage(1); }
         else pos.push_back(a);
     }
     const std::string prog = argv[0];
     const size_t slash = prog.find_last_of('/');
     const bool as_fuse = (slash == std::string::npos ? prog : prog.substr(slash + 1)) == "fuse";
+    if (o.sampling()) {   // what sampling cannot be combined with is refused here, before any file is read or any GPU work
+        auto refuse = [&](const char *why) { std::cerr << "juliet: " << (o.mix.empty() ? "--downsample " : "--mix ") << why << "\n"; std::exit(1); };
+        if (o.have_downsample && o.downsample == 0) refuse("wants at least one read (--downsample 0)");
+        if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
+        if (!o.consensus.empty() || as_fuse) refuse("carries no insertion counters into the sample: no consensus (drop --consensus)");
+        if (!o.mix.empty()) {
+            if (!o.batch.empty()) refuse("mixes into one sample (not with --batch)");
+            if (o.mix.size() + 1 > (size_t)JL_TAKE_MAX_PARTS) refuse("takes at most 15 minor clones");
+            if (!o.have_downsample) o.downsample = 3000;   // mixdata's COVERAGE (doc/MIXDATA.md)
+            std::vector<uint64_t> counts(o.mix.size() + 1);
+            if (jl_mix_counts((uint32_t)counts.size(), o.downsample, o.mix_perc, counts.data()) != JL_OK)
+                refuse("wants --mix-perc inside (0, 100) and minor clones that together stay within the coverage");
+        }
+    }
     if (!o.batch.empty()) {   // everything a batch cannot do is refused here, before any file is read or any GPU work
         auto refuse = [](const char *why) { std::cerr << "juliet: --batch " << why << "\n"; std::exit(1); };
         if (as_fuse) refuse("is not an option of fuse");
@@ -954,9 +995,94 @@ const char *fetch_phase(jl_ctx *ctx, uint64_t n_reads, Results &R)
     return nullptr;
 }
 
+// What --downsample / --mix did to a sample: the `sampling` block of the JSON's input section, present only when reads were chosen.
+struct SamplingInfo {
+    bool acted = false;
+    uint64_t seed = 0;
+    struct Source { std::string file; uint64_t reads, kept; };
+    std::vector<Source> sources;
+};
+
+// --downsample on a window that is resident on `ctx` (its reads' names in `names`): when it holds more than opt.downsample reads,
+// the reads of jl_sample_reads are gathered into `taken` — a second context of the device, on the same stream — and names / n_reads
+// follow the indices.  JL_OK, or the status of the call that failed (jl_last_error(taken)); *acted: the window to run is `taken` now.
+int downsample_window(const Options &opt, const std::string &bam, jl_ctx *ctx, jl_ctx *taken, std::vector<std::string> &names, uint64_t &n_reads,
+                      SamplingInfo &info, bool *acted)
+{
+    *acted = false;
+    if (!opt.have_downsample || n_reads <= opt.downsample) return JL_OK;
+    std::vector<uint32_t> idx((size_t)opt.downsample);
+    uint64_t kept = 0;
+    if (const int rc = jl_sample_reads(n_reads, opt.downsample, opt.sample_seed, idx.data(), &kept)) return rc;
+    const jl_take_part part = {ctx, idx.data(), kept};
+    if (const int rc = jl_msa_take(taken, &part, 1)) return rc;
+    std::vector<std::string> chosen((size_t)kept);
+    for (uint64_t j = 0; j < kept; ++j) chosen[(size_t)j].swap(names[idx[(size_t)j]]);
+    names.swap(chosen);
+    info.acted = true;
+    info.seed = opt.sample_seed;
+    info.sources.assign(1, {bam, n_reads, kept});
+    n_reads = kept;
+    *acted = true;
+    return JL_OK;
+}
+
+// --mix: the mixture of doc/MIXDATA.md in `taken`.  `major` holds the positional BAM's window; every BAM of the list is decoded and
+// ingested into a context of its own over the same window (same device and stream), jl_mix_counts says how many reads each source
+// gives, source m is sampled with seed S + m, and ONE jl_msa_take with the parts in argument order builds the mixture; names and
+// n_reads become the mixture's.  0, or the process's exit status (message printed): 2 an input error, 3 a device error.
+int mix_window(const Options &opt, const IngestOptions &io, jl_ctx *major, jl_ctx *taken, uint32_t n_cols, uint32_t win_begin,
+               std::vector<std::string> &names, uint64_t &n_reads, SamplingInfo &info)
+{
+    const size_t n_src = opt.mix.size() + 1;
+    std::vector<jl_ctx *> ctxs(1, major);
+    std::vector<std::vector<std::string>> src_names(n_src);
+    std::vector<uint64_t> reads(1, n_reads);
+    src_names[0].swap(names);
+    for (const std::string &file : opt.mix) {
+        jl_ctx *c = nullptr;
+        if (jl_ctx_create(opt.device, jl_ctx_stream(major), &c) != JL_OK) die_jl(nullptr, "context of a minor clone");
+        std::promise<std::pair<int, jl_ctx *>> ready;
+        ready.set_value(std::make_pair((int)JL_OK, c));
+        RecordUploader up({ready.get_future().share()}, file_bytes(file), opt.min_qv > 0, io.qv_mask);
+        RecordArrays rec;
+        const Decoded d = decode_bam(file, io, &up, rec);
+        if (up.finish() != JL_OK) die_jl(up.failed() ? up.failed() : c, "record upload");
+        if (d.ext.n_reads == 0) { std::cerr << "juliet: no primary or supplementary alignments in " << file << "\n"; return 2; }
+        if (up.n_reads != d.ext.n_reads) die_jl(nullptr, "record upload lost reads");
+        if (jl_records_finish(c, n_cols, win_begin, opt.min_qv) != JL_OK) die_jl(c, "ingest");
+        src_names[ctxs.size()].swap(up.names);
+        ctxs.push_back(c);
+        reads.push_back(d.ext.n_reads);
+    }
+    std::vector<uint64_t> counts(n_src);
+    if (jl_mix_counts((uint32_t)n_src, opt.downsample, opt.mix_perc, counts.data()) != JL_OK) die_jl(nullptr, "mixture counts");
+    for (size_t m = 0; m < n_src; ++m)
+        if (reads[m] < counts[m]) {
+            std::cerr << "juliet: --mix: " << (m ? opt.mix[m - 1] : opt.bam) << " has " << reads[m] << " reads, the mixture wants " << counts[m] << " of it\n";
+            return 2;
+        }
+    std::vector<std::vector<uint32_t>> idx(n_src);
+    std::vector<jl_take_part> parts(n_src);
+    info.acted = true;
+    info.seed = opt.sample_seed;
+    info.sources.clear();
+    for (size_t m = 0; m < n_src; ++m) {
+        idx[m].resize((size_t)std::max<uint64_t>(counts[m], 1));
+        uint64_t kept = 0;
+        if (jl_sample_reads(reads[m], counts[m], opt.sample_seed + m, idx[m].data(), &kept) != JL_OK || kept != counts[m]) die_jl(nullptr, "sample of a clone");
+        parts[m] = {ctxs[m], idx[m].data(), kept};
+        info.sources.push_back({m ? opt.mix[m - 1] : opt.bam, reads[m], kept});
+        for (uint64_t j = 0; j < kept; ++j) names.push_back(std::move(src_names[m][idx[m][(size_t)j]]));
+    }
+    if (jl_msa_take(taken, parts.data(), (uint32_t)n_src) != JL_OK) die_jl(taken, "mixture");
+    n_reads = names.size();
+    return 0;
+}
+
 // The JSON document of one sample (doc/JULIET.md:61-107, 207-211); the HTML output is its rendering.
 Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam, const std::string &cmdline,
-                const std::vector<std::string> &names, uint64_t n_reads, const Results &R)
+                const std::vector<std::string> &names, uint64_t n_reads, const Results &R, const SamplingInfo *sampling = nullptr)
 {
     const TargetConfig &cfg = s.cfg;
     const uint32_t win_begin = s.win_begin, n_cols = s.n_cols;
@@ -974,6 +1100,14 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
                           .set("input_file", Json::of(bam))
                           .set("command_line", Json::of(cmdline))
                           .set("juliet_version", Json::of(kVersion)));
+    if (sampling && sampling->acted) {   // (only then: a run whose flags chose nothing writes what a run without them writes)
+        Json srcs = Json::array();
+        for (const SamplingInfo::Source &x : sampling->sources)
+            srcs.push(Json::object().set("file", Json::of(x.file)).set("reads", Json::of((int64_t)x.reads)).set("kept", Json::of((int64_t)x.kept)));
+        Json sj = Json::object();
+        sj.set("seed", Json::of((int64_t)sampling->seed)).set("sources", std::move(srcs));
+        root.obj.back().second.set("sampling", std::move(sj));
+    }
     Json tc = cfg.echo();
     tc.set("n_reads", Json::of((int64_t)n_reads));
     tc.set("window_begin", Json::of(win_begin + 1)).set("window_end", Json::of(win_begin + n_cols + 1));
@@ -1187,6 +1321,7 @@ public:
             _exit(failed ? 2 : 0);
         }
         for (auto &g : groups_) jl_group_destroy(g.second);
+        for (auto &t : taken_) jl_ctx_destroy(t.second);
         for (jl_ctx *c : pool_) jl_ctx_destroy(c);
         return failed ? 2 : 0;
     }
@@ -1198,7 +1333,9 @@ private:
 
     struct Sample {
         const Options::BatchLine *line = nullptr;
-        jl_ctx *ctx = nullptr;
+        jl_ctx *ctx = nullptr;       // of the pool: the sample's records and its window as ingested
+        jl_ctx *run = nullptr;       // the window that is called: ctx, or — downsampled — the pool context's companion (taken_)
+        SamplingInfo sampling;
         SampleSetup s;
         std::vector<std::string> names;
         uint64_t n_reads = 0;
@@ -1300,6 +1437,13 @@ private:
         }
         cv_.notify_all();
     }
+    // The context a pool context's downsampled window goes into: same device, same stream, made when first needed and kept.
+    jl_ctx *companion_of(jl_ctx *c)   // (decoding thread only)
+    {
+        jl_ctx *&t = taken_[c];
+        if (!t && jl_ctx_create(opt_.device, jl_ctx_stream(c), &t) != JL_OK) gpu_error("context of a downsampled window");
+        return t;
+    }
     jl_ctx *context_of(const std::shared_future<std::pair<int, jl_ctx *>> &up)
     {
         const auto r = up.get();
@@ -1339,9 +1483,17 @@ private:
         const int rc = jl_records_finish(smp.ctx, smp.s.n_cols, smp.s.win_begin, opt_.min_qv);
         if (rc == JL_ERR_ARG || rc == JL_ERR_STATE) return std::string("ingest: ") + jl_last_error(smp.ctx);   // (a malformed record)
         if (rc != JL_OK) gpu_error(std::string("ingest: ") + jl_last_error(smp.ctx));
+        smp.run = smp.ctx;
+        if (opt_.have_downsample && smp.n_reads > opt_.downsample) {   // (every sample of the list goes to the same depth)
+            jl_ctx *taken = companion_of(smp.ctx);
+            bool acted = false;
+            if (downsample_window(opt_, l.bam, smp.ctx, taken, smp.names, smp.n_reads, smp.sampling, &acted) != JL_OK)
+                gpu_error(std::string("downsample: ") + jl_last_error(taken));
+            if (acted) smp.run = taken;
+        }
         if (opt_.drm_only) {
             const DeviceStageInput in{&opt_, &smp.s.cfg, &smp.s.genes, &smp.s.refcodes, smp.s.prm, smp.s.win_begin, smp.s.n_cols, smp.n_reads};
-            if (drm_masks_of(smp.ctx, in, smp.drm_masks)) gpu_error(std::string("pileup: ") + jl_last_error(smp.ctx));
+            if (drm_masks_of(smp.run, in, smp.drm_masks)) gpu_error(std::string("pileup: ") + jl_last_error(smp.run));
         }
         if (opt_.timing)
             fprintf(stderr, "juliet: timing batch decode  line %u  %llu reads  %.1f ms\n", l.line, (unsigned long long)smp.n_reads,
@@ -1379,7 +1531,7 @@ private:
         auto t0 = std::chrono::steady_clock::now();
         if (chunk.size() >= 2) {
             // the contexts in one order whatever the samples' order: a group of the same contexts is used again
-            std::sort(chunk.begin(), chunk.end(), [](const Sample *a, const Sample *b) { return std::less<jl_ctx *>()(a->ctx, b->ctx); });
+            std::sort(chunk.begin(), chunk.end(), [](const Sample *a, const Sample *b) { return std::less<jl_ctx *>()(a->run, b->run); });
             jl_group *g = group_of(chunk);
             const SampleSetup &s = chunk[0]->s;
             std::vector<const uint64_t *> masks;
@@ -1387,7 +1539,7 @@ private:
             const int rc = jl_group_run_masked_async(g, s.genes.data(), (uint32_t)s.genes.size(), s.refp(), (uint32_t)s.refcodes.size(), &s.prm,
                                                      masks.data(), opt_.phasing, opt_.min_reads, opt_.phasing);
             if (rc == JL_OK) {
-                for (const Sample *x : chunk) last_group_[x->ctx] = g;
+                for (const Sample *x : chunk) last_group_[x->run] = g;
                 fetch(chunk);
                 timing_line("group ", chunk, t0);
                 return;
@@ -1399,10 +1551,10 @@ private:
         for (Sample *x : chunk) {
             if (x != chunk[0]) t0 = std::chrono::steady_clock::now();
             const SampleSetup &s = x->s;
-            if (jl_run_async(x->ctx, s.genes.data(), (uint32_t)s.genes.size(), s.refp(), (uint32_t)s.refcodes.size(), &s.prm, x->masks(),
+            if (jl_run_async(x->run, s.genes.data(), (uint32_t)s.genes.size(), s.refp(), (uint32_t)s.refcodes.size(), &s.prm, x->masks(),
                              opt_.phasing, opt_.min_reads, opt_.phasing) != JL_OK)
-                gpu_error(std::string("run: ") + jl_last_error(x->ctx));
-            last_group_[x->ctx] = nullptr;
+                gpu_error(std::string("run: ") + jl_last_error(x->run));
+            last_group_[x->run] = nullptr;
             fetch({x});
             timing_line("single", {x}, t0);
         }
@@ -1413,10 +1565,10 @@ private:
         const Tick quiet = [](const char *) {};
         for (Sample *x : chunk) {
             x->R.col_counts.assign((size_t)x->s.n_cols * 6, 0);
-            const char *what = fetch_calls(x->ctx, true, x->R, quiet);
-            if (!what && opt_.phasing) what = fetch_phase(x->ctx, x->n_reads, x->R);
-            if (!what && jl_sync(x->ctx) != JL_OK) what = "sync";   // (the group's stream too: nothing of the run is left on the device)
-            if (what) gpu_error(std::string(what) + ": " + jl_last_error(x->ctx));
+            const char *what = fetch_calls(x->run, true, x->R, quiet);
+            if (!what && opt_.phasing) what = fetch_phase(x->run, x->n_reads, x->R);
+            if (!what && jl_sync(x->run) != JL_OK) what = "sync";   // (the group's stream too: nothing of the run is left on the device)
+            if (what) gpu_error(std::string(what) + ": " + jl_last_error(x->run));
             release(x->ctx);
         }
     }
@@ -1433,7 +1585,7 @@ private:
     jl_group *group_of(const std::vector<Sample *> &chunk)
     {
         std::vector<jl_ctx *> ctxs;
-        for (const Sample *x : chunk) ctxs.push_back(x->ctx);
+        for (const Sample *x : chunk) ctxs.push_back(x->run);
         for (auto &e : groups_)
             if (e.first == ctxs) return e.second;
         if (groups_.size() >= kGroupCache)
@@ -1453,7 +1605,7 @@ private:
     void write(Sample &x)
     {
         try {
-            const Json root = build_json(opt_, x.s, x.line->bam, cmdline_, x.names, x.n_reads, x.R);
+            const Json root = build_json(opt_, x.s, x.line->bam, cmdline_, x.names, x.n_reads, x.R, &x.sampling);
             std::lock_guard<std::mutex> lk(io_m_);
             const std::string failed = write_outputs(x.line->outputs, root);
             if (!failed.empty()) sample_failed(*x.line, "cannot write " + failed);
@@ -1476,6 +1628,7 @@ private:
     std::atomic<unsigned> n_failed_{0};
     std::vector<std::pair<std::vector<jl_ctx *>, jl_group *>> groups_;   // main thread only
     std::map<jl_ctx *, jl_group *> last_group_;                          // main thread only
+    std::map<jl_ctx *, jl_ctx *> taken_;                                 // decoding thread only: pool context -> its companion
 };
 
 int run_batch(const Options &opt, const TargetConfig &cfg, const std::string &cmdline)
@@ -1585,6 +1738,7 @@ int main(int argc, char **argv)
                     uploader->ms_gather, uploader->ms_begin, uploader->n_appends, uploader->ms_append, uploader->ms_append_max, uploader->ms_names);
         const uint8_t *refp = smp.refp();
         Results R;
+        SamplingInfo sampling;
         R.col_counts.assign((size_t)n_cols * 6, 0);
         DeviceStageInput in{&opt, &smp.cfg, &genes, &refcodes, smp.prm, win_begin, n_cols, n_reads};
         const size_t n_ranks = opt.devices.size();
@@ -1668,6 +1822,19 @@ int main(int argc, char **argv)
         if (!opt.consensus.empty()) jl_msa_track_insertions(ctx, 1);   // fuse keeps in-frame insertions (doc/FUSE.md:19)
         if (jl_records_finish(ctx, n_cols, win_begin, opt.min_qv) != JL_OK) die_jl(ctx, "ingest");
         tick("device ingest");
+        if (opt.sampling()) {   // the window to call is made of chosen reads, in a second context on the same device and stream
+            jl_ctx *taken = nullptr;
+            if (jl_ctx_create(opt.device, jl_ctx_stream(ctx), &taken) != JL_OK) die_jl(nullptr, "context of the sample");
+            if (!opt.mix.empty()) {
+                if (const int code = mix_window(opt, io, ctx, taken, n_cols, win_begin, names, n_reads, sampling)) return code;
+                ctx = taken;
+            } else {
+                bool acted = false;
+                if (downsample_window(opt, opt.bam, ctx, taken, names, n_reads, sampling, &acted) != JL_OK) die_jl(taken, "downsample");
+                if (acted) ctx = taken;
+            }
+            tick("sample");
+        }
 
         // --drm-only needs the position list, which the plan of a first pileup provides
         std::vector<uint64_t> drm_masks;
@@ -1702,7 +1869,7 @@ int main(int argc, char **argv)
         // 4-6 ms of a 0.1 s run)
         }
         // ---------------------------------------------------------------- JSON / HTML (doc/JULIET.md:61-107, 207-211)
-        const Json root = build_json(opt, smp, opt.bam, cmdline, names, n_reads, R);
+        const Json root = build_json(opt, smp, opt.bam, cmdline, names, n_reads, R, &sampling);
         const std::string failed = write_outputs(opt.outputs, root);
         if (!failed.empty()) { std::cerr << "juliet: cannot write " << failed << "\n"; return 2; }
         tick("json / html");

@@ -1,0 +1,404 @@
+"""jl_msa_take on the device (docs/SPEC.md §12): a resident window made of chosen reads of other resident windows, and
+`juliet --downsample / --mix` on top of it.  The expected matrix is always numpy row selection of the rows that were uploaded,
+compared cell by cell with what the destination holds — padding included — never with another device result."""
+import json
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+from minorseq_amd import capi, msa, synth
+from test_gpu_parity import assert_phase_equal, assert_variants_equal
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+JULIET = os.path.join(ROOT, "minorseq_amd", "bin", "juliet")
+SYNTH = os.path.join(ROOT, "minorseq_amd", "bin", "juliet-synth")
+
+
+@pytest.fixture(scope="module", autouse=True)
+def built():
+    """The binaries normally travel with the tree; build them only if they are missing (never under a loaded .so)."""
+    if not os.path.exists(os.path.join(ROOT, "minorseq_amd", "libjuliet_hip.so")):
+        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "minorseq_amd", "csrc")])
+    if not (os.path.exists(JULIET) and os.path.exists(SYNTH)):
+        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "minorseq_amd", "host")])
+
+
+@pytest.fixture(scope="module")
+def ctxs():
+    c = [capi.Juliet(0) for _ in range(4)]
+    yield c
+    for j in c:
+        j.close()
+
+
+def code_rows(n, l, seed):
+    """Seeded codes 0..6 with ragged code-6 ends, as reads that start late and end early have."""
+    rng = np.random.default_rng(seed)
+    rows = rng.integers(0, 6, size=(n, l), dtype=np.uint8)
+    lo, hi = rng.integers(0, l // 3 + 1, size=n), l - rng.integers(0, l // 3 + 1, size=n)
+    ci = np.arange(l)[None, :]
+    rows[(ci < lo[:, None]) | (ci >= hi[:, None])] = 6
+    return rows
+
+
+def cells_of(j):
+    """The whole destination as the device holds it, by read: every read position of the interchange format, i.e. the n reads
+    and the padding behind them (which must be code 6)."""
+    packed = j.download_columns()
+    return msa.unpack_columns(packed, 2 * packed.shape[1])
+
+
+def assert_is_selection(dst, expected_rows):
+    """dst holds exactly expected_rows, and code 6 in every read position behind them."""
+    got = cells_of(dst)
+    n = len(expected_rows)
+    assert dst.n_reads == n and dst.n_cols == expected_rows.shape[1]
+    assert (got[:n] == expected_rows).all()
+    assert (got[n:] == 6).all()
+
+
+def pattern(name, n_src, n_keep):
+    if name == "identity":
+        return np.arange(n_src, dtype=np.uint32)
+    if name == "reversed":
+        return np.arange(n_src, dtype=np.uint32)[::-1].copy()
+    if name == "repeat":          # one read, n_keep times
+        return np.full(n_keep, n_src // 2, dtype=np.uint32)
+    if name == "every17":
+        return np.arange(0, n_src, 17, dtype=np.uint32)
+    if name == "last":
+        return np.array([n_src - 1], dtype=np.uint32)
+    if name == "random":          # n_keep reads in any order, repeats allowed (a bootstrap)
+        return np.random.default_rng(n_src * 7919 + n_keep).integers(0, n_src, size=n_keep).astype(np.uint32)
+    raise ValueError(name)
+
+
+# (source reads, kept reads, columns, index pattern): every size of the byte / ballot word / 128-byte line / column chunk edges as
+# a source and as a destination, every pattern, sparsely paired
+CASES = [
+    (1, 1, 1, "identity"), (7, 7, 2, "reversed"), (8, 9, 3, "repeat"), (9, 8, 4, "random"), (63, 64, 130, "random"),
+    (64, 63, 1, "random"), (65, 65, 2, "identity"), (1023, 1025, 3, "repeat"), (1024, 1024, 4, "reversed"), (1025, 1023, 130, "random"),
+    (2049, 1, 1, "last"), (2049, 121, 2, "every17"), (2049, 2049, 3, "reversed"), (1024, 61, 4, "every17"), (1, 2049, 130, "repeat"),
+    (1023, 1, 3, "last"), (65, 7, 130, "random"), (1025, 2049, 4, "random"), (9, 1, 17, "last"), (64, 1024, 16, "random"),
+]
+
+
+@pytest.mark.parametrize("n_src,n_keep,l,name", CASES)
+def test_take_is_row_selection(ctxs, n_src, n_keep, l, name):
+    src, dst = ctxs[0], ctxs[1]
+    rows = code_rows(n_src, l, n_src * 1000 + l)
+    idx = pattern(name, n_src, n_keep)
+    if name in ("repeat", "random"):
+        assert len(idx) == n_keep
+    src.upload_rows(rows, win_begin=5)
+    dst.take([(src, idx)])
+    assert_is_selection(dst, rows[idx])
+    assert (msa.unpack_columns(src.download_columns(), n_src) == rows).all()     # the source is untouched
+
+
+@pytest.mark.parametrize("sizes", [(1, 1023, 1), (65, 7, 1025)])
+def test_take_of_three_parts(ctxs, sizes):
+    """Three sources of different depth; the part boundaries fall inside a byte, inside a ballot word and across a line."""
+    l = 19
+    srcs, dst = ctxs[:3], ctxs[3]
+    n_src = (300, 1500, 2049)
+    rows = [code_rows(n, l, 40 + n) for n in n_src]
+    rng = np.random.default_rng(sum(sizes))
+    idx = [rng.integers(0, n, size=k).astype(np.uint32) for n, k in zip(n_src, sizes)]
+    for j, r in zip(srcs, rows):
+        j.upload_rows(r)
+    dst.take(list(zip(srcs, idx)))
+    assert_is_selection(dst, np.concatenate([r[i] for r, i in zip(rows, idx)]))
+    # the same source twice and an empty part in between: parts are positions, not sources
+    dst.take([(srcs[2], idx[2]), (srcs[0], np.zeros(0, dtype=np.uint32)), (srcs[2], idx[2][::-1])])
+    assert_is_selection(dst, np.concatenate([rows[2][idx[2]], rows[2][idx[2][::-1]]]))
+
+
+def test_take_from_an_adopted_source_with_its_own_stride(ctxs):
+    """A torch tensor as the source: 1000 reads in planes of 144 bytes (the library's own stride would be 128), garbage in the
+    bytes past ceil(n / 8) of every plane row.  None of it may show in the destination."""
+    import torch
+    n, l, stride = 1000, 23, 144
+    rows = code_rows(n, l, 99)
+    planes = msa.pack_planes(rows, stride)
+    assert planes.shape == (l, 3, stride)
+    planes[:, :, (n + 7) // 8:] = np.random.default_rng(1).integers(0, 256, size=(l, 3, stride - (n + 7) // 8), dtype=np.uint8)
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        t = torch.from_numpy(planes).cuda(non_blocking=False)
+    stream.synchronize()
+    src = capi.Juliet(0, stream=stream.cuda_stream)
+    src.adopt(t.data_ptr(), n, l, stride, keep_alive=t)
+    dst = ctxs[1]
+    for idx in (np.arange(n, dtype=np.uint32), np.arange(n, dtype=np.uint32)[::-1].copy(), np.array([999, 0, 992, 999], dtype=np.uint32)):
+        dst.take([(src, idx)])
+        assert_is_selection(dst, rows[idx])
+    # beside a source with the library's stride, in one take
+    other = ctxs[0]
+    rows2 = code_rows(77, l, 3)
+    other.upload_rows(rows2)
+    i1, i2 = np.arange(0, n, 3, dtype=np.uint32), np.arange(77, dtype=np.uint32)
+    dst.take([(src, i1), (other, i2), (src, i1[:5])])
+    assert_is_selection(dst, np.concatenate([rows[i1], rows2[i2], rows[i1[:5]]]))
+    src.close()
+
+
+def test_take_into_a_destination_that_held_more(ctxs):
+    """dst held 2049 reads of all A; after a take of 5 reads nothing of them is left: padding is code 6 out to the end of the
+    plane row and every pileup column sums to at most 5."""
+    l = 12
+    src, dst = ctxs[0], ctxs[1]
+    dst.upload_rows(np.zeros((2049, l), dtype=np.uint8))
+    rows = code_rows(40, l, 8)
+    src.upload_rows(rows)
+    idx = np.array([3, 39, 0, 3, 17], dtype=np.uint32)
+    dst.take([(src, idx)])
+    assert_is_selection(dst, rows[idx])
+    assert cells_of(dst).shape[0] >= 256           # (the check above looked at more read positions than the 5)
+    genes = np.array([(1, l + 1)], dtype=capi.GENE)
+    dst.pileup_async(genes)
+    col = dst.pileup_fetch()["col_counts"]
+    assert (col.sum(axis=1) <= 5).all()
+    exp = np.stack([(rows[idx] == s).sum(axis=0) for s in range(6)], axis=1)
+    assert (col == exp).all()
+
+
+# ---------------------------------------------------------------------------------------------- the path on a taken window
+PIPE_N, PIPE_L, PIPE_KEEP, PIPE_SEED = 5000, 300, 1500, 11
+PIPE_SP = synth.SynthParams(seed=21, minor_permille=(90, 70, 50, 40), partial_rate=0.1)
+
+
+@pytest.fixture(scope="module")
+def pipe_rows():
+    ref = synth.reference(PIPE_SP.seed, PIPE_L)
+    return synth.rows(PIPE_SP, PIPE_L, 0, PIPE_N, ref), ref
+
+
+def test_run_on_a_downsampled_window_equals_the_oracle_on_the_selected_rows(ctxs, oracle, pipe_rows):
+    rows, ref = pipe_rows
+    src, dst = ctxs[0], ctxs[1]
+    genes = np.array([(1, PIPE_L + 1)], dtype=capi.GENE)
+    idx = capi.sample_reads(PIPE_N, PIPE_KEEP, PIPE_SEED)
+    sel = rows[idx]
+    exp_v = oracle.call(sel, genes, refseq=ref)
+    exp_p = oracle.phase(sel, exp_v)
+    assert len(exp_v) >= 1 and exp_p["summary"]["n_haplotypes"] >= 2       # the input was chosen so that there is something to find
+    src.upload_rows(rows)
+    dst.take([(src, idx)], wait=False)      # enqueue only: the run is ordered behind it on the destination's stream
+    out = dst.run(genes, ref, capi.default_params(), phasing=True)
+    assert_variants_equal(out["variants"], exp_v)
+    assert_phase_equal(out["phase"], exp_p, len(exp_v))     # summary, patterns, hit, every read id, cooc
+    assert_is_selection(dst, sel)
+
+
+def test_four_depths_of_one_upload_in_one_group_run(ctxs, pipe_rows):
+    """A coverage titration: one source, four depths with one seed into four contexts, ONE group launch; every view equals
+    run() on that context alone."""
+    rows, ref = pipe_rows
+    src = capi.Juliet(0)
+    src.upload_rows(rows)
+    genes = np.array([(1, PIPE_L + 1)], dtype=capi.GENE)
+    prm = capi.default_params()
+    depths = (3000, 1500, 700, 250)
+    for j, k in zip(ctxs, depths):
+        j.take([(src, capi.sample_reads(PIPE_N, k, PIPE_SEED))])
+    grp = capi.Group(ctxs)
+    grp.run_async(genes, ref, prm, True, 10, True)
+    views = []
+    for j in ctxs:
+        v = j.run_view()
+        assert v is not None
+        views.append(dict(variants=v["variants"].copy(),
+                          phase={k: (x.copy() if hasattr(x, "copy") else x) for k, x in v["phase"].items()}))
+    assert len(views[0]["variants"]) >= 1
+    for j, k, v in zip(ctxs, depths, views):
+        alone = j.run(genes, ref, prm, phasing=True)
+        assert j.n_reads == k
+        assert_variants_equal(v["variants"], alone["variants"])
+        ph = dict(alone["phase"])
+        ph["hit"] = ph["hit"][:len(alone["variants"]), :ph["summary"]["n_haplotypes"]]
+        ph["cooc"] = ph["cooc"][:len(alone["variants"]), :len(alone["variants"])]
+        assert_phase_equal(v["phase"], ph, len(alone["variants"]))
+    grp.close()
+    src.close()
+
+
+# ---------------------------------------------------------------------------------------------- errors
+def test_take_errors_leave_the_destination_usable(ctxs):
+    l = 9
+    a, b, dst, empty = ctxs[0], ctxs[1], ctxs[2], capi.Juliet(0)
+    rows_a, rows_d = code_rows(50, l, 1), code_rows(33, l, 2)
+    a.upload_rows(rows_a, win_begin=4)
+    dst.upload_rows(rows_d, win_begin=4)
+    ok = np.arange(10, dtype=np.uint32)
+
+    def refused(status, parts, word):
+        with pytest.raises(capi.JulietError) as e:
+            dst.take(parts)
+        assert e.value.status == status, str(e.value)
+        assert word in str(e.value), str(e.value)
+        assert dst.n_reads == 33 and (msa.unpack_columns(dst.download_columns(), 33) == rows_d).all()
+
+    refused(-1, [], "no parts")
+    refused(-1, [(a, ok)] * 17, "at most 16")
+    refused(-1, [(a, np.zeros(0, dtype=np.uint32))], "no reads")
+    refused(-1, [(a, np.array([0, 50], dtype=np.uint32))], "50 reads")                 # an index AT the source's read count
+    refused(-1, [(a, ok), (a, np.array([7, 0xFFFFFFFF], dtype=np.uint32))], "part 1")
+    b.upload_rows(code_rows(20, l + 1, 3), win_begin=4)
+    refused(-1, [(a, ok), (b, ok)], "window")                                          # another n_cols
+    b.upload_rows(code_rows(20, l, 3), win_begin=5)
+    refused(-1, [(a, ok), (b, ok)], "window")                                          # another win_begin
+    refused(-1, [(a, ok), (dst, ok)], "destination itself")
+    refused(-4, [(a, ok), (empty, ok)], "no resident matrix")
+    if capi.load_library().jl_device_count() > 1:
+        far = capi.Juliet(1)
+        far.upload_rows(rows_a, win_begin=4)
+        refused(-1, [(far, ok)], "device")
+        far.close()
+    # ... and the destination still takes
+    dst.take([(a, ok[::-1].copy())])
+    assert_is_selection(dst, rows_a[ok[::-1]])
+    empty.close()
+
+
+# ---------------------------------------------------------------------------------------------- the command line
+N_CLI, L_CLI, REF_SEED = 4000, 600, 77
+MINOR = (80, 60, 50, 40)
+
+
+def synth_bam(d, name, reads, seed, cfg=None):
+    args = [SYNTH, "--reads", str(reads), "--cols", str(L_CLI), "--seed", str(seed), "--ref-seed", str(REF_SEED), "--partial", "0.1",
+            "--minor-permille", *map(str, MINOR), "-o", str(d / name)]
+    if cfg:
+        args += ["--config-out", str(d / cfg)]
+    subprocess.check_call(args)
+    sp = synth.SynthParams(seed=seed, partial_rate=0.1, minor_permille=MINOR)
+    return synth.rows(sp, L_CLI, 0, reads, synth.reference(REF_SEED, L_CLI))
+
+
+@pytest.fixture(scope="module")
+def cli(tmp_path_factory):
+    d = tmp_path_factory.mktemp("take_cli")
+    rows = {name: synth_bam(d, name, n, seed, cfg="cfg.json" if name == "a.bam" else None)
+            for name, n, seed in (("a.bam", N_CLI, 31), ("b.bam", 900, 32), ("c.bam", 2500, 33))}
+    return d, rows, synth.reference(REF_SEED, L_CLI)
+
+
+def juliet(d, *args):
+    return subprocess.run([JULIET, *args], cwd=d, capture_output=True, text=True, timeout=120)
+
+
+def flat_variants(j):
+    out = []
+    for gi, g in enumerate(j["genes"]):
+        for vp in g["variant_positions"]:
+            for aa in vp["variant_amino_acids"]:
+                for vc in aa["variant_codons"]:
+                    out.append((gi, vp["ref_position"], msa.codon_index(vc["codon"]), vc, vp))
+    return sorted(out, key=lambda r: r[:3])
+
+
+def assert_json_is_oracle(j, sel, names_idx, ref, oracle):
+    """The JSON of a phasing run against the oracle on the rows `sel`; names_idx[i] = the number in the name of read i."""
+    genes = np.array([(1, L_CLI + 1)], dtype=capi.GENE)
+    exp = oracle.call(sel, genes, refseq=ref)
+    got = flat_variants(j)
+    assert len(got) == len(exp) >= 1
+    for (gi, pos, cod, vc, vp), e in zip(got, exp):
+        assert (gi, pos, cod) == (e["gene"], e["codon_pos"], e["codon"])
+        assert vc["count"] == e["count"] and vp["coverage"] == e["coverage"] and vc["expected"] == e["expected"]
+        assert abs(vc["pValue"] - e["p_value"]) <= 1e-10
+    ph = oracle.phase(sel, exp)
+    hb, s = j["haplotype"], ph["summary"]
+    assert (hb["reported_reads"], hb["insufficient_coverage_reads"], hb["damaged_reads"]) == \
+        (s["reported_reads"], s["insufficient_reads"], s["damaged_reads"])
+    assert [h["reads"] for h in hb["haplotypes"]] == ph["hap_count"].tolist() and len(hb["haplotypes"]) >= 2
+    for hi, h in enumerate(hb["haplotypes"]):
+        assert [msa.codon_index(c) for c in h["codons"]] == ph["hap_pattern"][hi].tolist()
+        # the names follow the indices: read i of the taken window carries the name of the read it was taken from
+        assert [int(n.split("/")[1]) for n in h["read_names"]] == names_idx[np.nonzero(ph["read_hap"] == hi)[0]].tolist()
+    for k, (gi, pos, cod, vc, vp) in enumerate(got):
+        assert vc["haplotype_hit"] == [bool(x) for x in ph["hit"][k]]
+    assert j["target_config"]["n_reads"] == len(sel)
+
+
+def test_cli_downsample_equals_the_oracle_on_the_mirrored_selection(cli, oracle):
+    d, rows, ref = cli
+    r = juliet(d, "-c", "cfg.json", "--mode-phasing", "--downsample", "1500", "--sample-seed", "9", "a.bam", "ds.json", "ds.html")
+    assert r.returncode == 0, r.stderr
+    j = json.load(open(d / "ds.json"))
+    idx = capi.sample_reads(N_CLI, 1500, 9)
+    assert_json_is_oracle(j, rows["a.bam"][idx], idx.astype(np.int64), ref, oracle)
+    assert j["input"]["sampling"] == dict(seed=9, sources=[dict(file="a.bam", reads=N_CLI, kept=1500)])
+    html = open(d / "ds.html").read()        # the HTML renders the block: seed, file, reads, kept
+    m = re.search(r'<table id="sampling-table" data-seed="9">.*?</table>', html, flags=re.S)
+    assert m and f"<td>a.bam</td><td>{N_CLI}</td><td>1500</td>" in m.group(0)
+
+
+def norm(path):
+    j = json.load(open(path))
+    j["input"].pop("timestamp")
+    j["input"].pop("command_line")
+    return j
+
+
+def norm_html(path):
+    return re.sub(r"(<tr><th>(?:timestamp|command_line)</th>)<td>.*?</td>", r"\1<td></td>", open(path).read())
+
+
+def test_cli_downsample_at_or_above_the_read_count_changes_nothing(cli):
+    d, rows, ref = cli
+    assert juliet(d, "-c", "cfg.json", "--mode-phasing", "a.bam", "plain.json", "plain.html").returncode == 0
+    for n, tag in ((N_CLI, "eq"), (N_CLI + 1, "above")):
+        r = juliet(d, "-c", "cfg.json", "--mode-phasing", "--downsample", str(n), "--sample-seed", "3", "a.bam", f"{tag}.json", f"{tag}.html")
+        assert r.returncode == 0, r.stderr
+        assert norm(d / f"{tag}.json") == norm(d / "plain.json") and "sampling" not in norm(d / f"{tag}.json")["input"]
+        assert norm_html(d / f"{tag}.html") == norm_html(d / "plain.html")
+
+
+def test_cli_batch_with_downsample_equals_the_single_runs(cli):
+    """The barcoded case: every sample of the list to the same depth (c.bam goes down, b.bam is below it and stays)."""
+    d, rows, ref = cli
+    opts = ["-c", "cfg.json", "--mode-phasing", "--downsample", "1200", "--sample-seed", "4"]
+    (d / "list.tsv").write_text("".join(f"{s}.bam\tbatch_{s}.json\tbatch_{s}.html\n" for s in "abc"))
+    r = juliet(d, *opts, "--batch", "list.tsv")
+    assert r.returncode == 0, r.stderr
+    for s, n in (("a", N_CLI), ("b", 900), ("c", 2500)):
+        assert juliet(d, *opts, f"{s}.bam", f"one_{s}.json", f"one_{s}.html").returncode == 0
+        assert norm(d / f"batch_{s}.json") == norm(d / f"one_{s}.json")
+        assert norm_html(d / f"batch_{s}.html") == norm_html(d / f"one_{s}.html")
+        assert norm(d / f"batch_{s}.json")["target_config"]["n_reads"] == min(n, 1200)
+        assert ("sampling" in norm(d / f"batch_{s}.json")["input"]) == (n > 1200)
+
+
+def test_cli_mix_equals_the_oracle_on_the_mirrored_mixture(cli, oracle):
+    d, rows, ref = cli
+    r = juliet(d, "-c", "cfg.json", "--mode-phasing", "--mix", "b.bam,c.bam", "--mix-perc", "20", "--downsample", "2000", "--sample-seed", "5",
+               "a.bam", "mix.json")
+    assert r.returncode == 0, r.stderr
+    counts = capi.mix_counts(3, 2000, 20).tolist()
+    assert counts == [1200, 400, 400]
+    files = ("a.bam", "b.bam", "c.bam")
+    idx = [capi.sample_reads(len(rows[f]), k, 5 + m) for m, (f, k) in enumerate(zip(files, counts))]
+    sel = np.concatenate([rows[f][i] for f, i in zip(files, idx)])
+    j = json.load(open(d / "mix.json"))
+    assert_json_is_oracle(j, sel, np.concatenate(idx).astype(np.int64), ref, oracle)
+    assert j["input"]["sampling"] == dict(seed=5, sources=[dict(file=f, reads=len(rows[f]), kept=k) for f, k in zip(files, counts)])
+    # the default coverage is mixdata's 3000 and the default share 1 %
+    r = juliet(d, "-c", "cfg.json", "--mix", "b.bam", "a.bam", "mix_default.json")
+    assert r.returncode == 0, r.stderr
+    j = json.load(open(d / "mix_default.json"))
+    assert [s["kept"] for s in j["input"]["sampling"]["sources"]] == [2970, 30] and j["target_config"]["n_reads"] == 3000
+
+
+def test_cli_mix_with_a_clone_that_is_too_small(cli):
+    d, rows, ref = cli
+    r = juliet(d, "-c", "cfg.json", "--mix", "b.bam", "--mix-perc", "50", "--downsample", "2000", "a.bam", "small.json")
+    assert r.returncode == 2, (r.returncode, r.stderr)
+    assert "b.bam" in r.stderr and "900" in r.stderr and "1000" in r.stderr       # the file and the two numbers
+    assert not os.path.exists(d / "small.json")
