@@ -293,6 +293,29 @@ int jl_pileup_fetch(jl_ctx *ctx, uint32_t *col_counts, uint32_t *pos_gene, uint3
  */
 int jl_consensus_fetch(jl_ctx *ctx, uint8_t *out);
 /*
+ * Column pileup of the resident matrix BY CLASS OF READS (docs/SPEC.md §13): what a haplotype — or the damaged reads, or any
+ * other set of reads — looks like along the whole window, not only at the called codons.  A read is one bit position in every
+ * plane row, so a class is a bit mask in the plane-row layout and a per-class count is popcount(symbol word & class mask) over
+ * the words the plain pileup streams: one pass over the matrix for up to 16 classes, ceil(n_classes / 16) passes in all.
+ * label[n_reads]: read i belongs to class label[i] when label[i] < n_classes and to no class otherwise, so the ids of
+ * jl_phase_fetch can be passed as they are (JL_HAP_INSUFFICIENT / JL_HAP_DAMAGED fall out).  The labels are copied before the
+ * call returns; it uploads and enqueues on the context's stream, into buffers of its own (grown on demand, released with the
+ * context), and touches nothing else: the matrix, the insertion counters, the results of an earlier jl_pileup_async /
+ * jl_call_async / jl_phase_async / jl_run_async and what their fetch calls return afterwards, and the context's captured
+ * graph stay as they are.  Every kind of resident matrix is accepted, an adopted one with its own plane stride included.
+ * JL_ERR_STATE: no resident matrix.  JL_ERR_ARG (jl_last_error says which): label == NULL, n_classes == 0 or above
+ * JL_CLASS_MAX.  A refused call changes nothing.
+ */
+enum { JL_CLASS_MAX = 704 };   /* JL_MAX_HAPLOTYPES + the two read categories */
+int jl_class_pileup_async(jl_ctx *ctx, const uint16_t *label, uint32_t n_classes);
+/* Wait and copy out: counts[n_classes][n_cols][6] (A C G T - N, as col_counts of jl_pileup_fetch), class_reads[n_classes]
+ * (reads per class), both of the last jl_class_pileup_async.  Either pointer may be NULL.  JL_ERR_STATE: none was enqueued. */
+int jl_class_pileup_fetch(jl_ctx *ctx, uint32_t *counts, uint32_t *class_reads);
+/* Host only (no device, no context).  Per-column consensus of ONE [n_cols][6] count table by the rule of jl_consensus_fetch:
+ * majority of A C G T -, lowest code on ties (N does not vote); out[n_cols]: 0..3 base, 4 = majority deletion, 5 = nobody
+ * covers the column. */
+int jl_consensus_of_counts(const uint32_t *col_counts, uint32_t n_cols, uint8_t *out);
+/*
  * Reference/majority codon, error model, Fisher's exact x Bonferroni, filters, variant table
  * (SPEC §4-7; J:38-42).  `drm_masks`: optional [P] 64-bit codon masks; with --drm-only a codon is kept
  * only if its bit is set (J:370); NULL disables.  Table stays on the device; enqueues only.

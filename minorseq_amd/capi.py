@@ -31,7 +31,7 @@ SUMMARY = np.dtype([(n, "<u4") for n in SUMMARY_FIELDS])
 EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", "jl_ctx_destroy", "jl_last_error",
            "jl_sync", "jl_col_stride", "jl_plane_stride", "jl_msa_upload", "jl_msa_alloc", "jl_msa_adopt", "jl_msa_pack_rows",
            "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_take", "jl_msa_take_async", "jl_sample_reads", "jl_mix_counts", "jl_msa_download", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
-           "jl_consensus_fetch", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_phase_async", "jl_phase_fetch",
+           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_phase_async", "jl_phase_fetch",
            "jl_ctx_stream", "jl_run_async", "jl_run_wait", "jl_run_done", "jl_run_view_get", "jl_group_create", "jl_group_destroy",
            "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
            "jl_allgather_variants", "jl_allgather_variants_async", "jl_allgather_variants_async_many", "jl_allgather_variants_many", "jl_group_exchange_bind", "jl_group_exchange_collect", "jl_xwin_plan", "jl_xwin_assemble_local",
@@ -200,6 +200,9 @@ def load_library(path=LIB_PATH):
     lib.jl_n_positions.restype = u32
     lib.jl_pileup_fetch.argtypes = [vp] * 7
     lib.jl_consensus_fetch.argtypes = [vp, vp]
+    lib.jl_class_pileup_async.argtypes = [vp, vp, u32]
+    lib.jl_class_pileup_fetch.argtypes = [vp, vp, vp]
+    lib.jl_consensus_of_counts.argtypes = [vp, u32, vp]
     lib.jl_call_async.argtypes = [vp, C.POINTER(Params), vp]
     lib.jl_call_fetch.argtypes = [vp, vp, u32, C.POINTER(u32)]
     lib.jl_variant_table_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u32)]
@@ -497,6 +500,24 @@ class Juliet:
         out = np.zeros(self.n_cols, dtype=np.uint8)
         self._chk(self.lib.jl_consensus_fetch(self.h, _p(out)))
         return out
+
+    def class_pileup(self, labels, n_classes, wait=True):
+        """jl_class_pileup_async (docs/SPEC.md §13): the column pileup of the resident matrix by class of reads — read i counts
+        for class labels[i] when labels[i] < n_classes, for none otherwise (the ids of a phasing run can be passed as they are).
+        Returns (counts[n_classes, n_cols, 6], class_reads[n_classes]); wait=False only enqueues on this context's stream and
+        returns None (class_pileup_fetch brings the arrays)."""
+        labels = np.ascontiguousarray(labels, dtype=np.uint16)
+        assert len(labels) == self.n_reads
+        self._chk(self.lib.jl_class_pileup_async(self.h, _p(labels), int(n_classes)))
+        self._class_shape = (int(n_classes), self.n_cols)
+        return self.class_pileup_fetch() if wait else None
+
+    def class_pileup_fetch(self):
+        k, l = getattr(self, "_class_shape", (0, 0))
+        counts = np.zeros((k, l, 6), dtype=np.uint32)
+        reads = np.zeros(k, dtype=np.uint32)
+        self._chk(self.lib.jl_class_pileup_fetch(self.h, _p(counts), _p(reads)))
+        return counts, reads
 
     def call_async(self, params=None, drm_masks=None):
         prm = params or default_params()
@@ -805,6 +826,19 @@ def sample_reads(n_reads, k, seed=0):
     if rc:
         raise JulietError(rc, "jl_sample_reads")
     return out[: n.value].copy()
+
+
+def consensus_of_counts(counts2d):
+    """jl_consensus_of_counts (host only, docs/SPEC.md §13): the per-column consensus of one [n_cols, 6] count table — majority
+    of A C G T -, lowest code on ties; 4 = majority deletion, 5 = nobody covers the column."""
+    lib = load_library()
+    counts2d = np.ascontiguousarray(counts2d, dtype=np.uint32)
+    assert counts2d.ndim == 2 and counts2d.shape[1] == 6
+    out = np.zeros(max(1, len(counts2d)), dtype=np.uint8)
+    rc = lib.jl_consensus_of_counts(_p(counts2d), len(counts2d), _p(out))
+    if rc:
+        raise JulietError(rc, "jl_consensus_of_counts")
+    return out[: len(counts2d)].copy()
 
 
 def mix_counts(n_sources, coverage, percentage):

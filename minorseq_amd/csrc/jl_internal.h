@@ -323,6 +323,22 @@ struct jl_take_args {
 };
 void jl_launch_take(const jl_take_args *a, hipStream_t st);
 
+// ---- column pileup by class of reads (kernels_class.hip, capi_class.hip)
+struct jl_class_args {
+    const uint8_t *msa;        // the window's bit planes
+    uint64_t plane_stride;     // ... and their stride (an adopted matrix brings its own)
+    uint64_t n_reads;
+    uint32_t n_cols, n_classes;
+    const uint16_t *label;     // [n_reads]
+    uint8_t *mask;             // [n_classes][mask_stride] one row per class in the plane-row layout
+    uint64_t mask_stride;      // jl_plane_stride(n_reads): whole 128-byte lines, whatever plane_stride is
+    uint32_t *counts;          // [n_classes][n_cols][6], zeroed
+    uint32_t *class_reads;     // [n_classes], zeroed
+    uint32_t seg_tiles;        // tiles of 512 reads a workgroup of the counting walks (set by the launcher, as is:)
+    uint32_t k_first;          // first class of the counting launch's pass 0
+};
+void jl_launch_class_pileup(const jl_class_args *a, hipStream_t st);
+
 inline int jl_hip_status(hipError_t e) { return e == hipErrorOutOfMemory ? JL_ERR_MEMORY : JL_ERR_DEVICE; }
 
 // A device array that grows: `cap` elements at `d`.  Making room returns HIP's error (jl_hip_status: the status it becomes).
@@ -457,6 +473,15 @@ struct jl_ctx {
     uint32_t *h_take_idx = nullptr;   // pinned staging of the same
     size_t h_take_cap = 0;            // ... in indices
     hipEvent_t take_ev = nullptr;     // behind the last upload out of the staging: it may be refilled then
+
+    // ---- jl_class_pileup_async: buffers of its own, grown on demand (capi_class.hip); no stage and no run touches them
+    jl_dev_array<uint16_t> class_label;
+    jl_dev_array<uint8_t> class_mask;
+    jl_dev_array<uint32_t> class_out;   // counts [class_k][class_cols][6], then class_reads [class_k]
+    uint16_t *h_class_label = nullptr;  // pinned staging of the labels
+    size_t h_class_cap = 0;             // ... in labels
+    hipEvent_t class_ev = nullptr;      // behind the last upload out of the staging
+    uint32_t class_k = 0, class_cols = 0;   // shape of the last class pileup enqueued (class_k = 0: none)
 
     // ---- phasing sharded by reads: the groups of this matrix exported for the merge (jl_phase_groups_async / _fetch)
     bool phase_export = false;        // the phase launch in flight / last run exported instead of selecting
@@ -663,6 +688,8 @@ extern "C" int jl_ingest_verdict(jl_ctx *ctx);
 void jl_records_release(jl_ctx *ctx);
 // capi_take.hip: frees the index buffers of the takes into `ctx` (jl_ctx_destroy)
 void jl_take_release(jl_ctx *ctx);
+// capi_class.hip: frees the buffers of the class pileups of `ctx` (jl_ctx_destroy)
+void jl_class_release(jl_ctx *ctx);
 void jl_launch_regroup(jl_ctx *ctx, const uint16_t *d_hap_of_group, uint32_t n_groups, uint32_t n_haplotypes, bool phased);
 void jl_launch_insertions(jl_ctx *dst, const jl_records &R);
 void jl_launch_fisher_eval(jl_ctx *ctx, uint32_t n, const uint32_t *a, const uint32_t *c, const uint32_t *cov, int tail,

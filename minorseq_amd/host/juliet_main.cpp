@@ -56,6 +56,7 @@ struct Options {
     uint32_t windows = 1;            // column windows the reference is cut into (doc/JULIET.md:261-264: the split never shows)
     std::vector<int> devices;        // --devices a,b,...: one rank (thread) per device, consecutive windows each
     std::string dump_msa, dump_config, consensus;
+    std::string hap_fasta;           // --haplotype-fasta: one consensus per reported haplotype (docs/SPEC.md §13)
     bool fuse_only = false;        // invoked as `fuse in.bam out.fasta` (doc/FUSE.md:26-31): the consensus and nothing else
     double ins_min_frac = 0.5;     // an insertion enters the consensus when more than this share of the covering reads carries it
     uint32_t ins_min_distance = 10;  // ... and the previous included insertion lies at least this many columns back (UNPINNED)
@@ -101,6 +102,12 @@ struct Options {
         "      --consensus <out.fasta>         also write the window's consensus as `fuse` would (doc/FUSE.md:17-20):\n"
         "                                      majority base, major deletions removed, in-frame majority insertions kept\n"
         "      --ins-min-frac 0.5  --ins-min-distance 10   when an insertion enters the consensus\n"
+        "      --haplotype-fasta <out.fasta>   with --mode-phasing: one consensus record per reported haplotype, in the JSON's\n"
+        "                                      order, from the column pileup of that haplotype's reads alone (docs/SPEC.md section\n"
+        "                                      13): majority base, major deletions removed, N where none of its reads covers the\n"
+        "                                      column.  Insertions are not included (their counters are per window, not per\n"
+        "                                      read).  Follows --downsample / --mix.  Not with --windows, --devices a,b, --batch\n"
+        "                                      or as fuse\n"
         "      --downsample N [--sample-seed S]  call on N reads of the sample (\"downsample it to 6000x\", doc/JULIETFLOW.md:23-25):\n"
         "                                      the reads are chosen by docs/SPEC.md section 12 (seed default 0; samples of one seed are\n"
         "                                      nested) and gathered on the device; N at or above the read count changes nothing.\n"
@@ -236,6 +243,7 @@ Options parse(int argc, char **argv)
             }
         }
         else if (a == "--consensus") o.consensus = need(i);
+        else if (a == "--haplotype-fasta") o.hap_fasta = need(i);
         else if (a == "--ins-min-frac") o.ins_min_frac = std::stod(need(i));
         else if (a == "--ins-min-distance") o.ins_min_distance = (uint32_t)std::stoul(need(i));
         else if (a == "--dump-msa") o.dump_msa = need(i);
@@ -260,6 +268,13 @@ Options parse(int argc, char **argv)
     const std::string prog = argv[0];
     const size_t slash = prog.find_last_of('/');
     const bool as_fuse = (slash == std::string::npos ? prog : prog.substr(slash + 1)) == "fuse";
+    if (!o.hap_fasta.empty()) {   // refused here, before any file is read or any GPU work
+        auto refuse = [](const char *why) { std::cerr << "juliet: --haplotype-fasta " << why << "\n"; std::exit(1); };
+        if (as_fuse) refuse("is not an option of fuse");
+        if (!o.phasing) refuse("writes the haplotypes of a phasing run (add --mode-phasing)");
+        if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
+        if (!o.batch.empty()) refuse("writes one file for one sample (not with --batch)");
+    }
     if (o.sampling()) {   // what sampling cannot be combined with is refused here, before any file is read or any GPU work
         auto refuse = [&](const char *why) { std::cerr << "juliet: " << (o.mix.empty() ? "--downsample " : "--mix ") << why << "\n"; std::exit(1); };
         if (o.have_downsample && o.downsample == 0) refuse("wants at least one read (--downsample 0)");
@@ -1246,6 +1261,34 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
     return root;
 }
 
+// --haplotype-fasta (docs/SPEC.md §13): one record per reported haplotype, in the JSON's order, from ONE class pileup of the window
+// resident on `ctx` with the phasing run's own per-read ids as labels.  No reported haplotype: an empty file.  0, or the exit code.
+int write_haplotype_fasta(const Options &opt, jl_ctx *ctx, const Results &R, uint32_t win_begin, uint32_t n_cols)
+{
+    const uint32_t H = R.ps.n_haplotypes;
+    std::vector<uint32_t> counts((size_t)H * n_cols * 6);
+    if (H) {
+        if (jl_class_pileup_async(ctx, R.read_hap.data(), H) != JL_OK) die_jl(ctx, "class pileup");
+        if (jl_class_pileup_fetch(ctx, counts.data(), nullptr) != JL_OK) die_jl(ctx, "class pileup fetch");
+    }
+    std::ofstream f(opt.hap_fasta);
+    if (!f) { std::cerr << "juliet: cannot write " << opt.hap_fasta << "\n"; return 2; }
+    std::vector<uint8_t> cons(n_cols);
+    for (uint32_t h = 0; h < H; ++h) {
+        if (jl_consensus_of_counts(counts.data() + (size_t)h * n_cols * 6, n_cols, cons.data()) != JL_OK) die_jl(nullptr, "consensus of counts");
+        std::string freq, seq;
+        Json::of(R.ps.reported_reads ? (double)R.hap_count[h] / (double)R.ps.reported_reads : 0.0).write(freq);
+        for (uint32_t c = 0; c < n_cols; ++c)
+            if (cons[c] != 4) seq += "ACGT?N"[cons[c]];   // (4: a major deletion, the column is removed)
+        f << ">" << haplotype_name(h) << " reads=" << R.hap_count[h] << " frequency=" << freq << " window=" << (win_begin + 1) << "-"
+          << (win_begin + n_cols) << " source=" << opt.bam << "\n";
+        for (size_t i = 0; i < seq.size(); i += 70) f << seq.substr(i, 70) << "\n";
+    }
+    f.close();
+    if (!f) { std::cerr << "juliet: cannot write " << opt.hap_fasta << "\n"; return 2; }
+    return 0;
+}
+
 // Every output of one run — the JSON text, or its HTML rendering, by extension — each file closed and its stream checked:
 // a short write or a full disk is a failed output, not a quiet success.  "" or the first output that failed.
 std::string write_outputs(const std::vector<std::string> &outputs, const Json &root)
@@ -1865,6 +1908,10 @@ int main(int argc, char **argv)
         if (opt.phasing)
             if (const char *what = fetch_phase(ctx, n_reads, R)) die_jl(ctx, what);
         tick("  haplotypes + ids");
+        if (!opt.hap_fasta.empty()) {
+            if (const int code = write_haplotype_fasta(opt, ctx, R, win_begin, n_cols)) return code;
+            tick("haplotype fasta");
+        }
         // (the context is not torn down: the process is about to end, and freeing two dozen device buffers one by one took
         // 4-6 ms of a 0.1 s run)
         }
