@@ -316,6 +316,30 @@ int jl_class_pileup_fetch(jl_ctx *ctx, uint32_t *counts, uint32_t *class_reads);
  * covers the column. */
 int jl_consensus_of_counts(const uint32_t *col_counts, uint32_t n_cols, uint8_t *out);
 /*
+ * Which reported haplotype a read agrees with WHERE IT CAN BE READ (docs/SPEC.md §14): phasing drops a read with a deletion, a
+ * filtered N or an uncovered cell at any variant position (JL_HAP_DAMAGED); most such reads are clean at the other positions and
+ * match exactly one reported haplotype there.  pos_cols[n_pos]: window columns of codon starts, strictly ascending, each + 2 <
+ * n_cols (overlapping codons allowed); pattern[n_hap] rows of n_pos codon indices 0..63, pattern_stride bytes apart — pos_cols
+ * and hap_pattern of jl_phase_fetch can be passed as they are.  Per read i: position p is INFORMATIVE iff the three codes at
+ * pos_cols[p] .. + 2 are all < 4 (a gap, an N and an uncovered cell alike make it open); k_i = informative positions; haplotype
+ * h AGREES iff its codon equals the read's at every informative position; m_i = agreeing haplotypes.  rescue[i] =
+ * JL_RESCUE_UNINFORMATIVE if k_i < min_positions, else JL_RESCUE_NONE if m_i == 0, else that h if m_i == 1, else
+ * JL_RESCUE_AMBIGUOUS.  Every read is evaluated, not only the damaged ones: a clean read of haplotype h gets h.
+ * The contract is jl_class_pileup_async's: the inputs are copied before the call returns; it enqueues on the context's stream
+ * into buffers of its own (grown on demand, released with the context) and touches nothing else — the matrix, the insertion
+ * counters, earlier stage results and the captured graph stay as they are.  Every kind of resident matrix is accepted.
+ * JL_ERR_STATE: no resident matrix.  JL_ERR_ARG (jl_last_error says which): a NULL array; n_pos 0 or above 4096; n_hap 0 or
+ * above JL_MAX_HAPLOTYPES; pattern_stride < n_pos; min_positions 0 or above n_pos; a column with c + 2 >= n_cols; columns not
+ * strictly ascending; a pattern byte above 63.  A refused call changes nothing: what an earlier call enqueued can still be fetched.
+ */
+enum { JL_RESCUE_UNINFORMATIVE = 0xFFFB, JL_RESCUE_NONE = 0xFFFC, JL_RESCUE_AMBIGUOUS = 0xFFFD };
+int jl_phase_rescue_async(jl_ctx *ctx, const uint32_t *pos_cols, uint32_t n_pos, const uint8_t *pattern,
+                          uint32_t pattern_stride, uint32_t n_hap, uint32_t min_positions);
+/* Wait and copy out, all of the last jl_phase_rescue_async: rescue[n_reads]; hap_reads[n_hap] = reads with rescue == h;
+ * tally[4] = reads {assigned, ambiguous, none, uninformative}, summing to n_reads.  Any pointer may be NULL.
+ * JL_ERR_STATE: none was enqueued. */
+int jl_phase_rescue_fetch(jl_ctx *ctx, uint16_t *rescue, uint32_t *hap_reads, uint64_t *tally /* [4] */);
+/*
  * Reference/majority codon, error model, Fisher's exact x Bonferroni, filters, variant table
  * (SPEC §4-7; J:38-42).  `drm_masks`: optional [P] 64-bit codon masks; with --drm-only a codon is kept
  * only if its bit is set (J:370); NULL disables.  Table stays on the device; enqueues only.

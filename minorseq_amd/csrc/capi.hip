@@ -150,6 +150,7 @@ void jl_ctx_destroy(jl_ctx *ctx)
     jl_records_release(ctx);
     jl_take_release(ctx);
     jl_class_release(ctx);
+    jl_rescue_release(ctx);
     void *ptrs[] = {ctx->d_pos_gene, ctx->d_pos_codon, ctx->d_pos_col, ctx->d_pos_refcfg, ctx->d_col_head, ctx->d_pos_next, ctx->d_guess, ctx->d_chunks,
                     ctx->d_counts, ctx->d_called, ctx->d_staged, ctx->d_drm, ctx->d_variants, ctx->d_nvar, ctx->d_meta, ctx->d_vpcols,
                     ctx->d_col2pos, ctx->d_varcol, ctx->d_keys, ctx->d_flagw, ctx->d_read_slot, ctx->d_read_hap,

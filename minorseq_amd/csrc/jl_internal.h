@@ -339,6 +339,24 @@ struct jl_class_args {
 };
 void jl_launch_class_pileup(const jl_class_args *a, hipStream_t st);
 
+// ---- which reported haplotype a read agrees with (kernels_rescue.hip, capi_rescue.hip; docs/SPEC.md §14)
+#define JL_RESCUE_POS_MAX JL_VARIANT_CAP   // variant positions of one call: the variant table's capacity
+#define JL_RESCUE_HAP_PAD 704u             // JL_MAX_HAPLOTYPES in whole chunks of 64 (a lane owns a haplotype)
+struct jl_rescue_args {
+    const uint8_t *msa;        // the window's bit planes
+    uint64_t plane_stride;     // ... and their stride (an adopted matrix brings its own)
+    uint64_t n_reads;
+    uint32_t n_runs;           // runs of 64 reads: ceil(n_reads / 64); 8 (n_runs) <= plane_stride
+    uint32_t n_pos, n_hap, min_positions;
+    uint32_t hap_pad, pad_;    // n_hap in whole chunks of 64
+    const uint32_t *pos_cols;  // [n_pos], each + 2 < n_cols
+    const uint32_t *pat4;      // [ceil(n_pos / 4)][hap_pad]: byte q of dword [g][h] = pattern[h][4 g + q] (0 where either does not exist)
+    uint16_t *rescue;          // [n_reads]
+    uint32_t *hap_reads;       // [n_hap], zeroed
+    unsigned long long *tally; // [4] assigned, ambiguous, none, uninformative; zeroed
+};
+void jl_launch_phase_rescue(const jl_rescue_args *a, hipStream_t st);
+
 inline int jl_hip_status(hipError_t e) { return e == hipErrorOutOfMemory ? JL_ERR_MEMORY : JL_ERR_DEVICE; }
 
 // A device array that grows: `cap` elements at `d`.  Making room returns HIP's error (jl_hip_status: the status it becomes).
@@ -482,6 +500,15 @@ struct jl_ctx {
     size_t h_class_cap = 0;             // ... in labels
     hipEvent_t class_ev = nullptr;      // behind the last upload out of the staging
     uint32_t class_k = 0, class_cols = 0;   // shape of the last class pileup enqueued (class_k = 0: none)
+
+    // ---- jl_phase_rescue_async: buffers of its own, grown on demand (capi_rescue.hip); no stage and no run touches them
+    jl_dev_array<uint32_t> rescue_in;    // pos_cols [n_pos], then pat4 (jl_rescue_args)
+    jl_dev_array<uint32_t> rescue_out;   // tally [4] as 8 words, hap_reads [JL_RESCUE_HAP_PAD], then rescue [rescue_n] 16 bits each
+    uint32_t *h_rescue_in = nullptr;     // pinned staging of rescue_in
+    size_t h_rescue_cap = 0;             // ... in words
+    hipEvent_t rescue_ev = nullptr;      // behind the last upload out of the staging
+    uint64_t rescue_n = 0;               // reads of the last rescue enqueued (0: none)
+    uint32_t rescue_h = 0;               // ... and its haplotypes
 
     // ---- phasing sharded by reads: the groups of this matrix exported for the merge (jl_phase_groups_async / _fetch)
     bool phase_export = false;        // the phase launch in flight / last run exported instead of selecting
@@ -690,6 +717,8 @@ void jl_records_release(jl_ctx *ctx);
 void jl_take_release(jl_ctx *ctx);
 // capi_class.hip: frees the buffers of the class pileups of `ctx` (jl_ctx_destroy)
 void jl_class_release(jl_ctx *ctx);
+// capi_rescue.hip: frees the buffers of the rescue calls of `ctx` (jl_ctx_destroy)
+void jl_rescue_release(jl_ctx *ctx);
 void jl_launch_regroup(jl_ctx *ctx, const uint16_t *d_hap_of_group, uint32_t n_groups, uint32_t n_haplotypes, bool phased);
 void jl_launch_insertions(jl_ctx *dst, const jl_records &R);
 void jl_launch_fisher_eval(jl_ctx *ctx, uint32_t n, const uint32_t *a, const uint32_t *c, const uint32_t *cov, int tail,

@@ -167,7 +167,26 @@ inline std::string render_html(const Json &root)
                     for (const Json &r : rn->arr) h += "<span class=\"rn\">" + html_escape(r.str) + "</span> ";
                 h += "</details></td></tr>\n";
             }
-        h += "</table></details>\n";
+        h += "</table>";
+        if (const Json *rs = hb->get("rescue")) {   // --rescue-damaged (docs/SPEC.md §14): the damaged reads, judged where they can be read
+            h += "\n<table id=\"hap-rescue\"><tr><th>Damaged reads, rescued (at least " + num_str(rs->get("min_positions")) +
+                 " informative positions)</th><th>#Reads</th></tr>\n";
+            static const char *rc[4][2] = {{"assigned_reads", "Assigned to one haplotype"}, {"ambiguous_reads", "Ambiguous (several agree)"},
+                                           {"incompatible_reads", "Incompatible (none agrees)"}, {"uninformative_reads", "Uninformative"}};
+            for (auto &c : rc) h += "<tr data-key=\"" + std::string(c[0]) + "\"><th>" + c[1] + "</th>" + td(num_str(rs->get(c[0]))) + "</tr>\n";
+            h += "</table>\n<table id=\"hap-rescued\"><tr><th>Haplotype</th><th>% with rescued</th><th>#Rescued</th><th>Rescued read names</th></tr>\n";
+            if (haps)
+                for (const Json &hp : haps->arr) {
+                    if (!hp.get("rescued_reads")) continue;
+                    h += "<tr>" + td(hp.get_str("name")) + td(format_hap_percent(100.0 * hp.get("frequency_with_rescued")->num)) +
+                         td(num_str(hp.get("rescued_reads"))) + "<td><details><summary>" +
+                         std::to_string(hp.get("rescued_read_names")->arr.size()) + "</summary>";
+                    for (const Json &r : hp.get("rescued_read_names")->arr) h += "<span class=\"rn\">" + html_escape(r.str) + "</span> ";
+                    h += "</details></td></tr>\n";
+                }
+            h += "</table>\n";
+        }
+        h += "</details>\n";
     }
     h += "</body></html>\n";
     return h;

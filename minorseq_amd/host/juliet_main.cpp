@@ -57,6 +57,9 @@ struct Options {
     std::vector<int> devices;        // --devices a,b,...: one rank (thread) per device, consecutive windows each
     std::string dump_msa, dump_config, consensus;
     std::string hap_fasta;           // --haplotype-fasta: one consensus per reported haplotype (docs/SPEC.md §13)
+    bool rescue = false;             // --rescue-damaged: which reported haplotype each damaged read agrees with (docs/SPEC.md §14)
+    uint32_t rescue_min = 1;         // --rescue-min-positions K: informative positions a read needs to be judged at all
+    bool have_rescue_min = false;
     bool fuse_only = false;        // invoked as `fuse in.bam out.fasta` (doc/FUSE.md:26-31): the consensus and nothing else
     double ins_min_frac = 0.5;     // an insertion enters the consensus when more than this share of the covering reads carries it
     uint32_t ins_min_distance = 10;  // ... and the previous included insertion lies at least this many columns back (UNPINNED)
@@ -108,6 +111,14 @@ struct Options {
         "                                      column.  Insertions are not included (their counters are per window, not per\n"
         "                                      read).  Follows --downsample / --mix.  Not with --windows, --devices a,b, --batch\n"
         "                                      or as fuse\n"
+        "      --rescue-damaged [--rescue-min-positions K]  with --mode-phasing: every damaged read (a deletion, a filtered N or an\n"
+        "                                      uncovered cell at some variant position) is compared with the reported haplotypes at\n"
+        "                                      the positions where it can be read, K of them at least (default 1; docs/SPEC.md\n"
+        "                                      section 14): it is assigned to the one haplotype that agrees there, or counted as\n"
+        "                                      ambiguous, incompatible or uninformative.  The haplotype block gains `rescue`, every\n"
+        "                                      haplotype rescued_reads, rescued_read_names and frequency_with_rescued; with\n"
+        "                                      --haplotype-fasta the rescued reads join their haplotype's consensus.  Follows\n"
+        "                                      --downsample / --mix.  Not with --windows, --devices a,b, --batch or as fuse\n"
         "      --downsample N [--sample-seed S]  call on N reads of the sample (\"downsample it to 6000x\", doc/JULIETFLOW.md:23-25):\n"
         "                                      the reads are chosen by docs/SPEC.md section 12 (seed default 0; samples of one seed are\n"
         "                                      nested) and gathered on the device; N at or above the read count changes nothing.\n"
@@ -244,6 +255,8 @@ Options parse(int argc, char **argv)
         }
         else if (a == "--consensus") o.consensus = need(i);
         else if (a == "--haplotype-fasta") o.hap_fasta = need(i);
+        else if (a == "--rescue-damaged") o.rescue = true;
+        else if (a == "--rescue-min-positions") { o.rescue_min = (uint32_t)std::stoul(need(i)); o.have_rescue_min = true; }
         else if (a == "--ins-min-frac") o.ins_min_frac = std::stod(need(i));
         else if (a == "--ins-min-distance") o.ins_min_distance = (uint32_t)std::stoul(need(i));
         else if (a == "--dump-msa") o.dump_msa = need(i);
@@ -274,6 +287,15 @@ Options parse(int argc, char **argv)
         if (!o.phasing) refuse("writes the haplotypes of a phasing run (add --mode-phasing)");
         if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
         if (!o.batch.empty()) refuse("writes one file for one sample (not with --batch)");
+    }
+    if (o.rescue || o.have_rescue_min) {   // refused here, before any file is read or any GPU work
+        auto refuse = [](const char *why) { std::cerr << "juliet: --rescue-damaged [--rescue-min-positions K] " << why << "\n"; std::exit(1); };
+        if (!o.rescue) refuse("--rescue-min-positions sets a threshold of --rescue-damaged (add it)");
+        if (o.rescue_min == 0) refuse("wants at least one informative position (--rescue-min-positions 0)");
+        if (as_fuse) refuse("are not options of fuse");
+        if (!o.phasing) refuse("assigns reads to the haplotypes of a phasing run (add --mode-phasing)");
+        if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
+        if (!o.batch.empty()) refuse("is not part of a batch (not with --batch)");
     }
     if (o.sampling()) {   // what sampling cannot be combined with is refused here, before any file is read or any GPU work
         auto refuse = [&](const char *why) { std::cerr << "juliet: " << (o.mix.empty() ? "--downsample " : "--mix ") << why << "\n"; std::exit(1); };
@@ -658,6 +680,17 @@ struct Results {
     std::vector<uint8_t> hap_pattern, hit;
     size_t pat_stride = 0, hit_stride = 0;       // hap_pattern[h * pat_stride + p], hit[v * hit_stride + h]
     std::vector<uint16_t> read_hap;
+    // --rescue-damaged (docs/SPEC.md §14): rescue[i] of every read by the run's own positions and haplotypes; empty when no call
+    // was made (no reported haplotype, or more positions asked for than the run has: every damaged read is uninformative then)
+    bool rescued = false;
+    uint32_t rescue_min = 0;
+    std::vector<uint16_t> rescue;
+    // the haplotype a damaged read was assigned to, or JL_HAP_DAMAGED; a read that is not damaged: its own id
+    uint16_t hap_with_rescued(uint64_t i) const
+    {
+        if (read_hap[i] != (uint16_t)JL_HAP_DAMAGED || rescue.empty()) return read_hap[i];
+        return rescue[i] < ps.n_haplotypes ? rescue[i] : (uint16_t)JL_HAP_DAMAGED;
+    }
 };
 
 struct WindowPlan {
@@ -1010,6 +1043,21 @@ const char *fetch_phase(jl_ctx *ctx, uint64_t n_reads, Results &R)
     return nullptr;
 }
 
+// --rescue-damaged, after fetch_phase: one call of the rule of docs/SPEC.md §14 with the run's own positions and haplotypes.
+const char *fetch_rescue(jl_ctx *ctx, uint32_t min_positions, Results &R)
+{
+    R.rescued = true;
+    R.rescue_min = min_positions;
+    R.rescue.clear();
+    if (R.ps.n_haplotypes == 0 || min_positions > R.ps.n_positions) return nullptr;
+    if (jl_phase_rescue_async(ctx, R.pos_cols.data(), R.ps.n_positions, R.hap_pattern.data(), (uint32_t)R.pat_stride, R.ps.n_haplotypes,
+                              min_positions) != JL_OK)
+        return "rescue";
+    R.rescue.resize(R.read_hap.size());
+    if (jl_phase_rescue_fetch(ctx, R.rescue.data(), nullptr, nullptr) != JL_OK) return "rescue fetch";
+    return nullptr;
+}
+
 // What --downsample / --mix did to a sample: the `sampling` block of the JSON's input section, present only when reads were chosen.
 struct SamplingInfo {
     bool acted = false;
@@ -1238,6 +1286,19 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
         std::vector<std::vector<uint32_t>> members(H);
         for (uint64_t i = 0; i < n_reads; ++i)
             if (read_hap[i] < H) members[read_hap[i]].push_back((uint32_t)i);
+        // --rescue-damaged: the damaged reads by what the rule of docs/SPEC.md §14 says of them
+        std::vector<std::vector<uint32_t>> rescued_members(H);
+        uint64_t rescue_cat[4] = {0, 0, 0, 0};   // assigned, ambiguous, incompatible, uninformative
+        uint64_t with_rescued_total = 0;
+        if (R.rescued && ps.n_positions) {   // (no variant position: nothing was phased, no read is damaged, §8)
+            for (uint64_t i = 0; i < n_reads; ++i) {
+                if (read_hap[i] != (uint16_t)JL_HAP_DAMAGED) continue;
+                const uint32_t r = R.rescue.empty() ? (uint32_t)JL_RESCUE_UNINFORMATIVE : R.rescue[i];
+                if (r < H) rescued_members[r].push_back((uint32_t)i), rescue_cat[0]++;
+                else rescue_cat[r == (uint32_t)JL_RESCUE_AMBIGUOUS ? 1 : r == (uint32_t)JL_RESCUE_NONE ? 2 : 3]++;
+            }
+            for (uint32_t h = 0; h < H; ++h) with_rescued_total += (uint64_t)hap_count[h] + rescued_members[h].size();
+        }
         Json hs = Json::array();
         for (uint32_t h = 0; h < H; ++h) {
             Json hj = Json::object();
@@ -1250,12 +1311,28 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
             rn.arr.reserve(members[h].size());
             for (uint32_t i : members[h]) rn.push(Json::of(names[i]));
             hj.set("read_names", std::move(rn));
+            if (R.rescued) {
+                const uint64_t with = (uint64_t)hap_count[h] + rescued_members[h].size();
+                hj.set("rescued_reads", Json::of((uint32_t)rescued_members[h].size()));
+                Json rr = Json::array();
+                rr.arr.reserve(rescued_members[h].size());
+                for (uint32_t i : rescued_members[h]) rr.push(Json::of(names[i]));
+                hj.set("rescued_read_names", std::move(rr));
+                hj.set("frequency_with_rescued", Json::of(with_rescued_total ? (double)with / (double)with_rescued_total : 0.0));
+            }
             hs.push(std::move(hj));
         }
         hb.set("haplotypes", std::move(hs));
         Json pc = Json::array();
         for (uint32_t p = 0; p < ps.n_positions; ++p) pc.push(Json::of(win_begin + pos_cols[p] + 1));
         hb.set("variant_positions_abs", std::move(pc));
+        if (R.rescued)
+            hb.set("rescue", Json::object()
+                                 .set("min_positions", Json::of(R.rescue_min))
+                                 .set("assigned_reads", Json::of((uint32_t)rescue_cat[0]))
+                                 .set("ambiguous_reads", Json::of((uint32_t)rescue_cat[1]))
+                                 .set("incompatible_reads", Json::of((uint32_t)rescue_cat[2]))
+                                 .set("uninformative_reads", Json::of((uint32_t)rescue_cat[3])));
         root.set("haplotype", std::move(hb));
     }
     return root;
@@ -1267,8 +1344,17 @@ int write_haplotype_fasta(const Options &opt, jl_ctx *ctx, const Results &R, uin
 {
     const uint32_t H = R.ps.n_haplotypes;
     std::vector<uint32_t> counts((size_t)H * n_cols * 6);
+    std::vector<uint32_t> rescued(H, 0u);
     if (H) {
-        if (jl_class_pileup_async(ctx, R.read_hap.data(), H) != JL_OK) die_jl(ctx, "class pileup");
+        std::vector<uint16_t> with_rescued;   // --rescue-damaged: the damaged reads count for the haplotype they were assigned to
+        if (R.rescued) {
+            with_rescued.resize(R.read_hap.size());
+            for (size_t i = 0; i < with_rescued.size(); ++i) {
+                with_rescued[i] = R.hap_with_rescued(i);
+                if (with_rescued[i] != R.read_hap[i]) rescued[with_rescued[i]]++;
+            }
+        }
+        if (jl_class_pileup_async(ctx, R.rescued ? with_rescued.data() : R.read_hap.data(), H) != JL_OK) die_jl(ctx, "class pileup");
         if (jl_class_pileup_fetch(ctx, counts.data(), nullptr) != JL_OK) die_jl(ctx, "class pileup fetch");
     }
     std::ofstream f(opt.hap_fasta);
@@ -1280,7 +1366,8 @@ int write_haplotype_fasta(const Options &opt, jl_ctx *ctx, const Results &R, uin
         Json::of(R.ps.reported_reads ? (double)R.hap_count[h] / (double)R.ps.reported_reads : 0.0).write(freq);
         for (uint32_t c = 0; c < n_cols; ++c)
             if (cons[c] != 4) seq += "ACGT?N"[cons[c]];   // (4: a major deletion, the column is removed)
-        f << ">" << haplotype_name(h) << " reads=" << R.hap_count[h] << " frequency=" << freq << " window=" << (win_begin + 1) << "-"
+        f << ">" << haplotype_name(h) << " reads=" << R.hap_count[h] << (R.rescued ? " rescued=" + std::to_string(rescued[h]) : std::string())
+          << " frequency=" << freq << " window=" << (win_begin + 1) << "-"
           << (win_begin + n_cols) << " source=" << opt.bam << "\n";
         for (size_t i = 0; i < seq.size(); i += 70) f << seq.substr(i, 70) << "\n";
     }
@@ -1908,6 +1995,10 @@ int main(int argc, char **argv)
         if (opt.phasing)
             if (const char *what = fetch_phase(ctx, n_reads, R)) die_jl(ctx, what);
         tick("  haplotypes + ids");
+        if (opt.rescue) {
+            if (const char *what = fetch_rescue(ctx, opt.rescue_min, R)) die_jl(ctx, what);
+            tick("rescue");
+        }
         if (!opt.hap_fasta.empty()) {
             if (const int code = write_haplotype_fasta(opt, ctx, R, win_begin, n_cols)) return code;
             tick("haplotype fasta");
