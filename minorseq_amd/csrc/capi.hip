@@ -30,13 +30,17 @@ int jl_fail(jl_ctx *ctx, int status, const char *fmt, ...)
     return status;
 }
 
-template <typename T>
-static int regrow(jl_ctx *ctx, T **p, size_t n)
+// The one place that reserves an array a run or a stage touches, and the one place that says so to the captured graphs: room for
+// exactly `n` elements (grow-only; `anew`: made anew whatever it holds, for a group of arrays that is re-made together), the old
+// array freed first (jl_owned_array::reserve_exact).  A pointer that moved is stale in every graph that captured it.
+template <class A>
+static int jl_ctx_reserve(jl_ctx *ctx, A &a, size_t n, bool anew = false)
 {
-    if (*p) hipFree(*p);
-    *p = nullptr;
-    ctx->alloc_version++;  // pointers captured in a graph are stale now
-    JL_HIP(ctx, hipMalloc(p, n * sizeof(T)));
+    if (anew) a.release();
+    bool moved;
+    const hipError_t e = a.reserve_exact(n, &moved);
+    if (moved) ctx->alloc_version++;
+    if (e != hipSuccess) return jl_fail(ctx, jl_hip_status(e), "context memory, %zu bytes: %s", n * sizeof(*a.d), hipGetErrorString(e));
     return JL_OK;
 }
 
@@ -100,20 +104,19 @@ int jl_ctx_create(int device, void *stream, jl_ctx **out)
     hipEventCreate(&ctx->ev0);
     hipEventCreate(&ctx->ev1);
 
-    bool ok = hipMalloc(&ctx->d_variants, sizeof(jl_variant) * JL_VARIANT_CAP) == hipSuccess &&
-              hipMalloc(&ctx->d_nvar, 2 * sizeof(uint32_t)) == hipSuccess &&
-              hipMalloc(&ctx->d_meta, sizeof(jl_phase_meta)) == hipSuccess &&
-              hipMalloc(&ctx->d_vpcols, sizeof(uint32_t) * JL_VARIANT_CAP) == hipSuccess &&
-              hipMalloc(&ctx->d_hap_count, sizeof(uint32_t) * JL_MAX_HAPLOTYPES) == hipSuccess &&
-              hipMalloc(&ctx->d_hap_pattern, (size_t)JL_MAX_HAPLOTYPES * JL_VARIANT_CAP) == hipSuccess &&
-              hipMalloc(&ctx->d_hit, (size_t)JL_VARIANT_CAP * JL_MAX_HAPLOTYPES) == hipSuccess &&
-              hipMalloc(&ctx->d_cooc, sizeof(uint32_t) * ctx->cooc_cap * ctx->cooc_cap) == hipSuccess &&
-              hipMalloc(&ctx->d_pack, 2 * sizeof(jl_pack)) == hipSuccess &&
-              hipMalloc(&ctx->d_sync, 16 * sizeof(uint32_t)) == hipSuccess;
-    ok = ok && hipHostMalloc(&ctx->h_pack, sizeof(jl_pack), hipHostMallocDefault) == hipSuccess &&
-              hipHostMalloc((void **)&ctx->h_seq, 64, hipHostMallocDefault) == hipSuccess &&
-              hipHostMalloc(&ctx->h_scratch, (size_t)1 << 20, hipHostMallocDefault) == hipSuccess;
-    if (ok) ctx->h_scratch_cap = (size_t)1 << 20;
+    const bool ok = jl_ctx_reserve(ctx, ctx->d_variants, JL_VARIANT_CAP) == JL_OK &&
+                    jl_ctx_reserve(ctx, ctx->d_nvar, 2) == JL_OK &&
+                    jl_ctx_reserve(ctx, ctx->d_meta, 1) == JL_OK &&
+                    jl_ctx_reserve(ctx, ctx->d_vpcols, JL_VARIANT_CAP) == JL_OK &&
+                    jl_ctx_reserve(ctx, ctx->d_hap_count, JL_MAX_HAPLOTYPES) == JL_OK &&
+                    jl_ctx_reserve(ctx, ctx->d_hap_pattern, (size_t)JL_MAX_HAPLOTYPES * JL_VARIANT_CAP) == JL_OK &&
+                    jl_ctx_reserve(ctx, ctx->d_hit, (size_t)JL_VARIANT_CAP * JL_MAX_HAPLOTYPES) == JL_OK &&
+                    jl_ctx_reserve(ctx, ctx->d_cooc, (size_t)ctx->cooc_cap * ctx->cooc_cap) == JL_OK &&
+                    jl_ctx_reserve(ctx, ctx->d_pack, 2) == JL_OK &&
+                    jl_ctx_reserve(ctx, ctx->d_sync, 16) == JL_OK &&
+                    jl_ctx_reserve(ctx, ctx->h_pack, 1) == JL_OK &&
+                    jl_ctx_reserve(ctx, ctx->h_seq, 16) == JL_OK &&
+                    jl_ctx_reserve(ctx, ctx->h_scratch, (size_t)1 << 20) == JL_OK;
     if (!ok) { jl_ctx_destroy(ctx); return jl_fail(nullptr, JL_ERR_MEMORY, "context allocation failed"); }
     hipMemsetAsync(ctx->d_nvar, 0, 2 * sizeof(uint32_t), ctx->stream);
     hipMemsetAsync(ctx->d_meta, 0, sizeof(jl_phase_meta), ctx->stream);
@@ -142,30 +145,12 @@ void jl_ctx_destroy(jl_ctx *ctx)
     hipStreamSynchronize(ctx->stream);
     if (ctx->graph_exec) hipGraphExecDestroy(ctx->graph_exec);
     if (ctx->graph) hipGraphDestroy(ctx->graph);
-    if (ctx->h_pack) hipHostFree(ctx->h_pack);
-    if (ctx->h_seq) hipHostFree((void *)ctx->h_seq);
-    if (ctx->h_read_hap) hipHostFree(ctx->h_read_hap);
-    if (ctx->h_scratch) hipHostFree(ctx->h_scratch);
     free_msa(ctx);
-    jl_records_release(ctx);
-    jl_take_release(ctx);
-    jl_class_release(ctx);
-    jl_rescue_release(ctx);
-    void *ptrs[] = {ctx->d_pos_gene, ctx->d_pos_codon, ctx->d_pos_col, ctx->d_pos_refcfg, ctx->d_col_head, ctx->d_pos_next, ctx->d_guess, ctx->d_chunks,
-                    ctx->d_counts, ctx->d_called, ctx->d_staged, ctx->d_drm, ctx->d_variants, ctx->d_nvar, ctx->d_meta, ctx->d_vpcols,
-                    ctx->d_col2pos, ctx->d_varcol, ctx->d_keys, ctx->d_flagw, ctx->d_read_slot, ctx->d_read_hap,
-                    ctx->d_slot_rep, ctx->d_slot_count, ctx->d_slot_key, ctx->d_slot_hap, ctx->d_occupied, ctx->d_hap_count,
-                    ctx->d_hap_pattern, ctx->d_hit, ctx->d_cooc, ctx->d_pack, ctx->d_sync,
-                    ctx->d_ins_len, ctx->d_ins_base,
-                    ctx->d_exp_count,
-                    ctx->d_exp_pattern, ctx->d_exp_hap, ctx->d_blockcat, ctx->d_slot_key_a, ctx->d_slot_key_b, ctx->d_occ_a, ctx->d_occ_b};
-    for (void *p : ptrs)
-        if (p) hipFree(p);
     if (ctx->ev0) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) hipEventDestroy(ctx->ev1);
 
     if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;   // (every array of the context frees itself here, the device still current)
 }
 
 int jl_sync(jl_ctx *ctx)
@@ -359,16 +344,12 @@ int jl_synth_fill_window(jl_ctx *ctx, const jl_synth_params *sp, const uint8_t *
 static int reserve_columns(jl_ctx *ctx)
 {
     int rc;
-    if (ctx->col_capacity < ctx->n_cols) {
-        if ((rc = regrow(ctx, &ctx->d_guess, (size_t)ctx->n_cols + JL_GUESS_PAD))) return rc;
-        if ((rc = regrow(ctx, &ctx->d_col2pos, ctx->n_cols))) return rc;
-        if ((rc = regrow(ctx, &ctx->d_varcol, ctx->n_cols))) return rc;
-        if ((rc = regrow(ctx, &ctx->d_col_head, ctx->n_cols))) return rc;
-        ctx->counts_words = (size_t)ctx->n_cols * (6 + 64);
-        if ((rc = regrow(ctx, &ctx->d_counts, ctx->counts_words))) return rc;
-        ctx->col_capacity = ctx->n_cols;
-    }
     ctx->counts_words = (size_t)ctx->n_cols * (6 + 64);
+    if ((rc = jl_ctx_reserve(ctx, ctx->d_guess, (size_t)ctx->n_cols + JL_GUESS_PAD))) return rc;
+    if ((rc = jl_ctx_reserve(ctx, ctx->d_col2pos, ctx->n_cols))) return rc;
+    if ((rc = jl_ctx_reserve(ctx, ctx->d_varcol, ctx->n_cols))) return rc;
+    if ((rc = jl_ctx_reserve(ctx, ctx->d_col_head, ctx->n_cols))) return rc;
+    if ((rc = jl_ctx_reserve(ctx, ctx->d_counts, ctx->counts_words))) return rc;
     ctx->d_hist = ctx->d_counts + (size_t)ctx->n_cols * 6;
     return JL_OK;
 }
@@ -463,22 +444,16 @@ static int build_plan(jl_ctx *ctx, const jl_gene *genes, uint32_t n_genes, const
     int rc;
     if ((rc = reserve_columns(ctx))) return rc;
     const size_t P = ctx->P ? ctx->P : 1;
-    if (ctx->pos_capacity < P) {
-        if ((rc = regrow(ctx, &ctx->d_pos_gene, P))) return rc;
-        if ((rc = regrow(ctx, &ctx->d_pos_codon, P))) return rc;
-        if ((rc = regrow(ctx, &ctx->d_pos_col, P))) return rc;
-        if ((rc = regrow(ctx, &ctx->d_pos_refcfg, P))) return rc;
-        if ((rc = regrow(ctx, &ctx->d_pos_next, P))) return rc;
-        if ((rc = regrow(ctx, &ctx->d_called, P))) return rc;
-        if ((rc = regrow(ctx, &ctx->d_staged, P * 64))) return rc;
-        if ((rc = regrow(ctx, &ctx->d_drm, P))) return rc;
-        ctx->pos_capacity = P;
-    }
+    if ((rc = jl_ctx_reserve(ctx, ctx->d_pos_gene, P))) return rc;
+    if ((rc = jl_ctx_reserve(ctx, ctx->d_pos_codon, P))) return rc;
+    if ((rc = jl_ctx_reserve(ctx, ctx->d_pos_col, P))) return rc;
+    if ((rc = jl_ctx_reserve(ctx, ctx->d_pos_refcfg, P))) return rc;
+    if ((rc = jl_ctx_reserve(ctx, ctx->d_pos_next, P))) return rc;
+    if ((rc = jl_ctx_reserve(ctx, ctx->d_called, P))) return rc;
+    if ((rc = jl_ctx_reserve(ctx, ctx->d_staged, P * 64))) return rc;
+    if ((rc = jl_ctx_reserve(ctx, ctx->d_drm, P))) return rc;
     ctx->n_chunks = (uint32_t)chunk_c0.size();
-    if (ctx->chunk_capacity < chunk_c0.size()) {
-        if ((rc = regrow(ctx, &ctx->d_chunks, chunk_c0.size()))) return rc;
-        ctx->chunk_capacity = chunk_c0.size();
-    }
+    if ((rc = jl_ctx_reserve(ctx, ctx->d_chunks, chunk_c0.size()))) return rc;
     // chunk records: first column | own columns, codon-start flags of the own columns, "needs the two halo columns"
     std::vector<uint64_t> recs(chunk_c0.size());
     for (size_t k = 0; k < chunk_c0.size(); ++k) {
@@ -554,7 +529,7 @@ int jl_fetch_to_host(jl_ctx *ctx, const void *d_src, size_t bytes, void *dst, si
     const size_t moved = (bytes + 15u) & ~(size_t)15u;
     hipStream_t st = ctx->run_stream ? ctx->run_stream : ctx->stream;
     if (ctx->run_stream && ctx->run_stream != ctx->stream) JL_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (moved > ctx->h_scratch_cap || moved > readable || ((uintptr_t)d_src & 15u)) {   // large or odd: the runtime's copy
+    if (moved > ctx->h_scratch.cap || moved > readable || ((uintptr_t)d_src & 15u)) {   // large or odd: the runtime's copy
         JL_HIP(ctx, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, st));
         JL_HIP(ctx, hipStreamSynchronize(st));
         return JL_OK;
@@ -696,40 +671,36 @@ static int reserve_phase(jl_ctx *ctx, jl_phase_form form, uint32_t kwords_needed
     ctx->phase_form = form;
     const size_t reads_pad = (size_t)ctx->col_stride * 2;
     int rc;
-    if (ctx->reads_capacity < reads_pad) {
+    const bool regroup = ctx->reads_capacity < reads_pad;
+    if (regroup) {
         uint64_t slots = 1024;
         while (slots < 2 * (uint64_t)ctx->n_reads) slots <<= 1;
         ctx->table_slots = slots;
-        if ((rc = regrow(ctx, &ctx->d_flagw, reads_pad / 8))) return rc;
-        if ((rc = regrow(ctx, &ctx->d_blockcat, (reads_pad / 2048u + 2u) * 4u))) return rc;
-        if ((rc = regrow(ctx, &ctx->d_read_slot, reads_pad))) return rc;
-        if ((rc = regrow(ctx, &ctx->d_read_hap, reads_pad))) return rc;
-        if ((rc = regrow(ctx, &ctx->d_occupied, reads_pad))) return rc;
-        if ((rc = regrow(ctx, &ctx->d_slot_rep, (size_t)slots))) return rc;
-        if ((rc = regrow(ctx, &ctx->d_slot_count, (size_t)slots))) return rc;
-        if ((rc = regrow(ctx, &ctx->d_slot_key, (size_t)slots))) return rc;
-        if ((rc = regrow(ctx, &ctx->d_slot_hap, (size_t)slots))) return rc;
+        // (anew: the table's size follows the reads, not reads_pad, and may be the same or smaller)
+        if ((rc = jl_ctx_reserve(ctx, ctx->d_flagw, reads_pad / 8, true))) return rc;
+        if ((rc = jl_ctx_reserve(ctx, ctx->d_blockcat, (reads_pad / 2048u + 2u) * 4u, true))) return rc;
+        if ((rc = jl_ctx_reserve(ctx, ctx->d_read_slot, reads_pad, true))) return rc;
+        if ((rc = jl_ctx_reserve(ctx, ctx->d_read_hap, reads_pad, true))) return rc;
+        if ((rc = jl_ctx_reserve(ctx, ctx->d_occupied, reads_pad, true))) return rc;
+        if ((rc = jl_ctx_reserve(ctx, ctx->d_slot_rep, (size_t)slots, true))) return rc;
+        if ((rc = jl_ctx_reserve(ctx, ctx->d_slot_count, (size_t)slots, true))) return rc;
+        if ((rc = jl_ctx_reserve(ctx, ctx->d_slot_key, (size_t)slots, true))) return rc;
+        if ((rc = jl_ctx_reserve(ctx, ctx->d_slot_hap, (size_t)slots, true))) return rc;
         // the grouping table is initialised once; phase_select_kernel empties the slots a run touched
         JL_HIP(ctx, hipMemsetAsync(ctx->d_slot_rep, 0xFF, (size_t)slots * 4, ctx->stream));
         JL_HIP(ctx, hipMemsetAsync(ctx->d_slot_count, 0, (size_t)slots * 4, ctx->stream));
         JL_HIP(ctx, hipMemsetAsync(ctx->d_slot_key, 0xFF, (size_t)slots * 8, ctx->stream));
         JL_HIP(ctx, hipStreamSynchronize(ctx->stream));
         ctx->reads_capacity = reads_pad;
-        ctx->keys_capacity = 0;
     }
     if (form == jl_phase_form::two_word && ctx->two_slots != ctx->table_slots) {   // the two-word fused launch numbers its half keys here
-        void *old[] = {ctx->d_slot_key_a, ctx->d_slot_key_b, ctx->d_occ_a, ctx->d_occ_b};
-        for (void *p : old)
-            if (p) hipFree(p);
-        ctx->d_slot_key_a = ctx->d_slot_key_b = nullptr;
-        ctx->d_occ_a = ctx->d_occ_b = nullptr;
         ctx->two_slots = 0;
-        ctx->alloc_version++;
         const size_t slots = (size_t)ctx->table_slots;
-        JL_HIP(ctx, hipMalloc(&ctx->d_slot_key_a, slots * 8));
-        JL_HIP(ctx, hipMalloc(&ctx->d_slot_key_b, slots * 8));
-        JL_HIP(ctx, hipMalloc(&ctx->d_occ_a, reads_pad * 4));
-        JL_HIP(ctx, hipMalloc(&ctx->d_occ_b, reads_pad * 4));
+        ctx->d_slot_key_a.release(), ctx->d_slot_key_b.release(), ctx->d_occ_a.release(), ctx->d_occ_b.release();   // all four go before one comes
+        if ((rc = jl_ctx_reserve(ctx, ctx->d_slot_key_a, slots))) return rc;
+        if ((rc = jl_ctx_reserve(ctx, ctx->d_slot_key_b, slots))) return rc;
+        if ((rc = jl_ctx_reserve(ctx, ctx->d_occ_a, reads_pad))) return rc;
+        if ((rc = jl_ctx_reserve(ctx, ctx->d_occ_b, reads_pad))) return rc;
         JL_HIP(ctx, hipMemsetAsync(ctx->d_slot_key_a, 0xFF, slots * 8, ctx->stream));
         JL_HIP(ctx, hipMemsetAsync(ctx->d_slot_key_b, 0xFF, slots * 8, ctx->stream));
         JL_HIP(ctx, hipMemsetAsync(ctx->d_sync + 10, 0, 8, ctx->stream));
@@ -737,11 +708,8 @@ static int reserve_phase(jl_ctx *ctx, jl_phase_form form, uint32_t kwords_needed
         ctx->two_slots = ctx->table_slots;
     }
     const size_t need = (size_t)kwords_needed * reads_pad;
-    if (ctx->keys_capacity < need) {
-        if ((rc = regrow(ctx, &ctx->d_keys, need))) return rc;
-        ctx->keys_capacity = need;
-    }
-    ctx->keys_words = (uint32_t)(ctx->keys_capacity / reads_pad);
+    if ((rc = jl_ctx_reserve(ctx, ctx->d_keys, need, regroup))) return rc;   // (anew with the reads' group: words of the new reads_pad)
+    ctx->keys_words = (uint32_t)(ctx->d_keys.cap / reads_pad);
     return JL_OK;
 }
 
@@ -754,14 +722,12 @@ static int reserve_export(jl_ctx *ctx, uint32_t kwords)
     const uint64_t budget = ((uint64_t)256 << 20) / stride;
     if (cap > budget) cap = budget;
     if (ctx->exp_cap >= cap && ctx->exp_stride >= stride) return JL_OK;
-    void *old[] = {ctx->d_exp_count, ctx->d_exp_pattern, ctx->d_exp_hap};
-    for (void *p : old)
-        if (p) hipFree(p);
-    ctx->d_exp_count = nullptr; ctx->d_exp_pattern = nullptr; ctx->d_exp_hap = nullptr;
     ctx->exp_cap = ctx->exp_stride = 0;
-    JL_HIP(ctx, hipMalloc(&ctx->d_exp_count, (size_t)cap * 4));
-    JL_HIP(ctx, hipMalloc(&ctx->d_exp_pattern, (size_t)cap * stride));
-    JL_HIP(ctx, hipMalloc(&ctx->d_exp_hap, (size_t)cap * 2));
+    ctx->d_exp_count.release(), ctx->d_exp_pattern.release(), ctx->d_exp_hap.release();   // all three go before one comes
+    int rc;
+    if ((rc = jl_ctx_reserve(ctx, ctx->d_exp_count, (size_t)cap))) return rc;
+    if ((rc = jl_ctx_reserve(ctx, ctx->d_exp_pattern, (size_t)cap * stride))) return rc;
+    if ((rc = jl_ctx_reserve(ctx, ctx->d_exp_hap, (size_t)cap))) return rc;
     ctx->exp_cap = (uint32_t)cap;
     ctx->exp_stride = stride;
     return JL_OK;
@@ -1154,13 +1120,7 @@ int jl_run_prepare(jl_ctx *ctx, const jl_gene *genes, uint32_t n_genes, const ui
     }
     if (phasing) {
         if ((rc = reserve_phase(ctx, ctx->phase_form, ctx->keys_words > 4 ? ctx->keys_words : 4))) return rc;
-        if (want_read_hap && ctx->h_read_hap_cap < (size_t)ctx->col_stride * 2) {
-            if (ctx->h_read_hap) hipHostFree(ctx->h_read_hap);
-            ctx->h_read_hap = nullptr;
-            ctx->alloc_version++;
-            JL_HIP(ctx, hipHostMalloc(&ctx->h_read_hap, (size_t)ctx->col_stride * 4, hipHostMallocDefault));
-            ctx->h_read_hap_cap = (size_t)ctx->col_stride * 2;
-        }
+        if (want_read_hap && (rc = jl_ctx_reserve(ctx, ctx->h_read_hap, (size_t)ctx->col_stride * 2))) return rc;
     }
     *n_tests_out = prm->n_tests > 0.0 ? prm->n_tests : ctx->default_n_tests;
     ctx->last_min_reads = min_reads;
@@ -1421,7 +1381,7 @@ int jl_run_pileup_ms(jl_ctx *ctx, float *ms, uint64_t *begin_ticks)
     if (ctx->clock_run == 0u || ctx->clock_run != ctx->runs_launched)
         return jl_fail(ctx, JL_ERR_STATE, "jl_run_pileup_ms: the context's last run carried no clock nodes (only jl_run_async runs with the clock on do; group runs do not)");
     if (int rc = jl_run_wait_impl(ctx)) return rc;
-    const volatile unsigned long long *t = reinterpret_cast<const volatile unsigned long long *>(const_cast<uint32_t *>(ctx->h_seq) + 8);
+    const volatile unsigned long long *t = ctx->h_seq.as<const volatile unsigned long long>() + 4;
     *ms = (float)((double)(t[1] - t[0]) * 1e-5);      // 100 MHz ticks
     if (begin_ticks) *begin_ticks = t[0];
     return JL_OK;

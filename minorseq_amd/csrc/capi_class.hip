@@ -6,17 +6,6 @@
 
 #include "jl_internal.h"
 
-void jl_class_release(jl_ctx *ctx)
-{
-    ctx->class_label.release(), ctx->class_mask.release(), ctx->class_out.release();
-    if (ctx->h_class_label) hipHostFree(ctx->h_class_label);
-    ctx->h_class_label = nullptr;
-    ctx->h_class_cap = 0;
-    if (ctx->class_ev) hipEventDestroy(ctx->class_ev);
-    ctx->class_ev = nullptr;
-    ctx->class_k = ctx->class_cols = 0;
-}
-
 extern "C" {
 
 int jl_class_pileup_async(jl_ctx *ctx, const uint16_t *label, uint32_t n_classes)
@@ -31,32 +20,23 @@ int jl_class_pileup_async(jl_ctx *ctx, const uint16_t *label, uint32_t n_classes
     hipStream_t st = ctx->stream;
     const uint64_t n = ctx->n_reads;
     // the labels into pinned staging (an upload of the last call may still read it: wait for that)
-    if (!ctx->class_ev) JL_HIP(ctx, hipEventCreateWithFlags(&ctx->class_ev, hipEventDisableTiming));
-    JL_HIP(ctx, hipEventSynchronize(ctx->class_ev));
-    if (ctx->h_class_cap < n) {
-        if (ctx->h_class_label) hipHostFree(ctx->h_class_label);
-        ctx->h_class_label = nullptr, ctx->h_class_cap = 0;
-        const size_t want = (size_t)(n + n / 8 + 1024);
-        JL_HIP(ctx, hipHostMalloc(&ctx->h_class_label, want * sizeof(uint16_t), hipHostMallocDefault));
-        ctx->h_class_cap = want;
-    }
-    memcpy(ctx->h_class_label, label, (size_t)n * sizeof(uint16_t));
+    uint16_t *h_label = nullptr;
+    JL_HIP(ctx, ctx->class_label.host((size_t)n, &h_label));
+    memcpy(h_label, label, (size_t)n * sizeof(uint16_t));
     const uint64_t mask_stride = jl_plane_stride(n);
     const size_t count_words = (size_t)n_classes * ctx->n_cols * 6u;
     ctx->class_k = 0;   // (what was fetchable is gone as soon as a buffer may move)
-    hipError_t e = ctx->class_label.grow_discard(st, (size_t)n);
-    if (e == hipSuccess) e = ctx->class_mask.grow_discard(st, (size_t)(n_classes * mask_stride));
+    hipError_t e = ctx->class_mask.grow_discard(st, (size_t)(n_classes * mask_stride));
     if (e == hipSuccess) e = ctx->class_out.grow_discard(st, count_words + n_classes);
-    if (e == hipSuccess) e = hipMemcpyAsync(ctx->class_label.d, ctx->h_class_label, (size_t)n * sizeof(uint16_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipEventRecord(ctx->class_ev, st);
-    if (e == hipSuccess) e = hipMemsetAsync(ctx->class_out.d, 0, (count_words + n_classes) * sizeof(uint32_t), st);
+    if (e == hipSuccess) e = ctx->class_label.upload(st, (size_t)n);
+    if (e == hipSuccess) e = hipMemsetAsync(ctx->class_out, 0, (count_words + n_classes) * sizeof(uint32_t), st);
     if (e == hipSuccess) {
         jl_class_args A = {};
         A.msa = ctx->d_msa, A.plane_stride = ctx->plane_stride;
         A.n_reads = n, A.n_cols = ctx->n_cols, A.n_classes = n_classes;
-        A.label = ctx->class_label.d;
-        A.mask = ctx->class_mask.d, A.mask_stride = mask_stride;
-        A.counts = ctx->class_out.d, A.class_reads = ctx->class_out.d + count_words;
+        A.label = ctx->class_label.dev;
+        A.mask = ctx->class_mask, A.mask_stride = mask_stride;
+        A.counts = ctx->class_out, A.class_reads = ctx->class_out + count_words;
         jl_launch_class_pileup(&A, st);
         e = hipGetLastError();
     }
@@ -71,9 +51,9 @@ int jl_class_pileup_fetch(jl_ctx *ctx, uint32_t *counts, uint32_t *class_reads)
     if (!ctx->class_k) return jl_fail(ctx, JL_ERR_STATE, "jl_class_pileup_fetch before jl_class_pileup_async");
     JL_HIP(ctx, hipSetDevice(ctx->device));
     const size_t count_words = (size_t)ctx->class_k * ctx->class_cols * 6u;
-    if (counts) JL_HIP(ctx, hipMemcpyAsync(counts, ctx->class_out.d, count_words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (counts) JL_HIP(ctx, hipMemcpyAsync(counts, ctx->class_out, count_words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (class_reads)
-        JL_HIP(ctx, hipMemcpyAsync(class_reads, ctx->class_out.d + count_words, (size_t)ctx->class_k * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        JL_HIP(ctx, hipMemcpyAsync(class_reads, ctx->class_out + count_words, (size_t)ctx->class_k * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     JL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return JL_OK;
 }

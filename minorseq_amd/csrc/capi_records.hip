@@ -10,17 +10,7 @@
 
 #include "jl_internal.h"
 
-static void records_drop(jl_ctx *ctx)
-{
-    ctx->rec.release();
-    ctx->rec = jl_records();
-}
-
-void jl_records_release(jl_ctx *ctx)
-{
-    ctx->rec.release();
-    ctx->ing.release();
-}
+static void records_drop(jl_ctx *ctx) { ctx->rec.release(); }
 
 // a HIP call of the upload ("records") or of a build ("ingest") failed
 static int hip_fail(jl_ctx *ctx, const char *what, hipError_t e) { return jl_fail(ctx, jl_hip_status(e), "%s: %s", what, hipGetErrorString(e)); }
@@ -140,7 +130,7 @@ static int records_append(jl_ctx *ctx, uint64_t n_reads, const int32_t *pos, con
     // (the mask's share of those 64 bytes: a piece's dword of flags lies inside the allocation wherever the piece does)
     // (its first allocation follows the bases' — the hint of jl_records_begin — so that it grows when they do, not chunk after chunk)
     if (e == hipSuccess && masked)
-        e = R.mask.grow_keep(st, (size_t)jl_qmask_bytes(R.n_seq), std::max((size_t)(seq_at / 4u) + n_mask, R.mask.d ? (size_t)0 : R.seq.cap / 4u), 16);
+        e = R.mask.grow_keep(st, (size_t)jl_qmask_bytes(R.n_seq), std::max((size_t)(seq_at / 4u) + n_mask, R.mask ? (size_t)0 : R.seq.cap / 4u), 16);
     if (e == hipSuccess && qual) e = R.qual.grow_keep(st, (size_t)R.n_qual, (size_t)R.n_qual + n_q, 64);
     if (e == hipSuccess && qual) e = R.qo.grow_keep(st, nr + 1, nr + n_reads + 1, 0);
     std::vector<uint64_t> off((size_t)(n_reads + 1) * (qual ? 3 : 2));
@@ -151,14 +141,14 @@ static int records_append(jl_ctx *ctx, uint64_t n_reads, const int32_t *pos, con
         if (qual) qo[r] = qual_off[r] - q0 + R.n_qual;
     }
     const size_t off_bytes = (size_t)(n_reads + 1) * 8;
-    if (e == hipSuccess && n_seq) e = hipMemcpyAsync(R.seq.d + seq_at, seq4 + s0, n_seq, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && n_mask) e = hipMemcpyAsync(R.mask.d + seq_at / 4u, qmask, n_mask, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && n_cig) e = hipMemcpyAsync(R.cig.d + R.n_cig, cigar + c0, n_cig * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(R.co.d + nr, co, off_bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(R.so.d + nr, so, off_bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(R.pos.d + nr, pos, (size_t)n_reads * 4, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && qual && n_q) e = hipMemcpyAsync(R.qual.d + R.n_qual, qual + q0, n_q, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && qual) e = hipMemcpyAsync(R.qo.d + nr, qo, off_bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && n_seq) e = hipMemcpyAsync(R.seq + seq_at, seq4 + s0, n_seq, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && n_mask) e = hipMemcpyAsync(R.mask + seq_at / 4u, qmask, n_mask, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && n_cig) e = hipMemcpyAsync(R.cig + R.n_cig, cigar + c0, n_cig * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(R.co + nr, co, off_bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(R.so + nr, so, off_bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(R.pos + nr, pos, (size_t)n_reads * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && qual && n_q) e = hipMemcpyAsync(R.qual + R.n_qual, qual + q0, n_q, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && qual) e = hipMemcpyAsync(R.qo + nr, qo, off_bytes, hipMemcpyHostToDevice, st);
     // the caller may reuse its chunk buffers (and `off` goes away) as soon as this returns
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
@@ -214,16 +204,9 @@ int jl_ingest_verdict(jl_ctx *ctx)
 // the insertion counters of `dst` for n_cols columns, zeroed on its stream
 static hipError_t reserve_insertions(jl_ctx *dst, uint32_t n_cols)
 {
-    hipError_t e = hipSuccess;
-    if (dst->ins_capacity < n_cols) {
-        if (dst->d_ins_len) hipFree(dst->d_ins_len);
-        if (dst->d_ins_base) hipFree(dst->d_ins_base);
-        dst->d_ins_len = dst->d_ins_base = nullptr;
-        dst->ins_capacity = 0;
-        e = hipMalloc(&dst->d_ins_len, (size_t)n_cols * JL_INS_LEN_BINS * 4);
-        if (e == hipSuccess) e = hipMalloc(&dst->d_ins_base, (size_t)n_cols * JL_INS_MAX_BASES * 16);
-        if (e == hipSuccess) dst->ins_capacity = n_cols;
-    }
+    bool moved;   // (no run and no stage touches the counters: no captured graph to tell)
+    hipError_t e = dst->d_ins_len.reserve_exact((size_t)n_cols * JL_INS_LEN_BINS, &moved);
+    if (e == hipSuccess) e = dst->d_ins_base.reserve_exact((size_t)n_cols * JL_INS_MAX_BASES * 4, &moved);
     if (e == hipSuccess) e = hipMemsetAsync(dst->d_ins_len, 0, (size_t)n_cols * JL_INS_LEN_BINS * 4, dst->stream);
     if (e == hipSuccess) e = hipMemsetAsync(dst->d_ins_base, 0, (size_t)n_cols * JL_INS_MAX_BASES * 16, dst->stream);
     return e;
@@ -247,7 +230,8 @@ static int records_build(jl_ctx *src, jl_ctx *dst, uint32_t n_cols, uint32_t win
     if (e == hipSuccess) e = S.desc.grow_discard(st, (nr + 1) * ns);
     if (e == hipSuccess) e = S.slow.grow_discard(st, jl_ingest_slow_room(dst));
     if (e == hipSuccess && !S.d_count) {
-        e = hipMalloc(&S.d_count, 64);
+        bool moved;
+        e = S.d_count.reserve_exact(16, &moved);
         // (counters zero, the verdict word — [2..3] — all ones: no malformed record seen; kernels_ingest.hip jl_launch_ingest)
         if (e == hipSuccess) e = hipMemsetAsync(S.d_count, 0, 64, st);
         if (e == hipSuccess) e = hipMemsetAsync(S.d_count + 2, 0xFF, 8, st);

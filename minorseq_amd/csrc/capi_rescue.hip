@@ -11,17 +11,6 @@ constexpr size_t kTallyWords = 8;                                  // tally [4],
 constexpr size_t kHeadWords = kTallyWords + JL_RESCUE_HAP_PAD;     // ... then hap_reads; the ids follow
 }
 
-void jl_rescue_release(jl_ctx *ctx)
-{
-    ctx->rescue_in.release(), ctx->rescue_out.release();
-    if (ctx->h_rescue_in) hipHostFree(ctx->h_rescue_in);
-    ctx->h_rescue_in = nullptr;
-    ctx->h_rescue_cap = 0;
-    if (ctx->rescue_ev) hipEventDestroy(ctx->rescue_ev);
-    ctx->rescue_ev = nullptr;
-    ctx->rescue_n = 0, ctx->rescue_h = 0;
-}
-
 extern "C" {
 
 int jl_phase_rescue_async(jl_ctx *ctx, const uint32_t *pos_cols, uint32_t n_pos, const uint8_t *pattern, uint32_t pattern_stride,
@@ -54,37 +43,28 @@ int jl_phase_rescue_async(jl_ctx *ctx, const uint32_t *pos_cols, uint32_t n_pos,
     const uint32_t hap_pad = (n_hap + 63u) / 64u * 64u, groups = (n_pos + 3u) / 4u;
     const size_t in_words = (size_t)n_pos + (size_t)groups * hap_pad;
     // positions and packed pattern into pinned staging (an upload of the last call may still read it: wait for that)
-    if (!ctx->rescue_ev) JL_HIP(ctx, hipEventCreateWithFlags(&ctx->rescue_ev, hipEventDisableTiming));
-    JL_HIP(ctx, hipEventSynchronize(ctx->rescue_ev));
-    if (ctx->h_rescue_cap < in_words) {
-        if (ctx->h_rescue_in) hipHostFree(ctx->h_rescue_in);
-        ctx->h_rescue_in = nullptr, ctx->h_rescue_cap = 0;
-        const size_t want = in_words + in_words / 8 + 1024;
-        JL_HIP(ctx, hipHostMalloc((void **)&ctx->h_rescue_in, want * sizeof(uint32_t), hipHostMallocDefault));
-        ctx->h_rescue_cap = want;
-    }
-    memcpy(ctx->h_rescue_in, pos_cols, (size_t)n_pos * sizeof(uint32_t));
-    uint32_t *pat4 = ctx->h_rescue_in + n_pos;
+    uint32_t *h_in = nullptr;
+    JL_HIP(ctx, ctx->rescue_in.host(in_words, &h_in));
+    memcpy(h_in, pos_cols, (size_t)n_pos * sizeof(uint32_t));
+    uint32_t *pat4 = h_in + n_pos;
     memset(pat4, 0, (size_t)groups * hap_pad * sizeof(uint32_t));
     for (uint32_t h = 0; h < n_hap; ++h)
         for (uint32_t p = 0; p < n_pos; ++p)
             pat4[(size_t)(p / 4u) * hap_pad + h] |= (uint32_t)pattern[(size_t)h * pattern_stride + p] << (8u * (p % 4u));
     const size_t out_words = kHeadWords + (size_t)((n + 1u) / 2u);
     ctx->rescue_n = 0;   // (what was fetchable is gone as soon as a buffer may move)
-    hipError_t e = ctx->rescue_in.grow_discard(st, in_words);
-    if (e == hipSuccess) e = ctx->rescue_out.grow_discard(st, out_words);
-    if (e == hipSuccess) e = hipMemcpyAsync(ctx->rescue_in.d, ctx->h_rescue_in, in_words * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipEventRecord(ctx->rescue_ev, st);
-    if (e == hipSuccess) e = hipMemsetAsync(ctx->rescue_out.d, 0, kHeadWords * sizeof(uint32_t), st);
+    hipError_t e = ctx->rescue_out.grow_discard(st, out_words);
+    if (e == hipSuccess) e = ctx->rescue_in.upload(st, in_words);
+    if (e == hipSuccess) e = hipMemsetAsync(ctx->rescue_out, 0, kHeadWords * sizeof(uint32_t), st);
     if (e == hipSuccess) {
         jl_rescue_args A = {};
         A.msa = ctx->d_msa, A.plane_stride = ctx->plane_stride;
         A.n_reads = n, A.n_runs = (uint32_t)((n + 63u) / 64u);   // (8 n_runs <= plane_stride: a multiple of 16 and >= ceil(n / 8))
         A.n_pos = n_pos, A.n_hap = n_hap, A.min_positions = min_positions, A.hap_pad = hap_pad;
-        A.pos_cols = ctx->rescue_in.d, A.pat4 = ctx->rescue_in.d + n_pos;
-        A.tally = (unsigned long long *)ctx->rescue_out.d;
-        A.hap_reads = ctx->rescue_out.d + kTallyWords;
-        A.rescue = (uint16_t *)(ctx->rescue_out.d + kHeadWords);
+        A.pos_cols = ctx->rescue_in.dev, A.pat4 = ctx->rescue_in.dev + n_pos;
+        A.tally = ctx->rescue_out.as<unsigned long long>();
+        A.hap_reads = ctx->rescue_out + kTallyWords;
+        A.rescue = (uint16_t *)(ctx->rescue_out + kHeadWords);
         jl_launch_phase_rescue(&A, st);
         e = hipGetLastError();
     }
@@ -98,7 +78,7 @@ int jl_phase_rescue_fetch(jl_ctx *ctx, uint16_t *rescue, uint32_t *hap_reads, ui
     if (!ctx) return JL_ERR_ARG;
     if (!ctx->rescue_n) return jl_fail(ctx, JL_ERR_STATE, "jl_phase_rescue_fetch before jl_phase_rescue_async");
     JL_HIP(ctx, hipSetDevice(ctx->device));
-    const uint32_t *out = ctx->rescue_out.d;
+    const uint32_t *out = ctx->rescue_out;
     if (tally) JL_HIP(ctx, hipMemcpyAsync(tally, out, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     if (hap_reads) JL_HIP(ctx, hipMemcpyAsync(hap_reads, out + kTallyWords, (size_t)ctx->rescue_h * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     if (rescue) JL_HIP(ctx, hipMemcpyAsync(rescue, out + kHeadWords, (size_t)ctx->rescue_n * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));

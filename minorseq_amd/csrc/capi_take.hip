@@ -9,16 +9,6 @@
 
 #include "jl_internal.h"
 
-void jl_take_release(jl_ctx *ctx)
-{
-    ctx->take_idx.release();
-    if (ctx->h_take_idx) hipHostFree(ctx->h_take_idx);
-    ctx->h_take_idx = nullptr;
-    ctx->h_take_cap = 0;
-    if (ctx->take_ev) hipEventDestroy(ctx->take_ev);
-    ctx->take_ev = nullptr;
-}
-
 // jl_msa_take (`wait`) and jl_msa_take_async, `fn` the one that was called
 static int msa_take(const char *fn, jl_ctx *dst, const jl_take_part *parts, uint32_t n_parts, bool wait)
 {
@@ -43,21 +33,14 @@ static int msa_take(const char *fn, jl_ctx *dst, const jl_take_part *parts, uint
     JL_HIP(dst, hipSetDevice(dst->device));
     hipStream_t st = dst->stream;
     // the indices into pinned staging, checked on the way (an upload of the last take may still read the staging: wait for it)
-    if (!dst->take_ev) JL_HIP(dst, hipEventCreateWithFlags(&dst->take_ev, hipEventDisableTiming));
-    JL_HIP(dst, hipEventSynchronize(dst->take_ev));
-    if (dst->h_take_cap < total) {
-        if (dst->h_take_idx) hipHostFree(dst->h_take_idx);
-        dst->h_take_idx = nullptr, dst->h_take_cap = 0;
-        const size_t want = (size_t)(total + total / 8 + 1024);
-        JL_HIP(dst, hipHostMalloc(&dst->h_take_idx, want * sizeof(uint32_t), hipHostMallocDefault));
-        dst->h_take_cap = want;
-    }
+    uint32_t *h_idx = nullptr;
+    JL_HIP(dst, dst->take_idx.host((size_t)total, &h_idx));
     jl_take_args A = {};
     uint64_t at = 0;
     for (uint32_t p = 0; p < n_parts; ++p) {
         const jl_ctx *s = parts[p].src;
         const uint32_t *idx = parts[p].idx;
-        uint32_t *out = dst->h_take_idx + at;
+        uint32_t *out = h_idx + at;
         const uint64_t n = parts[p].n, lim = s->n_reads;
         uint32_t worst = 0;
         for (uint64_t i = 0; i < n; ++i) {
@@ -81,13 +64,11 @@ static int msa_take(const char *fn, jl_ctx *dst, const jl_take_part *parts, uint
             if (parts[p].src->stream != st) JL_HIP(dst, hipStreamSynchronize(parts[p].src->stream));
     const uint32_t n_cols = parts[0].src->n_cols;
     if (int rc = jl_msa_alloc(dst, total, n_cols, parts[0].src->win_begin)) return rc;
-    hipError_t e = dst->take_idx.grow_discard(st, (size_t)total);
-    if (e == hipSuccess) e = hipMemcpyAsync(dst->take_idx.d, dst->h_take_idx, (size_t)total * sizeof(uint32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipEventRecord(dst->take_ev, st);
+    hipError_t e = dst->take_idx.upload(st, (size_t)total);
     if (e == hipSuccess) {
         A.n_parts = n_parts, A.n_cols = n_cols;
         A.n_total = total;
-        A.idx = dst->take_idx.d;
+        A.idx = dst->take_idx.dev;
         A.dst = dst->d_msa, A.dst_stride = dst->plane_stride;
         jl_launch_take(&A, st);
         e = hipGetLastError();

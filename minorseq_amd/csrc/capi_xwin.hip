@@ -918,9 +918,9 @@ int jl_xwin_read_hap_fetch(jl_xwin *x, uint16_t *read_hap)
     // first time a process makes one: 7 of the 30 ms `juliet --windows 8` spent behind the upload)
     std::vector<uint8_t> tmp(bytes);
     const size_t readable = (size_t)pc->col_stride * 2u * 2u;   // d_read_hap holds 16 bits for every read of the padded stride
-    for (size_t o = 0; o < bytes; o += pc->h_scratch_cap) {
-        const size_t n = std::min(bytes - o, pc->h_scratch_cap);
-        if (int rc = jl_fetch_to_host(pc, reinterpret_cast<const uint8_t *>(pc->d_read_hap) + o, n, tmp.data() + o, readable - o))
+    for (size_t o = 0; o < bytes; o += pc->h_scratch.cap) {
+        const size_t n = std::min(bytes - o, pc->h_scratch.cap);
+        if (int rc = jl_fetch_to_host(pc, pc->d_read_hap.as<const uint8_t>() + o, n, tmp.data() + o, readable - o))
             return xs_fail_ctx(x, rc, pc);
     }
     jl_expand_ids(tmp.data(), x->bits, x->n_mine, read_hap);

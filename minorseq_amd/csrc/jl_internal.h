@@ -359,11 +359,46 @@ void jl_launch_phase_rescue(const jl_rescue_args *a, hipStream_t st);
 
 inline int jl_hip_status(hipError_t e) { return e == hipErrorOutOfMemory ? JL_ERR_MEMORY : JL_ERR_DEVICE; }
 
-// A device array that grows: `cap` elements at `d`.  Making room returns HIP's error (jl_hip_status: the status it becomes).
-template <typename T>
-struct jl_dev_array {
+// ---- owning arrays.  Every buffer a context owns is one of these: it frees itself when the context is deleted (jl_ctx_destroy, the
+// device still current), so there is no list of pointers to keep.  None may have static or thread-local storage duration: its
+// destructor would call into a HIP runtime that is gone at process exit.
+// `cap` elements at `d`, device memory or (Pinned) pinned host memory.  The object stands where the pointer stood: it converts to T *.
+template <typename T, bool Pinned>
+struct jl_owned_array {
     T *d = nullptr;
     size_t cap = 0;
+    jl_owned_array() = default;
+    jl_owned_array(const jl_owned_array &) = delete;
+    jl_owned_array &operator=(const jl_owned_array &) = delete;
+    ~jl_owned_array() { release(); }
+    operator T *() const { return d; }
+    T *operator->() const { return d; }
+    template <typename U> U *as() const { return reinterpret_cast<U *>(d); }   // the same memory in another element type
+    // Room for exactly `n` elements, grow-only, contents not kept; *moved: `d` is another pointer now (or none: the error returned).
+    // The old array is freed BEFORE the new one is made: the peak stays low, and hipFree waits for the device, so nothing enqueued
+    // still reads what goes.
+    hipError_t reserve_exact(size_t n, bool *moved)
+    {
+        *moved = !(d && cap >= n);
+        if (!*moved) return hipSuccess;
+        release();
+        const hipError_t e = Pinned ? hipHostMalloc((void **)&d, n * sizeof(T), hipHostMallocDefault) : hipMalloc((void **)&d, n * sizeof(T));
+        if (e == hipSuccess) cap = n;
+        return e;
+    }
+    void release()
+    {
+        if (d) Pinned ? hipHostFree((void *)d) : hipFree((void *)d);
+        d = nullptr, cap = 0;
+    }
+};
+template <typename T> using jl_pinned_array = jl_owned_array<T, true>;
+
+// A device array that grows with slack.  Making room returns HIP's error (jl_hip_status: the status it becomes).
+template <typename T>
+struct jl_dev_array : jl_owned_array<T, false> {
+    using jl_owned_array<T, false>::d;
+    using jl_owned_array<T, false>::cap;
     // room for `need` elements (+ pad_bytes behind them); the first `used` move along, on `st`
     hipError_t grow_keep(hipStream_t st, size_t used, size_t need, size_t pad_bytes)
     {
@@ -386,17 +421,38 @@ struct jl_dev_array {
     {
         if (d && cap >= n) return hipSuccess;
         hipError_t e = d ? hipStreamSynchronize(st) : hipSuccess;   // what is enqueued on `st` may still read it
-        if (e != hipSuccess) return e;
-        release();
-        const size_t want = n + n / 8 + 64;
-        e = hipMalloc(&d, want * sizeof(T));
-        if (e == hipSuccess) cap = want;
+        bool moved;
+        return e != hipSuccess ? e : this->reserve_exact(n + n / 8 + 64, &moved);
+    }
+};
+
+// What a call uploads on every invocation: the host fills pinned staging, one copy takes it to the device array.
+template <typename T>
+struct jl_upload_staging {
+    jl_pinned_array<T> h;
+    jl_dev_array<T> dev;
+    hipEvent_t ev = nullptr;   // behind the last upload out of the staging: it may be refilled then
+    jl_upload_staging() = default;
+    jl_upload_staging(const jl_upload_staging &) = delete;
+    jl_upload_staging &operator=(const jl_upload_staging &) = delete;
+    ~jl_upload_staging() { if (ev) hipEventDestroy(ev); }
+    // *out = the staging with room for `n` elements, once the last upload has read it
+    hipError_t host(size_t n, T **out)
+    {
+        hipError_t e = ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventSynchronize(ev);
+        bool moved;
+        if (e == hipSuccess && h.cap < n) e = h.reserve_exact(n + n / 8 + 1024, &moved);
+        *out = h;
         return e;
     }
-    void release()
+    // its first `n` elements to `dev` (grown, the old contents not kept) on `st`
+    hipError_t upload(hipStream_t st, size_t n)
     {
-        if (d) hipFree(d);
-        d = nullptr, cap = 0;
+        hipError_t e = dev.grow_discard(st, n);
+        if (e == hipSuccess) e = hipMemcpyAsync(dev, h, n * sizeof(T), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipEventRecord(ev, st);
+        return e;
     }
 };
 
@@ -412,7 +468,13 @@ struct jl_records {
     // does any read need the ingest's launch for long reads (kernels_ingest.hip jl_ingest_read_is_long)?  Found out at the upload for
     // the few reads a CCS sample has with more ops than entries fit; `true` as soon as looking would cost more than the launch
     bool maybe_long = false;
-    void release() { seq.release(), qual.release(), mask.release(), cig.release(), co.release(), so.release(), qo.release(), pos.release(); }
+    // frees them and is a stream not begun again
+    void release()
+    {
+        seq.release(), qual.release(), mask.release(), cig.release(), co.release(), so.release(), qo.release(), pos.release();
+        open = have_qual = masked = maybe_long = false;
+        n_reads = n_cig = n_seq = n_qual = 0;
+    }
 };
 
 // How a build takes the QV filter: the planes kernel's template argument (kernels_ingest.hip kQvNone, kQvBytes, kQvMask).
@@ -432,14 +494,8 @@ struct jl_ingest_scratch {
     jl_dev_array<uint32_t> nruns;
     jl_dev_array<uint4> desc;       // one descriptor per (sweep, read): the run at every sweep's first column
     jl_dev_array<uint2> slow;       // the units handed on to the planes kernel's second size
-    uint32_t *d_count = nullptr;    // 64 bytes: the counters of a build and the verdict word (jl_launch_ingest)
+    jl_dev_array<uint32_t> d_count; // 64 bytes: the counters of a build and the verdict word (jl_launch_ingest)
     bool check_pending = false;     // an ingest ran (or is enqueued) whose verdict on the records has not been read yet
-    void release()
-    {
-        runs.release(), nruns.release(), desc.release(), slow.release();
-        if (d_count) hipFree(d_count);
-        d_count = nullptr;
-    }
 };
 
 enum class jl_phase_form : uint32_t {   // the pipeline that phases a context; the value is the plan's fast_only (phase_plan.h)
@@ -466,9 +522,9 @@ struct jl_ctx {
     // jl_plane_stride(n_reads) (reads padded to a multiple of 1024 with code 6: whole 128-byte lines per plane), or the
     // caller's for an adopted matrix.  `col_stride` = 4 * plane_stride is the same stride counted in "8 reads per dword"
     // units: the phasing kernels give a lane 8 reads (dword t of a column <=> byte t of each plane), reads_pad = 2 col_stride.
-    uint8_t *d_msa = nullptr;
+    uint8_t *d_msa = nullptr;         // raw: owned (own_msa) or the caller's (jl_msa_adopt)
     bool own_msa = false;
-    size_t msa_capacity = 0;
+    size_t msa_capacity = 0;          // bytes, of an owned one
     uint64_t plane_stride = 0;
     uint64_t n_reads = 0;
     uint32_t n_cols = 0;
@@ -478,44 +534,34 @@ struct jl_ctx {
     // ---- insertions per column (fuse-style consensus; off unless jl_msa_track_insertions)
     bool track_insertions = false;
     bool ins_valid = false;
-    uint32_t *d_ins_len = nullptr;    // [n_cols][JL_INS_LEN_BINS]
-    uint32_t *d_ins_base = nullptr;   // [n_cols][JL_INS_MAX_BASES][4]
-    size_t ins_capacity = 0;          // columns
+    jl_dev_array<uint32_t> d_ins_len;    // [n_cols][JL_INS_LEN_BINS]
+    jl_dev_array<uint32_t> d_ins_base;   // [n_cols][JL_INS_MAX_BASES][4]
 
     // ---- aligned records on their way in (jl_records_begin / _append / _finish)
     jl_records rec;
     jl_ingest_scratch ing;            // ... and of the builds into this context's matrix
 
     // ---- jl_msa_take INTO this context: the parts' indices on their way to the device (capi_take.hip)
-    jl_dev_array<uint32_t> take_idx;
-    uint32_t *h_take_idx = nullptr;   // pinned staging of the same
-    size_t h_take_cap = 0;            // ... in indices
-    hipEvent_t take_ev = nullptr;     // behind the last upload out of the staging: it may be refilled then
+    jl_upload_staging<uint32_t> take_idx;
 
     // ---- jl_class_pileup_async: buffers of its own, grown on demand (capi_class.hip); no stage and no run touches them
-    jl_dev_array<uint16_t> class_label;
+    jl_upload_staging<uint16_t> class_label;
     jl_dev_array<uint8_t> class_mask;
     jl_dev_array<uint32_t> class_out;   // counts [class_k][class_cols][6], then class_reads [class_k]
-    uint16_t *h_class_label = nullptr;  // pinned staging of the labels
-    size_t h_class_cap = 0;             // ... in labels
-    hipEvent_t class_ev = nullptr;      // behind the last upload out of the staging
     uint32_t class_k = 0, class_cols = 0;   // shape of the last class pileup enqueued (class_k = 0: none)
 
     // ---- jl_phase_rescue_async: buffers of its own, grown on demand (capi_rescue.hip); no stage and no run touches them
-    jl_dev_array<uint32_t> rescue_in;    // pos_cols [n_pos], then pat4 (jl_rescue_args)
+    jl_upload_staging<uint32_t> rescue_in;   // pos_cols [n_pos], then pat4 (jl_rescue_args)
     jl_dev_array<uint32_t> rescue_out;   // tally [4] as 8 words, hap_reads [JL_RESCUE_HAP_PAD], then rescue [rescue_n] 16 bits each
-    uint32_t *h_rescue_in = nullptr;     // pinned staging of rescue_in
-    size_t h_rescue_cap = 0;             // ... in words
-    hipEvent_t rescue_ev = nullptr;      // behind the last upload out of the staging
     uint64_t rescue_n = 0;               // reads of the last rescue enqueued (0: none)
     uint32_t rescue_h = 0;               // ... and its haplotypes
 
     // ---- phasing sharded by reads: the groups of this matrix exported for the merge (jl_phase_groups_async / _fetch)
     bool phase_export = false;        // the phase launch in flight / last run exported instead of selecting
-    uint32_t *d_exp_count = nullptr;  // [exp_cap]
-    uint8_t *d_exp_pattern = nullptr; // [exp_cap][exp_stride]
-    uint16_t *d_exp_hap = nullptr;    // [exp_cap] the merge's answer on its way to the slots
-    uint32_t exp_cap = 0, exp_stride = 0;
+    jl_dev_array<uint32_t> d_exp_count;  // [exp_cap]
+    jl_dev_array<uint8_t> d_exp_pattern; // [exp_cap][exp_stride]
+    jl_dev_array<uint16_t> d_exp_hap;    // [exp_cap] the merge's answer on its way to the slots
+    uint32_t exp_cap = 0, exp_stride = 0;   // the shape the three were made for (more than a capacity: kernels index with them)
     uint32_t exp_n_groups = 0;        // groups the last export produced, once the host has read the count (regroup checks it)
     uint32_t exp_vp = 0;              // ... and its variant positions (0: nothing was phased, no read has flags or a slot)
     bool exp_known = false;
@@ -535,81 +581,77 @@ struct jl_ctx {
     uint32_t P = 0;
     double default_n_tests = 0.0;
     std::vector<uint32_t> h_pos_gene, h_pos_codon, h_pos_col;
-    uint32_t *d_pos_gene = nullptr, *d_pos_codon = nullptr, *d_pos_col = nullptr;
-    uint8_t *d_pos_refcfg = nullptr;
-    size_t pos_capacity = 0;
+    jl_dev_array<uint32_t> d_pos_gene, d_pos_codon, d_pos_col;   // [P] each, as are d_pos_next, d_called, d_drm; d_staged [P][64]
+    jl_dev_array<uint8_t> d_pos_refcfg;
     // the positions by column, for the Fisher stage folded into the pileup launch (kernels_pileup.hip): col_head[c] = the first
     // position whose codon begins at column c (all ones: none), pos_next[p] = the next one at the same column (genes that overlap
     // in one frame)
-    uint32_t *d_col_head = nullptr, *d_pos_next = nullptr;
-    uint8_t *d_guess = nullptr;    // [n_cols + JL_GUESS_PAD] base the codon compare is seeded with (never affects
+    jl_dev_array<uint32_t> d_col_head, d_pos_next;
+    jl_dev_array<uint8_t> d_guess; // [n_cols + JL_GUESS_PAD] base the codon compare is seeded with (never affects
                                    // results); the zeroed pad lets the kernel fetch it as aligned dwords
-    size_t col_capacity = 0;
 
     // ---- pileup outputs: one zeroed region = col counts [n_cols][6] then hist [n_cols][64]
-    uint32_t *d_counts = nullptr;
-    uint32_t *d_hist = nullptr;
+    jl_dev_array<uint32_t> d_counts;
+    uint32_t *d_hist = nullptr;    // a view into d_counts
     size_t counts_words = 0;
     bool pileup_done = false;
     // pileup chunk table (host-built, see build_chunks): chunk k owns columns [c0, c0 + n), n <= pileup_w
     uint32_t pileup_w = 3;
     uint32_t n_chunks = 0;
-    uint64_t *d_chunks = nullptr;  // [n_chunks] records {first column, JL_CHUNK_META}: see kernels_pileup.hip
-    size_t chunk_capacity = 0;
+    jl_dev_array<uint64_t> d_chunks;  // [n_chunks] records {first column, JL_CHUNK_META}: see kernels_pileup.hip
 
     // ---- call
-    uint64_t *d_called = nullptr;  // [P] mask of called codons
-    jl_variant *d_staged = nullptr;  // [P][64] finished rows of the called codons, before the ordered compaction
-    uint64_t *d_drm = nullptr;     // [P] optional
-    jl_variant *d_variants = nullptr;  // [JL_VARIANT_CAP]
-    uint32_t *d_nvar = nullptr;        // [0] rows needed, [1] spare
+    jl_dev_array<uint64_t> d_called;   // [P] mask of called codons
+    jl_dev_array<jl_variant> d_staged; // [P][64] finished rows of the called codons, before the ordered compaction
+    jl_dev_array<uint64_t> d_drm;      // [P] optional
+    jl_dev_array<jl_variant> d_variants;  // [JL_VARIANT_CAP]
+    jl_dev_array<uint32_t> d_nvar;        // [0] rows needed, [1] spare
     bool call_done = false;
 
     // ---- phase
-    jl_phase_meta *d_meta = nullptr;
-    uint32_t *d_vpcols = nullptr;   // [JL_VARIANT_CAP]
-    uint32_t *d_col2pos = nullptr;  // [n_cols]
-    uint8_t *d_varcol = nullptr;    // [n_cols] scratch flags
-    uint64_t *d_keys = nullptr;     // [kwords_cap][reads_pad]
-    size_t keys_capacity = 0;       // in uint64
+    jl_dev_array<jl_phase_meta> d_meta;
+    jl_dev_array<uint32_t> d_vpcols;   // [JL_VARIANT_CAP]
+    jl_dev_array<uint32_t> d_col2pos;  // [n_cols]
+    jl_dev_array<uint8_t> d_varcol;    // [n_cols] scratch flags
+    jl_dev_array<uint64_t> d_keys;     // [kwords_cap][reads_pad]
     uint32_t keys_words = 0;        // 64-bit words per read the key buffer holds
     uint32_t last_min_reads = 10;
-    uint32_t *d_flagw = nullptr;    // [reads_pad/8] nibble flags
-    uint32_t *d_blockcat = nullptr; // [phase workgroups][4] read categories of each workgroup's reads (summed by the selection)
-    uint32_t *d_read_slot = nullptr;  // [reads_pad]
-    uint16_t *d_read_hap = nullptr;   // [reads_pad]
-    uint32_t *d_slot_rep = nullptr, *d_slot_count = nullptr;  // [M]
-    uint64_t *d_slot_key = nullptr;                           // [M] single-word keys (fused path)
-    uint32_t *d_slot_hap = nullptr;                           // [M] haplotype id of a table slot (32-bit: write-through stores)
-    uint32_t *d_occupied = nullptr;                           // [reads_pad]
+    jl_dev_array<uint32_t> d_flagw;    // [reads_pad/8] nibble flags
+    jl_dev_array<uint32_t> d_blockcat; // [phase workgroups][4] read categories of each workgroup's reads (summed by the selection)
+    jl_dev_array<uint32_t> d_read_slot;  // [reads_pad]
+    jl_dev_array<uint16_t> d_read_hap;   // [reads_pad]
+    jl_dev_array<uint32_t> d_slot_rep, d_slot_count;  // [M]
+    jl_dev_array<uint64_t> d_slot_key;                // [M] single-word keys (fused path)
+    jl_dev_array<uint32_t> d_slot_hap;                // [M] haplotype id of a table slot (32-bit: write-through stores)
+    jl_dev_array<uint32_t> d_occupied;                // [reads_pad]
     uint64_t table_slots = 0;
-    size_t reads_capacity = 0;
-    uint32_t *d_hap_count = nullptr;   // [JL_MAX_HAPLOTYPES]
-    uint8_t *d_hap_pattern = nullptr;  // [JL_MAX_HAPLOTYPES][JL_VARIANT_CAP]
-    uint8_t *d_hit = nullptr;          // [JL_VARIANT_CAP][JL_MAX_HAPLOTYPES]
-    uint32_t *d_cooc = nullptr;        // [cooc_cap][cooc_cap]
+    size_t reads_capacity = 0;      // reads_pad the per-read arrays and the grouping table were made AND INITIALISED for (more than a
+                                    // capacity: the whole group is made anew, its table emptied, when this grows)
+    jl_dev_array<uint32_t> d_hap_count;   // [JL_MAX_HAPLOTYPES]
+    jl_dev_array<uint8_t> d_hap_pattern;  // [JL_MAX_HAPLOTYPES][JL_VARIANT_CAP]
+    jl_dev_array<uint8_t> d_hit;          // [JL_VARIANT_CAP][JL_MAX_HAPLOTYPES]
+    jl_dev_array<uint32_t> d_cooc;        // [cooc_cap][cooc_cap]
     uint32_t cooc_cap = 256;
     bool phase_done = false;
     bool ids_separate = false;   // a phase launch of this context with inline ids timed out once: the ids take a launch of their own
     jl_phase_form phase_form = jl_phase_form::one_word;   // only grows, except where a session sets it (jl_phase_groups_prepare)
-    uint64_t *d_slot_key_a = nullptr, *d_slot_key_b = nullptr;   // half-key tables of the two-word launch [table slots]
-    uint32_t *d_occ_a = nullptr, *d_occ_b = nullptr;             // [reads_pad]
-    uint64_t two_slots = 0;                                      // table size the half-key tables were made for
+    jl_dev_array<uint64_t> d_slot_key_a, d_slot_key_b;   // half-key tables of the two-word launch [table slots]
+    jl_dev_array<uint32_t> d_occ_a, d_occ_b;             // [reads_pad]
+    uint64_t two_slots = 0;   // table size the half-key tables were made and emptied for (more than a capacity: 0 = to be made anew)
 
     // ---- whole-path run: result pack, pinned mirrors, captured graph
-    jl_pack *d_pack = nullptr;        // [2]: run n writes block n & 1 (an exchange may still read the other one)
-    jl_pack *h_pack = nullptr;        // pinned
-    uint16_t *h_read_hap = nullptr;   // pinned, [reads_pad]
-    size_t h_read_hap_cap = 0;
+    jl_dev_array<jl_pack> d_pack;     // [2]: run n writes block n & 1 (an exchange may still read the other one)
+    jl_pinned_array<jl_pack> h_pack;
+    jl_pinned_array<uint16_t> h_read_hap;   // [reads_pad]
     jl_pack *pack_mirror = nullptr;     // where kernels mirror the result block (h_pack during jl_run_async)
     uint16_t *read_hap_out = nullptr;   // where phase_assign_kernel writes (h_read_hap when the host wants the ids)
     bool pack_valid = false;          // the last stage calls were one jl_run_async
     bool run_read_hap = false;
     // completion without a HIP sync: the last kernel of a run bumps d_sync[0] and stores it to *h_seq (pinned)
-    uint32_t *d_sync = nullptr;       // [16] zeroed once: [0] runs completed, [1..] arrival counters of fused kernels
-    volatile uint32_t *h_seq = nullptr;  // pinned [16]: [0] the run word; [4] the word of jl_fetch_to_host
-    uint8_t *h_scratch = nullptr;     // pinned: small device arrays on their way to the host (a first pageable copy of a
-    size_t h_scratch_cap = 0;         // process costs the runtime milliseconds: staging buffers, pinning the target)
+    jl_dev_array<uint32_t> d_sync;    // [16] zeroed once: [0] runs completed, [1..] arrival counters of fused kernels
+    jl_pinned_array<volatile uint32_t> h_seq;  // [16]: [0] the run word; [4] the word of jl_fetch_to_host
+    jl_pinned_array<uint8_t> h_scratch;   // small device arrays on their way to the host (a first pageable copy of a
+                                          // process costs the runtime milliseconds: staging buffers, pinning the target)
     uint32_t fetches = 0;             // completed jl_fetch_to_host calls (device word d_sync[8], host word h_seq[4])
     uint32_t runs_launched = 0;
     uint32_t exch_pending = 0;        // exchanges requested and not yet collected: each still reads one of the two result blocks
@@ -621,7 +663,11 @@ struct jl_ctx {
     hipGraphExec_t graph_exec = nullptr;
     std::vector<uint8_t> graph_sig;
     std::vector<uint8_t> graph_seen;   // signature of the last eager run (a configuration is captured on its second run)
-    uint64_t alloc_version = 0;       // bumped by every (re)allocation: captured pointers go stale
+    // What a captured graph bakes in went stale.  Bumped by jl_ctx_reserve (capi.hip) when an array moved, the one place that
+    // reserves what a run or a stage touches, and by hand where no allocation is behind it.  These four are the complete list:
+    // set_shape (the matrix's shape), free_msa (an adopted or owned matrix goes), phase_ids_go_separate (the ids get a launch
+    // of their own), jl_run_pileup_clock (the clock nodes come or go).
+    uint64_t alloc_version = 0;
     uint64_t plan_version = 0;
     int pileup_blocks_per_cu[16] = {0};  // occupancy per kernel variant, queried once
 
@@ -711,14 +757,6 @@ void jl_launch_ingest(jl_ctx *dst, const jl_records &R, uint32_t min_qv);
 uint32_t jl_ingest_sweeps(uint32_t n_cols);
 size_t jl_ingest_slow_room(const jl_ctx *ctx);
 extern "C" int jl_ingest_verdict(jl_ctx *ctx);
-// capi_records.hip: frees the records uploaded to `ctx` and the scratch of the builds into it (jl_ctx_destroy)
-void jl_records_release(jl_ctx *ctx);
-// capi_take.hip: frees the index buffers of the takes into `ctx` (jl_ctx_destroy)
-void jl_take_release(jl_ctx *ctx);
-// capi_class.hip: frees the buffers of the class pileups of `ctx` (jl_ctx_destroy)
-void jl_class_release(jl_ctx *ctx);
-// capi_rescue.hip: frees the buffers of the rescue calls of `ctx` (jl_ctx_destroy)
-void jl_rescue_release(jl_ctx *ctx);
 void jl_launch_regroup(jl_ctx *ctx, const uint16_t *d_hap_of_group, uint32_t n_groups, uint32_t n_haplotypes, bool phased);
 void jl_launch_insertions(jl_ctx *dst, const jl_records &R);
 void jl_launch_fisher_eval(jl_ctx *ctx, uint32_t n, const uint32_t *a, const uint32_t *c, const uint32_t *cov, int tail,

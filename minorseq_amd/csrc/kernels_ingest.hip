@@ -1344,13 +1344,13 @@ void jl_launch_ingest(jl_ctx *dst, const jl_records &R, uint32_t min_qv)
     const jl_qv_mode mode = jl_qv_mode_of(R.have_qual, R.masked, min_qv);
     unsigned long long *bad = reinterpret_cast<unsigned long long *>(S.d_count + 2);
     // (the cigar kernels check a read's quality COUNT: the offsets whenever the stream has qualities, whatever min_qv is)
-    const uint64_t *qo = R.have_qual ? R.qo.d : nullptr;
+    const uint64_t *qo = R.have_qual ? R.qo : nullptr;
     hipLaunchKernelGGL(cigar_walk_kernel, dim3((uint32_t)((dst->n_reads + kWalkReads - 1u) / kWalkReads)), dim3(256), 0, st,
-                       dst->n_reads, R.pos.d, R.cig.d, R.co.d, R.so.d, qo, dst->win_begin, dst->n_cols, ns, S.runs.d, S.nruns.d, S.desc.d, bad, S.d_count, R.maybe_long ? 1u : 0u);
+                       dst->n_reads, R.pos, R.cig, R.co, R.so, qo, dst->win_begin, dst->n_cols, ns, S.runs, S.nruns, S.desc, bad, S.d_count, R.maybe_long ? 1u : 0u);
     // (the launch for the long reads: not when the upload has looked and found none — every CCS sample: 6 us of a build)
     if (R.maybe_long)
         hipLaunchKernelGGL(cigar_runs_kernel, dim3((uint32_t)std::min<uint64_t>(kRunsLongGrid, (dst->n_reads + 255u) / 256u)), dim3(256), 0, st,
-                           dst->n_reads, R.pos.d, R.cig.d, R.co.d, R.so.d, qo, dst->win_begin, dst->n_cols, ns, S.runs.d, S.nruns.d, S.desc.d, bad);
+                           dst->n_reads, R.pos, R.cig, R.co, R.so, qo, dst->win_begin, dst->n_cols, ns, S.runs, S.nruns, S.desc, bad);
     ingest_args a;
     a.n_reads = dst->n_reads;
     a.n_cols = dst->n_cols;
@@ -1358,18 +1358,18 @@ void jl_launch_ingest(jl_ctx *dst, const jl_records &R, uint32_t min_qv)
     const uint64_t reads_pad = dst->plane_stride * 8u;                 // a multiple of 1024: whole line groups of tiles
     a.n_groups = (uint32_t)(reads_pad / 1024u);
     a.min_qv = std::min<uint32_t>(min_qv, 127u);   // (the byte-parallel compare of the QV path; BAM qualities end at 93)
-    a.cig_off = R.co.d;
-    a.seq4 = R.seq.d;
-    a.seq_off = R.so.d;
+    a.cig_off = R.co;
+    a.seq4 = R.seq;
+    a.seq_off = R.so;
     // (null unless the mode is theirs: slow_pair tests these pointers)
-    a.qual = mode == JL_QV_BYTES ? R.qual.d : nullptr;
-    a.qual_off = mode == JL_QV_BYTES ? R.qo.d : nullptr;
-    a.qmask = mode == JL_QV_MASK ? R.mask.d : nullptr;
-    a.runs = S.runs.d;
-    a.nruns = S.nruns.d;
-    a.desc = S.desc.d;
+    a.qual = mode == JL_QV_BYTES ? R.qual : nullptr;
+    a.qual_off = mode == JL_QV_BYTES ? R.qo : nullptr;
+    a.qmask = mode == JL_QV_MASK ? R.mask : nullptr;
+    a.runs = S.runs;
+    a.nruns = S.nruns;
+    a.desc = S.desc;
     a.slow_count = S.d_count;
-    a.big_list = reinterpret_cast<uint32_t *>(S.slow.d);
+    a.big_list = S.slow.as<uint32_t>();
     a.msa = dst->d_msa;
     a.plane_stride = dst->plane_stride;
     const uint32_t grid = planes_units(dst);

@@ -1684,7 +1684,7 @@ void jl_fill_win_phase(jl_ctx *ctx, uint32_t min_reads, bool signal, bool ids_in
     const bool signal_select = signal && !ids_to_host;   // no ids wanted on the host: the selection ends the run
     w->msa = ctx->d_msa; w->col_stride = ctx->col_stride; w->n_reads = ctx->n_reads; w->reads_pad = ctx->col_stride * 2u;
     w->vpcols = ctx->d_vpcols; w->meta = ctx->d_meta; w->keys = ctx->d_keys; w->flagw = ctx->d_flagw;
-    w->slots_mask = ctx->table_slots - 1u; w->slot_key = (unsigned long long *)ctx->d_slot_key;
+    w->slots_mask = ctx->table_slots - 1u; w->slot_key = ctx->d_slot_key.as<unsigned long long>();
     w->slot_rep = ctx->d_slot_rep; w->slot_count = ctx->d_slot_count; w->occupied = ctx->d_occupied;
     w->read_slot = ctx->d_read_slot;
     w->blockcat = ctx->d_blockcat;
@@ -1750,13 +1750,13 @@ bool jl_launch_phase(jl_ctx *ctx, hipStream_t st, uint32_t min_reads, jl_phase_p
                            ctx->d_meta, ctx->d_slot_rep, ctx->d_slot_count, ctx->d_occupied, ctx->d_slot_hap,
                            ctx->d_variants, ctx->d_col2pos, ctx->n_cols, ctx->d_hap_count, ctx->d_hap_pattern, ctx->d_hit,
                            ctx->d_nvar, ctx->d_vpcols, ctx->d_cooc, ctx->cooc_cap, ctx->d_pack, ctx->pack_mirror,
-                           (unsigned long long *)ctx->d_slot_key, ctx->d_sync, signal_select ? ctx->h_seq : nullptr,
+                           ctx->d_slot_key.as<unsigned long long>(), ctx->d_sync, signal_select ? ctx->h_seq : nullptr,
                            w.S.exp_count, w.S.exp_pattern, w.S.exp_cap, w.S.exp_stride, w.S.exp_head);
     } else if (ctx->direct.on && !w.S.called) {
         hipLaunchKernelGGL(phase_fused1_direct_kernel, dim3(w.n_blocks), dim3(256), 0, st, w, ctx->direct);
     } else if (ctx->phase_form == jl_phase_form::two_word) {
         jl_two_word tw;
-        tw.key_a = (unsigned long long *)ctx->d_slot_key_a; tw.key_b = (unsigned long long *)ctx->d_slot_key_b;
+        tw.key_a = ctx->d_slot_key_a.as<unsigned long long>(); tw.key_b = ctx->d_slot_key_b.as<unsigned long long>();
         tw.occ_a = ctx->d_occ_a; tw.occ_b = ctx->d_occ_b; tw.n_occ = ctx->d_sync + 10;
         hipLaunchKernelGGL(phase_fused2_kernel, dim3(w.n_blocks + (w.S.called ? 1u : 0u)), dim3(256), 0, st, w, tw);
     } else {

@@ -435,7 +435,7 @@ void jl_launch_pileup(jl_ctx *ctx, hipStream_t st)
     const uint32_t nt = planes_tiles(ctx, false);
 #define JL_LAUNCH_PLANES(W, NQ)                                                                                                       \
     hipLaunchKernelGGL((pileup_planes_kernel<W, NQ>), dim3(ctx->n_chunks, rsplit), dim3(256), 0, st, ctx->d_msa, ctx->plane_stride,   \
-                       ctx->n_cols, nt, (const uint2 *)ctx->d_chunks, (const uint32_t *)ctx->d_guess, ctx->d_counts, ctx->d_hist)
+                       ctx->n_cols, nt, ctx->d_chunks.as<const uint2>(), ctx->d_guess.as<const uint32_t>(), ctx->d_counts, ctx->d_hist)
     if (ctx->pileup_w == 6) JL_LAUNCH_PLANES(6, 2);
     else if (planes_nq(ctx, false) == 4) JL_LAUNCH_PLANES(3, 4);
     else JL_LAUNCH_PLANES(3, 2);
@@ -463,8 +463,8 @@ void jl_launch_pileup_fold(jl_ctx *ctx, hipStream_t st, const jl_win_call *call)
     w.n_tiles = planes_tiles(ctx, false);
     w.n_chunks = ctx->n_chunks;
     w.pad_ = 0;
-    w.chunks = (const uint2 *)ctx->d_chunks;
-    w.guess32 = (const uint32_t *)ctx->d_guess;
+    w.chunks = ctx->d_chunks.as<const uint2>();
+    w.guess32 = ctx->d_guess.as<const uint32_t>();
     w.counts = ctx->d_counts;
     w.hist = ctx->d_hist;
     jl_fill_win_fold(ctx, call, &f);
@@ -495,8 +495,8 @@ void jl_fill_win_pileup(jl_ctx *ctx, jl_win_pileup *w)
     w->n_tiles = planes_tiles(ctx, true);
     w->n_chunks = ctx->n_chunks;
     w->pad_ = 0;
-    w->chunks = (const uint2 *)ctx->d_chunks;
-    w->guess32 = (const uint32_t *)ctx->d_guess;
+    w->chunks = ctx->d_chunks.as<const uint2>();
+    w->guess32 = ctx->d_guess.as<const uint32_t>();
     w->counts = ctx->d_counts;
     w->hist = ctx->d_hist;
 }

@@ -277,7 +277,7 @@ void jl_launch_done_on(jl_ctx *ctx, hipStream_t st)
 __global__ void clock_kernel(volatile unsigned long long *dst) { *dst = wall_clock64(); }
 void jl_launch_clock(jl_ctx *ctx, hipStream_t st, uint32_t which)
 {
-    hipLaunchKernelGGL(clock_kernel, dim3(1), dim3(1), 0, st, reinterpret_cast<volatile unsigned long long *>(const_cast<uint32_t *>(ctx->h_seq) + 8u + 2u * which));
+    hipLaunchKernelGGL(clock_kernel, dim3(1), dim3(1), 0, st, ctx->h_seq.as<volatile unsigned long long>() + 4u + which);
 }
 
 const jl_env_switches &jl_env()
@@ -319,7 +319,7 @@ void jl_launch_planes_to_nibbles(jl_ctx *ctx, uint8_t *d_nib, uint64_t nib_strid
 void jl_launch_insertions(jl_ctx *dst, const jl_records &R)
 {
     hipLaunchKernelGGL(insertions_kernel, dim3((uint32_t)((dst->n_reads + 255u) / 256u)), dim3(256), 0, dst->stream, dst->n_reads,
-                       dst->n_cols, dst->win_begin, R.pos.d, R.cig.d, R.co.d, R.seq.d, R.so.d, dst->d_ins_len, dst->d_ins_base);
+                       dst->n_cols, dst->win_begin, R.pos, R.cig, R.co, R.seq, R.so, dst->d_ins_len, dst->d_ins_base);
 }
 
 void jl_launch_synth(jl_ctx *ctx, const jl_synth_plan *plan, const uint8_t *d_ref, uint32_t col0)

@@ -207,6 +207,16 @@ def test_repeat_on_one_context(ctx):
     assert (counts == exp_counts).all() and (reads == exp_reads).all()
 
 
+def test_staging_grows_and_is_reused(ctx):
+    """1500, then 5000, then 1500 reads on one context: the label staging, the mask rows and the counts grow for the second call
+    and serve the third, larger than it needs."""
+    l = 60
+    for seed, n in enumerate((1500, 5000, 1500)):
+        rows = code_rows(n, l, 50 + seed)
+        ctx.upload_rows(rows)
+        check(ctx, rows, labels("random", n, 17, seed), 17)
+
+
 def test_refusals_change_nothing():
     lib = capi.load_library()
     j = capi.Juliet(0)

@@ -413,6 +413,68 @@ def test_run_graph_replay_tracks_new_data_and_parameters(jl, oracle):
     j.close()
 
 
+def test_run_graph_survives_a_context_that_grows(oracle):
+    """One context: a small window (its second run captures a graph, its third replays it), then a larger one with two genes and
+    11..20 variant positions — every per-column, per-position and per-read array moves, and the phase form goes to two-word
+    with tables of its own — then the small one again.  No replay may reach memory that was freed: every run equals the oracle."""
+    j = capi.Juliet(0)
+    small = (2000, 90, np.array([(1, 91)], dtype=capi.GENE), 0.0, (61, 62, 63))
+    large = (6000, 300, np.array([(1, 151), (151, 301)], dtype=capi.GENE), 0.005, (51, 52, 51))
+    for n, l, genes, sub_rate, seeds in (small, large, small):
+        ref = synth.reference(seeds[0], l)      # one reference a shape: the plan, and the graph, stay valid across its seeds
+        j.alloc(n, l)
+        for seed in seeds:
+            j.synth_fill(synth.SynthParams(seed=seed, sub_rate=sub_rate, minor_permille=(60, 50, 40, 30)), ref)
+            rows = msa.unpack_columns(j.download_columns(), n)
+            out = j.run(genes, ref)
+            exp_v = oracle.call(rows, genes, refseq=ref)
+            exp_p = oracle.phase(rows, exp_v)
+            if l == 300:
+                assert 11 <= exp_p["summary"]["n_positions"] <= 20      # (the two-word form)
+            assert_variants_equal(out["variants"], exp_v)
+            assert_phase_equal(out["phase"], exp_p, len(exp_v))
+    j.close()
+
+
+def test_destroyed_contexts_give_their_memory_back(jl):
+    """50 contexts made and destroyed, every tenth after a matrix, a run with phasing, a take, a class pileup and a rescue: the
+    device has as much free memory afterwards as before, to within what ONE such context holds (measured here)."""
+    import torch
+    n, l = 1500, 60
+    sp = synth.SynthParams(seed=7, minor_permille=(150, 120, 100, 80))
+    ref = synth.reference(sp.seed, l)
+    genes = np.array([(1, l + 1)], dtype=capi.GENE)
+    jl.upload_rows(synth.rows(sp, l, 0, n, ref))
+    idx = np.arange(n, dtype=np.uint32)[::-1].copy()
+
+    def busy():
+        j = capi.Juliet(0)
+        j.take([(jl, idx)])
+        ph = j.run(genes, ref)["phase"]
+        h = ph["summary"]["n_haplotypes"]
+        assert h >= 2
+        assert int(j.class_pileup(ph["read_hap"], h)[1].sum()) == ph["summary"]["reported_reads"]
+        assert int(j.phase_rescue(ph["pos_cols"], ph["hap_pattern"], 1)["tally"].sum()) == n
+        return j
+
+    def free_bytes():
+        torch.cuda.synchronize()
+        return torch.cuda.mem_get_info(0)[0]
+
+    busy().close()                  # (the runtime's own pools are warm after one)
+    at = free_bytes()
+    j = busy()
+    footprint = at - free_bytes()
+    j.close()
+    assert footprint > 0
+    before = free_bytes()
+    for i in range(50):
+        (busy() if i % 10 == 9 else capi.Juliet(0)).close()
+    lost = before - free_bytes()
+    print("footprint of one context %d bytes, lost over 50 contexts %d bytes" % (footprint, lost))
+    assert lost <= footprint
+
+
 def test_run_results_larger_than_the_pack(jl, oracle):
     """More variants / positions than the pinned result block holds: the fetch calls fall back to piecewise copies."""
     n, l = 6000, 600

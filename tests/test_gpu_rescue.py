@@ -148,6 +148,25 @@ def test_repeat_on_one_context(ctx):
     assert (out["rescue"] == exp[0]).all() and (out["hap_reads"] == exp[1]).all() and (out["tally"] == exp[2]).all()
 
 
+def test_staging_grows_and_is_reused(ctx):
+    """1500 reads and 3 positions, then 5000 and 40, then 1500 and 3 again, at 60 columns on one context: the staging of positions
+    and pattern and the buffers of the ids grow for the second call and serve the third, larger than it needs."""
+    l, n_hap = 60, 9
+    for seed, (n, cols) in enumerate(((1500, [0, 1, 57]), (5000, list(range(20)) + list(range(38, 58))), (1500, [0, 1, 57]))):
+        rng = np.random.default_rng(70 + seed)
+        pos_cols = np.array(cols, dtype=np.uint32)
+        haps = rng.integers(0, 4, size=(n_hap, l), dtype=np.uint8)
+        rows = haps[rng.integers(0, n_hap, size=n)]
+        cell = rng.random(size=rows.shape)
+        rows[cell < 0.01] = 4                       # scattered '-', N and uncovered cells
+        rows[cell > 0.99] = 5
+        rows[(cell > 0.49) & (cell < 0.50)] = 6
+        sub = (cell > 0.200) & (cell < 0.203) & (rows < 4)      # a substitution: such a read may agree with nobody
+        rows[sub] = (rows[sub] + 1) % 4
+        ctx.upload_rows(rows)
+        check(ctx, rows, pos_cols, codons_at(haps, pos_cols), 1 if len(cols) == 3 else 2)
+
+
 def fetch_copy(j):
     out = j.run_fetch(True, True, cap_var=64)
     return dict(variants=out["variants"].copy(), phase={k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in out["phase"].items()})

@@ -168,6 +168,19 @@ def test_take_into_a_destination_that_held_more(ctxs):
     assert (col == exp).all()
 
 
+def test_take_staging_grows_and_is_reused(ctxs):
+    """1500, then 5000, then 1500 reads into one destination: the index staging and the device array grow for the second take
+    and serve the third, larger than it needs."""
+    l = 60
+    src, dst = ctxs[0], ctxs[1]
+    rows = code_rows(5000, l, 31)
+    src.upload_rows(rows)
+    for k, n_keep in enumerate((1500, 5000, 1500)):
+        idx = np.random.default_rng(k).integers(0, 5000, size=n_keep).astype(np.uint32)
+        dst.take([(src, idx)])
+        assert_is_selection(dst, rows[idx])
+
+
 # ---------------------------------------------------------------------------------------------- the path on a taken window
 PIPE_N, PIPE_L, PIPE_KEEP, PIPE_SEED = 5000, 300, 1500, 11
 PIPE_SP = synth.SynthParams(seed=21, minor_permille=(90, 70, 50, 40), partial_rate=0.1)
