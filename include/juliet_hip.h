@@ -340,6 +340,48 @@ int jl_phase_rescue_async(jl_ctx *ctx, const uint32_t *pos_cols, uint32_t n_pos,
  * JL_ERR_STATE: none was enqueued. */
 int jl_phase_rescue_fetch(jl_ctx *ctx, uint16_t *rescue, uint32_t *hap_reads, uint64_t *tally /* [4] */);
 /*
+ * Pairwise linkage of called variants over EVERY READ COVERING BOTH (docs/SPEC.md §15): do variant v and variant w occur on the
+ * same molecules?  The co-occurrence of jl_phase_fetch counts the reads of the reported haplotypes only — reads that can be read
+ * at all Vp positions, in groups of min_reads; a pair needs only the reads that can be read at its TWO positions.
+ * pos_cols[n_pos]: window columns of codon starts, strictly ascending, each + 2 < n_cols (overlapping codons allowed);
+ * var_pos[n_var]: for each variant an index into pos_cols, non-decreasing (the variant table's order, several variants per
+ * position); var_codon[n_var]: codons 0..63.  1 <= n_pos <= JL_LINK_MAX, 1 <= n_var <= JL_LINK_MAX.  Per read i: it is
+ * INFORMATIVE at p iff its three codes at pos_cols[p] .. + 2 are all < 4 (jl_phase_rescue_async's definition); it CARRIES v iff
+ * it is informative at var_pos[v] and its codon there equals var_codon[v].  Outputs, 32 bits, exact, independent of launch shape
+ * and order:
+ *   both[n_pos][n_pos]   reads informative at p and q; symmetric; both[p][p] = the codon coverage
+ *   carry[n_var][n_pos]  reads that carry v and are informative at q; carry[v][var_pos[v]] = the variant's count
+ *   joint[n_var][n_var]  reads that carry v and w; symmetric; joint[v][v] = the count; 0 for two different codons at one position
+ * Reads past n_reads count nowhere: the padding, and whatever an adopted matrix holds past byte ceil(n_reads / 8) of a plane row.
+ * Only the upper triangle of the symmetric outputs is computed; it is mirrored on store, on the device: the fetch copies whole tables.
+ * The contract is jl_class_pileup_async's: the inputs are copied before the call returns; it enqueues on the context's stream
+ * into buffers of its own (grown on demand, released with the context) and touches nothing else — the matrix, the insertion
+ * counters, earlier stage results and the captured graph stay as they are.  Every kind of resident matrix is accepted.
+ * JL_ERR_STATE: no resident matrix.  JL_ERR_ARG (jl_last_error says which): a NULL array; n_pos or n_var 0 or above
+ * JL_LINK_MAX; a column with c + 2 >= n_cols; columns not strictly ascending; var_pos[v] >= n_pos, or var_pos decreasing; a
+ * codon above 63.  A refused call changes nothing: what an earlier call enqueued can still be fetched.
+ */
+enum { JL_LINK_MAX = 1024 };
+int jl_variant_linkage_async(jl_ctx *ctx, const uint32_t *pos_cols, uint32_t n_pos, const uint32_t *var_pos,
+                             const uint8_t *var_codon, uint32_t n_var);
+/* Wait and copy out, all of the last jl_variant_linkage_async: both[n_pos][n_pos], carry[n_var][n_pos], joint[n_var][n_var].
+ * Any pointer may be NULL.  JL_ERR_STATE: none was enqueued. */
+int jl_variant_linkage_fetch(jl_ctx *ctx, uint32_t *both, uint32_t *carry, uint32_t *joint);
+/* The 2 x 2 table of a pair (v, w) at different positions p != q and its statistics: n = both[p][q], n11 = joint[v][w],
+ * n10 = carry[v][q] - n11, n01 = carry[w][p] - n11, n00 = n - n11 - n10 - n01.  D_num = n11 n - (n11 + n10)(n11 + n01), in exact
+ * integers; r2 = D_num^2 / ((n11 + n10)(n01 + n00)(n11 + n01)(n10 + n00)), 0 when a margin is 0; d_prime = D_num / D_max with
+ * D_max = min((n11 + n10)(n10 + n00), (n01 + n00)(n11 + n01)) when D_num >= 0, min((n11 + n10)(n11 + n01), (n01 + n00)(n10 + n00))
+ * when D_num < 0, and 0 when D_max is 0; p_positive = P(X >= n11) and p_negative = P(X <= n11), X hypergeometric with the
+ * table's margins: the two one-sided Fisher tests, NOT Bonferroni-corrected. */
+typedef struct {
+    uint32_t n, n11, n10, n01, n00, pad_;
+    double r2, d_prime, p_positive, p_negative;
+} jl_link_pair;
+/* Host only (no device, no context): *out = the pair (v, w) of the tables of jl_variant_linkage_fetch.  JL_ERR_ARG
+ * (jl_last_error(NULL) says which): a NULL array; v or w >= n_var; var_pos[v] == var_pos[w]. */
+int jl_linkage_stats(const uint32_t *both, const uint32_t *carry, const uint32_t *joint, const uint32_t *var_pos,
+                     uint32_t n_pos, uint32_t n_var, uint32_t v, uint32_t w, jl_link_pair *out);
+/*
  * Reference/majority codon, error model, Fisher's exact x Bonferroni, filters, variant table
  * (SPEC §4-7; J:38-42).  `drm_masks`: optional [P] 64-bit codon masks; with --drm-only a codon is kept
  * only if its bit is set (J:370); NULL disables.  Table stays on the device; enqueues only.

@@ -17,6 +17,7 @@ MAX_HAPLOTYPES = 702
 HAP_INSUFFICIENT = 0xFFFE
 HAP_DAMAGED = 0xFFFF
 RESCUE_UNINFORMATIVE, RESCUE_NONE, RESCUE_AMBIGUOUS = 0xFFFB, 0xFFFC, 0xFFFD   # jl_phase_rescue_async (docs/SPEC.md §14)
+LINK_MAX = 1024   # jl_variant_linkage_async (docs/SPEC.md §15): positions, and variants, of one call
 VARIANT_CAP = 4096
 PACK_PATTERN_BYTES, PACK_HIT_BYTES = 8192, 16384   # jl_internal.h: what the pinned result block holds of hap_pattern / hit
 
@@ -32,7 +33,7 @@ SUMMARY = np.dtype([(n, "<u4") for n in SUMMARY_FIELDS])
 EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", "jl_ctx_destroy", "jl_last_error",
            "jl_sync", "jl_col_stride", "jl_plane_stride", "jl_msa_upload", "jl_msa_alloc", "jl_msa_adopt", "jl_msa_pack_rows",
            "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_take", "jl_msa_take_async", "jl_sample_reads", "jl_mix_counts", "jl_msa_download", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
-           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_phase_async", "jl_phase_fetch",
+           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_phase_async", "jl_phase_fetch",
            "jl_ctx_stream", "jl_run_async", "jl_run_wait", "jl_run_done", "jl_run_view_get", "jl_group_create", "jl_group_destroy",
            "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
            "jl_allgather_variants", "jl_allgather_variants_async", "jl_allgather_variants_async_many", "jl_allgather_variants_many", "jl_group_exchange_bind", "jl_group_exchange_collect", "jl_xwin_plan", "jl_xwin_assemble_local",
@@ -206,6 +207,9 @@ def load_library(path=LIB_PATH):
     lib.jl_phase_rescue_async.argtypes = [vp, vp, u32, vp, u32, u32, u32]
     lib.jl_phase_rescue_fetch.argtypes = [vp, vp, vp, vp]
     lib.jl_consensus_of_counts.argtypes = [vp, u32, vp]
+    lib.jl_variant_linkage_async.argtypes = [vp, vp, u32, vp, vp, u32]
+    lib.jl_variant_linkage_fetch.argtypes = [vp, vp, vp, vp]
+    lib.jl_linkage_stats.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, vp]
     lib.jl_call_async.argtypes = [vp, C.POINTER(Params), vp]
     lib.jl_call_fetch.argtypes = [vp, vp, u32, C.POINTER(u32)]
     lib.jl_variant_table_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u32)]
@@ -544,6 +548,29 @@ class Juliet:
         self._chk(self.lib.jl_phase_rescue_fetch(self.h, _p(rescue), _p(hap_reads), _p(tally)))
         return dict(rescue=rescue, hap_reads=hap_reads, tally=tally)
 
+    def variant_linkage(self, pos_cols, var_pos, var_codon, wait=True):
+        """jl_variant_linkage_async (docs/SPEC.md §15): pairwise linkage of variants over every read covering both.  pos_cols[P]
+        codon starts, strictly ascending; var_pos[V] indices into pos_cols, non-decreasing; var_codon[V] codons 0..63; P and V from
+        1 to LINK_MAX.  Read i is informative at p iff its three codes at pos_cols[p] .. + 2 are all < 4; it carries v iff it is
+        informative at var_pos[v] and its codon there equals var_codon[v].  Returns dict(both[P, P]: reads informative at p and q;
+        carry[V, P]: reads that carry v and are informative at q; joint[V, V]: reads that carry v and w), 32 bits, exact;
+        wait=False only enqueues on this context's stream and returns None (variant_linkage_fetch brings the arrays)."""
+        pos_cols = np.ascontiguousarray(pos_cols, dtype=np.uint32)
+        var_pos = np.ascontiguousarray(var_pos, dtype=np.uint32)
+        var_codon = np.ascontiguousarray(var_codon, dtype=np.uint8)
+        assert len(var_pos) == len(var_codon)
+        self._chk(self.lib.jl_variant_linkage_async(self.h, _p(pos_cols), len(pos_cols), _p(var_pos), _p(var_codon), len(var_pos)))
+        self._link_shape = (len(pos_cols), len(var_pos))
+        return self.variant_linkage_fetch() if wait else None
+
+    def variant_linkage_fetch(self):
+        p, v = getattr(self, "_link_shape", (0, 0))
+        both = np.zeros((p, p), dtype=np.uint32)
+        carry = np.zeros((v, p), dtype=np.uint32)
+        joint = np.zeros((v, v), dtype=np.uint32)
+        self._chk(self.lib.jl_variant_linkage_fetch(self.h, _p(both), _p(carry), _p(joint)))
+        return dict(both=both, carry=carry, joint=joint)
+
     def call_async(self, params=None, drm_masks=None):
         prm = params or default_params()
         if drm_masks is not None:
@@ -864,6 +891,30 @@ def consensus_of_counts(counts2d):
     if rc:
         raise JulietError(rc, "jl_consensus_of_counts")
     return out[: len(counts2d)].copy()
+
+
+class LinkPair(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("n11", C.c_uint32), ("n10", C.c_uint32), ("n01", C.c_uint32), ("n00", C.c_uint32),
+                ("pad_", C.c_uint32), ("r2", C.c_double), ("d_prime", C.c_double), ("p_positive", C.c_double),
+                ("p_negative", C.c_double)]
+
+
+def linkage_stats(both, carry, joint, var_pos, v, w):
+    """jl_linkage_stats (host only, docs/SPEC.md §15): the 2 x 2 table of the pair (v, w) — variants at different positions —
+    from the tables of Juliet.variant_linkage, and its statistics: dict(n, n11, n10, n01, n00, r2, d_prime, p_positive,
+    p_negative); the p-values are the two one-sided Fisher tests, not Bonferroni-corrected."""
+    lib = load_library()
+    both = np.ascontiguousarray(both, dtype=np.uint32)
+    carry = np.ascontiguousarray(carry, dtype=np.uint32)
+    joint = np.ascontiguousarray(joint, dtype=np.uint32)
+    var_pos = np.ascontiguousarray(var_pos, dtype=np.uint32)
+    n_pos, n_var = both.shape[0], joint.shape[0]
+    assert both.shape == (n_pos, n_pos) and carry.shape == (n_var, n_pos) and joint.shape == (n_var, n_var) and len(var_pos) == n_var
+    out = LinkPair()
+    rc = lib.jl_linkage_stats(_p(both), _p(carry), _p(joint), _p(var_pos), n_pos, n_var, int(v), int(w), C.byref(out))
+    if rc:
+        raise JulietError(rc, "jl_linkage_stats: " + lib.jl_last_error(None).decode())
+    return {name: getattr(out, name) for name, _ in LinkPair._fields_ if name != "pad_"}
 
 
 def mix_counts(n_sources, coverage, percentage):

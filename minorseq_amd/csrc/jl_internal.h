@@ -357,6 +357,27 @@ struct jl_rescue_args {
 };
 void jl_launch_phase_rescue(const jl_rescue_args *a, hipStream_t st);
 
+// ---- pairwise linkage of variants over every read covering both (kernels_link.hip, capi_link.hip; docs/SPEC.md §15)
+#define JL_LINK_TILE 8u                    // rows of a wave's tile side: 8 x 8 pairs in the registers of every lane
+#define JL_LINK_BLOCK_TILE 16u             // ... and of a workgroup's: four waves, 2 x 2 wave tiles
+#define JL_LINK_SPLIT_WORDS 256u           // smallest run of words (32 reads each) a workgroup takes of a row: four rounds a lane
+struct jl_link_args {
+    const uint8_t *msa;        // the window's bit planes
+    uint64_t plane_stride;     // ... and their stride (an adopted matrix brings its own)
+    uint64_t n_reads;
+    uint32_t n_pos, n_var;
+    uint32_t n_words;          // words of a row that hold reads: ceil(n_reads / 32)
+    uint32_t row_words;        // words of a row: jl_plane_stride(n_reads) / 4, whole 128-byte lines, >= n_words
+    uint32_t split_words;      // words of a row a workgroup of the product takes: a multiple of 64
+    uint32_t n_splits;         // ceil(n_words / split_words)
+    const uint32_t *pos_cols;  // [n_pos], each + 2 < n_cols
+    const uint32_t *var_first; // [n_pos + 1]: the variants of position p are var_first[p] .. var_first[p + 1] - 1
+    const uint32_t *var_codon; // [n_var], 0..63
+    uint32_t *rows;            // [n_pos + n_var][row_words]: the informative rows, then the carry rows; a bit per read
+    uint32_t *both, *carry, *joint;   // [n_pos][n_pos], [n_var][n_pos], [n_var][n_var]; zeroed
+};
+void jl_launch_variant_linkage(const jl_link_args *a, hipStream_t st);
+
 inline int jl_hip_status(hipError_t e) { return e == hipErrorOutOfMemory ? JL_ERR_MEMORY : JL_ERR_DEVICE; }
 
 // ---- owning arrays.  Every buffer a context owns is one of these: it frees itself when the context is deleted (jl_ctx_destroy, the
@@ -555,6 +576,12 @@ struct jl_ctx {
     jl_dev_array<uint32_t> rescue_out;   // tally [4] as 8 words, hap_reads [JL_RESCUE_HAP_PAD], then rescue [rescue_n] 16 bits each
     uint64_t rescue_n = 0;               // reads of the last rescue enqueued (0: none)
     uint32_t rescue_h = 0;               // ... and its haplotypes
+
+    // ---- jl_variant_linkage_async: buffers of its own, grown on demand (capi_link.hip); no stage and no run touches them
+    jl_upload_staging<uint32_t> link_in;   // pos_cols [n_pos], var_first [n_pos + 1], var_codon [n_var] (jl_link_args)
+    jl_dev_array<uint32_t> link_rows;      // the bit rows
+    jl_dev_array<uint32_t> link_out;       // both [link_p][link_p], carry [link_v][link_p], joint [link_v][link_v]
+    uint32_t link_p = 0, link_v = 0;       // shape of the last linkage enqueued (link_p = 0: none)
 
     // ---- phasing sharded by reads: the groups of this matrix exported for the merge (jl_phase_groups_async / _fetch)
     bool phase_export = false;        // the phase launch in flight / last run exported instead of selecting

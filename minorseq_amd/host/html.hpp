@@ -188,6 +188,25 @@ inline std::string render_html(const Json &root)
         }
         h += "</details>\n";
     }
+    // ---- --linkage (docs/SPEC.md §15): every pair of variants over the reads covering both; doubles as the JSON prints them
+    if (const Json *lb = root.get("linkage")) {
+        h += "<details open id=\"linkage\"><summary>Linkage</summary><table id=\"linkage-summary\">\n";
+        for (const char *key : {"n_variants", "n_pairs_tested", "skipped"})
+            if (lb->get(key)) h += "<tr data-key=\"" + std::string(key) + "\"><th>" + key + "</th>" + td(num_str(lb->get(key))) + "</tr>\n";
+        h += "</table>\n<p id=\"linkage-positions\">";
+        if (const Json *pc = lb->get("variant_positions_abs"))
+            for (const Json &p : pc->arr) h += "<span>" + num_str(&p) + "</span> ";
+        h += "</p>\n<table id=\"linkage-table\"><tr><th>Gene</th><th>Pos</th><th>Codon</th><th>Gene</th><th>Pos</th><th>Codon</th><th>#Reads both</th>"
+             "<th>n11</th><th>n10</th><th>n01</th><th>n00</th><th>r2</th><th>D'</th><th>p positive</th><th>p negative</th></tr>\n";
+        if (const Json *pairs = lb->get("pairs"))
+            for (const Json &pr : pairs->arr) {
+                h += "<tr>";
+                for (const char *s : {"a", "b"}) h += td(pr.get(s)->get_str("gene")) + td(num_str(pr.get(s)->get("ref_position"))) + td(pr.get(s)->get_str("codon"));
+                for (const char *key : {"reads_both", "n11", "n10", "n01", "n00", "r2", "d_prime", "p_positive", "p_negative"}) h += td(num_str(pr.get(key)));
+                h += "</tr>\n";
+            }
+        h += "</table></details>\n";
+    }
     h += "</body></html>\n";
     return h;
 }

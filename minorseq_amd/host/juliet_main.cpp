@@ -60,6 +60,7 @@ struct Options {
     bool rescue = false;             // --rescue-damaged: which reported haplotype each damaged read agrees with (docs/SPEC.md §14)
     uint32_t rescue_min = 1;         // --rescue-min-positions K: informative positions a read needs to be judged at all
     bool have_rescue_min = false;
+    bool linkage = false;            // --linkage: every pair of called variants over the reads covering both (docs/SPEC.md §15)
     bool fuse_only = false;        // invoked as `fuse in.bam out.fasta` (doc/FUSE.md:26-31): the consensus and nothing else
     double ins_min_frac = 0.5;     // an insertion enters the consensus when more than this share of the covering reads carries it
     uint32_t ins_min_distance = 10;  // ... and the previous included insertion lies at least this many columns back (UNPINNED)
@@ -119,6 +120,16 @@ struct Options {
         "                                      haplotype rescued_reads, rescued_read_names and frequency_with_rescued; with\n"
         "                                      --haplotype-fasta the rescued reads join their haplotype's consensus.  Follows\n"
         "                                      --downsample / --mix.  Not with --windows, --devices a,b, --batch or as fuse\n"
+        "      --linkage                       pairwise linkage of the called variants over every read covering both (docs/SPEC.md\n"
+        "                                      section 15), with and without --mode-phasing: read i is informative at a position iff\n"
+        "                                      its three codes there are all < 4; it carries a variant iff it is informative at its\n"
+        "                                      position and its codon there equals the variant's.  The JSON root gains `linkage`:\n"
+        "                                      one entry per pair of variants at different positions with reads_both > 0 — the 2 x 2\n"
+        "                                      table n11 n10 n01 n00 of the reads informative at both, r2, d_prime and the two\n"
+        "                                      one-sided Fisher tests p_positive, p_negative, not Bonferroni-corrected\n"
+        "                                      (n_pairs_tested is there to correct with).  At most 1024 variants at 1024 positions:\n"
+        "                                      beyond, a warning and \"skipped\": true.  Follows --downsample / --mix.  Not with\n"
+        "                                      --windows, --devices a,b, --batch or as fuse\n"
         "      --downsample N [--sample-seed S]  call on N reads of the sample (\"downsample it to 6000x\", doc/JULIETFLOW.md:23-25):\n"
         "                                      the reads are chosen by docs/SPEC.md section 12 (seed default 0; samples of one seed are\n"
         "                                      nested) and gathered on the device; N at or above the read count changes nothing.\n"
@@ -256,6 +267,7 @@ Options parse(int argc, char **argv)
         else if (a == "--consensus") o.consensus = need(i);
         else if (a == "--haplotype-fasta") o.hap_fasta = need(i);
         else if (a == "--rescue-damaged") o.rescue = true;
+        else if (a == "--linkage") o.linkage = true;
         else if (a == "--rescue-min-positions") { o.rescue_min = (uint32_t)std::stoul(need(i)); o.have_rescue_min = true; }
         else if (a == "--ins-min-frac") o.ins_min_frac = std::stod(need(i));
         else if (a == "--ins-min-distance") o.ins_min_distance = (uint32_t)std::stoul(need(i));
@@ -294,6 +306,12 @@ Options parse(int argc, char **argv)
         if (o.rescue_min == 0) refuse("wants at least one informative position (--rescue-min-positions 0)");
         if (as_fuse) refuse("are not options of fuse");
         if (!o.phasing) refuse("assigns reads to the haplotypes of a phasing run (add --mode-phasing)");
+        if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
+        if (!o.batch.empty()) refuse("is not part of a batch (not with --batch)");
+    }
+    if (o.linkage) {   // refused here, before any file is read or any GPU work
+        auto refuse = [](const char *why) { std::cerr << "juliet: --linkage " << why << "\n"; std::exit(1); };
+        if (as_fuse) refuse("is not an option of fuse");
         if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
         if (!o.batch.empty()) refuse("is not part of a batch (not with --batch)");
     }
@@ -685,6 +703,10 @@ struct Results {
     bool rescued = false;
     uint32_t rescue_min = 0;
     std::vector<uint16_t> rescue;
+    // --linkage (docs/SPEC.md §15): the three tables of ONE call over the table's distinct columns and its rows; link_var[k] = the
+    // row of `var` that is variant k of the call (the rows by column: var_pos must not decrease, and genes may overlap)
+    bool linked = false, link_skipped = false;
+    std::vector<uint32_t> link_cols, link_var, link_var_pos, link_both, link_carry, link_joint;
     // the haplotype a damaged read was assigned to, or JL_HAP_DAMAGED; a read that is not damaged: its own id
     uint16_t hap_with_rescued(uint64_t i) const
     {
@@ -1058,6 +1080,39 @@ const char *fetch_rescue(jl_ctx *ctx, uint32_t min_positions, Results &R)
     return nullptr;
 }
 
+// --linkage, after fetch_calls: ONE call of docs/SPEC.md §15 with the table's distinct columns as positions and its rows as variants.
+// No variant: no call.  More than JL_LINK_MAX variants or positions: a warning, no call, the block says "skipped".
+const char *fetch_linkage(jl_ctx *ctx, Results &R)
+{
+    R.linked = true;
+    R.link_skipped = false;
+    const uint32_t V = (uint32_t)R.var.size();
+    R.link_var.resize(V);
+    for (uint32_t k = 0; k < V; ++k) R.link_var[k] = k;
+    std::stable_sort(R.link_var.begin(), R.link_var.end(), [&](uint32_t a, uint32_t b) { return R.var[a].col < R.var[b].col; });
+    R.link_cols.clear();
+    R.link_var_pos.resize(V);
+    std::vector<uint8_t> codon(V);
+    for (uint32_t k = 0; k < V; ++k) {
+        const jl_variant &f = R.var[R.link_var[k]];
+        if (R.link_cols.empty() || R.link_cols.back() != f.col) R.link_cols.push_back(f.col);
+        R.link_var_pos[k] = (uint32_t)R.link_cols.size() - 1u;
+        codon[k] = f.codon;
+    }
+    if (V == 0) return nullptr;
+    const uint32_t P = (uint32_t)R.link_cols.size();
+    if (V > (uint32_t)JL_LINK_MAX || P > (uint32_t)JL_LINK_MAX) {
+        std::cerr << "juliet: warning: --linkage takes at most " << (int)JL_LINK_MAX << " variants at " << (int)JL_LINK_MAX << " positions, the table has " << V
+                  << " at " << P << ": no pair is tested (narrow the table with --min-perc / --max-perc / --region)\n";
+        R.link_skipped = true;
+        return nullptr;
+    }
+    if (jl_variant_linkage_async(ctx, R.link_cols.data(), P, R.link_var_pos.data(), codon.data(), V) != JL_OK) return "linkage";
+    R.link_both.resize((size_t)P * P), R.link_carry.resize((size_t)V * P), R.link_joint.resize((size_t)V * V);
+    if (jl_variant_linkage_fetch(ctx, R.link_both.data(), R.link_carry.data(), R.link_joint.data()) != JL_OK) return "linkage fetch";
+    return nullptr;
+}
+
 // What --downsample / --mix did to a sample: the `sampling` block of the JSON's input section, present only when reads were chosen.
 struct SamplingInfo {
     bool acted = false;
@@ -1334,6 +1389,37 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
                                  .set("incompatible_reads", Json::of((uint32_t)rescue_cat[2]))
                                  .set("uninformative_reads", Json::of((uint32_t)rescue_cat[3])));
         root.set("haplotype", std::move(hb));
+    }
+    if (R.linked) {   // --linkage (docs/SPEC.md §15): one entry per pair of rows v < w at different positions that some read covers both of
+        const uint32_t V = (uint32_t)var.size(), P = (uint32_t)R.link_cols.size();
+        Json lb = Json::object();
+        Json pc = Json::array();
+        for (uint32_t c : R.link_cols) pc.push(Json::of(win_begin + c + 1));
+        lb.set("variant_positions_abs", std::move(pc)).set("n_variants", Json::of(V));
+        Json pairs = Json::array();
+        if (!R.link_skipped && V) {
+            std::vector<uint32_t> at(V);   // row of the table -> variant of the call
+            for (uint32_t k = 0; k < V; ++k) at[R.link_var[k]] = k;
+            auto side = [&](const jl_variant &f) {
+                return Json::object().set("gene", Json::of(cfg.genes[f.gene].name)).set("ref_position", Json::of(f.codon_pos + cfg.genes[f.gene].first_codon))
+                    .set("codon", Json::of(codon_string(f.codon)));
+            };
+            for (uint32_t v = 0; v < V; ++v)
+                for (uint32_t w = v + 1; w < V; ++w) {
+                    if (var[v].col == var[w].col) continue;
+                    jl_link_pair lp;
+                    if (jl_linkage_stats(R.link_both.data(), R.link_carry.data(), R.link_joint.data(), R.link_var_pos.data(), P, V, at[v], at[w], &lp) != JL_OK)
+                        die_jl(nullptr, "linkage statistics");
+                    if (lp.n == 0) continue;
+                    pairs.push(Json::object().set("a", side(var[v])).set("b", side(var[w])).set("reads_both", Json::of(lp.n))
+                                   .set("n11", Json::of(lp.n11)).set("n10", Json::of(lp.n10)).set("n01", Json::of(lp.n01)).set("n00", Json::of(lp.n00))
+                                   .set("r2", Json::of(lp.r2)).set("d_prime", Json::of(lp.d_prime))
+                                   .set("p_positive", Json::of(lp.p_positive)).set("p_negative", Json::of(lp.p_negative)));
+                }
+        }
+        lb.set("n_pairs_tested", Json::of((uint32_t)pairs.arr.size())).set("pairs", std::move(pairs));
+        if (R.link_skipped) lb.set("skipped", Json::of(true));
+        root.set("linkage", std::move(lb));
     }
     return root;
 }
@@ -1998,6 +2084,10 @@ int main(int argc, char **argv)
         if (opt.rescue) {
             if (const char *what = fetch_rescue(ctx, opt.rescue_min, R)) die_jl(ctx, what);
             tick("rescue");
+        }
+        if (opt.linkage) {
+            if (const char *what = fetch_linkage(ctx, R)) die_jl(ctx, what);
+            tick("linkage");
         }
         if (!opt.hap_fasta.empty()) {
             if (const int code = write_haplotype_fasta(opt, ctx, R, win_begin, n_cols)) return code;
