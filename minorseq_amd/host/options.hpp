@@ -1,0 +1,355 @@
+// options.hpp — the command line of `juliet` / `fuse`: Options, the usage text, parse() with everything it refuses before any
+// file is read or any GPU work starts, and the --batch list (read_batch_list, output_kind_ok).  Like the headers below it, a part
+// of juliet_main.cpp's one translation unit: internal linkage, as in the file it was cut from.
+#pragma once
+#include <cstdlib>
+#include <filesystem>
+#include <fstream>
+#include <iostream>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "../../include/juliet_hip.h"
+
+namespace jlhost {
+namespace {
+
+const char *kVersion = "0.1.0 (minorseq_amd, MI355X)";
+
+struct Options {
+    std::string bam, config;
+    std::vector<std::string> outputs;
+    bool phasing = false, drm_only = false;
+    bool have_region = false;
+    uint32_t region_b = 0, region_e = 0;
+    double min_perc = -1.0, max_perc = -1.0;
+    double alpha = 0.01, n_tests = 0.0;
+    std::string chemistry = "auto";
+    double match = -1.0, substitution = -1.0;
+    int expected_round = 0;
+    int fisher_tail = 0;             // --fisher-tail greater|two-sided (doc/JULIET.md:38-42 leaves the sidedness open)
+    uint32_t min_reads = 10, min_qv = 0;
+    bool qv_upload_mask = false;     // --qv-upload mask|bytes: what --min-qv sends to the device (bytes: DESIGN.md, the record ingest)
+    double min_rq = 0.0;
+    int device = 0;
+    uint32_t windows = 1;            // column windows the reference is cut into (doc/JULIET.md:261-264: the split never shows)
+    std::vector<int> devices;        // --devices a,b,...: one rank (thread) per device, consecutive windows each
+    std::string dump_msa, dump_config, consensus;
+    std::string hap_fasta;           // --haplotype-fasta: one consensus per reported haplotype (docs/SPEC.md §13)
+    bool rescue = false;             // --rescue-damaged: which reported haplotype each damaged read agrees with (docs/SPEC.md §14)
+    uint32_t rescue_min = 1;         // --rescue-min-positions K: informative positions a read needs to be judged at all
+    bool have_rescue_min = false;
+    bool linkage = false;            // --linkage: every pair of called variants over the reads covering both (docs/SPEC.md §15)
+    bool fuse_only = false;        // invoked as `fuse in.bam out.fasta` (doc/FUSE.md:26-31): the consensus and nothing else
+    double ins_min_frac = 0.5;     // an insertion enters the consensus when more than this share of the covering reads carries it
+    uint32_t ins_min_distance = 10;  // ... and the previous included insertion lies at least this many columns back (UNPINNED)
+    bool timing = false;
+    std::string exchange;            // --exchange rccl|inproc: how the rank threads exchange (default: rccl, inproc when a device repeats)
+    // Sampling (docs/SPEC.md §12): the window is ingested whole, then replaced by chosen reads of it on the device (jl_msa_take)
+    bool have_downsample = false;
+    uint64_t downsample = 0;         // --downsample N: keep N reads (with --mix: the mixture's coverage, default 3000 as mixdata's COVERAGE)
+    uint64_t sample_seed = 0;        // --sample-seed S (source m of a mixture is sampled with S + m)
+    std::vector<std::string> mix;    // --mix b.bam[,c.bam...]: the minor clones; the positional BAM is the major one (doc/MIXDATA.md)
+    double mix_perc = 1.0;           // --mix-perc P: percent of the mixture each minor clone gets
+    bool sampling() const { return have_downsample || !mix.empty(); }
+    std::string batch;               // --batch samples.tsv: one `in.bam<TAB>out1[<TAB>out2]` per line, every other option for all of them
+    struct BatchLine { unsigned line; std::string bam; std::vector<std::string> outputs; };
+    std::vector<BatchLine> batch_lines;
+};
+
+[[noreturn]] void usage(int code)
+{
+    std::cerr <<
+        "juliet " << kVersion << "\n"
+        "usage: juliet [options] in.align.bam out.json|out.html [second output]\n"
+        "       juliet [options] --batch samples.tsv\n"
+        "  -c, --config <HIV|ABL1|file.json>   target config (doc/JULIET.md:109-180)\n"
+        "  -p, --mode-phasing                  cluster reads into haplotypes (doc/JULIET.md:192-211)\n"
+        "  -r, --region <begin-end>            1-based [begin,end) window of the config to call\n"
+        "      --min-perc <x> / --max-perc <x> only calls above / below x percent\n"
+        "  -k, --drm-only                      only known DRM positions of the config\n"
+        "  parameters the reference text leaves open (docs/SPEC.md):\n"
+        "      --alpha 0.01  --n-tests <auto>  --chemistry auto|sequel|permissive\n"
+        "      --match-rate <r> --substitution-rate <r> --expected-round ceil|floor|nearest\n"
+        "      --fisher-tail greater|two-sided  sidedness of Fisher's exact test (default greater: an excess of observed codons)\n"
+        "      --min-reads 10  --min-qv 0  --min-rq 0  --device 0\n"
+        "      --qv-upload mask|bytes          what --min-qv sends to the device: the filter decided while decoding, one bit per\n"
+        "                                      base, or the folded qualities, one byte per base, and the threshold (default);\n"
+        "                                      the same output\n"
+        "      --windows K [--devices a,b,...] cut the reference into K column windows (2-column overlap, global Bonferroni\n"
+        "                                      factor), consecutive windows per device; phasing runs across the windows with\n"
+        "                                      the reads sharded over the devices.  The output is that of one window.\n"
+        "      --exchange rccl|inproc          how the rank threads exchange: RCCL (default), or device copies between the ranks'\n"
+        "                                      buffers (peer copies over xGMI; the default when a device is named twice,\n"
+        "                                      which RCCL refuses)\n"
+        "      --consensus <out.fasta>         also write the window's consensus as `fuse` would (doc/FUSE.md:17-20):\n"
+        "                                      majority base, major deletions removed, in-frame majority insertions kept\n"
+        "      --ins-min-frac 0.5  --ins-min-distance 10   when an insertion enters the consensus\n"
+        "      --haplotype-fasta <out.fasta>   with --mode-phasing: one consensus record per reported haplotype, in the JSON's\n"
+        "                                      order, from the column pileup of that haplotype's reads alone (docs/SPEC.md section\n"
+        "                                      13): majority base, major deletions removed, N where none of its reads covers the\n"
+        "                                      column.  Insertions are not included (their counters are per window, not per\n"
+        "                                      read).  Follows --downsample / --mix.  Not with --windows, --devices a,b, --batch\n"
+        "                                      or as fuse\n"
+        "      --rescue-damaged [--rescue-min-positions K]  with --mode-phasing: every damaged read (a deletion, a filtered N or an\n"
+        "                                      uncovered cell at some variant position) is compared with the reported haplotypes at\n"
+        "                                      the positions where it can be read, K of them at least (default 1; docs/SPEC.md\n"
+        "                                      section 14): it is assigned to the one haplotype that agrees there, or counted as\n"
+        "                                      ambiguous, incompatible or uninformative.  The haplotype block gains `rescue`, every\n"
+        "                                      haplotype rescued_reads, rescued_read_names and frequency_with_rescued; with\n"
+        "                                      --haplotype-fasta the rescued reads join their haplotype's consensus.  Follows\n"
+        "                                      --downsample / --mix.  Not with --windows, --devices a,b, --batch or as fuse\n"
+        "      --linkage                       pairwise linkage of the called variants over every read covering both (docs/SPEC.md\n"
+        "                                      section 15), with and without --mode-phasing: read i is informative at a position iff\n"
+        "                                      its three codes there are all < 4; it carries a variant iff it is informative at its\n"
+        "                                      position and its codon there equals the variant's.  The JSON root gains `linkage`:\n"
+        "                                      one entry per pair of variants at different positions with reads_both > 0 — the 2 x 2\n"
+        "                                      table n11 n10 n01 n00 of the reads informative at both, r2, d_prime and the two\n"
+        "                                      one-sided Fisher tests p_positive, p_negative, not Bonferroni-corrected\n"
+        "                                      (n_pairs_tested is there to correct with).  At most 1024 variants at 1024 positions:\n"
+        "                                      beyond, a warning and \"skipped\": true.  Follows --downsample / --mix.  Not with\n"
+        "                                      --windows, --devices a,b, --batch or as fuse\n"
+        "      --downsample N [--sample-seed S]  call on N reads of the sample (\"downsample it to 6000x\", doc/JULIETFLOW.md:23-25):\n"
+        "                                      the reads are chosen by docs/SPEC.md section 12 (seed default 0; samples of one seed are\n"
+        "                                      nested) and gathered on the device; N at or above the read count changes nothing.\n"
+        "                                      With --batch: every sample.  Not with --windows, --devices a,b or --consensus\n"
+        "      --mix b.bam[,c.bam...] [--mix-perc P]  a mixture as mixdata makes it (doc/MIXDATA.md): in.bam is the major clone, every\n"
+        "                                      listed BAM a minor clone with P percent (default 1) of --downsample C reads (default\n"
+        "                                      3000); source m is sampled with seed S + m.  A source with too few reads is an input\n"
+        "                                      error (2).  Not with --batch, --windows, --devices a,b or --consensus\n"
+        "      --batch <samples.tsv>           many samples in one process: one `in.bam<TAB>out1[<TAB>out2]` per line (blank lines\n"
+        "                                      and lines starting with # skipped); every other option applies to every sample and\n"
+        "                                      each sample gets the files a single run would write.  A sample that fails is named\n"
+        "                                      on stderr and the others go on (exit status 2 if any failed); a GPU error stops\n"
+        "                                      the batch (3).  Not with --windows, --devices a,b, --consensus or --dump-*\n"
+        "      --timing                        wall time of each stage on stderr\n"
+        "  diagnostics (no GPU needed): --dump-msa <file>  --dump-config <file>\n";
+    std::exit(code);
+}
+
+bool output_kind_ok(const std::string &out)   // the outputs are told apart by their extension (doc/JULIET.md:61-66)
+{
+    return out.size() > 5 && (out.substr(out.size() - 5) == ".json" || out.substr(out.size() - 5) == ".html");
+}
+
+// The --batch list: `in.bam<TAB>out1[<TAB>out2 ...]` per line; blank lines and lines starting with # are skipped.  Anything
+// wrong with it ends the process with status 1 before any BAM is read.
+std::vector<Options::BatchLine> read_batch_list(const std::string &path)
+{
+    auto bad = [&](unsigned line, const std::string &why) {
+        std::cerr << "juliet: --batch " << path;
+        if (line) std::cerr << " line " << line;
+        std::cerr << ": " << why << "\n";
+        std::exit(1);
+    };
+    std::error_code ec;
+    if (std::filesystem::is_directory(path, ec)) bad(0, "is a directory");
+    std::ifstream f(path);
+    if (!f) bad(0, "cannot be read");
+    std::vector<Options::BatchLine> lines;
+    std::map<std::string, unsigned> written;   // output path (absolute, normalised) -> the line that names it
+    std::string text;
+    unsigned no = 0;
+    while (std::getline(f, text)) {
+        ++no;
+        if (!text.empty() && text.back() == '\r') text.pop_back();
+        if (text.find_first_not_of(" \t") == std::string::npos || text[0] == '#') continue;
+        std::vector<std::string> fields;
+        for (size_t b = 0;;) {
+            const size_t e = text.find('\t', b);
+            fields.push_back(text.substr(b, e == std::string::npos ? std::string::npos : e - b));
+            if (e == std::string::npos) break;
+            b = e + 1;
+        }
+        if (fields.size() < 2) bad(no, "wants an input BAM and at least one output, separated by tabs");
+        for (const std::string &fld : fields)
+            if (fld.empty()) bad(no, "has an empty field");
+        Options::BatchLine l{no, fields[0], std::vector<std::string>(fields.begin() + 1, fields.end())};
+        for (const std::string &out : l.outputs) {
+            if (!output_kind_ok(out)) bad(no, "output '" + out + "' must end in .json or .html (doc/JULIET.md:61-66)");
+            const std::string key = std::filesystem::absolute(out, ec).lexically_normal().string();
+            const auto it = written.find(key);
+            if (it != written.end())
+                bad(no, "output '" + out + "' is also written by line " + std::to_string(it->second) + " (every output once)");
+            written.emplace(key, no);
+        }
+        lines.push_back(std::move(l));
+    }
+    if (f.bad()) bad(0, "cannot be read");
+    if (lines.empty()) bad(0, "names no sample");
+    return lines;
+}
+
+Options parse(int argc, char **argv)
+{
+    Options o;
+    auto need = [&](int &i) -> std::string {
+        if (i + 1 >= argc) { std::cerr << "juliet: " << argv[i] << " needs a value\n"; usage(1); }
+        return argv[++i];
+    };
+    std::vector<std::string> pos;
+    for (int i = 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        if (a == "-h" || a == "--help") usage(0);
+        else if (a == "--version") { std::cout << kVersion << "\n"; std::exit(0); }
+        else if (a == "-c" || a == "--config") o.config = need(i);
+        else if (a == "-p" || a == "--mode-phasing") o.phasing = true;
+        else if (a == "-k" || a == "--drm-only") o.drm_only = true;
+        else if (a == "-r" || a == "--region") {
+            const std::string v = need(i);
+            const size_t d = v.find('-');
+            if (d == std::string::npos) { std::cerr << "juliet: --region wants begin-end\n"; usage(1); }
+            o.region_b = (uint32_t)std::stoul(v.substr(0, d));
+            o.region_e = (uint32_t)std::stoul(v.substr(d + 1));
+            o.have_region = true;
+        }
+        else if (a == "--min-perc") o.min_perc = std::stod(need(i));
+        else if (a == "--max-perc") o.max_perc = std::stod(need(i));
+        else if (a == "--alpha") o.alpha = std::stod(need(i));
+        else if (a == "--n-tests") o.n_tests = std::stod(need(i));
+        else if (a == "--chemistry") o.chemistry = need(i);
+        else if (a == "--match-rate") o.match = std::stod(need(i));
+        else if (a == "--substitution-rate") o.substitution = std::stod(need(i));
+        else if (a == "--expected-round") {
+            const std::string v = need(i);
+            o.expected_round = v == "floor" ? 1 : v == "nearest" ? 2 : 0;
+        }
+        else if (a == "--fisher-tail") {
+            const std::string v = need(i);
+            if (v == "greater") o.fisher_tail = 0;
+            else if (v == "two-sided") o.fisher_tail = 1;
+            else { std::cerr << "juliet: --fisher-tail takes greater or two-sided\n"; usage(1); }
+        }
+        else if (a == "--min-reads") o.min_reads = (uint32_t)std::stoul(need(i));
+        else if (a == "--min-qv") o.min_qv = (uint32_t)std::stoul(need(i));
+        else if (a == "--qv-upload") {
+            const std::string v = need(i);
+            if (v != "mask" && v != "bytes") { std::cerr << "juliet: --qv-upload takes mask or bytes\n"; usage(1); }
+            o.qv_upload_mask = v == "mask";
+        }
+        else if (a == "--min-rq") o.min_rq = std::stod(need(i));
+        else if (a == "--device") o.device = std::stoi(need(i));
+        else if (a == "--windows") o.windows = (uint32_t)std::stoul(need(i));
+        else if (a == "--exchange") {
+            o.exchange = need(i);
+            if (o.exchange != "rccl" && o.exchange != "inproc") { std::cerr << "juliet: --exchange wants rccl or inproc\n"; usage(1); }
+        }
+        else if (a == "--devices") {
+            const std::string v = need(i);
+            size_t b = 0;
+            while (b <= v.size()) {
+                const size_t e = std::min(v.find(',', b), v.size());
+                if (e > b) o.devices.push_back(std::stoi(v.substr(b, e - b)));
+                b = e + 1;
+            }
+        }
+        else if (a == "--consensus") o.consensus = need(i);
+        else if (a == "--haplotype-fasta") o.hap_fasta = need(i);
+        else if (a == "--rescue-damaged") o.rescue = true;
+        else if (a == "--linkage") o.linkage = true;
+        else if (a == "--rescue-min-positions") { o.rescue_min = (uint32_t)std::stoul(need(i)); o.have_rescue_min = true; }
+        else if (a == "--ins-min-frac") o.ins_min_frac = std::stod(need(i));
+        else if (a == "--ins-min-distance") o.ins_min_distance = (uint32_t)std::stoul(need(i));
+        else if (a == "--dump-msa") o.dump_msa = need(i);
+        else if (a == "--dump-config") o.dump_config = need(i);
+        else if (a == "--timing") o.timing = true;
+        else if (a == "--batch") o.batch = need(i);
+        else if (a == "--downsample") { o.downsample = std::stoull(need(i)); o.have_downsample = true; }
+        else if (a == "--sample-seed") o.sample_seed = std::stoull(need(i));
+        else if (a == "--mix") {
+            const std::string v = need(i);
+            for (size_t b = 0; b <= v.size();) {
+                const size_t e = std::min(v.find(',', b), v.size());
+                if (e > b) o.mix.push_back(v.substr(b, e - b));
+                b = e + 1;
+            }
+            if (o.mix.empty()) { std::cerr << "juliet: --mix names no BAM\n"; std::exit(1); }
+        }
+        else if (a == "--mix-perc") o.mix_perc = std::stod(need(i));
+        else if (!a.empty() && a[0] == '-') { std::cerr << "juliet: unknown option " << a << "\n"; usage(1); }
+        else pos.push_back(a);
+    }
+    const std::string prog = argv[0];
+    const size_t slash = prog.find_last_of('/');
+    const bool as_fuse = (slash == std::string::npos ? prog : prog.substr(slash + 1)) == "fuse";
+    if (!o.hap_fasta.empty()) {   // refused here, before any file is read or any GPU work
+        auto refuse = [](const char *why) { std::cerr << "juliet: --haplotype-fasta " << why << "\n"; std::exit(1); };
+        if (as_fuse) refuse("is not an option of fuse");
+        if (!o.phasing) refuse("writes the haplotypes of a phasing run (add --mode-phasing)");
+        if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
+        if (!o.batch.empty()) refuse("writes one file for one sample (not with --batch)");
+    }
+    if (o.rescue || o.have_rescue_min) {   // refused here, before any file is read or any GPU work
+        auto refuse = [](const char *why) { std::cerr << "juliet: --rescue-damaged [--rescue-min-positions K] " << why << "\n"; std::exit(1); };
+        if (!o.rescue) refuse("--rescue-min-positions sets a threshold of --rescue-damaged (add it)");
+        if (o.rescue_min == 0) refuse("wants at least one informative position (--rescue-min-positions 0)");
+        if (as_fuse) refuse("are not options of fuse");
+        if (!o.phasing) refuse("assigns reads to the haplotypes of a phasing run (add --mode-phasing)");
+        if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
+        if (!o.batch.empty()) refuse("is not part of a batch (not with --batch)");
+    }
+    if (o.linkage) {   // refused here, before any file is read or any GPU work
+        auto refuse = [](const char *why) { std::cerr << "juliet: --linkage " << why << "\n"; std::exit(1); };
+        if (as_fuse) refuse("is not an option of fuse");
+        if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
+        if (!o.batch.empty()) refuse("is not part of a batch (not with --batch)");
+    }
+    if (o.sampling()) {   // what sampling cannot be combined with is refused here, before any file is read or any GPU work
+        auto refuse = [&](const char *why) { std::cerr << "juliet: " << (o.mix.empty() ? "--downsample " : "--mix ") << why << "\n"; std::exit(1); };
+        if (o.have_downsample && o.downsample == 0) refuse("wants at least one read (--downsample 0)");
+        if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
+        if (!o.consensus.empty() || as_fuse) refuse("carries no insertion counters into the sample: no consensus (drop --consensus)");
+        if (!o.mix.empty()) {
+            if (!o.batch.empty()) refuse("mixes into one sample (not with --batch)");
+            if (o.mix.size() + 1 > (size_t)JL_TAKE_MAX_PARTS) refuse("takes at most 15 minor clones");
+            if (!o.have_downsample) o.downsample = 3000;   // mixdata's COVERAGE (doc/MIXDATA.md)
+            std::vector<uint64_t> counts(o.mix.size() + 1);
+            if (jl_mix_counts((uint32_t)counts.size(), o.downsample, o.mix_perc, counts.data()) != JL_OK)
+                refuse("wants --mix-perc inside (0, 100) and minor clones that together stay within the coverage");
+        }
+    }
+    if (!o.batch.empty()) {   // everything a batch cannot do is refused here, before any file is read or any GPU work
+        auto refuse = [](const char *why) { std::cerr << "juliet: --batch " << why << "\n"; std::exit(1); };
+        if (as_fuse) refuse("is not an option of fuse");
+        if (!pos.empty()) refuse("takes no input BAM or outputs on the command line: they are the lines of the list");
+        if (o.windows > 1) refuse("runs one window per sample (drop --windows)");
+        if (o.devices.size() > 1) refuse("runs on one device (--device, not a --devices list)");
+        if (!o.consensus.empty()) refuse("writes no consensus (drop --consensus)");
+        if (!o.dump_msa.empty() || !o.dump_config.empty()) refuse("does not combine with --dump-msa or --dump-config");
+        if (!o.devices.empty()) o.device = o.devices[0];
+        o.devices.assign(1, o.device);
+        o.batch_lines = read_batch_list(o.batch);
+        return o;
+    }
+    if (!o.dump_config.empty() && pos.empty()) { if (o.devices.empty()) o.devices.push_back(o.device); return o; }
+    {   // `fuse in.bam out.fasta` (doc/FUSE.md:26-31): the same front end, asked for the consensus only
+        if (as_fuse) {
+            if (pos.size() != 2) { std::cerr << "fuse: usage: fuse in.align.bam out.fasta\n"; std::exit(1); }
+            o.bam = pos[0];
+            o.consensus = pos[1];
+            o.fuse_only = true;
+            o.devices.assign(1, o.device);
+            o.windows = 1;
+            return o;
+        }
+    }
+    if (o.devices.empty()) o.devices.push_back(o.device);
+    if (o.windows == 0 || o.windows > 32u * o.devices.size()) { std::cerr << "juliet: --windows wants 1 .. 32 per device\n"; usage(1); }
+    if (o.windows < o.devices.size()) { std::cerr << "juliet: fewer windows than devices\n"; usage(1); }
+    if ((o.windows > 1 || o.devices.size() > 1) && !o.consensus.empty()) {
+        std::cerr << "juliet: --consensus works on one window (drop --windows / --devices)\n";
+        usage(1);
+    }
+    if (pos.size() < 2 && o.dump_msa.empty()) { std::cerr << "juliet: need an input BAM and at least one output\n"; usage(1); }
+    if (pos.empty()) usage(1);
+    o.bam = pos[0];
+    o.outputs.assign(pos.begin() + 1, pos.end());
+    for (const std::string &out : o.outputs) {
+        if (!output_kind_ok(out)) { std::cerr << "juliet: output '" << out << "' must end in .json or .html (doc/JULIET.md:61-66)\n"; usage(1); }
+    }
+    return o;
+}
+
+}  // namespace
+}  // namespace jlhost

@@ -1,0 +1,333 @@
+// report.hpp — what a run writes: the JSON document of one sample (build_json; the HTML output is its rendering, html.hpp),
+// every output file closed and checked (write_outputs), the --haplotype-fasta records and the consensus FASTA of --consensus / fuse.
+#pragma once
+#include <chrono>
+#include <ctime>
+#include <fstream>
+
+#include "fuse.hpp"
+#include "html.hpp"
+#include "sample.hpp"
+
+namespace jlhost {
+namespace {
+
+std::string iso_now()
+{
+    using namespace std::chrono;
+    const auto now = system_clock::now();
+    const std::time_t t = system_clock::to_time_t(now);
+    const int ms = (int)(duration_cast<milliseconds>(now.time_since_epoch()).count() % 1000);
+    std::tm tm;
+    gmtime_r(&t, &tm);
+    char buf[80];
+    snprintf(buf, sizeof buf, "%04d-%02d-%02dT%02d:%02d:%02d.%03dZ", tm.tm_year + 1900, tm.tm_mon + 1, tm.tm_mday,
+             tm.tm_hour, tm.tm_min, tm.tm_sec, ms);
+    return buf;
+}
+
+std::string haplotype_name(uint32_t h)  // [A-Z]{1}[a-z]?  (doc/JULIET.md:198)
+{
+    if (h < 26) return std::string(1, (char)('A' + h));
+    h -= 26;
+    return std::string{(char)('A' + h / 26), (char)('a' + h % 26)};
+}
+
+// The JSON document of one sample (doc/JULIET.md:61-107, 207-211); the HTML output is its rendering.
+Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam, const std::string &cmdline,
+                const std::vector<std::string> &names, uint64_t n_reads, const Results &R, const SamplingInfo *sampling = nullptr)
+{
+    const TargetConfig &cfg = s.cfg;
+    const uint32_t win_begin = s.win_begin, n_cols = s.n_cols;
+    const std::string &chem = s.chem;
+    const std::vector<jl_variant> &var = R.var;
+    const std::vector<uint32_t> &col_counts = R.col_counts;
+    const jl_phase_summary &ps = R.ps;
+    const std::vector<uint32_t> &pos_cols = R.pos_cols, &hap_count = R.hap_count;
+    const std::vector<uint8_t> &hap_pattern = R.hap_pattern, &hit = R.hit;
+    const std::vector<uint16_t> &read_hap = R.read_hap;
+
+    Json root = Json::object();
+    root.set("input", Json::object()
+                          .set("timestamp", Json::of(iso_now()))
+                          .set("input_file", Json::of(bam))
+                          .set("command_line", Json::of(cmdline))
+                          .set("juliet_version", Json::of(kVersion)));
+    if (sampling && sampling->acted) {   // (only then: a run whose flags chose nothing writes what a run without them writes)
+        Json srcs = Json::array();
+        for (const SamplingInfo::Source &x : sampling->sources)
+            srcs.push(Json::object().set("file", Json::of(x.file)).set("reads", Json::of((int64_t)x.reads)).set("kept", Json::of((int64_t)x.kept)));
+        Json sj = Json::object();
+        sj.set("seed", Json::of((int64_t)sampling->seed)).set("sources", std::move(srcs));
+        root.obj.back().second.set("sampling", std::move(sj));
+    }
+    Json tc = cfg.echo();
+    tc.set("n_reads", Json::of((int64_t)n_reads));
+    tc.set("window_begin", Json::of(win_begin + 1)).set("window_end", Json::of(win_begin + n_cols + 1));
+    tc.set("chemistry_model", Json::of(chem));
+    root.set("target_config", tc);
+
+    Json genes_json = Json::array();
+    const uint32_t H = ps.n_haplotypes;
+    for (size_t g = 0; g < cfg.genes.size(); ++g) {
+        Json gj = Json::object();
+        gj.set("name", Json::of(cfg.genes[g].name));
+        Json vps = Json::array();
+        size_t v = 0;
+        while (v < var.size()) {
+            if (var[v].gene != g) { ++v; continue; }
+            size_t e = v;
+            while (e < var.size() && var[e].gene == g && var[e].codon_pos == var[v].codon_pos) ++e;
+            const jl_variant &f = var[v];
+            Json vp = Json::object();
+            vp.set("ref_codon", Json::of(codon_string(f.ref_codon)));
+            vp.set("ref_amino_acid", Json::of(std::string(1, translate(f.ref_codon))));
+            const uint32_t aa_pos = f.codon_pos + cfg.genes[g].first_codon;
+            vp.set("ref_position", Json::of(aa_pos));
+            vp.set("coverage", Json::of(f.coverage));
+            // variant codons grouped by amino acid (position 223 with two rows)
+            Json aas = Json::array();
+            std::vector<char> order;
+            for (size_t k = v; k < e; ++k) {
+                const char aa = translate(var[k].codon);
+                if (std::find(order.begin(), order.end(), aa) == order.end()) order.push_back(aa);
+            }
+            // amino acids in alphabetical order: juliet_abl-nohaplotype.png prints "A GCC" above "P CCA" at ABL1 223
+            std::sort(order.begin(), order.end());
+            for (char aa : order) {
+                Json aj = Json::object();
+                aj.set("amino_acid", Json::of(std::string(1, aa)));
+                Json cods = Json::array();
+                for (size_t k = v; k < e; ++k) {
+                    if (translate(var[k].codon) != aa) continue;
+                    Json cj = Json::object();
+                    cj.set("codon", Json::of(codon_string(var[k].codon)));
+                    cj.set("frequency", Json::of((double)var[k].count / (double)var[k].coverage));
+                    cj.set("count", Json::of(var[k].count));
+                    cj.set("expected", Json::of(var[k].expected));
+                    cj.set("pValue", Json::of(var[k].p_value));
+                    cj.set("log_pValue", Json::of(var[k].log_p));
+                    cj.set("known_drm", Json::of(cfg.known_drms(g, aa_pos, aa)));
+                    if (opt.phasing) {
+                        Json hh = Json::array();
+                        for (uint32_t h = 0; h < H; ++h) hh.push(Json::of(hit[(size_t)k * R.hit_stride + h] != 0));
+                        cj.set("haplotype_hit", hh);  // doc/JULIET.md:207-209
+                    }
+                    cods.push(cj);
+                }
+                aj.set("variant_codons", cods);
+                aas.push(aj);
+            }
+            vp.set("variant_amino_acids", aas);
+            // MSA context: -3 .. +5 around the codon's first base (doc/JULIET.md:99-100)
+            Json msa = Json::array();
+            for (int rel = -3; rel <= 5; ++rel) {
+                const int64_t c = (int64_t)f.col + rel;
+                if (c < 0 || c >= (int64_t)n_cols) continue;
+                const uint32_t *cc = &col_counts[(size_t)c * 6];
+                Json mj = Json::object();
+                mj.set("rel_pos", Json::of((int64_t)rel)).set("abs_pos", Json::of((int64_t)(win_begin + c + 1)));
+                static const char *sym[6] = {"A", "C", "G", "T", "-", "N"};
+                for (int s = 0; s < 6; ++s) mj.set(sym[s], Json::of(cc[s]));
+                const size_t r = (size_t)win_begin + (size_t)c;
+                if (r < cfg.reference_sequence.size()) mj.set("wt", Json::of(std::string(1, (char)std::toupper((unsigned char)cfg.reference_sequence[r]))));
+                msa.push(mj);
+            }
+            vp.set("msa", msa);
+            vps.push(vp);
+            v = e;
+        }
+        gj.set("variant_positions", vps);
+        genes_json.push(gj);
+    }
+    root.set("genes", genes_json);
+
+    // Section 4, drug summaries: variants grouped by annotated drug (doc/JULIET.md:104-107)
+    {
+        std::vector<std::pair<std::string, Json>> by_drug;
+        for (const jl_variant &f : var) {
+            const GeneCfg &g = cfg.genes[f.gene];
+            const uint32_t aa_pos = f.codon_pos + g.first_codon;
+            const char aa = translate(f.codon);
+            for (const Drm &d : g.drms) {
+                bool hit_drm = false;
+                for (const DrmPosition &dp : d.positions) hit_drm = hit_drm || dp.matches(aa_pos, aa);
+                if (!hit_drm) continue;
+                Json e = Json::object();
+                e.set("gene", Json::of(g.name));
+                e.set("mutation", Json::of(std::string(1, translate(f.ref_codon)) + std::to_string(aa_pos) + std::string(1, aa)));
+                e.set("codon", Json::of(codon_string(f.codon)));
+                e.set("frequency", Json::of((double)f.count / (double)f.coverage));
+                auto it = std::find_if(by_drug.begin(), by_drug.end(), [&](const std::pair<std::string, Json> &kv) { return kv.first == d.name; });
+                if (it == by_drug.end()) { by_drug.emplace_back(d.name, Json::array()); it = by_drug.end() - 1; }
+                it->second.push(e);
+            }
+        }
+        Json ds = Json::array();
+        for (auto &kv : by_drug) ds.push(Json::object().set("drug", Json::of(kv.first)).set("variants", kv.second));
+        root.set("drug_summaries", ds);
+    }
+
+    if (opt.phasing) {  // root `haplotype` block: counts and read names, same order as haplotype_hit (doc/JULIET.md:209-211)
+        Json hb = Json::object();
+        hb.set("reported_reads", Json::of(ps.reported_reads)).set("insufficient_coverage_reads", Json::of(ps.insufficient_reads));
+        hb.set("damaged_reads", Json::of(ps.damaged_reads)).set("marginal_gaps", Json::of(ps.marginal_gap));
+        hb.set("marginal_heteroduplexes", Json::of(ps.marginal_heteroduplex)).set("marginal_partial", Json::of(ps.marginal_partial));
+        std::vector<std::vector<uint32_t>> members(H);
+        for (uint64_t i = 0; i < n_reads; ++i)
+            if (read_hap[i] < H) members[read_hap[i]].push_back((uint32_t)i);
+        // --rescue-damaged: the damaged reads by what the rule of docs/SPEC.md §14 says of them
+        std::vector<std::vector<uint32_t>> rescued_members(H);
+        uint64_t rescue_cat[4] = {0, 0, 0, 0};   // assigned, ambiguous, incompatible, uninformative
+        uint64_t with_rescued_total = 0;
+        if (R.rescued && ps.n_positions) {   // (no variant position: nothing was phased, no read is damaged, §8)
+            for (uint64_t i = 0; i < n_reads; ++i) {
+                if (read_hap[i] != (uint16_t)JL_HAP_DAMAGED) continue;
+                const uint32_t r = R.rescue.empty() ? (uint32_t)JL_RESCUE_UNINFORMATIVE : R.rescue[i];
+                if (r < H) rescued_members[r].push_back((uint32_t)i), rescue_cat[0]++;
+                else rescue_cat[r == (uint32_t)JL_RESCUE_AMBIGUOUS ? 1 : r == (uint32_t)JL_RESCUE_NONE ? 2 : 3]++;
+            }
+            for (uint32_t h = 0; h < H; ++h) with_rescued_total += (uint64_t)hap_count[h] + rescued_members[h].size();
+        }
+        Json hs = Json::array();
+        for (uint32_t h = 0; h < H; ++h) {
+            Json hj = Json::object();
+            hj.set("name", Json::of(haplotype_name(h))).set("reads", Json::of(hap_count[h]));
+            hj.set("frequency", Json::of(ps.reported_reads ? (double)hap_count[h] / (double)ps.reported_reads : 0.0));
+            Json cods = Json::array();
+            for (uint32_t p = 0; p < ps.n_positions; ++p) cods.push(Json::of(codon_string(hap_pattern[(size_t)h * R.pat_stride + p])));
+            hj.set("codons", std::move(cods));
+            Json rn = Json::array();      // (moved on, level by level: a copy of this list per level was most of the stage at a million reads)
+            rn.arr.reserve(members[h].size());
+            for (uint32_t i : members[h]) rn.push(Json::of(names[i]));
+            hj.set("read_names", std::move(rn));
+            if (R.rescued) {
+                const uint64_t with = (uint64_t)hap_count[h] + rescued_members[h].size();
+                hj.set("rescued_reads", Json::of((uint32_t)rescued_members[h].size()));
+                Json rr = Json::array();
+                rr.arr.reserve(rescued_members[h].size());
+                for (uint32_t i : rescued_members[h]) rr.push(Json::of(names[i]));
+                hj.set("rescued_read_names", std::move(rr));
+                hj.set("frequency_with_rescued", Json::of(with_rescued_total ? (double)with / (double)with_rescued_total : 0.0));
+            }
+            hs.push(std::move(hj));
+        }
+        hb.set("haplotypes", std::move(hs));
+        Json pc = Json::array();
+        for (uint32_t p = 0; p < ps.n_positions; ++p) pc.push(Json::of(win_begin + pos_cols[p] + 1));
+        hb.set("variant_positions_abs", std::move(pc));
+        if (R.rescued)
+            hb.set("rescue", Json::object()
+                                 .set("min_positions", Json::of(R.rescue_min))
+                                 .set("assigned_reads", Json::of((uint32_t)rescue_cat[0]))
+                                 .set("ambiguous_reads", Json::of((uint32_t)rescue_cat[1]))
+                                 .set("incompatible_reads", Json::of((uint32_t)rescue_cat[2]))
+                                 .set("uninformative_reads", Json::of((uint32_t)rescue_cat[3])));
+        root.set("haplotype", std::move(hb));
+    }
+    if (R.linked) {   // --linkage (docs/SPEC.md §15): one entry per pair of rows v < w at different positions that some read covers both of
+        const uint32_t V = (uint32_t)var.size(), P = (uint32_t)R.link_cols.size();
+        Json lb = Json::object();
+        Json pc = Json::array();
+        for (uint32_t c : R.link_cols) pc.push(Json::of(win_begin + c + 1));
+        lb.set("variant_positions_abs", std::move(pc)).set("n_variants", Json::of(V));
+        Json pairs = Json::array();
+        if (!R.link_skipped && V) {
+            std::vector<uint32_t> at(V);   // row of the table -> variant of the call
+            for (uint32_t k = 0; k < V; ++k) at[R.link_var[k]] = k;
+            auto side = [&](const jl_variant &f) {
+                return Json::object().set("gene", Json::of(cfg.genes[f.gene].name)).set("ref_position", Json::of(f.codon_pos + cfg.genes[f.gene].first_codon))
+                    .set("codon", Json::of(codon_string(f.codon)));
+            };
+            for (uint32_t v = 0; v < V; ++v)
+                for (uint32_t w = v + 1; w < V; ++w) {
+                    if (var[v].col == var[w].col) continue;
+                    jl_link_pair lp;
+                    if (jl_linkage_stats(R.link_both.data(), R.link_carry.data(), R.link_joint.data(), R.link_var_pos.data(), P, V, at[v], at[w], &lp) != JL_OK)
+                        die_jl(nullptr, "linkage statistics");
+                    if (lp.n == 0) continue;
+                    pairs.push(Json::object().set("a", side(var[v])).set("b", side(var[w])).set("reads_both", Json::of(lp.n))
+                                   .set("n11", Json::of(lp.n11)).set("n10", Json::of(lp.n10)).set("n01", Json::of(lp.n01)).set("n00", Json::of(lp.n00))
+                                   .set("r2", Json::of(lp.r2)).set("d_prime", Json::of(lp.d_prime))
+                                   .set("p_positive", Json::of(lp.p_positive)).set("p_negative", Json::of(lp.p_negative)));
+                }
+        }
+        lb.set("n_pairs_tested", Json::of((uint32_t)pairs.arr.size())).set("pairs", std::move(pairs));
+        if (R.link_skipped) lb.set("skipped", Json::of(true));
+        root.set("linkage", std::move(lb));
+    }
+    return root;
+}
+
+// --haplotype-fasta (docs/SPEC.md §13): one record per reported haplotype, in the JSON's order, from ONE class pileup of the window
+// resident on `ctx` with the phasing run's own per-read ids as labels.  No reported haplotype: an empty file.  0, or the exit code.
+int write_haplotype_fasta(const Options &opt, jl_ctx *ctx, const Results &R, uint32_t win_begin, uint32_t n_cols)
+{
+    const uint32_t H = R.ps.n_haplotypes;
+    std::vector<uint32_t> counts((size_t)H * n_cols * 6);
+    std::vector<uint32_t> rescued(H, 0u);
+    if (H) {
+        std::vector<uint16_t> with_rescued;   // --rescue-damaged: the damaged reads count for the haplotype they were assigned to
+        if (R.rescued) {
+            with_rescued.resize(R.read_hap.size());
+            for (size_t i = 0; i < with_rescued.size(); ++i) {
+                with_rescued[i] = R.hap_with_rescued(i);
+                if (with_rescued[i] != R.read_hap[i]) rescued[with_rescued[i]]++;
+            }
+        }
+        if (jl_class_pileup_async(ctx, R.rescued ? with_rescued.data() : R.read_hap.data(), H) != JL_OK) die_jl(ctx, "class pileup");
+        if (jl_class_pileup_fetch(ctx, counts.data(), nullptr) != JL_OK) die_jl(ctx, "class pileup fetch");
+    }
+    std::ofstream f(opt.hap_fasta);
+    if (!f) { std::cerr << "juliet: cannot write " << opt.hap_fasta << "\n"; return 2; }
+    std::vector<uint8_t> cons(n_cols);
+    for (uint32_t h = 0; h < H; ++h) {
+        if (jl_consensus_of_counts(counts.data() + (size_t)h * n_cols * 6, n_cols, cons.data()) != JL_OK) die_jl(nullptr, "consensus of counts");
+        std::string freq, seq;
+        Json::of(R.ps.reported_reads ? (double)R.hap_count[h] / (double)R.ps.reported_reads : 0.0).write(freq);
+        for (uint32_t c = 0; c < n_cols; ++c)
+            if (cons[c] != 4) seq += "ACGT?N"[cons[c]];   // (4: a major deletion, the column is removed)
+        f << ">" << haplotype_name(h) << " reads=" << R.hap_count[h] << (R.rescued ? " rescued=" + std::to_string(rescued[h]) : std::string())
+          << " frequency=" << freq << " window=" << (win_begin + 1) << "-"
+          << (win_begin + n_cols) << " source=" << opt.bam << "\n";
+        for (size_t i = 0; i < seq.size(); i += 70) f << seq.substr(i, 70) << "\n";
+    }
+    f.close();
+    if (!f) { std::cerr << "juliet: cannot write " << opt.hap_fasta << "\n"; return 2; }
+    return 0;
+}
+
+// --consensus, and all of `fuse`: what `fuse` writes for the window resident on `ctx` (doc/FUSE.md:17-24), from the column counts
+// in R and the insertion counters.  0, or the exit code.
+int write_consensus(const Options &opt, jl_ctx *ctx, const Results &R, uint32_t win_begin, uint32_t n_cols)
+{
+    std::vector<uint32_t> len_hist((size_t)n_cols * 32), base_counts((size_t)n_cols * 120);
+    if (jl_insertions_fetch(ctx, len_hist.data(), base_counts.data()) != JL_OK) die_jl(ctx, "insertions");
+    const std::string seq = fuse_consensus(n_cols, R.col_counts, len_hist, base_counts, opt.ins_min_frac, opt.ins_min_distance);
+    std::ofstream f(opt.consensus);
+    if (!f) { std::cerr << "juliet: cannot write " << opt.consensus << "\n"; return 2; }
+    f << ">consensus window=" << (win_begin + 1) << "-" << (win_begin + n_cols) << " source=" << opt.bam << "\n";
+    for (size_t i = 0; i < seq.size(); i += 70) f << seq.substr(i, 70) << "\n";
+    return 0;
+}
+
+// Every output of one run — the JSON text, or its HTML rendering, by extension — each file closed and its stream checked:
+// a short write or a full disk is a failed output, not a quiet success.  "" or the first output that failed.
+std::string write_outputs(const std::vector<std::string> &outputs, const Json &root)
+{
+    std::string text;
+    root.write(text);
+    text += "\n";
+    for (const std::string &out : outputs) {
+        std::ofstream f(out);
+        if (!f) return out;
+        if (out.substr(out.size() - 5) == ".json") f << text;
+        else f << render_html(root);
+        f.close();
+        if (!f) return out;
+    }
+    return "";
+}
+
+}  // namespace
+}  // namespace jlhost

@@ -1,0 +1,427 @@
+// sample.hpp — one sample, step by step.  What `juliet in.bam out...` does to its file, cut into the steps that a batch (--batch)
+// runs for each of its samples too: decode and upload (load_sample: the ONE place a BAM gets onto a context), the sample's setup
+// (sample_window, sample_params), the window ingest (ingest_window), --downsample / --mix on the resident window, the fetch of
+// its results (Results, fetch_*).  Every path calls these, so a sample of a batch gets what a single run of the same file gets.
+// Also here: what the modes share to end with (die_jl, end_process).
+#pragma once
+#include <unistd.h>
+
+#include <functional>
+#include <iostream>
+#include <limits>
+#include <memory>
+
+#include "config.hpp"
+#include "format.hpp"
+#include "options.hpp"
+#include "record_upload.hpp"
+
+namespace jlhost {
+namespace {
+
+// Everything is written and closed.  What a `return` would still do — free a gigabyte of record arrays page by page, take down
+// the uploader and the decode pool, destroy the GPU contexts and the HIP runtime's own state — the operating system does at
+// once when the process ends: 40-60 ms of the wall time of a 100k-read run.  With JL_SLOW_EXIT set the callers do not come here:
+// they return and run their teardown (the long way, for leak checkers).
+[[noreturn]] void end_process(int code)
+{
+    std::cout.flush();
+    std::cerr.flush();
+    fflush(nullptr);
+    _exit(code);
+}
+
+void die_jl(jl_ctx *ctx, const char *what)
+{
+    std::cerr << "juliet: " << what << ": " << jl_last_error(ctx) << "\n";
+    std::exit(3);
+}
+
+// What the device stage hands to the writers, whichever way it ran (one window, or K windows over R devices).
+struct Results {
+    std::vector<jl_variant> var;          // (gene, codon_pos, codon) order; col relative to the overall window
+    std::vector<uint32_t> col_counts;     // [n_cols][6] of the overall window
+    jl_phase_summary ps = {};
+    std::vector<uint32_t> pos_cols, hap_count;   // pos_cols relative to the overall window
+    std::vector<uint8_t> hap_pattern, hit;
+    size_t pat_stride = 0, hit_stride = 0;       // hap_pattern[h * pat_stride + p], hit[v * hit_stride + h]
+    std::vector<uint16_t> read_hap;
+    // --rescue-damaged (docs/SPEC.md §14): rescue[i] of every read by the run's own positions and haplotypes; empty when no call
+    // was made (no reported haplotype, or more positions asked for than the run has: every damaged read is uninformative then)
+    bool rescued = false;
+    uint32_t rescue_min = 0;
+    std::vector<uint16_t> rescue;
+    // --linkage (docs/SPEC.md §15): the three tables of ONE call over the table's distinct columns and its rows; link_var[k] = the
+    // row of `var` that is variant k of the call (the rows by column: var_pos must not decrease, and genes may overlap)
+    bool linked = false, link_skipped = false;
+    std::vector<uint32_t> link_cols, link_var, link_var_pos, link_both, link_carry, link_joint;
+    // the haplotype a damaged read was assigned to, or JL_HAP_DAMAGED; a read that is not damaged: its own id
+    uint16_t hap_with_rescued(uint64_t i) const
+    {
+        if (read_hap[i] != (uint16_t)JL_HAP_DAMAGED || rescue.empty()) return read_hap[i];
+        return rescue[i] < ps.n_haplotypes ? rescue[i] : (uint16_t)JL_HAP_DAMAGED;
+    }
+};
+
+struct DeviceStageInput {
+    const Options *opt;
+    const TargetConfig *cfg;
+    const std::vector<jl_gene> *genes;
+    const std::vector<uint8_t> *refcodes;
+    jl_params prm;
+    uint32_t win_begin, n_cols;
+    uint64_t n_reads;
+};
+
+// --drm-only: the codons of the config's DRMs per evaluated position of one window (doc/JULIET.md:370)
+int drm_masks_of(jl_ctx *ctx, const DeviceStageInput &in, std::vector<uint64_t> &masks)
+{
+    const uint8_t *refp = in.refcodes->empty() ? nullptr : in.refcodes->data();
+    if (jl_pileup_async(ctx, in.genes->data(), (uint32_t)in.genes->size(), refp, (uint32_t)in.refcodes->size()) != JL_OK) return 1;
+    const uint32_t P = jl_n_positions(ctx);
+    std::vector<uint32_t> pg(P), pk(P);
+    if (jl_pileup_fetch(ctx, nullptr, pg.data(), pk.data(), nullptr, nullptr, nullptr) != JL_OK) return 1;
+    masks.assign(P, 0);
+    for (uint32_t p = 0; p < P; ++p) {
+        const GeneCfg &g = in.cfg->genes[pg[p]];
+        for (unsigned cod = 0; cod < 64; ++cod)
+            if (!in.cfg->known_drms(pg[p], pk[p] + g.first_codon, translate(cod)).empty()) masks[p] |= 1ull << cod;
+    }
+    return 0;
+}
+
+// Everything a sample's device stage and outputs are derived from, besides its reads.
+struct SampleSetup {
+    TargetConfig cfg;                // the config, or the ORF "unknown" over the sample's reads
+    uint32_t win_begin = 0, n_cols = 0;
+    std::string chem;
+    jl_params prm = {};
+    std::vector<jl_gene> genes;
+    std::vector<uint8_t> refcodes;
+    const uint8_t *refp() const { return refcodes.empty() ? nullptr : refcodes.data(); }
+};
+
+// The genes and the window of one sample: 0, or 1 when --region leaves no gene of the config (message printed).
+int sample_window(const Options &opt, const TargetConfig &config, const Decoded &d, SampleSetup &s)
+{
+    s.cfg = config;
+    TargetConfig &cfg = s.cfg;
+    int64_t ref_len = std::numeric_limits<int64_t>::max();
+    if (d.ext.ref_id >= 0 && (size_t)d.ext.ref_id < d.refs.size()) ref_len = d.refs[(size_t)d.ext.ref_id].length;
+
+    const bool have_cfg = !cfg.genes.empty();
+    if (!have_cfg) {
+        // no target config: one ORF over the covered window, labelled "unknown" (doc/JULIET.md:182-188);
+        // --region marks the reading frame
+        GeneCfg g;
+        g.name = "unknown";
+        g.begin = g.begin_eff = opt.have_region ? opt.region_b : (uint32_t)d.ext.min_pos + 1;
+        g.end = g.end_eff = opt.have_region ? opt.region_e : (uint32_t)d.ext.max_end + 1;
+        cfg.genes.push_back(g);
+    } else if (opt.have_region) {
+        cfg.apply_region(opt.region_b, opt.region_e);
+        if (cfg.genes.empty()) { std::cerr << "juliet: --region leaves no gene of the config\n"; return 1; }
+    }
+    // window: the called genes plus the -3..+5 context columns (doc/JULIET.md:99-100), inside the reference
+    int64_t gb = std::numeric_limits<int64_t>::max(), ge = 0;
+    for (const GeneCfg &g : cfg.genes) { gb = std::min<int64_t>(gb, (int64_t)g.begin_eff - 1); ge = std::max<int64_t>(ge, (int64_t)g.end_eff - 1); }
+    const int64_t wb = std::max<int64_t>(0, gb - 3);
+    const int64_t we = std::max<int64_t>(wb + 1, std::min<int64_t>(ref_len, ge + 5));
+    s.win_begin = (uint32_t)wb;
+    s.n_cols = (uint32_t)(we - wb);
+    return 0;
+}
+
+// Chemistry (from the sample's own @RG header with --chemistry auto), parameters, genes and reference codes of one sample.
+void sample_params(const Options &opt, const Decoded &d, SampleSetup &s)
+{
+    std::string chem = opt.chemistry;
+    if (chem == "auto") {
+        // chemistry-keyed rates with a permissive fallback (doc/JULIET.md:221-225); the key here is the
+        // platform model in the @RG line
+        chem = (d.header_text.find("SEQUEL") != std::string::npos || d.header_text.find("S/P") != std::string::npos) ? "sequel" : "permissive";
+        if (chem == "permissive") std::cerr << "juliet: chemistry not recognised, permissive mode is active (doc/JULIET.md:221-225)\n";
+    }
+    s.chem = chem;
+    jl_params &prm = s.prm;
+    prm.alpha = opt.alpha;
+    prm.n_tests = opt.n_tests;
+    if (chem == "sequel") prm.err = {0.998826, 5.8e-5, 1.0e-3};
+    else prm.err = {0.99764, 1.2e-4, 2.0e-3};
+    if (opt.match > 0) prm.err.match = opt.match;
+    if (opt.substitution >= 0) prm.err.substitution = opt.substitution;
+    prm.expected_round = opt.expected_round;
+    prm.tail = opt.fisher_tail;
+    prm.min_perc = opt.min_perc;
+    prm.max_perc = opt.max_perc;
+
+    s.genes.clear();
+    for (const GeneCfg &g : s.cfg.genes) s.genes.push_back({g.begin_eff, g.end_eff});
+    s.refcodes.clear();
+    if (!s.cfg.reference_sequence.empty())
+        for (char ch : s.cfg.reference_sequence) s.refcodes.push_back(base_code(ch));
+}
+
+using Tick = std::function<void(const char *)>;
+
+// The variant table (unless `calls` is off: the pileup alone ran) and the column counts of the run last enqueued on `ctx`,
+// whether it ran alone or in a group.  R.col_counts holds n_cols * 6 entries.  nullptr, or the step that failed.
+const char *fetch_calls(jl_ctx *ctx, bool calls, Results &R, const Tick &tick)
+{
+    R.var.resize(4096);
+    uint32_t nv = 0;
+    if (calls && jl_call_fetch(ctx, R.var.data(), 4096, &nv) != JL_OK) return "call fetch";
+    R.var.resize(nv);
+    tick("  wait for the run + table");
+    if (jl_pileup_fetch(ctx, R.col_counts.data(), nullptr, nullptr, nullptr, nullptr, nullptr) != JL_OK) return "pileup fetch";
+    tick("  column counts");
+    return nullptr;
+}
+
+// The haplotypes and the per-read ids of a phasing run, after fetch_calls.
+const char *fetch_phase(jl_ctx *ctx, uint64_t n_reads, Results &R)
+{
+    const uint32_t cap_var = std::max<uint32_t>(1, (uint32_t)R.var.size());
+    R.pos_cols.resize(cap_var);
+    R.hap_count.resize(JL_MAX_HAPLOTYPES);
+    R.hap_pattern.resize((size_t)JL_MAX_HAPLOTYPES * cap_var);
+    R.hit.resize((size_t)cap_var * JL_MAX_HAPLOTYPES);
+    R.read_hap.resize(n_reads);
+    R.pat_stride = cap_var;
+    R.hit_stride = JL_MAX_HAPLOTYPES;
+    if (jl_phase_fetch(ctx, &R.ps, R.pos_cols.data(), R.hap_count.data(), R.hap_pattern.data(), R.hit.data(), R.read_hap.data(), nullptr, cap_var) != JL_OK)
+        return "phase fetch";
+    return nullptr;
+}
+
+// --rescue-damaged, after fetch_phase: one call of the rule of docs/SPEC.md §14 with the run's own positions and haplotypes.
+const char *fetch_rescue(jl_ctx *ctx, uint32_t min_positions, Results &R)
+{
+    R.rescued = true;
+    R.rescue_min = min_positions;
+    R.rescue.clear();
+    if (R.ps.n_haplotypes == 0 || min_positions > R.ps.n_positions) return nullptr;
+    if (jl_phase_rescue_async(ctx, R.pos_cols.data(), R.ps.n_positions, R.hap_pattern.data(), (uint32_t)R.pat_stride, R.ps.n_haplotypes,
+                              min_positions) != JL_OK)
+        return "rescue";
+    R.rescue.resize(R.read_hap.size());
+    if (jl_phase_rescue_fetch(ctx, R.rescue.data(), nullptr, nullptr) != JL_OK) return "rescue fetch";
+    return nullptr;
+}
+
+// --linkage, after fetch_calls: ONE call of docs/SPEC.md §15 with the table's distinct columns as positions and its rows as variants.
+// No variant: no call.  More than JL_LINK_MAX variants or positions: a warning, no call, the block says "skipped".
+const char *fetch_linkage(jl_ctx *ctx, Results &R)
+{
+    R.linked = true;
+    R.link_skipped = false;
+    const uint32_t V = (uint32_t)R.var.size();
+    R.link_var.resize(V);
+    for (uint32_t k = 0; k < V; ++k) R.link_var[k] = k;
+    std::stable_sort(R.link_var.begin(), R.link_var.end(), [&](uint32_t a, uint32_t b) { return R.var[a].col < R.var[b].col; });
+    R.link_cols.clear();
+    R.link_var_pos.resize(V);
+    std::vector<uint8_t> codon(V);
+    for (uint32_t k = 0; k < V; ++k) {
+        const jl_variant &f = R.var[R.link_var[k]];
+        if (R.link_cols.empty() || R.link_cols.back() != f.col) R.link_cols.push_back(f.col);
+        R.link_var_pos[k] = (uint32_t)R.link_cols.size() - 1u;
+        codon[k] = f.codon;
+    }
+    if (V == 0) return nullptr;
+    const uint32_t P = (uint32_t)R.link_cols.size();
+    if (V > (uint32_t)JL_LINK_MAX || P > (uint32_t)JL_LINK_MAX) {
+        std::cerr << "juliet: warning: --linkage takes at most " << (int)JL_LINK_MAX << " variants at " << (int)JL_LINK_MAX << " positions, the table has " << V
+                  << " at " << P << ": no pair is tested (narrow the table with --min-perc / --max-perc / --region)\n";
+        R.link_skipped = true;
+        return nullptr;
+    }
+    if (jl_variant_linkage_async(ctx, R.link_cols.data(), P, R.link_var_pos.data(), codon.data(), V) != JL_OK) return "linkage";
+    R.link_both.resize((size_t)P * P), R.link_carry.resize((size_t)V * P), R.link_joint.resize((size_t)V * V);
+    if (jl_variant_linkage_fetch(ctx, R.link_both.data(), R.link_carry.data(), R.link_joint.data()) != JL_OK) return "linkage fetch";
+    return nullptr;
+}
+
+const Tick quiet_tick = [](const char *) {};   // for the callers that print no laps (--batch, --mix)
+
+IngestOptions ingest_options(const Options &opt)
+{
+    IngestOptions io;
+    io.min_qv = opt.min_qv;
+    io.min_rq = opt.min_rq;
+    io.qv_mask = opt.qv_upload_mask;
+    return io;
+}
+
+// How a step of loading a sample ended.  The callers keep their own policies and map this: a single run and --mix print and leave
+// (exit_code_of), a batch fails the sample or stops (BatchRunner::prepare).
+enum class Outcome { ok, input, device };   // input: the records or the file are at fault
+struct Status {
+    Outcome outcome = Outcome::ok;
+    std::string what;          // the step that failed (device), or what is wrong with the input
+    jl_ctx *ctx = nullptr;     // device: the context whose jl_last_error tells more (nullptr: none does)
+    int rc = JL_OK;            // device: the status of the call that failed
+    std::string text() const { return ctx ? what + ": " + jl_last_error(ctx) : what; }
+};
+
+// A sample on its context(s): what load_sample leaves.  The uploader stays (its contexts by index: ctx(k)) until the owner drops it.
+struct SampleLoad : Status {
+    Decoded dec;
+    std::vector<std::string> names;
+    uint64_t n_reads = 0;
+    std::unique_ptr<RecordUploader> uploader;   // none: a GPU-free decode (no context asked for)
+};
+
+// Loading, first half: the uploader, the decode (a file that cannot be decoded throws), the no-alignments check.  The contexts
+// may still be coming up: what needs no device (the sample's setup, --dump-msa) runs between the halves of a single run.
+SampleLoad load_begin(const std::string &bam, const IngestOptions &io, const std::vector<CtxFuture> &ctxs, const Options &opt, const Tick &tick)
+{
+    SampleLoad l;
+    if (!ctxs.empty()) l.uploader.reset(new RecordUploader(ctxs, file_bytes(bam), opt.min_qv > 0, io.qv_mask));
+    RecordArrays rec;
+    l.dec = decode_bam(bam, io, l.uploader.get(), rec);
+    tick("bam decode");
+    if (l.dec.ext.n_reads == 0) {
+        l.outcome = Outcome::input;
+        l.what = "no primary or supplementary alignments";
+    }
+    return l;
+}
+
+// Loading, second half: waits for the contexts and for the uploads, checks that every read arrived, takes the names.  The records
+// are on every context when this leaves `l` ok; their window is not ingested yet (ingest_window, or per window: run_rank).
+void load_finish(SampleLoad &l, const std::vector<CtxFuture> &ctxs, const Tick &tick)
+{
+    auto fail = [&](const char *what, jl_ctx *c, int rc) {
+        l.outcome = Outcome::device;
+        l.what = what;
+        l.ctx = c;
+        l.rc = rc;
+    };
+    jl_ctx *ctx = nullptr;
+    for (const CtxFuture &f : ctxs) {
+        const auto up = f.get();
+        if (up.first != JL_OK) return fail("no usable GPU (this tool has no CPU fallback)", nullptr, up.first);
+        if (!ctx) ctx = up.second;
+    }
+    tick("context ready");
+    if (const int rc = l.uploader->finish()) return fail("record upload", l.uploader->failed() ? l.uploader->failed() : ctx, rc);
+    if (l.uploader->n_reads != l.dec.ext.n_reads) return fail("record upload lost reads", nullptr, JL_OK);
+    l.names.swap(l.uploader->names);
+    l.n_reads = l.dec.ext.n_reads;
+    tick("rest of the upload");
+}
+
+SampleLoad load_sample(const std::string &bam, const IngestOptions &io, const std::vector<CtxFuture> &ctxs, const Options &opt, const Tick &tick)
+{
+    SampleLoad l = load_begin(bam, io, ctxs, opt, tick);
+    if (l.outcome == Outcome::ok) load_finish(l, ctxs, tick);
+    return l;
+}
+
+// The window ingest of a loaded sample on ONE context (K windows ingest per window instead: run_rank).  With a consensus asked
+// for, the insertion counters too: fuse keeps in-frame insertions (doc/FUSE.md:19).
+Status ingest_window(jl_ctx *ctx, uint32_t n_cols, uint32_t win_begin, const Options &opt)
+{
+    Status st;
+    if (!opt.consensus.empty()) jl_msa_track_insertions(ctx, 1);
+    if (const int rc = jl_records_finish(ctx, n_cols, win_begin, opt.min_qv)) {
+        st.outcome = Outcome::device;
+        st.what = "ingest";
+        st.ctx = ctx;
+        st.rc = rc;
+    }
+    return st;
+}
+
+// The policy of a single run and of --mix: 0 when the step went fine; an input failure is printed and is the exit status 2; a
+// device failure ends the process (3).
+int exit_code_of(const Status &st, const std::string &file)
+{
+    if (st.outcome == Outcome::ok) return 0;
+    if (st.outcome == Outcome::device) die_jl(st.ctx, st.what.c_str());
+    std::cerr << "juliet: " << st.what << " in " << file << "\n";
+    return 2;
+}
+
+// What --downsample / --mix did to a sample: the `sampling` block of the JSON's input section, present only when reads were chosen.
+struct SamplingInfo {
+    bool acted = false;
+    uint64_t seed = 0;
+    struct Source { std::string file; uint64_t reads, kept; };
+    std::vector<Source> sources;
+};
+
+// --downsample on a window that is resident on `ctx` (its reads' names in `names`): when it holds more than opt.downsample reads,
+// the reads of jl_sample_reads are gathered into `taken` — a second context of the device, on the same stream — and names / n_reads
+// follow the indices.  JL_OK, or the status of the call that failed (jl_last_error(taken)); *acted: the window to run is `taken` now.
+int downsample_window(const Options &opt, const std::string &bam, jl_ctx *ctx, jl_ctx *taken, std::vector<std::string> &names, uint64_t &n_reads,
+                      SamplingInfo &info, bool *acted)
+{
+    *acted = false;
+    if (!opt.have_downsample || n_reads <= opt.downsample) return JL_OK;
+    std::vector<uint32_t> idx((size_t)opt.downsample);
+    uint64_t kept = 0;
+    if (const int rc = jl_sample_reads(n_reads, opt.downsample, opt.sample_seed, idx.data(), &kept)) return rc;
+    const jl_take_part part = {ctx, idx.data(), kept};
+    if (const int rc = jl_msa_take(taken, &part, 1)) return rc;
+    std::vector<std::string> chosen((size_t)kept);
+    for (uint64_t j = 0; j < kept; ++j) chosen[(size_t)j].swap(names[idx[(size_t)j]]);
+    names.swap(chosen);
+    info.acted = true;
+    info.seed = opt.sample_seed;
+    info.sources.assign(1, {bam, n_reads, kept});
+    n_reads = kept;
+    *acted = true;
+    return JL_OK;
+}
+
+// --mix: the mixture of doc/MIXDATA.md in `taken`.  `major` holds the positional BAM's window; every BAM of the list is decoded and
+// ingested into a context of its own over the same window (same device and stream), jl_mix_counts says how many reads each source
+// gives, source m is sampled with seed S + m, and ONE jl_msa_take with the parts in argument order builds the mixture; names and
+// n_reads become the mixture's.  0, or the process's exit status (message printed): 2 an input error, 3 a device error.
+int mix_window(const Options &opt, const IngestOptions &io, jl_ctx *major, jl_ctx *taken, uint32_t n_cols, uint32_t win_begin,
+               std::vector<std::string> &names, uint64_t &n_reads, SamplingInfo &info)
+{
+    const size_t n_src = opt.mix.size() + 1;
+    std::vector<jl_ctx *> ctxs(1, major);
+    std::vector<std::vector<std::string>> src_names(n_src);
+    std::vector<uint64_t> reads(1, n_reads);
+    src_names[0].swap(names);
+    for (const std::string &file : opt.mix) {
+        jl_ctx *c = nullptr;
+        if (jl_ctx_create(opt.device, jl_ctx_stream(major), &c) != JL_OK) die_jl(nullptr, "context of a minor clone");
+        SampleLoad load = load_sample(file, io, {ctx_ready(c)}, opt, quiet_tick);
+        if (const int code = exit_code_of(load, file)) return code;
+        if (const int code = exit_code_of(ingest_window(c, n_cols, win_begin, opt), file)) return code;
+        src_names[ctxs.size()].swap(load.names);
+        ctxs.push_back(c);
+        reads.push_back(load.n_reads);
+    }
+    std::vector<uint64_t> counts(n_src);
+    if (jl_mix_counts((uint32_t)n_src, opt.downsample, opt.mix_perc, counts.data()) != JL_OK) die_jl(nullptr, "mixture counts");
+    for (size_t m = 0; m < n_src; ++m)
+        if (reads[m] < counts[m]) {
+            std::cerr << "juliet: --mix: " << (m ? opt.mix[m - 1] : opt.bam) << " has " << reads[m] << " reads, the mixture wants " << counts[m] << " of it\n";
+            return 2;
+        }
+    std::vector<std::vector<uint32_t>> idx(n_src);
+    std::vector<jl_take_part> parts(n_src);
+    info.acted = true;
+    info.seed = opt.sample_seed;
+    info.sources.clear();
+    for (size_t m = 0; m < n_src; ++m) {
+        idx[m].resize((size_t)std::max<uint64_t>(counts[m], 1));
+        uint64_t kept = 0;
+        if (jl_sample_reads(reads[m], counts[m], opt.sample_seed + m, idx[m].data(), &kept) != JL_OK || kept != counts[m]) die_jl(nullptr, "sample of a clone");
+        parts[m] = {ctxs[m], idx[m].data(), kept};
+        info.sources.push_back({m ? opt.mix[m - 1] : opt.bam, reads[m], kept});
+        for (uint64_t j = 0; j < kept; ++j) names.push_back(std::move(src_names[m][idx[m][(size_t)j]]));
+    }
+    if (jl_msa_take(taken, parts.data(), (uint32_t)n_src) != JL_OK) die_jl(taken, "mixture");
+    n_reads = names.size();
+    return 0;
+}
+
+}  // namespace
+}  // namespace jlhost
