@@ -60,7 +60,8 @@ typedef struct {
 typedef struct {
     double match;
     double substitution; /* per target base */
-    double deletion;     /* reserved: indels are ignored (J:26-27) */
+    double deletion;     /* a read shows a whole-codon deletion by error (jl_deletion_test, docs/SPEC.md section 16); the
+                            codon calls ignore indels (J:26-27) and this field */
 } jl_error_model;
 
 typedef struct {
@@ -381,6 +382,45 @@ typedef struct {
  * (jl_last_error(NULL) says which): a NULL array; v or w >= n_var; var_pos[v] == var_pos[w]. */
 int jl_linkage_stats(const uint32_t *both, const uint32_t *carry, const uint32_t *joint, const uint32_t *var_pos,
                      uint32_t n_pos, uint32_t n_var, uint32_t v, uint32_t w, jl_link_pair *out);
+/*
+ * Whole-codon deletions at EVERY CODON START of the resident matrix (docs/SPEC.md §16): the codon calls skip a read with a '-' in
+ * the codon (J:26-27), so a clean three-base deletion — a real allele — shows only as a dip in coverage, lumped together with the
+ * frame-shifting damage around it.  For every column c with c + 2 < n_cols and every read, by the three codes at c, c + 1, c + 2
+ * the read counts in at most one of
+ *   codon    all three < 4 (the codon coverage of jl_pileup_fetch, both[p][p] of jl_variant_linkage_fetch)
+ *   del3     all three == 4
+ *   partial  none is 5, none is 6, at least one is 4 and at least one is < 4: a deletion that breaks this codon
+ * and in span when none of the three is 6.  A read with an N in the codon counts in span only, a code-6 cell counts nowhere.
+ * cnt[n_cols - 2][4] = {codon, del3, partial, span}, 32 bits, exact, independent of launch shape and order.  There is no position
+ * list: every column is a codon start of some frame, the host picks the ones it wants.  Reads past n_reads count nowhere: the
+ * padding, and whatever an adopted matrix holds past byte ceil(n_reads / 8) of a plane row or past the last read in its last byte.
+ * The contract is jl_class_pileup_async's: it enqueues on the context's stream into a buffer of its own (grown on demand, released
+ * with the context) and touches nothing else — the matrix, the insertion counters, earlier stage results and the captured graph stay
+ * as they are.  Every kind of resident matrix is accepted, an adopted one with its own plane stride included.
+ * JL_ERR_STATE: no resident matrix.  JL_ERR_ARG: fewer than 3 columns.  A refused call changes nothing.
+ */
+int jl_codon_deletions_async(jl_ctx *ctx);
+/* Wait and copy out cnt[n_cols - 2][4] of the last jl_codon_deletions_async (NULL: only wait).  JL_ERR_STATE: none was enqueued. */
+int jl_codon_deletions_fetch(jl_ctx *ctx, uint32_t *cnt /* [n_cols-2][4] */);
+/* One position of that table tested against the error model: coverage = codon + del3, expected = round_mode(coverage *
+ * prm->err.deletion) clamped to [0, coverage] (prm->expected_round, the product in IEEE double), the table [[del3, coverage -
+ * del3], [expected, coverage - expected]], p by prm->tail from the routines of the codon test, p_value = min(1, p * n_tests),
+ * called = del3 > 0 and p_value < prm->alpha and the prm->min_perc / max_perc filters on 100 del3 / coverage (strict, as the
+ * codon calls).  coverage == 0: not called, p_value 1, log_p 0. */
+typedef struct {
+    uint32_t count;     /* del3 */
+    uint32_t coverage;  /* codon + del3 */
+    uint32_t expected;
+    uint32_t partial;   /* reads whose deletion breaks this codon: not part of the test */
+    uint32_t called;    /* 0 or 1 */
+    uint32_t pad_;
+    double p_value;     /* Bonferroni-adjusted, <= 1 */
+    double log_p;       /* ln of the unadjusted p */
+} jl_deletion_call;
+/* Host only (no device, no context).  n_tests: the Bonferroni factor, RESOLVED (the codon test's own: prm->n_tests is not read).
+ * JL_ERR_ARG (jl_last_error(NULL) says which): a NULL argument; n_tests <= 0; prm->err.deletion outside [0, 1]; codon + del3
+ * above 2^32 - 1. */
+int jl_deletion_test(const uint32_t cnt[4], const jl_params *prm, double n_tests, jl_deletion_call *out);
 /*
  * Reference/majority codon, error model, Fisher's exact x Bonferroni, filters, variant table
  * (SPEC §4-7; J:38-42).  `drm_masks`: optional [P] 64-bit codon masks; with --drm-only a codon is kept

@@ -33,7 +33,7 @@ SUMMARY = np.dtype([(n, "<u4") for n in SUMMARY_FIELDS])
 EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", "jl_ctx_destroy", "jl_last_error",
            "jl_sync", "jl_col_stride", "jl_plane_stride", "jl_msa_upload", "jl_msa_alloc", "jl_msa_adopt", "jl_msa_pack_rows",
            "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_take", "jl_msa_take_async", "jl_sample_reads", "jl_mix_counts", "jl_msa_download", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
-           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_phase_async", "jl_phase_fetch",
+           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_phase_async", "jl_phase_fetch",
            "jl_ctx_stream", "jl_run_async", "jl_run_wait", "jl_run_done", "jl_run_view_get", "jl_group_create", "jl_group_destroy",
            "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
            "jl_allgather_variants", "jl_allgather_variants_async", "jl_allgather_variants_async_many", "jl_allgather_variants_many", "jl_group_exchange_bind", "jl_group_exchange_collect", "jl_xwin_plan", "jl_xwin_assemble_local",
@@ -210,6 +210,9 @@ def load_library(path=LIB_PATH):
     lib.jl_variant_linkage_async.argtypes = [vp, vp, u32, vp, vp, u32]
     lib.jl_variant_linkage_fetch.argtypes = [vp, vp, vp, vp]
     lib.jl_linkage_stats.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, vp]
+    lib.jl_codon_deletions_async.argtypes = [vp]
+    lib.jl_codon_deletions_fetch.argtypes = [vp, vp]
+    lib.jl_deletion_test.argtypes = [vp, vp, C.c_double, vp]
     lib.jl_call_async.argtypes = [vp, C.POINTER(Params), vp]
     lib.jl_call_fetch.argtypes = [vp, vp, u32, C.POINTER(u32)]
     lib.jl_variant_table_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u32)]
@@ -571,6 +574,20 @@ class Juliet:
         self._chk(self.lib.jl_variant_linkage_fetch(self.h, _p(both), _p(carry), _p(joint)))
         return dict(both=both, carry=carry, joint=joint)
 
+    def codon_deletions(self, wait=True):
+        """jl_codon_deletions_async (docs/SPEC.md §16): at every codon start c (c + 2 < n_cols) of the resident matrix the reads
+        with a whole codon there, with all three bases deleted, with a deletion that breaks the codon, and the reads spanning it.
+        Returns cnt[n_cols - 2, 4] = (codon, del3, partial, span), uint32, exact; wait=False only enqueues on this context's
+        stream and returns None (codon_deletions_fetch brings the array)."""
+        self._chk(self.lib.jl_codon_deletions_async(self.h))
+        self._del_cols = self.n_cols
+        return self.codon_deletions_fetch() if wait else None
+
+    def codon_deletions_fetch(self):
+        cnt = np.zeros((max(0, getattr(self, "_del_cols", 0) - 2), 4), dtype=np.uint32)
+        self._chk(self.lib.jl_codon_deletions_fetch(self.h, _p(cnt) if cnt.size else None))
+        return cnt
+
     def call_async(self, params=None, drm_masks=None):
         prm = params or default_params()
         if drm_masks is not None:
@@ -915,6 +932,27 @@ def linkage_stats(both, carry, joint, var_pos, v, w):
     if rc:
         raise JulietError(rc, "jl_linkage_stats: " + lib.jl_last_error(None).decode())
     return {name: getattr(out, name) for name, _ in LinkPair._fields_ if name != "pad_"}
+
+
+class DeletionCall(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("coverage", C.c_uint32), ("expected", C.c_uint32), ("partial", C.c_uint32),
+                ("called", C.c_uint32), ("pad_", C.c_uint32), ("p_value", C.c_double), ("log_p", C.c_double)]
+
+
+def deletion_test(cnt, params, n_tests):
+    """jl_deletion_test (host only, docs/SPEC.md §16): one row (codon, del3, partial, span) of Juliet.codon_deletions against the
+    error model's deletion rate, with the codon test's resolved Bonferroni factor n_tests: dict(count, coverage, expected,
+    partial, called, p_value = min(1, p * n_tests), log_p = ln p)."""
+    lib = load_library()
+    cnt = np.ascontiguousarray(cnt, dtype=np.uint32)
+    assert cnt.shape == (4,)
+    out = DeletionCall()
+    rc = lib.jl_deletion_test(_p(cnt), C.byref(params), float(n_tests), C.byref(out))
+    if rc:
+        raise JulietError(rc, "jl_deletion_test: " + lib.jl_last_error(None).decode())
+    d = {name: getattr(out, name) for name, _ in DeletionCall._fields_ if name != "pad_"}
+    d["called"] = bool(d["called"])
+    return d
 
 
 def mix_counts(n_sources, coverage, percentage):

@@ -378,6 +378,17 @@ struct jl_link_args {
 };
 void jl_launch_variant_linkage(const jl_link_args *a, hipStream_t st);
 
+// ---- whole-codon deletions at every codon start (kernels_del.hip, capi_del.hip; docs/SPEC.md §16)
+struct jl_del_args {
+    const uint8_t *msa;        // the window's bit planes
+    uint64_t plane_stride;     // ... and their stride (an adopted matrix brings its own)
+    uint64_t n_reads;
+    uint32_t n_cols;           // >= 3
+    uint32_t seg_tiles;        // tiles of 512 reads a workgroup walks (set by the launcher)
+    uint32_t *cnt;             // [n_cols - 2][4] codon, del3, partial, span; zeroed
+};
+void jl_launch_codon_deletions(const jl_del_args *a, hipStream_t st);
+
 inline int jl_hip_status(hipError_t e) { return e == hipErrorOutOfMemory ? JL_ERR_MEMORY : JL_ERR_DEVICE; }
 
 // ---- owning arrays.  Every buffer a context owns is one of these: it frees itself when the context is deleted (jl_ctx_destroy, the
@@ -582,6 +593,10 @@ struct jl_ctx {
     jl_dev_array<uint32_t> link_rows;      // the bit rows
     jl_dev_array<uint32_t> link_out;       // both [link_p][link_p], carry [link_v][link_p], joint [link_v][link_v]
     uint32_t link_p = 0, link_v = 0;       // shape of the last linkage enqueued (link_p = 0: none)
+
+    // ---- jl_codon_deletions_async: a buffer of its own, grown on demand (capi_del.hip); no stage and no run touches it
+    jl_dev_array<uint32_t> del_out;        // cnt [del_cols - 2][4]
+    uint32_t del_cols = 0;                 // columns of the last call enqueued (0: none)
 
     // ---- phasing sharded by reads: the groups of this matrix exported for the merge (jl_phase_groups_async / _fetch)
     bool phase_export = false;        // the phase launch in flight / last run exported instead of selecting

@@ -137,6 +137,28 @@ inline std::string render_html(const Json &root)
         }
         h += "</details>\n";
     }
+    // ---- --call-deletions (docs/SPEC.md §16): the called codon deletions, a table per gene; doubles as the JSON prints them
+    if (const Json *genes = root.get("genes")) {
+        bool any = false;
+        for (const Json &g : genes->arr) any = any || g.get("deletion_positions");
+        if (any) {
+            h += "<details open id=\"deletions\"><summary>Codon Deletions</summary>\n";
+            for (const Json &g : genes->arr) {
+                const Json *dps = g.get("deletion_positions");
+                if (!dps) continue;
+                h += "<table class=\"deletions\" data-gene=\"" + html_escape(g.get_str("name")) + "\"><caption>" + html_escape(g.get_str("name")) +
+                     "</caption>\n<tr><th>Pos</th><th>Codon</th><th>AA</th><th>#Reads</th><th>Coverage</th><th>Frequency</th><th>Expected</th>"
+                     "<th>pValue</th><th>log_pValue</th><th>#Frame-shift reads</th></tr>\n";
+                for (const Json &d : dps->arr) {
+                    h += "<tr class=\"deletion\">" + td(num_str(d.get("ref_position"))) + td(d.get_str("ref_codon")) + td(d.get_str("ref_amino_acid"));
+                    for (const char *key : {"count", "coverage", "frequency", "expected", "pValue", "log_pValue", "frameshift_reads"}) h += td(num_str(d.get(key)));
+                    h += "</tr>\n";
+                }
+                h += "</table>\n";
+            }
+            h += "</details>\n";
+        }
+    }
     // ---- 4. Drug Summaries (doc/JULIET.md:104-107)
     if (const Json *ds = root.get("drug_summaries")) {
         h += "<details open id=\"drugs\"><summary>Drug Summaries</summary><table id=\"drug-table\"><tr><th>Drug</th><th>Gene</th><th>Mutation</th><th>Codon</th><th>%</th></tr>\n";

@@ -41,6 +41,7 @@ struct Options {
     uint32_t rescue_min = 1;         // --rescue-min-positions K: informative positions a read needs to be judged at all
     bool have_rescue_min = false;
     bool linkage = false;            // --linkage: every pair of called variants over the reads covering both (docs/SPEC.md §15)
+    bool call_deletions = false;     // --call-deletions: in-frame codon deletions at every evaluated position (docs/SPEC.md §16)
     bool fuse_only = false;        // invoked as `fuse in.bam out.fasta` (doc/FUSE.md:26-31): the consensus and nothing else
     double ins_min_frac = 0.5;     // an insertion enters the consensus when more than this share of the covering reads carries it
     uint32_t ins_min_distance = 10;  // ... and the previous included insertion lies at least this many columns back (UNPINNED)
@@ -110,6 +111,16 @@ struct Options {
         "                                      (n_pairs_tested is there to correct with).  At most 1024 variants at 1024 positions:\n"
         "                                      beyond, a warning and \"skipped\": true.  Follows --downsample / --mix.  Not with\n"
         "                                      --windows, --devices a,b, --batch or as fuse\n"
+        "      --call-deletions                in-frame codon deletions (docs/SPEC.md section 16), with and without --mode-phasing:\n"
+        "                                      at every evaluated codon position the reads whose three bases there are all\n"
+        "                                      deleted are tested against the error model's deletion rate by the codon test's own\n"
+        "                                      Fisher test, Bonferroni factor and --min-perc / --max-perc, over coverage = reads\n"
+        "                                      with a whole codon + reads with the whole codon deleted.  Every gene of the JSON\n"
+        "                                      gains `deletion_positions`: ref_position, ref_codon, ref_amino_acid, count,\n"
+        "                                      coverage, frequency, expected, pValue, log_pValue and frameshift_reads (reads whose\n"
+        "                                      deletion breaks the codon: not part of the test).  Empty with --drm-only.  Phasing\n"
+        "                                      is unchanged.  Follows --downsample / --mix.  Not with --windows, --devices a,b,\n"
+        "                                      --batch or as fuse\n"
         "      --downsample N [--sample-seed S]  call on N reads of the sample (\"downsample it to 6000x\", doc/JULIETFLOW.md:23-25):\n"
         "                                      the reads are chosen by docs/SPEC.md section 12 (seed default 0; samples of one seed are\n"
         "                                      nested) and gathered on the device; N at or above the read count changes nothing.\n"
@@ -248,6 +259,7 @@ Options parse(int argc, char **argv)
         else if (a == "--haplotype-fasta") o.hap_fasta = need(i);
         else if (a == "--rescue-damaged") o.rescue = true;
         else if (a == "--linkage") o.linkage = true;
+        else if (a == "--call-deletions") o.call_deletions = true;
         else if (a == "--rescue-min-positions") { o.rescue_min = (uint32_t)std::stoul(need(i)); o.have_rescue_min = true; }
         else if (a == "--ins-min-frac") o.ins_min_frac = std::stod(need(i));
         else if (a == "--ins-min-distance") o.ins_min_distance = (uint32_t)std::stoul(need(i));
@@ -291,6 +303,12 @@ Options parse(int argc, char **argv)
     }
     if (o.linkage) {   // refused here, before any file is read or any GPU work
         auto refuse = [](const char *why) { std::cerr << "juliet: --linkage " << why << "\n"; std::exit(1); };
+        if (as_fuse) refuse("is not an option of fuse");
+        if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
+        if (!o.batch.empty()) refuse("is not part of a batch (not with --batch)");
+    }
+    if (o.call_deletions) {   // refused here, before any file is read or any GPU work
+        auto refuse = [](const char *why) { std::cerr << "juliet: --call-deletions " << why << "\n"; std::exit(1); };
         if (as_fuse) refuse("is not an option of fuse");
         if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
         if (!o.batch.empty()) refuse("is not part of a batch (not with --batch)");

@@ -138,6 +138,25 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
             v = e;
         }
         gj.set("variant_positions", vps);
+        if (R.deletions) {   // --call-deletions (docs/SPEC.md §16): the called positions of this gene, ascending
+            Json dps = Json::array();
+            for (const Results::Deletion &d : R.del_rows) {
+                if (d.gene != g) continue;
+                Json dj = Json::object();
+                dj.set("ref_position", Json::of(d.codon_pos + cfg.genes[g].first_codon));
+                if (d.ref_codon >= 0) {
+                    dj.set("ref_codon", Json::of(codon_string((uint8_t)d.ref_codon)));
+                    dj.set("ref_amino_acid", Json::of(std::string(1, translate((uint8_t)d.ref_codon))));
+                }
+                dj.set("count", Json::of(d.call.count)).set("coverage", Json::of(d.call.coverage));
+                dj.set("frequency", Json::of((double)d.call.count / (double)d.call.coverage));
+                dj.set("expected", Json::of(d.call.expected));
+                dj.set("pValue", Json::of(d.call.p_value)).set("log_pValue", Json::of(d.call.log_p));
+                dj.set("frameshift_reads", Json::of(d.call.partial));
+                dps.push(dj);
+            }
+            gj.set("deletion_positions", dps);
+        }
         genes_json.push(gj);
     }
     root.set("genes", genes_json);

@@ -55,6 +55,10 @@ struct Results {
     // row of `var` that is variant k of the call (the rows by column: var_pos must not decrease, and genes may overlap)
     bool linked = false, link_skipped = false;
     std::vector<uint32_t> link_cols, link_var, link_var_pos, link_both, link_carry, link_joint;
+    // --call-deletions (docs/SPEC.md §16): the called positions in (gene, codon) order; ref_codon < 0: none exists at the position
+    struct Deletion { uint32_t gene, codon_pos; int ref_codon; jl_deletion_call call; };
+    bool deletions = false;
+    std::vector<Deletion> del_rows;
     // the haplotype a damaged read was assigned to, or JL_HAP_DAMAGED; a read that is not damaged: its own id
     uint16_t hap_with_rescued(uint64_t i) const
     {
@@ -239,6 +243,50 @@ const char *fetch_linkage(jl_ctx *ctx, Results &R)
     if (jl_variant_linkage_async(ctx, R.link_cols.data(), P, R.link_var_pos.data(), codon.data(), V) != JL_OK) return "linkage";
     R.link_both.resize((size_t)P * P), R.link_carry.resize((size_t)V * P), R.link_joint.resize((size_t)V * V);
     if (jl_variant_linkage_fetch(ctx, R.link_both.data(), R.link_carry.data(), R.link_joint.data()) != JL_OK) return "linkage fetch";
+    return nullptr;
+}
+
+// --call-deletions, after fetch_calls: ONE call of docs/SPEC.md §16 on the window that was called, then the test of every evaluated
+// codon position (§3's positions of the run's plan) with the run's own parameters and resolved Bonferroni factor.  --drm-only: no
+// DRM notation names a deletion, nothing is tested.
+const char *fetch_deletions(jl_ctx *ctx, const Options &opt, const jl_params &prm, const std::vector<jl_gene> &genes,
+                            const std::vector<uint8_t> &refcodes, uint32_t win_begin, uint32_t n_cols, Results &R)
+{
+    R.deletions = true;
+    R.del_rows.clear();
+    if (opt.drm_only || n_cols < 3) return nullptr;
+    if (jl_codon_deletions_async(ctx) != JL_OK) return "codon deletions";
+    std::vector<uint32_t> cnt((size_t)(n_cols - 2) * 4);
+    if (jl_codon_deletions_fetch(ctx, cnt.data()) != JL_OK) return "codon deletions fetch";
+    const uint32_t P = jl_n_positions(ctx);
+    std::vector<uint32_t> pg(P), pk(P), pc(P), hist;
+    const bool majority = refcodes.empty();   // (§4: the reference codon is the majority codon then)
+    if (majority) hist.resize((size_t)P * 64);
+    if (P && jl_pileup_fetch(ctx, nullptr, pg.data(), pk.data(), pc.data(), majority ? hist.data() : nullptr, nullptr) != JL_OK) return "positions";
+    double n_tests = prm.n_tests;
+    if (!(n_tests > 0.0)) {   // §5: the codons of all genes
+        n_tests = 0.0;
+        for (const jl_gene &g : genes)
+            if (g.begin != 0 && g.end > g.begin) n_tests += (double)((g.end - g.begin) / 3);
+    }
+    for (uint32_t p = 0; p < P; ++p) {
+        jl_deletion_call dc;
+        if (jl_deletion_test(&cnt[(size_t)pc[p] * 4], &prm, n_tests, &dc) != JL_OK) return "deletion test";
+        if (!dc.called) continue;
+        int ref = -1;
+        if (majority) {
+            const uint32_t *h = &hist[(size_t)p * 64];
+            uint32_t best = 0;
+            for (uint32_t k = 1; k < 64; ++k)
+                if (h[k] > h[best]) best = k;
+            if (h[best]) ref = (int)best;
+        } else {
+            const size_t r = (size_t)win_begin + pc[p];
+            if (r + 2 < refcodes.size() && refcodes[r] < 4 && refcodes[r + 1] < 4 && refcodes[r + 2] < 4)
+                ref = 16 * refcodes[r] + 4 * refcodes[r + 1] + refcodes[r + 2];
+        }
+        R.del_rows.push_back({pg[p], pk[p], ref, dc});
+    }
     return nullptr;
 }
 
