@@ -245,12 +245,19 @@ int jl_group_create(jl_ctx *const *ctxs, uint32_t n_ctx, jl_group **out)
 void jl_group_destroy(jl_group *g)
 {
     if (!g) return;
+    bool live;   // still in the list: none of its contexts has been destroyed (jl_group_forget_ctx)
     {
         std::lock_guard<std::mutex> lk(g_live_mu);
+        live = std::find(g_live.begin(), g_live.end(), g) != g_live.end();
         g_live.erase(std::remove(g_live.begin(), g_live.end(), g), g_live.end());
     }
     hipSetDevice(g->device);
     if (g->stream) hipStreamSynchronize(g->stream);
+    // The windows outlive the group and their last run was enqueued on its stream, which goes away below: everything of that run
+    // is done now, so their fetches (and whatever else waits on "the stream of the last run") go back to their own streams.
+    if (live)
+        for (jl_ctx *c : g->ctxs)
+            if (c->run_stream == g->stream) c->run_stream = c->stream;
     group_drop_graphs(g);
     if (g->x_host) hipHostFree(g->x_host);
     if (g->x_dev) hipFree(g->x_dev);

@@ -515,3 +515,28 @@ int jl_launch_pileup_group(jl_ctx *const *ctxs, uint32_t n_win, const jl_win_pil
     else hipLaunchKernelGGL((pileup_planes_group_kernel<6, 2>), dim3(max_chunks, 1, n_win), dim3(256), 0, st, args);
     return JL_OK;
 }
+
+#ifdef JL_TUNING
+// test hook of the -DJL_TUNING build (beside jl_tuning_group_forms, capi_group.hip): the launch shape of a context whose plan is
+// built, so that a test knows which kernel form it ran.  out[0..11] = chunk width; NQ and tiles of a single run; NQ and tiles of a
+// grouped run; n_chunks; read splits of a single run (gridDim.y); can_fold; resident blocks per CU of the single run's kernel;
+// chunks on the fast stream; chunks that load their halo; tiles per flush batch of a single run.
+extern "C" __attribute__((visibility("default"))) int jl_tuning_pileup_shape(jl_ctx *ctx, uint32_t *out)
+{
+    if (!ctx || !out || !ctx->plan_valid) return JL_ERR_ARG;
+    std::vector<uint2> recs(ctx->n_chunks);
+    if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess ||
+        (ctx->n_chunks && hipMemcpy(recs.data(), ctx->d_chunks.as<const uint2>(), recs.size() * sizeof(uint2), hipMemcpyDeviceToHost) != hipSuccess))
+        return JL_ERR_DEVICE;
+    uint32_t n_fast = 0, n_halo = 0;
+    for (const uint2 &r : recs) {
+        n_fast += ctx->pileup_w == 3 && r.y == JL_CHUNK_META(3, 1, 0);
+        n_halo += (r.y >> 16) & 1u;
+    }
+    const uint32_t v[12] = {ctx->pileup_w, (uint32_t)planes_nq(ctx, false), planes_tiles(ctx, false), (uint32_t)planes_nq(ctx, true),
+                            planes_tiles(ctx, true), ctx->n_chunks, jl_pileup_rsplit(ctx), (uint32_t)jl_pileup_can_fold(ctx),
+                            (uint32_t)ctx->pileup_blocks_per_cu[planes_slot(ctx)], n_fast, n_halo, plane_flush_tiles(planes_nq(ctx, false))};
+    memcpy(out, v, sizeof v);
+    return JL_OK;
+}
+#endif

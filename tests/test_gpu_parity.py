@@ -107,7 +107,10 @@ def test_fisher_device_vs_oracle_random(jl, oracle):
 
 
 # --------------------------------------------------------------------------------------------- pileup
-SHAPES = [  # n_reads, n_cols, partial_rate  — ragged sizes around the 8192-read tile and the 12-column chunk
+# n_reads, n_cols, partial_rate — small ragged sizes; with the three overlapping genes below every row takes the 6-column chunk
+# table, whose tile is 16 384 reads (only the last two rows reach a second one).  The edges of the bit-plane kernels — tiles, flush
+# batches, load widths, narrow closing chunks, every instantiation — are in tests/test_gpu_pileup_edges.py.
+SHAPES = [
     (1, 3, 0.0), (2, 4, 0.0), (63, 12, 0.0), (64, 13, 0.5), (300, 11, 0.2), (1000, 36, 0.0), (1001, 37, 0.3),
     (8192, 24, 0.0), (8193, 25, 0.1), (20000, 50, 0.2), (33000, 14, 0.0),
 ]
