@@ -422,6 +422,53 @@ typedef struct {
  * above 2^32 - 1. */
 int jl_deletion_test(const uint32_t cnt[4], const jl_params *prm, double n_tests, jl_deletion_call *out);
 /*
+ * In-frame insertion ALLELES of a record build (docs/SPEC.md §17).  An insertion never enters the matrix (J:26-27) and the
+ * counters of jl_msa_track_insertions lose the joint sequence, have no denominator and apply no QV filter.  With this switch on,
+ * the next record build INTO `ctx` (jl_records_finish, jl_records_window[_async], jl_msa_ingest_records[_masked]) also forms, on
+ * the window's stream, per junction c (between window columns c - 1 and c, 1 <= c < n_cols; row 0 exists and stays zero)
+ *   jcnt[c] = {span, inframe, frameshift, unread}, 32 bits each, exact, independent of launch shape and order:
+ *     span        reads whose matrix cells at c - 1 and c are both covered (code != 6), counted from the resident planes
+ *   and of the reads spanning c whose 'I' ops between the two reference-consuming ops around the junction — all of them, 'S',
+ *   'H', 'P' and empty ops do not separate them — add up to L > 0 bases, each in exactly one of
+ *     inframe     L % 3 == 0, 3 <= L <= 30, every inserted base exactly A, C, G or T and past the build's QV filter
+ *     frameshift  L % 3 != 0
+ *     unread      L % 3 == 0 and (L > 30 or some base is not readable)
+ * and the table of the distinct (col = c, len = L, seq) among the inframe reads with their read counts: base j of the
+ * insertion (A C G T = 0..3) in bits 2 j, 2 j + 1 of seq, the bits above 2 L zero; len is part of the key (AAA and AAAAAA have one
+ * seq).  An insertion of a read that does not span its junction — at the read's first or last aligned base, next to an 'N' op,
+ * outside 1 .. n_cols - 1 — counts nowhere.  The counters of jl_msa_track_insertions, the matrix and every stage are untouched.
+ */
+typedef struct {
+    uint32_t col, len;
+    uint64_t seq;
+    uint32_t count, pad_;
+} jl_insertion_allele;
+int jl_msa_track_insertion_alleles(jl_ctx *ctx, int on);
+/* Wait, and copy out jcnt[n_cols][4] (NULL: not wanted) and the table, sorted ascending by (col, len, seq): *n_rows (NULL: not
+ * wanted) = its rows; rows == NULL returns only that count, else `cap` rows of room are needed.  JL_ERR_STATE: the last build into
+ * `ctx` did not track, or a later call replaced the matrix (jl_msa_take, jl_msa_upload, ...).  JL_ERR_ARG: cap is too small. */
+int jl_insertion_alleles_fetch(jl_ctx *ctx, uint32_t *jcnt /* [n_cols][4] */, jl_insertion_allele *rows, uint32_t cap, uint32_t *n_rows);
+/* One allele of that table tested against `rate`, the probability that a read shows ANY in-frame insertion at a junction by
+ * error (used for one specific sequence: conservative): coverage = span - frameshift - unread (the reads with no insertion there
+ * and the reads with a readable in-frame one), expected = round_mode(coverage * rate) clamped to [0, coverage]
+ * (prm->expected_round, the product in IEEE double), the table [[count, coverage - count], [expected, coverage - expected]], p by
+ * prm->tail from the routines of the codon test, p_value = min(1, p * n_tests), called = count > 0 and p_value < prm->alpha and
+ * the prm->min_perc / max_perc filters on 100 count / coverage (strict).  coverage == 0: not called, p_value 1, log_p 0. */
+typedef struct {
+    uint32_t count;
+    uint32_t coverage;    /* span - frameshift - unread */
+    uint32_t expected;
+    uint32_t frameshift;  /* jcnt[2], jcnt[3]: not part of the test */
+    uint32_t unread;
+    uint32_t called;      /* 0 or 1 */
+    double p_value;       /* Bonferroni-adjusted, <= 1 */
+    double log_p;         /* ln of the unadjusted p */
+} jl_insertion_call;
+/* Host only (no device, no context).  jcnt: one junction's row of jl_insertion_alleles_fetch; n_tests: the Bonferroni factor,
+ * RESOLVED.  JL_ERR_ARG (jl_last_error(NULL) says which): a NULL argument; n_tests <= 0; rate outside [0, 1]; frameshift + unread
+ * above span; count above the coverage. */
+int jl_insertion_test(uint32_t count, const uint32_t jcnt[4], const jl_params *prm, double rate, double n_tests, jl_insertion_call *out);
+/*
  * Reference/majority codon, error model, Fisher's exact x Bonferroni, filters, variant table
  * (SPEC §4-7; J:38-42).  `drm_masks`: optional [P] 64-bit codon masks; with --drm-only a codon is kept
  * only if its bit is set (J:370); NULL disables.  Table stays on the device; enqueues only.

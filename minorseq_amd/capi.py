@@ -28,12 +28,13 @@ VARIANT = np.dtype([("gene", "<u4"), ("codon_pos", "<u4"), ("col", "<u4"), ("ref
 SUMMARY_FIELDS = ("reported_reads", "insufficient_reads", "damaged_reads", "marginal_gap", "marginal_heteroduplex",
                   "marginal_partial", "n_positions", "n_haplotypes")
 SUMMARY = np.dtype([(n, "<u4") for n in SUMMARY_FIELDS])
+INSERTION_ALLELE = np.dtype([("col", "<u4"), ("len", "<u4"), ("seq", "<u8"), ("count", "<u4"), ("pad_", "<u4")])   # jl_insertion_allele
 
 # every symbol include/juliet_hip.h declares (checked by tests/test_capi_exports.py)
 EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", "jl_ctx_destroy", "jl_last_error",
            "jl_sync", "jl_col_stride", "jl_plane_stride", "jl_msa_upload", "jl_msa_alloc", "jl_msa_adopt", "jl_msa_pack_rows",
            "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_take", "jl_msa_take_async", "jl_sample_reads", "jl_mix_counts", "jl_msa_download", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
-           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_phase_async", "jl_phase_fetch",
+           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_phase_async", "jl_phase_fetch",
            "jl_ctx_stream", "jl_run_async", "jl_run_wait", "jl_run_done", "jl_run_view_get", "jl_group_create", "jl_group_destroy",
            "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
            "jl_allgather_variants", "jl_allgather_variants_async", "jl_allgather_variants_async_many", "jl_allgather_variants_many", "jl_group_exchange_bind", "jl_group_exchange_collect", "jl_xwin_plan", "jl_xwin_assemble_local",
@@ -213,6 +214,9 @@ def load_library(path=LIB_PATH):
     lib.jl_codon_deletions_async.argtypes = [vp]
     lib.jl_codon_deletions_fetch.argtypes = [vp, vp]
     lib.jl_deletion_test.argtypes = [vp, vp, C.c_double, vp]
+    lib.jl_msa_track_insertion_alleles.argtypes = [vp, C.c_int]
+    lib.jl_insertion_alleles_fetch.argtypes = [vp, vp, vp, u32, vp]
+    lib.jl_insertion_test.argtypes = [u32, vp, vp, C.c_double, C.c_double, vp]
     lib.jl_call_async.argtypes = [vp, C.POINTER(Params), vp]
     lib.jl_call_fetch.argtypes = [vp, vp, u32, C.POINTER(u32)]
     lib.jl_variant_table_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u32)]
@@ -444,6 +448,22 @@ class Juliet:
         bc = np.zeros((self.n_cols, 30, 4), dtype=np.uint32)
         self._chk(self.lib.jl_insertions_fetch(self.h, _p(lh), _p(bc)))
         return lh, bc
+
+    def track_insertion_alleles(self, on=True):
+        """jl_msa_track_insertion_alleles (docs/SPEC.md §17): the next record build into this context also forms the junction
+        counters and the table of in-frame insertion alleles."""
+        self._chk(self.lib.jl_msa_track_insertion_alleles(self.h, 1 if on else 0))
+
+    def insertion_alleles(self):
+        """(jcnt uint32[n_cols][4] = span, inframe, frameshift, unread per junction; rows INSERTION_ALLELE[n], ascending by
+        (col, len, seq)) of the last record build with track_insertion_alleles on."""
+        jcnt = np.zeros((self.n_cols, 4), dtype=np.uint32)
+        n = C.c_uint32(0)
+        self._chk(self.lib.jl_insertion_alleles_fetch(self.h, _p(jcnt), None, 0, C.byref(n)))
+        rows = np.zeros(n.value, dtype=INSERTION_ALLELE)
+        if n.value:
+            self._chk(self.lib.jl_insertion_alleles_fetch(self.h, None, _p(rows), n.value, C.byref(n)))
+        return jcnt, rows
 
     def alloc(self, n_reads, n_cols, win_begin=0):
         self._chk(self.lib.jl_msa_alloc(self.h, n_reads, n_cols, win_begin))
@@ -951,6 +971,27 @@ def deletion_test(cnt, params, n_tests):
     if rc:
         raise JulietError(rc, "jl_deletion_test: " + lib.jl_last_error(None).decode())
     d = {name: getattr(out, name) for name, _ in DeletionCall._fields_ if name != "pad_"}
+    d["called"] = bool(d["called"])
+    return d
+
+
+class InsertionCall(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("coverage", C.c_uint32), ("expected", C.c_uint32), ("frameshift", C.c_uint32),
+                ("unread", C.c_uint32), ("called", C.c_uint32), ("p_value", C.c_double), ("log_p", C.c_double)]
+
+
+def insertion_test(count, jcnt, params, rate, n_tests):
+    """jl_insertion_test (host only, docs/SPEC.md §17): `count` reads of one allele at a junction whose row of
+    Juliet.insertion_alleles()[0] is jcnt = (span, inframe, frameshift, unread), against `rate`, with the codon test's resolved
+    Bonferroni factor n_tests: dict(count, coverage, expected, frameshift, unread, called, p_value = min(1, p * n_tests), log_p)."""
+    lib = load_library()
+    jcnt = np.ascontiguousarray(jcnt, dtype=np.uint32)
+    assert jcnt.shape == (4,)
+    out = InsertionCall()
+    rc = lib.jl_insertion_test(int(count), _p(jcnt), C.byref(params), float(rate), float(n_tests), C.byref(out))
+    if rc:
+        raise JulietError(rc, "jl_insertion_test: " + lib.jl_last_error(None).decode())
+    d = {name: getattr(out, name) for name, _ in InsertionCall._fields_}
     d["called"] = bool(d["called"])
     return d
 

@@ -109,6 +109,10 @@ static int records_append(jl_ctx *ctx, uint64_t n_reads, const int32_t *pos, con
             R.maybe_long = looked > n_reads + 4096u || jl_ingest_read_is_long(cigar + cig_off[r], n_ops);
         }
     }
+    // ... and the chunk's 'I' ops, which size the allele table of a build that tracks insertion alleles (docs/SPEC.md §17; whether
+    // one will is not known here: the switch belongs to the window).  A compare and an add a word, no branch.
+    uint64_t n_ins = 0;
+    for (uint64_t k = cig_off[0]; k < cig_off[n_reads]; ++k) n_ins += (cigar[k] & 15u) == 1u;
     JL_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     // the chunk's arrays start wherever its offsets say; on the device everything is one run of arrays
@@ -159,6 +163,7 @@ static int records_append(jl_ctx *ctx, uint64_t n_reads, const int32_t *pos, con
     R.masked = masked;
     R.n_reads += n_reads;
     R.n_cig += n_cig;
+    R.n_ins_ops += n_ins;
     R.n_seq = seq_at + n_seq;
     R.n_qual += n_q;
     return JL_OK;
@@ -212,9 +217,44 @@ static hipError_t reserve_insertions(jl_ctx *dst, uint32_t n_cols)
     return e;
 }
 
+// the junction counters and the allele table of `dst` for a build from R, emptied on its stream (docs/SPEC.md §17)
+static hipError_t reserve_insertion_alleles(jl_ctx *dst, const jl_records &R, uint32_t n_cols)
+{
+    hipStream_t st = dst->stream;
+    uint64_t slots = 64;   // a power of two, at least twice the 'I' ops: an allele needs one
+    while (slots < 2u * R.n_ins_ops) slots *= 2u;
+    dst->insal_slots = slots;
+    hipError_t e = dst->insal_jcnt.grow_discard(st, (size_t)n_cols * 4u);
+    if (e == hipSuccess) e = dst->insal_keys.grow_discard(st, (size_t)slots * 2u);
+    if (e == hipSuccess) e = dst->insal_count.grow_discard(st, (size_t)slots * 2u + 1u);
+    if (e == hipSuccess) e = hipMemsetAsync(dst->insal_jcnt, 0, (size_t)n_cols * 16u, st);
+    if (e == hipSuccess) e = hipMemsetAsync(dst->insal_keys, 0xFF, (size_t)slots * 16u, st);
+    // (the counts and n_occ; occ[] between them is written before it is read)
+    if (e == hipSuccess) e = hipMemsetAsync(dst->insal_count, 0, ((size_t)slots * 2u + 1u) * 4u, st);
+    return e;
+}
+
+// the record walk of a tracking build: the filter as jl_launch_ingest resolves it
+static void launch_insertion_alleles(jl_ctx *dst, const jl_records &R, uint32_t min_qv)
+{
+    const jl_qv_mode mode = jl_qv_mode_of(R.have_qual, R.masked, min_qv);
+    jl_insal_args a = {};
+    a.n_reads = dst->n_reads, a.n_cols = dst->n_cols, a.win_begin = dst->win_begin;
+    a.min_qv = std::min<uint32_t>(min_qv, 127u);
+    a.pos = R.pos, a.cigar = R.cig, a.cig_off = R.co, a.seq4 = R.seq, a.seq_off = R.so;
+    a.qual = mode == JL_QV_BYTES ? R.qual : nullptr;
+    a.qual_off = mode == JL_QV_BYTES ? R.qo : nullptr;
+    a.qmask = mode == JL_QV_MASK ? R.mask : nullptr;
+    a.jcnt = dst->insal_jcnt;
+    a.key0 = dst->insal_keys, a.key1 = dst->insal_keys + dst->insal_slots;
+    a.count = dst->insal_count, a.occ = dst->insal_count + dst->insal_slots, a.n_occ = dst->insal_count + 2u * dst->insal_slots;
+    a.slots_mask = dst->insal_slots - 1u;
+    jl_launch_insertion_alleles(&a, dst->stream);
+}
+
 // The resident matrix of `dst` from the records uploaded to `src` (the same context for jl_records_finish; another one of
 // the same device when one upload feeds several column windows).  The records stay.  Everything is ENQUEUED on dst's
-// stream (three launches + the insertion counters when asked for); `wait`: return when it has run.
+// stream (three launches + the insertion counters and the insertion alleles when asked for); `wait`: return when it has run.
 static int records_build(jl_ctx *src, jl_ctx *dst, uint32_t n_cols, uint32_t win_begin, uint32_t min_qv, bool wait)
 {
     const jl_records &R = src->rec;
@@ -245,10 +285,29 @@ static int records_build(jl_ctx *src, jl_ctx *dst, uint32_t n_cols, uint32_t win
             dst->ins_valid = e == hipSuccess;
         }
     }
+    dst->insal_valid = false;
+    if (e == hipSuccess && dst->track_ins_alleles) {
+        e = reserve_insertion_alleles(dst, R, n_cols);
+        if (e == hipSuccess) {
+            launch_insertion_alleles(dst, R, min_qv);
+            e = hipGetLastError();
+        }
+    }
     if (e == hipSuccess) {
         jl_launch_ingest(dst, R, min_qv);
         e = hipGetLastError();
         S.check_pending = e == hipSuccess;
+        if (e == hipSuccess && dst->track_ins_alleles) {   // the reads spanning every junction, from the planes just built
+            if (n_cols >= 2u) {
+                jl_insal_span_args sa = {};
+                sa.msa = dst->d_msa, sa.plane_stride = dst->plane_stride;   // (a multiple of 16, >= ceil(n_reads / 8): set_shape)
+                sa.n_reads = dst->n_reads, sa.n_cols = n_cols;
+                sa.jcnt = dst->insal_jcnt;
+                jl_launch_junction_span(&sa, st);
+                e = hipGetLastError();
+            }
+            dst->insal_valid = e == hipSuccess;
+        }
         if (e == hipSuccess && wait) e = hipStreamSynchronize(st);
     }
     if (e != hipSuccess) return hip_fail(dst, "ingest", e);

@@ -389,6 +389,42 @@ struct jl_del_args {
 };
 void jl_launch_codon_deletions(const jl_del_args *a, hipStream_t st);
 
+// ---- in-frame insertion alleles of a record build (kernels_ins.hip, capi_ins.hip; docs/SPEC.md §17)
+#define JL_INSAL_MAX_BASES 30u             // longest insertion that is an allele: 60 bits of sequence
+struct jl_insal_args {
+    // the records (jl_records: one run of device arrays) and the window
+    uint64_t n_reads;
+    uint32_t n_cols, win_begin;
+    uint32_t min_qv, pad_;     // min_qv at most 127, as the planes kernel takes it
+    const int32_t *pos;
+    const uint32_t *cigar;
+    const uint64_t *cig_off;
+    const uint8_t *seq4;
+    const uint64_t *seq_off;
+    const uint8_t *qual;       // the filter in force, as jl_launch_ingest resolves it: quality bytes, or
+    const uint64_t *qual_off;
+    const uint8_t *qmask;      // a bit per base, or neither
+    uint32_t *jcnt;            // [n_cols][4] span, inframe, frameshift, unread; zeroed
+    // the allele table: `slots` (a power of two, at least twice the I ops of the records) of key words (col << 32 | len) and
+    // (seq), all ones = empty, and their read counts, zeroed; occ[] lists the slots in use, *n_occ (zeroed) how many
+    unsigned long long *key0, *key1;
+    uint32_t *count, *occ, *n_occ;
+    uint64_t slots_mask;
+};
+void jl_launch_insertion_alleles(const jl_insal_args *a, hipStream_t st);
+struct jl_insal_span_args {
+    const uint8_t *msa;        // the window's bit planes
+    uint64_t plane_stride;
+    uint64_t n_reads;
+    uint32_t n_cols;           // >= 2
+    uint32_t seg_tiles;        // tiles of 512 reads a workgroup walks (set by the launcher)
+    uint32_t *jcnt;            // [n_cols][4]: [c][0] += reads whose cells at c - 1 and c are both covered
+};
+void jl_launch_junction_span(const jl_insal_span_args *a, hipStream_t st);
+// the occupied slots of the table as rows, in the order of occ[] (capi_ins.hip sorts them on the host)
+void jl_launch_insertion_rows(const unsigned long long *key0, const unsigned long long *key1, const uint32_t *count, const uint32_t *occ,
+                              uint32_t n, jl_insertion_allele *rows, hipStream_t st);
+
 inline int jl_hip_status(hipError_t e) { return e == hipErrorOutOfMemory ? JL_ERR_MEMORY : JL_ERR_DEVICE; }
 
 // ---- owning arrays.  Every buffer a context owns is one of these: it frees itself when the context is deleted (jl_ctx_destroy, the
@@ -497,6 +533,7 @@ struct jl_records {
     jl_dev_array<uint64_t> co, so, qo;   // the reads' offsets into cig, seq, qual
     jl_dev_array<int32_t> pos;
     uint64_t n_reads = 0, n_cig = 0, n_seq = 0, n_qual = 0;
+    uint64_t n_ins_ops = 0;  // 'I' ops among the cigar words so far: what the allele table of a tracking build is sized from (docs/SPEC.md §17)
     // does any read need the ingest's launch for long reads (kernels_ingest.hip jl_ingest_read_is_long)?  Found out at the upload for
     // the few reads a CCS sample has with more ops than entries fit; `true` as soon as looking would cost more than the launch
     bool maybe_long = false;
@@ -505,7 +542,7 @@ struct jl_records {
     {
         seq.release(), qual.release(), mask.release(), cig.release(), co.release(), so.release(), qo.release(), pos.release();
         open = have_qual = masked = maybe_long = false;
-        n_reads = n_cig = n_seq = n_qual = 0;
+        n_reads = n_cig = n_seq = n_qual = n_ins_ops = 0;
     }
 };
 
@@ -568,6 +605,15 @@ struct jl_ctx {
     bool ins_valid = false;
     jl_dev_array<uint32_t> d_ins_len;    // [n_cols][JL_INS_LEN_BINS]
     jl_dev_array<uint32_t> d_ins_base;   // [n_cols][JL_INS_MAX_BASES][4]
+
+    // ---- in-frame insertion alleles of the last record build (docs/SPEC.md §17; off unless jl_msa_track_insertion_alleles)
+    bool track_ins_alleles = false;
+    bool insal_valid = false;                      // gone with the matrix they belong to: set_shape
+    jl_dev_array<uint32_t> insal_jcnt;             // [n_cols][4]
+    jl_dev_array<unsigned long long> insal_keys;   // key0 [insal_slots], then key1 [insal_slots]
+    jl_dev_array<uint32_t> insal_count;            // count [insal_slots], occ [insal_slots], n_occ [1]
+    jl_dev_array<jl_insertion_allele> insal_rows;  // the fetch's gather
+    uint64_t insal_slots = 0;                      // of the last tracking build
 
     // ---- aligned records on their way in (jl_records_begin / _append / _finish)
     jl_records rec;

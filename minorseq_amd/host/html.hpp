@@ -159,6 +159,31 @@ inline std::string render_html(const Json &root)
             h += "</details>\n";
         }
     }
+    // ---- --call-insertions (docs/SPEC.md §17): the called insertion alleles, a table per gene; doubles as the JSON prints them
+    if (const Json *genes = root.get("genes")) {
+        bool any = false;
+        for (const Json &g : genes->arr) any = any || g.get("insertion_positions");
+        if (any) {
+            h += "<details open id=\"insertions\"><summary>Codon Insertions</summary>\n";
+            for (const Json &g : genes->arr) {
+                const Json *ips = g.get("insertion_positions");
+                if (!ips) continue;
+                h += "<table class=\"insertions\" data-gene=\"" + html_escape(g.get_str("name")) + "\"><caption>" + html_escape(g.get_str("name")) +
+                     "</caption>\n<tr><th>After pos</th><th>Codons</th><th>AA</th><th>#Reads</th><th>Coverage</th><th>Frequency</th><th>Expected</th>"
+                     "<th>pValue</th><th>log_pValue</th><th>#Frame-shift reads</th><th>#Unread reads</th></tr>\n";
+                for (const Json &d : ips->arr) {
+                    std::string cods;
+                    for (const Json &c : d.get("inserted_codons")->arr) cods += (cods.empty() ? "" : " ") + c.str;
+                    h += "<tr class=\"insertion\">" + td(num_str(d.get("after_position"))) + td(cods) + td(d.get_str("inserted_amino_acids"));
+                    for (const char *key : {"count", "coverage", "frequency", "expected", "pValue", "log_pValue", "frameshift_reads", "unread_reads"})
+                        h += td(num_str(d.get(key)));
+                    h += "</tr>\n";
+                }
+                h += "</table>\n";
+            }
+            h += "</details>\n";
+        }
+    }
     // ---- 4. Drug Summaries (doc/JULIET.md:104-107)
     if (const Json *ds = root.get("drug_summaries")) {
         h += "<details open id=\"drugs\"><summary>Drug Summaries</summary><table id=\"drug-table\"><tr><th>Drug</th><th>Gene</th><th>Mutation</th><th>Codon</th><th>%</th></tr>\n";

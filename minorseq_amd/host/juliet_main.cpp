@@ -138,6 +138,10 @@ int run_one_window(Run &run)
         if (const char *what = fetch_deletions(ctx, opt, smp.prm, smp.genes, smp.refcodes, win_begin, n_cols, R)) die_jl(ctx, what);
         tick("deletions");
     }
+    if (opt.call_insertions) {
+        if (const char *what = fetch_insertions(ctx, opt, smp.prm, smp.genes, n_cols, R)) die_jl(ctx, what);
+        tick("insertions");
+    }
     if (!opt.hap_fasta.empty()) {
         if (const int code = write_haplotype_fasta(opt, ctx, R, win_begin, n_cols)) return code;
         tick("haplotype fasta");

@@ -42,6 +42,9 @@ struct Options {
     bool have_rescue_min = false;
     bool linkage = false;            // --linkage: every pair of called variants over the reads covering both (docs/SPEC.md §15)
     bool call_deletions = false;     // --call-deletions: in-frame codon deletions at every evaluated position (docs/SPEC.md §16)
+    bool call_insertions = false;    // --call-insertions: in-frame insertion alleles before every evaluated position (docs/SPEC.md §17)
+    bool have_insertion_rate = false;
+    double insertion_rate = 0.0;     // --insertion-rate r: a read shows an in-frame insertion at a junction by error (default: the chemistry's deletion rate)
     bool fuse_only = false;        // invoked as `fuse in.bam out.fasta` (doc/FUSE.md:26-31): the consensus and nothing else
     double ins_min_frac = 0.5;     // an insertion enters the consensus when more than this share of the covering reads carries it
     uint32_t ins_min_distance = 10;  // ... and the previous included insertion lies at least this many columns back (UNPINNED)
@@ -121,6 +124,19 @@ struct Options {
         "                                      deletion breaks the codon: not part of the test).  Empty with --drm-only.  Phasing\n"
         "                                      is unchanged.  Follows --downsample / --mix.  Not with --windows, --devices a,b,\n"
         "                                      --batch or as fuse\n"
+        "      --call-insertions [--insertion-rate r]  in-frame insertions by inserted sequence (docs/SPEC.md section 17), with and\n"
+        "                                      without --mode-phasing: during the record ingest the device forms the distinct\n"
+        "                                      (junction, length, sequence) among the reads whose insertion between two aligned\n"
+        "                                      bases is 3 .. 30 bases long, a multiple of 3 and readable (A C G T past --min-qv), with\n"
+        "                                      their read counts, and the reads spanning every junction.  Every allele in front of an\n"
+        "                                      evaluated codon position (not a gene's first) is tested by the codon test's own Fisher\n"
+        "                                      test, Bonferroni factor and --min-perc / --max-perc against r, the rate of in-frame\n"
+        "                                      insertions by error (default: the chemistry's deletion rate), over coverage = reads\n"
+        "                                      spanning the junction - frame-shifting - unreadable ones.  Every gene of the JSON gains\n"
+        "                                      `insertion_positions`: after_position, inserted_codons, inserted_amino_acids, count,\n"
+        "                                      coverage, frequency, expected, pValue, log_pValue, frameshift_reads, unread_reads.  An\n"
+        "                                      insertion that splits a codon of a gene is not reported for it.  Empty with\n"
+        "                                      --drm-only.  Not with --windows, --devices a,b, --batch, --downsample, --mix or as fuse\n"
         "      --downsample N [--sample-seed S]  call on N reads of the sample (\"downsample it to 6000x\", doc/JULIETFLOW.md:23-25):\n"
         "                                      the reads are chosen by docs/SPEC.md section 12 (seed default 0; samples of one seed are\n"
         "                                      nested) and gathered on the device; N at or above the read count changes nothing.\n"
@@ -260,6 +276,17 @@ Options parse(int argc, char **argv)
         else if (a == "--rescue-damaged") o.rescue = true;
         else if (a == "--linkage") o.linkage = true;
         else if (a == "--call-deletions") o.call_deletions = true;
+        else if (a == "--call-insertions") o.call_insertions = true;
+        else if (a == "--insertion-rate") {
+            const std::string v = need(i);
+            char *end = nullptr;
+            o.insertion_rate = std::strtod(v.c_str(), &end);
+            o.have_insertion_rate = true;
+            if (v.empty() || *end || !(o.insertion_rate >= 0.0 && o.insertion_rate <= 1.0)) {
+                std::cerr << "juliet: --insertion-rate wants a probability in [0, 1], not '" << v << "'\n";
+                std::exit(1);
+            }
+        }
         else if (a == "--rescue-min-positions") { o.rescue_min = (uint32_t)std::stoul(need(i)); o.have_rescue_min = true; }
         else if (a == "--ins-min-frac") o.ins_min_frac = std::stod(need(i));
         else if (a == "--ins-min-distance") o.ins_min_distance = (uint32_t)std::stoul(need(i));
@@ -312,6 +339,14 @@ Options parse(int argc, char **argv)
         if (as_fuse) refuse("is not an option of fuse");
         if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
         if (!o.batch.empty()) refuse("is not part of a batch (not with --batch)");
+    }
+    if (o.call_insertions || o.have_insertion_rate) {   // refused here, before any file is read or any GPU work
+        auto refuse = [](const char *why) { std::cerr << "juliet: --call-insertions [--insertion-rate r] " << why << "\n"; std::exit(1); };
+        if (!o.call_insertions) refuse("--insertion-rate sets the error rate of --call-insertions (add it)");
+        if (as_fuse) refuse("are not options of fuse");
+        if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
+        if (!o.batch.empty()) refuse("is not part of a batch (not with --batch)");
+        if (o.sampling()) refuse("reads the insertions of the records that were ingested, not of a sample of them (drop --downsample / --mix)");
     }
     if (o.sampling()) {   // what sampling cannot be combined with is refused here, before any file is read or any GPU work
         auto refuse = [&](const char *why) { std::cerr << "juliet: " << (o.mix.empty() ? "--downsample " : "--mix ") << why << "\n"; std::exit(1); };

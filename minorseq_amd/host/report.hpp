@@ -157,6 +157,30 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
             }
             gj.set("deletion_positions", dps);
         }
+        if (R.insertions) {   // --call-insertions (docs/SPEC.md §17): the called alleles of this gene, by position, length, sequence
+            Json ips = Json::array();
+            for (const Results::Insertion &in : R.ins_rows) {
+                if (in.gene != g) continue;
+                Json ij = Json::object();
+                ij.set("after_position", Json::of(in.codon_pos + cfg.genes[g].first_codon - 1));
+                Json cods = Json::array();
+                std::string aas;
+                for (uint32_t k = 0; k + 3 <= in.allele.len; k += 3) {
+                    const uint8_t codon = (uint8_t)(16u * ((in.allele.seq >> (2u * k)) & 3u) + 4u * ((in.allele.seq >> (2u * k + 2u)) & 3u) +
+                                                    ((in.allele.seq >> (2u * k + 4u)) & 3u));
+                    cods.push(Json::of(codon_string(codon)));
+                    aas += translate(codon);
+                }
+                ij.set("inserted_codons", cods).set("inserted_amino_acids", Json::of(aas));
+                ij.set("count", Json::of(in.call.count)).set("coverage", Json::of(in.call.coverage));
+                ij.set("frequency", Json::of((double)in.call.count / (double)in.call.coverage));
+                ij.set("expected", Json::of(in.call.expected));
+                ij.set("pValue", Json::of(in.call.p_value)).set("log_pValue", Json::of(in.call.log_p));
+                ij.set("frameshift_reads", Json::of(in.call.frameshift)).set("unread_reads", Json::of(in.call.unread));
+                ips.push(ij);
+            }
+            gj.set("insertion_positions", ips);
+        }
         genes_json.push(gj);
     }
     root.set("genes", genes_json);

@@ -59,6 +59,10 @@ struct Results {
     struct Deletion { uint32_t gene, codon_pos; int ref_codon; jl_deletion_call call; };
     bool deletions = false;
     std::vector<Deletion> del_rows;
+    // --call-insertions (docs/SPEC.md §17): the called alleles in (gene, codon, length, sequence) order; codon_pos: the position they precede
+    struct Insertion { uint32_t gene, codon_pos; jl_insertion_allele allele; jl_insertion_call call; };
+    bool insertions = false;
+    std::vector<Insertion> ins_rows;
     // the haplotype a damaged read was assigned to, or JL_HAP_DAMAGED; a read that is not damaged: its own id
     uint16_t hap_with_rescued(uint64_t i) const
     {
@@ -290,6 +294,42 @@ const char *fetch_deletions(jl_ctx *ctx, const Options &opt, const jl_params &pr
     return nullptr;
 }
 
+// --call-insertions, after fetch_calls: the junction counters and the allele table the record ingest of this window left (docs/SPEC.md
+// §17), then the test of every allele whose junction is the start column of an evaluated codon position that is not its gene's
+// first, with the run's own parameters and resolved Bonferroni factor.  An allele that splits a codon of a gene is none of that
+// gene's.  --drm-only: no DRM notation names an insertion, nothing is tested.
+const char *fetch_insertions(jl_ctx *ctx, const Options &opt, const jl_params &prm, const std::vector<jl_gene> &genes, uint32_t n_cols, Results &R)
+{
+    R.insertions = true;
+    R.ins_rows.clear();
+    if (opt.drm_only) return nullptr;
+    std::vector<uint32_t> jcnt((size_t)n_cols * 4);
+    uint32_t n = 0;
+    if (jl_insertion_alleles_fetch(ctx, jcnt.data(), nullptr, 0, &n) != JL_OK) return "insertion alleles";
+    std::vector<jl_insertion_allele> rows(n);
+    if (n && jl_insertion_alleles_fetch(ctx, nullptr, rows.data(), n, &n) != JL_OK) return "insertion alleles fetch";
+    const uint32_t P = jl_n_positions(ctx);
+    std::vector<uint32_t> pg(P), pk(P), pc(P);
+    if (P && jl_pileup_fetch(ctx, nullptr, pg.data(), pk.data(), pc.data(), nullptr, nullptr) != JL_OK) return "positions";
+    double n_tests = prm.n_tests;
+    if (!(n_tests > 0.0)) {   // §5: the codons of all genes
+        n_tests = 0.0;
+        for (const jl_gene &g : genes)
+            if (g.begin != 0 && g.end > g.begin) n_tests += (double)((g.end - g.begin) / 3);
+    }
+    const double rate = opt.have_insertion_rate ? opt.insertion_rate : prm.err.deletion;
+    auto by_col = [](const jl_insertion_allele &a, uint32_t col) { return a.col < col; };
+    for (uint32_t p = 0; p < P; ++p) {
+        if (pk[p] == 0 || pc[p] == 0) continue;   // in front of the gene's first codon: not inside the gene
+        for (auto it = std::lower_bound(rows.begin(), rows.end(), pc[p], by_col); it != rows.end() && it->col == pc[p]; ++it) {
+            jl_insertion_call ic;
+            if (jl_insertion_test(it->count, &jcnt[(size_t)pc[p] * 4], &prm, rate, n_tests, &ic) != JL_OK) return "insertion test";
+            if (ic.called) R.ins_rows.push_back({pg[p], pk[p], *it, ic});
+        }
+    }
+    return nullptr;
+}
+
 const Tick quiet_tick = [](const char *) {};   // for the callers that print no laps (--batch, --mix)
 
 IngestOptions ingest_options(const Options &opt)
@@ -368,11 +408,12 @@ SampleLoad load_sample(const std::string &bam, const IngestOptions &io, const st
 }
 
 // The window ingest of a loaded sample on ONE context (K windows ingest per window instead: run_rank).  With a consensus asked
-// for, the insertion counters too: fuse keeps in-frame insertions (doc/FUSE.md:19).
+// for, the insertion counters too: fuse keeps in-frame insertions (doc/FUSE.md:19); with --call-insertions the insertion alleles.
 Status ingest_window(jl_ctx *ctx, uint32_t n_cols, uint32_t win_begin, const Options &opt)
 {
     Status st;
     if (!opt.consensus.empty()) jl_msa_track_insertions(ctx, 1);
+    if (opt.call_insertions) jl_msa_track_insertion_alleles(ctx, 1);
     if (const int rc = jl_records_finish(ctx, n_cols, win_begin, opt.min_qv)) {
         st.outcome = Outcome::device;
         st.what = "ingest";
