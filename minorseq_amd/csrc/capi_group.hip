@@ -617,6 +617,26 @@ __attribute__((visibility("default"))) int jl_tuning_ctx_meta(jl_ctx *ctx, void 
         return JL_ERR_DEVICE;
     return (int)sizeof(jl_phase_meta);
 }
+// ... and the pipeline that phases the context (tests/phase_edges_child.py asserts which form a case ran): out[0..3] = the
+// jl_phase_form, key words the key buffer holds, workgroups of the window's phasing grid, whether a launch of this window alone
+// writes the per-read ids itself (inline ids).
+__attribute__((visibility("default"))) int jl_tuning_phase_form(jl_ctx *ctx, uint32_t *out)
+{
+    if (!ctx || !out) return JL_ERR_ARG;
+    out[0] = (uint32_t)ctx->phase_form;
+    out[1] = ctx->keys_words;
+    out[2] = jl_phase_grid_blocks(ctx);
+    out[3] = jl_phase_ids_inline(&ctx, 1) ? 1u : 0u;
+    return JL_OK;
+}
+// ... and who wrote the per-read ids of the group's last launch configuration: out[k] = 1 where chunk k's phasing launch wrote
+// them itself (inline ids), 0 where the separate launch did.  Returns the number of chunks, or a negative status.
+__attribute__((visibility("default"))) int jl_tuning_group_ids_inline(jl_group *g, uint32_t *out, uint32_t cap)
+{
+    if (!g || !out || g->chunks.size() > cap) return JL_ERR_ARG;
+    for (size_t k = 0; k < g->chunks.size(); ++k) out[k] = g->chunks[k].ids_inline ? 1u : 0u;
+    return (int)g->chunks.size();
+}
 #endif
 
 }  // extern "C"

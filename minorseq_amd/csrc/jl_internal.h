@@ -19,7 +19,7 @@
 //                              (group runs choose between the two per launch otherwise: capi_group.hip)
 // Inline ids = the phasing launch writing the per-read ids itself (JL_INLINE_IDS_MAX_BLOCKS below):
 //   JL_FORCE_IDS_WAIT_TIMEOUT  test hook of the -DJL_TUNING build (tools_tuning/build_tuning_lib.sh): such a launch gives up waiting at
-//                              once (test_fold_timeout_is_rerun_unfolded).  JL_TUNING adds three read-outs besides (capi_group.hip, kernels_pileup.hip), nothing else.
+//                              once (test_fold_timeout_is_rerun_unfolded).  JL_TUNING adds five read-outs besides (capi_group.hip, kernels_pileup.hip), nothing else.
 struct jl_env_switches {
     bool no_fold_call, no_graph, exchange_staged, force_ids_wait_timeout;
 };

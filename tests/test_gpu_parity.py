@@ -255,6 +255,9 @@ def test_filters_min_max_perc_and_drm(jl, oracle):
 
 
 # --------------------------------------------------------------------------------------------- phase
+# Shapes as the synthetic mixtures give them.  The edges of the phasing kernels — 10 / 11, 20 / 21 and 30 / 31 positions, a block's
+# reads and its LDS table, min_reads, the id widths, the selection's capacities, the plan's two paths, the form that only grows —
+# are in tests/test_gpu_phase_edges.py.
 @pytest.mark.parametrize("n,l,partial", [(1000, 3000, 0.0), (5000, 300, 0.2), (9000, 120, 0.0), (64, 30, 0.0)])
 def test_phase_matches_oracle(jl, oracle, n, l, partial):
     sp = synth.SynthParams(seed=n + l, minor_permille=(80, 60, 50, 40), partial_rate=partial)
