@@ -422,6 +422,40 @@ typedef struct {
  * above 2^32 - 1. */
 int jl_deletion_test(const uint32_t cnt[4], const jl_params *prm, double n_tests, jl_deletion_call *out);
 /*
+ * The SITE MATRIX (docs/SPEC.md §18): called codon deletions as sites of a haplotype.  Phasing groups reads by their codons at the
+ * variant positions, and a deleted codon is no codon: its carriers are GAP-damaged where the position is a variant position and
+ * invisible where it is not.  This call builds, as jl_xwin_assemble_local does, a compact matrix of chosen codon starts of `src`
+ * — n_reads of `src` x 3 n_sites columns, win_begin 0, plane stride jl_plane_stride(n_reads), site k at columns 3k..3k+2 — with
+ * the deletion sites recoded to a two-letter alphabet, so that jl_phase_async on `pc` groups over codons and deletions alike and
+ * no phasing kernel changes.  Per read and site, by the three codes at col, col + 1, col + 2 of `src` and the classes of
+ * jl_codon_deletions_async:
+ *                                  JL_SITE_CODON, fill 0xFF   JL_SITE_CODON, fill f (0..63)    JL_SITE_DELETION
+ *   codon (all three < 4)          copied                     copied                           A A A (codon JL_SITE_PRESENT)
+ *   del3 (all three == 4)          copied                     the three bases of codon f       A A C (codon JL_SITE_DELETED)
+ *   anything else                  copied                     copied                           copied
+ * "Copied" keeps the three cells, so the damage flags of such a read are those of a plain codon position; only the del3 reads stop
+ * being GAP at a recoded site.  A variant position that is also a called deletion is a codon site filled with a codon that is no
+ * variant row there (its reference codon) FOLLOWED by a deletion site at the same column.  Every bit at or beyond n_reads, out to
+ * the end of every plane row of `pc`, is code 6 — whatever an adopted `src` holds in those bits and whatever its own plane stride
+ * is; bytes of `src` that do not exist read as uncovered.
+ * Whatever `pc` held is replaced, as with jl_msa_alloc.  The call waits on the host for `src`'s stream, stages the table through a
+ * pinned buffer of `pc`'s own, enqueues on `pc`'s stream and returns: later calls on `pc` are stream-ordered behind it.  Nothing
+ * of `src` changes: matrix, insertion counters, stage results and captured graph stay as they are.  A site of a third kind
+ * (an insertion allele) has room in `kind`; the record build keeps no per-read record of the allele a read carries, so none exists.
+ * JL_ERR_STATE: `src` has no resident matrix.  JL_ERR_ARG (jl_last_error(pc) says which): a NULL argument; pc == src; different
+ * devices; n_sites 0 or above JL_SITES_MAX; col + 2 >= src's n_cols; kind above 1; fill neither 0xFF nor <= 63; a fill on a
+ * deletion site; sites not non-decreasing by (col, kind); the same (col, kind) twice.  A refused call changes nothing of `pc`.
+ */
+enum { JL_SITE_CODON = 0, JL_SITE_DELETION = 1 };
+enum { JL_SITE_NO_FILL = 0xFF, JL_SITE_PRESENT = 0 /* AAA */, JL_SITE_DELETED = 1 /* AAC */, JL_SITES_MAX = 4096 };
+typedef struct {
+    uint32_t col;   /* codon start in `src` */
+    uint8_t kind;   /* JL_SITE_CODON, JL_SITE_DELETION */
+    uint8_t fill;   /* JL_SITE_NO_FILL, or the codon a del3 read of a codon site becomes */
+    uint16_t pad_;
+} jl_site;
+int jl_sites_assemble(jl_ctx *pc, jl_ctx *src, const jl_site *sites, uint32_t n_sites);
+/*
  * In-frame insertion ALLELES of a record build (docs/SPEC.md §17).  An insertion never enters the matrix (J:26-27) and the
  * counters of jl_msa_track_insertions lose the joint sequence, have no denominator and apply no QV filter.  With this switch on,
  * the next record build INTO `ctx` (jl_records_finish, jl_records_window[_async], jl_msa_ingest_records[_masked]) also forms, on

@@ -28,13 +28,16 @@ VARIANT = np.dtype([("gene", "<u4"), ("codon_pos", "<u4"), ("col", "<u4"), ("ref
 SUMMARY_FIELDS = ("reported_reads", "insufficient_reads", "damaged_reads", "marginal_gap", "marginal_heteroduplex",
                   "marginal_partial", "n_positions", "n_haplotypes")
 SUMMARY = np.dtype([(n, "<u4") for n in SUMMARY_FIELDS])
+SITE = np.dtype([("col", "<u4"), ("kind", "u1"), ("fill", "u1"), ("pad_", "<u2")])   # jl_site
+SITE_CODON, SITE_DELETION = 0, 1
+SITE_NO_FILL, SITE_PRESENT, SITE_DELETED, SITES_MAX = 0xFF, 0, 1, 4096
 INSERTION_ALLELE = np.dtype([("col", "<u4"), ("len", "<u4"), ("seq", "<u8"), ("count", "<u4"), ("pad_", "<u4")])   # jl_insertion_allele
 
 # every symbol include/juliet_hip.h declares (checked by tests/test_capi_exports.py)
 EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", "jl_ctx_destroy", "jl_last_error",
            "jl_sync", "jl_col_stride", "jl_plane_stride", "jl_msa_upload", "jl_msa_alloc", "jl_msa_adopt", "jl_msa_pack_rows",
            "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_take", "jl_msa_take_async", "jl_sample_reads", "jl_mix_counts", "jl_msa_download", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
-           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_phase_async", "jl_phase_fetch",
+           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_phase_async", "jl_phase_fetch",
            "jl_ctx_stream", "jl_run_async", "jl_run_wait", "jl_run_done", "jl_run_view_get", "jl_group_create", "jl_group_destroy",
            "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
            "jl_allgather_variants", "jl_allgather_variants_async", "jl_allgather_variants_async_many", "jl_allgather_variants_many", "jl_group_exchange_bind", "jl_group_exchange_collect", "jl_xwin_plan", "jl_xwin_assemble_local",
@@ -214,6 +217,7 @@ def load_library(path=LIB_PATH):
     lib.jl_codon_deletions_async.argtypes = [vp]
     lib.jl_codon_deletions_fetch.argtypes = [vp, vp]
     lib.jl_deletion_test.argtypes = [vp, vp, C.c_double, vp]
+    lib.jl_sites_assemble.argtypes = [vp, vp, vp, u32]
     lib.jl_msa_track_insertion_alleles.argtypes = [vp, C.c_int]
     lib.jl_insertion_alleles_fetch.argtypes = [vp, vp, vp, u32, vp]
     lib.jl_insertion_test.argtypes = [u32, vp, vp, C.c_double, C.c_double, vp]
@@ -607,6 +611,19 @@ class Juliet:
         cnt = np.zeros((max(0, getattr(self, "_del_cols", 0) - 2), 4), dtype=np.uint32)
         self._chk(self.lib.jl_codon_deletions_fetch(self.h, _p(cnt) if cnt.size else None))
         return cnt
+
+    def sites_assemble(self, src, sites):
+        """jl_sites_assemble (docs/SPEC.md §18): this context becomes the site matrix of `src` — its reads x 3 len(sites) columns,
+        site k = (col, kind, fill) at columns 3k..3k+2: the three columns at `col` of `src`, the del3 reads of a SITE_DELETION site
+        recoded to codon SITE_DELETED and its codon reads to SITE_PRESENT, the del3 reads of a SITE_CODON site with a fill (0..63)
+        recoded to that codon; everything else copied.  Sites ascend by (col, kind).  Waits on the host for `src`'s stream, enqueues
+        on this context's and returns; phase_async / phase_fetch of this context then group over codon and deletion sites alike."""
+        arr = np.zeros(len(sites), dtype=SITE)
+        for k, (col, kind, fill) in enumerate(sites):
+            arr[k] = (col, kind, fill, 0)
+        self._chk(self.lib.jl_sites_assemble(self.h, src.h, _p(arr) if len(arr) else _p(np.zeros(1, dtype=SITE)), len(arr)))
+        self._shape(src.n_reads, 3 * len(arr))
+        self._keep = None
 
     def call_async(self, params=None, drm_masks=None):
         prm = params or default_params()

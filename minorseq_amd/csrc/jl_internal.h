@@ -389,6 +389,18 @@ struct jl_del_args {
 };
 void jl_launch_codon_deletions(const jl_del_args *a, hipStream_t st);
 
+// ---- the site matrix: chosen codon starts of a matrix, deletion sites recoded (kernels_sites.hip, capi_sites.hip; docs/SPEC.md §18)
+struct jl_sites_args {
+    const uint8_t *src;        // the source's bit planes
+    uint64_t src_stride;       // ... and their stride (an adopted matrix brings its own)
+    uint64_t n_reads;
+    uint8_t *dst;              // [9 n_sites][dst_stride]
+    uint64_t dst_stride;       // jl_plane_stride(n_reads): whole 128-byte lines, whatever src_stride is
+    const jl_site *sites;      // [n_sites], each col + 2 < the source's n_cols
+    uint32_t n_sites, pad_;    // 1 .. JL_SITES_MAX
+};
+void jl_launch_sites_assemble(const jl_sites_args *a, hipStream_t st);
+
 // ---- in-frame insertion alleles of a record build (kernels_ins.hip, capi_ins.hip; docs/SPEC.md §17)
 #define JL_INSAL_MAX_BASES 30u             // longest insertion that is an allele: 60 bits of sequence
 struct jl_insal_args {
@@ -643,6 +655,9 @@ struct jl_ctx {
     // ---- jl_codon_deletions_async: a buffer of its own, grown on demand (capi_del.hip); no stage and no run touches it
     jl_dev_array<uint32_t> del_out;        // cnt [del_cols - 2][4]
     uint32_t del_cols = 0;                 // columns of the last call enqueued (0: none)
+
+    // ---- jl_sites_assemble INTO this context: the site table on its way to the device (capi_sites.hip)
+    jl_upload_staging<jl_site> sites_in;
 
     // ---- phasing sharded by reads: the groups of this matrix exported for the merge (jl_phase_groups_async / _fetch)
     bool phase_export = false;        // the phase launch in flight / last run exported instead of selecting

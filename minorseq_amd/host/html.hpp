@@ -148,10 +148,15 @@ inline std::string render_html(const Json &root)
                 if (!dps) continue;
                 h += "<table class=\"deletions\" data-gene=\"" + html_escape(g.get_str("name")) + "\"><caption>" + html_escape(g.get_str("name")) +
                      "</caption>\n<tr><th>Pos</th><th>Codon</th><th>AA</th><th>#Reads</th><th>Coverage</th><th>Frequency</th><th>Expected</th>"
-                     "<th>pValue</th><th>log_pValue</th><th>#Frame-shift reads</th></tr>\n";
+                     "<th>pValue</th><th>log_pValue</th><th>#Frame-shift reads</th>";
+                if (haps && hb->get("deletion_positions_abs"))   // --phase-deletions (docs/SPEC.md §18): a column per haplotype
+                    for (const Json &hp : haps->arr) h += "<th class=\"hapname\">" + html_escape(hp.get_str("name")) + "</th>";
+                h += "</tr>\n";
                 for (const Json &d : dps->arr) {
                     h += "<tr class=\"deletion\">" + td(num_str(d.get("ref_position"))) + td(d.get_str("ref_codon")) + td(d.get_str("ref_amino_acid"));
                     for (const char *key : {"count", "coverage", "frequency", "expected", "pValue", "log_pValue", "frameshift_reads"}) h += td(num_str(d.get(key)));
+                    if (const Json *hh = d.get("haplotype_hit"))
+                        for (const Json &x : hh->arr) h += x.b ? "<td class=\"hit\">x</td>" : "<td class=\"nohit\"></td>";
                     h += "</tr>\n";
                 }
                 h += "</table>\n";
@@ -203,13 +208,27 @@ inline std::string render_html(const Json &root)
         h += "</table>\n<p id=\"hap-positions\">";
         if (const Json *pc = hb->get("variant_positions_abs"))
             for (const Json &p : pc->arr) h += "<span>" + num_str(&p) + "</span> ";
-        h += "</p>\n<table id=\"hap-table\"><tr><th>Haplotype</th><th>%</th><th>#Reads</th><th>Codons</th><th>Read names</th></tr>\n";
+        h += "</p>\n";
+        const Json *dpa = hb->get("deletion_positions_abs");   // --phase-deletions (docs/SPEC.md §18)
+        if (dpa) {
+            h += "<p id=\"hap-deletion-positions\">";
+            for (const Json &p : dpa->arr) h += "<span>" + num_str(&p) + "</span> ";
+            h += "</p>\n";
+        }
+        h += std::string("<table id=\"hap-table\"><tr><th>Haplotype</th><th>%</th><th>#Reads</th><th>Codons</th>") + (dpa ? "<th>Deletions</th>" : "") +
+             "<th>Read names</th></tr>\n";
         if (haps)
             for (const Json &hp : haps->arr) {
                 h += "<tr>" + td(hp.get_str("name")) + td(format_hap_percent(100.0 * hp.get("frequency")->num)) + td(num_str(hp.get("reads"))) + "<td>";
                 if (const Json *cs = hp.get("codons"))
                     for (size_t i = 0; i < cs->arr.size(); ++i) h += (i ? " " : "") + cs->arr[i].str;
-                h += "</td><td><details><summary>" + std::to_string(hp.get("read_names") ? hp.get("read_names")->arr.size() : 0) + "</summary>";
+                h += "</td>";
+                if (const Json *ds = hp.get("deletions")) {
+                    h += "<td class=\"hap-deletions\">";
+                    for (size_t i = 0; i < ds->arr.size(); ++i) h += std::string(i ? " " : "") + (ds->arr[i].b ? "x" : "-");
+                    h += "</td>";
+                }
+                h += "<td><details><summary>" + std::to_string(hp.get("read_names") ? hp.get("read_names")->arr.size() : 0) + "</summary>";
                 if (const Json *rn = hp.get("read_names"))
                     for (const Json &r : rn->arr) h += "<span class=\"rn\">" + html_escape(r.str) + "</span> ";
                 h += "</details></td></tr>\n";

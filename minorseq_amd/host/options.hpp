@@ -42,6 +42,7 @@ struct Options {
     bool have_rescue_min = false;
     bool linkage = false;            // --linkage: every pair of called variants over the reads covering both (docs/SPEC.md §15)
     bool call_deletions = false;     // --call-deletions: in-frame codon deletions at every evaluated position (docs/SPEC.md §16)
+    bool phase_deletions = false;    // --phase-deletions: the called deletions as sites of the haplotypes (docs/SPEC.md §18)
     bool call_insertions = false;    // --call-insertions: in-frame insertion alleles before every evaluated position (docs/SPEC.md §17)
     bool have_insertion_rate = false;
     double insertion_rate = 0.0;     // --insertion-rate r: a read shows an in-frame insertion at a junction by error (default: the chemistry's deletion rate)
@@ -124,6 +125,14 @@ struct Options {
         "                                      deletion breaks the codon: not part of the test).  Empty with --drm-only.  Phasing\n"
         "                                      is unchanged.  Follows --downsample / --mix.  Not with --windows, --devices a,b,\n"
         "                                      --batch or as fuse\n"
+        "      --phase-deletions               with --mode-phasing --call-deletions: the called deletions are sites of the\n"
+        "                                      haplotypes (docs/SPEC.md section 18).  Phasing runs on a site matrix of the variant\n"
+        "                                      positions and the called deletion positions: reads with the codon deleted carry the\n"
+        "                                      allele instead of being damaged, a deletion at a position without a codon variant\n"
+        "                                      splits the haplotypes that differ by it.  The haplotype block gains\n"
+        "                                      deletion_positions_abs and every haplotype `deletions`; a codon prints --- where\n"
+        "                                      the haplotype has it deleted; every deletion_positions entry gains haplotype_hit.\n"
+        "                                      Not with --rescue-damaged, nor where --call-deletions is refused\n"
         "      --call-insertions [--insertion-rate r]  in-frame insertions by inserted sequence (docs/SPEC.md section 17), with and\n"
         "                                      without --mode-phasing: during the record ingest the device forms the distinct\n"
         "                                      (junction, length, sequence) among the reads whose insertion between two aligned\n"
@@ -276,6 +285,7 @@ Options parse(int argc, char **argv)
         else if (a == "--rescue-damaged") o.rescue = true;
         else if (a == "--linkage") o.linkage = true;
         else if (a == "--call-deletions") o.call_deletions = true;
+        else if (a == "--phase-deletions") o.phase_deletions = true;
         else if (a == "--call-insertions") o.call_insertions = true;
         else if (a == "--insertion-rate") {
             const std::string v = need(i);
@@ -339,6 +349,13 @@ Options parse(int argc, char **argv)
         if (as_fuse) refuse("is not an option of fuse");
         if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
         if (!o.batch.empty()) refuse("is not part of a batch (not with --batch)");
+    }
+    if (o.phase_deletions) {   // refused here, before any file is read or any GPU work
+        auto refuse = [](const char *why) { std::cerr << "juliet: --phase-deletions " << why << "\n"; std::exit(1); };
+        if (as_fuse) refuse("is not an option of fuse");
+        if (!o.phasing) refuse("adds sites to the haplotypes of a phasing run (add --mode-phasing)");
+        if (!o.call_deletions) refuse("phases the deletions that --call-deletions calls (add it)");
+        if (o.rescue) refuse("leaves no deletion for --rescue-damaged to judge as damage (drop one of the two)");
     }
     if (o.call_insertions || o.have_insertion_rate) {   // refused here, before any file is read or any GPU work
         auto refuse = [](const char *why) { std::cerr << "juliet: --call-insertions [--insertion-rate r] " << why << "\n"; std::exit(1); };

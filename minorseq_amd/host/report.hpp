@@ -110,7 +110,8 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
                     cj.set("known_drm", Json::of(cfg.known_drms(g, aa_pos, aa)));
                     if (opt.phasing) {
                         Json hh = Json::array();
-                        for (uint32_t h = 0; h < H; ++h) hh.push(Json::of(hit[(size_t)k * R.hit_stride + h] != 0));
+                        const size_t row = R.sites_phased && !R.sites.empty() ? R.var_row[k] : k;   // (§18: the row of the site matrix's table)
+                        for (uint32_t h = 0; h < H; ++h) hh.push(Json::of(hit[row * R.hit_stride + h] != 0));
                         cj.set("haplotype_hit", hh);  // doc/JULIET.md:207-209
                     }
                     cods.push(cj);
@@ -153,6 +154,12 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
                 dj.set("expected", Json::of(d.call.expected));
                 dj.set("pValue", Json::of(d.call.p_value)).set("log_pValue", Json::of(d.call.log_p));
                 dj.set("frameshift_reads", Json::of(d.call.partial));
+                if (R.sites_phased) {   // --phase-deletions (docs/SPEC.md §18): the haplotypes that have this codon deleted
+                    const int site = R.deletion_site(d.col);
+                    Json hh = Json::array();
+                    for (uint32_t h = 0; h < H; ++h) hh.push(Json::of(site >= 0 && hap_pattern[(size_t)h * R.pat_stride + (size_t)site] == JL_SITE_DELETED));
+                    dj.set("haplotype_hit", hh);
+                }
                 dps.push(dj);
             }
             gj.set("deletion_positions", dps);
@@ -232,13 +239,26 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
             }
             for (uint32_t h = 0; h < H; ++h) with_rescued_total += (uint64_t)hap_count[h] + rescued_members[h].size();
         }
+        // --phase-deletions with at least one site (docs/SPEC.md §18): position p of the run is site p
+        const bool with_sites = R.sites_phased && !R.sites.empty();
         Json hs = Json::array();
         for (uint32_t h = 0; h < H; ++h) {
             Json hj = Json::object();
             hj.set("name", Json::of(haplotype_name(h))).set("reads", Json::of(hap_count[h]));
             hj.set("frequency", Json::of(ps.reported_reads ? (double)hap_count[h] / (double)ps.reported_reads : 0.0));
             Json cods = Json::array();
-            for (uint32_t p = 0; p < ps.n_positions; ++p) cods.push(Json::of(codon_string(hap_pattern[(size_t)h * R.pat_stride + p])));
+            const uint8_t *pat = &hap_pattern[(size_t)h * R.pat_stride];
+            if (!with_sites)
+                for (uint32_t p = 0; p < ps.n_positions; ++p) cods.push(Json::of(codon_string(pat[p])));
+            else {   // the codon sites only; a codon whose companion deletion site says "deleted" prints ---
+                Json dels = Json::array();
+                for (size_t k = 0; k < R.sites.size(); ++k) {
+                    if (R.sites[k].kind == (uint8_t)JL_SITE_DELETION) { dels.push(Json::of(pat[k] == JL_SITE_DELETED)); continue; }
+                    const int companion = R.deletion_site(R.sites[k].col);
+                    cods.push(Json::of(companion >= 0 && pat[companion] == JL_SITE_DELETED ? std::string("---") : codon_string(pat[k])));
+                }
+                hj.set("deletions", std::move(dels));
+            }
             hj.set("codons", std::move(cods));
             Json rn = Json::array();      // (moved on, level by level: a copy of this list per level was most of the stage at a million reads)
             rn.arr.reserve(members[h].size());
@@ -257,8 +277,18 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
         }
         hb.set("haplotypes", std::move(hs));
         Json pc = Json::array();
-        for (uint32_t p = 0; p < ps.n_positions; ++p) pc.push(Json::of(win_begin + pos_cols[p] + 1));
+        if (!with_sites)
+            for (uint32_t p = 0; p < ps.n_positions; ++p) pc.push(Json::of(win_begin + pos_cols[p] + 1));
+        else
+            for (const jl_site &x : R.sites)
+                if (x.kind == (uint8_t)JL_SITE_CODON) pc.push(Json::of(win_begin + x.col + 1));
         hb.set("variant_positions_abs", std::move(pc));
+        if (R.sites_phased) {
+            Json dp = Json::array();
+            for (const jl_site &x : R.sites)
+                if (x.kind == (uint8_t)JL_SITE_DELETION) dp.push(Json::of(win_begin + x.col + 1));
+            hb.set("deletion_positions_abs", std::move(dp));
+        }
         if (R.rescued)
             hb.set("rescue", Json::object()
                                  .set("min_positions", Json::of(R.rescue_min))

@@ -56,9 +56,22 @@ struct Results {
     bool linked = false, link_skipped = false;
     std::vector<uint32_t> link_cols, link_var, link_var_pos, link_both, link_carry, link_joint;
     // --call-deletions (docs/SPEC.md §16): the called positions in (gene, codon) order; ref_codon < 0: none exists at the position
-    struct Deletion { uint32_t gene, codon_pos; int ref_codon; jl_deletion_call call; };
+    struct Deletion { uint32_t gene, codon_pos, col; int ref_codon; jl_deletion_call call; };
     bool deletions = false;
     std::vector<Deletion> del_rows;
+    // --phase-deletions (docs/SPEC.md §18): the phasing results above are those of the site matrix then.  sites: ascending by
+    // (col, kind); site_rows: the phasing table on it; var_row[k]: the row of site_rows that is row k of `var`
+    bool sites_phased = false;
+    std::vector<jl_site> sites;
+    std::vector<jl_variant> site_rows;
+    std::vector<uint32_t> var_row;
+    // the site of the deletion called at window column `col`: its index, or -1
+    int deletion_site(uint32_t col) const
+    {
+        for (size_t k = 0; k < sites.size(); ++k)
+            if (sites[k].col == col && sites[k].kind == (uint8_t)JL_SITE_DELETION) return (int)k;
+        return -1;
+    }
     // --call-insertions (docs/SPEC.md §17): the called alleles in (gene, codon, length, sequence) order; codon_pos: the position they precede
     struct Insertion { uint32_t gene, codon_pos; jl_insertion_allele allele; jl_insertion_call call; };
     bool insertions = false;
@@ -289,8 +302,68 @@ const char *fetch_deletions(jl_ctx *ctx, const Options &opt, const jl_params &pr
             if (r + 2 < refcodes.size() && refcodes[r] < 4 && refcodes[r + 1] < 4 && refcodes[r + 2] < 4)
                 ref = 16 * refcodes[r] + 4 * refcodes[r + 1] + refcodes[r + 2];
         }
-        R.del_rows.push_back({pg[p], pk[p], ref, dc});
+        R.del_rows.push_back({pg[p], pk[p], pc[p], ref, dc});
     }
+    return nullptr;
+}
+
+// --phase-deletions, after fetch_calls and fetch_deletions: the sites and the phasing table of docs/SPEC.md §18 from the variant table
+// and the called deletions, the site matrix of the window on `ctx` in a context of its own on the same device and stream, and the
+// phasing that exists on it.  Its results replace the plain run's in R; the read order is the window's.  No site: nothing to phase,
+// R keeps the plain run's (no haplotype).
+const char *fetch_sites_phase(jl_ctx *ctx, int device, uint32_t min_reads, uint64_t n_reads, Results &R, jl_ctx **pc_out)
+{
+    R.sites_phased = true;
+    R.sites.clear(), R.site_rows.clear();
+    std::vector<uint32_t> dels;   // the distinct codon starts of the called deletions over all genes, ascending
+    for (const Results::Deletion &d : R.del_rows) dels.push_back(d.col);
+    std::sort(dels.begin(), dels.end());
+    dels.erase(std::unique(dels.begin(), dels.end()), dels.end());
+    std::vector<uint32_t> order(R.var.size());   // the rows by column (genes may overlap), the rows of one column in the table's order
+    for (uint32_t k = 0; k < order.size(); ++k) order[k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return R.var[a].col < R.var[b].col; });
+    R.var_row.assign(R.var.size(), 0);
+    size_t v = 0, d = 0;
+    while (v < order.size() || d < dels.size()) {
+        const uint32_t vc = v < order.size() ? R.var[order[v]].col : 0xFFFFFFFFu, dc = d < dels.size() ? dels[d] : 0xFFFFFFFFu;
+        const uint32_t col = std::min(vc, dc);
+        if (vc == col) {   // a codon site, filled with the reference codon where a deletion is called too
+            const uint32_t k = (uint32_t)R.sites.size();
+            R.sites.push_back(jl_site{col, (uint8_t)JL_SITE_CODON, dc == col ? R.var[order[v]].ref_codon : (uint8_t)JL_SITE_NO_FILL, 0});
+            for (; v < order.size() && R.var[order[v]].col == col; ++v) {
+                R.var_row[order[v]] = (uint32_t)R.site_rows.size();
+                R.site_rows.push_back(R.var[order[v]]);
+                R.site_rows.back().col = 3u * k;
+            }
+        }
+        if (dc == col) {   // a deletion site and its pseudo-row
+            jl_variant row = {};
+            row.col = 3u * (uint32_t)R.sites.size(), row.codon = (uint8_t)JL_SITE_DELETED, row.ref_codon = (uint8_t)JL_SITE_PRESENT;
+            R.sites.push_back(jl_site{col, (uint8_t)JL_SITE_DELETION, (uint8_t)JL_SITE_NO_FILL, 0});
+            R.site_rows.push_back(row);
+            ++d;
+        }
+    }
+    if (R.sites.empty()) return nullptr;
+    if (R.site_rows.size() > 4096) {
+        std::cerr << "juliet: --phase-deletions: " << R.site_rows.size() << " variants and deletion sites, phasing takes 4096 (narrow the table with --min-perc / --max-perc / --region)\n";
+        std::exit(2);
+    }
+    jl_ctx *pc = nullptr;
+    if (jl_ctx_create(device, jl_ctx_stream(ctx), &pc) != JL_OK) return "context of the site matrix";
+    *pc_out = pc;
+    if (jl_sites_assemble(pc, ctx, R.sites.data(), (uint32_t)R.sites.size()) != JL_OK) return "site matrix";
+    if (jl_phase_async(pc, R.site_rows.data(), (uint32_t)R.site_rows.size(), min_reads) != JL_OK) return "phasing of the site matrix";
+    const uint32_t cap_var = (uint32_t)R.site_rows.size();
+    R.pos_cols.assign(cap_var, 0);
+    R.hap_count.assign(JL_MAX_HAPLOTYPES, 0);
+    R.hap_pattern.assign((size_t)JL_MAX_HAPLOTYPES * cap_var, 0);
+    R.hit.assign((size_t)cap_var * JL_MAX_HAPLOTYPES, 0);
+    R.read_hap.assign(n_reads, 0);
+    R.pat_stride = cap_var;
+    R.hit_stride = JL_MAX_HAPLOTYPES;
+    if (jl_phase_fetch(pc, &R.ps, R.pos_cols.data(), R.hap_count.data(), R.hap_pattern.data(), R.hit.data(), R.read_hap.data(), nullptr, cap_var) != JL_OK)
+        return "phase fetch of the site matrix";
     return nullptr;
 }
 
