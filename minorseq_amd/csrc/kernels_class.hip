@@ -5,28 +5,24 @@
 //                         at or beyond n_reads clear, out to the end of the row) and class_reads[k]
 //   class_pileup_kernel   counts[k][column][A C G T - N] of at most 16 classes a pass (blockIdx.z = pass; the classes of a pass
 //                         are a template argument: their counters are registers)
-// Shape of the counting.  A lane owns a COLUMN (64 columns a wave, one wave a workgroup) and walks a segment of the reads; the
-// grid is (column group, read segment, pass).  Per tile of 512 reads (64 bytes of every plane row) the 192 plane rows of the
-// wave's columns are staged through LDS by coalesced 16-byte loads — four lanes a row, sixteen rows a load instruction, no lane
-// pulls bytes out of a line of its own — and each lane reads its column's three rows back as ds_read_b128 (rows padded to 80
-// bytes: lane l starts 60 l dwords on, conflict-free within the instruction's 16-lane groups).  The class mask words are the
-// same for all columns of the wave: wave-uniform loads, once per read word.  Per 32 reads the six symbol words come from the
-// three plane words by the identities of kernels_pileup.hip (code 7 does not occur): T = b0 & b1, N = b0 & b2, uncovered =
-// b1 & b2, C G - the remainders of b0 b1 b2, A what no plane has.  A lane keeps its 16 x 6 counters in registers across the
-// segment: no wave reduction at all, 12 VALU operations per class and word, which is what bounds the kernel.
-// Counts are integers added to the zeroed output with integer atomics: independent of order and of the launch shape.
-// Addresses are formed from the sizes the host checked only (capi_class.hip).  A label is data: it is compared with the class
-// numbers a wave builds rows for and never indexes anything.
+// Shape of the counting: the tile walk of plane_walk.h — a lane owns a COLUMN, the grid is (column group, read segment, pass), the
+// 192 plane rows of the wave's columns are staged per tile of 512 reads, loaded at the top of the iteration and stored at once.
+// The class mask words are the same for all columns of the wave: wave-uniform loads, once per read word.  Per 32 reads the six
+// symbol words come from the three plane words by the identities of kernels_pileup.hip (code 7 does not occur): T = b0 & b1,
+// N = b0 & b2, uncovered = b1 & b2, C G - the remainders of b0 b1 b2, A what no plane has.  A lane keeps its 16 x 6 counters in
+// registers across the segment: 12 VALU operations per class and word, which is what bounds the kernel.
+// A label is data: it is compared with the class numbers a wave builds rows for and never indexes anything.
+#include <array>
+#include <utility>
+
 #include "jl_internal.h"
+#include "plane_walk.h"
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+using namespace jl_walk;
 
 constexpr uint32_t kMaskWaves = 4;      // waves of a masks workgroup: the same line of reads, different classes
-constexpr uint32_t kTileBytes = 64;     // bytes of a plane row a tile stages: 512 reads, 16 words
-constexpr uint32_t kTileWords = kTileBytes / 4u;
-constexpr uint32_t kRowDwords = 20;     // a staged row in LDS: 16 words + 4 of padding
 constexpr uint32_t kRows = 192;         // plane rows of a wave's 64 columns
 
 // grid: x = line of 1024 reads (128 bytes of every mask row), y = class chunk (classes beyond the grid's y: a loop)
@@ -59,14 +55,12 @@ __global__ __launch_bounds__(64 * kMaskWaves) void class_masks_kernel(jl_class_a
 template <uint32_t NK>
 __global__ __launch_bounds__(64) void class_pileup_kernel(jl_class_args a)
 {
-    __shared__ u32x4 s_rows[kRows * kRowDwords / 4u];
+    __shared__ u32x4 s_rows[rows::slot(kRows)];
     const uint32_t lane = threadIdx.x;
     const uint32_t col0 = blockIdx.x * 64u, col = col0 + lane;
     const uint32_t k0 = a.k_first + blockIdx.z * 16u;
-    const uint32_t n_words = (uint32_t)((a.n_reads + 31u) / 32u);
-    const uint32_t n_tiles = (n_words + kTileWords - 1u) / kTileWords;
-    const uint32_t t0 = blockIdx.y * a.seg_tiles, t1 = min(t0 + a.seg_tiles, n_tiles);
-    const uint32_t n_rows = 3u * min(64u, a.n_cols - col0);   // plane rows of this group that exist
+    const range seg = segment(a.n_reads, a.seg_tiles);
+    const rows staged{3u * min(64u, a.n_cols - col0)};   // plane rows of this group that exist
     const uint8_t JL_AS1 *planes = (const uint8_t JL_AS1 *)a.msa + 3ull * col0 * a.plane_stride;
     // the mask rows have a stride of their own, whole 128-byte lines of n_reads whatever the planes' is: every word of every
     // tile exists in them, and the words behind the last read are zero — a tile needs no end of its own
@@ -79,28 +73,16 @@ __global__ __launch_bounds__(64) void class_pileup_kernel(jl_class_args a)
 #pragma unroll
         for (uint32_t s = 0; s < 6u; ++s) cnt[k][s] = 0u;
 
-    for (uint32_t t = t0; t < t1; ++t) {
-        // stage: instruction i brings 16 bytes of rows 16 i .. 16 i + 15, four lanes a row; what lies beyond the plane row (the
-        // caller's stride may end inside the tile) or beyond the last column is zero, and no class has a read there
-        const uint64_t at = (uint64_t)t * kTileBytes + 16u * (lane & 3u);
-        u32x4 v[12];
-#pragma unroll
-        for (uint32_t i = 0; i < 12u; ++i) {
-            const uint32_t row = 16u * i + (lane >> 2);
-            v[i] = u32x4{0u, 0u, 0u, 0u};
-            if (row < n_rows && at + 16u <= a.plane_stride)
-                v[i] = __builtin_nontemporal_load((const u32x4 JL_AS1 *)(planes + (uint64_t)row * a.plane_stride + at));
-        }
-        __syncthreads();   // the last tile has been read
-#pragma unroll
-        for (uint32_t i = 0; i < 12u; ++i) s_rows[(16u * i + (lane >> 2)) * (kRowDwords / 4u) + (lane & 3u)] = v[i];
-        __syncthreads();
+    for (uint32_t t = seg.t0; t < seg.t1; ++t) {
+        tile<kRows, rows> v;   // what lies beyond a plane row or the last column is zero, and no class has a read there
+        v.load(staged, planes, a.plane_stride, t, lane);
+        v.store(s_rows, lane);
         const uint32_t JL_AS1 *mw = mask + (uint64_t)t * kTileWords;
 #pragma unroll 1
         for (uint32_t q = 0; q < kTileWords / 4u; ++q, mw += 4) {
-            const u32x4 p0 = s_rows[(3u * lane + 0u) * (kRowDwords / 4u) + q];
-            const u32x4 p1 = s_rows[(3u * lane + 1u) * (kRowDwords / 4u) + q];
-            const u32x4 p2 = s_rows[(3u * lane + 2u) * (kRowDwords / 4u) + q];
+            const u32x4 p0 = s_rows[rows::slot(3u * lane + 0u) + q];
+            const u32x4 p1 = s_rows[rows::slot(3u * lane + 1u) + q];
+            const u32x4 p2 = s_rows[rows::slot(3u * lane + 2u) + q];
 #pragma unroll
             for (uint32_t j = 0; j < 4u; ++j) {
                 const uint32_t b0 = p0[j], b1 = p1[j], b2 = p2[j];
@@ -138,16 +120,16 @@ void launch_counting(const jl_class_args &A, dim3 grid, hipStream_t st)
     hipLaunchKernelGGL(class_pileup_kernel<NK>, grid, dim3(64), 0, st, A);
 }
 
-}  // namespace
-
-// tiles a read segment of the counting launch walks: segments x column groups fill the chip a few times over
-static uint32_t class_seg_tiles(uint32_t n_tiles, uint32_t n_groups)
+// kCounting[n - 1]: the counting launch of a pass of n classes
+using counting_fn = void (*)(const jl_class_args &, dim3, hipStream_t);
+template <size_t... I>
+constexpr std::array<counting_fn, sizeof...(I)> counting_table(std::index_sequence<I...>)
 {
-    const uint32_t want_blocks = 4096u;   // 256 CUs x 8 one-wave workgroups, twice
-    const uint32_t segs = std::max(1u, std::min(n_tiles, want_blocks / std::max(1u, n_groups)));
-    const uint32_t tiles = (n_tiles + segs - 1u) / segs;
-    return (tiles + 1u) & ~1u;   // whole 128-byte lines
+    return {launch_counting<(uint32_t)I + 1u>...};
 }
+constexpr auto kCounting = counting_table(std::make_index_sequence<16>{});
+
+}  // namespace
 
 // masks and class_reads from the labels, then ceil(n_classes / 16) passes of the counting; a->counts and a->class_reads are zero
 void jl_launch_class_pileup(const jl_class_args *a, hipStream_t st)
@@ -156,32 +138,12 @@ void jl_launch_class_pileup(const jl_class_args *a, hipStream_t st)
     const uint32_t n_lines = (uint32_t)((A.n_reads + 1023u) / 1024u);
     const uint32_t class_chunks = (A.n_classes + kMaskWaves - 1u) / kMaskWaves;
     hipLaunchKernelGGL(class_masks_kernel, dim3(n_lines, class_chunks), dim3(64 * kMaskWaves), 0, st, A);
-    const uint32_t n_words = (uint32_t)((A.n_reads + 31u) / 32u);
-    const uint32_t n_tiles = (n_words + kTileWords - 1u) / kTileWords;
     const uint32_t n_groups = (A.n_cols + 63u) / 64u;
-    A.seg_tiles = class_seg_tiles(n_tiles, n_groups);
-    const uint32_t n_segs = (n_tiles + A.seg_tiles - 1u) / A.seg_tiles;
+    const jl_walk_shape shape = jl_walk_shape_for(A.n_reads, n_groups);
+    A.seg_tiles = shape.seg_tiles;
     const uint32_t full = A.n_classes / 16u, rest = A.n_classes % 16u;
     A.k_first = 0u;
-    if (full) launch_counting<16>(A, dim3(n_groups, n_segs, full), st);
+    if (full) kCounting[15](A, dim3(n_groups, shape.n_segs, full), st);
     A.k_first = 16u * full;
-    const dim3 grid(n_groups, n_segs, 1);
-    switch (rest) {
-    case 1: launch_counting<1>(A, grid, st); break;
-    case 2: launch_counting<2>(A, grid, st); break;
-    case 3: launch_counting<3>(A, grid, st); break;
-    case 4: launch_counting<4>(A, grid, st); break;
-    case 5: launch_counting<5>(A, grid, st); break;
-    case 6: launch_counting<6>(A, grid, st); break;
-    case 7: launch_counting<7>(A, grid, st); break;
-    case 8: launch_counting<8>(A, grid, st); break;
-    case 9: launch_counting<9>(A, grid, st); break;
-    case 10: launch_counting<10>(A, grid, st); break;
-    case 11: launch_counting<11>(A, grid, st); break;
-    case 12: launch_counting<12>(A, grid, st); break;
-    case 13: launch_counting<13>(A, grid, st); break;
-    case 14: launch_counting<14>(A, grid, st); break;
-    case 15: launch_counting<15>(A, grid, st); break;
-    default: break;
-    }
+    if (rest) kCounting[rest - 1u](A, dim3(n_groups, shape.n_segs, 1), st);
 }

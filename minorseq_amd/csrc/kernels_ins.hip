@@ -23,16 +23,15 @@
 // against its qualities (a record whose cigar consumes more than it holds is refused by the build's verdict anyway).
 //
 // SPAN PASS (junction_span_kernel).  span[c] = reads whose cells at c - 1 and c are both covered (code != 6, i.e. not plane 2 and
-// plane 1 both set).  kernels_del.hip's shape with two planes and a halo of one: a lane owns a junction, a one-wave workgroup 64
-// junctions and a segment of the reads; per tile of 512 reads the planes 1 and 2 of the group's 65 columns are staged through LDS
-// by coalesced 16-byte loads (four lanes a row, sixteen rows an instruction) and read back as ds_read_b128, a column's two rows
-// next to each other in 36 dwords: lane l starts 36 l dwords on, conflict-free within the instruction's 16-lane groups.
-// A load reads row r < 3 n_cols at bytes [at, at + 16) with at + 16 <= plane_stride; bits beyond n_reads are cut by `valid`.
+// plane 1 both set).  The tile walk of plane_walk.h with two planes and a halo of one: a lane owns a junction, and staged are the
+// planes 1 and 2 of the group's 65 columns, a column's two rows next to each other in LDS (span_cols).  The loads of the next
+// tile are issued before the current one is counted.
 #include "jl_internal.h"
+#include "plane_walk.h"
 
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+using namespace jl_walk;
 
 constexpr unsigned long long kEmptyKey = ~0ull;
 constexpr uint32_t kInframe = 1u, kFrameshift = 2u, kUnread = 3u;   // an event's kind: its column of jcnt
@@ -168,60 +167,42 @@ __global__ __launch_bounds__(256) void insertion_rows_kernel(const unsigned long
 }
 
 // ---------------------------------------------------------------------------------------- span
-constexpr uint32_t kTileBytes = 64;     // bytes of a plane row a tile stages: 512 reads, 16 words
-constexpr uint32_t kTileWords = kTileBytes / 4u;
 constexpr uint32_t kJunctions = 64;     // junctions of a group: one a lane
 constexpr uint32_t kCols = kJunctions + 1u;          // columns staged: the junctions' own and the one before the first
 constexpr uint32_t kRows = 2u * kCols;               // ... their planes 1 and 2
-constexpr uint32_t kColVec = 9;         // a staged column in LDS, in 16-byte units: plane 1 (4), plane 2 (4), 1 of padding (36 dwords)
-constexpr uint32_t kLoads = (kRows + 15u) / 16u;     // load instructions a tile: sixteen rows each, the last one two
 
-// 16 bytes of staged rows 16 i + (lane >> 2) of tile t — row 2 k + p is plane 1 + p of column cb + k — zero where the column or the bytes do not exist
-__device__ __forceinline__ void load_tile(const jl_insal_span_args &a, uint32_t cb, uint32_t n_here, uint32_t t, uint32_t lane, u32x4 (&v)[kLoads])
-{
-    const uint8_t JL_AS1 *planes = (const uint8_t JL_AS1 *)a.msa;
-    const uint64_t at = (uint64_t)t * kTileBytes + 16u * (lane & 3u);
-#pragma unroll
-    for (uint32_t i = 0; i < kLoads; ++i) {
-        const uint32_t row = 16u * i + (lane >> 2);
-        v[i] = u32x4{0u, 0u, 0u, 0u};
-        if ((row >> 1) < n_here && at + 16u <= a.plane_stride)
-            v[i] = __builtin_nontemporal_load((const u32x4 JL_AS1 *)(planes + (3ull * (cb + (row >> 1)) + 1u + (row & 1u)) * a.plane_stride + at));
-    }
-}
+// the layout of the span's tile: staged row 2 k + p is plane 1 + p of column cb + k, the first n_here columns exist
+struct span_cols {
+    static constexpr uint32_t kColVec = 9;   // a staged column in LDS, in 16-byte units: plane 1 (4), plane 2 (4), 1 of padding
+    uint32_t cb, n_here;
+    __device__ __forceinline__ bool exists(uint32_t r) const { return (r >> 1) < n_here; }
+    __device__ __forceinline__ uint64_t plane_row(uint32_t r) const { return 3ull * (cb + (r >> 1)) + 1u + (r & 1u); }
+    __device__ __forceinline__ static constexpr uint32_t slot(uint32_t r) { return (r >> 1) * kColVec + (r & 1u) * 4u; }
+};
 
 // grid: x = group of 64 junctions (junction cb + 1 + lane, cb = 64 x), y = read segment of `seg_tiles` tiles
 __global__ __launch_bounds__(64) void junction_span_kernel(jl_insal_span_args a)
 {
-    __shared__ u32x4 s_cols[kCols * kColVec];
+    __shared__ u32x4 s_cols[span_cols::slot(kRows)];
     const uint32_t lane = threadIdx.x;
     const uint32_t cb = blockIdx.x * kJunctions;
-    const uint32_t n_words = (uint32_t)((a.n_reads + 31u) / 32u);
-    const uint32_t n_tiles = (n_words + kTileWords - 1u) / kTileWords;
-    const uint32_t t0 = blockIdx.y * a.seg_tiles, t1 = min(t0 + a.seg_tiles, n_tiles);
-    const uint32_t n_here = min(kCols, a.n_cols - cb);   // columns of this group that exist
+    const range seg = segment(a.n_reads, a.seg_tiles);
+    const span_cols staged{cb, min(kCols, a.n_cols - cb)};   // ... the columns of this group that exist
+    const uint8_t JL_AS1 *planes = (const uint8_t JL_AS1 *)a.msa;
 
     uint32_t span = 0u;
-    u32x4 v[kLoads];
-    if (t0 < t1) load_tile(a, cb, n_here, t0, lane, v);
-    for (uint32_t t = t0; t < t1; ++t) {
-        __syncthreads();   // the last tile has been read
-#pragma unroll
-        for (uint32_t i = 0; i < kLoads; ++i) {
-            const uint32_t row = 16u * i + (lane >> 2);
-            if (row < kRows) s_cols[(row >> 1) * kColVec + (row & 1u) * 4u + (lane & 3u)] = v[i];
-        }
-        __syncthreads();
-        if (t + 1u < t1) load_tile(a, cb, n_here, t + 1u, lane, v);   // in flight while this tile is counted
+    tile<kRows, span_cols> v;
+    if (seg.t0 < seg.t1) v.load(staged, planes, a.plane_stride, seg.t0, lane);
+    for (uint32_t t = seg.t0; t < seg.t1; ++t) {
+        v.store(s_cols, lane);
+        if (t + 1u < seg.t1) v.load(staged, planes, a.plane_stride, t + 1u, lane);   // in flight while this tile is counted
 #pragma unroll
         for (uint32_t q = 0; q < kTileWords / 4u; ++q) {
-            const u32x4 x1 = s_cols[lane * kColVec + q], x2 = s_cols[lane * kColVec + 4u + q];                   // column c - 1
-            const u32x4 y1 = s_cols[(lane + 1u) * kColVec + q], y2 = s_cols[(lane + 1u) * kColVec + 4u + q];     // column c
+            const u32x4 x1 = s_cols[span_cols::slot(2u * lane) + q], x2 = s_cols[span_cols::slot(2u * lane + 1u) + q];        // column c - 1
+            const u32x4 y1 = s_cols[span_cols::slot(2u * lane + 2u) + q], y2 = s_cols[span_cols::slot(2u * lane + 3u) + q];   // column c
 #pragma unroll
             for (uint32_t j = 0; j < 4u; ++j) {
-                // the reads of this word that exist (wave-uniform)
-                const int64_t left = (int64_t)a.n_reads - 32ll * (int64_t)(t * kTileWords + 4u * q + j);
-                const uint32_t valid = left >= 32 ? 0xFFFFFFFFu : left > 0 ? (1u << (uint32_t)left) - 1u : 0u;
+                const uint32_t valid = jl_valid_bits(a.n_reads, t * kTileWords + 4u * q + j);   // (wave-uniform)
                 span += __popc(valid & ~((x1[j] & x2[j]) | (y1[j] & y2[j])));
             }
         }
@@ -248,13 +229,8 @@ void jl_launch_insertion_rows(const unsigned long long *key0, const unsigned lon
 void jl_launch_junction_span(const jl_insal_span_args *a, hipStream_t st)
 {
     jl_insal_span_args A = *a;
-    const uint32_t n_words = (uint32_t)((A.n_reads + 31u) / 32u);
-    const uint32_t n_tiles = (n_words + kTileWords - 1u) / kTileWords;
     const uint32_t n_groups = (A.n_cols - 1u + kJunctions - 1u) / kJunctions;
-    // tiles a read segment walks: segments x groups fill the chip a few times over (kernels_del.hip's rule)
-    const uint32_t want_blocks = 4096u;
-    const uint32_t segs = std::max(1u, std::min(n_tiles, want_blocks / std::max(1u, n_groups)));
-    A.seg_tiles = ((n_tiles + segs - 1u) / segs + 1u) & ~1u;   // whole 128-byte lines
-    const uint32_t n_segs = (n_tiles + A.seg_tiles - 1u) / A.seg_tiles;
-    hipLaunchKernelGGL(junction_span_kernel, dim3(n_groups, n_segs), dim3(64), 0, st, A);
+    const jl_walk_shape shape = jl_walk_shape_for(A.n_reads, n_groups);
+    A.seg_tiles = shape.seg_tiles;
+    hipLaunchKernelGGL(junction_span_kernel, dim3(n_groups, shape.n_segs), dim3(64), 0, st, A);
 }

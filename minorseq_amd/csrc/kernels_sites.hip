@@ -18,6 +18,7 @@
 // uncovered; the bits of a word at or beyond n_reads — padding, and whatever an adopted source holds there — are cut by `valid`
 // and written as code 6 (plane 0 clear, planes 1 and 2 set) out to the end of every destination row.
 #include "jl_internal.h"
+#include "planes.h"
 
 namespace {
 
@@ -51,9 +52,7 @@ __global__ __launch_bounds__(kLanes) void sites_assemble_kernel(jl_sites_args a)
     u32x4 o[9];
 #pragma unroll
     for (uint32_t w = 0; w < 4u; ++w) {
-        // the reads of this word that exist
-        const int64_t left = (int64_t)a.n_reads - 32ll * (int64_t)(4u * piece + w);
-        const uint32_t valid = left >= 32 ? 0xFFFFFFFFu : left > 0 ? (1u << (uint32_t)left) - 1u : 0u;
+        const uint32_t valid = jl_valid_bits(a.n_reads, 4u * piece + w);
         const uint32_t x0 = p[0][w], x1 = p[1][w], x2 = p[2][w];
         const uint32_t y0 = p[3][w], y1 = p[4][w], y2 = p[5][w];
         const uint32_t z0 = p[6][w], z1 = p[7][w], z2 = p[8][w];

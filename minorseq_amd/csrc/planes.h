@@ -31,6 +31,20 @@ JL_PL_FN uint32_t jl_planes_to_nibbles8(uint32_t b0, uint32_t b1, uint32_t b2)
     return jl_spread8(b0) | (jl_spread8(b1) << 1) | (jl_spread8(b2) << 2);
 }
 
+// the bits of 32-read word `word` of a plane row that are reads: the low min(32, max(0, n_reads - 32 word)).  What a row holds
+// beyond them — the padding, and whatever an adopted matrix has there — is cut by this mask and by nothing else.
+JL_PL_FN uint32_t jl_valid_bits(uint64_t n_reads, uint64_t word)
+{
+    const int64_t left = (int64_t)n_reads - 32ll * (int64_t)word;
+    return left >= 32 ? 0xFFFFFFFFu : left > 0 ? (1u << (uint32_t)left) - 1u : 0u;
+}
+
+// tiles of 512 reads (64 bytes of every plane row) that n_reads fill, the last one in part (plane_walk.h)
+JL_PL_FN uint32_t jl_walk_tiles(uint64_t n_reads)
+{
+    return (uint32_t)((n_reads + 511u) / 512u);
+}
+
 #if defined(__HIPCC__)
 // eight reads of one column as a dword of codes: byte `p` of plane 0 and the same byte of planes 1 and 2
 __device__ __forceinline__ uint32_t jl_load_codes8(const uint8_t *p, uint64_t plane_stride)
