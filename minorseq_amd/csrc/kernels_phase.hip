@@ -16,11 +16,14 @@
 // blockIdx.z): keys + grouping in every block, the selection by the block that arrives last, and — when all
 // workgroups of the launch are resident together (<= JL_INLINE_IDS_MAX_BLOCKS) — the per-read ids ("inline ids") by every block from the slots still
 // in its registers (the others wait on a flag); larger launches leave the ids to a separate launch, phase_assign(_group)_kernel.
-// Vp > 10: phase_keys_kernel, phase_group_kernel, phase_select_kernel, phase_assign_kernel.
+// A workgroup of these launches is phase_fused_body: its stages, in order, are fused_plan_stage, fused_keys_stage, group_round,
+// fused_arrive, then fused_last (the last workgroup) or fused_wait (the others), and fused_ids_and_leave; its LDS is one fused_lds.
+// 11 <= Vp <= 20: the same body with two key words, phase_fused2_kernel (jl_two_word).
+// Vp > 20, or a context on the multi-word form: phase_keys_kernel, phase_group_kernel, phase_select_kernel, phase_assign_kernel.
+// Every selection reads the window's argument block, jl_win_phase; the kernels take it by value.
 #include <string.h>
 
 #include <algorithm>
-#include <type_traits>
 
 #include "call_eval.h"
 #include "jl_internal.h"
@@ -48,19 +51,45 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z)
 }
 
 // ---------------------------------------------------------------------------------------- plan
-__global__ __launch_bounds__(1024) void phase_plan_kernel(const jl_variant *__restrict__ variants,
-                                                           const uint32_t *__restrict__ n_rows, uint32_t cap,
-                                                           uint32_t n_cols, uint8_t *__restrict__ varcol,
-                                                           uint32_t *__restrict__ vpcols,
-                                                           uint32_t *__restrict__ col2pos, uint32_t kwords_cap,
-                                                           uint32_t fast_only, jl_phase_meta *__restrict__ meta)
+// (the argument block of the compact launch, which makes the same plan behind a call stage: jl_fill_win_compact)
+__global__ __launch_bounds__(1024) void phase_plan_kernel(jl_win_compact c)
 {
-    uint32_t nv = n_rows[0];
-    if (nv > cap) nv = cap;
-    jl_phase_plan_block(variants, nv, n_cols, varcol, vpcols, col2pos, kwords_cap, fast_only, meta);
+    uint32_t nv = c.n_rows[0];
+    if (nv > c.cap) nv = c.cap;
+    jl_phase_plan_block(c.rows, nv, c.n_cols, c.varcol, c.vpcols, c.col2pos, c.kwords_cap, c.fast_only, c.meta);
 }
 
 // ---------------------------------------------------------------------------------------- keys
+// One variant position of a lane's 8 reads: w[k] = the codes of column c + k, a nibble per read.  Adds the reads' flags (bit
+// 4r of each mask) and appends the position's 6-bit codon index to every read's key word.
+__device__ __forceinline__ void key_add_position(const uint32_t (&w)[3], uint32_t &gap, uint32_t &het, uint32_t &par, uint64_t (&key)[8])
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const uint32_t b0 = w[k] & kM1, b1 = (w[k] >> 1) & kM1, b2 = (w[k] >> 2) & kM1;
+        gap |= b2 & ~b1 & ~b0;  // 4 = '-'
+        het |= b2 & b0;         // 5 = 'N'
+        par |= b2 & b1;         // 6 = not covered
+    }
+    const uint32_t hi2 = w[0] & 0x33333333u;
+    const uint32_t lo4 = ((w[1] & 0x33333333u) << 2) | (w[2] & 0x33333333u);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const uint64_t code = (((hi2 >> (4 * r)) & 3u) << 4) | ((lo4 >> (4 * r)) & 15u);
+        key[r] = (key[r] << 6) | code;
+    }
+}
+
+// bit 4r: read r of the 8 reads of dword t exists (reads beyond n_reads are padding, not damaged reads)
+__device__ __forceinline__ uint32_t valid_reads8(uint64_t t, uint64_t n_reads)
+{
+    uint32_t valid = 0;
+#pragma unroll
+    for (int r = 0; r < 8; ++r)
+        if (t * 8u + r < n_reads) valid |= 1u << (4 * r);
+    return valid;
+}
+
 // One lane = 8 consecutive reads = one byte of each plane of every variant column, put back together as a dword of eight codes.
 __global__ __launch_bounds__(256) void phase_keys_kernel(const uint8_t *__restrict__ msa, uint64_t plane_stride,
                                                           uint64_t n_reads, uint64_t reads_pad,
@@ -84,20 +113,7 @@ __global__ __launch_bounds__(256) void phase_keys_kernel(const uint8_t *__restri
 #pragma unroll
             for (int k = 0; k < 3; ++k)
                 w[k] = live ? jl_load_codes8(msa + (uint64_t)(c + k) * 3u * plane_stride + t, plane_stride) : 0x66666666u;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const uint32_t b0 = w[k] & kM1, b1 = (w[k] >> 1) & kM1, b2 = (w[k] >> 2) & kM1;
-                gap |= b2 & ~b1 & ~b0;  // 4 = '-'
-                het |= b2 & b0;         // 5 = 'N'
-                par |= b2 & b1;         // 6 = not covered
-            }
-            const uint32_t hi2 = w[0] & 0x33333333u;
-            const uint32_t lo4 = ((w[1] & 0x33333333u) << 2) | (w[2] & 0x33333333u);
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const uint32_t code = (((hi2 >> (4 * r)) & 3u) << 4) | ((lo4 >> (4 * r)) & 15u);
-                key[r] = (key[r] << 6) | code;
-            }
+            key_add_position(w, gap, het, par, key);
         }
         if (live) {
             uint64_t *dst = keys + (uint64_t)gw * reads_pad + t * 8u;
@@ -110,13 +126,7 @@ __global__ __launch_bounds__(256) void phase_keys_kernel(const uint8_t *__restri
             }
         }
     }
-    // reads beyond n_reads are padding, not damaged reads
-    uint32_t valid = 0;
-    if (live) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-            if (t * 8u + r < n_reads) valid |= 1u << (4 * r);
-    }
+    const uint32_t valid = live ? valid_reads8(t, n_reads) : 0u;
     gap &= valid; het &= valid; par &= valid;
     if (live) flagw[t] = gap | (het << 1) | (par << 2) | ((valid ^ kM1) << 3);  // bit3: padding
     const uint32_t n_gap = wave_sum_all(__popc(gap));
@@ -140,23 +150,18 @@ __device__ __forceinline__ bool keys_equal(const uint64_t *__restrict__ keys, ui
     return true;
 }
 
-__global__ __launch_bounds__(256) void phase_group_kernel(uint64_t n_reads, uint64_t reads_pad,
-                                                           const uint64_t *__restrict__ keys,
-                                                           const uint32_t *__restrict__ flagw,
-                                                           jl_phase_meta *__restrict__ meta, uint64_t slots_mask,
-                                                           uint32_t *__restrict__ slot_rep,
-                                                           uint32_t *__restrict__ slot_count,
-                                                           uint32_t *__restrict__ occupied,
-                                                           uint32_t *__restrict__ read_slot)
+__global__ __launch_bounds__(256) void phase_group_kernel(jl_win_phase w)
 {
-    const uint32_t kwords = meta->kwords;
+    const uint64_t reads_pad = w.reads_pad, slots_mask = w.slots_mask;
+    const uint64_t *__restrict__ keys = w.keys;
+    const uint32_t kwords = w.meta->kwords;
     if (kwords == 0) return;  // nothing to phase
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u;
     bool active = false;
     uint64_t k0 = 0;
-    if (i < n_reads) {
-        const uint32_t f = (flagw[i >> 3] >> (4u * (uint32_t)(i & 7u))) & 15u;
+    if (i < w.n_reads) {
+        const uint32_t f = (w.flagw[i >> 3] >> (4u * (uint32_t)(i & 7u))) & 15u;
         active = f == 0;
         if (active) k0 = keys[i];
     }
@@ -178,16 +183,16 @@ __global__ __launch_bounds__(256) void phase_group_kernel(uint64_t n_reads, uint
             uint64_t s = h & slots_mask;
             const uint32_t cnt = (uint32_t)__popcll(grp);
             for (;;) {
-                uint32_t rep = __hip_atomic_load(&slot_rep[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                uint32_t rep = __hip_atomic_load(&w.slot_rep[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (rep == kEmpty) {
-                    rep = atomicCAS(&slot_rep[s], kEmpty, (uint32_t)i);
+                    rep = atomicCAS(&w.slot_rep[s], kEmpty, (uint32_t)i);
                     if (rep == kEmpty) {
-                        occupied[atomicAdd(&meta->n_occupied, 1u)] = (uint32_t)s;
+                        w.occupied[atomicAdd(&w.meta->n_occupied, 1u)] = (uint32_t)s;
                         rep = (uint32_t)i;
                     }
                 }
                 if (rep == (uint32_t)i || keys_equal(keys, reads_pad, kwords, rep, i)) {
-                    atomicAdd(&slot_count[s], cnt);
+                    atomicAdd(&w.slot_count[s], cnt);
                     break;
                 }
                 s = (s + 1u) & slots_mask;
@@ -196,33 +201,47 @@ __global__ __launch_bounds__(256) void phase_group_kernel(uint64_t n_reads, uint
         }
         slot = __shfl(slot, leader, 64);
         if (same) {
-            read_slot[i] = slot;
+            w.read_slot[i] = slot;
             active = false;
         }
         todo &= ~grp;
     }
 }
 
-__device__ __forceinline__ uint32_t ld_coherent(const uint32_t *p) { return jl_ld_coherent(p); }
-__device__ __forceinline__ unsigned long long ld_coherent64(const unsigned long long *p) { return jl_ld_coherent64(p); }
-__device__ __forceinline__ void signal_done(uint32_t *seq_dev, volatile uint32_t *seq_host) { jl_signal_done(seq_dev, seq_host); }
-
 // width of the per-read ids for H reported haplotypes (jl_internal.h: JL_ID4_MAX_H / JL_ID8_MAX_H)
 __device__ __forceinline__ uint32_t id_bits_for(uint32_t H) { return H <= JL_ID4_MAX_H ? 4u : (H <= JL_ID8_MAX_H ? 8u : 16u); }
 
-__device__ __forceinline__ void store_ids(uint16_t *base, uint64_t t, const uint16_t (&h)[8], uint32_t bits) { jl_store_ids(base, t, h, bits); }
-
-// ---------------------------------------------------------------------------------------- select
-template <bool BYKEY>
-__device__ __forceinline__ uint32_t pattern_code(const uint64_t *keys, unsigned long long *slot_key, uint64_t reads_pad,
-                                                 uint32_t vp, uint32_t id, uint32_t p)
+// ---------------------------------------------------------------------------------------- patterns
+// the one decode: the 6-bit code of position i of the n positions a key word holds (the first is the most significant)
+__device__ __forceinline__ uint32_t key_code(uint64_t word, uint32_t n, uint32_t i) { return (uint32_t)(word >> (6u * (n - 1u - i))) & 63u; }
+// position p of a vp-position pattern, out of the word that holds it (word p / JL_POS_PER_WORD, full but for the last)
+__device__ __forceinline__ uint32_t word_code(uint64_t word, uint32_t vp, uint32_t p)
 {
     const uint32_t g = p / JL_POS_PER_WORD;
-    const uint32_t in_word = min(JL_POS_PER_WORD, vp - g * JL_POS_PER_WORD);
-    const uint32_t sh = 6u * (in_word - 1u - (p - g * JL_POS_PER_WORD));
-    const uint64_t k = BYKEY ? (uint64_t)ld_coherent64(&slot_key[id])
-                             : keys[(uint64_t)g * reads_pad + id];
-    return (uint32_t)(k >> sh) & 63u;
+    return key_code(word, min(JL_POS_PER_WORD, vp - g * JL_POS_PER_WORD), p - g * JL_POS_PER_WORD);
+}
+// the same for a pattern of up to 20 positions whose two words are at hand: positions 0..9 in w0, the rest in w1
+__device__ __forceinline__ uint32_t key_code2(uint64_t w0, uint64_t w1, uint32_t vp, uint32_t p)
+{
+    const uint32_t n0 = vp < JL_POS_PER_WORD ? vp : JL_POS_PER_WORD;
+    return p < n0 ? key_code(w0, n0, p) : key_code(w1, vp - n0, p - n0);
+}
+
+// leave the table empty for the next run: only the slots this run touched.  All threads of the block; no barrier.
+__device__ __forceinline__ void empty_slot(const jl_win_phase &w, uint32_t s) { w.slot_key[s] = ~0ull; w.slot_rep[s] = 0xFFFFFFFFu; w.slot_count[s] = 0; }
+__device__ __forceinline__ void empty_used_slots(const jl_win_phase &w, uint32_t n_occ)
+{
+    for (uint32_t q = threadIdx.x; q < n_occ; q += blockDim.x) empty_slot(w, jl_ld_coherent(&w.occupied[q]));
+}
+
+// ---------------------------------------------------------------------------------------- select
+// code of position p of the pattern of group `id` (BYKEY: a table slot, else a read that carries the pattern)
+template <bool BYKEY>
+__device__ __forceinline__ uint32_t pattern_code(const jl_win_phase &w, uint32_t vp, uint32_t id, uint32_t p)
+{
+    const uint64_t k = BYKEY ? (uint64_t)jl_ld_coherent64(&w.slot_key[id])
+                             : w.keys[(uint64_t)(p / JL_POS_PER_WORD) * w.reads_pad + id];
+    return word_code(k, vp, p);
 }
 
 // Block-level (any block size that is a multiple of 64): groups with >= min_reads ranked by (count desc, pattern asc),
@@ -230,45 +249,44 @@ __device__ __forceinline__ uint32_t pattern_code(const uint64_t *keys, unsigned 
 // Every table / key / meta word it reads was written by other workgroups: the caller has acquired them.
 // BYKEY: single-word pipeline — a group's pattern is its 64-bit table key (coherent: written by CAS), so no
 // representative read has to be looked up in the key buffer another workgroup may have written in this launch.
+// Everything but the LDS comes from the window's argument block.
 #define JL_SELECT_LDS_WORDS (JL_CAND_CAP + 704u)
+struct select_lds {   // the caller's LDS (the fused launch lends the tables its grouping is done with, and has no caches)
+    uint32_t *scratch;               // [JL_SELECT_LDS_WORDS]
+    uint32_t *cache;                 // [2 * JL_CAND_CAP] or null: see below
+    unsigned long long *key_cache;   // [key_cache_words] or null
+    uint32_t key_cache_words;
+};
 
 template <bool BYKEY>
-__device__ __forceinline__ void phase_select_block(uint32_t min_reads, uint64_t reads_pad, const uint64_t *keys,
-                                                   jl_phase_meta *meta, uint32_t *slot_rep, uint32_t *slot_count,
-                                                   const uint32_t *occupied, uint32_t *slot_hap,
-                                                   const jl_variant *variants, const uint32_t *col2pos, uint32_t n_cols,
-                                                   uint32_t *hap_count, uint8_t *hap_pattern, uint8_t *hit,
-                                                   const uint32_t *n_rows, const uint32_t *vpcols, uint32_t *cooc,
-                                                   uint32_t cooc_cap, jl_pack *pk, jl_pack *mirror,
-                                                   unsigned long long *slot_key, uint32_t *seq_dev, uint32_t *lds,
-                                                   uint32_t *exp_count = nullptr, uint8_t *exp_pattern = nullptr,
-                                                   uint32_t exp_cap = 0, uint32_t exp_stride = 0, uint32_t *cache = nullptr,
-                                                   unsigned long long *key_cache = nullptr, uint32_t key_cache_words = 0,
-                                                   uint32_t *exp_head = nullptr)
+__device__ __forceinline__ void phase_select_block(const jl_win_phase &w, const select_lds &lds)
 {
-    // `lds`: JL_SELECT_LDS_WORDS words of LDS of the caller (the fused launch lends the tables its grouping is done with)
-    uint32_t *s_cand = lds;                               // [JL_CAND_CAP] slot of each candidate
-    uint32_t *s_hrep = lds + JL_CAND_CAP;                 // [JL_MAX_HAPLOTYPES]
+    const jl_select_args &S = w.S;
+    jl_phase_meta *meta = w.meta;
+    uint32_t *s_cand = lds.scratch;                       // [JL_CAND_CAP] slot of each candidate
+    uint32_t *s_hrep = lds.scratch + JL_CAND_CAP;         // [JL_MAX_HAPLOTYPES]
+    uint32_t *const cache = lds.cache;
+    unsigned long long *const key_cache = lds.key_cache;
     __shared__ uint32_t s_ncand, s_insufficient, s_reported, s_nhap;
     const uint32_t tid = threadIdx.x, nt = blockDim.x;
-    const uint32_t vp = ld_coherent(&meta->vp);
-    const uint32_t kwords = ld_coherent(&meta->kwords);
-    const uint32_t nv = ld_coherent(&meta->n_var);
-    const uint32_t n_occ = ld_coherent(&meta->n_occupied);
-    if (vp != 0 && exp_count) {  // block-uniform: the groups go out as they are (see jl_select_args)
+    const uint32_t vp = jl_ld_coherent(&meta->vp);
+    const uint32_t kwords = jl_ld_coherent(&meta->kwords);
+    const uint32_t nv = jl_ld_coherent(&meta->n_var);
+    const uint32_t n_occ = jl_ld_coherent(&meta->n_occupied);
+    if (vp != 0 && S.exp_count) {  // block-uniform: the groups go out as they are (see jl_select_args)
         if (tid == 0) s_insufficient = 0;
         __syncthreads();
         for (uint32_t q = tid; q < n_occ; q += nt) {
-            const uint32_t s = ld_coherent(&occupied[q]);
-            const uint32_t c = ld_coherent(&slot_count[s]);
+            const uint32_t s = jl_ld_coherent(&w.occupied[q]);
+            const uint32_t c = jl_ld_coherent(&w.slot_count[s]);
             atomicAdd(&s_insufficient, c);
             // the slot remembers WHICH exported group it is: the merge answers per group (jl_phase_regroup, jl_xwin_phase_sharded)
-            __hip_atomic_store(&slot_hap[s], q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (q < exp_cap) {
-                exp_count[q] = c;
+            __hip_atomic_store(&S.slot_hap[s], q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (q < S.exp_cap) {
+                S.exp_count[q] = c;
                 // the group's key words once each, its row of codon codes stored 8 bytes at a time (exp_stride is a multiple
                 // of 8: the rows may lie in pinned host memory, where every store is a transaction of its own)
-                const uint32_t rep = BYKEY ? s : ld_coherent(&slot_rep[s]);
+                const uint32_t rep = BYKEY ? s : jl_ld_coherent(&w.slot_rep[s]);
                 uint64_t word = 0;
                 uint32_t have = 0xFFFFFFFFu;
                 for (uint32_t p8 = 0; p8 < vp; p8 += 8u) {
@@ -276,44 +294,42 @@ __device__ __forceinline__ void phase_select_block(uint32_t min_reads, uint64_t 
                     for (uint32_t j = 0; j < 8u && p8 + j < vp; ++j) {
                         const uint32_t p = p8 + j, g = p / JL_POS_PER_WORD;
                         if (g != have) {
-                            word = BYKEY ? (uint64_t)ld_coherent64(&slot_key[s]) : keys[(uint64_t)g * reads_pad + rep];
+                            word = BYKEY ? (uint64_t)jl_ld_coherent64(&w.slot_key[s]) : w.keys[(uint64_t)g * w.reads_pad + rep];
                             have = g;
                         }
-                        const uint32_t in_word = min(JL_POS_PER_WORD, vp - g * JL_POS_PER_WORD);
-                        const uint32_t sh = 6u * (in_word - 1u - (p - g * JL_POS_PER_WORD));
-                        out |= (unsigned long long)((word >> sh) & 63u) << (8u * j);
+                        out |= (unsigned long long)word_code(word, vp, p) << (8u * j);
                     }
-                    *reinterpret_cast<unsigned long long *>(exp_pattern + (uint64_t)q * exp_stride + p8) = out;
+                    *reinterpret_cast<unsigned long long *>(S.exp_pattern + (uint64_t)q * S.exp_stride + p8) = out;
                 }
             }
         }
         __syncthreads();
         if (tid == 0) {
-            if (n_occ > exp_cap) meta->overflow |= JL_PHASE_OVF_EXPORT;
+            if (n_occ > S.exp_cap) meta->overflow |= JL_PHASE_OVF_EXPORT;
             meta->summary.reported_reads = 0;
             meta->summary.insufficient_reads = s_insufficient;   // clean reads: the merge decides which are reported
             meta->summary.n_haplotypes = 0;
             __hip_atomic_store(&meta->id_bits, 16u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (exp_head) {   // the scalars a merge needs, next to the groups (pinned host memory or an all-gather's send buffer)
-                exp_head[0] = n_occ; exp_head[1] = vp; exp_head[2] = n_occ > exp_cap ? 1u : 0u;
-                exp_head[3] = ld_coherent(&meta->summary.damaged_reads); exp_head[4] = ld_coherent(&meta->summary.marginal_gap);
-                exp_head[5] = ld_coherent(&meta->summary.marginal_heteroduplex); exp_head[6] = ld_coherent(&meta->summary.marginal_partial);
-                exp_head[7] = s_insufficient;
+            if (S.exp_head) {   // the scalars a merge needs, next to the groups (pinned host memory or an all-gather's send buffer)
+                S.exp_head[0] = n_occ; S.exp_head[1] = vp; S.exp_head[2] = n_occ > S.exp_cap ? 1u : 0u;
+                S.exp_head[3] = jl_ld_coherent(&meta->summary.damaged_reads); S.exp_head[4] = jl_ld_coherent(&meta->summary.marginal_gap);
+                S.exp_head[5] = jl_ld_coherent(&meta->summary.marginal_heteroduplex); S.exp_head[6] = jl_ld_coherent(&meta->summary.marginal_partial);
+                S.exp_head[7] = s_insufficient;
             }
         }
     } else if (vp != 0) {  // block-uniform
     if (tid == 0) { s_ncand = 0; s_insufficient = 0; s_reported = 0; s_nhap = 0; }
     __syncthreads();
     for (uint32_t q = tid; q < n_occ; q += nt) {
-        const uint32_t s = ld_coherent(&occupied[q]);
-        const uint32_t c = ld_coherent(&slot_count[s]);
-        if (c >= min_reads) {
+        const uint32_t s = jl_ld_coherent(&w.occupied[q]);
+        const uint32_t c = jl_ld_coherent(&w.slot_count[s]);
+        if (c >= S.min_reads) {
             const uint32_t k = atomicAdd(&s_ncand, 1u);
             if (k < JL_CAND_CAP) s_cand[k] = s;
-            else { atomicAdd(&s_insufficient, c); __hip_atomic_store(&slot_hap[s], (uint32_t)JL_HAP_INSUFFICIENT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+            else { atomicAdd(&s_insufficient, c); __hip_atomic_store(&S.slot_hap[s], (uint32_t)JL_HAP_INSUFFICIENT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
         } else {
             atomicAdd(&s_insufficient, c);
-            __hip_atomic_store(&slot_hap[s], (uint32_t)JL_HAP_INSUFFICIENT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&S.slot_hap[s], (uint32_t)JL_HAP_INSUFFICIENT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     __syncthreads();
@@ -328,29 +344,29 @@ __device__ __forceinline__ void phase_select_block(uint32_t min_reads, uint64_t 
     if (cache) {
         for (uint32_t a = tid; a < ncand; a += nt) {
             const uint32_t sa = s_cand[a];
-            s_ccnt[a] = ld_coherent(&slot_count[sa]);
-            s_crep[a] = BYKEY ? sa : ld_coherent(&slot_rep[sa]);
+            s_ccnt[a] = jl_ld_coherent(&w.slot_count[sa]);
+            s_crep[a] = BYKEY ? sa : jl_ld_coherent(&w.slot_rep[sa]);
         }
         __syncthreads();
     }
     // ... and, when they fit, the candidates' keys: equal counts are common among the small groups, and every tie was two
     // more trips to the key buffer
-    const bool keys_lds = !BYKEY && cache && key_cache && (uint64_t)ncand * kwords <= key_cache_words;
+    const bool keys_lds = !BYKEY && cache && key_cache && (uint64_t)ncand * kwords <= lds.key_cache_words;
     if (keys_lds) {
         for (uint32_t q = tid; q < ncand * kwords; q += nt) {
             const uint32_t a = q / kwords, g = q - a * kwords;
-            key_cache[q] = keys[(uint64_t)g * reads_pad + s_crep[a]];
+            key_cache[q] = w.keys[(uint64_t)g * w.reads_pad + s_crep[a]];
         }
         __syncthreads();
     }
     // rank sort: (count desc, pattern asc); patterns are unique so ranks are a permutation
     for (uint32_t a = tid; a < ncand; a += nt) {
-        const uint32_t sa = s_cand[a], ca = cache ? s_ccnt[a] : ld_coherent(&slot_count[sa]);
-        const uint32_t ra = cache ? s_crep[a] : (BYKEY ? sa : ld_coherent(&slot_rep[sa]));
+        const uint32_t sa = s_cand[a], ca = cache ? s_ccnt[a] : jl_ld_coherent(&w.slot_count[sa]);
+        const uint32_t ra = cache ? s_crep[a] : (BYKEY ? sa : jl_ld_coherent(&w.slot_rep[sa]));
         uint32_t rank = 0;
         if (cache && (BYKEY || keys_lds)) {
             // everything the comparison needs sits in LDS: one pass without a trip to memory
-            const uint64_t ka0 = BYKEY ? ld_coherent64(&slot_key[sa]) : key_cache[a * kwords];
+            const uint64_t ka0 = BYKEY ? jl_ld_coherent64(&w.slot_key[sa]) : key_cache[a * kwords];
             // eight candidates per trip, count and first key word of each read unconditionally (independent LDS reads in
             // flight: one at a time behind a data-dependent branch was 380 cycles per candidate, and equal counts are the
             // rule among small groups); only equal counts AND equal first words go on to the remaining words
@@ -367,7 +383,7 @@ __device__ __forceinline__ void phase_select_block(uint32_t min_reads, uint64_t 
                 for (uint32_t j = 0; j < 8u; ++j) {
                     const uint32_t b = b0 + j < ncand ? b0 + j : a;
                     cb[j] = l_ccnt[b];
-                    kb[j] = BYKEY ? ld_coherent64(&slot_key[l_cand[b]]) : l_key[b * kwords];
+                    kb[j] = BYKEY ? jl_ld_coherent64(&w.slot_key[l_cand[b]]) : l_key[b * kwords];
                 }
                 uint32_t ties = 0;
 #pragma unroll
@@ -388,29 +404,29 @@ __device__ __forceinline__ void phase_select_block(uint32_t min_reads, uint64_t 
         } else
         for (uint32_t b = 0; b < ncand; ++b) {
             if (b == a) continue;
-            const uint32_t sb = s_cand[b], cb = cache ? s_ccnt[b] : ld_coherent(&slot_count[sb]);
+            const uint32_t sb = s_cand[b], cb = cache ? s_ccnt[b] : jl_ld_coherent(&w.slot_count[sb]);
             if (cb > ca) { ++rank; continue; }
             if (cb < ca) continue;
             if (BYKEY) {
-                const uint64_t ka = ld_coherent64(&slot_key[sa]);
-                const uint64_t kb = ld_coherent64(&slot_key[sb]);
+                const uint64_t ka = jl_ld_coherent64(&w.slot_key[sa]);
+                const uint64_t kb = jl_ld_coherent64(&w.slot_key[sb]);
                 if (kb < ka) ++rank;
                 continue;
             }
-            const uint32_t rb = cache ? s_crep[b] : ld_coherent(&slot_rep[sb]);
+            const uint32_t rb = cache ? s_crep[b] : jl_ld_coherent(&w.slot_rep[sb]);
             for (uint32_t g = 0; g < kwords; ++g) {
-                const uint64_t ka = keys[(uint64_t)g * reads_pad + ra], kb = keys[(uint64_t)g * reads_pad + rb];
+                const uint64_t ka = w.keys[(uint64_t)g * w.reads_pad + ra], kb = w.keys[(uint64_t)g * w.reads_pad + rb];
                 if (kb != ka) { if (kb < ka) ++rank; break; }
             }
         }
         if (rank < JL_MAX_HAPLOTYPES) {
-            hap_count[rank] = ca;
+            S.hap_count[rank] = ca;
             s_hrep[rank] = ra;  // BYKEY: the slot, else a read carrying the pattern
-            __hip_atomic_store(&slot_hap[sa], rank, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // write-through: read by other workgroups
+            __hip_atomic_store(&S.slot_hap[sa], rank, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // write-through: read by other workgroups
             atomicAdd(&s_reported, ca);
             atomicAdd(&s_nhap, 1u);
         } else {
-            __hip_atomic_store(&slot_hap[sa], (uint32_t)JL_HAP_INSUFFICIENT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&S.slot_hap[sa], (uint32_t)JL_HAP_INSUFFICIENT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             atomicAdd(&s_insufficient, ca);
         }
     }
@@ -425,12 +441,12 @@ __device__ __forceinline__ void phase_select_block(uint32_t min_reads, uint64_t 
     }
     for (uint32_t q = tid; q < H * vp; q += nt) {
         const uint32_t h = q / vp, p = q - h * vp;
-        hap_pattern[(uint64_t)h * JL_VARIANT_CAP + p] = (uint8_t)pattern_code<BYKEY>(keys, slot_key, reads_pad, vp, s_hrep[h], p);
+        S.hap_pattern[(uint64_t)h * JL_VARIANT_CAP + p] = (uint8_t)pattern_code<BYKEY>(w, vp, s_hrep[h], p);
     }
     // With the cache (free again after the ranking) the co-occurrence sums run out of LDS: the haplotype counts and, per
     // variant, the set of haplotypes that carry it as a bit mask — filled by the hit loop below.  (Summing over two
     // global hit rows per pair was most of this launch at 49 variants x 125 haplotypes: 98 us.)
-    const uint32_t nvc_l = nv < cooc_cap ? nv : cooc_cap;
+    const uint32_t nvc_l = nv < S.cooc_cap ? nv : S.cooc_cap;
     constexpr uint32_t kHapWords = (JL_MAX_HAPLOTYPES + 31u) / 32u;
     const bool cooc_lds = cache && (uint64_t)nvc_l * kHapWords + 1024u <= 2u * JL_CAND_CAP;
     uint32_t *s_hc = cache, *s_bits = cache ? cache + 1024 : nullptr;   // [JL_MAX_HAPLOTYPES <= 1024], [nvc][kHapWords]
@@ -442,22 +458,22 @@ __device__ __forceinline__ void phase_select_block(uint32_t min_reads, uint64_t 
     for (uint32_t q = tid; q < nv * H; q += nt) {
         const uint32_t v = q / H, h = q - v * H;
         // BYKEY: the table (and col2pos) may come from another workgroup of this launch
-        const uint32_t c = BYKEY ? ld_coherent(&variants[v].col) : variants[v].col;
+        const uint32_t c = BYKEY ? jl_ld_coherent(&S.variants[v].col) : S.variants[v].col;
         uint8_t x = 0;
-        if (c + 2u < n_cols) {  // rows outside this window never hit
-            const uint32_t p = BYKEY ? ld_coherent(&col2pos[c]) : col2pos[c];
+        if (c + 2u < S.n_cols) {  // rows outside this window never hit
+            const uint32_t p = BYKEY ? jl_ld_coherent(&S.col2pos[c]) : S.col2pos[c];
             // ref_codon / codon / flags share one dword
-            const uint32_t cw = BYKEY ? ld_coherent(reinterpret_cast<const uint32_t *>(&variants[v]) + 3) : 0u;
-            const uint32_t codon = BYKEY ? ((cw >> 8) & 0xFFu) : (uint32_t)variants[v].codon;
-            x = pattern_code<BYKEY>(keys, slot_key, reads_pad, vp, s_hrep[h], p) == codon;
+            const uint32_t cw = BYKEY ? jl_ld_coherent(reinterpret_cast<const uint32_t *>(&S.variants[v]) + 3) : 0u;
+            const uint32_t codon = BYKEY ? ((cw >> 8) & 0xFFu) : (uint32_t)S.variants[v].codon;
+            x = pattern_code<BYKEY>(w, vp, s_hrep[h], p) == codon;
         }
-        hit[(uint64_t)v * JL_MAX_HAPLOTYPES + h] = x;
+        S.hit[(uint64_t)v * JL_MAX_HAPLOTYPES + h] = x;
         if (cooc_lds && x && v < nvc_l) atomicOr(&s_bits[v * kHapWords + (h >> 5)], 1u << (h & 31u));
     }
     __syncthreads();
     // co-occurrence over the reported haplotypes, for the first cooc_cap variants
     if (cooc_lds) {
-        for (uint32_t h = tid; h < H; h += nt) s_hc[h] = hap_count[h];
+        for (uint32_t h = tid; h < H; h += nt) s_hc[h] = S.hap_count[h];
         __syncthreads();
         for (uint32_t q = tid; q < nvc_l * nvc_l; q += nt) {
             const uint32_t v = q / nvc_l, w = q - v * nvc_l;
@@ -469,7 +485,7 @@ __device__ __forceinline__ void phase_select_block(uint32_t min_reads, uint64_t 
                     m &= m - 1u;
                 }
             }
-            cooc[(uint64_t)v * cooc_cap + w] = sum;
+            S.cooc[(uint64_t)v * S.cooc_cap + w] = sum;
         }
     } else {
         const uint32_t nvc = nvc_l;
@@ -477,61 +493,42 @@ __device__ __forceinline__ void phase_select_block(uint32_t min_reads, uint64_t 
             const uint32_t v = q / nvc, w = q - v * nvc;
             uint32_t sum = 0;
             for (uint32_t h = 0; h < H; ++h)
-                if (hit[(uint64_t)v * JL_MAX_HAPLOTYPES + h] && hit[(uint64_t)w * JL_MAX_HAPLOTYPES + h]) sum += hap_count[h];
-            cooc[(uint64_t)v * cooc_cap + w] = sum;
+                if (S.hit[(uint64_t)v * JL_MAX_HAPLOTYPES + h] && S.hit[(uint64_t)w * JL_MAX_HAPLOTYPES + h]) sum += S.hap_count[h];
+            S.cooc[(uint64_t)v * S.cooc_cap + w] = sum;
         }
     }
     } else if (tid == 0) {
         __hip_atomic_store(&meta->id_bits, 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // nothing phased: every read is "damaged"
-        if (exp_head) {
-            exp_head[0] = 0; exp_head[1] = 0; exp_head[2] = 0;
-            exp_head[3] = 0; exp_head[4] = 0; exp_head[5] = 0; exp_head[6] = 0; exp_head[7] = 0;
+        if (S.exp_head) {
+            S.exp_head[0] = 0; S.exp_head[1] = 0; S.exp_head[2] = 0;
+            S.exp_head[3] = 0; S.exp_head[4] = 0; S.exp_head[5] = 0; S.exp_head[6] = 0; S.exp_head[7] = 0;
         }
     }
     __syncthreads();
     // device copy double-buffered by the parity of the run index (an exchange may still read run n's block while
     // run n+1 writes its own); an exporting run has no result block: its groups ARE the result
-    if (!exp_count) {
-        pk += __hip_atomic_load(seq_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1u;
-        jl_result_pack_block(variants, ld_coherent(&n_rows[0]), meta, 1u, vpcols, hap_count, hap_pattern, hit, cooc, cooc_cap, 1u, pk,
-                             mirror, BYKEY);
+    if (!S.exp_count) {
+        jl_pack *pk = S.pk + (__hip_atomic_load(S.seq_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1u);
+        jl_result_pack_block(S.variants, jl_ld_coherent(&S.n_rows[0]), meta, 1u, w.vpcols, S.hap_count, S.hap_pattern, S.hit, S.cooc,
+                             S.cooc_cap, 1u, pk, S.mirror, BYKEY);
     }
-    // leave the table empty for the next run: only the slots this run touched
-    for (uint32_t q = tid; q < n_occ; q += nt) {
-        const uint32_t s = ld_coherent(&occupied[q]);
-        slot_key[s] = ~0ull;
-        slot_rep[s] = 0xFFFFFFFFu;
-        slot_count[s] = 0;
-    }
+    empty_used_slots(w, n_occ);
 }
 
-__global__ __launch_bounds__(1024) void phase_select_kernel(uint32_t min_reads, uint64_t reads_pad, const uint64_t *keys,
-                                                             jl_phase_meta *meta, uint32_t *slot_rep,
-                                                             uint32_t *slot_count, const uint32_t *occupied,
-                                                             uint32_t *slot_hap, const jl_variant *variants,
-                                                             const uint32_t *col2pos, uint32_t n_cols,
-                                                             uint32_t *hap_count, uint8_t *hap_pattern, uint8_t *hit,
-                                                             const uint32_t *n_rows, const uint32_t *vpcols,
-                                                             uint32_t *cooc, uint32_t cooc_cap, jl_pack *pk,
-                                                             jl_pack *mirror, unsigned long long *slot_key,
-                                                             uint32_t *seq_dev, volatile uint32_t *seq_host,
-                                                             uint32_t *exp_count, uint8_t *exp_pattern, uint32_t exp_cap,
-                                                             uint32_t exp_stride, uint32_t *exp_head)
+// The multi-word pipeline's selection.  The argument block travels by value, i.e. in the kernel-argument segment (see the
+// comment above JL_GROUP_MAX: pointers loaded from there are known to be global ones).
+__global__ __launch_bounds__(1024) void phase_select_kernel(jl_win_phase w)
 {
     __shared__ uint32_t s_select[JL_SELECT_LDS_WORDS];
     __shared__ uint32_t s_cache[2u * JL_CAND_CAP];
     __shared__ unsigned long long s_keys[2048];
-    phase_select_block<false>(min_reads, reads_pad, keys, meta, slot_rep, slot_count, occupied, slot_hap, variants, col2pos,
-                              n_cols, hap_count, hap_pattern, hit, n_rows, vpcols, cooc, cooc_cap, pk, mirror, slot_key, seq_dev,
-                              s_select, exp_count, exp_pattern, exp_cap, exp_stride, s_cache, s_keys, 2048u, exp_head);
-    if (seq_host) {  // last kernel of the run: the result block is on its way to the host
+    phase_select_block<false>(w, select_lds{s_select, s_cache, s_keys, 2048u});
+    if (w.S.seq_host) {  // last kernel of the run: the result block is on its way to the host
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (threadIdx.x == 0) signal_done(seq_dev, seq_host);
+        if (threadIdx.x == 0) jl_signal_done(w.S.seq_dev, w.S.seq_host);
     }
 }
-
-typedef jl_select_args select_args;
 
 // ---------------------------------------------------------------------------------------- fused keys + group
 // Vp <= 10: the whole pattern is ONE 64-bit word, so the table can be keyed by value (64-bit CAS, no
@@ -557,7 +554,7 @@ struct plan_state {   // LDS: what the prologue derives — identical in every w
 };
 
 // Distinct start columns of the called positions, ascending, from the call masks (SPEC §8).  All 256 threads.
-__device__ __forceinline__ void plan_prologue(const select_args &S, uint32_t n_cols, plan_state &L)
+__device__ __forceinline__ void plan_prologue(const jl_select_args &S, uint32_t n_cols, plan_state &L)
 {
     const uint32_t tid = threadIdx.x;
     if (tid == 0) { L.n_list = 0; L.n_rows = 0; L.vp = 0; L.ovf = 0; }
@@ -603,14 +600,6 @@ __device__ __forceinline__ void plan_prologue(const select_args &S, uint32_t n_c
     __syncthreads();
 }
 
-__device__ __forceinline__ uint32_t key_code(uint64_t key, uint32_t vp, uint32_t p) { return (uint32_t)(key >> (6u * (vp - 1u - p))) & 63u; }
-// the same for a pattern of up to 20 positions in two words: positions 0..9 in w0, the rest in w1
-__device__ __forceinline__ uint32_t key_code2(uint64_t w0, uint64_t w1, uint32_t vp, uint32_t p)
-{
-    const uint32_t n0 = vp < JL_POS_PER_WORD ? vp : JL_POS_PER_WORD;
-    return p < n0 ? key_code(w0, n0, p) : key_code(w1, vp - n0, p - n0);
-}
-
 // Selection of the single-word pipeline out of LDS: every table word it needs is fetched ONCE (occupied list -> counts
 // and keys: two dependent round trips), ranking, patterns, hit matrix and co-occurrence then run on LDS copies, and
 // the result block is stored from there.  The general routine above chases each of them through memory again (a
@@ -620,9 +609,9 @@ __device__ __forceinline__ uint32_t key_code2(uint64_t w0, uint64_t w1, uint32_t
 __device__ __forceinline__ void two_word_cleanup(const jl_two_word &tw)
 {
     const uint32_t tid = threadIdx.x, nt = blockDim.x;
-    const uint32_t na = ld_coherent(&tw.n_occ[0]), nb = ld_coherent(&tw.n_occ[1]);
-    for (uint32_t q = tid; q < na; q += nt) tw.key_a[ld_coherent(&tw.occ_a[q])] = ~0ull;
-    for (uint32_t q = tid; q < nb; q += nt) tw.key_b[ld_coherent(&tw.occ_b[q])] = ~0ull;
+    const uint32_t na = jl_ld_coherent(&tw.n_occ[0]), nb = jl_ld_coherent(&tw.n_occ[1]);
+    for (uint32_t q = tid; q < na; q += nt) tw.key_a[jl_ld_coherent(&tw.occ_a[q])] = ~0ull;
+    for (uint32_t q = tid; q < nb; q += nt) tw.key_b[jl_ld_coherent(&tw.occ_b[q])] = ~0ull;
     __syncthreads();
     if (tid == 0) { tw.n_occ[0] = 0; tw.n_occ[1] = 0; }
 }
@@ -641,20 +630,58 @@ struct sel_lds {
 static_assert(sizeof(sel_lds) <= kLdsSlots * 5u * 4u, "the selection's scratch must fit the grouping tables");
 static_assert(offsetof(sel_lds, hmask) % 8 == 0, "a variant's haplotype set is read as two 64-bit words");
 
+// All the LDS of a workgroup of the fused launch; NS table sets.  One set = the grouping tables (8 + 3 x 4 KB), lent to the
+// selection once the grouping is done.  The two-word launch has two sets: its first two rounds — the two words of the
+// patterns, independent of each other — run together, one set each.
+template <uint32_t NS>
+struct fused_lds {
+    unsigned long long tables[NS][kLdsSlots * 5u / 2u];
+    plan_state plan;
+    unsigned long long dom[NS];                             // dominant key of the block, per set
+    uint32_t domcnt[NS], domfirst, domslot[NS], nlist[NS];
+    uint32_t last, cat[4], idbits, scan[4], running;
+    uint16_t list[NS][kLdsSlots];                           // the occupied slots of a set, densely
+    // a set's four tables, [kLdsSlots] each
+    __device__ __forceinline__ unsigned long long *key(uint32_t z) { return tables[z]; }
+    __device__ __forceinline__ uint32_t *cnt(uint32_t z) { return reinterpret_cast<uint32_t *>(tables[z] + kLdsSlots); }
+    __device__ __forceinline__ uint32_t *first(uint32_t z) { return cnt(z) + kLdsSlots; }
+    __device__ __forceinline__ uint32_t *gslot(uint32_t z) { return cnt(z) + 2u * kLdsSlots; }
+    // what the selections take of set 0 once the grouping is done
+    __device__ __forceinline__ sel_lds &selection() { return *reinterpret_cast<sel_lds *>(tables[0]); }
+    // Empties the first n_sets sets and their dominant-key words.  All 256 threads; no barrier: the caller's follows.
+    __device__ __forceinline__ void clear_sets(uint32_t n_sets)
+    {
+        const uint32_t tid = threadIdx.x;
+        for (uint32_t z = 0; z < n_sets; ++z) {
+            for (uint32_t i = tid; i < kLdsSlots; i += 256u) { key(z)[i] = kNoKey; cnt(z)[i] = 0; first(z)[i] = 0xFFFFFFFFu; }
+            if (tid == 0) { dom[z] = kNoKey; domcnt[z] = 0; domslot[z] = 0; nlist[z] = 0; }
+        }
+        if (tid == 0) domfirst = 0xFFFFFFFFu;
+    }
+};
+
+// what the last workgroup requests for the selection beside the read categories, one round trip for all of it
+struct select_pre {
+    uint32_t nv, n_rows;      // rows of the variant table in use / in all
+    uint32_t n_occ, occ0;     // the group count and this thread's first entry of the group list (only meaningful below n_occ)
+};
+
 // KW = 2: the main table's key of a group is the pair (slot of its first word in table A, slot of its second word in
 // table B); the words themselves are one more round trip away (jl_two_word).
 // `ranked(bits)`: called by every thread once the slot -> haplotype table is complete and performed (the ids depend on nothing
 // else): the caller releases the workgroups that wait for it and writes its own reads' ids THERE, so that the rest of the
 // selection — hit matrix, co-occurrence, result block: 3.5 us at five positions, 11 at sixteen — runs beside the other
 // workgroups' ids instead of in front of them.
-template <int KW, typename Ranked>
-__device__ __forceinline__ bool phase_select_lds(const jl_win_phase &w, const plan_state &L, uint32_t vp, uint32_t nv,
-                                                 uint32_t n_rows, sel_lds &T, const jl_two_word *tw, uint32_t n_occ, uint32_t occ0,
-                                                 const uint32_t *cat, uint32_t *id_bits_out, Ranked &&ranked)
+template <int KW, uint32_t NS, typename Ranked>
+__device__ __forceinline__ bool phase_select_lds(const jl_win_phase &w, const jl_two_word *tw, fused_lds<NS> &F, uint32_t vp,
+                                                 const select_pre &pre, uint32_t *id_bits_out, Ranked &&ranked)
 {
-    // n_occ, occ0: the group count and this thread's first entry of the group list, loaded by the caller beside the read
-    // categories (occ0 is only meaningful below n_occ); cat: the read categories of the whole window (LDS)
-    const select_args &S = w.S;
+    // of the LDS: the plan's columns, the scratch, and the read categories of the whole window (summed by the caller)
+    const plan_state &L = F.plan;
+    sel_lds &T = F.selection();
+    const uint32_t *cat = F.cat;
+    const uint32_t nv = pre.nv, n_rows = pre.n_rows, n_occ = pre.n_occ, occ0 = pre.occ0;
+    const jl_select_args &S = w.S;
     jl_phase_meta *meta = w.meta;
     const uint32_t tid = threadIdx.x, nt = blockDim.x;
     if (tid == 0) { T.ncand = 0; T.insufficient = 0; T.reported = 0; T.bail = (nv > JL_PACK_MAX_VAR || n_rows > JL_PACK_MAX_VAR) ? 1u : 0u; }
@@ -675,16 +702,16 @@ __device__ __forceinline__ bool phase_select_lds(const jl_win_phase &w, const pl
     uint32_t row_c = 0, row_cw = 0;
     if (tid < nv) {
         const uint32_t *row = reinterpret_cast<const uint32_t *>(S.variants + tid);
-        row_c = ld_coherent(row + 2);
-        row_cw = ld_coherent(row + 3);
+        row_c = jl_ld_coherent(row + 2);
+        row_cw = jl_ld_coherent(row + 3);
     }
     const uint32_t seq_pre = __hip_atomic_load(S.seq_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     uint32_t tw_n[2] = {0, 0}, tw_first[2] = {0, 0};
     if (KW == 2) {
-        tw_n[0] = ld_coherent(&tw->n_occ[0]);
-        tw_n[1] = ld_coherent(&tw->n_occ[1]);
-        tw_first[0] = ld_coherent(&tw->occ_a[tid]);   // (the lists hold at least 256 entries; used below the counts only)
-        tw_first[1] = ld_coherent(&tw->occ_b[tid]);
+        tw_n[0] = jl_ld_coherent(&tw->n_occ[0]);
+        tw_n[1] = jl_ld_coherent(&tw->n_occ[1]);
+        tw_first[0] = jl_ld_coherent(&tw->occ_a[tid]);   // (the lists hold at least 256 entries; used below the counts only)
+        tw_first[1] = jl_ld_coherent(&tw->occ_b[tid]);
     }
     for (uint32_t q0 = 0; q0 < n_occ; q0 += 4u * nt) {
         uint32_t sl[4], cn[4];
@@ -692,15 +719,15 @@ __device__ __forceinline__ bool phase_select_lds(const jl_win_phase &w, const pl
 #pragma unroll
         for (uint32_t j = 0; j < 4u; ++j) {
             const uint32_t q = q0 + j * nt + tid;
-            sl[j] = q < n_occ ? ((q0 == 0u && j == 0u) ? occ0 : ld_coherent(&w.occupied[q])) : 0xFFFFFFFFu;
+            sl[j] = q < n_occ ? ((q0 == 0u && j == 0u) ? occ0 : jl_ld_coherent(&w.occupied[q])) : 0xFFFFFFFFu;
         }
 #pragma unroll
         for (uint32_t j = 0; j < 4u; ++j) {
             cn[j] = 0;
             ky[j] = 0;
             if (sl[j] != 0xFFFFFFFFu) {
-                cn[j] = ld_coherent(&w.slot_count[sl[j]]);
-                ky[j] = ld_coherent64(&w.slot_key[sl[j]]);
+                cn[j] = jl_ld_coherent(&w.slot_count[sl[j]]);
+                ky[j] = jl_ld_coherent64(&w.slot_key[sl[j]]);
             }
         }
 #pragma unroll
@@ -734,7 +761,7 @@ __device__ __forceinline__ bool phase_select_lds(const jl_win_phase &w, const pl
     // the variant rows: column -> position index, codon (the table may come from another workgroup of this launch)
     for (uint32_t v = tid; v < nv; v += nt) {
         const uint32_t *row = reinterpret_cast<const uint32_t *>(S.variants + v);
-        const uint32_t c = v == tid ? row_c : ld_coherent(row + 2), cw = v == tid ? row_cw : ld_coherent(row + 3);
+        const uint32_t c = v == tid ? row_c : jl_ld_coherent(row + 2), cw = v == tid ? row_cw : jl_ld_coherent(row + 3);
         uint32_t pos = 0xFFu;
         if (c + 2u < S.n_cols)
             for (uint32_t p = 0; p < vp; ++p) pos = L.cols[p] == c ? p : pos;
@@ -752,8 +779,8 @@ __device__ __forceinline__ bool phase_select_lds(const jl_win_phase &w, const pl
     if (KW == 2) {   // the candidates' two words, from the half-key tables
         for (uint32_t a = tid; a < H; a += nt) {
             const unsigned long long pair = T.key[a];
-            T.key[a] = ld_coherent64(&tw->key_a[(uint32_t)(pair >> 32)]);
-            T.key1[a] = ld_coherent64(&tw->key_b[(uint32_t)pair]);
+            T.key[a] = jl_ld_coherent64(&tw->key_a[(uint32_t)(pair >> 32)]);
+            T.key1[a] = jl_ld_coherent64(&tw->key_b[(uint32_t)pair]);
         }
         __syncthreads();
     }
@@ -762,22 +789,13 @@ __device__ __forceinline__ bool phase_select_lds(const jl_win_phase &w, const pl
     // (the first 1024 groups' slots are still in registers from the scan: stores only)
 #pragma unroll
     for (uint32_t j = 0; j < 4u; ++j)
-        if (sl_keep[j] != 0xFFFFFFFFu) {
-            w.slot_key[sl_keep[j]] = ~0ull;
-            w.slot_rep[sl_keep[j]] = 0xFFFFFFFFu;
-            w.slot_count[sl_keep[j]] = 0;
-        }
-    for (uint32_t q = 4u * nt + tid; q < n_occ; q += nt) {
-        const uint32_t sl = ld_coherent(&w.occupied[q]);
-        w.slot_key[sl] = ~0ull;
-        w.slot_rep[sl] = 0xFFFFFFFFu;
-        w.slot_count[sl] = 0;
-    }
+        if (sl_keep[j] != 0xFFFFFFFFu) empty_slot(w, sl_keep[j]);
+    for (uint32_t q = 4u * nt + tid; q < n_occ; q += nt) empty_slot(w, jl_ld_coherent(&w.occupied[q]));
     if (KW == 2) {
         if (tid < tw_n[0]) tw->key_a[tw_first[0]] = ~0ull;
         if (tid < tw_n[1]) tw->key_b[tw_first[1]] = ~0ull;
-        for (uint32_t q = nt + tid; q < tw_n[0]; q += nt) tw->key_a[ld_coherent(&tw->occ_a[q])] = ~0ull;
-        for (uint32_t q = nt + tid; q < tw_n[1]; q += nt) tw->key_b[ld_coherent(&tw->occ_b[q])] = ~0ull;
+        for (uint32_t q = nt + tid; q < tw_n[0]; q += nt) tw->key_a[jl_ld_coherent(&tw->occ_a[q])] = ~0ull;
+        for (uint32_t q = nt + tid; q < tw_n[1]; q += nt) tw->key_b[jl_ld_coherent(&tw->occ_b[q])] = ~0ull;
         if (tid == 0) { tw->n_occ[0] = 0; tw->n_occ[1] = 0; }   // (every thread has its copy of the counts)
     }
     // rank: (count desc, pattern asc); patterns are unique, so the ranks are a permutation.  Two threads per candidate
@@ -956,7 +974,7 @@ __device__ __forceinline__ bool phase_select_lds(const jl_win_phase &w, const pl
             if (!o) continue;
             for (uint32_t i = tid; i < nv * (uint32_t)(sizeof(jl_variant) / 8); i += nt)
                 reinterpret_cast<unsigned long long *>(o->variants)[i] =
-                    ld_coherent64(reinterpret_cast<const unsigned long long *>(S.variants) + i);
+                    jl_ld_coherent64(reinterpret_cast<const unsigned long long *>(S.variants) + i);
             for (uint32_t i = tid; i < vp; i += nt) o->pos_cols[i] = L.cols[i];
             for (uint32_t i = tid; i < n_cnt8; i += nt) reinterpret_cast<unsigned long long *>(o->hap_count)[i] = cnt8[i];
             for (uint32_t i = tid; i < n_pat8; i += nt) reinterpret_cast<unsigned long long *>(o->hap_pattern)[i] = pat8[i];
@@ -975,24 +993,24 @@ template <int KW>
 __device__ __forceinline__ void phase_export_fast(const jl_win_phase &w, uint32_t vp, const uint32_t *cat, uint32_t *s_acc,
                                                   const jl_two_word *tw = nullptr)
 {
-    const select_args &S = w.S;
+    const jl_select_args &S = w.S;
     jl_phase_meta *meta = w.meta;
     const uint32_t tid = threadIdx.x, nt = blockDim.x;
     if (tid == 0) *s_acc = 0;
     // trip 1 (the occupied list always holds at least one entry per thread: it is sized by the reads)
-    const uint32_t n_occ = ld_coherent(&meta->n_occupied);
-    uint32_t s_first = ld_coherent(&w.occupied[tid]);
+    const uint32_t n_occ = jl_ld_coherent(&meta->n_occupied);
+    uint32_t s_first = jl_ld_coherent(&w.occupied[tid]);
     __syncthreads();
     uint32_t clean = 0;
     for (uint32_t q = tid; q < n_occ; q += nt) {
-        const uint32_t s = q == tid ? s_first : ld_coherent(&w.occupied[q]);
+        const uint32_t s = q == tid ? s_first : jl_ld_coherent(&w.occupied[q]);
         // trip 2: both words of the group before either is used
-        const uint32_t c = ld_coherent(&w.slot_count[s]);
-        unsigned long long key = ld_coherent64(&w.slot_key[s]), key_b = 0;
+        const uint32_t c = jl_ld_coherent(&w.slot_count[s]);
+        unsigned long long key = jl_ld_coherent64(&w.slot_key[s]), key_b = 0;
         if (KW == 2) {   // the pair of half-key slots -> the two words (one more round trip, all groups at once)
             const unsigned long long pair = key;
-            key = ld_coherent64(&tw->key_a[(uint32_t)(pair >> 32)]);
-            key_b = ld_coherent64(&tw->key_b[(uint32_t)pair]);
+            key = jl_ld_coherent64(&tw->key_a[(uint32_t)(pair >> 32)]);
+            key_b = jl_ld_coherent64(&tw->key_b[(uint32_t)pair]);
         }
         clean += c;
         // the slot remembers WHICH exported group it is: the merge answers per group
@@ -1006,10 +1024,7 @@ __device__ __forceinline__ void phase_export_fast(const jl_win_phase &w, uint32_
                 *reinterpret_cast<unsigned long long *>(S.exp_pattern + (uint64_t)q * S.exp_stride + p8) = out;
             }
         }
-        // leave the table empty for the next run: only the slots this run touched
-        w.slot_key[s] = ~0ull;
-        w.slot_rep[s] = 0xFFFFFFFFu;
-        w.slot_count[s] = 0;
+        empty_slot(w, s);
     }
     clean = wave_sum_all(clean);
     if ((tid & 63u) == 0 && clean) atomicAdd(s_acc, clean);
@@ -1040,91 +1055,82 @@ __device__ __forceinline__ void phase_export_fast(const jl_win_phase &w, uint32_
     }
 }
 
-__device__ __forceinline__ uint32_t global_insert64(uint64_t key, uint32_t cnt, uint32_t first, uint64_t slots_mask,
-                                                    unsigned long long *__restrict__ slot_key,
-                                                    uint32_t *__restrict__ slot_rep, uint32_t *__restrict__ slot_count,
-                                                    uint32_t *__restrict__ occupied, uint32_t *__restrict__ n_occupied)
+// a global grouping table (rep / cnt null: a table that only numbers its keys — the half-key tables of the two-word launch)
+struct table_t { unsigned long long *key; uint32_t *rep, *cnt, *occ, *nocc; uint64_t mask; };
+
+__device__ __forceinline__ uint32_t global_insert64(uint64_t key, uint32_t cnt, uint32_t first, const table_t &T)
 {
-    // (slot_rep / slot_count null: a table that only numbers its keys — the half-key tables of the two-word launch)
-    uint64_t s = mix64(key + 0x9E3779B97F4A7C15ull) & slots_mask;
+    uint64_t s = mix64(key + 0x9E3779B97F4A7C15ull) & T.mask;
     for (;;) {
         // Look first: a slot's key never changes within a run, so a resident key read past the L1 is final and needs no
         // atomic.  Same-address atomics serialise at the memory side (about 12 ns each): with one CAS per workgroup on
         // the wild type's slot a million reads queued 500 of them in front of every workgroup's arrival.
-        unsigned long long old = ld_coherent64(&slot_key[s]);
-        if (old == kNoKey) old = atomicCAS(&slot_key[s], (unsigned long long)kNoKey, (unsigned long long)key);
+        unsigned long long old = jl_ld_coherent64(&T.key[s]);
+        if (old == kNoKey) old = atomicCAS(&T.key[s], (unsigned long long)kNoKey, (unsigned long long)key);
         if (old == kNoKey) {
             // write-through stores: the selection may run in another workgroup of this launch
-            if (slot_rep) __hip_atomic_store(&slot_rep[s], first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // any read carrying the key
-            __hip_atomic_store(&occupied[atomicAdd(n_occupied, 1u)], (uint32_t)s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (T.rep) __hip_atomic_store(&T.rep[s], first, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // any read carrying the key
+            __hip_atomic_store(&T.occ[atomicAdd(T.nocc, 1u)], (uint32_t)s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             old = key;
         }
         if (old == key) {
-            if (slot_count) atomicAdd(&slot_count[s], cnt);
+            if (T.cnt) atomicAdd(&T.cnt[s], cnt);
             return (uint32_t)s;
         }
-        s = (s + 1u) & slots_mask;
+        s = (s + 1u) & T.mask;
     }
 }
 
-template <int KW>
-__device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const jl_direct_cols *dc = nullptr, const jl_two_word *tw = nullptr)
+// ---- the stages of a workgroup of the fused launch, in the order phase_fused_body goes through them.  All of them are
+// called by all 256 threads under block-uniform conditions; `L` is the workgroup's LDS.
+struct fused_plan {   // block-uniform
+    uint32_t vp, n_rows;   // variant positions; called rows (whole-path runs, else 0)
+    bool work;             // there is something to phase, and this launch's key width covers it
+};
+struct own_reads {   // what a lane keeps of its 8 reads for their ids: registers
+    uint64_t t;            // dword index within a column
+    bool live;             // never for the extra workgroup
+    uint32_t clean;        // bit 4r: read r is clean (and grouped)
+    uint32_t gslot[1][8];  // global table slot of each clean read
+};
+
+// ---- 0. the plan, from one of three sources: the call masks (whole-path runs: every workgroup derives it; the compacting
+// workgroup, `plan_block`, also writes the ordered table and the plan through to memory), the launch's direct columns, or
+// the resident plan in meta / vpcols.  Reads S.called / S.pos_col or meta and w.vpcols; writes L.plan (cols, n_rows) and,
+// in the compacting workgroup, S.rows, the *_out arrays and the run's scalars in meta with agent-scope stores.  Barriers:
+// those of plan_prologue and jl_compact_rows_block, or one after L.plan.cols (resident plan), or none (direct columns).
+// On entry nothing of this launch has to be complete.
+template <int KW, uint32_t NS>
+__device__ __forceinline__ fused_plan fused_plan_stage(const jl_win_phase &w, const jl_direct_cols *dc, bool plan_block, fused_lds<NS> &L)
 {
     constexpr uint32_t NP = (uint32_t)KW * JL_POS_PER_WORD;   // positions this instantiation covers
-    const uint8_t *__restrict__ msa = w.msa;
-    const uint64_t col_stride = w.col_stride, n_reads = w.n_reads, reads_pad = w.reads_pad;
+    const jl_select_args &S = w.S;
     jl_phase_meta *meta = w.meta;
-    uint64_t *keys = w.keys;
-    uint32_t *flagw = w.flagw;
-    const uint64_t slots_mask = w.slots_mask;
-    unsigned long long *slot_key = w.slot_key;
-    uint32_t *slot_rep = w.slot_rep, *slot_count = w.slot_count, *occupied = w.occupied, *read_slot = w.read_slot;
-    const select_args &S = w.S;
-    // one LDS block per table set: the grouping tables (8 + 3 x 4 KB), lent to the selection once the grouping is done.  The
-    // two-word launch has two sets: its first two rounds — the two words of the patterns, independent of each other — run
-    // together, one set each.
-    constexpr uint32_t NS = KW == 2 ? 2u : 1u;
-    __shared__ unsigned long long s_tables[NS][kLdsSlots * 5u / 2u];
-    auto s_key = [&](uint32_t z) -> unsigned long long * { return s_tables[z]; };                                          // [kLdsSlots]
-    auto s_cnt = [&](uint32_t z) -> uint32_t * { return reinterpret_cast<uint32_t *>(s_tables[z] + kLdsSlots); };          // [kLdsSlots]
-    auto s_first = [&](uint32_t z) -> uint32_t * { return s_cnt(z) + kLdsSlots; };                                         // [kLdsSlots]
-    auto s_gslot = [&](uint32_t z) -> uint32_t * { return s_cnt(z) + 2u * kLdsSlots; };                                    // [kLdsSlots]
-    __shared__ plan_state s_plan;
-    __shared__ unsigned long long s_dom[NS];
-    __shared__ uint32_t s_domcnt[NS], s_domfirst, s_domslot[NS], s_nlist[NS];
-    __shared__ uint32_t s_last, s_cat[4], s_idbits, s_scan[4], s_running;
-    __shared__ uint16_t s_list[NS][kLdsSlots];
     const uint32_t tid = threadIdx.x;
-    const bool from_called = S.called != nullptr;
-    // whole-path runs launch one workgroup more than the reads need: it compacts the called rows meanwhile
-    const uint32_t n_arrive = w.n_blocks + (from_called ? 1u : 0u);
-    const bool plan_block = from_called && blockIdx.x == w.n_blocks;
-
-    // ---- 0. the plan
     uint32_t vp, n_rows;
     bool work;
-    if (from_called) {
-        plan_prologue(S, S.n_cols, s_plan);
-        const uint32_t vpt = s_plan.vp;
-        work = !s_plan.ovf && vpt >= 1u && vpt <= NP;
+    if (S.called != nullptr) {
+        plan_prologue(S, S.n_cols, L.plan);
+        const uint32_t vpt = L.plan.vp;
+        work = !L.plan.ovf && vpt >= 1u && vpt <= NP;
         vp = work ? vpt : 0u;
-        n_rows = s_plan.n_rows;
+        n_rows = L.plan.n_rows;
         if (plan_block) {
             // the ordered table (SPEC §6) + what the fetch calls and a multi-word re-run read: written through, the
             // selection runs in whichever workgroup arrives last
-            const uint32_t n = jl_compact_rows_block<false>(S.P, S.called, S.staged, S.rows, S.cap, s_scan, &s_running,
+            const uint32_t n = jl_compact_rows_block<false>(S.P, S.called, S.staged, S.rows, S.cap, L.scan, &L.running,
                                                             nullptr, 0u, true);
             if (tid < vp) {
-                __hip_atomic_store(&S.vpcols_out[tid], s_plan.cols[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&S.col2pos_out[s_plan.cols[tid]], tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&S.vpcols_out[tid], L.plan.cols[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&S.col2pos_out[L.plan.cols[tid]], tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             if (tid == 0) {
                 __hip_atomic_store(S.n_rows_out, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 const uint32_t need_kw = (vpt + JL_POS_PER_WORD - 1u) / JL_POS_PER_WORD;
                 uint32_t ovf = 0;
-                if (!work && (vpt != 0u || s_plan.ovf)) ovf = (s_plan.ovf || need_kw <= S.kwords_cap) ? JL_PHASE_OVF_FORM : JL_PHASE_OVF_KEY_WORDS;
+                if (!work && (vpt != 0u || L.plan.ovf)) ovf = (L.plan.ovf || need_kw <= S.kwords_cap) ? JL_PHASE_OVF_FORM : JL_PHASE_OVF_KEY_WORDS;
                 __hip_atomic_store(&meta->n_var, n < S.cap ? n : S.cap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&meta->vp_true, s_plan.ovf ? JL_POS_PER_WORD + 1u : vpt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&meta->vp_true, L.plan.ovf ? JL_POS_PER_WORD + 1u : vpt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(&meta->vp, vp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(&meta->kwords, work ? (uint32_t)KW : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(&meta->overflow, ovf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1140,46 +1146,42 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
         work = (mvp != 0) & (kw >= 1) & (kw <= (uint32_t)KW);   // block-uniform
         vp = work ? mvp : 0u;
         // all the column indices in one go (the array always holds JL_VARIANT_CAP words; entries past vp are never used)
-        if (tid < NP) s_plan.cols[tid] = w.vpcols[tid];
-        if (tid == 0) s_plan.n_rows = 0;
+        if (tid < NP) L.plan.cols[tid] = w.vpcols[tid];
+        if (tid == 0) L.plan.n_rows = 0;
         n_rows = 0;
         __syncthreads();
     }
-    const uint64_t t = (uint64_t)blockIdx.x * 256u + tid;  // dword index within a column = 8 reads
-    const bool live = t * 4u < col_stride;                 // never for the extra workgroup
-    uint32_t clean_keep = 0;   // bit 4r: read r of this lane is clean
-    uint32_t gslot[8];         // global table slot of each clean read
-#pragma unroll
-    for (int r = 0; r < 8; ++r) gslot[r] = 0;
-    if (work && !plan_block) {
-    auto clear_sets = [&](uint32_t n_sets) {
-        for (uint32_t z = 0; z < n_sets; ++z) {
-            for (uint32_t i = tid; i < kLdsSlots; i += 256u) { s_key(z)[i] = kNoKey; s_cnt(z)[i] = 0; s_first(z)[i] = 0xFFFFFFFFu; }
-            if (tid == 0) { s_dom[z] = kNoKey; s_domcnt[z] = 0; s_domslot[z] = 0; s_nlist[z] = 0; }
-        }
-        if (tid == 0) s_domfirst = 0xFFFFFFFFu;
-    };
-    clear_sets(NS);
-    if (tid < 4) s_cat[tid] = 0;
-    __syncthreads();
+    return {vp, n_rows, work};
+}
 
-    // ---- 1. keys and flags
+// ---- 1. keys and flags of this lane's 8 reads: kk[z][r] = word z of read r's pattern (positions 0 .. 9 in word 0, 10 .. 19
+// in word 1 of the two-word launch).  Reads L.plan.cols and the plane rows (or the direct columns); writes kk, the wave sums
+// of the read categories into L.cat (LDS atomics), and to memory the flag words (only for a separate id launch) and the
+// keys (only for the multi-word pipeline's group launch).  No barrier.  On entry L.plan.cols is complete and L.cat is zero,
+// both behind a barrier.  Returns the clean reads, bit 4r for read r.
+template <int KW, uint32_t NS>
+__device__ __forceinline__ uint32_t fused_keys_stage(const jl_win_phase &w, const jl_direct_cols *dc, uint32_t vp, uint64_t t, bool live,
+                                                     fused_lds<NS> &L, uint64_t (&kk)[KW][8])
+{
+    constexpr uint32_t NP = (uint32_t)KW * JL_POS_PER_WORD;
+    const jl_select_args &S = w.S;
+    const uint32_t tid = threadIdx.x;
     // Lanes past the end of the columns load from a clamped address and drop the value, so the loads need no
     // per-lane branch.
     uint32_t cols[NP];
 #pragma unroll
-    for (uint32_t p = 0; p < NP; ++p) cols[p] = s_plan.cols[p];
+    for (uint32_t p = 0; p < NP; ++p) cols[p] = L.plan.cols[p];
     // (a lane whose eight reads are all past the last read loads nothing of its own: a slice read in place — `direct` —
     // ends where the window's rows may end too)
-    const uint64_t t_ld = (live && t * 8u < n_reads) ? t : 0u;
+    const uint64_t t_ld = (live && t * 8u < w.n_reads) ? t : 0u;
     uint32_t wd[NP][3];
     const bool direct = dc && dc->on;   // block-uniform
 #pragma unroll
     for (uint32_t p = 0; p < NP; ++p) {
         if (p < vp) {  // block-uniform
             // nine plane rows per position (three columns x three planes), one byte = 8 reads of each
-            const uint64_t ps = direct ? dc->stride : col_stride / 4u;
-            const uint8_t *c0 = (direct && p < JL_POS_PER_WORD) ? dc->col[p] : msa + (uint64_t)cols[p] * 3u * ps;
+            const uint64_t ps = direct ? dc->stride : w.col_stride / 4u;
+            const uint8_t *c0 = (direct && p < JL_POS_PER_WORD) ? dc->col[p] : w.msa + (uint64_t)cols[p] * 3u * ps;
 #pragma unroll
             for (int k = 0; k < 3; ++k) wd[p][k] = jl_load_codes8(c0 + (uint64_t)k * 3u * ps + t_ld, ps);
         } else {
@@ -1194,48 +1196,32 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
             for (int k = 0; k < 3; ++k) wd[p][k] = 0x66666666u;
     }
     uint32_t gap = 0, het = 0, par = 0;
-    uint64_t key[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t key1[KW == 2 ? 8 : 1] = {0};   // positions 10 .. 19 (two-word launch)
+    // (built in an array of its own and handed over at the end: a round of two picks the dominant key out of kk by a run-time
+    // read number, which keeps kk in scratch there — and would send every step of the build through it)
+    uint64_t key[KW][8];
+#pragma unroll
+    for (int z = 0; z < KW; ++z)
+#pragma unroll
+        for (int r = 0; r < 8; ++r) key[z][r] = 0;
 #pragma unroll
     for (uint32_t p = 0; p < NP; ++p) {
-        if (p < vp) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const uint32_t b0 = wd[p][k] & kM1, b1 = (wd[p][k] >> 1) & kM1, b2 = (wd[p][k] >> 2) & kM1;
-                gap |= b2 & ~b1 & ~b0;
-                het |= b2 & b0;
-                par |= b2 & b1;
-            }
-            const uint32_t hi2 = wd[p][0] & 0x33333333u;
-            const uint32_t lo4 = ((wd[p][1] & 0x33333333u) << 2) | (wd[p][2] & 0x33333333u);
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const uint64_t code = (((hi2 >> (4 * r)) & 3u) << 4) | ((lo4 >> (4 * r)) & 15u);
-                if (KW == 1 || p < JL_POS_PER_WORD) key[r] = (key[r] << 6) | code;
-                else key1[KW == 2 ? r : 0] = (key1[KW == 2 ? r : 0] << 6) | code;
-            }
-        }
+        if (p < vp) key_add_position(wd[p], gap, het, par, key[p / JL_POS_PER_WORD]);
     }
-    uint32_t valid = 0;
-    if (live) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-            if (t * 8u + r < n_reads) valid |= 1u << (4 * r);
-    }
+    const uint32_t valid = live ? valid_reads8(t, w.n_reads) : 0u;
     gap &= valid; het &= valid; par &= valid;
     const uint32_t dirty = gap | het | par;
     const uint32_t cleanm = valid & ~dirty;  // bit 4r: read r is clean
     if (live && S.ids_mode == JL_IDS_SEPARATE) {
         // the flags and slots of every read are only needed by a later launch that writes the ids
-        flagw[t] = gap | (het << 1) | (par << 2) | ((valid ^ kM1) << 3);
+        w.flagw[t] = gap | (het << 1) | (par << 2) | ((valid ^ kM1) << 3);
     }
     if (KW == 1 && live && !S.run) {   // the multi-word pipeline's own group launch reads the keys
-        uint64_t *dst = keys + t * 8u;
+        uint64_t *dst = w.keys + t * 8u;
 #pragma unroll
         for (int r = 0; r < 8; r += 2) {
             ulonglong2 v;
-            v.x = key[r];
-            v.y = key[r + 1];
+            v.x = key[0][r];
+            v.y = key[0][r + 1];
             *reinterpret_cast<ulonglong2 *>(dst + r) = v;
         }
     }
@@ -1245,177 +1231,165 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
         const uint32_t n_gap = wave_sum_all(__popc(gap)), n_het = wave_sum_all(__popc(het));
         const uint32_t n_par = wave_sum_all(__popc(par)), n_dam = wave_sum_all(__popc(dirty));
         if ((tid & 63u) == 0) {
-            if (n_dam) atomicAdd(&s_cat[0], n_dam);
-            if (n_gap) atomicAdd(&s_cat[1], n_gap);
-            if (n_het) atomicAdd(&s_cat[2], n_het);
-            if (n_par) atomicAdd(&s_cat[3], n_par);
+            if (n_dam) atomicAdd(&L.cat[0], n_dam);
+            if (n_gap) atomicAdd(&L.cat[1], n_gap);
+            if (n_het) atomicAdd(&L.cat[2], n_het);
+            if (n_par) atomicAdd(&L.cat[3], n_par);
         }
     }
-    // One ROUND of grouping: the clean reads' 64-bit keys kk[z] -> the slot of each in the global table T[z] (gs[z][r]), for N
-    // independent key words at once (they share the round's barriers and their trips to the global tables overlap: a round is
-    // 6.5 us whatever it carries).  The one-word launch runs one round of one, on the patterns themselves; the two-word
-    // launch a round of two — the words of the patterns — and a round of one on the pairs of their slots (jl_two_word).
-    struct table_t { unsigned long long *key; uint32_t *rep, *cnt, *occ, *nocc; };
-    auto group_round = [&](auto n_const, const uint64_t (&kk)[decltype(n_const)::value][8], const table_t (&T)[decltype(n_const)::value],
-                           uint32_t (&gs)[decltype(n_const)::value][8], bool first_round) {
-        constexpr uint32_t N = decltype(n_const)::value;
-        if (!first_round) {   // (the first round's tables were cleared while the columns were on their way)
-            clear_sets(N);
-            __syncthreads();
-        }
-        // ---- 2. dominant key of the block = key of its first clean read
-        uint32_t myfirst = 0xFFFFFFFFu;
-        if (cleanm) myfirst = (uint32_t)(t * 8u) + ((uint32_t)__ffs((int)cleanm) - 1u) / 4u;
-        {
-            uint32_t m = myfirst;
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) m = min(m, (uint32_t)__shfl_xor((int)m, o, 64));
-            if ((tid & 63u) == 0 && m != 0xFFFFFFFFu) atomicMin(&s_domfirst, m);
-        }
+    for (int z = 0; z < KW; ++z)
+#pragma unroll
+        for (int r = 0; r < 8; ++r) kk[z][r] = key[z][r];
+    return cleanm;
+}
+
+// ---- 2-3. One ROUND of grouping: the clean reads' 64-bit keys kk[z] -> the slot of each in the global table T[z] (gs[z][r]), for N
+// independent key words at once (they share the round's barriers and their trips to the global tables overlap: a round is
+// 6.5 us whatever it carries).  The one-word launch runs one round of one, on the patterns themselves; the two-word
+// launch a round of two — the words of the patterns — and a round of one on the pairs of their slots (jl_two_word).
+// Reads kk and cleanm (registers); uses table sets 0 .. N-1 of L with their dominant-key words and lists; writes the global
+// tables (atomics and write-through stores) and gs for the clean reads.  Barriers: one after the clearing (not in the
+// first round), two around the dominant key, one after the LDS inserts, one after the lists, one after the global
+// inserts, and in a two-word launch one at the end.  On entry, first round: sets 0 .. N-1 are cleared behind a barrier.
+template <uint32_t N, uint32_t NS>
+__device__ __forceinline__ void group_round(const uint64_t (&kk)[N][8], const table_t (&T)[N], uint32_t cleanm, uint64_t t,
+                                            bool first_round, fused_lds<NS> &L, uint32_t (&gs)[N][8])
+{
+    const uint32_t tid = threadIdx.x;
+    if (!first_round) {   // (the first round's tables were cleared while the columns were on their way)
+        L.clear_sets(N);
         __syncthreads();
-        const uint32_t domfirst = s_domfirst;
-        if (domfirst != 0xFFFFFFFFu && (uint64_t)(domfirst >> 3) == t) {
-#pragma unroll
-            for (int r = 0; r < 8; ++r)  // static indices keep the keys in registers
-                if ((domfirst & 7u) == (uint32_t)r) {
-#pragma unroll
-                    for (uint32_t z = 0; z < N; ++z) s_dom[z] = kk[z][r];
-                }
-        }
-        __syncthreads();
-        unsigned long long dom[N];
-        uint32_t isdom[N];  // bit 4r
-#pragma unroll
-        for (uint32_t z = 0; z < N; ++z) {
-            dom[z] = s_dom[z];
-            isdom[z] = 0;
-#pragma unroll
-            for (int r = 0; r < 8; ++r)
-                if (((cleanm >> (4 * r)) & 1u) && kk[z][r] == dom[z]) isdom[z] |= 1u << (4 * r);
-            const uint32_t c = wave_sum_all(__popc(isdom[z]));
-            if ((tid & 63u) == 0 && c) atomicAdd(&s_domcnt[z], c);
-        }
-        // ---- 3. everything else through the LDS table
-        uint32_t myslot[N][8];
-#pragma unroll
-        for (uint32_t z = 0; z < N; ++z) {
-            const uint32_t rest = cleanm & ~isdom[z];
-            unsigned long long *tk = s_key(z);
-            uint32_t *tc = s_cnt(z), *tf = s_first(z);
-#pragma unroll
-            for (int r = 0; r < 8; ++r) myslot[z][r] = 0xFFFFFFFFu;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                if ((rest >> (4 * r)) & 1u) {
-                    const unsigned long long k = kk[z][r];
-                    uint32_t sl = (uint32_t)mix64(k) & (kLdsSlots - 1u);
-                    for (uint32_t probe = 0; probe < kLdsSlots; ++probe) {
-                        const unsigned long long old = atomicCAS(&tk[sl], (unsigned long long)kNoKey, k);
-                        if (old == kNoKey || old == k) {
-                            atomicAdd(&tc[sl], 1u);
-                            atomicMin(&tf[sl], (uint32_t)(t * 8u + r));
-                            myslot[z][r] = sl;
-                            break;
-                        }
-                        sl = (sl + 1u) & (kLdsSlots - 1u);
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        // One global insert per distinct key of the block, ALL AT ONCE: the keys are listed densely first, so thread i takes
-        // the i-th (a sweep over the 1024 table slots, four per thread, made the thread that owned two occupied slots — and
-        // thread 0, which also had the dominant key — do its inserts one after the other: 8.7 us of a 25 us launch at a
-        // million reads, two to three dependent round trips each).  The lists of a round of two lie one behind the other.
-        // The dominant keys go with the last threads, which have list entries of their own only in blocks with some 250
-        // distinct keys or more.
-        {
-            // (the lists are made by a sweep over the tables: four LDS reads per thread and set, and a barrier)
-#pragma unroll
-            for (uint32_t z = 0; z < N; ++z)
-                for (uint32_t sl = tid; sl < kLdsSlots; sl += 256u)
-                    if (s_cnt(z)[sl]) s_list[z][atomicAdd(&s_nlist[z], 1u)] = (uint16_t)sl;
-            __syncthreads();
-            const uint32_t n0 = s_nlist[0], n_all = n0 + (N == 2u ? s_nlist[N - 1u] : 0u);
-            for (uint32_t i = tid; i < n_all; i += 256u) {
-                const uint32_t z = (N == 2u && i >= n0) ? 1u : 0u;
-                const uint32_t sl = s_list[z][i - (z ? n0 : 0u)];
-                s_gslot(z)[sl] = global_insert64(s_key(z)[sl], s_cnt(z)[sl], s_first(z)[sl], slots_mask, T[z].key, T[z].rep, T[z].cnt, T[z].occ, T[z].nocc);
-            }
-#pragma unroll
-            for (uint32_t z = 0; z < N; ++z)
-                if (tid == 255u - z && s_domcnt[z])
-                    s_domslot[z] = global_insert64(dom[z], s_domcnt[z], s_domfirst, slots_mask, T[z].key, T[z].rep, T[z].cnt, T[z].occ, T[z].nocc);
-        }
-        __syncthreads();
-#pragma unroll
-        for (uint32_t z = 0; z < N; ++z)
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                if ((cleanm >> (4 * r)) & 1u) {
-                    uint32_t g;
-                    if ((isdom[z] >> (4 * r)) & 1u) g = s_domslot[z];
-                    else if (myslot[z][r] != 0xFFFFFFFFu) g = s_gslot(z)[myslot[z][r]];
-                    else  // LDS table full (> 1024 distinct keys in 2048 reads): straight to the global table
-                        g = global_insert64(kk[z][r], 1u, (uint32_t)(t * 8u + r), slots_mask, T[z].key, T[z].rep, T[z].cnt, T[z].occ, T[z].nocc);
-                    gs[z][r] = g;
-                }
-            }
-        if (KW == 2) __syncthreads();   // the next round clears the LDS tables this one still reads
-    };
-    const table_t T_main = {slot_key, slot_rep, slot_count, occupied, &meta->n_occupied};
-    if constexpr (KW == 1) {
-        const uint64_t (&k1)[1][8] = reinterpret_cast<const uint64_t (&)[1][8]>(key);
-        uint32_t (&g1)[1][8] = reinterpret_cast<uint32_t (&)[1][8]>(gslot);
-        const table_t T1[1] = {T_main};
-        group_round(std::integral_constant<uint32_t, 1u>{}, k1, T1, g1, true);
-    } else {
-        uint64_t kk2[2][8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) { kk2[0][r] = key[r]; kk2[1][r] = key1[r]; }
-        uint32_t g01[2][8] = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}};
-        const table_t T2[2] = {{tw->key_a, nullptr, nullptr, tw->occ_a, tw->n_occ}, {tw->key_b, nullptr, nullptr, tw->occ_b, tw->n_occ + 1}};
-        group_round(std::integral_constant<uint32_t, 2u>{}, kk2, T2, g01, true);
-        uint64_t kk3[1][8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) kk3[0][r] = ((uint64_t)g01[0][r] << 32) | g01[1][r];   // never all ones: slots are 31-bit numbers
-        uint32_t (&g1)[1][8] = reinterpret_cast<uint32_t (&)[1][8]>(gslot);
-        const table_t T1[1] = {T_main};
-        group_round(std::integral_constant<uint32_t, 1u>{}, kk3, T1, g1, false);
     }
-    // read categories of this workgroup's reads: written through to its own four words; the selection adds the workgroups
-    // up (four atomics per workgroup on ONE cache line were the longest queue of the launch at a million reads)
-    if (tid >= 64u && tid < 68u)
-        __hip_atomic_store(&w.blockcat[blockIdx.x * 4u + (tid - 64u)], s_cat[tid - 64u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (S.ids_mode == JL_IDS_SEPARATE) {
+    // ---- 2. dominant key of the block = key of its first clean read
+    uint32_t myfirst = 0xFFFFFFFFu;
+    if (cleanm) myfirst = (uint32_t)(t * 8u) + ((uint32_t)__ffs((int)cleanm) - 1u) / 4u;
+    {
+        uint32_t m = myfirst;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = min(m, (uint32_t)__shfl_xor((int)m, o, 64));
+        if ((tid & 63u) == 0 && m != 0xFFFFFFFFu) atomicMin(&L.domfirst, m);
+    }
+    __syncthreads();
+    const uint32_t domfirst = L.domfirst;
+    if (domfirst != 0xFFFFFFFFu && (uint64_t)(domfirst >> 3) == t) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r)  // static indices keep the keys in registers
+            if ((domfirst & 7u) == (uint32_t)r) {
+#pragma unroll
+                for (uint32_t z = 0; z < N; ++z) L.dom[z] = kk[z][r];
+            }
+    }
+    __syncthreads();
+    unsigned long long dom[N];
+    uint32_t isdom[N];  // bit 4r
+#pragma unroll
+    for (uint32_t z = 0; z < N; ++z) {
+        dom[z] = L.dom[z];
+        isdom[z] = 0;
 #pragma unroll
         for (int r = 0; r < 8; ++r)
-            if ((cleanm >> (4 * r)) & 1u) read_slot[t * 8u + r] = gslot[r];
+            if (((cleanm >> (4 * r)) & 1u) && kk[z][r] == dom[z]) isdom[z] |= 1u << (4 * r);
+        const uint32_t c = wave_sum_all(__popc(isdom[z]));
+        if ((tid & 63u) == 0 && c) atomicAdd(&L.domcnt[z], c);
     }
-    clean_keep = cleanm;
-    }  // work
-    if (!S.run) return;  // the generic pipeline has its own select launch
-    bool ids_written = false;
-    auto write_ids = [&](uint32_t bits) {
-        if (live && bits) {
-            uint16_t h[8];
+    // ---- 3. everything else through the LDS table
+    uint32_t myslot[N][8];
 #pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                h[r] = JL_HAP_DAMAGED;
-                if ((clean_keep >> (4 * r)) & 1u)
-                    h[r] = (uint16_t)__hip_atomic_load(&S.slot_hap[gslot[r]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (uint32_t z = 0; z < N; ++z) {
+        const uint32_t rest = cleanm & ~isdom[z];
+        unsigned long long *tk = L.key(z);
+        uint32_t *tc = L.cnt(z), *tf = L.first(z);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) myslot[z][r] = 0xFFFFFFFFu;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            if ((rest >> (4 * r)) & 1u) {
+                const unsigned long long k = kk[z][r];
+                uint32_t sl = (uint32_t)mix64(k) & (kLdsSlots - 1u);
+                for (uint32_t probe = 0; probe < kLdsSlots; ++probe) {
+                    const unsigned long long old = atomicCAS(&tk[sl], (unsigned long long)kNoKey, k);
+                    if (old == kNoKey || old == k) {
+                        atomicAdd(&tc[sl], 1u);
+                        atomicMin(&tf[sl], (uint32_t)(t * 8u + r));
+                        myslot[z][r] = sl;
+                        break;
+                    }
+                    sl = (sl + 1u) & (kLdsSlots - 1u);
+                }
             }
-            store_ids(S.read_hap, t, h, bits);
         }
-    };
-    // ---- hand-off: the block that arrives last ranks the groups and writes the result block.  Everything the
-    // selection reads was written by agent-scope atomics or write-through stores (slot keys and counts, the occupied
-    // list, the read-category counters, the compacted rows): no release fence — an L2 write-back per block serialises
-    // in the L2.  Every wave drains its stores -> block barrier -> one lane: the arrival add; the last arriver reads
-    // with agent-scope loads (past its L1).  The counter is zero before the first launch and the last arriver leaves it zero.
+    }
+    __syncthreads();
+    // One global insert per distinct key of the block, ALL AT ONCE: the keys are listed densely first, so thread i takes
+    // the i-th (a sweep over the 1024 table slots, four per thread, made the thread that owned two occupied slots — and
+    // thread 0, which also had the dominant key — do its inserts one after the other: 8.7 us of a 25 us launch at a
+    // million reads, two to three dependent round trips each).  The lists of a round of two lie one behind the other.
+    // The dominant keys go with the last threads, which have list entries of their own only in blocks with some 250
+    // distinct keys or more.
+    {
+        // (the lists are made by a sweep over the tables: four LDS reads per thread and set, and a barrier)
+#pragma unroll
+        for (uint32_t z = 0; z < N; ++z)
+            for (uint32_t sl = tid; sl < kLdsSlots; sl += 256u)
+                if (L.cnt(z)[sl]) L.list[z][atomicAdd(&L.nlist[z], 1u)] = (uint16_t)sl;
+        __syncthreads();
+        const uint32_t n0 = L.nlist[0], n_all = n0 + (N == 2u ? L.nlist[N - 1u] : 0u);
+        for (uint32_t i = tid; i < n_all; i += 256u) {
+            const uint32_t z = (N == 2u && i >= n0) ? 1u : 0u;
+            const uint32_t sl = L.list[z][i - (z ? n0 : 0u)];
+            L.gslot(z)[sl] = global_insert64(L.key(z)[sl], L.cnt(z)[sl], L.first(z)[sl], T[z]);
+        }
+#pragma unroll
+        for (uint32_t z = 0; z < N; ++z)
+            if (tid == 255u - z && L.domcnt[z]) L.domslot[z] = global_insert64(dom[z], L.domcnt[z], L.domfirst, T[z]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t z = 0; z < N; ++z)
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            if ((cleanm >> (4 * r)) & 1u) {
+                uint32_t g;
+                if ((isdom[z] >> (4 * r)) & 1u) g = L.domslot[z];
+                else if (myslot[z][r] != 0xFFFFFFFFu) g = L.gslot(z)[myslot[z][r]];
+                else  // LDS table full (> 1024 distinct keys in 2048 reads): straight to the global table
+                    g = global_insert64(kk[z][r], 1u, (uint32_t)(t * 8u + r), T[z]);
+                gs[z][r] = g;
+            }
+        }
+    if (NS == 2u) __syncthreads();   // the next round clears the LDS tables this one still reads
+}
+
+// The per-read ids of this lane's reads, from the slots still in its registers and the slot -> haplotype table (agent-scope
+// loads); bits = 0: none (the wait timed out).  No barrier.  On entry the table is complete and visible (see the callers).
+__device__ __forceinline__ void write_own_ids(const jl_select_args &S, const own_reads &R, uint32_t bits)
+{
+    if (R.live && bits) {
+        uint16_t h[8];
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            h[r] = JL_HAP_DAMAGED;
+            if ((R.clean >> (4 * r)) & 1u)
+                h[r] = (uint16_t)__hip_atomic_load(&S.slot_hap[R.gslot[0][r]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        jl_store_ids(S.read_hap, R.t, h, bits);
+    }
+}
+
+// ---- hand-off: the block that arrives last ranks the groups and writes the result block.  Everything the
+// selection reads was written by agent-scope atomics or write-through stores (slot keys and counts, the occupied
+// list, the read-category counters, the compacted rows): no release fence — an L2 write-back per block serialises
+// in the L2.  Every wave drains its stores -> block barrier -> one lane: the arrival add; the last arriver reads
+// with agent-scope loads (past its L1).  The counter is zero before the first launch and the last arriver leaves it zero.
+// Reads and writes S.arrive; writes L.last.  Barriers: one before the add, one after.  On entry every store of this
+// workgroup that the selection reads has been issued.  Returns whether this workgroup arrived last.
+template <uint32_t NS>
+__device__ __forceinline__ bool fused_arrive(const jl_select_args &S, uint32_t n_arrive, fused_lds<NS> &L)
+{
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (tid == 0) {
+    if (threadIdx.x == 0) {
         const uint32_t prev = __hip_atomic_fetch_add(S.arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const uint32_t last = prev == n_arrive - 1u;
         if (last) {
@@ -1423,160 +1397,199 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __hip_atomic_store(S.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        s_last = last;
+        L.last = last;
     }
     __syncthreads();
-    const bool last = s_last != 0;
-    if (!last && S.ids_mode == JL_IDS_SEPARATE) return;
-    if (last) {
-        uint32_t nv = 0, seq_before = 0;
-        const bool fast_export = work && S.exp_count != nullptr;
-        // the selection's first loads go out beside those of the read categories (the list entry is used below the count only)
-        uint32_t n_occ_pre = 0, occ_pre = 0;
-        if (work && !S.exp_count) {
-            n_occ_pre = ld_coherent(&meta->n_occupied);
-            occ_pre = ld_coherent(&occupied[tid]);   // (the list holds at least 256 entries: reserve_phase)
-        }
-        if (!S.exp_count) {   // (an exporting selection needs neither: it ranks nothing)
-            nv = from_called ? (n_rows < S.cap ? n_rows : S.cap) : ld_coherent(&meta->n_var);
-            if (!from_called) n_rows = ld_coherent(&S.n_rows[0]);
-        } else if (tid == 0 && S.seq_host) {
-            seq_before = ld_coherent(S.seq_dev);   // beside the loads below: not a round trip of its own at the end
-        }
-        if (work) {   // the read categories: every workgroup's four words, summed here
-            uint32_t c4[4] = {0, 0, 0, 0};
-            for (uint32_t b = tid; b < w.n_blocks; b += 256u) {
+    return L.last != 0;
+}
+
+// The last workgroup: the read categories of the window, every workgroup's four words (written through by their
+// workgroups) summed into L.cat and, unless the fast export follows, stored to the run's scalars in meta.  Two barriers.
+// On entry this workgroup has arrived last.
+template <uint32_t NS>
+__device__ __forceinline__ void sum_categories(const jl_win_phase &w, bool fast_export, fused_lds<NS> &L)
+{
+    jl_phase_meta *meta = w.meta;
+    const uint32_t tid = threadIdx.x;
+    uint32_t c4[4] = {0, 0, 0, 0};
+    for (uint32_t b = tid; b < w.n_blocks; b += 256u) {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) c4[k] += ld_coherent(&w.blockcat[b * 4u + k]);   // written through by their workgroups
-            }
+        for (int k = 0; k < 4; ++k) c4[k] += jl_ld_coherent(&w.blockcat[b * 4u + k]);   // written through by their workgroups
+    }
 #pragma unroll
-            for (int k = 0; k < 4; ++k) c4[k] = wave_sum_all(c4[k]);
-            if (tid < 4u) s_cat[tid] = 0;
-            __syncthreads();
-            if ((tid & 63u) == 0) {
+    for (int k = 0; k < 4; ++k) c4[k] = wave_sum_all(c4[k]);
+    if (tid < 4u) L.cat[tid] = 0;
+    __syncthreads();
+    if ((tid & 63u) == 0) {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) atomicAdd(&s_cat[k], c4[k]);
-            }
-            __syncthreads();
-            if (!fast_export && tid == 0) {   // the run's scalars (the general selection and the stage-API fetches read them there)
-                __hip_atomic_store(&meta->summary.damaged_reads, s_cat[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&meta->summary.marginal_gap, s_cat[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&meta->summary.marginal_heteroduplex, s_cat[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&meta->summary.marginal_partial, s_cat[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+        for (int k = 0; k < 4; ++k) atomicAdd(&L.cat[k], c4[k]);
+    }
+    __syncthreads();
+    if (!fast_export && tid == 0) {   // the run's scalars (the general selection and the stage-API fetches read them there)
+        __hip_atomic_store(&meta->summary.damaged_reads, L.cat[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&meta->summary.marginal_gap, L.cat[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&meta->summary.marginal_heteroduplex, L.cat[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&meta->summary.marginal_partial, L.cat[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// The last workgroup of a two-word launch whose selection out of LDS did not run.  More candidates / rows than it holds
+// (or nothing to phase): the general routine reads one-word keys, so the run is handed to the multi-word pipeline —
+// tables emptied, the run flagged as one that needs it (the fetch calls re-run it, as they do for more than 20
+// positions).  One barrier at the start, that of two_word_cleanup, and a drain of the stores at the end.
+__device__ __forceinline__ void hand_down_two_word(const jl_win_phase &w, const jl_two_word &tw, bool work)
+{
+    jl_phase_meta *meta = w.meta;
+    __syncthreads();
+    if (work) {
+        empty_used_slots(w, jl_ld_coherent(&meta->n_occupied));
+        two_word_cleanup(tw);
+        if (threadIdx.x == 0) {
+            __hip_atomic_store(&meta->overflow, JL_PHASE_OVF_FORM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&meta->vp_true, 2u * JL_POS_PER_WORD + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&meta->vp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&meta->kwords, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&meta->n_occupied, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        if (fast_export) {
-            phase_export_fast<KW>(w, vp, s_cat, &s_running, tw);
-            // every wave's stores (the groups may lie in host memory) are performed; ONE system-scope release, carried by
-            // the completion word's store, pushes them out in front of it: data and word leave the same workgroup
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (S.seq_host && tid == 0) jl_signal_done_from(seq_before, S.seq_dev, S.seq_host);
-            return;
-        }
-        bool done = false;
-        uint32_t sel_bits = 0;   // width of the ids, when the selection out of LDS ran
-        if (work && !S.exp_count)
-            done = phase_select_lds<KW>(w, s_plan, vp, nv, n_rows, *reinterpret_cast<sel_lds *>(s_tables[0]), tw, n_occ_pre, occ_pre, s_cat,
-                                        &sel_bits, [&](uint32_t bits) {
-                                            if (S.ids_mode == JL_IDS_SEPARATE) return;
-                                            if (tid == 0) __hip_atomic_store(S.flag, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                                            write_ids(bits);
-                                            ids_written = true;
-                                        });
-        if (KW == 2 && !done) {
-            // More candidates / rows than the selection out of LDS holds (or nothing to phase): the general routine reads
-            // one-word keys, so the run is handed to the multi-word pipeline — tables emptied, the run flagged as one that
-            // needs it (the fetch calls re-run it, as they do for more than 20 positions).
-            __syncthreads();
-            if (work) {
-                const uint32_t n_occ = ld_coherent(&meta->n_occupied);
-                for (uint32_t q = tid; q < n_occ; q += 256u) {
-                    const uint32_t sl = ld_coherent(&occupied[q]);
-                    slot_key[sl] = ~0ull;
-                    slot_rep[sl] = 0xFFFFFFFFu;
-                    slot_count[sl] = 0;
-                }
-                two_word_cleanup(*tw);
-                if (tid == 0) {
-                    __hip_atomic_store(&meta->overflow, JL_PHASE_OVF_FORM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&meta->vp_true, 2u * JL_POS_PER_WORD + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&meta->vp, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&meta->kwords, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&meta->n_occupied, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the general routine below reads these scalars back
-        }
-        if (!done) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the read categories: it reads them from the run's scalars)
-            __syncthreads();
-            phase_select_block<true>(S.min_reads, reads_pad, keys, meta, slot_rep, slot_count, occupied, S.slot_hap, S.variants,
-                                     S.col2pos, S.n_cols, S.hap_count, S.hap_pattern, S.hit, S.n_rows, w.vpcols, S.cooc, S.cooc_cap,
-                                     S.pk, S.mirror, slot_key, S.seq_dev, reinterpret_cast<uint32_t *>(s_tables[0]), S.exp_count,
-                                     S.exp_pattern, S.exp_cap, S.exp_stride, nullptr, nullptr, 0u, S.exp_head);
-        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the general routine below reads these scalars back
+}
+
+// ---- the last workgroup: the selection — the fast export, or out of LDS, or (two-word launch) the hand-down, or the
+// general routine — then the exchange head, the release of the result block, and the flag that releases the waiting
+// workgroups.  Reads the tables, lists and scalars the other workgroups wrote; L.plan and L.cat; writes every result of the
+// run, L.idbits and S.flag; sets ids_written when this lane's ids went out from within the selection.  Barriers: those of
+// sum_categories and of the selection taken, one behind a drain after each of export / selection / head copy, one at the
+// end.  On entry fused_arrive has returned true.  Returns false when the launch ends here for this workgroup (an export, or
+// ids by a separate launch).
+template <int KW, uint32_t NS>
+__device__ __forceinline__ bool fused_last(const jl_win_phase &w, const jl_two_word *tw, const fused_plan &P, const own_reads &R,
+                                           fused_lds<NS> &L, bool &ids_written)
+{
+    const jl_select_args &S = w.S;
+    jl_phase_meta *meta = w.meta;
+    const uint32_t tid = threadIdx.x;
+    const bool from_called = S.called != nullptr, work = P.work;
+    uint32_t seq_before = 0;
+    const bool fast_export = work && S.exp_count != nullptr;
+    // the selection's first loads go out beside those of the read categories (the list entry is used below the count only)
+    select_pre pre = {0, P.n_rows, 0, 0};
+    if (work && !S.exp_count) {
+        pre.n_occ = jl_ld_coherent(&meta->n_occupied);
+        pre.occ0 = jl_ld_coherent(&w.occupied[tid]);   // (the list holds at least 256 entries: reserve_phase)
+    }
+    if (!S.exp_count) {   // (an exporting selection needs neither: it ranks nothing)
+        pre.nv = from_called ? (P.n_rows < S.cap ? P.n_rows : S.cap) : jl_ld_coherent(&meta->n_var);
+        if (!from_called) pre.n_rows = jl_ld_coherent(&S.n_rows[0]);
+    } else if (tid == 0 && S.seq_host) {
+        seq_before = jl_ld_coherent(S.seq_dev);   // beside the loads below: not a round trip of its own at the end
+    }
+    if (work) sum_categories(w, fast_export, L);
+    if (fast_export) {
+        phase_export_fast<KW>(w, P.vp, L.cat, &L.running, tw);
+        // every wave's stores (the groups may lie in host memory) are performed; ONE system-scope release, carried by
+        // the completion word's store, pushes them out in front of it: data and word leave the same workgroup
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (S.xhead) {   // bound exchange: the head into the region the launch's all-gather works in
-            jl_result_head_copy(S.pk + (__hip_atomic_load(S.seq_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1u), S.xhead);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-        }
-        // The result block went to pinned host memory from THIS compute die; the completion word will be stored by
-        // whichever workgroup arrives last, possibly on another die.  A system-scope release here pushes the block
-        // out of this die's L2 first — without it the host now and then saw the word before the block's header
-        // (new per-read ids and variant rows beside the previous run's read categories: one group run in ten).
-        if (tid == 0) __threadfence_system();
-        if (S.ids_mode == JL_IDS_SEPARATE) {
-            if (S.seq_host && tid == 0) signal_done(S.seq_dev, S.seq_host);  // no per-read ids wanted: the run ends here
-            return;
-        }
-        // the slot -> haplotype table is complete (write-through stores, drained above): release the waiting
-        // workgroups; the flag carries the width of the ids
-        if (tid == 0) {
-            const uint32_t bits = done ? sel_bits : ld_coherent(&meta->id_bits);
-            s_idbits = bits;
-            if (!ids_written) {     // (the selection out of LDS released them as soon as it had ranked)
-                __hip_atomic_store(S.flag, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        __syncthreads();
-    } else {
-        // wait for the selection.  Every workgroup of this launch is resident (the host asks only small grids for inline ids), so
-        // the flag does arrive; the bound turns a broken invariant into a loud failure, not a hang — and not a fault
-        // either (a trap can take the device down for every tenant): the run is marked failed where both ways of reading
-        // it look (the phase scalars for jl_phase_fetch, the pinned block's magic for jl_run_view_get), this workgroup
-        // writes no ids and goes on to the second arrival so that the launch still ends.
-        if (tid == 0) {
-            uint32_t spins = 0, bits;
-            while ((bits = __hip_atomic_load(S.flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0u) {
-                __builtin_amdgcn_s_sleep(8);
-                if (++spins > (1u << 23)) {
-                    atomicOr(&meta->overflow, JL_PHASE_OVF_IDS_WAIT_TIMEOUT);
-                    if (S.mirror) __hip_atomic_store(&S.mirror->magic, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    break;
-                }
-            }
-#ifdef JL_TUNING
-            if (S.ids_mode == JL_IDS_INLINE_GIVE_UP && bits != 0u) {   // forced: behave as if the wait had run out just before the selection arrived
-                atomicOr(&meta->overflow, JL_PHASE_OVF_IDS_WAIT_TIMEOUT);
-                if (S.mirror) __hip_atomic_store(&S.mirror->magic, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                bits = 0u;
-            }
-#endif
-            s_idbits = bits;   // 0: timed out
-        }
-        __syncthreads();
+        if (S.seq_host && tid == 0) jl_signal_done_from(seq_before, S.seq_dev, S.seq_host);
+        return false;
     }
-    // ---- per-read haplotype ids of this workgroup's own reads, straight from the slots still in registers
-    if (!ids_written) write_ids(s_idbits);
-    // Second arrival: every workgroup is past the flag by now, so the one that arrives last resets it (and the
-    // counter) for the next launch and, when this launch ends a run, stores the completion word behind all the ids.
+    bool done = false;
+    uint32_t sel_bits = 0;   // width of the ids, when the selection out of LDS ran
+    if (work && !S.exp_count)
+        done = phase_select_lds<KW>(w, tw, L, P.vp, pre, &sel_bits, [&](uint32_t bits) {
+            if (S.ids_mode == JL_IDS_SEPARATE) return;
+            if (tid == 0) __hip_atomic_store(S.flag, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            write_own_ids(S, R, bits);
+            ids_written = true;
+        });
+    if constexpr (KW == 2) {
+        if (!done) hand_down_two_word(w, *tw, work);
+    }
+    if (!done) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the read categories: it reads them from the run's scalars)
+        __syncthreads();
+        phase_select_block<true>(w, select_lds{reinterpret_cast<uint32_t *>(L.tables[0]), nullptr, nullptr, 0u});
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    if (S.xhead) {   // bound exchange: the head into the region the launch's all-gather works in
+        jl_result_head_copy(S.pk + (__hip_atomic_load(S.seq_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1u), S.xhead);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+    // The result block went to pinned host memory from THIS compute die; the completion word will be stored by
+    // whichever workgroup arrives last, possibly on another die.  A system-scope release here pushes the block
+    // out of this die's L2 first — without it the host now and then saw the word before the block's header
+    // (new per-read ids and variant rows beside the previous run's read categories: one group run in ten).
+    if (tid == 0) __threadfence_system();
+    if (S.ids_mode == JL_IDS_SEPARATE) {
+        if (S.seq_host && tid == 0) jl_signal_done(S.seq_dev, S.seq_host);  // no per-read ids wanted: the run ends here
+        return false;
+    }
+    // the slot -> haplotype table is complete (write-through stores, drained above): release the waiting
+    // workgroups; the flag carries the width of the ids
     if (tid == 0) {
-        if (S.seq_host) __threadfence_system();   // this workgroup's ids leave its die's L2 before it arrives (see above)
+        const uint32_t bits = done ? sel_bits : jl_ld_coherent(&meta->id_bits);
+        L.idbits = bits;
+        if (!ids_written) {     // (the selection out of LDS released them as soon as it had ranked)
+            __hip_atomic_store(S.flag, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    __syncthreads();
+    return true;
+}
+
+// ---- the other workgroups of a launch that writes the ids: wait for the selection.  Every workgroup of this launch is
+// resident (the host asks only small grids for inline ids), so
+// the flag does arrive; the bound turns a broken invariant into a loud failure, not a hang — and not a fault
+// either (a trap can take the device down for every tenant): the run is marked failed where both ways of reading
+// it look (the phase scalars for jl_phase_fetch, the pinned block's magic for jl_run_view_get), this workgroup
+// writes no ids and goes on to the second arrival so that the launch still ends.
+// Thread 0 spins on S.flag (agent-scope loads); writes L.idbits (0: timed out).  One barrier, at the end.  On entry
+// fused_arrive has returned false.
+template <uint32_t NS>
+__device__ __forceinline__ void fused_wait(const jl_win_phase &w, fused_lds<NS> &L)
+{
+    const jl_select_args &S = w.S;
+    jl_phase_meta *meta = w.meta;
+    if (threadIdx.x == 0) {
+        uint32_t spins = 0, bits;
+        while ((bits = __hip_atomic_load(S.flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0u) {
+            __builtin_amdgcn_s_sleep(8);
+            if (++spins > (1u << 23)) {
+                atomicOr(&meta->overflow, JL_PHASE_OVF_IDS_WAIT_TIMEOUT);
+                if (S.mirror) __hip_atomic_store(&S.mirror->magic, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                break;
+            }
+        }
+#ifdef JL_TUNING
+        if (S.ids_mode == JL_IDS_INLINE_GIVE_UP && bits != 0u) {   // forced: behave as if the wait had run out just before the selection arrived
+            atomicOr(&meta->overflow, JL_PHASE_OVF_IDS_WAIT_TIMEOUT);
+            if (S.mirror) __hip_atomic_store(&S.mirror->magic, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            bits = 0u;
+        }
+#endif
+        L.idbits = bits;   // 0: timed out
+    }
+    __syncthreads();
+}
+
+// ---- per-read haplotype ids of this workgroup's own reads, straight from the slots still in registers, and the
+// second arrival: every workgroup is past the flag by now, so the one that arrives last resets it (and the
+// counter) for the next launch and, when this launch ends a run, stores the completion word behind all the ids.
+// Reads L.idbits, S.slot_hap; writes S.read_hap, S.arrive2, S.flag.  One barrier, behind a drain of the ids.  On entry
+// L.idbits is set behind a barrier (fused_last or fused_wait).
+template <uint32_t NS>
+__device__ __forceinline__ void fused_ids_and_leave(const jl_win_phase &w, uint32_t n_arrive, const own_reads &R, bool ids_written,
+                                                    const fused_lds<NS> &L)
+{
+    const jl_select_args &S = w.S;
+    if (!ids_written) write_own_ids(S, R, L.idbits);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (S.seq_host) __threadfence_system();   // this workgroup's ids leave its die's L2 before it arrives (see fused_last)
         const uint32_t prev = __hip_atomic_fetch_add(S.arrive2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (prev == n_arrive - 1u) {
             __hip_atomic_store(S.arrive2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1584,27 +1597,86 @@ __device__ __forceinline__ void phase_fused1_body(const jl_win_phase &w, const j
             // A workgroup that gave up waiting marked the run failed; a selection that was only LATE has since written a
             // valid result block over that mark.  The mark in the run's scalars is the lasting one: whoever arrives last
             // makes the blocks say so again, just before the completion word.
-            if (ld_coherent(&meta->overflow) & JL_PHASE_OVF_IDS_WAIT_TIMEOUT) {
+            if (jl_ld_coherent(&w.meta->overflow) & JL_PHASE_OVF_IDS_WAIT_TIMEOUT) {
                 if (S.mirror) __hip_atomic_store(&S.mirror->magic, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 jl_pack *pk = S.pk + (__hip_atomic_load(S.seq_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1u);
                 __hip_atomic_store(&pk->magic, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
-            if (S.seq_host) signal_done(S.seq_dev, S.seq_host);
+            if (S.seq_host) jl_signal_done(S.seq_dev, S.seq_host);
         }
     }
 }
 
-__global__ __launch_bounds__(256) void phase_fused1_kernel(jl_win_phase w) { phase_fused1_body<1>(w); }
-__global__ __launch_bounds__(256) void phase_fused1_direct_kernel(jl_win_phase w, jl_direct_cols dc) { phase_fused1_body<1>(w, &dc); }
+// A workgroup of the fused launch with KW key words: the one-word launch (a window, with or without direct columns), the
+// group launch, the two-word launch.
+template <int KW>
+__device__ __forceinline__ void phase_fused_body(const jl_win_phase &w, const jl_direct_cols *dc = nullptr, const jl_two_word *tw = nullptr)
+{
+    constexpr uint32_t NS = KW == 2 ? 2u : 1u;
+    __shared__ fused_lds<NS> L;
+    const jl_select_args &S = w.S;
+    const uint32_t tid = threadIdx.x;
+    const bool from_called = S.called != nullptr;
+    // whole-path runs launch one workgroup more than the reads need: it compacts the called rows meanwhile
+    const uint32_t n_arrive = w.n_blocks + (from_called ? 1u : 0u);
+    const bool plan_block = from_called && blockIdx.x == w.n_blocks;
+
+    const fused_plan P = fused_plan_stage<KW>(w, dc, plan_block, L);
+    const uint64_t t = (uint64_t)blockIdx.x * 256u + tid;  // dword index within a column = 8 reads
+    own_reads R = {t, t * 4u < w.col_stride, 0u, {{0, 0, 0, 0, 0, 0, 0, 0}}};
+    if (P.work && !plan_block) {
+        L.clear_sets(NS);
+        if (tid < 4) L.cat[tid] = 0;
+        __syncthreads();
+        uint64_t kk[KW][8];
+        const uint32_t cleanm = fused_keys_stage<KW>(w, dc, P.vp, t, R.live, L, kk);
+        const table_t T_main[1] = {{w.slot_key, w.slot_rep, w.slot_count, w.occupied, &w.meta->n_occupied, w.slots_mask}};
+        if constexpr (KW == 1) {
+            group_round(kk, T_main, cleanm, t, true, L, R.gslot);
+        } else {   // the two words numbered in the half-key tables, then the pairs of their numbers in the window's table
+            uint32_t g01[2][8] = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}};
+            const table_t T2[2] = {{tw->key_a, nullptr, nullptr, tw->occ_a, tw->n_occ, w.slots_mask},
+                                   {tw->key_b, nullptr, nullptr, tw->occ_b, tw->n_occ + 1, w.slots_mask}};
+            group_round(kk, T2, cleanm, t, true, L, g01);
+            uint64_t kk3[1][8];
+#pragma unroll
+            for (int r = 0; r < 8; ++r) kk3[0][r] = ((uint64_t)g01[0][r] << 32) | g01[1][r];   // never all ones: slots are 31-bit numbers
+            group_round(kk3, T_main, cleanm, t, false, L, R.gslot);
+        }
+        // read categories of this workgroup's reads: written through to its own four words; the selection adds the workgroups
+        // up (four atomics per workgroup on ONE cache line were the longest queue of the launch at a million reads)
+        if (tid >= 64u && tid < 68u)
+            __hip_atomic_store(&w.blockcat[blockIdx.x * 4u + (tid - 64u)], L.cat[tid - 64u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (S.ids_mode == JL_IDS_SEPARATE) {
+#pragma unroll
+            for (int r = 0; r < 8; ++r)
+                if ((cleanm >> (4 * r)) & 1u) w.read_slot[t * 8u + r] = R.gslot[0][r];
+        }
+        R.clean = cleanm;
+    }
+    if (!S.run) return;  // the generic pipeline has its own select launch
+    const bool last = fused_arrive(S, n_arrive, L);
+    if (!last && S.ids_mode == JL_IDS_SEPARATE) return;
+    bool ids_written = false;
+    if (last) {
+        if (!fused_last<KW>(w, tw, P, R, L, ids_written)) return;
+    } else {
+        fused_wait(w, L);
+    }
+    fused_ids_and_leave(w, n_arrive, R, ids_written, L);
+}
+
+__global__ __launch_bounds__(256) void phase_fused1_kernel(jl_win_phase w) { phase_fused_body<1>(w); }
+__global__ __launch_bounds__(256) void phase_fused1_direct_kernel(jl_win_phase w, jl_direct_cols dc) { phase_fused_body<1>(w, &dc); }
 // 11 .. 20 variant positions: the same launch with two key words (jl_two_word)
-__global__ __launch_bounds__(256) void phase_fused2_kernel(jl_win_phase w, jl_two_word tw) { phase_fused1_body<2>(w, nullptr, &tw); }
+__global__ __launch_bounds__(256) void phase_fused2_kernel(jl_win_phase w, jl_two_word tw) { phase_fused_body<2>(w, nullptr, &tw); }
 
 // one launch for several windows: blockIdx.z = window
 __global__ __launch_bounds__(256) void phase_group_run_kernel(jl_phase_group_args args)
 {
     const jl_win_phase &w = args.w[blockIdx.z];
     if (blockIdx.x >= w.n_blocks + (w.S.called ? 1u : 0u)) return;
-    phase_fused1_body<1>(w);
+    phase_fused_body<1>(w);
 }
 
 // ---------------------------------------------------------------------------------------- assign
@@ -1630,7 +1702,7 @@ __device__ __forceinline__ void assign_body(uint64_t n_dwords, const uint32_t *_
             for (int r = 0; r < 8; ++r)
                 if (((f >> (4 * r)) & 15u) == 0) h[r] = (uint16_t)slot_hap[slot[r]];   // clean reads only: their slot is valid
         }
-        store_ids(read_hap, t, h, bits);
+        jl_store_ids(read_hap, t, h, bits);
     }
 }
 
@@ -1689,7 +1761,7 @@ void jl_fill_win_phase(jl_ctx *ctx, uint32_t min_reads, bool signal, bool ids_in
     w->read_slot = ctx->d_read_slot;
     w->blockcat = ctx->d_blockcat;
     w->n_blocks = jl_phase_grid_blocks(ctx) - 1u;   // (the arrival counters do not count the compacting workgroup)
-    select_args &S = w->S;
+    jl_select_args &S = w->S;
     S.run = ctx->phase_form == jl_phase_form::multi_word ? 0u : 1u;
     S.min_reads = min_reads; S.n_cols = ctx->n_cols; S.cooc_cap = ctx->cooc_cap;
     S.slot_hap = ctx->d_slot_hap; S.variants = ctx->d_variants; S.col2pos = ctx->d_col2pos;
@@ -1728,13 +1800,13 @@ bool jl_launch_phase(jl_ctx *ctx, hipStream_t st, uint32_t min_reads, jl_phase_p
     const uint64_t reads_pad = ctx->col_stride * 2u;
     const bool generic = ctx->phase_form == jl_phase_form::multi_word;
     const bool ids_to_host = ctx->read_hap_out != nullptr;
-    const bool signal_select = signal && !ids_to_host;
     // only the fused launches read call masks: behind them the multi-word pipeline finds the plan its compact launch wrote
     if (generic && plan == jl_phase_plan::call_masks) plan = jl_phase_plan::resident;
-    if (plan == jl_phase_plan::plan_kernel)
-        hipLaunchKernelGGL(phase_plan_kernel, dim3(1), dim3(1024), 0, st, ctx->d_variants, ctx->d_nvar, JL_VARIANT_CAP,
-                           ctx->n_cols, ctx->d_varcol, ctx->d_vpcols, ctx->d_col2pos, ctx->keys_words,
-                           (uint32_t)ctx->phase_form, ctx->d_meta);
+    if (plan == jl_phase_plan::plan_kernel) {
+        jl_win_compact c;
+        jl_fill_win_compact(ctx, true, false, false, &c);
+        hipLaunchKernelGGL(phase_plan_kernel, dim3(1), dim3(1024), 0, st, c);
+    }
     const uint32_t n_dwords = (uint32_t)(ctx->col_stride / 4u);
     jl_win_phase w;
     const bool ids_inline = jl_phase_ids_inline(&ctx, 1);   // a chunk of one window
@@ -1743,15 +1815,10 @@ bool jl_launch_phase(jl_ctx *ctx, hipStream_t st, uint32_t min_reads, jl_phase_p
         hipLaunchKernelGGL(phase_keys_kernel, dim3((n_dwords + 255u) / 256u), dim3(256), 0, st, ctx->d_msa,
                            ctx->plane_stride, ctx->n_reads, reads_pad, ctx->d_vpcols, ctx->d_meta, ctx->d_keys,
                            ctx->d_flagw);
-        hipLaunchKernelGGL(phase_group_kernel, dim3((uint32_t)((ctx->n_reads + 255u) / 256u)), dim3(256), 0, st, ctx->n_reads,
-                           reads_pad, ctx->d_keys, ctx->d_flagw, ctx->d_meta, ctx->table_slots - 1u, ctx->d_slot_rep,
-                           ctx->d_slot_count, ctx->d_occupied, ctx->d_read_slot);
-        hipLaunchKernelGGL(phase_select_kernel, dim3(1), dim3(1024), 0, st, min_reads, reads_pad, ctx->d_keys,
-                           ctx->d_meta, ctx->d_slot_rep, ctx->d_slot_count, ctx->d_occupied, ctx->d_slot_hap,
-                           ctx->d_variants, ctx->d_col2pos, ctx->n_cols, ctx->d_hap_count, ctx->d_hap_pattern, ctx->d_hit,
-                           ctx->d_nvar, ctx->d_vpcols, ctx->d_cooc, ctx->cooc_cap, ctx->d_pack, ctx->pack_mirror,
-                           ctx->d_slot_key.as<unsigned long long>(), ctx->d_sync, signal_select ? ctx->h_seq : nullptr,
-                           w.S.exp_count, w.S.exp_pattern, w.S.exp_cap, w.S.exp_stride, w.S.exp_head);
+        hipLaunchKernelGGL(phase_group_kernel, dim3((uint32_t)((ctx->n_reads + 255u) / 256u)), dim3(256), 0, st, w);
+        // (the selection ends the run when no ids are wanted on the host: w.S.seq_host is `signal && !ids_to_host ? h_seq :
+        // null` here, as this form never takes inline ids — phase_ids_inline_ok)
+        hipLaunchKernelGGL(phase_select_kernel, dim3(1), dim3(1024), 0, st, w);
     } else if (ctx->direct.on && !w.S.called) {
         hipLaunchKernelGGL(phase_fused1_direct_kernel, dim3(w.n_blocks), dim3(256), 0, st, w, ctx->direct);
     } else if (ctx->phase_form == jl_phase_form::two_word) {
