@@ -441,7 +441,7 @@ int jl_deletion_test(const uint32_t cnt[4], const jl_params *prm, double n_tests
  * Whatever `pc` held is replaced, as with jl_msa_alloc.  The call waits on the host for `src`'s stream, stages the table through a
  * pinned buffer of `pc`'s own, enqueues on `pc`'s stream and returns: later calls on `pc` are stream-ordered behind it.  Nothing
  * of `src` changes: matrix, insertion counters, stage results and captured graph stay as they are.  A site of a third kind
- * (an insertion allele) has room in `kind`; the record build keeps no per-read record of the allele a read carries, so none exists.
+ * (JL_SITE_INSERTION: the called insertion alleles of a junction) is jl_sites_assemble_alleles's, below; this call refuses it.
  * JL_ERR_STATE: `src` has no resident matrix.  JL_ERR_ARG (jl_last_error(pc) says which): a NULL argument; pc == src; different
  * devices; n_sites 0 or above JL_SITES_MAX; col + 2 >= src's n_cols; kind above 1; fill neither 0xFF nor <= 63; a fill on a
  * deletion site; sites not non-decreasing by (col, kind); the same (col, kind) twice.  A refused call changes nothing of `pc`.
@@ -450,7 +450,7 @@ enum { JL_SITE_CODON = 0, JL_SITE_DELETION = 1 };
 enum { JL_SITE_NO_FILL = 0xFF, JL_SITE_PRESENT = 0 /* AAA */, JL_SITE_DELETED = 1 /* AAC */, JL_SITES_MAX = 4096 };
 typedef struct {
     uint32_t col;   /* codon start in `src` */
-    uint8_t kind;   /* JL_SITE_CODON, JL_SITE_DELETION */
+    uint8_t kind;   /* JL_SITE_CODON, JL_SITE_DELETION; JL_SITE_INSERTION (col = the junction): jl_sites_assemble_alleles only */
     uint8_t fill;   /* JL_SITE_NO_FILL, or the codon a del3 read of a codon site becomes */
     uint16_t pad_;
 } jl_site;
@@ -502,6 +502,44 @@ typedef struct {
  * RESOLVED.  JL_ERR_ARG (jl_last_error(NULL) says which): a NULL argument; n_tests <= 0; rate outside [0, 1]; frameshift + unread
  * above span; count above the coverage. */
 int jl_insertion_test(uint32_t count, const uint32_t jcnt[4], const jl_params *prm, double rate, double n_tests, jl_insertion_call *out);
+/*
+ * The per-read insertion EVENTS of a record build (docs/SPEC.md §19; this build's own rule: UNPINNED).  The switch implies
+ * jl_msa_track_insertion_alleles for the builds it is on — jcnt and the allele table are exactly that build's — and the build also
+ * leaves one event per (read, junction) that §17 counts in inframe, frameshift or unread: `kind` 1, 2 or 3, the event's column of
+ * jcnt; for kind 1 `len` and `seq` are the allele's key, exactly the table's, for kinds 2 and 3 both are 0.  A read has at most
+ * one event per junction (all 'I' ops of a junction are one insertion) and none where it does not span.  Off: nothing changes.
+ */
+typedef struct {
+    uint32_t read, col, len, kind;
+    uint64_t seq;
+} jl_insertion_event;   /* 24 bytes */
+int jl_msa_track_insertion_reads(jl_ctx *ctx, int on);
+/* Wait, and copy out the events ascending by (read, col): *n_rows (NULL: not wanted) = how many; rows == NULL returns only that
+ * count, else `cap` rows of room are needed.  JL_ERR_STATE: the last build into `ctx` did not track reads, or a later call replaced
+ * the matrix (the invalidation points of jl_insertion_alleles_fetch).  JL_ERR_ARG: cap is too small. */
+int jl_insertion_reads_fetch(jl_ctx *ctx, jl_insertion_event *rows, uint32_t cap, uint32_t *n_rows);
+/*
+ * The site matrix with INSERTION sites (docs/SPEC.md §19): jl_sites_assemble, and a third kind of site whose letters are the called
+ * insertion alleles of one junction.  Sites of kind 0 and 1 follow every rule above.  A site of kind JL_SITE_INSERTION has col =
+ * the junction c (1 <= c < src's n_cols; no col + 2 rule) and fill JL_SITE_NO_FILL; sites ascend by (col, kind), so it follows the
+ * codon and the deletion site of its column.  `alleles`: rows of jl_insertion_alleles_fetch (count is not read), strictly ascending
+ * by (col, len, seq), len in 3, 6 .. 30, seq zero above bit 2 len, every col the column of an insertion site, every insertion site
+ * with 1 to JL_SITE_INS_MAX_ALLELES of them, n_alleles <= JL_SITES_MAX.  The CODE of an allele is 1 + its rank among the alleles of
+ * its site.  Per read at an insertion site k (columns 3k..3k+2, the three cells one codon), by the events `src`'s record build left:
+ *   does not span c (cell c - 1 or c of `src` is 6), and every bit at or beyond n_reads     6 6 6
+ *   spans, no event                                                                          A A A  (codon JL_SITE_INS_NONE)
+ *   in-frame event, allele listed with code r                                                the three bases of codon r (1 .. 62)
+ *   in-frame event, allele not listed                                                        T T T  (codon JL_SITE_INS_OTHER)
+ *   frameshift event                                                                         4 4 4
+ *   unread event                                                                             5 5 5
+ * With no insertion site and n_alleles == 0 the result is jl_sites_assemble's, byte for byte.  JL_ERR_STATE: `src` has no resident
+ * matrix, or an insertion site is asked for and `src` holds no valid events (jl_msa_track_insertion_reads before its record build).
+ * JL_ERR_ARG (jl_last_error(pc) says which): every rule above.  A refused call changes nothing of `pc`.
+ */
+enum { JL_SITE_INSERTION = 2 };
+enum { JL_SITE_INS_NONE = 0 /* AAA */, JL_SITE_INS_OTHER = 63 /* TTT */, JL_SITE_INS_MAX_ALLELES = 62 };
+int jl_sites_assemble_alleles(jl_ctx *pc, jl_ctx *src, const jl_site *sites, uint32_t n_sites, const jl_insertion_allele *alleles,
+                              uint32_t n_alleles);
 /*
  * Reference/majority codon, error model, Fisher's exact x Bonferroni, filters, variant table
  * (SPEC §4-7; J:38-42).  `drm_masks`: optional [P] 64-bit codon masks; with --drm-only a codon is kept

@@ -32,12 +32,15 @@ SITE = np.dtype([("col", "<u4"), ("kind", "u1"), ("fill", "u1"), ("pad_", "<u2")
 SITE_CODON, SITE_DELETION = 0, 1
 SITE_NO_FILL, SITE_PRESENT, SITE_DELETED, SITES_MAX = 0xFF, 0, 1, 4096
 INSERTION_ALLELE = np.dtype([("col", "<u4"), ("len", "<u4"), ("seq", "<u8"), ("count", "<u4"), ("pad_", "<u4")])   # jl_insertion_allele
+INSERTION_EVENT = np.dtype([("read", "<u4"), ("col", "<u4"), ("len", "<u4"), ("kind", "<u4"), ("seq", "<u8")])       # jl_insertion_event
+SITE_INSERTION = 2
+SITE_INS_NONE, SITE_INS_OTHER, SITE_INS_MAX_ALLELES = 0, 63, 62
 
 # every symbol include/juliet_hip.h declares (checked by tests/test_capi_exports.py)
 EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", "jl_ctx_destroy", "jl_last_error",
            "jl_sync", "jl_col_stride", "jl_plane_stride", "jl_msa_upload", "jl_msa_alloc", "jl_msa_adopt", "jl_msa_pack_rows",
            "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_take", "jl_msa_take_async", "jl_sample_reads", "jl_mix_counts", "jl_msa_download", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
-           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_phase_async", "jl_phase_fetch",
+           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_msa_track_insertion_reads", "jl_insertion_reads_fetch", "jl_sites_assemble_alleles", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_phase_async", "jl_phase_fetch",
            "jl_ctx_stream", "jl_run_async", "jl_run_wait", "jl_run_done", "jl_run_view_get", "jl_group_create", "jl_group_destroy",
            "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
            "jl_allgather_variants", "jl_allgather_variants_async", "jl_allgather_variants_async_many", "jl_allgather_variants_many", "jl_group_exchange_bind", "jl_group_exchange_collect", "jl_xwin_plan", "jl_xwin_assemble_local",
@@ -220,6 +223,9 @@ def load_library(path=LIB_PATH):
     lib.jl_sites_assemble.argtypes = [vp, vp, vp, u32]
     lib.jl_msa_track_insertion_alleles.argtypes = [vp, C.c_int]
     lib.jl_insertion_alleles_fetch.argtypes = [vp, vp, vp, u32, vp]
+    lib.jl_msa_track_insertion_reads.argtypes = [vp, C.c_int]
+    lib.jl_insertion_reads_fetch.argtypes = [vp, vp, u32, vp]
+    lib.jl_sites_assemble_alleles.argtypes = [vp, vp, vp, u32, vp, u32]
     lib.jl_insertion_test.argtypes = [u32, vp, vp, C.c_double, C.c_double, vp]
     lib.jl_call_async.argtypes = [vp, C.POINTER(Params), vp]
     lib.jl_call_fetch.argtypes = [vp, vp, u32, C.POINTER(u32)]
@@ -469,6 +475,21 @@ class Juliet:
             self._chk(self.lib.jl_insertion_alleles_fetch(self.h, None, _p(rows), n.value, C.byref(n)))
         return jcnt, rows
 
+    def track_insertion_reads(self, on=True):
+        """jl_msa_track_insertion_reads (docs/SPEC.md §19): the next record build into this context forms what
+        track_insertion_alleles gives and one event per (read, junction) with an insertion."""
+        self._chk(self.lib.jl_msa_track_insertion_reads(self.h, 1 if on else 0))
+
+    def insertion_reads(self):
+        """INSERTION_EVENT[n], ascending by (read, col), of the last record build with track_insertion_reads on: kind 1 in frame
+        (len, seq the allele's key), 2 frameshift, 3 unread (len, seq zero)."""
+        n = C.c_uint32(0)
+        self._chk(self.lib.jl_insertion_reads_fetch(self.h, None, 0, C.byref(n)))
+        rows = np.zeros(n.value, dtype=INSERTION_EVENT)
+        if n.value:
+            self._chk(self.lib.jl_insertion_reads_fetch(self.h, _p(rows), n.value, C.byref(n)))
+        return rows
+
     def alloc(self, n_reads, n_cols, win_begin=0):
         self._chk(self.lib.jl_msa_alloc(self.h, n_reads, n_cols, win_begin))
         self._shape(n_reads, n_cols)
@@ -622,6 +643,23 @@ class Juliet:
         for k, (col, kind, fill) in enumerate(sites):
             arr[k] = (col, kind, fill, 0)
         self._chk(self.lib.jl_sites_assemble(self.h, src.h, _p(arr) if len(arr) else _p(np.zeros(1, dtype=SITE)), len(arr)))
+        self._shape(src.n_reads, 3 * len(arr))
+        self._keep = None
+
+    def sites_assemble_alleles(self, src, sites, alleles):
+        """jl_sites_assemble_alleles (docs/SPEC.md §19): sites_assemble, with sites of kind SITE_INSERTION (col = the junction,
+        fill SITE_NO_FILL) whose letters are the listed alleles [(col, len, seq)] of that junction, ascending: a read of `src` with
+        the allele of rank r at the junction becomes codon 1 + r there, a read without an insertion SITE_INS_NONE, one with an
+        in-frame allele that is not listed SITE_INS_OTHER, a frame-shifting or unreadable insertion 4 4 4 or 5 5 5.  `src`: a record
+        build with track_insertion_reads on."""
+        arr = np.zeros(len(sites), dtype=SITE)
+        for k, (col, kind, fill) in enumerate(sites):
+            arr[k] = (col, kind, fill, 0)
+        al = np.zeros(len(alleles), dtype=INSERTION_ALLELE)
+        for k, a in enumerate(alleles):
+            al[k] = (a[0], a[1], a[2], 0, 0)
+        self._chk(self.lib.jl_sites_assemble_alleles(self.h, src.h, _p(arr) if len(arr) else _p(np.zeros(1, dtype=SITE)), len(arr),
+                                                     _p(al) if len(al) else None, len(al)))
         self._shape(src.n_reads, 3 * len(arr))
         self._keep = None
 

@@ -183,7 +183,7 @@ static int set_shape(jl_ctx *ctx, uint64_t n_reads, uint32_t n_cols, uint64_t pl
     ctx->alloc_version++;
     ctx->pack_valid = false;
     ctx->pileup_done = ctx->call_done = ctx->phase_done = false;
-    ctx->ins_valid = ctx->insal_valid = false;
+    ctx->ins_valid = ctx->insal_valid = ctx->insev_valid = false;
     return JL_OK;
 }
 

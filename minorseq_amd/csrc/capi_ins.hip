@@ -1,6 +1,6 @@
 // capi_ins.hip — the in-frame insertion alleles of include/juliet_hip.h (docs/SPEC.md §17): the switch, the fetch of what a tracking
 // record build left (capi_records.hip records_build enqueues the kernels of kernels_ins.hip), and the host-only test of one allele
-// against a rate of in-frame insertions by error (jl_insertion_test).
+// against a rate of in-frame insertions by error (jl_insertion_test); the per-read events of such a build (§19): switch and fetch.
 #include <math.h>
 #include <string.h>
 
@@ -45,6 +45,35 @@ int jl_insertion_alleles_fetch(jl_ctx *ctx, uint32_t *jcnt, jl_insertion_allele 
     std::sort(rows, rows + n, [](const jl_insertion_allele &x, const jl_insertion_allele &y) {
         return x.col != y.col ? x.col < y.col : x.len != y.len ? x.len < y.len : x.seq < y.seq;
     });
+    return JL_OK;
+}
+
+int jl_msa_track_insertion_reads(jl_ctx *ctx, int on)
+{
+    if (!ctx) return JL_ERR_ARG;
+    ctx->track_ins_reads = on != 0;
+    return JL_OK;
+}
+
+int jl_insertion_reads_fetch(jl_ctx *ctx, jl_insertion_event *rows, uint32_t cap, uint32_t *n_rows)
+{
+    static const char *fn = "jl_insertion_reads_fetch";
+    if (!ctx) return JL_ERR_ARG;
+    if (!ctx->insev_valid)
+        return jl_fail(ctx, JL_ERR_STATE, "%s: no insertion events: jl_msa_track_insertion_reads(ctx, 1) before the record build of this matrix", fn);
+    JL_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    uint32_t n = 0;
+    JL_HIP(ctx, hipMemcpyAsync(&n, ctx->insev_count, sizeof n, hipMemcpyDeviceToHost, st));
+    JL_HIP(ctx, hipStreamSynchronize(st));
+    if (n > ctx->insev_cap) return jl_fail(ctx, JL_ERR_DEVICE, "%s: %u events in a list of %u", fn, n, ctx->insev_cap);
+    if (n_rows) *n_rows = n;
+    if (!rows || !n) return JL_OK;
+    if (cap < n) return jl_fail(ctx, JL_ERR_ARG, "%s: room for %u rows, the list has %u", fn, cap, n);
+    JL_HIP(ctx, hipMemcpyAsync(rows, ctx->insev_rows, (size_t)n * sizeof *rows, hipMemcpyDeviceToHost, st));
+    JL_HIP(ctx, hipStreamSynchronize(st));
+    // the list's order is the order of the walk's atomics: the delivered one is (read, col)
+    std::sort(rows, rows + n, [](const jl_insertion_event &x, const jl_insertion_event &y) { return x.read != y.read ? x.read < y.read : x.col < y.col; });
     return JL_OK;
 }
 

@@ -234,6 +234,18 @@ static hipError_t reserve_insertion_alleles(jl_ctx *dst, const jl_records &R, ui
     return e;
 }
 
+// the event rows of `dst` for a build from R that tracks reads, their counter zeroed on its stream (docs/SPEC.md §19): a row an
+// 'I' op, since an event needs one (R.n_ins_ops fits 32 bits: records_build)
+static hipError_t reserve_insertion_events(jl_ctx *dst, const jl_records &R)
+{
+    hipStream_t st = dst->stream;
+    dst->insev_cap = (uint32_t)R.n_ins_ops;
+    hipError_t e = dst->insev_rows.grow_discard(st, (size_t)R.n_ins_ops);
+    if (e == hipSuccess) e = dst->insev_count.grow_discard(st, 1);
+    if (e == hipSuccess) e = hipMemsetAsync(dst->insev_count, 0, 4u, st);
+    return e;
+}
+
 // the record walk of a tracking build: the filter as jl_launch_ingest resolves it
 static void launch_insertion_alleles(jl_ctx *dst, const jl_records &R, uint32_t min_qv)
 {
@@ -249,6 +261,7 @@ static void launch_insertion_alleles(jl_ctx *dst, const jl_records &R, uint32_t 
     a.key0 = dst->insal_keys, a.key1 = dst->insal_keys + dst->insal_slots;
     a.count = dst->insal_count, a.occ = dst->insal_count + dst->insal_slots, a.n_occ = dst->insal_count + 2u * dst->insal_slots;
     a.slots_mask = dst->insal_slots - 1u;
+    if (dst->track_ins_reads) a.events = dst->insev_rows, a.n_events = dst->insev_count, a.events_cap = dst->insev_cap;
     jl_launch_insertion_alleles(&a, dst->stream);
 }
 
@@ -258,6 +271,9 @@ static void launch_insertion_alleles(jl_ctx *dst, const jl_records &R, uint32_t 
 static int records_build(jl_ctx *src, jl_ctx *dst, uint32_t n_cols, uint32_t win_begin, uint32_t min_qv, bool wait)
 {
     const jl_records &R = src->rec;
+    const bool track_alleles = dst->track_ins_alleles || dst->track_ins_reads;   // (the events imply the alleles: docs/SPEC.md §19)
+    if (dst->track_ins_reads && R.n_ins_ops > 0xFFFFFFFFull)
+        return jl_fail(dst, JL_ERR_ARG, "records: %llu 'I' ops, the event list of jl_msa_track_insertion_reads holds 2^32 - 1", (unsigned long long)R.n_ins_ops);
     // (a stream nothing was appended to ends here, "empty matrix": what follows never sees zero reads)
     int rc = jl_msa_alloc(dst, R.n_reads, n_cols, win_begin);
     if (rc) return rc;
@@ -285,9 +301,10 @@ static int records_build(jl_ctx *src, jl_ctx *dst, uint32_t n_cols, uint32_t win
             dst->ins_valid = e == hipSuccess;
         }
     }
-    dst->insal_valid = false;
-    if (e == hipSuccess && dst->track_ins_alleles) {
+    dst->insal_valid = dst->insev_valid = false;
+    if (e == hipSuccess && track_alleles) {
         e = reserve_insertion_alleles(dst, R, n_cols);
+        if (e == hipSuccess && dst->track_ins_reads) e = reserve_insertion_events(dst, R);
         if (e == hipSuccess) {
             launch_insertion_alleles(dst, R, min_qv);
             e = hipGetLastError();
@@ -297,7 +314,7 @@ static int records_build(jl_ctx *src, jl_ctx *dst, uint32_t n_cols, uint32_t win
         jl_launch_ingest(dst, R, min_qv);
         e = hipGetLastError();
         S.check_pending = e == hipSuccess;
-        if (e == hipSuccess && dst->track_ins_alleles) {   // the reads spanning every junction, from the planes just built
+        if (e == hipSuccess && track_alleles) {   // the reads spanning every junction, from the planes just built
             if (n_cols >= 2u) {
                 jl_insal_span_args sa = {};
                 sa.msa = dst->d_msa, sa.plane_stride = dst->plane_stride;   // (a multiple of 16, >= ceil(n_reads / 8): set_shape)
@@ -307,6 +324,7 @@ static int records_build(jl_ctx *src, jl_ctx *dst, uint32_t n_cols, uint32_t win
                 e = hipGetLastError();
             }
             dst->insal_valid = e == hipSuccess;
+            dst->insev_valid = dst->insal_valid && dst->track_ins_reads;
         }
         if (e == hipSuccess && wait) e = hipStreamSynchronize(st);
     }

@@ -396,10 +396,30 @@ struct jl_sites_args {
     uint64_t n_reads;
     uint8_t *dst;              // [9 n_sites][dst_stride]
     uint64_t dst_stride;       // jl_plane_stride(n_reads): whole 128-byte lines, whatever src_stride is
-    const jl_site *sites;      // [n_sites], each col + 2 < the source's n_cols
+    const jl_site *sites;      // [n_sites], each of kind 0 or 1 with col + 2 < the source's n_cols (an insertion site is skipped)
     uint32_t n_sites, pad_;    // 1 .. JL_SITES_MAX
 };
 void jl_launch_sites_assemble(const jl_sites_args *a, hipStream_t st);
+// ... its insertion sites (docs/SPEC.md §19): an init pass over the planes, then one thread per event of the source's record build
+struct jl_ins_site {
+    uint32_t col;              // the junction: 1 .. the source's n_cols - 1
+    uint32_t k;                // its site: destination rows 9 k .. 9 k + 8
+    uint32_t a_begin, a_end;   // its alleles: [a_begin, a_end) of `alleles`, 1 .. JL_SITE_INS_MAX_ALLELES of them
+};
+struct jl_sites_ins_args {
+    const uint8_t *src;
+    uint64_t src_stride;
+    uint64_t n_reads;
+    uint8_t *dst;
+    uint64_t dst_stride;
+    const jl_ins_site *isites;            // [n_isites] ascending by col, no column twice
+    const jl_insertion_allele *alleles;   // ascending by (col, len, seq)
+    const jl_insertion_event *events;     // the source's, [min(*n_events, events_cap)]
+    const uint32_t *n_events;
+    uint32_t events_cap;
+    uint32_t n_isites;                    // 1 .. JL_SITES_MAX
+};
+void jl_launch_sites_insertions(const jl_sites_ins_args *a, hipStream_t st);
 
 // ---- in-frame insertion alleles of a record build (kernels_ins.hip, capi_ins.hip; docs/SPEC.md §17)
 #define JL_INSAL_MAX_BASES 30u             // longest insertion that is an allele: 60 bits of sequence
@@ -422,6 +442,11 @@ struct jl_insal_args {
     unsigned long long *key0, *key1;
     uint32_t *count, *occ, *n_occ;
     uint64_t slots_mask;
+    // the per-read events (jl_msa_track_insertion_reads; docs/SPEC.md §19), null when not tracked: room for events_cap rows,
+    // *n_events (zeroed) counts every event, written or not
+    jl_insertion_event *events;
+    uint32_t *n_events;
+    uint32_t events_cap, pad2_;
 };
 void jl_launch_insertion_alleles(const jl_insal_args *a, hipStream_t st);
 struct jl_insal_span_args {
@@ -626,6 +651,12 @@ struct jl_ctx {
     jl_dev_array<uint32_t> insal_count;            // count [insal_slots], occ [insal_slots], n_occ [1]
     jl_dev_array<jl_insertion_allele> insal_rows;  // the fetch's gather
     uint64_t insal_slots = 0;                      // of the last tracking build
+    // ... and its per-read events (docs/SPEC.md §19; off unless jl_msa_track_insertion_reads, which implies the alleles)
+    bool track_ins_reads = false;
+    bool insev_valid = false;                      // gone where insal_valid goes
+    jl_dev_array<jl_insertion_event> insev_rows;   // [insev_cap], in the order of the walk's atomics
+    jl_dev_array<uint32_t> insev_count;            // [1]: events counted
+    uint32_t insev_cap = 0;                        // the 'I' ops of the last tracking build's records
 
     // ---- aligned records on their way in (jl_records_begin / _append / _finish)
     jl_records rec;
@@ -658,6 +689,8 @@ struct jl_ctx {
 
     // ---- jl_sites_assemble INTO this context: the site table on its way to the device (capi_sites.hip)
     jl_upload_staging<jl_site> sites_in;
+    jl_upload_staging<jl_ins_site> ins_sites_in;             // jl_sites_assemble_alleles: the insertion sites and
+    jl_upload_staging<jl_insertion_allele> site_alleles_in;  // their alleles
 
     // ---- phasing sharded by reads: the groups of this matrix exported for the merge (jl_phase_groups_async / _fetch)
     bool phase_export = false;        // the phase launch in flight / last run exported instead of selecting

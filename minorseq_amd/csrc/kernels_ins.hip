@@ -21,6 +21,11 @@
 // it is never more than half full and a probe always ends; the walk is bounded by the table's size all the same.
 // Everything a lane reads lies inside its read's own bytes: a base index is checked against the read's bases, a quality index
 // against its qualities (a record whose cigar consumes more than it holds is refused by the build's verdict anyway).
+// EVENTS (the kEvents instantiation: jl_msa_track_insertion_reads, docs/SPEC.md §19).  In the round where lanes hold an event, the
+// first of them reserves popc(todo) rows of a->events with ONE atomic add on *a->n_events, and every lane with an event writes its
+// own row at base + its rank among them — an atomic a wave round, not a read.  The counter counts every event; a row at or beyond
+// events_cap is never written (the host sizes the rows by the records' 'I' ops: an event needs one).  The other instantiation
+// holds none of this.
 //
 // SPAN PASS (junction_span_kernel).  span[c] = reads whose cells at c - 1 and c are both covered (code != 6, i.e. not plane 2 and
 // plane 1 both set).  The tile walk of plane_walk.h with two planes and a halo of one: a lane owns a junction, and staged are the
@@ -68,6 +73,7 @@ __device__ __forceinline__ void table_add(const jl_insal_args &a, unsigned long 
     }
 }
 
+template <bool kEvents>
 __global__ __launch_bounds__(256) void insertion_alleles_kernel(jl_insal_args a)
 {
     const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
@@ -137,6 +143,19 @@ __global__ __launch_bounds__(256) void insertion_alleles_kernel(jl_insal_args a)
         }
         uint64_t todo = __ballot(have);
         if (!todo) break;   // no lane has an event: every lane has reached its cigar's end
+        if constexpr (kEvents) {
+            const int first = __ffsll((unsigned long long)todo) - 1;
+            uint32_t base = 0;
+            if ((int)lane == first) base = atomicAdd(a.n_events, (uint32_t)__popcll(todo));
+            base = __shfl(base, first, 64);
+            const uint64_t row = (uint64_t)base + (uint32_t)__popcll(todo & ((1ull << lane) - 1ull));
+            if (have && row < a.events_cap) {
+                jl_insertion_event ev;
+                ev.read = (uint32_t)r, ev.col = col, ev.len = (uint32_t)k0, ev.kind = kind;   // (k0's low word: the length of an allele, else 0)
+                ev.seq = k1;
+                a.events[row] = ev;
+            }
+        }
         while (todo) {      // wave-uniform: one round per distinct event of the wave
             const int leader = __ffsll((unsigned long long)todo) - 1;
             const unsigned long long l0 = __shfl(k0, leader, 64), l1 = __shfl(k1, leader, 64);
@@ -213,10 +232,12 @@ __global__ __launch_bounds__(64) void junction_span_kernel(jl_insal_span_args a)
 
 }  // namespace
 
-// a->jcnt, a->count, *a->n_occ zeroed, the keys all ones; a->n_reads > 0
+// a->jcnt, a->count, *a->n_occ zeroed, the keys all ones; a->n_reads > 0; with a->events: *a->n_events zeroed
 void jl_launch_insertion_alleles(const jl_insal_args *a, hipStream_t st)
 {
-    hipLaunchKernelGGL(insertion_alleles_kernel, dim3((uint32_t)((a->n_reads + 255u) / 256u)), dim3(256), 0, st, *a);
+    const dim3 grid((uint32_t)((a->n_reads + 255u) / 256u));
+    if (a->events) hipLaunchKernelGGL(insertion_alleles_kernel<true>, grid, dim3(256), 0, st, *a);
+    else hipLaunchKernelGGL(insertion_alleles_kernel<false>, grid, dim3(256), 0, st, *a);
 }
 
 void jl_launch_insertion_rows(const unsigned long long *key0, const unsigned long long *key1, const uint32_t *count, const uint32_t *occ,

@@ -175,13 +175,18 @@ inline std::string render_html(const Json &root)
                 if (!ips) continue;
                 h += "<table class=\"insertions\" data-gene=\"" + html_escape(g.get_str("name")) + "\"><caption>" + html_escape(g.get_str("name")) +
                      "</caption>\n<tr><th>After pos</th><th>Codons</th><th>AA</th><th>#Reads</th><th>Coverage</th><th>Frequency</th><th>Expected</th>"
-                     "<th>pValue</th><th>log_pValue</th><th>#Frame-shift reads</th><th>#Unread reads</th></tr>\n";
+                     "<th>pValue</th><th>log_pValue</th><th>#Frame-shift reads</th><th>#Unread reads</th>";
+                if (haps && hb->get("insertion_alleles"))   // --phase-insertions (docs/SPEC.md §19): a column per haplotype
+                    for (const Json &hp : haps->arr) h += "<th class=\"hapname\">" + html_escape(hp.get_str("name")) + "</th>";
+                h += "</tr>\n";
                 for (const Json &d : ips->arr) {
                     std::string cods;
                     for (const Json &c : d.get("inserted_codons")->arr) cods += (cods.empty() ? "" : " ") + c.str;
                     h += "<tr class=\"insertion\">" + td(num_str(d.get("after_position"))) + td(cods) + td(d.get_str("inserted_amino_acids"));
                     for (const char *key : {"count", "coverage", "frequency", "expected", "pValue", "log_pValue", "frameshift_reads", "unread_reads"})
                         h += td(num_str(d.get(key)));
+                    if (const Json *hh = d.get("haplotype_hit"))
+                        for (const Json &x : hh->arr) h += x.b ? "<td class=\"hit\">x</td>" : "<td class=\"nohit\"></td>";
                     h += "</tr>\n";
                 }
                 h += "</table>\n";
@@ -215,8 +220,18 @@ inline std::string render_html(const Json &root)
             for (const Json &p : dpa->arr) h += "<span>" + num_str(&p) + "</span> ";
             h += "</p>\n";
         }
+        const Json *ial = hb->get("insertion_alleles");        // --phase-insertions (docs/SPEC.md §19)
+        if (ial) {
+            h += "<p id=\"hap-insertion-alleles\">";
+            for (const Json &a : ial->arr) {
+                std::string cods;
+                for (const Json &c : a.get("inserted_codons")->arr) cods += (cods.empty() ? "" : " ") + c.str;
+                h += "<span data-gene=\"" + html_escape(a.get_str("gene")) + "\" data-after=\"" + num_str(a.get("after_position")) + "\">" + cods + "</span> ";
+            }
+            h += "</p>\n";
+        }
         h += std::string("<table id=\"hap-table\"><tr><th>Haplotype</th><th>%</th><th>#Reads</th><th>Codons</th>") + (dpa ? "<th>Deletions</th>" : "") +
-             "<th>Read names</th></tr>\n";
+             (ial ? "<th>Insertions</th>" : "") + "<th>Read names</th></tr>\n";
         if (haps)
             for (const Json &hp : haps->arr) {
                 h += "<tr>" + td(hp.get_str("name")) + td(format_hap_percent(100.0 * hp.get("frequency")->num)) + td(num_str(hp.get("reads"))) + "<td>";
@@ -226,6 +241,11 @@ inline std::string render_html(const Json &root)
                 if (const Json *ds = hp.get("deletions")) {
                     h += "<td class=\"hap-deletions\">";
                     for (size_t i = 0; i < ds->arr.size(); ++i) h += std::string(i ? " " : "") + (ds->arr[i].b ? "x" : "-");
+                    h += "</td>";
+                }
+                if (const Json *is = hp.get("insertions")) {
+                    h += "<td class=\"hap-insertions\">";
+                    for (size_t i = 0; i < is->arr.size(); ++i) h += std::string(i ? " " : "") + (is->arr[i].b ? "x" : "-");
                     h += "</td>";
                 }
                 h += "<td><details><summary>" + std::to_string(hp.get("read_names") ? hp.get("read_names")->arr.size() : 0) + "</summary>";

@@ -138,14 +138,14 @@ int run_one_window(Run &run)
         if (const char *what = fetch_deletions(ctx, opt, smp.prm, smp.genes, smp.refcodes, win_begin, n_cols, R)) die_jl(ctx, what);
         tick("deletions");
     }
-    if (opt.phase_deletions) {   // (the haplotypes, hit rows and per-read ids from here on are those of the site matrix)
-        jl_ctx *pc = nullptr;
-        if (const char *what = fetch_sites_phase(ctx, opt.device, opt.min_reads, n_reads, R, &pc)) die_jl(pc ? pc : ctx, what);
-        tick("sites");
-    }
     if (opt.call_insertions) {
         if (const char *what = fetch_insertions(ctx, opt, smp.prm, smp.genes, n_cols, R)) die_jl(ctx, what);
         tick("insertions");
+    }
+    if (opt.phase_deletions || opt.phase_insertions) {   // (the haplotypes, hit rows and per-read ids from here on are those of the site matrix)
+        jl_ctx *pc = nullptr;
+        if (const char *what = fetch_sites_phase(ctx, opt.device, opt.min_reads, n_reads, opt.phase_deletions, opt.phase_insertions, R, &pc)) die_jl(pc ? pc : ctx, what);
+        tick("sites");
     }
     if (!opt.hap_fasta.empty()) {
         if (const int code = write_haplotype_fasta(opt, ctx, R, win_begin, n_cols)) return code;

@@ -43,6 +43,7 @@ struct Options {
     bool linkage = false;            // --linkage: every pair of called variants over the reads covering both (docs/SPEC.md §15)
     bool call_deletions = false;     // --call-deletions: in-frame codon deletions at every evaluated position (docs/SPEC.md §16)
     bool phase_deletions = false;    // --phase-deletions: the called deletions as sites of the haplotypes (docs/SPEC.md §18)
+    bool phase_insertions = false;   // --phase-insertions: the called insertion alleles as sites of the haplotypes (docs/SPEC.md §19)
     bool call_insertions = false;    // --call-insertions: in-frame insertion alleles before every evaluated position (docs/SPEC.md §17)
     bool have_insertion_rate = false;
     double insertion_rate = 0.0;     // --insertion-rate r: a read shows an in-frame insertion at a junction by error (default: the chemistry's deletion rate)
@@ -146,6 +147,15 @@ struct Options {
         "                                      coverage, frequency, expected, pValue, log_pValue, frameshift_reads, unread_reads.  An\n"
         "                                      insertion that splits a codon of a gene is not reported for it.  Empty with\n"
         "                                      --drm-only.  Not with --windows, --devices a,b, --batch, --downsample, --mix or as fuse\n"
+        "      --phase-insertions              with --mode-phasing --call-insertions: the called insertion alleles are sites of the\n"
+        "                                      haplotypes (docs/SPEC.md section 19), with and without --call-deletions\n"
+        "                                      --phase-deletions.  The record ingest keeps which read carries which insertion; every\n"
+        "                                      junction with a called allele is a site of the site matrix whose letters are its\n"
+        "                                      called alleles, \"none\" and \"another in-frame insertion\"; reads with a frame-shifting\n"
+        "                                      or unreadable insertion there are damaged.  The haplotype block gains\n"
+        "                                      insertion_alleles (gene, after_position, inserted_codons) and every haplotype\n"
+        "                                      `insertions`, a flag per allele; every insertion_positions entry gains haplotype_hit.\n"
+        "                                      Not with --rescue-damaged, nor where --call-insertions is refused\n"
         "      --downsample N [--sample-seed S]  call on N reads of the sample (\"downsample it to 6000x\", doc/JULIETFLOW.md:23-25):\n"
         "                                      the reads are chosen by docs/SPEC.md section 12 (seed default 0; samples of one seed are\n"
         "                                      nested) and gathered on the device; N at or above the read count changes nothing.\n"
@@ -286,6 +296,7 @@ Options parse(int argc, char **argv)
         else if (a == "--linkage") o.linkage = true;
         else if (a == "--call-deletions") o.call_deletions = true;
         else if (a == "--phase-deletions") o.phase_deletions = true;
+        else if (a == "--phase-insertions") o.phase_insertions = true;
         else if (a == "--call-insertions") o.call_insertions = true;
         else if (a == "--insertion-rate") {
             const std::string v = need(i);
@@ -364,6 +375,13 @@ Options parse(int argc, char **argv)
         if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
         if (!o.batch.empty()) refuse("is not part of a batch (not with --batch)");
         if (o.sampling()) refuse("reads the insertions of the records that were ingested, not of a sample of them (drop --downsample / --mix)");
+    }
+    if (o.phase_insertions) {   // refused here, before any file is read or any GPU work (what --call-insertions refuses: above)
+        auto refuse = [](const char *why) { std::cerr << "juliet: --phase-insertions " << why << "\n"; std::exit(1); };
+        if (as_fuse) refuse("is not an option of fuse");
+        if (!o.phasing) refuse("adds sites to the haplotypes of a phasing run (add --mode-phasing)");
+        if (!o.call_insertions) refuse("phases the insertions that --call-insertions calls (add it)");
+        if (o.rescue) refuse("leaves no insertion for --rescue-damaged to judge as damage (drop one of the two)");
     }
     if (o.sampling()) {   // what sampling cannot be combined with is refused here, before any file is read or any GPU work
         auto refuse = [&](const char *why) { std::cerr << "juliet: " << (o.mix.empty() ? "--downsample " : "--mix ") << why << "\n"; std::exit(1); };

@@ -154,7 +154,7 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
                 dj.set("expected", Json::of(d.call.expected));
                 dj.set("pValue", Json::of(d.call.p_value)).set("log_pValue", Json::of(d.call.log_p));
                 dj.set("frameshift_reads", Json::of(d.call.partial));
-                if (R.sites_phased) {   // --phase-deletions (docs/SPEC.md §18): the haplotypes that have this codon deleted
+                if (R.dels_phased) {   // --phase-deletions (docs/SPEC.md §18): the haplotypes that have this codon deleted
                     const int site = R.deletion_site(d.col);
                     Json hh = Json::array();
                     for (uint32_t h = 0; h < H; ++h) hh.push(Json::of(site >= 0 && hap_pattern[(size_t)h * R.pat_stride + (size_t)site] == JL_SITE_DELETED));
@@ -184,6 +184,13 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
                 ij.set("expected", Json::of(in.call.expected));
                 ij.set("pValue", Json::of(in.call.p_value)).set("log_pValue", Json::of(in.call.log_p));
                 ij.set("frameshift_reads", Json::of(in.call.frameshift)).set("unread_reads", Json::of(in.call.unread));
+                if (R.ins_phased) {   // --phase-insertions (docs/SPEC.md §19): the haplotypes that carry this allele
+                    const int a = R.site_allele_of(in.allele);
+                    Json hh = Json::array();
+                    for (uint32_t h = 0; h < H; ++h)
+                        hh.push(Json::of(a >= 0 && hap_pattern[(size_t)h * R.pat_stride + R.site_alleles[(size_t)a].site] == R.site_alleles[(size_t)a].code));
+                    ij.set("haplotype_hit", hh);
+                }
                 ips.push(ij);
             }
             gj.set("insertion_positions", ips);
@@ -239,7 +246,7 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
             }
             for (uint32_t h = 0; h < H; ++h) with_rescued_total += (uint64_t)hap_count[h] + rescued_members[h].size();
         }
-        // --phase-deletions with at least one site (docs/SPEC.md §18): position p of the run is site p
+        // --phase-deletions / --phase-insertions with at least one site (docs/SPEC.md §18, §19): position p of the run is site p
         const bool with_sites = R.sites_phased && !R.sites.empty();
         Json hs = Json::array();
         for (uint32_t h = 0; h < H; ++h) {
@@ -253,11 +260,17 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
             else {   // the codon sites only; a codon whose companion deletion site says "deleted" prints ---
                 Json dels = Json::array();
                 for (size_t k = 0; k < R.sites.size(); ++k) {
+                    if (R.sites[k].kind == (uint8_t)JL_SITE_INSERTION) continue;
                     if (R.sites[k].kind == (uint8_t)JL_SITE_DELETION) { dels.push(Json::of(pat[k] == JL_SITE_DELETED)); continue; }
                     const int companion = R.deletion_site(R.sites[k].col);
                     cods.push(Json::of(companion >= 0 && pat[companion] == JL_SITE_DELETED ? std::string("---") : codon_string(pat[k])));
                 }
-                hj.set("deletions", std::move(dels));
+                if (R.dels_phased) hj.set("deletions", std::move(dels));
+            }
+            if (R.ins_phased) {   // a flag per listed allele; a pattern that is "another insertion" or none has none of its site's
+                Json flags = Json::array();
+                for (const Results::SiteAllele &a : R.site_alleles) flags.push(Json::of(pat[a.site] == a.code));
+                hj.set("insertions", std::move(flags));
             }
             hj.set("codons", std::move(cods));
             Json rn = Json::array();      // (moved on, level by level: a copy of this list per level was most of the stage at a million reads)
@@ -283,11 +296,24 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
             for (const jl_site &x : R.sites)
                 if (x.kind == (uint8_t)JL_SITE_CODON) pc.push(Json::of(win_begin + x.col + 1));
         hb.set("variant_positions_abs", std::move(pc));
-        if (R.sites_phased) {
+        if (R.dels_phased) {
             Json dp = Json::array();
             for (const jl_site &x : R.sites)
                 if (x.kind == (uint8_t)JL_SITE_DELETION) dp.push(Json::of(win_begin + x.col + 1));
             hb.set("deletion_positions_abs", std::move(dp));
+        }
+        if (R.ins_phased) {   // the letters of the insertion sites: by site, then code (an allele called for two genes: under the first)
+            Json ia = Json::array();
+            for (const Results::SiteAllele &a : R.site_alleles) {
+                const Results::Insertion &in = R.ins_rows[a.row];
+                Json cods = Json::array();
+                for (uint32_t k = 0; k + 3 <= in.allele.len; k += 3)
+                    cods.push(Json::of(codon_string((uint8_t)(16u * ((in.allele.seq >> (2u * k)) & 3u) + 4u * ((in.allele.seq >> (2u * k + 2u)) & 3u) +
+                                                              ((in.allele.seq >> (2u * k + 4u)) & 3u)))));
+                ia.push(Json::object().set("gene", Json::of(cfg.genes[in.gene].name))
+                            .set("after_position", Json::of(in.codon_pos + cfg.genes[in.gene].first_codon - 1)).set("inserted_codons", std::move(cods)));
+            }
+            hb.set("insertion_alleles", std::move(ia));
         }
         if (R.rescued)
             hb.set("rescue", Json::object()

@@ -59,9 +59,10 @@ struct Results {
     struct Deletion { uint32_t gene, codon_pos, col; int ref_codon; jl_deletion_call call; };
     bool deletions = false;
     std::vector<Deletion> del_rows;
-    // --phase-deletions (docs/SPEC.md §18): the phasing results above are those of the site matrix then.  sites: ascending by
-    // (col, kind); site_rows: the phasing table on it; var_row[k]: the row of site_rows that is row k of `var`
-    bool sites_phased = false;
+    // --phase-deletions (docs/SPEC.md §18), --phase-insertions (§19): the phasing results above are those of the site matrix then.
+    // sites: ascending by (col, kind); site_rows: the phasing table on it; var_row[k]: the row of site_rows that is row k of `var`
+    bool sites_phased = false;                      // either flag
+    bool dels_phased = false, ins_phased = false;   // which kinds of site were asked for
     std::vector<jl_site> sites;
     std::vector<jl_variant> site_rows;
     std::vector<uint32_t> var_row;
@@ -70,6 +71,18 @@ struct Results {
     {
         for (size_t k = 0; k < sites.size(); ++k)
             if (sites[k].col == col && sites[k].kind == (uint8_t)JL_SITE_DELETION) return (int)k;
+        return -1;
+    }
+    // §19: the distinct called alleles, ascending by (col, len, seq) — by site, then code — as the site matrix takes them, and per
+    // allele its site, its code there and the first row of ins_rows that names it
+    struct SiteAllele { uint32_t site, code, row; };
+    std::vector<jl_insertion_allele> site_allele_keys;
+    std::vector<SiteAllele> site_alleles;
+    // the listed allele that row `in` of ins_rows is: its index, or -1
+    int site_allele_of(const jl_insertion_allele &a) const
+    {
+        for (size_t i = 0; i < site_allele_keys.size(); ++i)
+            if (site_allele_keys[i].col == a.col && site_allele_keys[i].len == a.len && site_allele_keys[i].seq == a.seq) return (int)i;
         return -1;
     }
     // --call-insertions (docs/SPEC.md §17): the called alleles in (gene, codon, length, sequence) order; codon_pos: the position they precede
@@ -307,52 +320,84 @@ const char *fetch_deletions(jl_ctx *ctx, const Options &opt, const jl_params &pr
     return nullptr;
 }
 
-// --phase-deletions, after fetch_calls and fetch_deletions: the sites and the phasing table of docs/SPEC.md §18 from the variant table
-// and the called deletions, the site matrix of the window on `ctx` in a context of its own on the same device and stream, and the
-// phasing that exists on it.  Its results replace the plain run's in R; the read order is the window's.  No site: nothing to phase,
-// R keeps the plain run's (no haplotype).
-const char *fetch_sites_phase(jl_ctx *ctx, int device, uint32_t min_reads, uint64_t n_reads, Results &R, jl_ctx **pc_out)
+// --phase-deletions and / or --phase-insertions, after fetch_calls, fetch_deletions and fetch_insertions: the sites and the phasing
+// table of docs/SPEC.md §18 and §19 from the variant table, the called deletions (`dels`) and the called insertion alleles (`ins`),
+// the site matrix of the window on `ctx` in a context of its own on the same device and stream, and the phasing that exists on it.
+// Its results replace the plain run's in R; the read order is the window's.  No site: nothing to phase, R keeps the plain run's.
+const char *fetch_sites_phase(jl_ctx *ctx, int device, uint32_t min_reads, uint64_t n_reads, bool dels, bool ins, Results &R, jl_ctx **pc_out)
 {
     R.sites_phased = true;
-    R.sites.clear(), R.site_rows.clear();
-    std::vector<uint32_t> dels;   // the distinct codon starts of the called deletions over all genes, ascending
-    for (const Results::Deletion &d : R.del_rows) dels.push_back(d.col);
-    std::sort(dels.begin(), dels.end());
-    dels.erase(std::unique(dels.begin(), dels.end()), dels.end());
+    R.dels_phased = dels, R.ins_phased = ins;
+    R.sites.clear(), R.site_rows.clear(), R.site_allele_keys.clear(), R.site_alleles.clear();
     std::vector<uint32_t> order(R.var.size());   // the rows by column (genes may overlap), the rows of one column in the table's order
     for (uint32_t k = 0; k < order.size(); ++k) order[k] = k;
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return R.var[a].col < R.var[b].col; });
     R.var_row.assign(R.var.size(), 0);
-    size_t v = 0, d = 0;
-    while (v < order.size() || d < dels.size()) {
-        const uint32_t vc = v < order.size() ? R.var[order[v]].col : 0xFFFFFFFFu, dc = d < dels.size() ? dels[d] : 0xFFFFFFFFu;
-        const uint32_t col = std::min(vc, dc);
-        if (vc == col) {   // a codon site, filled with the reference codon where a deletion is called too
-            const uint32_t k = (uint32_t)R.sites.size();
-            R.sites.push_back(jl_site{col, (uint8_t)JL_SITE_CODON, dc == col ? R.var[order[v]].ref_codon : (uint8_t)JL_SITE_NO_FILL, 0});
+    // the sites: the distinct columns of the variant rows, of the called deletions and of the called insertion alleles over all genes
+    std::vector<std::pair<uint32_t, uint8_t>> keys;   // (col, kind)
+    for (const jl_variant &v : R.var) keys.emplace_back(v.col, (uint8_t)JL_SITE_CODON);
+    if (dels)
+        for (const Results::Deletion &d : R.del_rows) keys.emplace_back(d.col, (uint8_t)JL_SITE_DELETION);
+    if (ins)
+        for (const Results::Insertion &in : R.ins_rows) {
+            keys.emplace_back(in.allele.col, (uint8_t)JL_SITE_INSERTION);
+            R.site_allele_keys.push_back(jl_insertion_allele{in.allele.col, in.allele.len, in.allele.seq, 0, 0});
+        }
+    std::sort(keys.begin(), keys.end());
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    auto allele_less = [](const jl_insertion_allele &x, const jl_insertion_allele &y) {
+        return x.col != y.col ? x.col < y.col : x.len != y.len ? x.len < y.len : x.seq < y.seq;
+    };
+    std::sort(R.site_allele_keys.begin(), R.site_allele_keys.end(), allele_less);   // (an allele called for two genes: once)
+    R.site_allele_keys.erase(std::unique(R.site_allele_keys.begin(), R.site_allele_keys.end(),
+                                         [&](const jl_insertion_allele &x, const jl_insertion_allele &y) { return !allele_less(x, y) && !allele_less(y, x); }),
+                             R.site_allele_keys.end());
+    size_t v = 0, a = 0;
+    for (size_t i = 0; i < keys.size(); ++i) {
+        const uint32_t col = keys[i].first, k = (uint32_t)R.sites.size();
+        if (keys[i].second == (uint8_t)JL_SITE_CODON) {   // filled with the reference codon where a deletion site follows
+            const bool deleted_too = i + 1 < keys.size() && keys[i + 1] == std::make_pair(col, (uint8_t)JL_SITE_DELETION);
+            R.sites.push_back(jl_site{col, (uint8_t)JL_SITE_CODON, deleted_too ? R.var[order[v]].ref_codon : (uint8_t)JL_SITE_NO_FILL, 0});
             for (; v < order.size() && R.var[order[v]].col == col; ++v) {
                 R.var_row[order[v]] = (uint32_t)R.site_rows.size();
                 R.site_rows.push_back(R.var[order[v]]);
                 R.site_rows.back().col = 3u * k;
             }
-        }
-        if (dc == col) {   // a deletion site and its pseudo-row
+        } else if (keys[i].second == (uint8_t)JL_SITE_DELETION) {   // a deletion site and its pseudo-row
             jl_variant row = {};
-            row.col = 3u * (uint32_t)R.sites.size(), row.codon = (uint8_t)JL_SITE_DELETED, row.ref_codon = (uint8_t)JL_SITE_PRESENT;
+            row.col = 3u * k, row.codon = (uint8_t)JL_SITE_DELETED, row.ref_codon = (uint8_t)JL_SITE_PRESENT;
             R.sites.push_back(jl_site{col, (uint8_t)JL_SITE_DELETION, (uint8_t)JL_SITE_NO_FILL, 0});
             R.site_rows.push_back(row);
-            ++d;
+        } else {   // an insertion site and a pseudo-row per called allele, ascending by code
+            R.sites.push_back(jl_site{col, (uint8_t)JL_SITE_INSERTION, (uint8_t)JL_SITE_NO_FILL, 0});
+            for (uint32_t code = 1; a < R.site_allele_keys.size() && R.site_allele_keys[a].col == col; ++a, ++code) {
+                if (code > (uint32_t)JL_SITE_INS_MAX_ALLELES) {
+                    std::cerr << "juliet: --phase-insertions: more than " << (int)JL_SITE_INS_MAX_ALLELES << " called alleles at one junction (window column " << col
+                              << "), a site holds that many (narrow the calls with --min-perc / --insertion-rate)\n";
+                    std::exit(2);
+                }
+                jl_variant row = {};
+                row.col = 3u * k, row.codon = (uint8_t)code, row.ref_codon = (uint8_t)JL_SITE_INS_NONE;
+                R.site_rows.push_back(row);
+                uint32_t first = 0;
+                while (R.site_allele_of(R.ins_rows[first].allele) != (int)a) ++first;
+                R.site_alleles.push_back({k, code, first});
+            }
         }
     }
     if (R.sites.empty()) return nullptr;
     if (R.site_rows.size() > 4096) {
-        std::cerr << "juliet: --phase-deletions: " << R.site_rows.size() << " variants and deletion sites, phasing takes 4096 (narrow the table with --min-perc / --max-perc / --region)\n";
+        std::cerr << "juliet: " << (dels ? "--phase-deletions" : "--phase-insertions") << ": " << R.site_rows.size()
+                  << " variants and deletion sites, phasing takes 4096 (narrow the table with --min-perc / --max-perc / --region)\n";
         std::exit(2);
     }
     jl_ctx *pc = nullptr;
     if (jl_ctx_create(device, jl_ctx_stream(ctx), &pc) != JL_OK) return "context of the site matrix";
     *pc_out = pc;
-    if (jl_sites_assemble(pc, ctx, R.sites.data(), (uint32_t)R.sites.size()) != JL_OK) return "site matrix";
+    if (!ins) {
+        if (jl_sites_assemble(pc, ctx, R.sites.data(), (uint32_t)R.sites.size()) != JL_OK) return "site matrix";
+    } else if (jl_sites_assemble_alleles(pc, ctx, R.sites.data(), (uint32_t)R.sites.size(), R.site_allele_keys.data(), (uint32_t)R.site_allele_keys.size()) != JL_OK)
+        return "site matrix";
     if (jl_phase_async(pc, R.site_rows.data(), (uint32_t)R.site_rows.size(), min_reads) != JL_OK) return "phasing of the site matrix";
     const uint32_t cap_var = (uint32_t)R.site_rows.size();
     R.pos_cols.assign(cap_var, 0);
@@ -487,6 +532,7 @@ Status ingest_window(jl_ctx *ctx, uint32_t n_cols, uint32_t win_begin, const Opt
     Status st;
     if (!opt.consensus.empty()) jl_msa_track_insertions(ctx, 1);
     if (opt.call_insertions) jl_msa_track_insertion_alleles(ctx, 1);
+    if (opt.phase_insertions) jl_msa_track_insertion_reads(ctx, 1);   // (docs/SPEC.md §19: which read carries which insertion)
     if (const int rc = jl_records_finish(ctx, n_cols, win_begin, opt.min_qv)) {
         st.outcome = Outcome::device;
         st.what = "ingest";
