@@ -43,12 +43,17 @@
 //                       quarter of the piece's byte offset — one register a piece, asked for with the piece.
 //                       (Rounds 1-3 expanded every read into a by-row matrix in HBM: 870 MB moved for the 316 MB needed;
 //                       round 4 scattered the codes into a by-row LDS tile with masked, shifted XORs: 137 us.)
+// Where things are: what a cigar op means, the entries' fields, the verdict on a record and the long-read rule — cigar_rules.h, shared
+// with the host (jl_ingest_read_is_long); the descriptor — make_desc and the desc_… readers, below its layout; a planes workgroup's
+// LDS — planes_lds; block number -> (tile, sweep) — place_of; a unit of the planes kernel — planes_unit = pieces_stage | read_stage,
+// barrier, the hand-on check, table_stage, barrier, gather_stage, store_block_words, the slow tail (slow_pair).
 
 #include <algorithm>
 
+#include "cigar_rules.h"
 #include "jl_internal.h"
 
-#ifndef JL_NT_QM      // sibling tiles a workgroup of the planes kernel's mask mode (jl_launch_ingest): 1 or 2
+#ifndef JL_NT_QM     // sibling tiles a workgroup of the planes kernel's mask mode (jl_launch_ingest): 1 or 2
 #define JL_NT_QM 2
 #endif
 
@@ -63,18 +68,27 @@ constexpr uint32_t kTileReads = 128u;               // reads per workgroup (64-r
 constexpr uint32_t kTileGroups = kTileReads / 32u;  // groups of 32 reads = dwords of a plane the tile writes per column
 constexpr uint32_t kSubTiles = 1024u / kTileReads;  // tiles that share the 128-byte lines of the planes
 constexpr uint32_t kThreads = 2u * kTileReads;      // a thread per read in the prologue, two in the table fill
-constexpr uint32_t kRunMask = 0x3FFFFFFFu;          // window column of an entry; kind in the two bits above
 static_assert(kSweep % 16u == 0 && kTileReads % 32u == 0 && kThreads <= 1024u, "whole blocks for both table threads, whole plane dwords");
 static_assert(kTileGroups * kBlocks <= kThreads, "a thread per 32 reads x 8 columns in the transposing phase");
 
+// the cigar rules, the entries' fields and makers, the verdict on a record, the long-read rule's kWalkOps and kWalkEnt: cigar_rules.h
+using namespace jl_cigar;
+__device__ __forceinline__ uint2 as_uint2(entry_t e) { return make_uint2(e.x, e.y); }
+
 // ---------------------------------------------------------------------------------------- runs
-// inclusive prefix sum over the 64 lanes by DPP (four shifts within rows of 16, two row broadcasts)
-__device__ __forceinline__ uint32_t wave_scan(uint32_t v)
+// inclusive prefix sum within the DPP rows of sixteen lanes (four shifts)
+__device__ __forceinline__ uint32_t row_scan(uint32_t v)
 {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);   // row_shr:1
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);   // row_shr:2
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);   // row_shr:4
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);   // row_shr:8
+    return v;
+}
+// ... and over the 64 lanes: the rows' sums go on by two row broadcasts
+__device__ __forceinline__ uint32_t wave_scan(uint32_t v)
+{
+    v = row_scan(v);
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xA, 0xF, false);  // row_bcast:15 -> rows 1, 3
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xC, 0xF, false);  // row_bcast:31 -> rows 2, 3
     return v;
@@ -101,6 +115,67 @@ constexpr uint32_t kDescMax = 255u;         // "more than the planes kernel take
 // The entries of a sweep: from the one that contains its first column to the first one that begins behind its last column.
 // Two entries = ONE entry covers the whole sweep, the common case: then `entries` reads 1, y = the query offset of the sweep's
 // first column and bits 8-9 of w = the entry's kind — the planes kernel never asks for the entries.
+// a row of the planes kernel's staging area: a sweep's pieces and one more — its first piece may begin seven bases before the sweep,
+// which leaves room for 25 inserted bases (a read with more of them in a sweep goes to slow_pair)
+constexpr uint32_t kRowPieces = (kSweep + 31u) / 32u + 1u;
+// the aligned bases of a sweep's entries in the query, [q_lo, q_hi): empty until an entry adds to it
+struct query_range {
+    uint32_t q_lo = 0xFFFFFFFFu, q_hi = 0;
+};
+// entry e (the one behind it: nx) within the sweep's columns [X, Xend)
+__device__ __forceinline__ void range_add(query_range &g, uint2 e, uint2 nx, uint32_t X, uint32_t Xend)
+{
+    if (entry_kind(e.x) != kAligned) return;
+    const uint32_t W = entry_col(e.x), ca = max(W, X), cbv = min(entry_col(nx.x), Xend);
+    if (ca < cbv) {
+        g.q_lo = min(g.q_lo, e.y + (ca - W));
+        g.q_hi = max(g.q_hi, e.y + (cbv - W));
+    }
+}
+// the descriptor of a sweep that begins at column X: its first entry and that entry's index in runs[], its entries (kDescMax: too
+// many), the query range they take; seq_off: the read's first byte of packed bases
+__device__ __forceinline__ uint4 make_desc(uint2 first, uint64_t first_idx, uint32_t n_ent, query_range g, uint32_t X, uint64_t seq_off)
+{
+    // the 16-byte pieces of packed bases the sweep takes: from the DWORD that holds its first base on — at most seven bases
+    // before it, so that a row of the planes kernel (a sweep + 32 bases) has room for 25 inserted ones (byte offsets are
+    // even in bases: all of this in 32 bits relative to the read's first byte, the one 64-bit sum at the end)
+    uint64_t piece = 0;
+    uint32_t np = 0;
+    int32_t q0 = 0;
+    if (g.q_lo < g.q_hi) {
+        const uint32_t al = (uint32_t)seq_off & 3u;                          // the read's first byte within its dword
+        const uint32_t b_lo = al + (g.q_lo >> 1), b_hi = al + (g.q_hi + 1u) / 2u;   // bytes from that dword's first on
+        const uint32_t d_lo = b_lo >> 2;
+        piece = (seq_off >> 2) + d_lo;
+        np = min((b_hi + 15u - 4u * d_lo) >> 4, kDescMax);
+        q0 = 2 * ((int32_t)(4u * d_lo) - (int32_t)al);
+    }
+    uint4 d;
+    d.x = (uint32_t)piece;
+    d.z = (uint32_t)q0;
+    if (n_ent == 2u) {
+        // ONE entry covers the whole sweep (three reads in four of a CCS sample): the planes kernel needs no entries for it —
+        // what the entry is, and the query offset of the sweep's first column
+        d.y = first.y + (X - entry_col(first.x));
+        d.w = (uint32_t)((piece >> 32) & 0xFFu) | (entry_kind(first.x) << 8) | (np << 16) | (1u << 24);
+    } else {
+        d.y = (uint32_t)first_idx;
+        d.w = (uint32_t)((piece >> 32) & 0xFFu) | ((uint32_t)((first_idx >> 32) & 0xFFu) << 8) | (np << 16) | (n_ent << 24);
+    }
+    return d;
+}
+// ... and as the planes kernel reads it
+__device__ __forceinline__ uint4 desc_of_no_read() { return make_uint4(0, 0, 0, kNothing << 8 | 1u << 24); }   // one entry of nothing
+__device__ __forceinline__ uint32_t desc_pieces(const uint4 &d) { return (d.w >> 16) & 0xFFu; }
+__device__ __forceinline__ uint32_t desc_entries(const uint4 &d) { return d.w >> 24; }
+__device__ __forceinline__ bool desc_simple(const uint4 &d) { return desc_entries(d) == 1u; }
+__device__ __forceinline__ uint32_t desc_simple_kind(const uint4 &d) { return (d.w >> 8) & 3u; }
+__device__ __forceinline__ uint32_t desc_simple_q(const uint4 &d) { return d.y; }      // query offset of the sweep's first column
+__device__ __forceinline__ uint64_t desc_piece_dw(const uint4 &d) { return (((uint64_t)d.w & 0xFFu) << 32) | d.x; }
+__device__ __forceinline__ uint64_t desc_entry_idx(const uint4 &d) { return (((uint64_t)(d.w >> 8) & 0xFFu) << 32) | d.y; }
+__device__ __forceinline__ int32_t desc_q0(const uint4 &d) { return (int32_t)d.z; }
+// more pieces than a staging row holds, or more entries than a descriptor counts: the pair is left to slow_pair
+__device__ __forceinline__ bool desc_slow(const uint4 &d) { return desc_pieces(d) > kRowPieces || desc_entries(d) == kDescMax; }
 
 // The records are untrusted: a cigar with an 'M' (forbidden in PacBio BAM, doc/JULIET.md:53), one that consumes more bases
 // (or qualities) than the record holds, or one that spans 2^30 reference bases or more is reported — *bad = min over such reads
@@ -170,22 +245,8 @@ __global__ __launch_bounds__(256) void cigar_runs_kernel(uint64_t n_reads, const
     uint32_t max_ops = n_ops;                  // of the wave's four reads
 #pragma unroll
     for (int t = 0; t < 4; ++t) max_ops = max(max_ops, (uint32_t)__builtin_amdgcn_readlane((int)n_ops, 16 * t));
-    // inclusive scan within the row of sixteen lanes
-    auto row_scan = [](uint32_t v) -> uint32_t {
-        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);   // row_shr:1
-        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);   // row_shr:2
-        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);   // row_shr:4
-        v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);   // row_shr:8
-        return v;
-    };
     auto row_last = [&](uint32_t v) -> uint32_t {   // lane 15 of the row's value, in all of its lanes
         return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(4u * (lane | 15u)), (int)v);
-    };
-    // window column of reference offset `ref`, clamped to the window; `before`: how far in front of it
-    auto window_col = [&](uint64_t ref, uint32_t &before) -> uint32_t {
-        const int64_t w = base + (int64_t)ref;      // (below 2^60: 28-bit lengths, fewer than 2^32 ops)
-        before = w >= 0 ? 0u : (-w > (int64_t)0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)(-w));
-        return w < 0 ? 0u : (w > (int64_t)n_cols ? n_cols : (uint32_t)w);
     };
     auto put = [&](uint32_t idx, uint2 e) {
         out[idx] = e;
@@ -203,26 +264,22 @@ __global__ __launch_bounds__(256) void cigar_runs_kernel(uint64_t n_reads, const
             wb = k + 4u < n_ops ? *reinterpret_cast<const u32x4a4 *>(cig + k + 4u) : z;
         }
         const uint32_t w8[8] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
-        // what an op does, from three constants indexed by its code: D N = X consume the reference, I S = X the query; kind 1
-        // for = X, 2 for D, 3 for N
-        constexpr uint32_t kRefOps = (1u << 2) | (1u << 3) | (1u << 7) | (1u << 8);
-        constexpr uint32_t kQueryOps = (1u << 1) | (1u << 4) | (1u << 7) | (1u << 8);
-        constexpr uint32_t kKinds = (2u << 4) | (3u << 6) | (1u << 14) | (1u << 16);   // two bits per op
-        uint32_t kinds = 0, rsum = 0, qsum = 0, big = 0;      // kinds: two bits an op
+        uint32_t kinds = 0, rsum = 0, qsum = 0, big = 0;      // kinds: the ops' kinds (cigar_rules.h), two bits an op
 #pragma unroll
         for (uint32_t t = 0; t < 8u; ++t) {
             const bool in = k + t < n_ops;
             const uint32_t op = w8[t] & 15u, len = in ? w8[t] >> 4 : 0u;
-            kinds |= (len == 0u ? 0u : (kKinds >> (2u * op)) & 3u) << (2u * t);
+            kinds |= kind_of(op, len) << (2u * t);
             has_m = has_m || (op == 0u && in);
-            rsum += ((kRefOps >> op) & 1u) ? len : 0u;
-            qsum += ((kQueryOps >> op) & 1u) ? len : 0u;
+            rsum += consumes_ref(op) ? len : 0u;
+            qsum += consumes_query(op) ? len : 0u;
             big |= len;
         }
         // the kind of the op before this lane's first one: the lane before's last (the row's first lane: the step before's)
         uint32_t before = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(kinds >> 14), 0x111, 0xF, 0xF, true);   // row_shr:1
         if (sl == 0u) before = prev_kind;
-        // bit 2 t: op t begins an entry — it has a kind, and not both it and the op before are aligned bases
+        // bit 2 t: op t begins an entry — begins_entry(its kind, the kind before), the eight at once: it has a kind, and not both it
+        // and the op before are aligned bases (kind 1 = 01: the low bit without the high one)
         const uint32_t prevs = (kinds << 2) | before;
         const uint32_t any = (kinds | (kinds >> 1)) & 0x5555u, both1 = (kinds & ~(kinds >> 1)) & (prevs & ~(prevs >> 1)) & 0x5555u;
         const uint32_t starts = any & ~both1;
@@ -246,13 +303,12 @@ __global__ __launch_bounds__(256) void cigar_runs_kernel(uint64_t n_reads, const
         for (uint32_t t = 0; t < 8u; ++t) {
             const uint32_t op = w8[t] & 15u, len = k + t < n_ops ? w8[t] >> 4 : 0u;
             if ((starts >> (2u * t)) & 1u) {
-                uint32_t bf;
-                const uint32_t w = window_col(ref_at, bf);
-                put(idx, make_uint2(w | (((kinds >> (2u * t)) & 3u) << 30), (uint32_t)q_at + bf));
+                const col_t c = window_col(base, ref_at, n_cols);
+                put(idx, as_uint2(entry_run(c.col, (kinds >> (2u * t)) & 3u, (uint32_t)q_at + c.before)));
                 ++idx;
             }
-            ref_at += ((kRefOps >> op) & 1u) ? len : 0u;
-            q_at += ((kQueryOps >> op) & 1u) ? len : 0u;
+            ref_at += consumes_ref(op) ? len : 0u;
+            q_at += consumes_query(op) ? len : 0u;
         }
         n_runs += row_last(ni);
         prev_kind = row_last(kinds >> 14);   // (only a full step has a successor)
@@ -261,25 +317,16 @@ __global__ __launch_bounds__(256) void cigar_runs_kernel(uint64_t n_reads, const
     }
     // M anywhere in the row?  (a ballot's sixteen bits)
     const uint64_t bm = __ballot(has_m);
-    uint32_t code = ((bm >> (16u * q)) & 0xFFFFull) != 0ull ? 1u : 0u;
-    if (!code) {
-        if (q_total > 2u * (so1 - my_so) || q_total > 0x7FFFFFFFull) code = 2u;
-        else if (q_total > qlen) code = 3u;
-        else if (ref_total > (uint64_t)kRunMask) code = 4u;
-    }
+    uint32_t code = verdict(((bm >> (16u * q)) & 0xFFFFull) != 0ull, q_total, so1 - my_so, qlen, ref_total);
     if (!live) code = 0;
     uint32_t end_col = 0;
     if (code) {
         n_runs = 0;
         if (sl == 0u) atomicMin(bad, ((unsigned long long)r << 8) | code);
-    } else {
-        uint32_t bf;
-        end_col = window_col(ref_total, bf);
-    }
+    } else end_col = window_col(base, ref_total, n_cols).col;
     if (live && sl < 3u) {
         const uint32_t idx = sl == 0u ? 0u : n_runs + sl;
-        const uint2 e = sl == 0u ? make_uint2(3u << 30, 0u) : sl == 1u ? make_uint2(end_col | (3u << 30), (uint32_t)q_total) : make_uint2(kRunMask | (3u << 30), 0u);
-        put(idx, e);
+        put(idx, as_uint2(sl == 0u ? entry_before() : sl == 1u ? entry_end(end_col, (uint32_t)q_total) : entry_never()));
         if (sl == 0u) nruns[r] = n_runs;
     }
     // ---- the descriptors: a lane per sweep (fifteen sweeps a pass: a sweep needs the bound of the next one too).  Entries
@@ -306,58 +353,25 @@ __global__ __launch_bounds__(256) void cigar_runs_kernel(uint64_t n_reads, const
             uint32_t f = 0;
             for (uint32_t step = top; step; step >>= 1) {
                 const uint32_t t = f + step;
-                if (live && t <= n_ent_all && (entry(t - 1u).x & kRunMask) <= X_bound) f = t;
+                if (live && t <= n_ent_all && entry_col(entry(t - 1u).x) <= X_bound) f = t;
             }
             const uint32_t f_next = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)f, 0x101, 0xF, 0xF, false);   // row_shl:1
             if (!live || sl == kDescSweeps || s >= n_sweeps) continue;
             const uint32_t Xend = min(n_cols, X + kSweep);
             const uint32_t lo = f - 1u;
             uint32_t n_ent = f_next - f + 2u;
-            uint32_t q_lo = 0xFFFFFFFFu, q_hi = 0;
+            query_range g;
             uint2 e = entry(lo);
             const uint2 first = e;
             if (n_ent >= kDescMax) n_ent = kDescMax;
             else {
                 for (uint32_t i = lo; i + 1u < lo + n_ent; ++i) {
                     const uint2 nx = entry(i + 1u);
-                    if ((e.x >> 30) == 1u) {
-                        const uint32_t W = e.x & kRunMask, ca = max(W, X), cbv = min(nx.x & kRunMask, Xend);
-                        if (ca < cbv) {
-                            q_lo = min(q_lo, e.y + (ca - W));
-                            q_hi = max(q_hi, e.y + (cbv - W));
-                        }
-                    }
+                    range_add(g, e, nx, X, Xend);
                     e = nx;
                 }
             }
-            // the 16-byte pieces of packed bases the sweep takes: from the DWORD that holds its first base on — at most seven bases
-            // before it, so that a row of the planes kernel (a sweep + 32 bases) has room for 25 inserted ones (byte offsets are
-            // even in bases: all of this in 32 bits relative to the read's first byte, the one 64-bit sum at the end)
-            uint64_t piece = 0;
-            uint32_t np = 0;
-            int32_t q0 = 0;
-            if (q_lo < q_hi) {
-                const uint32_t al = (uint32_t)my_so & 3u;                        // the read's first byte within its dword
-                const uint32_t b_lo = al + (q_lo >> 1), b_hi = al + (q_hi + 1u) / 2u;   // bytes from that dword's first on
-                const uint32_t d_lo = b_lo >> 2;
-                piece = (my_so >> 2) + d_lo;
-                np = min((b_hi + 15u - 4u * d_lo) >> 4, kDescMax);
-                q0 = 2 * ((int32_t)(4u * d_lo) - (int32_t)al);
-            }
-            const uint64_t e_idx = ent0 + lo;
-            uint4 d;
-            d.x = (uint32_t)piece;
-            d.z = (uint32_t)q0;
-            if (n_ent == 2u) {
-                // ONE entry covers the whole sweep (three reads in four of a CCS sample): the planes kernel needs no entries for it —
-                // what the entry is, and the query offset of the sweep's first column
-                d.y = first.y + (X - (first.x & kRunMask));
-                d.w = (uint32_t)((piece >> 32) & 0xFFu) | ((first.x >> 30) << 8) | (np << 16) | (1u << 24);
-            } else {
-                d.y = (uint32_t)e_idx;
-                d.w = (uint32_t)((piece >> 32) & 0xFFu) | ((uint32_t)((e_idx >> 32) & 0xFFu) << 8) | (np << 16) | (n_ent << 24);
-            }
-            desc[(uint64_t)s * n_reads + r] = d;
+            desc[(uint64_t)s * n_reads + r] = make_desc(first, ent0 + lo, n_ent, g, X, my_so);
         }
     };
     const uint2 *s_mine = s_run[q];
@@ -389,11 +403,7 @@ __global__ __launch_bounds__(256) void cigar_runs_kernel(uint64_t n_reads, const
 // SIMD then, 1563 waves for 1024 SIMDs, and the length of the dependent chain is all that counts.)
 // A read with more than kWalkOps ops or more than kWalkEnt entries is left, whole, to the long-read launch (cigar_runs_kernel):
 // nruns[r] = kRunsDeferred.
-constexpr uint32_t kWalkOps = 192u;
-// entries of a read in LDS: a CCS read has a dozen.  With 24 two reads in a thousand went to the other launch; with 32 two in 100 000
-// (fifteen deletions) — enough for the upload to have to ask for that launch in every build; with 40 none of a CCS sample does
-// (48: 26 KB of LDS a workgroup, six a CU — not all 1563 of a 100k-read build at once: 28 us instead of 22)
-constexpr uint32_t kWalkEnt = 40u;
+// (kWalkOps, kWalkEnt: cigar_rules.h, with the host's statement of this rule)
 constexpr uint32_t kWalkReads = 64u;    // reads of a workgroup
 
 __global__ __launch_bounds__(256) void cigar_walk_kernel(uint64_t n_reads, const int32_t *__restrict__ pos, const uint32_t *__restrict__ cigar,
@@ -406,7 +416,8 @@ __global__ __launch_bounds__(256) void cigar_walk_kernel(uint64_t n_reads, const
     // second = 0: the host has looked at the cigars (jl_ingest_read_is_long, at the upload) and found no read for the other launch, which
     // is then not made (6 us of a build).  Should this kernel find one all the same, the read covers nothing and the build fails with
     // code 5 — never descriptors nobody wrote.
-    // (the build's counters — [0] pairs listed, [1] units handed on — begin at zero: the planes kernels, which count, come behind this
+    // (the build's counters — [0] retired: it counted the pairs of a list no kernel makes any more, and is zeroed with [1] only because
+    // the block's layout is shared with jl_ingest_verdict; [1] units handed on — begin at zero: the planes kernels, which count, come behind this
     // launch on the stream; a launch of its own for this was 4 us of a build)
     if (blockIdx.x == 0 && threadIdx.x < 2u) count[threadIdx.x] = 0u;
     __shared__ uint2 s_ent[kWalkEnt * kWalkReads];      // entry i of read j at [i * 64 + j]
@@ -426,20 +437,12 @@ __global__ __launch_bounds__(256) void cigar_walk_kernel(uint64_t n_reads, const
             if (n_ops > kWalkOps && !second) {
                 atomicMin(bad, ((unsigned long long)r << 8) | 5u);
                 n_runs = 0;
-                s_ent[j] = make_uint2(3u << 30, 0u);
-                s_ent[kWalkReads + j] = make_uint2(3u << 30, 0u);
-                s_ent[2u * kWalkReads + j] = make_uint2(kRunMask | (3u << 30), 0u);
+                s_ent[j] = as_uint2(entry_before());
+                s_ent[kWalkReads + j] = as_uint2(entry_end(0u, 0u));
+                s_ent[2u * kWalkReads + j] = as_uint2(entry_never());
             }
             if (n_ops <= kWalkOps) {
                 const uint32_t *cig = cigar + my_cb;
-                auto window_col = [&](uint64_t ref, uint32_t &before) -> uint32_t {
-                    const int64_t w = base + (int64_t)ref;
-                    before = w >= 0 ? 0u : (-w > (int64_t)0xFFFFFFFFll ? 0xFFFFFFFFu : (uint32_t)(-w));
-                    return w < 0 ? 0u : (w > (int64_t)n_cols ? n_cols : (uint32_t)w);
-                };
-                constexpr uint32_t kRefOps = (1u << 2) | (1u << 3) | (1u << 7) | (1u << 8);
-                constexpr uint32_t kQueryOps = (1u << 1) | (1u << 4) | (1u << 7) | (1u << 8);
-                constexpr uint32_t kKinds = (2u << 4) | (3u << 6) | (1u << 14) | (1u << 16);   // two bits per op
                 // (the loads take sixteen words from the step's first op on whatever the read's length: words past its ops are the
                 // next read's or the array's slack, and are not looked at)
                 struct ops16 { u32x4a4 a, b, c, d; };
@@ -456,7 +459,7 @@ __global__ __launch_bounds__(256) void cigar_walk_kernel(uint64_t n_reads, const
                 uint32_t prev_kind = 0;
                 bool has_m = false;
                 n_runs = 0;
-                s_ent[j] = make_uint2(3u << 30, 0u);
+                s_ent[j] = as_uint2(entry_before());
                 ops16 cur = ask(0);
                 for (uint32_t k0 = 0; k0 < n_ops; k0 += 16u) {
                     const ops16 nxt = ask(k0 + 16u < n_ops ? k0 + 16u : 0u);
@@ -466,35 +469,29 @@ __global__ __launch_bounds__(256) void cigar_walk_kernel(uint64_t n_reads, const
                     for (uint32_t t = 0; t < 16u; ++t) {
                         const bool in = k0 + t < n_ops;
                         const uint32_t op = w16[t] & 15u, len = in ? w16[t] >> 4 : 0u;
-                        const uint32_t kind = len == 0u ? 0u : (kKinds >> (2u * op)) & 3u;
+                        const uint32_t kind = kind_of(op, len);
                         has_m = has_m || (in && op == 0u);
-                        if (kind != 0u && !(kind == 1u && prev_kind == 1u)) {     // an entry begins: not both this op and the one before are aligned bases
-                            uint32_t bf;
-                            const uint32_t col = window_col(ref_at, bf);
+                        if (begins_entry(kind, prev_kind)) {
+                            const col_t c = window_col(base, ref_at, n_cols);
                             ++n_runs;
-                            if (n_runs < kWalkEnt) s_ent[n_runs * kWalkReads + j] = make_uint2(col | (kind << 30), (uint32_t)q_at + bf);
+                            if (n_runs < kWalkEnt) s_ent[n_runs * kWalkReads + j] = as_uint2(entry_run(c.col, kind, (uint32_t)q_at + c.before));
                         }
                         if (in) prev_kind = kind;
-                        ref_at += ((kRefOps >> op) & 1u) ? len : 0u;
-                        q_at += ((kQueryOps >> op) & 1u) ? len : 0u;
+                        ref_at += consumes_ref(op) ? len : 0u;
+                        q_at += consumes_query(op) ? len : 0u;
                     }
                     cur = nxt;
                 }
                 if (n_runs + 3u > kWalkEnt && second) n_runs = kRunsDeferred;
                 else {
-                    uint32_t code = n_runs + 3u > kWalkEnt ? 5u : has_m ? 1u : 0u;
-                    if (!code) {
-                        if (q_at > 2u * (so1 - my_so) || q_at > 0x7FFFFFFFull) code = 2u;
-                        else if (q_at > qlen) code = 3u;
-                        else if (ref_at > (uint64_t)kRunMask) code = 4u;
-                    }
-                    uint32_t end_col = 0, bf;
+                    const uint32_t code = n_runs + 3u > kWalkEnt ? 5u : verdict(has_m, q_at, so1 - my_so, qlen, ref_at);
+                    uint32_t end_col = 0;
                     if (code) {      // a malformed record covers nothing (see cigar_runs_kernel)
                         atomicMin(bad, ((unsigned long long)r << 8) | code);
                         n_runs = 0;
-                    } else end_col = window_col(ref_at, bf);
-                    s_ent[(n_runs + 1u) * kWalkReads + j] = make_uint2(end_col | (3u << 30), (uint32_t)q_at);
-                    s_ent[(n_runs + 2u) * kWalkReads + j] = make_uint2(kRunMask | (3u << 30), 0u);
+                    } else end_col = window_col(base, ref_at, n_cols).col;
+                    s_ent[(n_runs + 1u) * kWalkReads + j] = as_uint2(entry_end(end_col, (uint32_t)q_at));
+                    s_ent[(n_runs + 2u) * kWalkReads + j] = as_uint2(entry_never());
                 }
             }
             nruns[r] = n_runs;
@@ -516,49 +513,22 @@ __global__ __launch_bounds__(256) void cigar_walk_kernel(uint64_t n_reads, const
         uint32_t lo = 0, hi = n_ent_all - 1u;
         while (hi - lo > 1u) {
             const uint32_t mid = (lo + hi) >> 1;
-            if ((ent(mid).x & kRunMask) <= X) lo = mid;
+            if (entry_col(ent(mid).x) <= X) lo = mid;
             else hi = mid;
         }
         const uint2 first = ent(lo);
         uint2 e = first;
-        uint32_t q_lo = 0xFFFFFFFFu, q_hi = 0, i = lo;
+        query_range g;
+        uint32_t i = lo;
         for (;;) {
             ++i;
             const uint2 nx = ent(i);
-            if ((e.x >> 30) == 1u) {
-                const uint32_t W = e.x & kRunMask, ca = max(W, X), cbv = min(nx.x & kRunMask, Xend);
-                if (ca < cbv) {
-                    q_lo = min(q_lo, e.y + (ca - W));
-                    q_hi = max(q_hi, e.y + (cbv - W));
-                }
-            }
-            if ((nx.x & kRunMask) > bound) break;      // it begins behind the sweep: the closing entry
+            range_add(g, e, nx, X, Xend);
+            if (entry_col(nx.x) > bound) break;      // it begins behind the sweep: the closing entry
             e = nx;
         }
-        const uint32_t n_ent = i - lo + 1u;      // (< kWalkEnt < kDescMax)
-        uint64_t piece = 0;
-        uint32_t np = 0;
-        int32_t q0 = 0;
-        if (q_lo < q_hi) {
-            const uint32_t al = (uint32_t)my_so & 3u;
-            const uint32_t b_lo = al + (q_lo >> 1), b_hi = al + (q_hi + 1u) / 2u;
-            const uint32_t d_lo = b_lo >> 2;
-            piece = (my_so >> 2) + d_lo;
-            np = min((b_hi + 15u - 4u * d_lo) >> 4, kDescMax);
-            q0 = 2 * ((int32_t)(4u * d_lo) - (int32_t)al);
-        }
-        const uint64_t at = ent0 + lo;
-        uint4 d;
-        d.x = (uint32_t)piece;
-        d.z = (uint32_t)q0;
-        if (n_ent == 2u) {      // ONE entry covers the whole sweep: what it is, and the query offset of the sweep's first column
-            d.y = first.y + (X - (first.x & kRunMask));
-            d.w = (uint32_t)((piece >> 32) & 0xFFu) | ((first.x >> 30) << 8) | (np << 16) | (1u << 24);
-        } else {
-            d.y = (uint32_t)at;
-            d.w = (uint32_t)((piece >> 32) & 0xFFu) | ((uint32_t)((at >> 32) & 0xFFu) << 8) | (np << 16) | (n_ent << 24);
-        }
-        desc[(uint64_t)s * n_reads + r] = d;
+        // (i - lo + 1 entries: < kWalkEnt < kDescMax)
+        desc[(uint64_t)s * n_reads + r] = make_desc(first, ent0 + lo, i - lo + 1u, g, X, my_so);
     }
     // ---- the entries: thread (read, part) writes entries part, part + 4, ...
     uint2 *out = runs + ent0;
@@ -657,9 +627,8 @@ constexpr uint32_t kMinWgs = 4u;      // workgroups a CU must be able to hold: 1
 // pieces whose qualities a thread has asked for ahead of their turn (8 registers each; with all seven ahead one tile a workgroup is
 // 5 us faster, two tiles a workgroup 11 us slower)
 constexpr uint32_t kQualAhead = 3u;
-// a row: a sweep's pieces and one more — its first piece may begin seven bases before the sweep, which leaves room for 25 inserted
-// bases (a read with more of them in a sweep goes to slow_pair)
-constexpr uint32_t kRowPieces = (kSweep + 31u) / 32u + 1u, kRowDw = 4u * kRowPieces, kGroupPadDw = 8u;
+// a row: kRowPieces pieces (above, with the descriptor)
+constexpr uint32_t kRowDw = 4u * kRowPieces, kGroupPadDw = 8u;
 // The kernel comes in two sizes of its entry area (entries of the reads that need them, 4 bytes each in LDS: column - sweep's first
 // (0..256: 9 bits) | kind << 9 | (query offset there - the row's first) << 11): four entries a read on average — a CCS read has 4
 // in a sweep with an indel — with five workgroups to a CU, and sixteen, with three: for the (tile, sweep) units whose reads have
@@ -689,6 +658,48 @@ static_assert(kTileReads % 64u == 0 && kThreads == 2u * kTileReads && kBlocks <=
 // the pieces of a tile: the upper half of the threads take kPieceRoundsB rounds of kTileReads pieces, the read threads — who have
 // their rows of the table to make as well — the rest
 constexpr uint32_t kPieceRoundsA = kRowPieces >= 8u ? 2u : 1u, kPieceRoundsB = kRowPieces - kPieceRoundsA;
+
+// All the LDS of a planes workgroup: declared once, in ingest_planes_kernel, and handed down.
+template <uint32_t EPR>
+struct planes_lds {
+    using shape = planes_shape<EPR>;
+    __attribute__((aligned(16))) uint32_t stage[shape::kStageDw];
+    __attribute__((aligned(16))) uint16_t tab[kTabSize];
+    uint32_t ent[shape::kEntCap];          // the entries of the reads with several in the sweep, a half per read wave
+    uint8_t own[shape::kEntCap];           // whose: the read | 0x80 for its last one
+    uint32_t nent[2u * kReadWaves];        // entries in each part; [kReadWaves + w]: wave w hands the unit on
+    uint32_t nslow;                        // reads left to slow_pair
+    uint8_t slow[kTileReads];
+};
+static_assert(kTileReads <= 128u, "a read of the tile and a flag in a byte");
+
+// block -> (read tile, sweep).  Blocks b, b + 8, b + 16, ... are dealt to the same XCD one after the other; an XCD takes
+// whole groups of 1024 reads (group = xcd, xcd + 8, ...), and of a group all sweeps in turn, the tiles of the group
+// innermost.  So (a) the tiles that share the 128-byte lines of a sweep's planes meet in one L2, and (b) what the
+// sweeps of a group read again — the reads' entries, the 128-byte lines of packed bases that straddle two sweeps — is
+// in that L2 when the next sweep asks for it.
+struct unit_place {
+    uint32_t xcd, group, tile, sweep;
+    uint32_t X, width;       // the sweep's first column, its columns (the window's last sweep: fewer than kSweep)
+    uint64_t r0;             // the tile's first read
+    bool in_range;           // false: a group past the window's (the grid is whole rounds of the eight XCDs)
+};
+__device__ __forceinline__ unit_place place_of(const ingest_args &a, uint32_t b)
+{
+    unit_place p;
+    const uint32_t jb = b >> 3, sub = jb % kSubTiles, qq = jb / kSubTiles;
+    p.xcd = b & 7u;
+    p.group = p.xcd + 8u * (qq / a.n_sweeps);
+    p.sweep = qq % a.n_sweeps;
+    p.in_range = p.group < a.n_groups;
+    p.tile = kSubTiles * p.group + sub;
+    p.X = p.sweep * kSweep;
+    p.width = min(a.n_cols, p.X + kSweep) - p.X;
+    p.r0 = (uint64_t)p.tile * kTileReads;
+    return p;
+}
+// the descriptors of the unit's sweep, by read
+__device__ __forceinline__ const uint4 *descs_of(const ingest_args &a, const unit_place &pl) { return a.desc + (uint64_t)pl.sweep * a.n_reads; }
 
 
 // Eight of BAM's 4-bit bases, one per nibble -> eight symbol codes: A C G T (1 2 4 8) -> 0..3, everything else (N = 15, '=' = 0, the
@@ -774,6 +785,16 @@ __device__ __forceinline__ void piece_bases(const ingest_args &a, const u32x4 &v
     if (QV == kQvMask) mask_flagged(fl, S);
 }
 
+// An entry in LDS, 4 bytes: column - sweep's first (0..256: 9 bits) | kind << 9 | (query offset there - the row's first) << 11.
+// From entry {x, y} of runs[], for the sweep that begins at column X and whose row begins at query offset q0:
+__device__ __forceinline__ uint32_t ent_make(uint32_t x, uint32_t y, uint32_t X, int32_t q0)
+{
+    const uint32_t W = entry_col(x), kind = entry_kind(x);
+    const uint32_t wr = W <= X ? 0u : min(W - X, 256u);
+    const uint32_t yq = y + (W < X ? X - W : 0u);      // query offset at the sweep's first column of the entry
+    const uint32_t yr = (kind == kAligned && wr < 256u) ? (yq - (uint32_t)q0) & 0x1FFFu : 0u;
+    return wr | (kind << 9) | (yr << 11);
+}
 __device__ __forceinline__ uint32_t ent_col(uint32_t e) { return e & 511u; }
 __device__ __forceinline__ uint32_t ent_kind(uint32_t e) { return (e >> 9) & 3u; }
 // staging nibble address of column c (relative to the sweep's first) in entry e of a read whose row begins at nibble row8
@@ -798,15 +819,15 @@ __device__ __forceinline__ void slow_pair(const ingest_args &a, uint64_t r, uint
         uint32_t lo = 0, hi = ne - 1u;   // the last entry that begins at or before c (entry 0 does, the last one never)
         while (hi - lo > 1u) {
             const uint32_t mid = (lo + hi) >> 1;
-            if ((int)(runs[mid].x & kRunMask) <= c) lo = mid;
+            if ((int)entry_col(runs[mid].x) <= c) lo = mid;
             else hi = mid;
         }
         const uint2 e = runs[lo];
-        const uint32_t kind = e.x >> 30;
+        const uint32_t kind = entry_kind(e.x);
         uint32_t sym = 6u;
-        if (kind == 2u) sym = 4u;
-        else if (kind == 1u) {
-            const uint64_t q = (uint64_t)e.y + (uint64_t)(c - (int)(e.x & kRunMask));
+        if (kind == kDeletion) sym = 4u;
+        else if (kind == kAligned) {
+            const uint64_t q = (uint64_t)e.y + (uint64_t)(c - (int)entry_col(e.x));
             const uint32_t by = a.seq4[so + (q >> 1)];
             const uint32_t b16 = (q & 1u) ? (by & 15u) : (by >> 4);
             sym = (uint32_t)((0x5555555355525105ull >> (4u * b16)) & 15ull);   // A=1 C=2 G=4 T=8 -> 0..3, else 5
@@ -842,105 +863,361 @@ __device__ __forceinline__ void slow_pair(const ingest_args &a, uint64_t r, uint
 // DEFER (the first size, several sibling tiles a workgroup: ingest_planes_kernel): the unit's plane words are handed back in `keep`
 // instead of being stored — returns whether the unit made any (false: outside the window's groups, or handed on) — and a read
 // the workgroup has no room for hands the unit on instead of going through slow_pair (whose bit flips need the stores done).
-template <uint32_t QV, uint32_t EPR, bool BIG, bool DEFER = false>
-__device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t b, uint32_t (&keep)[8][3])
+// ---- pieces.  The pieces p0, p0 + 128, ... (K of them) of the tile's 128 x kRowPieces: the descriptors of their reads, then the
+// pieces, all of a thread's requests in flight together; a piece that is not there (the read has fewer) asks for the read's first
+// one again — the same number of requests in every lane, so that a wait for something asked earlier does not wait for these.
+struct piece_t { u32x4 v; uint32_t dst; int32_t Q; uint64_t qb; uint32_t fl; };    // dst: dword in the staging area, 0 = none; fl: the piece's 32 flags (kQvMask)
+// (every load is asked for whatever the read's number — a read past the last asks for the first one's, and is set to nothing
+// afterwards: loads inside a branch made the compiler wait for each before it asked for the next)
+template <uint32_t QV>
+__device__ __forceinline__ void ask_descs(const ingest_args &a, const unit_place &pl, uint32_t p0, uint32_t K, uint4 (&d)[kPieceRoundsB], uint64_t (&qo)[kPieceRoundsB])
+{
+    const uint4 *desc = descs_of(a, pl);
+    bool in[kPieceRoundsB];
+#pragma unroll
+    for (uint32_t k = 0; k < kPieceRoundsB; ++k) {
+        if (k >= K) break;
+        const uint32_t j = (p0 + kTileReads * k) / kRowPieces;
+        in[k] = pl.r0 + j < a.n_reads;
+        const uint64_t at = in[k] ? pl.r0 + j : 0u;
+        d[k] = desc[at];
+        qo[k] = QV == kQvBytes ? a.qual_off[at] : 0u;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < kPieceRoundsB; ++k) {
+        if (k >= K) break;
+        if (!in[k]) {
+            d[k] = make_uint4(0, 0, 0, 0);
+            qo[k] = 0;
+        }
+    }
+}
+template <uint32_t QV, uint32_t EPR>
+__device__ __forceinline__ void ask_pieces(const ingest_args &a, uint32_t p0, uint32_t K, const uint4 (&d)[kPieceRoundsB], const uint64_t (&qo)[kPieceRoundsB], piece_t (&pc)[kPieceRoundsB])
+{
+    typedef uint32_t u32a1 __attribute__((aligned(1)));
+#pragma unroll
+    for (uint32_t k = 0; k < kPieceRoundsB; ++k) {
+        if (k >= K) break;
+        const uint32_t p = p0 + kTileReads * k, j = p / kRowPieces, i = p - kRowPieces * j;
+        const uint32_t np = desc_slow(d[k]) ? 0u : desc_pieces(d[k]);      // (slow_pair's: none)
+        const uint64_t at = desc_piece_dw(d[k]) + (i < np ? 4u * i : 0u);     // (in dwords)
+        // (plain loads: neighbouring lanes' pieces share lines, and so do the sweeps of a read)
+        pc[k].v = *reinterpret_cast<const u32x4a4 *>(a.seq4 + 4u * at);
+        // (kQvMask: the piece begins at byte 4 at of the bases = bit 8 at of the mask, its 32 flags are the four bytes from byte
+        // `at` on — one register a piece, asked for WITH the piece: all of a thread's requests are out before the first is used)
+        if (QV == kQvMask) pc[k].fl = *reinterpret_cast<const u32a1 *>(a.qmask + at);
+        pc[k].dst = i < np ? planes_shape<EPR>::row_dw(j) + 4u * i : 0u;
+        pc[k].Q = desc_q0(d[k]) + (i < np ? 32 * (int32_t)i : 0);      // (a piece that is not there: its read's first one's qualities)
+        pc[k].qb = qo[k];
+    }
+}
+// (QV: a piece's qualities are asked for kQualAhead pieces ahead of its turn, outside any branch — the loads of a piece that is
+// not there ask for its read's first piece's again.  Asked for inside the piece's own turn, as round 5 had it, every piece
+// of a thread waited for its own trip to HBM, seven in a row: 184 us against 111 without qualities.)
+template <uint32_t QV, uint32_t EPR>
+__device__ __forceinline__ void stage_pieces(const ingest_args &a, planes_lds<EPR> &lds, uint32_t K, const piece_t (&pc)[kPieceRoundsB])
+{
+    piece_quals pq[kPieceRoundsB];
+    if (QV == kQvBytes) {
+#pragma unroll
+        for (uint32_t k = 0; k < kPieceRoundsB; ++k)
+            if (k < K && k < kQualAhead) pq[k] = ask_quals(a, pc[k].Q, pc[k].qb);
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < kPieceRoundsB; ++k) {
+        if (k >= K) break;
+        if (QV == kQvBytes && k + kQualAhead < K && k + kQualAhead < kPieceRoundsB) pq[k + kQualAhead] = ask_quals(a, pc[k + kQualAhead].Q, pc[k + kQualAhead].qb);
+        if (pc[k].dst) {
+            uint32_t S[4];
+            piece_bases<QV>(a, pc[k].v, pq[k], pc[k].fl, S);
+            u32x4 o = {S[0], S[1], S[2], S[3]};
+            *reinterpret_cast<u32x4 *>(&lds.stage[pc[k].dst]) = o;
+        }
+    }
+}
+
+// ---- the stages of a unit (planes_unit below), in their order.  `tid` is the unit's own copy of the thread's number (planes_unit).
+// pieces_stage — waves 2, 3, before the first barrier.  Reads the descriptors and the packed bases (qualities, flags) of the
+// pieces tid - 128, + 128, ... (kPieceRoundsB rounds: 7 of 9); writes their codes, in query order, to lds.stage's rows.  Needs
+// nothing of the workgroup to be complete: what it asks HBM for depends on no other thread.
+template <uint32_t QV, uint32_t EPR>
+__device__ __forceinline__ void pieces_stage(const ingest_args &a, const unit_place &pl, planes_lds<EPR> &lds, uint32_t tid)
+{
+    uint4 d[kPieceRoundsB];
+    uint64_t qo[kPieceRoundsB];
+    piece_t pc[kPieceRoundsB];
+    const uint32_t p0 = tid - kTileReads;
+    ask_descs<QV>(a, pl, p0, kPieceRoundsB, d, qo);
+    ask_pieces<QV, EPR>(a, p0, kPieceRoundsB, d, qo, pc);
+    stage_pieces<QV, EPR>(a, lds, kPieceRoundsB, pc);
+}
+
+// the table row of a read whose sweep ONE entry covers (or nothing the workgroup takes: kind 3): its blocks' addresses rise by
+// eight codes a block (aligned bases, from nibble a0) or stay (the dword of '-', of 'not covered'), four blocks a store
+template <uint32_t EPR>
+__device__ __forceinline__ void table_row_of_one_entry(planes_lds<EPR> &lds, uint32_t tid, uint32_t kind, uint32_t first_nibble)
+{
+    const uint32_t a0 = kind == kAligned ? first_nibble : kind == kDeletion ? 16u : 0u, st = kind == kAligned ? 8u : 0u;
+    uint32_t lo = a0 | ((a0 + st) << 16), hi = lo + 2u * (st | st << 16);
+    const uint32_t step = 4u * (st | st << 16);
+#pragma unroll
+    for (uint32_t k = 0; k < kBlocks / 4u; ++k) {
+        *reinterpret_cast<uint2 *>(lds.tab + tab_at(tid, 4u * k)) = make_uint2(lo, hi);
+        lo += step;
+        hi += step;
+    }
+}
+
+// read_stage — waves 0, 1, a thread per read, before the first barrier.  Reads the read's descriptor, the sweep's entries of the
+// read from runs[] and the other kPieceRoundsA rounds of pieces; writes the constant dwords in front of lds.stage, the counters
+// (lds.nent, lds.nslow: zero before anybody adds), the read's row of lds.tab when one entry covers the sweep, otherwise its entries
+// and their owners to its wave's part of lds.ent / lds.own, and its pieces' codes to lds.stage.  Needs nothing complete on entry
+// (the barrier between units has passed).  Returns whether the read is left to slow_pair; a wave that hands the unit on says so in
+// lds.nent[kReadWaves + wave].
+template <uint32_t QV, uint32_t EPR, bool BIG, bool DEFER>
+__device__ __forceinline__ bool read_stage(const ingest_args &a, const unit_place &pl, planes_lds<EPR> &lds, uint32_t tid)
 {
     using shape = planes_shape<EPR>;
-    constexpr uint32_t kEntCap = shape::kEntCap, kEntCapWave = shape::kEntCapWave, kRowBase = shape::kRowBase, kStageDw = shape::kStageDw;
-    __shared__ __attribute__((aligned(16))) uint32_t s_stage[kStageDw];
-    __shared__ __attribute__((aligned(16))) uint16_t s_tab[kTabSize];
-    __shared__ uint32_t s_ent[kEntCap];           // the entries of the reads with several in the sweep, a half per read wave
-    __shared__ uint8_t s_own[kEntCap];            // whose: the read | 0x80 for its last one
-    static_assert(kTileReads <= 128u, "a read of the tile and a flag in a byte");
-    __shared__ uint32_t s_nent[2u * kReadWaves];  // entries in each part; [kReadWaves + w]: wave w hands the unit on
-    __shared__ uint32_t s_nslow;                  // reads left to slow_pair
-    __shared__ uint8_t s_slow[kTileReads];
+    typedef uint32_t u32x4a8 __attribute__((ext_vector_type(4), aligned(8)));
+    const uint32_t wid = tid >> 6, lane = tid & 63u;
+    uint4 dp[kPieceRoundsB];
+    uint64_t qo[kPieceRoundsB];
+    piece_t pc[kPieceRoundsB];
+    const uint32_t p0 = kTileReads * kPieceRoundsB + tid;
+    const uint64_t r = pl.r0 + tid;
+    uint4 d = desc_of_no_read();
+    if (r < a.n_reads) d = descs_of(a, pl)[r];
+    ask_descs<QV>(a, pl, p0, kPieceRoundsA, dp, qo);
+    if (tid < 4u) lds.stage[tid] = tid < 2u ? 0x66666666u : 0x44444444u;
+    if (tid == 4u) lds.nslow = 0;
+    if (lane == 0) lds.nent[wid] = 0, lds.nent[kReadWaves + wid] = 0;
+    uint32_t n_ent = desc_entries(d);
+    bool slow = desc_slow(d);
+    const bool simple = desc_simple(d);
+    if (simple || slow) n_ent = 0;
+    // exclusive scan of the entries over the wave: each read wave has its own half of the entry area
+    const uint32_t inc = wave_scan(n_ent);
+    uint32_t off_e = inc - n_ent;
+    if (n_ent && off_e + n_ent > shape::kEntCapWave) {
+        // more entries than the wave's part holds: the first size hands the whole unit on to the second (nothing of it is
+        // written here, and no read of it goes to the slow list: the second size lists its own); the second leaves the
+        // reads past the part's end to slow_pair
+        if (!BIG) lds.nent[kReadWaves + wid] = 1u;
+        else slow = true;
+        n_ent = 0;
+    }
+    if (DEFER && slow) {
+        lds.nent[kReadWaves + wid] = 1u;
+        slow = false;
+    }
+    off_e += wid * shape::kEntCapWave;
+    // the sweep's entries of this read: the first eight in four 16-byte requests that go out together (entries past the
+    // read's own belong to the next read or to the array's slack) — two deletions in a sweep are six entries, and a
+    // wave in which ONE read needs a ninth makes another trip for it
+    const uint2 *src = a.runs + (n_ent ? desc_entry_idx(d) : 0u);
+    u32x4a8 e01 = {0, 0, 0, 0}, e23 = e01, e45 = e01, e67 = e01;
+    if (n_ent) {
+        e01 = *reinterpret_cast<const u32x4a8 *>(src);
+        e23 = *reinterpret_cast<const u32x4a8 *>(src + 2);
+    }
+    if (n_ent > 4u) {
+        e45 = *reinterpret_cast<const u32x4a8 *>(src + 4);
+        e67 = *reinterpret_cast<const u32x4a8 *>(src + 6);
+    }
+    ask_pieces<QV, EPR>(a, p0, kPieceRoundsA, dp, qo, pc);
+    const int32_t q0 = desc_q0(d);
+    if (!n_ent) table_row_of_one_entry(lds, tid, (simple && !slow) ? desc_simple_kind(d) : kNothing, 8u * shape::row_dw(tid) + (desc_simple_q(d) - (uint32_t)q0));
+    // several entries: -> LDS, four bytes each, with their owner; everybody makes table rows of them behind the barrier
+    if (n_ent) {
+        const uint32_t X = pl.X;
+        const uint32_t e8[8] = {ent_make(e01.x, e01.y, X, q0), ent_make(e01.z, e01.w, X, q0), ent_make(e23.x, e23.y, X, q0), ent_make(e23.z, e23.w, X, q0),
+                                ent_make(e45.x, e45.y, X, q0), ent_make(e45.z, e45.w, X, q0), ent_make(e67.x, e67.y, X, q0), ent_make(e67.z, e67.w, X, q0)};
+        uint32_t *ent = lds.ent + off_e;
+        uint8_t *own = lds.own + off_e;
+#pragma unroll
+        for (uint32_t i = 0; i < 8u; ++i)
+            if (i < n_ent) {
+                ent[i] = e8[i];
+                own[i] = (uint8_t)(tid | (i + 1u == n_ent ? 0x80u : 0u));
+            }
+        for (uint32_t i = 8; i < n_ent; ++i) {
+            const uint2 g = src[i];
+            ent[i] = ent_make(g.x, g.y, X, q0);
+            own[i] = (uint8_t)(tid | (i + 1u == n_ent ? 0x80u : 0u));
+        }
+        atomicMax(&lds.nent[wid], off_e - wid * shape::kEntCapWave + n_ent);
+    }
+    stage_pieces<QV, EPR>(a, lds, kPieceRoundsA, pc);
+    return slow;
+}
+
+// table_stage — everybody, between the two barriers: a thread an entry.  Reads lds.nent, lds.ent, lds.own and, for the boundary
+// blocks, the codes in lds.stage's rows; writes the table rows of the reads with several entries and the side dwords
+// lds.stage[4 + slot].  Needs read_stage and pieces_stage complete in every wave: behind the first barrier.
+// Entry i of a read covers the columns [its column, the next entry's column) and the read's last one only ends the one before
+// it: the blocks that lie WHOLLY inside are the entry's — addresses that rise by eight codes a block, or the dword of '-' /
+// of 'not covered' — and every block is wholly inside one entry or has an entry that begins inside it; those are put
+// together, by the thread of the first such entry, in that entry's side dword.  No list, no search, no loop per block.
+// (a) the whole blocks [bf, be) of entry e of read `own`, from nibble address av on: singly up to a multiple of four, four a store, singly again
+template <uint32_t EPR>
+__device__ __forceinline__ void table_whole_blocks(planes_lds<EPR> &lds, uint32_t own, uint32_t e, uint32_t bf, uint32_t be)
+{
+    const uint32_t st = ent_kind(e) == 1u ? 8u : 0u;
+    uint32_t av = ent_addr(e, 8u * planes_shape<EPR>::row_dw(own), 8u * bf);
+#pragma unroll
+    for (uint32_t k = 0; k < 3u; ++k)
+        if ((bf & 3u) && bf < be) {
+            lds.tab[tab_at(own, bf)] = (uint16_t)av;
+            av += st;
+            ++bf;
+        }
+    uint32_t p01 = av | ((av + st) << 16);
+    const uint32_t p_st = st | st << 16;
+    for (; bf + 4u <= be; bf += 4u) {
+        *reinterpret_cast<uint2 *>(lds.tab + tab_at(own, bf)) = make_uint2(p01, p01 + 2u * p_st);
+        p01 += 4u * p_st;
+    }
+    av = p01 & 0xFFFFu;
+#pragma unroll
+    for (uint32_t k = 0; k < 3u; ++k)
+        if (bf < be) {
+            lds.tab[tab_at(own, bf)] = (uint16_t)av;
+            av += st;
+            ++bf;
+        }
+}
+// (b) the block bb that the entry at `slot` begins inside, put together from the entries around it: the one before (an entry
+// that begins inside a block is not its read's first) up to the first that ends behind the block
+template <uint32_t EPR>
+__device__ __forceinline__ void table_boundary_block(planes_lds<EPR> &lds, uint32_t slot, uint32_t own, uint32_t bb)
+{
+    const uint32_t row8 = 8u * planes_shape<EPR>::row_dw(own);
+    uint32_t ee = lds.ent[slot - 1u];
+    const uint32_t c0 = 8u * bb, c1 = c0 + 8u;
+    uint32_t bases = 0, m_al = 0, m_del = 0;      // the block's aligned bases (BAM's codes), where they are, where a deletion is
+    for (uint32_t kk = slot;; ++kk) {
+        const uint32_t nn = lds.ent[kk];
+        const uint32_t W = ent_col(ee), Wn = ent_col(nn);
+        const uint32_t ca = max(W, c0), cb = min(Wn, c1);
+        const uint32_t kind = ent_kind(ee);
+        if (ca < cb && kind != 3u) {
+            const uint32_t m = (cb - ca == 8u ? 0xFFFFFFFFu : ((1u << (4u * (cb - ca))) - 1u)) << (4u * (ca - c0));
+            if (kind == 1u) {
+                const uint32_t A = ent_addr(ee, row8, ca);
+                bases |= (__builtin_amdgcn_alignbit(lds.stage[(A >> 3) + 1u], lds.stage[A >> 3], 4u * (A & 7u)) << (4u * (ca - c0))) & m;
+                m_al |= m;
+            } else m_del |= m;
+        }
+        if (Wn >= c1 || (lds.own[kk] & 0x80u)) break;     // (the read's last entry is nothing: 'not covered' stays)
+        ee = nn;
+    }
+    const uint32_t R = (codes_of_bases8(bases) & m_al) | (0x44444444u & m_del) | (0x66666666u & ~(m_al | m_del));
+    lds.stage[4u + slot] = R;
+    lds.tab[tab_at(own, bb)] = (uint16_t)(8u * (4u + slot));
+}
+template <uint32_t EPR>
+__device__ __forceinline__ void table_stage(planes_lds<EPR> &lds, uint32_t width, uint32_t tid)
+{
+    constexpr uint32_t kEntCapWave = planes_shape<EPR>::kEntCapWave;
+    uint32_t n_e = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kReadWaves; ++w) n_e += lds.nent[w];
+    for (uint32_t si = tid; si < n_e; si += kThreads) {
+        uint32_t slot = 0, rem = si;      // the si-th entry of the parts one behind the other
+        bool found = false;
+#pragma unroll
+        for (uint32_t w = 0; w < kReadWaves; ++w) {
+            const uint32_t nw = lds.nent[w];
+            if (!found && rem < nw) {
+                slot = w * kEntCapWave + rem;
+                found = true;
+            }
+            if (!found) rem -= nw;
+        }
+        const uint32_t own = lds.own[slot], e = lds.ent[slot], nx = lds.ent[slot + 1u];
+        const uint32_t wr = ent_col(e);
+        if ((own & 0x80u) || wr >= width) continue;
+        const uint32_t wn = ent_col(nx);
+        const uint32_t be = wn >= width ? kBlocks : wn >> 3, bf = (wr + 7u) >> 3;
+        if (bf < be) table_whole_blocks(lds, own, e, bf, be);
+        // ... the block it begins inside, if it is the first entry to do so
+        if (!(wr & 7u)) continue;
+        if (ent_col(lds.ent[slot - 1u]) > 8u * (wr >> 3)) continue;
+        table_boundary_block(lds, slot, own, wr >> 3);
+    }
+}
+
+// gather_stage — behind the second barrier: the table and the staging area are complete.  GATHER AT THE TRANSPOSE: thread = 32
+// reads x 8 columns (group G = tid % kTileGroups of the tile's reads, block tid / kTileGroups); reads lds.tab and lds.stage only,
+// writes out[j][k] = the dword of plane k of the block's column j.  Returns whether the thread has a block of the sweep (false: `out`
+// is not written).
+template <uint32_t EPR>
+__device__ __forceinline__ bool gather_stage(const planes_lds<EPR> &lds, uint32_t width, uint32_t tid, uint32_t (&out)[8][3])
+{
+    const uint32_t G = tid % kTileGroups, blk = tid / kTileGroups;
+    if (!(blk < kBlocks && 8u * blk < width)) return false;
+    // (the dwords in front of the reads' rows — 'not covered', '-', the boundary blocks — hold symbol codes already; `codes`
+    // collects, a bit a read, whose dword is one of those: v_alignbit shifts the sign of address - first row in)
+    uint32_t R[32], codes = 0;
+    // (the block's place in the rows of the reads i, i + 8, ...: eight offsets)
+    uint32_t at[8];
+#pragma unroll
+    for (uint32_t i = 0; i < 8u; ++i) at[i] = tab_at(32u * G + i, blk);
+#pragma unroll
+    for (int i = 31; i >= 0; --i) {
+        const uint32_t A = lds.tab[at[i & 7] + (uint32_t)(i & ~7) * kTabRow];
+        R[i] = __builtin_amdgcn_alignbit(lds.stage[(A >> 3) + 1u], lds.stage[A >> 3], 4u * (A & 7u));
+        codes = __builtin_amdgcn_alignbit(codes, A - 8u * planes_shape<EPR>::kRowBase, 31u);
+    }
+    nibble_rows_to_plane_words(R, codes, out);
+    return true;
+}
+
+// The plane words of a block of eight columns -> the matrix: words[j][k] to row + (3 j + k) * stride, the first columns_valid (> 0)
+// columns of the block.  A block of eight whole columns — all but the window's last — stores without a question per column (a
+// predicate per store was a sixth of the single tile's store phase); the ragged one, the window's last, goes column by column.
+__device__ __forceinline__ void store_block_words(uint8_t *row, uint64_t stride, const uint32_t (&words)[8][3], uint32_t columns_valid)
+{
+    if (columns_valid >= 8u) {
+#pragma unroll
+        for (uint32_t jj = 0; jj < 8u; ++jj)
+#pragma unroll
+            for (uint32_t k = 0; k < 3u; ++k) {
+                *reinterpret_cast<uint32_t *>(row) = words[jj][k];
+                row += stride;
+            }
+    } else {
+        // (a loop over the columns there are, the word picked by comparisons: stores under a predicate each, unrolled, had the
+        // compiler merge them behind a computed address — the words went to scratch)
+        for (uint32_t jj = 0; jj < columns_valid; ++jj)
+            for (uint32_t k = 0; k < 3u; ++k) {
+                *reinterpret_cast<uint32_t *>(row) = jj == 0u ? words[0][k] : jj == 1u ? words[1][k] : jj == 2u ? words[2][k] : jj == 3u ? words[3][k] : jj == 4u ? words[4][k] : jj == 5u ? words[5][k] : words[6][k];
+                row += stride;
+            }
+    }
+}
+
+// A workgroup = 128 reads x one sweep, four waves with two jobs.  Nothing a thread asks HBM for depends on another thread: every
+// thread reads the descriptors of the reads whose pieces it takes itself (neighbouring lanes share them), so the two trips —
+// descriptor, then pieces / entries — are the only waits before the first barrier, and there are two barriers in all (a third in
+// front of the slow tail).
+// (Device stamps of the form before this one — the read waves made the table while the others waited, then everybody staged:
+// descriptor 0.75 us, prologue 0.9, table 4.7 of which 1.5 a third trip for the reads with more than four entries, staging 1.8,
+// general 1.1, transposing 2.6; waves 2, 3 waited 5.2 us of 14.6 at the first barrier.)
+// The unit's plane words come back in `out` (the thread's block of eight columns: gather_stage).  Returns whether the unit made
+// any — false: outside the window's groups, or handed on to the second size (BIG: never); the same in every thread of the workgroup.
+// DEFER (the first size, several sibling tiles a workgroup: ingest_planes_kernel): the words are NOT stored here, and a read the
+// workgroup has no room for hands the unit on instead of going through slow_pair (whose bit flips need the stores done).
+template <uint32_t QV, uint32_t EPR, bool BIG, bool DEFER = false>
+__device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t b, planes_lds<EPR> &lds, uint32_t (&out)[8][3])
+{
     uint32_t tid_ = threadIdx.x;
     if (DEFER) asm volatile("" : "+v"(tid_));      // (the units of a workgroup run in a loop: what follows from the thread's number is not to be
                                                    // kept in registers across it — hoisted, it was 110 of them)
-    const uint32_t tid = tid_, wid = tid >> 6, lane = tid & 63u;
-    // block -> (read tile, sweep).  Blocks b, b + 8, b + 16, ... are dealt to the same XCD one after the other; an XCD takes
-    // whole groups of 1024 reads (group = xcd, xcd + 8, ...), and of a group all sweeps in turn, the tiles of the group
-    // innermost.  So (a) the tiles that share the 128-byte lines of a sweep's planes meet in one L2, and (b) what the
-    // sweeps of a group read again — the reads' entries, the 128-byte lines of packed bases that straddle two sweeps — is
-    // in that L2 when the next sweep asks for it.
-    const uint32_t xcd = b & 7u, jb = b >> 3, sub = jb % kSubTiles, qq = jb / kSubTiles;
-    const uint32_t group = xcd + 8u * (qq / a.n_sweeps), sweep = qq % a.n_sweeps;
-    if (group >= a.n_groups) return false;
-    const uint32_t tile = kSubTiles * group + sub;
-    const uint32_t X = sweep * kSweep, Xend = min(a.n_cols, X + kSweep), width = Xend - X;
-    const uint4 *desc = a.desc + (uint64_t)sweep * a.n_reads;
-    const uint64_t r0 = (uint64_t)tile * kTileReads;
-
-    // the pieces p0, p0 + 128, ... (K of them): the descriptors of their reads, then the pieces, all of a thread's requests in
-    // flight together; a piece that is not there (the read has fewer) asks for the read's first one again — the same number of
-    // requests in every lane, so that a wait for something asked earlier does not wait for these
-    struct piece_t { u32x4 v; uint32_t dst; int32_t Q; uint64_t qb; uint32_t fl; };    // dst: dword in the staging area, 0 = none; fl: the piece's 32 flags (kQvMask)
-    // (every load is asked for whatever the read's number — a read past the last asks for the first one's, and is set to nothing
-    // afterwards: loads inside a branch made the compiler wait for each before it asked for the next)
-    auto ask_descs = [&](uint32_t p0, uint32_t K, uint4 (&d)[kPieceRoundsB], uint64_t (&qo)[kPieceRoundsB]) {
-        bool in[kPieceRoundsB];
-#pragma unroll
-        for (uint32_t k = 0; k < kPieceRoundsB; ++k) {
-            if (k >= K) break;
-            const uint32_t j = (p0 + kTileReads * k) / kRowPieces;
-            in[k] = r0 + j < a.n_reads;
-            const uint64_t at = in[k] ? r0 + j : 0u;
-            d[k] = desc[at];
-            qo[k] = QV == kQvBytes ? a.qual_off[at] : 0u;
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < kPieceRoundsB; ++k) {
-            if (k >= K) break;
-            if (!in[k]) {
-                d[k] = make_uint4(0, 0, 0, 0);
-                qo[k] = 0;
-            }
-        }
-    };
-    typedef uint32_t u32a1 __attribute__((aligned(1)));
-    auto ask_pieces = [&](uint32_t p0, uint32_t K, const uint4 (&d)[kPieceRoundsB], const uint64_t (&qo)[kPieceRoundsB], piece_t (&pc)[kPieceRoundsB]) {
-#pragma unroll
-        for (uint32_t k = 0; k < kPieceRoundsB; ++k) {
-            if (k >= K) break;
-            const uint32_t p = p0 + kTileReads * k, j = p / kRowPieces, i = p - kRowPieces * j;
-            uint32_t np = (d[k].w >> 16) & 0xFFu;
-            if (np > kRowPieces || (d[k].w >> 24) == kDescMax) np = 0;      // (slow_pair's)
-            const uint64_t at = ((((uint64_t)d[k].w & 0xFFu) << 32) | d[k].x) + (i < np ? 4u * i : 0u);     // (in dwords)
-            // (plain loads: neighbouring lanes' pieces share lines, and so do the sweeps of a read)
-            pc[k].v = *reinterpret_cast<const u32x4a4 *>(a.seq4 + 4u * at);
-            // (kQvMask: the piece begins at byte 4 at of the bases = bit 8 at of the mask, its 32 flags are the four bytes from byte
-            // `at` on — one register a piece, asked for WITH the piece: all of a thread's requests are out before the first is used)
-            if (QV == kQvMask) pc[k].fl = *reinterpret_cast<const u32a1 *>(a.qmask + at);
-            pc[k].dst = i < np ? shape::row_dw(j) + 4u * i : 0u;
-            pc[k].Q = (int32_t)d[k].z + (i < np ? 32 * (int32_t)i : 0);      // (a piece that is not there: its read's first one's qualities)
-            pc[k].qb = qo[k];
-        }
-    };
-    // (QV: a piece's qualities are asked for kQualAhead pieces ahead of its turn, outside any branch — the loads of a piece that is
-    // not there ask for its read's first piece's again.  Asked for inside the piece's own turn, as round 5 had it, every piece
-    // of a thread waited for its own trip to HBM, seven in a row: 184 us against 111 without qualities.)
-    auto stage_pieces = [&](uint32_t K, const piece_t (&pc)[kPieceRoundsB]) {
-        piece_quals pq[kPieceRoundsB];
-        if (QV == kQvBytes) {
-#pragma unroll
-            for (uint32_t k = 0; k < kPieceRoundsB; ++k)
-                if (k < K && k < kQualAhead) pq[k] = ask_quals(a, pc[k].Q, pc[k].qb);
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < kPieceRoundsB; ++k) {
-            if (k >= K) break;
-            if (QV == kQvBytes && k + kQualAhead < K && k + kQualAhead < kPieceRoundsB) pq[k + kQualAhead] = ask_quals(a, pc[k + kQualAhead].Q, pc[k + kQualAhead].qb);
-            if (pc[k].dst) {
-                uint32_t S[4];
-                piece_bases<QV>(a, pc[k].v, pq[k], pc[k].fl, S);
-                u32x4 o = {S[0], S[1], S[2], S[3]};
-                *reinterpret_cast<u32x4 *>(&s_stage[pc[k].dst]) = o;
-            }
-        }
-    };
-
-    bool slow_read = false;
+    const uint32_t tid = tid_;
+    const unit_place pl = place_of(a, b);
+    if (!pl.in_range) return false;
     // WITHOUT QUALITIES a wave that still has its requests to HBM to make and its rows to stage goes before the waves that transpose
     // (s_setprio: the CU's arbiter picks by it among the waves ready to issue).  Without it the transposing waves of the CU's other
     // workgroups — three quarters of all instructions — hold up the few instructions that put the next tile's loads in flight: the
@@ -951,261 +1228,37 @@ __device__ __forceinline__ bool planes_unit(const ingest_args &a, const uint32_t
     // raised for the transposing instead: 116 / 176.)
     constexpr bool kPrio = QV == kQvNone;
     if (kPrio) __builtin_amdgcn_s_setprio(3);
-    if (tid >= kTileReads) {
-        // ---- waves 2, 3: pieces
-        uint4 d[kPieceRoundsB];
-        uint64_t qo[kPieceRoundsB];
-        piece_t pc[kPieceRoundsB];
-        const uint32_t p0 = tid - kTileReads;
-        ask_descs(p0, kPieceRoundsB, d, qo);
-        ask_pieces(p0, kPieceRoundsB, d, qo, pc);
-        stage_pieces(kPieceRoundsB, pc);
-    } else {
-        // ---- waves 0, 1: a thread per read
-        typedef uint32_t u32x4a8 __attribute__((ext_vector_type(4), aligned(8)));
-        uint4 dp[kPieceRoundsB];
-        uint64_t qo[kPieceRoundsB];
-        piece_t pc[kPieceRoundsB];
-        const uint32_t p0 = kTileReads * kPieceRoundsB + tid;
-        const uint64_t r = r0 + tid;
-        uint4 d = make_uint4(0, 0, 0, 3u << 8 | 1u << 24);   // (no read: one entry of nothing)
-        if (r < a.n_reads) d = desc[r];
-        ask_descs(p0, kPieceRoundsA, dp, qo);
-        if (tid < 4u) s_stage[tid] = tid < 2u ? 0x66666666u : 0x44444444u;
-        if (tid == 4u) s_nslow = 0;
-        if (lane == 0) s_nent[wid] = 0, s_nent[kReadWaves + wid] = 0;
-        const uint32_t np = (d.w >> 16) & 0xFFu;
-        uint32_t n_ent = d.w >> 24;
-        bool slow = np > kRowPieces || n_ent == kDescMax;
-        const bool simple = n_ent == 1u;
-        if (simple || slow) n_ent = 0;
-        // exclusive scan of the entries over the wave: each read wave has its own half of the entry area
-        const uint32_t inc = wave_scan(n_ent);
-        uint32_t off_e = inc - n_ent;
-        if (n_ent && off_e + n_ent > kEntCapWave) {
-            // more entries than the wave's part holds: the first size hands the whole unit on to the second (nothing of it is
-            // written here, and no read of it goes to the slow list: the second size lists its own); the second leaves the
-            // reads past the part's end to slow_pair
-            if (!BIG) s_nent[kReadWaves + wid] = 1u;
-            else slow = true;
-            n_ent = 0;
-        }
-        if (DEFER && slow) {
-            s_nent[kReadWaves + wid] = 1u;
-            slow = false;
-        }
-        slow_read = slow;
-        off_e += wid * kEntCapWave;
-        // the sweep's entries of this read: the first eight in four 16-byte requests that go out together (entries past the
-        // read's own belong to the next read or to the array's slack) — two deletions in a sweep are six entries, and a
-        // wave in which ONE read needs a ninth makes another trip for it
-        const uint64_t src_at = n_ent ? ((((uint64_t)(d.w >> 8) & 0xFFu) << 32) | d.y) : 0u;
-        const uint2 *src = a.runs + src_at;
-        u32x4a8 e01 = {0, 0, 0, 0}, e23 = e01, e45 = e01, e67 = e01;
-        if (n_ent) {
-            e01 = *reinterpret_cast<const u32x4a8 *>(src);
-            e23 = *reinterpret_cast<const u32x4a8 *>(src + 2);
-        }
-        if (n_ent > 4u) {
-            e45 = *reinterpret_cast<const u32x4a8 *>(src + 4);
-            e67 = *reinterpret_cast<const u32x4a8 *>(src + 6);
-        }
-        ask_pieces(p0, kPieceRoundsA, dp, qo, pc);
-        const int32_t q0 = (int32_t)d.z;
-        const uint32_t row8 = 8u * shape::row_dw(tid);
-        if (!n_ent) {
-            // one entry covers the sweep: its blocks' addresses rise by eight codes a block (aligned bases) or stay (the
-            // dword of '-', of 'not covered'), four blocks a store
-            const uint32_t kind = (simple && !slow) ? (d.w >> 8) & 3u : 3u;
-            const uint32_t a0 = kind == 1u ? row8 + (d.y - (uint32_t)q0) : kind == 2u ? 16u : 0u, st = kind == 1u ? 8u : 0u;
-            uint32_t lo = a0 | ((a0 + st) << 16), hi = lo + 2u * (st | st << 16);
-            const uint32_t step = 4u * (st | st << 16);
-#pragma unroll
-            for (uint32_t k = 0; k < kBlocks / 4u; ++k) {
-                *reinterpret_cast<uint2 *>(s_tab + tab_at(tid, 4u * k)) = make_uint2(lo, hi);
-                lo += step;
-                hi += step;
-            }
-        }
-        // several entries: -> LDS, four bytes each, with their owner; everybody makes table rows of them behind the barrier
-        if (n_ent) {
-            auto pack = [&](uint32_t x, uint32_t y) -> uint32_t {
-                const uint32_t W = x & kRunMask, kind = x >> 30;
-                const uint32_t wr = W <= X ? 0u : min(W - X, 256u);
-                const uint32_t yq = y + (W < X ? X - W : 0u);      // query offset at the sweep's first column of the entry
-                const uint32_t yr = (kind == 1u && wr < 256u) ? (yq - (uint32_t)q0) & 0x1FFFu : 0u;
-                return wr | (kind << 9) | (yr << 11);
-            };
-            const uint32_t e8[8] = {pack(e01.x, e01.y), pack(e01.z, e01.w), pack(e23.x, e23.y), pack(e23.z, e23.w),
-                                    pack(e45.x, e45.y), pack(e45.z, e45.w), pack(e67.x, e67.y), pack(e67.z, e67.w)};
-            uint32_t *ent = s_ent + off_e;
-            uint8_t *own = s_own + off_e;
-#pragma unroll
-            for (uint32_t i = 0; i < 8u; ++i)
-                if (i < n_ent) {
-                    ent[i] = e8[i];
-                    own[i] = (uint8_t)(tid | (i + 1u == n_ent ? 0x80u : 0u));
-                }
-            for (uint32_t i = 8; i < n_ent; ++i) {
-                const uint2 g = src[i];
-                ent[i] = pack(g.x, g.y);
-                own[i] = (uint8_t)(tid | (i + 1u == n_ent ? 0x80u : 0u));
-            }
-            atomicMax(&s_nent[wid], off_e - wid * kEntCapWave + n_ent);
-        }
-        stage_pieces(kPieceRoundsA, pc);
-    }
+    bool slow_read = false;
+    if (tid >= kTileReads) pieces_stage<QV, EPR>(a, pl, lds, tid);
+    else slow_read = read_stage<QV, EPR, BIG, DEFER>(a, pl, lds, tid);
     __syncthreads();
+    // ---- the hand-on check (the first size): a read wave had more entries than its part holds (DEFER: or a read for slow_pair)
     if (!BIG) {
         uint32_t handed = 0;
 #pragma unroll
-        for (uint32_t w = 0; w < kReadWaves; ++w) handed |= s_nent[kReadWaves + w];
+        for (uint32_t w = 0; w < kReadWaves; ++w) handed |= lds.nent[kReadWaves + w];
         if (handed) {
             if (tid == 0) a.big_list[atomicAdd(a.slow_count + 1, 1u)] = b;
             return false;
         }
     }
-    if (slow_read) s_slow[atomicAdd(&s_nslow, 1u)] = (uint8_t)tid;      // (its row of the table says 'not covered')
-
-    // ---- the table rows of the reads with several entries, everybody: a thread an entry.  Entry i
-    // of a read covers the columns [its column, the next entry's column) and the read's last one only ends the one before
-    // it: the blocks that lie WHOLLY inside are the entry's — addresses that rise by eight codes a block, or the dword of '-' /
-    // of 'not covered' — and every block is wholly inside one entry or has an entry that begins inside it; those are put
-    // together, by the thread of the first such entry, in that entry's side dword.  No list, no search, no loop per block.
-    uint32_t n_e = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kReadWaves; ++w) n_e += s_nent[w];
-    for (uint32_t si = tid; si < n_e; si += kThreads) {
-        uint32_t slot = 0, rem = si;      // the si-th entry of the parts one behind the other
-        bool found = false;
-#pragma unroll
-        for (uint32_t w = 0; w < kReadWaves; ++w) {
-            const uint32_t nw = s_nent[w];
-            if (!found && rem < nw) {
-                slot = w * kEntCapWave + rem;
-                found = true;
-            }
-            if (!found) rem -= nw;
-        }
-        const uint32_t own = s_own[slot], e = s_ent[slot], nx = s_ent[slot + 1u];
-        const uint32_t wr = ent_col(e);
-        if ((own & 0x80u) || wr >= width) continue;
-        const uint32_t row8 = 8u * shape::row_dw(own);
-        // (a) the entry's whole blocks [bf, be): singly up to a multiple of four, four a store, singly again
-        const uint32_t wn = ent_col(nx);
-        const uint32_t be = wn >= width ? kBlocks : wn >> 3;
-        uint32_t bf = (wr + 7u) >> 3;
-        if (bf < be) {
-            const uint32_t st = ent_kind(e) == 1u ? 8u : 0u;
-            uint32_t av = ent_addr(e, row8, 8u * bf);
-#pragma unroll
-            for (uint32_t k = 0; k < 3u; ++k)
-                if ((bf & 3u) && bf < be) {
-                    s_tab[tab_at(own, bf)] = (uint16_t)av;
-                    av += st;
-                    ++bf;
-                }
-            uint32_t p01 = av | ((av + st) << 16);
-            const uint32_t p_st = st | st << 16;
-            for (; bf + 4u <= be; bf += 4u) {
-                *reinterpret_cast<uint2 *>(s_tab + tab_at(own, bf)) = make_uint2(p01, p01 + 2u * p_st);
-                p01 += 4u * p_st;
-            }
-            av = p01 & 0xFFFFu;
-#pragma unroll
-            for (uint32_t k = 0; k < 3u; ++k)
-                if (bf < be) {
-                    s_tab[tab_at(own, bf)] = (uint16_t)av;
-                    av += st;
-                    ++bf;
-                }
-        }
-        // (b) the block it begins inside, if it is the first entry to do so
-        const uint32_t bb = wr >> 3;
-        if (!(wr & 7u)) continue;
-        uint32_t ee = s_ent[slot - 1u];        // (an entry that begins inside a block is not its read's first)
-        if (ent_col(ee) > 8u * bb) continue;
-        const uint32_t c0 = 8u * bb, c1 = c0 + 8u;
-        uint32_t bases = 0, m_al = 0, m_del = 0;      // the block's aligned bases (BAM's codes), where they are, where a deletion is
-        for (uint32_t kk = slot;; ++kk) {
-            const uint32_t nn = s_ent[kk];
-            const uint32_t W = ent_col(ee), Wn = ent_col(nn);
-            const uint32_t ca = max(W, c0), cb = min(Wn, c1);
-            const uint32_t kind = ent_kind(ee);
-            if (ca < cb && kind != 3u) {
-                const uint32_t m = (cb - ca == 8u ? 0xFFFFFFFFu : ((1u << (4u * (cb - ca))) - 1u)) << (4u * (ca - c0));
-                if (kind == 1u) {
-                    const uint32_t A = ent_addr(ee, row8, ca);
-                    bases |= (__builtin_amdgcn_alignbit(s_stage[(A >> 3) + 1u], s_stage[A >> 3], 4u * (A & 7u)) << (4u * (ca - c0))) & m;
-                    m_al |= m;
-                } else m_del |= m;
-            }
-            if (Wn >= c1 || (s_own[kk] & 0x80u)) break;     // (the read's last entry is nothing: 'not covered' stays)
-            ee = nn;
-        }
-        const uint32_t R = (codes_of_bases8(bases) & m_al) | (0x44444444u & m_del) | (0x66666666u & ~(m_al | m_del));
-        s_stage[4u + slot] = R;
-        s_tab[tab_at(own, bb)] = (uint16_t)(8u * (4u + slot));
-    }
+    if (slow_read) lds.slow[atomicAdd(&lds.nslow, 1u)] = (uint8_t)tid;      // (its row of the table says 'not covered')
+    table_stage(lds, pl.width, tid);
     __syncthreads();
-    const uint32_t n_slow = s_nslow;
-
-    // ---- gather at the transpose: thread = 32 reads x 8 columns; neighbouring lanes write consecutive dwords of a plane
+    const uint32_t n_slow = lds.nslow;
     if (kPrio) __builtin_amdgcn_s_setprio(0);
-    {
+    const bool act = gather_stage(lds, pl.width, tid, out);
+    if (!DEFER && act) {
         const uint32_t G = tid % kTileGroups, blk = tid / kTileGroups;
-        const bool act = blk < kBlocks && 8u * blk < width;
-        uint32_t out[8][3];
-        if (act) {
-            // (the dwords in front of the reads' rows — 'not covered', '-', the boundary blocks — hold symbol codes already; `codes`
-            // collects, a bit a read, whose dword is one of those: v_alignbit shifts the sign of address - first row in)
-            uint32_t R[32], codes = 0;
-            // (the block's place in the rows of the reads i, i + 8, ...: eight offsets)
-            uint32_t at[8];
-#pragma unroll
-            for (uint32_t i = 0; i < 8u; ++i) at[i] = tab_at(32u * G + i, blk);
-#pragma unroll
-            for (int i = 31; i >= 0; --i) {
-                const uint32_t A = s_tab[at[i & 7] + (uint32_t)(i & ~7) * kTabRow];
-                R[i] = __builtin_amdgcn_alignbit(s_stage[(A >> 3) + 1u], s_stage[A >> 3], 4u * (A & 7u));
-                codes = __builtin_amdgcn_alignbit(codes, A - 8u * kRowBase, 31u);
-            }
-            nibble_rows_to_plane_words(R, codes, out);
-        }
-        if (DEFER) {
-#pragma unroll
-            for (uint32_t jj = 0; jj < 8u; ++jj)
-#pragma unroll
-                for (uint32_t k = 0; k < 3u; ++k) keep[jj][k] = out[jj][k];
-        } else if (act) {
-            const uint64_t byte = (uint64_t)tile * (kTileReads / 8u) + (uint64_t)G * 4u;
-            if (byte < a.plane_stride) {
-                // (one 64-bit multiply for the first plane row, then a stride at a time; a block of eight whole columns — all but
-                // the window's last — stores without a question per column: a predicate per store was a sixth of this phase)
-                uint8_t *row = a.msa + (uint64_t)((X + 8u * blk) * 3u) * a.plane_stride + byte;
-                if (8u * blk + 8u <= width) {
-#pragma unroll
-                    for (uint32_t jj = 0; jj < 8u; ++jj)
-#pragma unroll
-                        for (uint32_t k = 0; k < 3u; ++k) {
-                            *reinterpret_cast<uint32_t *>(row) = out[jj][k];
-                            row += a.plane_stride;
-                        }
-                } else {
-                    for (uint32_t jj = 0; 8u * blk + jj < width; ++jj)
-                        for (uint32_t k = 0; k < 3u; ++k) {
-                            *reinterpret_cast<uint32_t *>(row) = jj == 0u ? out[0][k] : jj == 1u ? out[1][k] : jj == 2u ? out[2][k] : jj == 3u ? out[3][k] : jj == 4u ? out[4][k] : jj == 5u ? out[5][k] : out[6][k];
-                            row += a.plane_stride;
-                        }
-                }
-            }
-        }
+        const uint64_t byte = (uint64_t)pl.tile * (kTileReads / 8u) + (uint64_t)G * 4u;
+        // (one 64-bit multiply for the first plane row, then a stride at a time)
+        if (byte < a.plane_stride) store_block_words(a.msa + (uint64_t)((pl.X + 8u * blk) * 3u) * a.plane_stride + byte, a.plane_stride, out, pl.width - 8u * blk);
     }
-    // ---- the reads left out (none, in a CCS sample): column by column behind the workgroup's own stores, a wave a read
+    // ---- the slow tail, the reads left out (none, in a CCS sample): column by column behind the workgroup's own stores, a wave a read
     if (!DEFER && n_slow) {       // (the same in every thread)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        for (uint32_t i = wid; i < n_slow; i += kThreads / 64u) slow_pair(a, r0 + s_slow[i], sweep, lane);
+        for (uint32_t i = tid >> 6; i < n_slow; i += kThreads / 64u) slow_pair(a, pl.r0 + lds.slow[i], pl.sweep, tid & 63u);
     }
     return true;
 }
@@ -1224,16 +1277,17 @@ template <uint32_t QV, uint32_t EPR, bool BIG, uint32_t NT = 1u>
 __global__ __launch_bounds__(kThreads, (BIG ? 1 : kMinWgs)) void ingest_planes_kernel(ingest_args a)
 {
     static_assert(NT == 1u || NT == 2u, "one tile a workgroup, or two");
+    __shared__ planes_lds<EPR> lds;
     if constexpr (BIG) {
         uint32_t none[8][3];
         const uint32_t n = a.slow_count[1];
         for (uint32_t u = blockIdx.x; u < n; u += gridDim.x) {
-            planes_unit<QV, EPR, true>(a, a.big_list[u], none);
+            planes_unit<QV, EPR, true>(a, a.big_list[u], lds, none);
             __syncthreads();      // (the next unit's LDS)
         }
     } else if constexpr (NT == 1u) {
         uint32_t none[8][3];
-        planes_unit<QV, EPR, false>(a, blockIdx.x, none);
+        planes_unit<QV, EPR, false>(a, blockIdx.x, lds, none);
     } else {
         // workgroup w -> the units (planes_unit's block numbers) of NT consecutive tiles of one (group, sweep), on w's XCD
         const uint32_t w = blockIdx.x, xcd = w & 7u, jw = w >> 3, h = jw % (kSubTiles / NT), qq = jw / (kSubTiles / NT);
@@ -1249,7 +1303,7 @@ __global__ __launch_bounds__(kThreads, (BIG ? 1 : kMinWgs)) void ingest_planes_k
                 for (uint32_t jj = 0; jj < 8u; ++jj)
 #pragma unroll
                     for (uint32_t k = 0; k < 3u; ++k) D[t][jj][k] = D[t + 1u][jj][k];
-            const bool got = planes_unit<QV, EPR, false, true>(a, b0 + 8u * i, D[NT - 1u]);
+            const bool got = planes_unit<QV, EPR, false, true>(a, b0 + 8u * i, lds, D[NT - 1u]);
             ok = (ok >> 1) | (got ? 1u << (NT - 1u) : 0u);
             __syncthreads();      // (the next tile's LDS)
         }
@@ -1269,33 +1323,23 @@ __global__ __launch_bounds__(kThreads, (BIG ? 1 : kMinWgs)) void ingest_planes_k
             }
         // ---- D[p] = this lane's tile's (tile u of the NT) words of block (blk & ~(NT - 1)) + p: NT x 4 lanes a row
         if (!((ok >> u) & 1u)) return;                      // (this lane's tile was handed on)
-        const uint32_t sub0 = NT * h, group = xcd + 8u * (qq / a.n_sweeps), sweep = qq % a.n_sweeps;
-        const uint32_t X = sweep * kSweep, width = min(a.n_cols, X + kSweep) - X;
-        const uint64_t byte = (uint64_t)(kSubTiles * group + sub0 + u) * (kTileReads / 8u) + (uint64_t)G * 4u;
+        const unit_place pl = place_of(a, b0);              // (the first of the sibling tiles: the lane's is u behind it)
+        const uint64_t byte = (uint64_t)(pl.tile + u) * (kTileReads / 8u) + (uint64_t)G * 4u;
 #pragma unroll
         for (uint32_t p = 0; p < NT; ++p) {
             const uint32_t bp = (blk & ~(NT - 1u)) + p;
-            if (8u * bp >= width) continue;
-            uint8_t *row = a.msa + (uint64_t)((X + 8u * bp) * 3u) * a.plane_stride + byte;
-            if (8u * bp + 8u <= width) {
-#pragma unroll
-                for (uint32_t jj = 0; jj < 8u; ++jj)
-#pragma unroll
-                    for (uint32_t k = 0; k < 3u; ++k) {
-                        *reinterpret_cast<uint32_t *>(row) = D[p][jj][k];
-                        row += a.plane_stride;
-                    }
-            } else {
-#pragma unroll
-                for (uint32_t jj = 0; jj < 8u; ++jj)
-#pragma unroll
-                    for (uint32_t k = 0; k < 3u; ++k) {
-                        if (8u * bp + jj < width) *reinterpret_cast<uint32_t *>(row) = D[p][jj][k];
-                        row += a.plane_stride;
-                    }
-            }
+            if (8u * bp >= pl.width) continue;
+            store_block_words(a.msa + (uint64_t)((pl.X + 8u * bp) * 3u) * a.plane_stride + byte, a.plane_stride, D[p], pl.width - 8u * bp);
         }
     }
+}
+
+// the planes kernel's two launches of a build: the first size, NT sibling tiles a workgroup, and the second behind it
+template <uint32_t QV, uint32_t NT>
+void launch_planes(const ingest_args &a, uint32_t units, hipStream_t st)
+{
+    hipLaunchKernelGGL((ingest_planes_kernel<QV, kEntPerRead, false, NT>), dim3(units / NT), dim3(kThreads), 0, st, a);
+    hipLaunchKernelGGL((ingest_planes_kernel<QV, kEntPerReadBig, true>), dim3(kBigGrid), dim3(kThreads), 0, st, a);
 }
 
 }  // namespace
@@ -1312,27 +1356,15 @@ static uint32_t planes_units(const jl_ctx *ctx)
 // pairs (8 bytes) of d_slow: the units handed on (a word each)
 size_t jl_ingest_slow_room(const jl_ctx *ctx) { return (size_t)planes_units(ctx) / 2u + 8u; }
 
-// The host's copy of cigar_walk_kernel's rule — which reads it leaves to the long-read launch (more than kWalkOps ops, or more entries
-// than a read has room for in its LDS) — for the upload (jl_records_append), which looks at the few reads of a CCS sample with more
+// cigar_walk_kernel's rule (cigar_rules.h: the same functions on the host) — which reads it leaves to the long-read launch (more than
+// kWalkOps ops, or more entries than a read has room for in its LDS) — for the upload (jl_records_append), which looks at the few reads of a CCS sample with more
 // ops than a read has entries: when it finds none, jl_launch_ingest does not make that launch.
-uint32_t jl_ingest_short_ops() { return kWalkEnt - 3u; }      // a read of so many ops at most cannot be a long one
-bool jl_ingest_read_is_long(const uint32_t *cigar, uint64_t n_ops)
-{
-    if (n_ops > kWalkOps) return true;
-    constexpr uint32_t kKinds = (2u << 4) | (3u << 6) | (1u << 14) | (1u << 16);   // two bits per op: D, N, =, X (cigar_walk_kernel)
-    uint32_t n_runs = 0, prev_kind = 0;
-    for (uint64_t t = 0; t < n_ops; ++t) {
-        const uint32_t op = cigar[t] & 15u, len = cigar[t] >> 4;
-        const uint32_t kind = len == 0u ? 0u : (kKinds >> (2u * op)) & 3u;
-        if (kind != 0u && !(kind == 1u && prev_kind == 1u)) ++n_runs;
-        prev_kind = kind;
-    }
-    return n_runs + 3u > kWalkEnt;
-}
+uint32_t jl_ingest_short_ops() { return jl_cigar::kWalkEnt - 3u; }      // a read of so many ops at most cannot be a long one
+bool jl_ingest_read_is_long(const uint32_t *cigar, uint64_t n_ops) { return jl_cigar::read_is_long(cigar, n_ops); }
 
 // The scratch of `dst` (capi_records.hip records_build): runs, n_cig + 3 n_reads + 8 entries; nruns, n_reads; desc, n_reads x sweeps
 // descriptors; slow, jl_ingest_slow_room() pairs.
-// d_count, 64 bytes: [0] pairs listed, [1] units handed on — zeroed by the first block of the build's first launch (cigar_walk_kernel);
+// d_count, 64 bytes: [0] retired (zeroed, never read), [1] units handed on — zeroed by the first block of the build's first launch (cigar_walk_kernel);
 // [2..3] the 64-bit word of the first malformed record (all ones: none — so it is set when the block is allocated, and again by
 // jl_ingest_verdict when it has read one; a build whose predecessor's word has not been read yet folds its own into it, atomicMin).
 // Everything is enqueued on dst->stream; nothing waits.  dst->n_reads is not zero: the matrix has been allocated.
@@ -1379,17 +1411,8 @@ void jl_launch_ingest(jl_ctx *dst, const jl_records &R, uint32_t min_qv)
     // the same runs: profiles/qmask_ingest_ab.txt; -DJL_NT_QM=1 through tools_tuning/build_tuning_lib.sh builds the other)
     constexpr uint32_t kNt = 1u, kNtQv = 2u, kNtQm = JL_NT_QM;
     switch (mode) {
-    case JL_QV_BYTES:
-        hipLaunchKernelGGL((ingest_planes_kernel<kQvBytes, kEntPerRead, false, kNtQv>), dim3(grid / kNtQv), dim3(kThreads), 0, st, a);
-        hipLaunchKernelGGL((ingest_planes_kernel<kQvBytes, kEntPerReadBig, true>), dim3(kBigGrid), dim3(kThreads), 0, st, a);
-        break;
-    case JL_QV_MASK:
-        hipLaunchKernelGGL((ingest_planes_kernel<kQvMask, kEntPerRead, false, kNtQm>), dim3(grid / kNtQm), dim3(kThreads), 0, st, a);
-        hipLaunchKernelGGL((ingest_planes_kernel<kQvMask, kEntPerReadBig, true>), dim3(kBigGrid), dim3(kThreads), 0, st, a);
-        break;
-    case JL_QV_NONE:
-        hipLaunchKernelGGL((ingest_planes_kernel<kQvNone, kEntPerRead, false, kNt>), dim3(grid / kNt), dim3(kThreads), 0, st, a);
-        hipLaunchKernelGGL((ingest_planes_kernel<kQvNone, kEntPerReadBig, true>), dim3(kBigGrid), dim3(kThreads), 0, st, a);
-        break;
+    case JL_QV_BYTES: launch_planes<kQvBytes, kNtQv>(a, grid, st); break;
+    case JL_QV_MASK: launch_planes<kQvMask, kNtQm>(a, grid, st); break;
+    case JL_QV_NONE: launch_planes<kQvNone, kNt>(a, grid, st); break;
     }
 }
