@@ -1234,7 +1234,7 @@ class Xwin:
         merged = _view(r.merged, VARIANT, nv).copy() if nv else np.zeros(0, dtype=VARIANT)
         out = dict(merged=merged, pos_cols=_view(r.pos_global, np.uint32, vp).copy() if vp else np.zeros(0, dtype=np.uint32),
                    summary={n: getattr(r.summary, n) for n in SUMMARY_FIELDS}, n_groups=r.n_groups,
-                   slice=(int(r.slice_begin), int(r.slice_reads)))
+                   slice=(int(r.slice_begin), int(r.slice_reads)), read_hap_bits=int(r.read_hap_bits))
         if vp:
             out.update(hap_count=_view(r.hap_count, np.uint32, h).copy() if h else np.zeros(0, dtype=np.uint32),
                        hap_pattern=_view(r.hap_pattern, np.uint8, h * vp).reshape(h, vp).copy() if h else np.zeros((0, vp), dtype=np.uint8),

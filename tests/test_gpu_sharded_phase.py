@@ -408,27 +408,7 @@ def test_allgather_groups_single_rank(oracle):
 # exchange schedule with its packed sends and receives, grouping per read slice, the group gather, merge + selection,
 # per-read ids of each rank's slice — except RCCL's own wire.
 
-def _ranks_in_threads(world, body):
-    """body(rank) in one thread per rank; re-raises the first failure."""
-    import threading
-    errs = [None] * world
-    outs = [None] * world
-
-    def run(r):
-        try:
-            outs[r] = body(r)
-        except BaseException as e:   # noqa: BLE001 - reported below
-            errs[r] = e
-
-    th = [threading.Thread(target=run, args=(r,)) for r in range(world)]
-    for t in th:
-        t.start()
-    for t in th:
-        t.join(600)
-    for e in errs:
-        if e is not None:
-            raise e
-    return outs
+from rank_threads import ranks_in_threads as _ranks_in_threads  # noqa: E402  (shared with tests/test_gpu_xwin_edges.py)
 
 
 @pytest.mark.parametrize("n,world,k_windows", [(7000, 2, 2), (7000, 3, 5), (1000, 3, 3), (40_000, 2, 4), (300, 4, 4)])
