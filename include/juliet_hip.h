@@ -422,6 +422,47 @@ typedef struct {
  * above 2^32 - 1. */
 int jl_deletion_test(const uint32_t cnt[4], const jl_params *prm, double n_tests, jl_deletion_call *out);
 /*
+ * PER-READ counters over the whole resident window (docs/SPEC.md §20): every other stage looks at the matrix by column; a read that
+ * disagrees with the window at dozens of columns (off-target, chimeric, hypermutated, badly aligned at its ends) raises several
+ * minor codons at once, and this is the call that shows it.  For read i, summed over all n_cols columns, with `code` its cell
+ * (0..3 base, 4 '-', 5 N, 6 uncovered) and compare[c] the column's compare code:
+ *   JL_READ_BASES       code < 4
+ *   JL_READ_GAPS        code == 4
+ *   JL_READ_MASKED      code == 5
+ *   JL_READ_COMPARED    code < 4 and compare[c] < 4
+ *   JL_READ_MISMATCHES  code < 4 and compare[c] < 4 and code != compare[c]
+ * A compare[c] of 4 or above means "this column is not compared": the output of jl_consensus_fetch / jl_consensus_of_counts (4 =
+ * majority deletion, 5 = uncovered) and a reference slice with non-ACGT codes can be passed as they are.  compare == NULL: no column
+ * is compared, `compared` and `mismatches` are zero.  The covered cells of a read are bases + gaps + masked; a code-6 cell counts
+ * nowhere.  Reads past n_reads count nowhere: the padding, and whatever an adopted matrix holds past the last read of a plane row.
+ * stats[JL_READ_STATS][n_reads], struct of arrays: counter k of read i at stats[k * n_reads + i], 32 bits, exact, independent of
+ * launch shape and order.
+ * The contract is jl_class_pileup_async's: compare[n_cols] is copied before the call returns; it enqueues on the context's stream
+ * into buffers of its own (grown on demand, released with the context) and touches nothing else — the matrix, the insertion
+ * counters, earlier stage results and the captured graph stay as they are.  Every kind of resident matrix is accepted, an adopted
+ * one with its own plane stride included.
+ * JL_ERR_STATE: no resident matrix.  A refused call changes nothing.
+ */
+enum { JL_READ_BASES = 0, JL_READ_GAPS = 1, JL_READ_MASKED = 2, JL_READ_COMPARED = 3, JL_READ_MISMATCHES = 4, JL_READ_STATS = 5 };
+int jl_read_stats_async(jl_ctx *ctx, const uint8_t *compare /* [n_cols] or NULL */);
+/* Wait and copy out stats[JL_READ_STATS][n_reads] of the last jl_read_stats_async (NULL: only wait).  JL_ERR_STATE: none was enqueued. */
+int jl_read_stats_fetch(jl_ctx *ctx, uint32_t *stats /* [JL_READ_STATS][n_reads] */);
+/* Which reads a rule keeps, from that table.  A read is kept when it passes every rule that is switched on; the products are
+ * evaluated in IEEE double, left to right, as written (a read with compared == 0 passes a percentage rule: 0 <= 0). */
+typedef struct {
+    uint32_t min_bases;          /* keep bases >= min_bases; 0 disables */
+    uint32_t max_mismatches;     /* keep mismatches <= max_mismatches; UINT32_MAX disables */
+    double max_mismatch_perc;    /* keep 100.0 * mismatches <= x * compared; < 0 disables */
+    double max_gap_perc;         /* keep 100.0 * gaps <= x * (bases + gaps); < 0 disables */
+    double max_masked_perc;      /* keep 100.0 * masked <= x * (bases + gaps + masked); < 0 disables */
+} jl_read_rule;
+/* Host only (no device, no context).  idx[0 .. *n_kept): the kept reads, ascending — what jl_msa_take takes; room for n_reads.
+ * failed[5], may be NULL: reads that fail {min_bases, max_mismatches, max_mismatch_perc, max_gap_perc, max_masked_perc}; a read
+ * that fails several rules counts in each.  JL_ERR_ARG (jl_last_error(NULL) says which): a NULL argument; a percentage above
+ * 100; n_reads above 2^32 - 1. */
+int jl_read_filter(const uint32_t *stats, uint64_t n_reads, const jl_read_rule *rule, uint32_t *idx, uint64_t *n_kept,
+                   uint64_t failed[5]);
+/*
  * The SITE MATRIX (docs/SPEC.md §18): called codon deletions as sites of a haplotype.  Phasing groups reads by their codons at the
  * variant positions, and a deleted codon is no codon: its carriers are GAP-damaged where the position is a variant position and
  * invisible where it is not.  This call builds, as jl_xwin_assemble_local does, a compact matrix of chosen codon starts of `src`

@@ -40,7 +40,7 @@ SITE_INS_NONE, SITE_INS_OTHER, SITE_INS_MAX_ALLELES = 0, 63, 62
 EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", "jl_ctx_destroy", "jl_last_error",
            "jl_sync", "jl_col_stride", "jl_plane_stride", "jl_msa_upload", "jl_msa_alloc", "jl_msa_adopt", "jl_msa_pack_rows",
            "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_take", "jl_msa_take_async", "jl_sample_reads", "jl_mix_counts", "jl_msa_download", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
-           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_msa_track_insertion_reads", "jl_insertion_reads_fetch", "jl_sites_assemble_alleles", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_phase_async", "jl_phase_fetch",
+           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_read_stats_async", "jl_read_stats_fetch", "jl_read_filter", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_msa_track_insertion_reads", "jl_insertion_reads_fetch", "jl_sites_assemble_alleles", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_phase_async", "jl_phase_fetch",
            "jl_ctx_stream", "jl_run_async", "jl_run_wait", "jl_run_done", "jl_run_view_get", "jl_group_create", "jl_group_destroy",
            "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
            "jl_allgather_variants", "jl_allgather_variants_async", "jl_allgather_variants_async_many", "jl_allgather_variants_many", "jl_group_exchange_bind", "jl_group_exchange_collect", "jl_xwin_plan", "jl_xwin_assemble_local",
@@ -48,6 +48,15 @@ EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", 
            "jl_phase_groups_fetch", "jl_phase_regroup", "jl_merge_tables", "jl_merge_groups", "jl_select_haplotypes",
            "jl_xwin_slice_plan", "jl_xwin_create", "jl_xwin_destroy", "jl_xwin_last_error", "jl_xwin_phase_sharded",
            "jl_xwin_read_hap_fetch", "jl_xwin_stage_us", "jl_allgather_groups")
+
+
+READ_BASES, READ_GAPS, READ_MASKED, READ_COMPARED, READ_MISMATCHES, READ_STATS = range(6)   # jl_read_stats_async (docs/SPEC.md §20)
+READ_RULES = ("min_bases", "mismatches", "mismatch_perc", "gap_perc", "n_perc")   # the order of jl_read_filter's failed[5]
+
+
+class ReadRule(C.Structure):   # jl_read_rule
+    _fields_ = [("min_bases", C.c_uint32), ("max_mismatches", C.c_uint32), ("max_mismatch_perc", C.c_double),
+                ("max_gap_perc", C.c_double), ("max_masked_perc", C.c_double)]
 
 
 class ErrorModel(C.Structure):
@@ -220,6 +229,9 @@ def load_library(path=LIB_PATH):
     lib.jl_codon_deletions_async.argtypes = [vp]
     lib.jl_codon_deletions_fetch.argtypes = [vp, vp]
     lib.jl_deletion_test.argtypes = [vp, vp, C.c_double, vp]
+    lib.jl_read_stats_async.argtypes = [vp, vp]
+    lib.jl_read_stats_fetch.argtypes = [vp, vp]
+    lib.jl_read_filter.argtypes = [vp, u64, C.POINTER(ReadRule), vp, C.POINTER(u64), vp]
     lib.jl_sites_assemble.argtypes = [vp, vp, vp, u32]
     lib.jl_msa_track_insertion_alleles.argtypes = [vp, C.c_int]
     lib.jl_insertion_alleles_fetch.argtypes = [vp, vp, vp, u32, vp]
@@ -633,6 +645,24 @@ class Juliet:
         self._chk(self.lib.jl_codon_deletions_fetch(self.h, _p(cnt) if cnt.size else None))
         return cnt
 
+    def read_stats(self, compare=None, wait=True):
+        """jl_read_stats_async (docs/SPEC.md §20): per read of the resident matrix, over all columns, its bases, gaps, masked cells,
+        bases in compared columns and mismatches among those.  compare[n_cols]: a code per column, 4 or above = not compared (the
+        output of consensus() can be passed as it is); None: no column is compared.  Returns stats[5, n_reads] (READ_BASES ..
+        READ_MISMATCHES), uint32, exact; wait=False only enqueues on this context's stream and returns None (read_stats_fetch
+        brings the array)."""
+        if compare is not None:
+            compare = np.ascontiguousarray(compare, dtype=np.uint8)
+            assert compare.shape == (self.n_cols,)
+        self._chk(self.lib.jl_read_stats_async(self.h, _p(compare)))
+        self._rs_reads = self.n_reads
+        return self.read_stats_fetch() if wait else None
+
+    def read_stats_fetch(self):
+        stats = np.zeros((READ_STATS, getattr(self, "_rs_reads", 0)), dtype=np.uint32)
+        self._chk(self.lib.jl_read_stats_fetch(self.h, _p(stats) if stats.size else None))
+        return stats
+
     def sites_assemble(self, src, sites):
         """jl_sites_assemble (docs/SPEC.md §18): this context becomes the site matrix of `src` — its reads x 3 len(sites) columns,
         site k = (col, kind, fill) at columns 3k..3k+2: the three columns at `col` of `src`, the del3 reads of a SITE_DELETION site
@@ -1028,6 +1058,29 @@ def deletion_test(cnt, params, n_tests):
     d = {name: getattr(out, name) for name, _ in DeletionCall._fields_ if name != "pad_"}
     d["called"] = bool(d["called"])
     return d
+
+
+def read_rule(min_bases=0, max_mismatches=0xFFFFFFFF, max_mismatch_perc=-1.0, max_gap_perc=-1.0, max_masked_perc=-1.0):
+    """A jl_read_rule; the defaults switch every rule off."""
+    return ReadRule(int(min_bases), int(max_mismatches), float(max_mismatch_perc), float(max_gap_perc), float(max_masked_perc))
+
+
+def read_filter(stats, **rule):
+    """jl_read_filter (host only, docs/SPEC.md §20): the reads of Juliet.read_stats' table that pass every rule that is switched
+    on (read_rule's keywords) — (idx, failed): ascending uint32 indices, what Juliet.take takes, and failed[5] = reads failing
+    each of READ_RULES (a read that fails several counts in each)."""
+    lib = load_library()
+    stats = np.ascontiguousarray(stats, dtype=np.uint32)
+    assert stats.ndim == 2 and stats.shape[0] == READ_STATS
+    n = stats.shape[1]
+    idx = np.zeros(max(1, n), dtype=np.uint32)
+    failed = np.zeros(5, dtype=np.uint64)
+    kept = C.c_uint64()
+    r = read_rule(**rule)
+    rc = lib.jl_read_filter(_p(stats), n, C.byref(r), _p(idx), C.byref(kept), _p(failed))
+    if rc:
+        raise JulietError(rc, "jl_read_filter: " + lib.jl_last_error(None).decode())
+    return idx[: kept.value].copy(), failed
 
 
 class InsertionCall(C.Structure):

@@ -19,7 +19,8 @@
 //                              (group runs choose between the two per launch otherwise: capi_group.hip)
 // Inline ids = the phasing launch writing the per-read ids itself (JL_INLINE_IDS_MAX_BLOCKS below):
 //   JL_FORCE_IDS_WAIT_TIMEOUT  test hook of the -DJL_TUNING build (tools_tuning/build_tuning_lib.sh): such a launch gives up waiting at
-//                              once (test_fold_timeout_is_rerun_unfolded).  JL_TUNING adds five read-outs besides (capi_group.hip, kernels_pileup.hip), nothing else.
+//                              once (test_fold_timeout_is_rerun_unfolded).  JL_TUNING adds five read-outs besides (capi_group.hip, kernels_pileup.hip) and
+//                              the shape override of the per-read counters (jl_tuning_read_stats_shape, capi_readstats.hip), nothing else.
 struct jl_env_switches {
     bool no_fold_call, no_graph, exchange_staged, force_ids_wait_timeout;
 };
@@ -389,6 +390,22 @@ struct jl_del_args {
 };
 void jl_launch_codon_deletions(const jl_del_args *a, hipStream_t st);
 
+// ---- per-read counters over the whole window (kernels_readstats.hip, capi_readstats.hip; docs/SPEC.md §20)
+struct jl_readstats_shape;     // readstats_shape.h
+struct jl_readstats_args {
+    const uint8_t *msa;        // the window's bit planes
+    uint64_t plane_stride;     // ... and their stride (an adopted matrix brings its own)
+    uint64_t n_reads;
+    uint32_t n_cols;
+    uint32_t n_words;          // words of a row that hold reads: ceil(n_reads / 32); 4 n_words <= plane_stride
+    uint32_t n_chunks, seg_cols;   // of the launch shape (set by the launcher)
+    const uint8_t *compare;    // [n_cols], or null: no column is compared
+    uint32_t *part;            // the segments' byte counters (jl_readstats_part_words), or null when the shape combines by atomics
+    uint32_t *stats;           // [JL_READ_STATS][n_reads]
+};
+void jl_launch_read_stats(const jl_readstats_args *a, const jl_readstats_shape *shape, hipStream_t st);
+size_t jl_readstats_part_words(const jl_readstats_shape *shape);
+
 // ---- the site matrix: chosen codon starts of a matrix, deletion sites recoded (kernels_sites.hip, capi_sites.hip; docs/SPEC.md §18)
 struct jl_sites_args {
     const uint8_t *src;        // the source's bit planes
@@ -686,6 +703,12 @@ struct jl_ctx {
     // ---- jl_codon_deletions_async: a buffer of its own, grown on demand (capi_del.hip); no stage and no run touches it
     jl_dev_array<uint32_t> del_out;        // cnt [del_cols - 2][4]
     uint32_t del_cols = 0;                 // columns of the last call enqueued (0: none)
+
+    // ---- jl_read_stats_async: buffers of its own, grown on demand (capi_readstats.hip); no stage and no run touches them
+    jl_upload_staging<uint8_t> rs_compare; // the compare row on its way to the device
+    jl_dev_array<uint32_t> rs_part;        // the column segments' byte counters, when a second kernel combines them
+    jl_dev_array<uint32_t> rs_out;         // stats [JL_READ_STATS][rs_reads]
+    uint64_t rs_reads = 0;                 // reads of the last call enqueued (0: none)
 
     // ---- jl_sites_assemble INTO this context: the site table on its way to the device (capi_sites.hip)
     jl_upload_staging<jl_site> sites_in;

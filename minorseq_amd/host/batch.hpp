@@ -76,6 +76,7 @@ private:
         jl_ctx *ctx = nullptr;       // of the pool: the sample's records and its window as ingested
         jl_ctx *run = nullptr;       // the window that is called: ctx, or — downsampled — the pool context's companion (taken_)
         SamplingInfo sampling;
+        ReadFilterInfo read_filter;
         SampleSetup s;
         std::vector<std::string> names;
         uint64_t n_reads = 0;
@@ -170,7 +171,7 @@ private:
         }
         cv_.notify_all();
     }
-    // The context a pool context's downsampled window goes into: same device, same stream, made when first needed and kept.
+    // The context a pool context's filtered or downsampled window goes into (a filtered window's own companion, when both act): same device, same stream, made when first needed and kept.
     jl_ctx *companion_of(jl_ctx *c)   // (decoding thread only)
     {
         jl_ctx *&t = taken_[c];
@@ -208,10 +209,18 @@ private:
         if (ingest.outcome == Outcome::device && ingest.rc != JL_ERR_ARG && ingest.rc != JL_ERR_STATE) gpu_error(ingest.text());
         if (ingest.outcome != Outcome::ok) return ingest.text();
         smp.run = smp.ctx;
-        if (opt_.have_downsample && smp.n_reads > opt_.downsample) {   // (every sample of the list goes to the same depth)
-            jl_ctx *taken = companion_of(smp.ctx);
+        if (opt_.read_filter()) {   // (every sample of the list by the same rule; docs/SPEC.md §20)
+            jl_ctx *kept = companion_of(smp.ctx);
             bool acted = false;
-            if (downsample_window(opt_, l.bam, smp.ctx, taken, smp.names, smp.n_reads, smp.sampling, &acted) != JL_OK)
+            const Status rf = read_filter_window(opt_, smp.s, smp.ctx, kept, smp.names, smp.n_reads, smp.read_filter, &acted);
+            if (rf.outcome == Outcome::device) gpu_error(rf.text());
+            if (rf.outcome != Outcome::ok) return rf.text();
+            if (acted) smp.run = kept;
+        }
+        if (opt_.have_downsample && smp.n_reads > opt_.downsample) {   // (every sample of the list goes to the same depth)
+            jl_ctx *taken = companion_of(smp.run);
+            bool acted = false;
+            if (downsample_window(opt_, l.bam, smp.run, taken, smp.names, smp.n_reads, smp.sampling, &acted) != JL_OK)
                 gpu_error(std::string("downsample: ") + jl_last_error(taken));
             if (acted) smp.run = taken;
         }
@@ -328,7 +337,7 @@ private:
     void write(Sample &x)
     {
         try {
-            const Json root = build_json(opt_, x.s, x.line->bam, cmdline_, x.names, x.n_reads, x.R, &x.sampling);
+            const Json root = build_json(opt_, x.s, x.line->bam, cmdline_, x.names, x.n_reads, x.R, &x.sampling, &x.read_filter);
             std::lock_guard<std::mutex> lk(io_m_);
             const std::string failed = write_outputs(x.line->outputs, root);
             if (!failed.empty()) sample_failed(*x.line, "cannot write " + failed);

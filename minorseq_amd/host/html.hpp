@@ -50,7 +50,7 @@ inline std::string render_html(const Json &root)
     if (const Json *in = root.get("input")) {
         h += "<details open id=\"input\"><summary>Input data</summary><table id=\"input-table\">\n";
         for (auto &kv : in->obj)
-            if (kv.first != "sampling") h += "<tr><th>" + html_escape(kv.first) + "</th>" + td(num_str(&kv.second)) + "</tr>\n";
+            if (kv.first != "sampling" && kv.first != "read_filter") h += "<tr><th>" + html_escape(kv.first) + "</th>" + td(num_str(&kv.second)) + "</tr>\n";
         h += "</table>\n";
         // --downsample / --mix: the seed and, per source, its file, its reads and how many of them were kept (docs/SPEC.md section 12)
         if (const Json *sp = in->get("sampling")) {
@@ -59,6 +59,18 @@ inline std::string render_html(const Json &root)
             if (const Json *srcs = sp->get("sources"))
                 for (const Json &x : srcs->arr)
                     h += "<tr>" + td(x.get_str("file")) + td(num_str(x.get("reads"))) + td(num_str(x.get("kept"))) + "</tr>\n";
+            h += "</table>\n";
+        }
+        // the read filter: its compare row, the rules that were given, and the reads each rule failed (docs/SPEC.md section 20)
+        if (const Json *rf = in->get("read_filter")) {
+            h += "<table id=\"read-filter-table\" data-compare=\"" + html_escape(rf->get_str("compare")) + "\">\n<tr><th>read filter (compare: " +
+                 html_escape(rf->get_str("compare")) + ")</th><th>bound</th><th>failed</th></tr>\n";
+            h += "<tr class=\"reads\">" + td("reads") + td("") + td(num_str(rf->get("reads"))) + "</tr>\n";
+            h += "<tr class=\"kept\">" + td("kept") + td("") + td(num_str(rf->get("kept"))) + "</tr>\n";
+            const Json *rule = rf->get("rule");
+            if (const Json *failed = rf->get("failed"))
+                for (auto &kv : failed->obj)
+                    h += "<tr class=\"rule\">" + td(kv.first) + td(rule ? num_str(rule->get(kv.first)) : "") + td(num_str(&kv.second)) + "</tr>\n";
             h += "</table>\n";
         }
         h += "</details>\n";

@@ -57,12 +57,13 @@ struct Run {
     SampleSetup smp;
     Results R;
     SamplingInfo sampling;
+    ReadFilterInfo read_filter;
 };
 
 // JSON / HTML (doc/JULIET.md:61-107, 207-211), and the end of the process
 int write_run(Run &run)
 {
-    const Json root = build_json(run.opt, run.smp, run.opt.bam, run.cmdline, run.load.names, run.load.n_reads, run.R, &run.sampling);
+    const Json root = build_json(run.opt, run.smp, run.opt.bam, run.cmdline, run.load.names, run.load.n_reads, run.R, &run.sampling, &run.read_filter);
     const std::string failed = write_outputs(run.opt.outputs, root);
     if (!failed.empty()) { std::cerr << "juliet: cannot write " << failed << "\n"; return 2; }
     run.tick("json / html");
@@ -83,7 +84,7 @@ int run_fuse(Run &run, jl_ctx *ctx)
     return 0;
 }
 
-// One window on one device: ingest, --downsample / --mix, the run, its results, the outputs.
+// One window on one device: ingest, the read filter, --downsample / --mix, the run, its results, the outputs.
 int run_one_window(Run &run)
 {
     const Options &opt = run.opt;
@@ -97,6 +98,14 @@ int run_one_window(Run &run)
     const DeviceStageInput in{&opt, &smp.cfg, &smp.genes, &smp.refcodes, smp.prm, win_begin, n_cols, n_reads};
     if (const int code = exit_code_of(ingest_window(ctx, n_cols, win_begin, opt), opt.bam)) return code;
     tick("device ingest");
+    if (opt.read_filter()) {   // the reads a rule keeps, in a second context on the same device and stream (docs/SPEC.md §20)
+        jl_ctx *kept = nullptr;
+        if (jl_ctx_create(opt.device, jl_ctx_stream(ctx), &kept) != JL_OK) die_jl(nullptr, "context of the kept reads");
+        bool acted = false;
+        if (const int code = exit_code_of(read_filter_window(opt, smp, ctx, kept, names, n_reads, run.read_filter, &acted), opt.bam)) return code;
+        if (acted) ctx = kept;
+        tick("read filter");
+    }
     if (opt.sampling()) {   // the window to call is made of chosen reads, in a second context on the same device and stream
         jl_ctx *taken = nullptr;
         if (jl_ctx_create(opt.device, jl_ctx_stream(ctx), &taken) != JL_OK) die_jl(nullptr, "context of the sample");
@@ -159,7 +168,7 @@ int run_one_window(Run &run)
 // `juliet in.bam out...`: the sample onto the device(s) — its setup and --dump-msa while the contexts come up — then the mode
 int run_sample(const Options &opt, const TargetConfig &cfg, const std::string &cmdline, const Tick &tick)
 {
-    Run run{opt, cmdline, tick, ingest_options(opt), {}, {}, {}, {}};
+    Run run{opt, cmdline, tick, ingest_options(opt), {}, {}, {}, {}, {}};
     // the GPU context comes up (runtime start, stream, pinned blocks) while the host reads the BAM
     const bool need_gpu = !opt.outputs.empty() || opt.fuse_only;
     std::vector<CtxFuture> ctx_ups;

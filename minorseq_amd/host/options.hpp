@@ -59,6 +59,12 @@ struct Options {
     std::vector<std::string> mix;    // --mix b.bam[,c.bam...]: the minor clones; the positional BAM is the major one (doc/MIXDATA.md)
     double mix_perc = 1.0;           // --mix-perc P: percent of the mixture each minor clone gets
     bool sampling() const { return have_downsample || !mix.empty(); }
+    // The read filter (docs/SPEC.md §20): per-read counters of the ingested window on the device, a rule over them on the host, the
+    // kept reads gathered on the device (jl_msa_take) before --downsample
+    jl_read_rule read_rule = {0u, 0xFFFFFFFFu, -1.0, -1.0, -1.0};   // every rule off
+    uint32_t read_rule_set = 0;      // bit r: rule r (the order of jl_read_filter's failed[]) was given
+    std::string read_stats_out;      // --read-stats out.tsv: the counters of every read of the loaded sample
+    bool read_filter() const { return read_rule_set != 0 || !read_stats_out.empty(); }
     std::string batch;               // --batch samples.tsv: one `in.bam<TAB>out1[<TAB>out2]` per line, every other option for all of them
     struct BatchLine { unsigned line; std::string bam; std::vector<std::string> outputs; };
     std::vector<BatchLine> batch_lines;
@@ -160,6 +166,19 @@ struct Options {
         "                                      the reads are chosen by docs/SPEC.md section 12 (seed default 0; samples of one seed are\n"
         "                                      nested) and gathered on the device; N at or above the read count changes nothing.\n"
         "                                      With --batch: every sample.  Not with --windows, --devices a,b or --consensus\n"
+        "      --min-read-bases K  --max-read-mismatches K  --max-read-mismatch-perc x  --max-read-gap-perc x  --max-read-n-perc x\n"
+        "                                      the read filter (docs/SPEC.md section 20): the device counts, per read over the whole\n"
+        "                                      window, its bases, gaps, N cells, the bases in compared columns and the mismatches\n"
+        "                                      among those; a read is kept when bases >= K, mismatches <= K, 100 mismatches <= x\n"
+        "                                      compared, 100 gaps <= x (bases + gaps), 100 N <= x (bases + gaps + N), for every rule\n"
+        "                                      given.  The compare row is the config's referenceSequence over the window, else the\n"
+        "                                      majority consensus of the unfiltered window.  The kept reads are gathered on the\n"
+        "                                      device; --downsample then samples them.  The JSON gains input.read_filter.  No read\n"
+        "                                      kept is an input error (2).  With --batch: every sample.  Not with --windows,\n"
+        "                                      --devices a,b, --consensus, --mix, --call-insertions or as fuse\n"
+        "      --read-stats <out.tsv>          name, bases, gaps, masked, compared, mismatches of every read of the loaded sample,\n"
+        "                                      tab-separated, in input order, before any filter; needs no rule.  Refused where the\n"
+        "                                      read filter is, and with --batch\n"
         "      --mix b.bam[,c.bam...] [--mix-perc P]  a mixture as mixdata makes it (doc/MIXDATA.md): in.bam is the major clone, every\n"
         "                                      listed BAM a minor clone with P percent (default 1) of --downsample C reads (default\n"
         "                                      3000); source m is sampled with seed S + m.  A source with too few reads is an input\n"
@@ -327,6 +346,18 @@ Options parse(int argc, char **argv)
             if (o.mix.empty()) { std::cerr << "juliet: --mix names no BAM\n"; std::exit(1); }
         }
         else if (a == "--mix-perc") o.mix_perc = std::stod(need(i));
+        else if (a == "--min-read-bases") { o.read_rule.min_bases = (uint32_t)std::stoul(need(i)); o.read_rule_set |= 1u; }
+        else if (a == "--max-read-mismatches") { o.read_rule.max_mismatches = (uint32_t)std::stoul(need(i)); o.read_rule_set |= 2u; }
+        else if (a == "--max-read-mismatch-perc" || a == "--max-read-gap-perc" || a == "--max-read-n-perc") {
+            const std::string v = need(i);
+            char *end = nullptr;
+            const double x = std::strtod(v.c_str(), &end);
+            if (v.empty() || *end || !(x >= 0.0 && x <= 100.0)) { std::cerr << "juliet: " << a << " wants a percentage in [0, 100], not '" << v << "'\n"; std::exit(1); }
+            if (a == "--max-read-mismatch-perc") o.read_rule.max_mismatch_perc = x, o.read_rule_set |= 4u;
+            else if (a == "--max-read-gap-perc") o.read_rule.max_gap_perc = x, o.read_rule_set |= 8u;
+            else o.read_rule.max_masked_perc = x, o.read_rule_set |= 16u;
+        }
+        else if (a == "--read-stats") o.read_stats_out = need(i);
         else if (!a.empty() && a[0] == '-') { std::cerr << "juliet: unknown option " << a << "\n"; usage(1); }
         else pos.push_back(a);
     }
@@ -375,6 +406,7 @@ Options parse(int argc, char **argv)
         if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
         if (!o.batch.empty()) refuse("is not part of a batch (not with --batch)");
         if (o.sampling()) refuse("reads the insertions of the records that were ingested, not of a sample of them (drop --downsample / --mix)");
+        if (o.read_filter()) refuse("reads the insertions of the records that were ingested, not of the reads a filter keeps (drop the read filter / --read-stats)");
     }
     if (o.phase_insertions) {   // refused here, before any file is read or any GPU work (what --call-insertions refuses: above)
         auto refuse = [](const char *why) { std::cerr << "juliet: --phase-insertions " << why << "\n"; std::exit(1); };
@@ -382,6 +414,14 @@ Options parse(int argc, char **argv)
         if (!o.phasing) refuse("adds sites to the haplotypes of a phasing run (add --mode-phasing)");
         if (!o.call_insertions) refuse("phases the insertions that --call-insertions calls (add it)");
         if (o.rescue) refuse("leaves no insertion for --rescue-damaged to judge as damage (drop one of the two)");
+    }
+    if (o.read_filter()) {   // refused here, before any file is read or any GPU work: what --downsample refuses, and --mix
+        auto refuse = [](const char *why) { std::cerr << "juliet: the read filter (--min-read-bases, --max-read-*, --read-stats) " << why << "\n"; std::exit(1); };
+        if (as_fuse) refuse("is not an option of fuse");
+        if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
+        if (!o.consensus.empty()) refuse("carries no insertion counters into the kept reads: no consensus (drop --consensus)");
+        if (!o.mix.empty()) refuse("filters one sample, not the sources of a mixture (drop --mix)");
+        if (!o.batch.empty() && !o.read_stats_out.empty()) refuse("writes one --read-stats file for one sample (not with --batch)");
     }
     if (o.sampling()) {   // what sampling cannot be combined with is refused here, before any file is read or any GPU work
         auto refuse = [&](const char *why) { std::cerr << "juliet: " << (o.mix.empty() ? "--downsample " : "--mix ") << why << "\n"; std::exit(1); };

@@ -35,7 +35,8 @@ std::string haplotype_name(uint32_t h)  // [A-Z]{1}[a-z]?  (doc/JULIET.md:198)
 
 // The JSON document of one sample (doc/JULIET.md:61-107, 207-211); the HTML output is its rendering.
 Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam, const std::string &cmdline,
-                const std::vector<std::string> &names, uint64_t n_reads, const Results &R, const SamplingInfo *sampling = nullptr)
+                const std::vector<std::string> &names, uint64_t n_reads, const Results &R, const SamplingInfo *sampling = nullptr,
+                const ReadFilterInfo *read_filter = nullptr)
 {
     const TargetConfig &cfg = s.cfg;
     const uint32_t win_begin = s.win_begin, n_cols = s.n_cols;
@@ -60,6 +61,20 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
         Json sj = Json::object();
         sj.set("seed", Json::of((int64_t)sampling->seed)).set("sources", std::move(srcs));
         root.obj.back().second.set("sampling", std::move(sj));
+    }
+    if (read_filter && read_filter->ran) {   // (only with a rule or --read-stats: docs/SPEC.md section 20)
+        static const char *rules[5] = {"min_bases", "mismatches", "mismatch_perc", "gap_perc", "n_perc"};
+        const double given[5] = {(double)opt.read_rule.min_bases, (double)opt.read_rule.max_mismatches, opt.read_rule.max_mismatch_perc,
+                                 opt.read_rule.max_gap_perc, opt.read_rule.max_masked_perc};
+        Json rule = Json::object(), failed = Json::object();
+        for (uint32_t r = 0; r < 5; ++r) {
+            if (opt.read_rule_set >> r & 1u) rule.set(rules[r], Json::of(given[r]));
+            failed.set(rules[r], Json::of((int64_t)read_filter->failed[r]));
+        }
+        Json rf = Json::object();
+        rf.set("compare", Json::of(std::string(read_filter->reference ? "reference" : "majority"))).set("rule", std::move(rule));
+        rf.set("reads", Json::of((int64_t)read_filter->reads)).set("kept", Json::of((int64_t)read_filter->kept)).set("failed", std::move(failed));
+        root.obj.back().second.set("read_filter", std::move(rf));
     }
     Json tc = cfg.echo();
     tc.set("n_reads", Json::of((int64_t)n_reads));

@@ -584,6 +584,79 @@ int downsample_window(const Options &opt, const std::string &bam, jl_ctx *ctx, j
     return JL_OK;
 }
 
+// What the read filter did to a sample (docs/SPEC.md §20): the `read_filter` block of the JSON's input section, present when a rule
+// or --read-stats was given.
+struct ReadFilterInfo {
+    bool ran = false;
+    bool reference = false;      // the compare row: the config's referenceSequence over the window, or the majority consensus
+    uint64_t reads = 0, kept = 0;
+    uint64_t failed[5] = {0, 0, 0, 0, 0};
+};
+
+// The read filter on a window that is resident on `ctx` (its reads' names in `names`): the compare row, the per-read counters
+// (jl_read_stats_async), --read-stats, the rule (jl_read_filter), and — when it drops a read — the kept reads gathered into `taken`,
+// a second context of the device on the same stream; names / n_reads follow the indices.  *acted: the window to run is `taken` now.
+// An input failure: no read is kept, or the --read-stats file cannot be written.
+Status read_filter_window(const Options &opt, const SampleSetup &smp, jl_ctx *ctx, jl_ctx *taken, std::vector<std::string> &names, uint64_t &n_reads,
+                          ReadFilterInfo &info, bool *acted)
+{
+    Status st;
+    *acted = false;
+    auto device = [&](const char *what, jl_ctx *c, int rc) {
+        st.outcome = Outcome::device, st.what = what, st.ctx = c, st.rc = rc;
+        return st;
+    };
+    const uint32_t n_cols = smp.n_cols;
+    std::vector<uint8_t> compare(n_cols);
+    info.reference = smp.refcodes.size() >= (size_t)smp.win_begin + n_cols;
+    if (info.reference) std::copy_n(smp.refcodes.begin() + smp.win_begin, n_cols, compare.begin());
+    else {   // the majority of the window as ingested: a plain pileup, then its consensus
+        if (const int rc = jl_pileup_async(ctx, smp.genes.data(), (uint32_t)smp.genes.size(), smp.refp(), (uint32_t)smp.refcodes.size())) return device("pileup of the read filter", ctx, rc);
+        if (const int rc = jl_consensus_fetch(ctx, compare.data())) return device("consensus of the read filter", ctx, rc);
+    }
+    std::vector<uint32_t> stats((size_t)JL_READ_STATS * n_reads);
+    if (const int rc = jl_read_stats_async(ctx, compare.data())) return device("read stats", ctx, rc);
+    if (const int rc = jl_read_stats_fetch(ctx, stats.data())) return device("read stats fetch", ctx, rc);
+    info.ran = true;
+    info.reads = info.kept = n_reads;
+    if (!opt.read_stats_out.empty()) {
+        std::string text;
+        for (uint64_t i = 0; i < n_reads; ++i) {
+            text += names[(size_t)i];
+            for (uint32_t k = 0; k < JL_READ_STATS; ++k) text += "\t" + std::to_string(stats[(size_t)(k * n_reads + i)]);
+            text += "\n";
+        }
+        std::ofstream f(opt.read_stats_out, std::ios::binary);
+        f << text;
+        f.close();
+        if (!f) {
+            st.outcome = Outcome::input, st.what = "cannot write " + opt.read_stats_out + " for the reads";
+            return st;
+        }
+    }
+    if (!opt.read_rule_set) return st;
+    std::vector<uint32_t> idx((size_t)n_reads);
+    uint64_t kept = 0;
+    if (const int rc = jl_read_filter(stats.data(), n_reads, &opt.read_rule, idx.data(), &kept, info.failed)) return device("read filter", nullptr, rc);
+    info.kept = kept;
+    if (kept == 0) {
+        st.outcome = Outcome::input;
+        st.what = "the read filter keeps none of " + std::to_string(n_reads) + " reads (failed min_bases " + std::to_string(info.failed[0]) + ", mismatches " +
+                  std::to_string(info.failed[1]) + ", mismatch_perc " + std::to_string(info.failed[2]) + ", gap_perc " + std::to_string(info.failed[3]) +
+                  ", n_perc " + std::to_string(info.failed[4]) + ")";
+        return st;
+    }
+    if (kept == n_reads) return st;
+    const jl_take_part part = {ctx, idx.data(), kept};
+    if (const int rc = jl_msa_take(taken, &part, 1)) return device("take of the read filter", taken, rc);
+    std::vector<std::string> chosen((size_t)kept);
+    for (uint64_t j = 0; j < kept; ++j) chosen[(size_t)j].swap(names[idx[(size_t)j]]);
+    names.swap(chosen);
+    n_reads = kept;
+    *acted = true;
+    return st;
+}
+
 // --mix: the mixture of doc/MIXDATA.md in `taken`.  `major` holds the positional BAM's window; every BAM of the list is decoded and
 // ingested into a context of its own over the same window (same device and stream), jl_mix_counts says how many reads each source
 // gives, source m is sampled with seed S + m, and ONE jl_msa_take with the parts in argument order builds the mixture; names and
