@@ -154,7 +154,8 @@ int jl_msa_alloc(jl_ctx *ctx, uint64_t n_reads, uint32_t n_cols, uint32_t win_be
  * matrix; never copied, not freed by the ctx, and the caller may rewrite it between runs. */
 int jl_msa_adopt(jl_ctx *ctx, void *d_planes, uint64_t n_reads, uint32_t n_cols, uint64_t plane_stride,
                  uint32_t win_begin);
-/* Device-side transpose of a host by-row matrix uint8[n_reads][n_cols] (codes 0..6) into the resident layout. */
+/* Device-side transpose of a host by-row matrix uint8[n_reads][n_cols] (codes 0..6) into the resident layout; a code
+ * outside 0..6 is rejected as jl_msa_upload rejects it (JL_ERR_ARG, the same message, and no resident matrix is left). */
 int jl_msa_pack_rows(jl_ctx *ctx, const uint8_t *rows, uint64_t n_reads, uint32_t n_cols, uint32_t win_begin);
 /*
  * Aligned records -> resident matrix entirely on the device: cigar expansion (= X I D S H N; M is rejected,
@@ -264,6 +265,10 @@ int jl_sample_reads(uint64_t n_reads, uint64_t k, uint64_t seed, uint32_t *idx, 
 int jl_mix_counts(uint32_t n_sources, uint64_t coverage, double percentage, uint64_t *counts);
 /* The resident matrix back on the host in the interchange format, [n_cols][jl_col_stride(n_reads)] nibbles (tests). */
 int jl_msa_download(jl_ctx *ctx, uint8_t *colpacked, uint64_t bytes);
+/* The first `bytes` bytes of the resident planes as they are, [n_cols][3][plane_stride] (owned or adopted): one copy behind
+ * what the context's stream holds and a wait, no conversion — padding reads and whatever an adopted matrix holds past them
+ * included (tests).  JL_ERR_ARG: bytes > 3 * n_cols * plane_stride, or no resident matrix. */
+int jl_msa_download_planes(jl_ctx *ctx, uint8_t *planes, uint64_t bytes);
 /* Fill the resident matrix with synthetic reads, on the device. `ref` = n_cols base codes (host). */
 int jl_synth_fill(jl_ctx *ctx, const jl_synth_params *sp, const uint8_t *ref);
 /* The same reads seen through a WINDOW of a longer reference (BASELINE.json configs[3]/[4]: one reference whose

@@ -39,7 +39,7 @@ SITE_INS_NONE, SITE_INS_OTHER, SITE_INS_MAX_ALLELES = 0, 63, 62
 # every symbol include/juliet_hip.h declares (checked by tests/test_capi_exports.py)
 EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", "jl_ctx_destroy", "jl_last_error",
            "jl_sync", "jl_col_stride", "jl_plane_stride", "jl_msa_upload", "jl_msa_alloc", "jl_msa_adopt", "jl_msa_pack_rows",
-           "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_take", "jl_msa_take_async", "jl_sample_reads", "jl_mix_counts", "jl_msa_download", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
+           "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_take", "jl_msa_take_async", "jl_sample_reads", "jl_mix_counts", "jl_msa_download", "jl_msa_download_planes", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
            "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_read_stats_async", "jl_read_stats_fetch", "jl_read_filter", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_msa_track_insertion_reads", "jl_insertion_reads_fetch", "jl_sites_assemble_alleles", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_phase_async", "jl_phase_fetch",
            "jl_ctx_stream", "jl_run_async", "jl_run_wait", "jl_run_done", "jl_run_view_get", "jl_group_create", "jl_group_destroy",
            "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
@@ -207,6 +207,7 @@ def load_library(path=LIB_PATH):
     lib.jl_msa_track_insertions.argtypes = [vp, C.c_int]
     lib.jl_insertions_fetch.argtypes = [vp, vp, vp]
     lib.jl_msa_download.argtypes = [vp, vp, u64]
+    lib.jl_msa_download_planes.argtypes = [vp, vp, u64]
     lib.jl_msa_take.argtypes = [vp, vp, u32]
     lib.jl_msa_take_async.argtypes = [vp, vp, u32]
     lib.jl_sample_reads.argtypes = [u64, u64, u64, vp, C.POINTER(u64)]
@@ -543,6 +544,12 @@ class Juliet:
     def download_columns(self):
         out = np.empty((self.n_cols, self.col_stride), dtype=np.uint8)
         self._chk(self.lib.jl_msa_download(self.h, _p(out), out.nbytes))
+        return out
+
+    def download_planes(self):
+        """The resident planes as the device holds them, uint8[n_cols][3][plane_stride] (msa.pack_planes), padding included."""
+        out = np.empty((self.n_cols, 3, self.plane_stride), dtype=np.uint8)
+        self._chk(self.lib.jl_msa_download_planes(self.h, _p(out), out.nbytes))
         return out
 
     # ------------------------------------------------------------------ stages

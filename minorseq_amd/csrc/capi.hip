@@ -267,13 +267,21 @@ int jl_msa_pack_rows(jl_ctx *ctx, const uint8_t *rows, uint64_t n_reads, uint32_
     if (rc) return rc;
     uint8_t *d_rows = nullptr;
     JL_HIP(ctx, hipMalloc(&d_rows, (size_t)n_reads * n_cols));
-    hipError_t e = hipMemcpyAsync(d_rows, rows, (size_t)n_reads * n_cols, hipMemcpyHostToDevice, ctx->stream);
+    uint32_t bad = 0;
+    hipError_t e = hipMemsetAsync(ctx->d_nvar + 1, 0, 4, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rows, rows, (size_t)n_reads * n_cols, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
-        jl_launch_pack_rows(ctx, d_rows);
-        e = hipStreamSynchronize(ctx->stream);
+        jl_launch_pack_rows(ctx, d_rows, ctx->d_nvar + 1);
+        e = hipGetLastError();
     }
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, ctx->d_nvar + 1, 4, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     hipFree(d_rows);
     if (e != hipSuccess) return jl_fail(ctx, JL_ERR_DEVICE, "pack_rows: %s", hipGetErrorString(e));
+    if (bad) {   // as an upload: no matrix is left behind
+        free_msa(ctx);
+        return jl_fail(ctx, JL_ERR_ARG, "matrix holds a symbol code outside 0..6");
+    }
     return JL_OK;
 }
 
@@ -300,6 +308,17 @@ int jl_msa_download(jl_ctx *ctx, uint8_t *colpacked, uint64_t bytes)
     }
     hipFree(d_stage);
     if (e != hipSuccess) return jl_fail(ctx, JL_ERR_DEVICE, "download: %s", hipGetErrorString(e));
+    return JL_OK;
+}
+
+// The resident planes as they are, [n_cols][3][plane_stride]: one copy behind whatever the context's stream holds, no kernel.
+int jl_msa_download_planes(jl_ctx *ctx, uint8_t *planes, uint64_t bytes)
+{
+    if (!ctx || !planes || !ctx->d_msa) return JL_ERR_ARG;
+    if (bytes > 3u * (uint64_t)ctx->n_cols * ctx->plane_stride) return jl_fail(ctx, JL_ERR_ARG, "download larger than the matrix");
+    JL_HIP(ctx, hipSetDevice(ctx->device));
+    if (bytes) JL_HIP(ctx, hipMemcpyAsync(planes, ctx->d_msa, (size_t)bytes, hipMemcpyDeviceToHost, ctx->stream));
+    JL_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return JL_OK;
 }
 

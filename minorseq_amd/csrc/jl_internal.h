@@ -889,7 +889,7 @@ void jl_launch_compact_group(const jl_win_compact *h_wins, uint32_t n_win, hipSt
 void jl_launch_phase_group(const jl_win_phase *h_wins, uint32_t n_win, uint32_t max_blocks, hipStream_t st);
 void jl_launch_assign_group(const jl_win_phase *h_wins, uint32_t n_win, uint32_t max_read_blocks, bool to_host, hipStream_t st);
 void jl_launch_synth(jl_ctx *ctx, const jl_synth_plan *plan, const uint8_t *d_ref, uint32_t col0);
-void jl_launch_pack_rows(jl_ctx *ctx, const uint8_t *d_rows);
+void jl_launch_pack_rows(jl_ctx *ctx, const uint8_t *d_rows, uint32_t *d_bad);
 // interchange format (column-packed nibbles, include/juliet_hip.h) <-> the resident planes, `n` columns from column c0 on
 void jl_launch_nibbles_to_planes(jl_ctx *ctx, const uint8_t *d_nib, uint64_t nib_stride, uint32_t c0, uint32_t n, uint32_t *d_bad);
 void jl_launch_planes_to_nibbles(jl_ctx *ctx, uint8_t *d_nib, uint64_t nib_stride, uint32_t c0, uint32_t n);

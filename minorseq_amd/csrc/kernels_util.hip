@@ -64,20 +64,22 @@ __global__ __launch_bounds__(256) void synth_kernel(jl_synth_plan pl, const uint
 }
 
 // by-row uint8 codes -> planes.  thread (x = 8 reads, y = column): gathers 8 reads of one column; the quad's bytes leave
-// as dwords.  (A test-size path: the by-row reads are strided.)
+// as dwords.  A code outside 0..6 sets `bad`, as an upload's does (SPEC §1).  (A test-size path: the by-row reads are strided.)
 __global__ __launch_bounds__(256) void pack_rows_kernel(const uint8_t *__restrict__ rows, uint64_t n_reads,
                                                          uint32_t n_cols, uint8_t *__restrict__ msa,
-                                                         uint64_t plane_stride)
+                                                         uint64_t plane_stride, uint32_t *__restrict__ bad)
 {
     const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     const uint32_t c = blockIdx.y;
-    uint32_t w = 0;
+    uint32_t w = 0, any = 0;
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         const uint64_t i = t * 8u + r;
         const uint32_t s = i < n_reads ? rows[i * n_cols + c] : 6u;
+        any |= s > 6u;
         w |= (s & 7u) << (4 * r);
     }
+    if (any) atomicOr(bad, 1u);
     store_planes_quad(msa + (uint64_t)c * 3u * plane_stride, plane_stride, t, w);
 }
 
@@ -329,9 +331,9 @@ void jl_launch_synth(jl_ctx *ctx, const jl_synth_plan *plan, const uint8_t *d_re
                        ctx->n_reads, col0, ctx->n_cols);
 }
 
-void jl_launch_pack_rows(jl_ctx *ctx, const uint8_t *d_rows)
+void jl_launch_pack_rows(jl_ctx *ctx, const uint8_t *d_rows, uint32_t *d_bad)
 {
     dim3 grid((uint32_t)((ctx->plane_stride + 255u) / 256u), ctx->n_cols);
     hipLaunchKernelGGL(pack_rows_kernel, grid, dim3(256), 0, ctx->stream, d_rows, ctx->n_reads, ctx->n_cols,
-                       ctx->d_msa, ctx->plane_stride);
+                       ctx->d_msa, ctx->plane_stride, d_bad);
 }
