@@ -596,6 +596,45 @@ int jl_call_async(jl_ctx *ctx, const jl_params *prm, const uint64_t *drm_masks);
 int jl_call_fetch(jl_ctx *ctx, jl_variant *out, uint32_t cap, uint32_t *n_out);
 /* Device address and capacity (rows) of the resident variant table and of its row counter (uint32). */
 int jl_variant_table_device(jl_ctx *ctx, void **d_rows, void **d_count, uint32_t *cap_rows);
+/*
+ * The codon calls of a SAMPLE against a CONTROL instead of the error model (docs/SPEC.md section 21).  Both contexts hold a
+ * pileup (jl_pileup_async) of the same window with the same genes and reference sequence.  At every position with coverage in
+ * both, the reference codon is resolved as jl_call_async resolves it (the majority from the SAMPLE's histogram), and every other
+ * codon j the sample shows is tested by the table [[hs[j], cov_s - hs[j]], [hc[j], cov_c - hc[j]]]: p = P(X >= hs[j]), X ~
+ * Hypergeometric(cov_s + cov_c, hs[j] + hc[j], cov_s), one-sided greater; p_value = min(1, p * n_tests), called iff p_value <
+ * prm->alpha, then prm->min_perc / max_perc and `drm_masks` on the sample's frequency as in jl_call_async.  prm->err and
+ * prm->expected_round are not read.  Rows are jl_variant in the order of jl_call_fetch with expected := hc[j], the control's count.
+ * Stream order and lifetime: the launch runs on the sample's stream behind an event recorded on the control's stream, so the
+ * control's pileup need not be waited for; the control must not start another pileup (or anything else that rewrites its
+ * histograms) until jl_control_call_fetch or jl_sync of the SAMPLE has returned.  The result lives in buffers of the sample's
+ * context that no other call reads: jl_call_fetch, jl_phase_async(NULL) and the runs see nothing of it.  The masks and staged
+ * rows of the sample's call stage are its scratch, so it is ordered with jl_call_async as stages of one stream are.
+ * sample == control is allowed (and calls nothing: no count exceeds itself).
+ * JL_ERR_STATE: no pileup in either context; windows, position lists or reference codons that differ.  JL_ERR_ARG: a NULL
+ * argument (drm_masks may be NULL), contexts on different devices, prm->tail != 0 (the two-sided test is not defined for
+ * unequal rows here), alpha <= 0.  A refused call changes nothing; jl_last_error(sample) says why (jl_last_error(NULL) when
+ * sample is NULL).
+ */
+int jl_control_call_async(jl_ctx *sample, jl_ctx *control, const jl_params *prm, const uint64_t *drm_masks);
+/* Wait and copy the table out: rows[i] and control_coverage[i] = cov_c at that row's position.  *n_out = rows produced;
+ * JL_ERR_OVERFLOW if > cap (the first cap rows and coverages are valid), as jl_call_fetch.  cap == 0: both arrays may be NULL.
+ * JL_ERR_STATE: none was enqueued. */
+int jl_control_call_fetch(jl_ctx *sample, jl_variant *rows, uint32_t *control_coverage, uint32_t cap, uint32_t *n_out);
+typedef struct {
+    uint32_t count;             /* a: the sample's reads with the codon */
+    uint32_t coverage;          /* cov_s */
+    uint32_t control_count;     /* c */
+    uint32_t control_coverage;  /* cov_c */
+    uint32_t called;            /* 0 or 1 */
+    uint32_t pad_;
+    double p_value;             /* Bonferroni-adjusted, <= 1 */
+    double log_p;               /* ln of the unadjusted p */
+} jl_control_call;
+/* Host only (no device, no context): one table of jl_control_call_async through the very routine its kernel compiles, with
+ * prm->alpha, min_perc and max_perc.  n_tests: the Bonferroni factor, RESOLVED.  a == 0, cov_s == 0 or cov_c == 0: not called,
+ * p_value 1, log_p 0.  JL_ERR_ARG (jl_last_error(NULL) says which): a NULL argument; n_tests <= 0; prm->tail != 0; a > cov_s or
+ * c > cov_c. */
+int jl_control_test(uint32_t a, uint32_t cov_s, uint32_t c, uint32_t cov_c, const jl_params *prm, double n_tests, jl_control_call *out);
 
 /* ---------------------------------------------------------------- phase */
 

@@ -40,7 +40,7 @@ SITE_INS_NONE, SITE_INS_OTHER, SITE_INS_MAX_ALLELES = 0, 63, 62
 EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", "jl_ctx_destroy", "jl_last_error",
            "jl_sync", "jl_col_stride", "jl_plane_stride", "jl_msa_upload", "jl_msa_alloc", "jl_msa_adopt", "jl_msa_pack_rows",
            "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_take", "jl_msa_take_async", "jl_sample_reads", "jl_mix_counts", "jl_msa_download", "jl_msa_download_planes", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
-           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_read_stats_async", "jl_read_stats_fetch", "jl_read_filter", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_msa_track_insertion_reads", "jl_insertion_reads_fetch", "jl_sites_assemble_alleles", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_phase_async", "jl_phase_fetch",
+           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_read_stats_async", "jl_read_stats_fetch", "jl_read_filter", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_msa_track_insertion_reads", "jl_insertion_reads_fetch", "jl_sites_assemble_alleles", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_control_call_async", "jl_control_call_fetch", "jl_control_test", "jl_phase_async", "jl_phase_fetch",
            "jl_ctx_stream", "jl_run_async", "jl_run_wait", "jl_run_done", "jl_run_view_get", "jl_group_create", "jl_group_destroy",
            "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
            "jl_allgather_variants", "jl_allgather_variants_async", "jl_allgather_variants_async_many", "jl_allgather_variants_many", "jl_group_exchange_bind", "jl_group_exchange_collect", "jl_xwin_plan", "jl_xwin_assemble_local",
@@ -243,6 +243,9 @@ def load_library(path=LIB_PATH):
     lib.jl_call_async.argtypes = [vp, C.POINTER(Params), vp]
     lib.jl_call_fetch.argtypes = [vp, vp, u32, C.POINTER(u32)]
     lib.jl_variant_table_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u32)]
+    lib.jl_control_call_async.argtypes = [vp, vp, C.POINTER(Params), vp]
+    lib.jl_control_call_fetch.argtypes = [vp, vp, vp, u32, C.POINTER(u32)]
+    lib.jl_control_test.argtypes = [u32, u32, u32, u32, C.POINTER(Params), C.c_double, vp]
     lib.jl_phase_async.argtypes = [vp, vp, u32, u32]
     lib.jl_phase_fetch.argtypes = [vp] * 8 + [u32]
     lib.jl_run_async.argtypes = [vp, vp, u32, vp, u32, C.POINTER(Params), vp, C.c_int, u32, C.c_int]
@@ -713,6 +716,25 @@ class Juliet:
         self._chk(self.lib.jl_call_fetch(self.h, _p(out), cap, C.byref(n)))
         return out[: n.value].copy()
 
+    def control_call_async(self, control, params=None, drm_masks=None):
+        """jl_control_call_async (docs/SPEC.md §21) with this context as the sample: its pileup's codons against the counts of
+        `control`'s pileup of the same window.  Enqueues only; `control` must not start another pileup before control_call_fetch
+        or sync of this context."""
+        prm = params or default_params()
+        if drm_masks is not None:
+            drm_masks = np.ascontiguousarray(drm_masks, dtype=np.uint64)
+            assert len(drm_masks) == self.lib.jl_n_positions(self.h)
+        self._chk(self.lib.jl_control_call_async(self.h, control.h, C.byref(prm), _p(drm_masks)))
+
+    def control_call_fetch(self, cap=VARIANT_CAP):
+        """(rows, control_coverage) of the last control_call_async: VARIANT rows with expected = the control's count of the codon,
+        and the control's coverage at each row's position.  Beyond `cap` rows: JulietError (overflow), as call_fetch."""
+        out = np.zeros(cap, dtype=VARIANT)
+        cov = np.zeros(cap, dtype=np.uint32)
+        n = C.c_uint32()
+        self._chk(self.lib.jl_control_call_fetch(self.h, _p(out) if cap else None, _p(cov) if cap else None, cap, C.byref(n)))
+        return out[: n.value].copy(), cov[: n.value].copy()
+
     def variant_table_device(self):
         rows, cnt, cap = C.c_void_p(), C.c_void_p(), C.c_uint32()
         self._chk(self.lib.jl_variant_table_device(self.h, C.byref(rows), C.byref(cnt), C.byref(cap)))
@@ -1063,6 +1085,25 @@ def deletion_test(cnt, params, n_tests):
     if rc:
         raise JulietError(rc, "jl_deletion_test: " + lib.jl_last_error(None).decode())
     d = {name: getattr(out, name) for name, _ in DeletionCall._fields_ if name != "pad_"}
+    d["called"] = bool(d["called"])
+    return d
+
+
+class ControlCall(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("coverage", C.c_uint32), ("control_count", C.c_uint32), ("control_coverage", C.c_uint32),
+                ("called", C.c_uint32), ("pad_", C.c_uint32), ("p_value", C.c_double), ("log_p", C.c_double)]
+
+
+def control_test(a, cov_s, c, cov_c, params, n_tests):
+    """jl_control_test (host only, docs/SPEC.md §21): the table [[a, cov_s - a], [c, cov_c - c]] of a sample against a control
+    through the routine the kernel compiles: dict(count, coverage, control_count, control_coverage, called, p_value = min(1, p *
+    n_tests), log_p = ln p)."""
+    lib = load_library()
+    out = ControlCall()
+    rc = lib.jl_control_test(int(a), int(cov_s), int(c), int(cov_c), C.byref(params), float(n_tests), C.byref(out))
+    if rc:
+        raise JulietError(rc, "jl_control_test: " + lib.jl_last_error(None).decode())
+    d = {name: getattr(out, name) for name, _ in ControlCall._fields_ if name != "pad_"}
     d["called"] = bool(d["called"])
     return d
 

@@ -390,6 +390,23 @@ struct jl_del_args {
 };
 void jl_launch_codon_deletions(const jl_del_args *a, hipStream_t st);
 
+// ---- codon calls against a control's histograms (kernels_control.hip, capi_control.hip; docs/SPEC.md §21)
+struct jl_control_args {
+    jl_call_args A;            // alpha, n_tests, min_perc, max_perc, P (the error model's fields are not read)
+    const uint32_t *pos_gene, *pos_codon, *pos_col;   // [P], the sample's (the control's are equal)
+    const uint8_t *pos_refcfg; // [P]
+    const uint32_t *hist_s;    // [n_cols][64] the sample's histograms
+    const uint32_t *hist_c;    // ... and the control's
+    const uint64_t *drm;       // [P] or null
+    uint64_t *called;          // [P] scratch: the masks of the called codons
+    jl_variant *staged;        // [P][64] scratch: their rows before the ordered compaction
+    uint32_t *ctl_cov;         // [P] the control's coverage
+    jl_variant *rows;          // [cap]
+    uint32_t *n_rows;          // [1] rows needed
+    uint32_t cap, pad_;
+};
+void jl_launch_control_call(const jl_control_args *a, hipStream_t st);
+
 // ---- per-read counters over the whole window (kernels_readstats.hip, capi_readstats.hip; docs/SPEC.md §20)
 struct jl_readstats_shape;     // readstats_shape.h
 struct jl_readstats_args {
@@ -703,6 +720,18 @@ struct jl_ctx {
     // ---- jl_codon_deletions_async: a buffer of its own, grown on demand (capi_del.hip); no stage and no run touches it
     jl_dev_array<uint32_t> del_out;        // cnt [del_cols - 2][4]
     uint32_t del_cols = 0;                 // columns of the last call enqueued (0: none)
+
+    // ---- jl_control_call_async with this context as the SAMPLE: result buffers of its own, grown on demand (capi_control.hip); the
+    // masks and the staged rows of the call stage (d_called, d_staged) are its scratch, no stage result and no run sees the rest
+    jl_dev_array<jl_variant> ctl_rows;     // [JL_VARIANT_CAP]
+    jl_dev_array<uint32_t> ctl_out;        // rows needed [2], then the control's coverage [ctl_p]
+    std::vector<uint32_t> ctl_pos_gene, ctl_pos_codon;   // the positions of the last call enqueued: the fetch finds a row's by them
+    uint32_t ctl_p = 0;                    // ... and how many
+    bool ctl_done = false;
+    struct event_slot {                    // the control's pileup before the sample's launch, when their streams differ
+        hipEvent_t ev = nullptr;
+        ~event_slot() { if (ev) hipEventDestroy(ev); }
+    } ctl_ev;
 
     // ---- jl_read_stats_async: buffers of its own, grown on demand (capi_readstats.hip); no stage and no run touches them
     jl_upload_staging<uint8_t> rs_compare; // the compare row on its way to the device

@@ -50,7 +50,7 @@ inline std::string render_html(const Json &root)
     if (const Json *in = root.get("input")) {
         h += "<details open id=\"input\"><summary>Input data</summary><table id=\"input-table\">\n";
         for (auto &kv : in->obj)
-            if (kv.first != "sampling" && kv.first != "read_filter") h += "<tr><th>" + html_escape(kv.first) + "</th>" + td(num_str(&kv.second)) + "</tr>\n";
+            if (kv.first != "sampling" && kv.first != "read_filter" && kv.first != "control") h += "<tr><th>" + html_escape(kv.first) + "</th>" + td(num_str(&kv.second)) + "</tr>\n";
         h += "</table>\n";
         // --downsample / --mix: the seed and, per source, its file, its reads and how many of them were kept (docs/SPEC.md section 12)
         if (const Json *sp = in->get("sampling")) {
@@ -61,6 +61,10 @@ inline std::string render_html(const Json &root)
                     h += "<tr>" + td(x.get_str("file")) + td(num_str(x.get("reads"))) + td(num_str(x.get("kept"))) + "</tr>\n";
             h += "</table>\n";
         }
+        // --control: the control sample the codons were called against (docs/SPEC.md section 21)
+        if (const Json *ct = in->get("control"))
+            h += "<table id=\"control-table\">\n<tr><th>control</th><th>reads</th></tr>\n<tr>" + td(ct->get_str("file")) + td(num_str(ct->get("reads"))) +
+                 "</tr>\n</table>\n";
         // the read filter: its compare row, the rules that were given, and the reads each rule failed (docs/SPEC.md section 20)
         if (const Json *rf = in->get("read_filter")) {
             h += "<table id=\"read-filter-table\" data-compare=\"" + html_escape(rf->get_str("compare")) + "\">\n<tr><th>read filter (compare: " +
@@ -123,7 +127,11 @@ inline std::string render_html(const Json &root)
                     for (const Json &aa : vp.get("variant_amino_acids")->arr)
                         for (const Json &vc : aa.get("variant_codons")->arr) {
                             h += "<tr class=\"variant\" title=\"count=" + num_str(vc.get("count")) + " expected=" + num_str(vc.get("expected")) +
-                                 " pValue=" + num_str(vc.get("pValue")) + " log_pValue=" + num_str(vc.get("log_pValue")) + "\">" +
+                                 " pValue=" + num_str(vc.get("pValue")) + " log_pValue=" + num_str(vc.get("log_pValue")) +
+                                 (vc.get("control_count") ? " control_count=" + num_str(vc.get("control_count")) + " control_coverage=" +
+                                                                num_str(vc.get("control_coverage")) + " control_frequency=" + num_str(vc.get("control_frequency"))
+                                                          : std::string()) +
+                                 "\">" +
                                  td(vp.get_str("ref_codon")) + td(vp.get_str("ref_amino_acid")) + td(num_str(vp.get("ref_position"))) +
                                  td(aa.get_str("amino_acid")) + td(vc.get_str("codon")) + td(format_percent(100.0 * vc.get("frequency")->num)) +
                                  td(num_str(vp.get("coverage"))) + td(vc.get_str("known_drm"));

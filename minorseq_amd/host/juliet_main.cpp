@@ -58,12 +58,13 @@ struct Run {
     Results R;
     SamplingInfo sampling;
     ReadFilterInfo read_filter;
+    ControlInfo control;
 };
 
 // JSON / HTML (doc/JULIET.md:61-107, 207-211), and the end of the process
 int write_run(Run &run)
 {
-    const Json root = build_json(run.opt, run.smp, run.opt.bam, run.cmdline, run.load.names, run.load.n_reads, run.R, &run.sampling, &run.read_filter);
+    const Json root = build_json(run.opt, run.smp, run.opt.bam, run.cmdline, run.load.names, run.load.n_reads, run.R, &run.sampling, &run.read_filter, &run.control);
     const std::string failed = write_outputs(run.opt.outputs, root);
     if (!failed.empty()) { std::cerr << "juliet: cannot write " << failed << "\n"; return 2; }
     run.tick("json / html");
@@ -124,12 +125,19 @@ int run_one_window(Run &run)
     std::vector<uint64_t> drm_masks;
     if (opt.drm_only && drm_masks_of(ctx, in, drm_masks)) die_jl(ctx, "pileup");
     if (opt.fuse_only) return run_fuse(run, ctx);
-    if (jl_run_async(ctx, smp.genes.data(), (uint32_t)smp.genes.size(), smp.refp(), (uint32_t)smp.refcodes.size(), &smp.prm,
-                     opt.drm_only ? drm_masks.data() : nullptr, opt.phasing, opt.min_reads, opt.phasing) != JL_OK)
-        die_jl(ctx, "run");
-    tick("plan + enqueue");
-
-    if (const char *what = fetch_calls(ctx, true, R, tick)) die_jl(ctx, what);
+    if (!opt.control.empty()) {   // the codons against a control's counts (docs/SPEC.md §21), in the place of the error-model run
+        jl_ctx *control = nullptr, *failed = nullptr;
+        if (const int code = control_window(opt, run.io, smp, ctx, &control, run.control)) return code;
+        tick("control");
+        if (const char *what = run_control_calls(ctx, control, smp, opt.drm_only ? drm_masks.data() : nullptr, opt.phasing, opt.min_reads, R, tick, &failed))
+            die_jl(failed, what);
+    } else {
+        if (jl_run_async(ctx, smp.genes.data(), (uint32_t)smp.genes.size(), smp.refp(), (uint32_t)smp.refcodes.size(), &smp.prm,
+                         opt.drm_only ? drm_masks.data() : nullptr, opt.phasing, opt.min_reads, opt.phasing) != JL_OK)
+            die_jl(ctx, "run");
+        tick("plan + enqueue");
+        if (const char *what = fetch_calls(ctx, true, R, tick)) die_jl(ctx, what);
+    }
     if (!opt.consensus.empty())
         if (const int code = write_consensus(opt, ctx, R, win_begin, n_cols)) return code;
     if (opt.phasing)
@@ -168,7 +176,7 @@ int run_one_window(Run &run)
 // `juliet in.bam out...`: the sample onto the device(s) — its setup and --dump-msa while the contexts come up — then the mode
 int run_sample(const Options &opt, const TargetConfig &cfg, const std::string &cmdline, const Tick &tick)
 {
-    Run run{opt, cmdline, tick, ingest_options(opt), {}, {}, {}, {}, {}};
+    Run run{opt, cmdline, tick, ingest_options(opt), {}, {}, {}, {}, {}, {}};
     // the GPU context comes up (runtime start, stream, pinned blocks) while the host reads the BAM
     const bool need_gpu = !opt.outputs.empty() || opt.fuse_only;
     std::vector<CtxFuture> ctx_ups;

@@ -65,6 +65,7 @@ struct Options {
     uint32_t read_rule_set = 0;      // bit r: rule r (the order of jl_read_filter's failed[]) was given
     std::string read_stats_out;      // --read-stats out.tsv: the counters of every read of the loaded sample
     bool read_filter() const { return read_rule_set != 0 || !read_stats_out.empty(); }
+    std::string control;             // --control control.bam: the codons are called against this sample's counts, not the error model (docs/SPEC.md §21)
     std::string batch;               // --batch samples.tsv: one `in.bam<TAB>out1[<TAB>out2]` per line, every other option for all of them
     struct BatchLine { unsigned line; std::string bam; std::vector<std::string> outputs; };
     std::vector<BatchLine> batch_lines;
@@ -183,6 +184,16 @@ struct Options {
         "                                      listed BAM a minor clone with P percent (default 1) of --downsample C reads (default\n"
         "                                      3000); source m is sampled with seed S + m.  A source with too few reads is an input\n"
         "                                      error (2).  Not with --batch, --windows, --devices a,b or --consensus\n"
+        "      --control <control.bam>         call the codons against a control sample instead of the error model (docs/SPEC.md\n"
+        "                                      section 21): the control is loaded as in.bam is (--min-qv, --min-rq, --region, the read\n"
+        "                                      filter) over the same window, and every codon is tested one-sided by Fisher's exact\n"
+        "                                      test on its counts in the sample and in the control, times the Bonferroni factor.\n"
+        "                                      --min-perc, --max-perc and --drm-only act on the sample's frequency; --downsample\n"
+        "                                      samples in.bam only; --mode-phasing phases the control-called table.  The JSON gains\n"
+        "                                      input.control and, per variant codon, control_count (also `expected`),\n"
+        "                                      control_coverage and control_frequency.  Refused with exit status 2: --windows,\n"
+        "                                      --devices a,b, --batch, --mix, --call-deletions, --call-insertions, --fisher-tail\n"
+        "                                      two-sided, and as fuse\n"
         "      --batch <samples.tsv>           many samples in one process: one `in.bam<TAB>out1[<TAB>out2]` per line (blank lines\n"
         "                                      and lines starting with # skipped); every other option applies to every sample and\n"
         "                                      each sample gets the files a single run would write.  A sample that fails is named\n"
@@ -358,6 +369,7 @@ Options parse(int argc, char **argv)
             else o.read_rule.max_masked_perc = x, o.read_rule_set |= 16u;
         }
         else if (a == "--read-stats") o.read_stats_out = need(i);
+        else if (a == "--control") o.control = need(i);
         else if (!a.empty() && a[0] == '-') { std::cerr << "juliet: unknown option " << a << "\n"; usage(1); }
         else pos.push_back(a);
     }
@@ -414,6 +426,15 @@ Options parse(int argc, char **argv)
         if (!o.phasing) refuse("adds sites to the haplotypes of a phasing run (add --mode-phasing)");
         if (!o.call_insertions) refuse("phases the insertions that --call-insertions calls (add it)");
         if (o.rescue) refuse("leaves no insertion for --rescue-damaged to judge as damage (drop one of the two)");
+    }
+    if (!o.control.empty()) {   // refused here, before any file is read or any GPU work
+        auto refuse = [](const char *why) { std::cerr << "juliet: --control " << why << "\n"; std::exit(2); };
+        if (as_fuse) refuse("is not an option of fuse");
+        if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
+        if (!o.batch.empty()) refuse("is the control of one sample (not with --batch)");
+        if (!o.mix.empty()) refuse("tests a sample, not a mixture made for the error model (drop --mix)");
+        if (o.call_deletions || o.call_insertions) refuse("calls codons; deletions and insertions are tested against the error model only (drop --call-deletions / --call-insertions)");
+        if (o.fisher_tail != 0) refuse("tests an excess over the control, one-sided (drop --fisher-tail two-sided)");
     }
     if (o.read_filter()) {   // refused here, before any file is read or any GPU work: what --downsample refuses, and --mix
         auto refuse = [](const char *why) { std::cerr << "juliet: the read filter (--min-read-bases, --max-read-*, --read-stats) " << why << "\n"; std::exit(1); };

@@ -36,7 +36,7 @@ std::string haplotype_name(uint32_t h)  // [A-Z]{1}[a-z]?  (doc/JULIET.md:198)
 // The JSON document of one sample (doc/JULIET.md:61-107, 207-211); the HTML output is its rendering.
 Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam, const std::string &cmdline,
                 const std::vector<std::string> &names, uint64_t n_reads, const Results &R, const SamplingInfo *sampling = nullptr,
-                const ReadFilterInfo *read_filter = nullptr)
+                const ReadFilterInfo *read_filter = nullptr, const ControlInfo *control = nullptr)
 {
     const TargetConfig &cfg = s.cfg;
     const uint32_t win_begin = s.win_begin, n_cols = s.n_cols;
@@ -76,6 +76,8 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
         rf.set("reads", Json::of((int64_t)read_filter->reads)).set("kept", Json::of((int64_t)read_filter->kept)).set("failed", std::move(failed));
         root.obj.back().second.set("read_filter", std::move(rf));
     }
+    if (control && control->used)   // (only with --control: docs/SPEC.md section 21)
+        root.obj.back().second.set("control", Json::object().set("file", Json::of(control->file)).set("reads", Json::of((int64_t)control->reads)));
     Json tc = cfg.echo();
     tc.set("n_reads", Json::of((int64_t)n_reads));
     tc.set("window_begin", Json::of(win_begin + 1)).set("window_end", Json::of(win_begin + n_cols + 1));
@@ -120,6 +122,10 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
                     cj.set("frequency", Json::of((double)var[k].count / (double)var[k].coverage));
                     cj.set("count", Json::of(var[k].count));
                     cj.set("expected", Json::of(var[k].expected));
+                    if (R.controlled) {   // §21: the table's second row is the control's
+                        cj.set("control_count", Json::of(var[k].expected)).set("control_coverage", Json::of(R.control_cov[k]));
+                        cj.set("control_frequency", Json::of((double)var[k].expected / (double)R.control_cov[k]));
+                    }
                     cj.set("pValue", Json::of(var[k].p_value));
                     cj.set("log_pValue", Json::of(var[k].log_p));
                     cj.set("known_drm", Json::of(cfg.known_drms(g, aa_pos, aa)));

@@ -55,6 +55,10 @@ struct Results {
     // row of `var` that is variant k of the call (the rows by column: var_pos must not decrease, and genes may overlap)
     bool linked = false, link_skipped = false;
     std::vector<uint32_t> link_cols, link_var, link_var_pos, link_both, link_carry, link_joint;
+    // --control (docs/SPEC.md §21): `var` was called against a control; control_cov[k] = the control's coverage at the position of
+    // var[k], and var[k].expected the control's count of the codon
+    bool controlled = false;
+    std::vector<uint32_t> control_cov;
     // --call-deletions (docs/SPEC.md §16): the called positions in (gene, codon) order; ref_codon < 0: none exists at the position
     struct Deletion { uint32_t gene, codon_pos, col; int ref_codon; jl_deletion_call call; };
     bool deletions = false;
@@ -702,6 +706,66 @@ int mix_window(const Options &opt, const IngestOptions &io, jl_ctx *major, jl_ct
     if (jl_msa_take(taken, parts.data(), (uint32_t)n_src) != JL_OK) die_jl(taken, "mixture");
     n_reads = names.size();
     return 0;
+}
+
+// What --control loaded: the `control` block of the JSON's input section.
+struct ControlInfo {
+    bool used = false;
+    std::string file;
+    uint64_t reads = 0;   // of the control's window as it was counted: after --min-rq and the read filter
+};
+
+// --control: the control's BAM through the one loading path, into a context of its own on the device and stream of `sample`, over
+// the sample's window, with the sample's read filter (and no --read-stats file of its own).  *control_out: the context that holds
+// the control's window.  0, or the process's exit status (message printed): 2 an input error; a device error ends the process (3).
+int control_window(const Options &opt, const IngestOptions &io, const SampleSetup &smp, jl_ctx *sample, jl_ctx **control_out, ControlInfo &info)
+{
+    jl_ctx *c = nullptr;
+    if (jl_ctx_create(opt.device, jl_ctx_stream(sample), &c) != JL_OK) die_jl(nullptr, "context of the control");
+    SampleLoad load = load_sample(opt.control, io, {ctx_ready(c)}, opt, quiet_tick);
+    if (const int code = exit_code_of(load, opt.control)) return code;
+    if (const int code = exit_code_of(ingest_window(c, smp.n_cols, smp.win_begin, opt), opt.control)) return code;
+    uint64_t n_reads = load.n_reads;
+    if (opt.read_filter()) {
+        Options rules = opt;
+        rules.read_stats_out.clear();
+        jl_ctx *kept = nullptr;
+        if (jl_ctx_create(opt.device, jl_ctx_stream(sample), &kept) != JL_OK) die_jl(nullptr, "context of the control's kept reads");
+        ReadFilterInfo rf;
+        bool acted = false;
+        if (const int code = exit_code_of(read_filter_window(rules, smp, c, kept, load.names, n_reads, rf, &acted), opt.control)) return code;
+        if (acted) c = kept;
+    }
+    info.used = true;
+    info.file = opt.control;
+    info.reads = n_reads;
+    *control_out = c;
+    return 0;
+}
+
+// --control, in the place of the run: the pileups of both windows, the control call (docs/SPEC.md §21), its table and the sample's
+// column counts, and with `phasing` the phasing of that table.  nullptr, or the step that failed (*failed: the context to ask).
+const char *run_control_calls(jl_ctx *ctx, jl_ctx *control, const SampleSetup &smp, const uint64_t *drm_masks, bool phasing, uint32_t min_reads,
+                              Results &R, const Tick &tick, jl_ctx **failed)
+{
+    *failed = control;
+    if (jl_pileup_async(control, smp.genes.data(), (uint32_t)smp.genes.size(), smp.refp(), (uint32_t)smp.refcodes.size()) != JL_OK) return "pileup of the control";
+    *failed = ctx;
+    if (jl_pileup_async(ctx, smp.genes.data(), (uint32_t)smp.genes.size(), smp.refp(), (uint32_t)smp.refcodes.size()) != JL_OK) return "pileup";
+    if (jl_control_call_async(ctx, control, &smp.prm, drm_masks) != JL_OK) return "control call";
+    tick("plan + enqueue");
+    R.controlled = true;
+    R.var.resize(4096);
+    R.control_cov.resize(4096);
+    uint32_t nv = 0;
+    if (jl_control_call_fetch(ctx, R.var.data(), R.control_cov.data(), 4096, &nv) != JL_OK) return "control call fetch";
+    R.var.resize(nv);
+    R.control_cov.resize(nv);
+    tick("  wait for the calls + table");
+    if (jl_pileup_fetch(ctx, R.col_counts.data(), nullptr, nullptr, nullptr, nullptr, nullptr) != JL_OK) return "pileup fetch";
+    tick("  column counts");
+    if (phasing && jl_phase_async(ctx, R.var.data(), nv, min_reads) != JL_OK) return "phasing of the control-called table";
+    return nullptr;
 }
 
 }  // namespace
