@@ -346,6 +346,32 @@ int jl_phase_rescue_async(jl_ctx *ctx, const uint32_t *pos_cols, uint32_t n_pos,
  * JL_ERR_STATE: none was enqueued. */
 int jl_phase_rescue_fetch(jl_ctx *ctx, uint16_t *rescue, uint32_t *hap_reads, uint64_t *tally /* [4] */);
 /*
+ * Which reported haplotype a read is NEAREST to, within a mismatch budget (docs/SPEC.md §22): one sequencing or PCR error at one
+ * variant position gives a read a pattern of its own, which never reaches min_reads (JL_HAP_INSUFFICIENT); such a read is one
+ * codon away from the haplotype it came from.  pos_cols, pattern, pattern_stride, n_hap and min_positions are
+ * jl_phase_rescue_async's, as are INFORMATIVE and k_i.  Per read i: d(i, h) = informative positions at which the read's codon
+ * differs from pattern[h][p] (a codon position counts once, however many of its bases differ); dmin_i = min over h of d(i, h);
+ * n_i = haplotypes at dmin_i.  The first line that holds decides nearest[i] and dist[i]:
+ *   k_i < min_positions      JL_RESCUE_UNINFORMATIVE   0xFF
+ *   dmin_i > max_distance    JL_RESCUE_NONE            max_distance + 1
+ *   n_i == 1                 that h                    dmin_i
+ *   otherwise                JL_RESCUE_AMBIGUOUS       dmin_i
+ * Two equal pattern rows tie.  With max_distance 0, nearest is jl_phase_rescue_async's rescue.  Every read is evaluated.
+ * The contract is jl_phase_rescue_async's: the inputs are copied before the call returns; it enqueues on the context's stream
+ * into buffers of its own and touches nothing else — the matrix, earlier stage results, the captured graph and the last
+ * rescue's results stay as they are.  JL_ERR_STATE: no resident matrix.  JL_ERR_ARG (jl_last_error says which): what
+ * jl_phase_rescue_async refuses, and max_distance above JL_NEAREST_MAX_DISTANCE.  A refused call changes nothing: what an
+ * earlier call enqueued can still be fetched.
+ */
+enum { JL_NEAREST_MAX_DISTANCE = 7 };
+int jl_phase_nearest_async(jl_ctx *ctx, const uint32_t *pos_cols, uint32_t n_pos, const uint8_t *pattern,
+                           uint32_t pattern_stride, uint32_t n_hap, uint32_t min_positions, uint32_t max_distance);
+/* Wait and copy out, all of the last jl_phase_nearest_async (D = its max_distance): nearest[n_reads]; dist[n_reads];
+ * hap_reads[n_hap][D + 1], rows D + 1 apart = reads with nearest == h and dist == d; tally[4] = reads {assigned, ambiguous,
+ * none, uninformative}, summing to n_reads.  Any pointer may be NULL.  JL_ERR_STATE: none was enqueued. */
+int jl_phase_nearest_fetch(jl_ctx *ctx, uint16_t *nearest, uint8_t *dist, uint32_t *hap_reads /* [n_hap][D+1] */,
+                           uint64_t *tally /* [4] */);
+/*
  * Pairwise linkage of called variants over EVERY READ COVERING BOTH (docs/SPEC.md §15): do variant v and variant w occur on the
  * same molecules?  The co-occurrence of jl_phase_fetch counts the reads of the reported haplotypes only — reads that can be read
  * at all Vp positions, in groups of min_reads; a pair needs only the reads that can be read at its TWO positions.

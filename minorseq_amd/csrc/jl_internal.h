@@ -358,6 +358,26 @@ struct jl_rescue_args {
 };
 void jl_launch_phase_rescue(const jl_rescue_args *a, hipStream_t st);
 
+// ---- which reported haplotype a read is nearest to, within a mismatch budget (kernels_nearest.hip, capi_nearest.hip; docs/SPEC.md §22)
+// positions, haplotypes and the packed pattern are the rescue's (JL_RESCUE_POS_MAX, JL_RESCUE_HAP_PAD, pat4)
+#define JL_NEAREST_HIST_WORDS (JL_RESCUE_HAP_PAD * (JL_NEAREST_MAX_DISTANCE + 1u))   // hap_reads at its largest: [704][8]
+struct jl_nearest_args {
+    const uint8_t *msa;        // the window's bit planes
+    uint64_t plane_stride;     // ... and their stride (an adopted matrix brings its own)
+    uint64_t n_reads;
+    uint32_t n_runs;           // runs of 64 reads: ceil(n_reads / 64); 8 (n_runs) <= plane_stride
+    uint32_t n_pos, n_hap, min_positions;
+    uint32_t hap_pad;          // n_hap in whole chunks of 64
+    uint32_t max_distance;     // D <= JL_NEAREST_MAX_DISTANCE
+    const uint32_t *pos_cols;  // [n_pos], each + 2 < n_cols
+    const uint32_t *pat4;      // [ceil(n_pos / 4)][hap_pad], as jl_rescue_args
+    uint16_t *nearest;         // [n_reads]
+    uint8_t *dist;             // [n_reads]
+    uint32_t *hap_reads;       // [n_hap][D + 1], zeroed
+    unsigned long long *tally; // [4] assigned, ambiguous, none, uninformative; zeroed
+};
+void jl_launch_phase_nearest(const jl_nearest_args *a, hipStream_t st);
+
 // ---- pairwise linkage of variants over every read covering both (kernels_link.hip, capi_link.hip; docs/SPEC.md §15)
 #define JL_LINK_TILE 8u                    // rows of a wave's tile side: 8 x 8 pairs in the registers of every lane
 #define JL_LINK_BLOCK_TILE 16u             // ... and of a workgroup's: four waves, 2 x 2 wave tiles
@@ -710,6 +730,12 @@ struct jl_ctx {
     jl_dev_array<uint32_t> rescue_out;   // tally [4] as 8 words, hap_reads [JL_RESCUE_HAP_PAD], then rescue [rescue_n] 16 bits each
     uint64_t rescue_n = 0;               // reads of the last rescue enqueued (0: none)
     uint32_t rescue_h = 0;               // ... and its haplotypes
+
+    // ---- jl_phase_nearest_async: buffers of its own, grown on demand (capi_nearest.hip); no stage, no run and no rescue touches them
+    jl_upload_staging<uint32_t> nearest_in;   // pos_cols [n_pos], then pat4 (jl_nearest_args)
+    jl_dev_array<uint32_t> nearest_out;  // tally [4] as 8 words, hap_reads [JL_NEAREST_HIST_WORDS], nearest [nearest_n] 16 bits each, dist [nearest_n] bytes
+    uint64_t nearest_n = 0;              // reads of the last call enqueued (0: none)
+    uint32_t nearest_h = 0, nearest_d = 0;   // ... its haplotypes and its budget D
 
     // ---- jl_variant_linkage_async: buffers of its own, grown on demand (capi_link.hip); no stage and no run touches them
     jl_upload_staging<uint32_t> link_in;   // pos_cols [n_pos], var_first [n_pos + 1], var_codon [n_var] (jl_link_args)

@@ -292,6 +292,31 @@ inline std::string render_html(const Json &root)
                 }
             h += "</table>\n";
         }
+        if (const Json *ab = hb->get("absorb")) {   // --absorb-distance (docs/SPEC.md §22): the reads phasing left out, by their nearest haplotype
+            h += "\n<table id=\"hap-absorb\" data-max-distance=\"" + num_str(ab->get("max_distance")) + "\" data-min-positions=\"" +
+                 num_str(ab->get("min_positions")) + "\"><tr><th>Reads absorbed (at most " + num_str(ab->get("max_distance")) +
+                 " codons away, at least " + num_str(ab->get("min_positions")) + " informative positions)</th><th>#Insufficient</th><th>#Damaged</th></tr>\n";
+            static const char *ac[4][2] = {{"assigned_reads", "Assigned to the nearest haplotype"}, {"ambiguous_reads", "Ambiguous (several are nearest)"},
+                                           {"distant_reads", "Distant (none within the budget)"}, {"uninformative_reads", "Uninformative"}};
+            const Json *ins = ab->get("insufficient"), *dam = ab->get("damaged");
+            for (auto &c : ac)
+                h += "<tr data-key=\"" + std::string(c[0]) + "\"><th>" + c[1] + "</th>" + td(num_str(ins->get(c[0]))) + td(num_str(dam->get(c[0]))) + "</tr>\n";
+            for (size_t d = 0; d < ins->get("assigned_by_distance")->arr.size(); ++d)
+                h += "<tr data-key=\"assigned_by_distance\" data-distance=\"" + std::to_string(d) + "\"><th>- assigned at distance " + std::to_string(d) +
+                     "</th>" + td(num_str(&ins->get("assigned_by_distance")->arr[d])) + td(num_str(&dam->get("assigned_by_distance")->arr[d])) + "</tr>\n";
+            h += "</table>\n<table id=\"hap-absorbed\"><tr><th>Haplotype</th><th>% with absorbed</th><th>#Absorbed</th><th>#Absorbed damaged</th>"
+                 "<th>Absorbed read names</th></tr>\n";
+            if (haps)
+                for (const Json &hp : haps->arr) {
+                    if (!hp.get("absorbed_reads")) continue;
+                    h += "<tr>" + td(hp.get_str("name")) + td(format_hap_percent(100.0 * hp.get("frequency_with_absorbed")->num)) +
+                         td(num_str(hp.get("absorbed_reads"))) + td(num_str(hp.get("absorbed_damaged_reads"))) + "<td><details><summary>" +
+                         std::to_string(hp.get("absorbed_read_names")->arr.size()) + "</summary>";
+                    for (const Json &r : hp.get("absorbed_read_names")->arr) h += "<span class=\"rn\">" + html_escape(r.str) + "</span> ";
+                    h += "</details></td></tr>\n";
+                }
+            h += "</table>\n";
+        }
         h += "</details>\n";
     }
     // ---- --linkage (docs/SPEC.md §15): every pair of variants over the reads covering both; doubles as the JSON prints them

@@ -147,6 +147,10 @@ int run_one_window(Run &run)
         if (const char *what = fetch_rescue(ctx, opt.rescue_min, R)) die_jl(ctx, what);
         tick("rescue");
     }
+    if (opt.have_absorb) {
+        if (const char *what = fetch_absorb(ctx, opt.absorb_min, opt.absorb_distance, R)) die_jl(ctx, what);
+        tick("absorb");
+    }
     if (opt.linkage) {
         if (const char *what = fetch_linkage(ctx, R)) die_jl(ctx, what);
         tick("linkage");

@@ -40,6 +40,10 @@ struct Options {
     bool rescue = false;             // --rescue-damaged: which reported haplotype each damaged read agrees with (docs/SPEC.md §14)
     uint32_t rescue_min = 1;         // --rescue-min-positions K: informative positions a read needs to be judged at all
     bool have_rescue_min = false;
+    uint32_t absorb_distance = 0;    // --absorb-distance D: reads join the one reported haplotype nearest to them, D codons away at most (docs/SPEC.md §22)
+    bool have_absorb = false;
+    uint32_t absorb_min = 0;         // --absorb-min-positions K: informative positions a read needs to be judged at all (default D + 1)
+    bool have_absorb_min = false;
     bool linkage = false;            // --linkage: every pair of called variants over the reads covering both (docs/SPEC.md §15)
     bool call_deletions = false;     // --call-deletions: in-frame codon deletions at every evaluated position (docs/SPEC.md §16)
     bool phase_deletions = false;    // --phase-deletions: the called deletions as sites of the haplotypes (docs/SPEC.md §18)
@@ -113,6 +117,16 @@ struct Options {
         "                                      haplotype rescued_reads, rescued_read_names and frequency_with_rescued; with\n"
         "                                      --haplotype-fasta the rescued reads join their haplotype's consensus.  Follows\n"
         "                                      --downsample / --mix.  Not with --windows, --devices a,b, --batch or as fuse\n"
+        "      --absorb-distance D [--absorb-min-positions K]  with --mode-phasing: every read phasing leaves out — with a pattern of\n"
+        "                                      fewer than --min-reads reads (insufficient coverage), or damaged — is compared with\n"
+        "                                      the reported haplotypes at the positions where it can be read, K of them at least\n"
+        "                                      (default D + 1; docs/SPEC.md section 22): it is assigned to the haplotype it differs\n"
+        "                                      from at the fewest codon positions, when that is one haplotype alone and D positions\n"
+        "                                      (1 .. 7) at most; else it is ambiguous, distant or uninformative.  The haplotype\n"
+        "                                      block gains `absorb`, every haplotype absorbed_reads, absorbed_damaged_reads,\n"
+        "                                      absorbed_read_names and frequency_with_absorbed.  Independent of --rescue-damaged.\n"
+        "                                      Follows --downsample / --mix.  Not with --windows, --devices a,b, --batch,\n"
+        "                                      --phase-deletions, --phase-insertions or as fuse\n"
         "      --linkage                       pairwise linkage of the called variants over every read covering both (docs/SPEC.md\n"
         "                                      section 15), with and without --mode-phasing: read i is informative at a position iff\n"
         "                                      its three codes there are all < 4; it carries a variant iff it is informative at its\n"
@@ -339,6 +353,8 @@ Options parse(int argc, char **argv)
             }
         }
         else if (a == "--rescue-min-positions") { o.rescue_min = (uint32_t)std::stoul(need(i)); o.have_rescue_min = true; }
+        else if (a == "--absorb-distance") { o.absorb_distance = (uint32_t)std::stoul(need(i)); o.have_absorb = true; }
+        else if (a == "--absorb-min-positions") { o.absorb_min = (uint32_t)std::stoul(need(i)); o.have_absorb_min = true; }
         else if (a == "--ins-min-frac") o.ins_min_frac = std::stod(need(i));
         else if (a == "--ins-min-distance") o.ins_min_distance = (uint32_t)std::stoul(need(i));
         else if (a == "--dump-msa") o.dump_msa = need(i);
@@ -391,6 +407,18 @@ Options parse(int argc, char **argv)
         if (!o.phasing) refuse("assigns reads to the haplotypes of a phasing run (add --mode-phasing)");
         if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
         if (!o.batch.empty()) refuse("is not part of a batch (not with --batch)");
+    }
+    if (o.have_absorb || o.have_absorb_min) {   // refused here, before any file is read or any GPU work
+        auto refuse = [](const char *why) { std::cerr << "juliet: --absorb-distance D [--absorb-min-positions K] " << why << "\n"; std::exit(1); };
+        if (!o.have_absorb) refuse("--absorb-min-positions sets a threshold of --absorb-distance (add it)");
+        if (o.absorb_distance == 0 || o.absorb_distance > (uint32_t)JL_NEAREST_MAX_DISTANCE) refuse("wants a budget D of 1 to 7 codon positions");
+        if (o.have_absorb_min && o.absorb_min == 0) refuse("wants at least one informative position (--absorb-min-positions 0)");
+        if (as_fuse) refuse("are not options of fuse");
+        if (!o.phasing) refuse("assigns reads to the haplotypes of a phasing run (add --mode-phasing)");
+        if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
+        if (!o.batch.empty()) refuse("is not part of a batch (not with --batch)");
+        if (o.phase_deletions || o.phase_insertions) refuse("measures distances in codons; the sites of --phase-deletions / --phase-insertions are none (drop them)");
+        if (!o.have_absorb_min) o.absorb_min = o.absorb_distance + 1u;
     }
     if (o.linkage) {   // refused here, before any file is read or any GPU work
         auto refuse = [](const char *why) { std::cerr << "juliet: --linkage " << why << "\n"; std::exit(1); };

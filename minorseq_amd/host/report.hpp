@@ -267,6 +267,29 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
             }
             for (uint32_t h = 0; h < H; ++h) with_rescued_total += (uint64_t)hap_count[h] + rescued_members[h].size();
         }
+        // --absorb-distance: the insufficient and the damaged reads by what the rule of docs/SPEC.md §22 says of them
+        std::vector<std::vector<uint32_t>> absorbed_members(H);   // both kinds, in read order
+        std::vector<uint32_t> absorbed_insufficient(H, 0u), absorbed_damaged(H, 0u);
+        uint64_t absorb_cat[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};   // [insufficient, damaged][assigned, ambiguous, distant, uninformative]
+        std::vector<uint64_t> absorb_by_distance[2];
+        uint64_t with_absorbed_total = 0;
+        if (R.absorbed) {
+            for (auto &v : absorb_by_distance) v.assign(R.absorb_distance + 1u, 0);
+            if (ps.n_positions)   // (no variant position: nothing was phased, no read is insufficient or damaged, §8)
+                for (uint64_t i = 0; i < n_reads; ++i) {
+                    if (read_hap[i] != (uint16_t)JL_HAP_INSUFFICIENT && read_hap[i] != (uint16_t)JL_HAP_DAMAGED) continue;
+                    const uint32_t kind = read_hap[i] == (uint16_t)JL_HAP_DAMAGED ? 1u : 0u;
+                    const uint32_t r = R.nearest.empty() ? (uint32_t)JL_RESCUE_UNINFORMATIVE : R.nearest[i];
+                    if (r < H) {
+                        absorbed_members[r].push_back((uint32_t)i);
+                        (kind ? absorbed_damaged : absorbed_insufficient)[r]++;
+                        absorb_cat[kind][0]++;
+                        absorb_by_distance[kind][R.nearest_dist[i]]++;
+                    } else
+                        absorb_cat[kind][r == (uint32_t)JL_RESCUE_AMBIGUOUS ? 1 : r == (uint32_t)JL_RESCUE_NONE ? 2 : 3]++;
+                }
+            for (uint32_t h = 0; h < H; ++h) with_absorbed_total += (uint64_t)hap_count[h] + absorbed_members[h].size();
+        }
         // --phase-deletions / --phase-insertions with at least one site (docs/SPEC.md §18, §19): position p of the run is site p
         const bool with_sites = R.sites_phased && !R.sites.empty();
         Json hs = Json::array();
@@ -307,6 +330,16 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
                 hj.set("rescued_read_names", std::move(rr));
                 hj.set("frequency_with_rescued", Json::of(with_rescued_total ? (double)with / (double)with_rescued_total : 0.0));
             }
+            if (R.absorbed) {
+                const uint64_t with = (uint64_t)hap_count[h] + absorbed_members[h].size();
+                hj.set("absorbed_reads", Json::of(absorbed_insufficient[h]));
+                hj.set("absorbed_damaged_reads", Json::of(absorbed_damaged[h]));
+                Json ar = Json::array();
+                ar.arr.reserve(absorbed_members[h].size());
+                for (uint32_t i : absorbed_members[h]) ar.push(Json::of(names[i]));
+                hj.set("absorbed_read_names", std::move(ar));
+                hj.set("frequency_with_absorbed", Json::of(with_absorbed_total ? (double)with / (double)with_absorbed_total : 0.0));
+            }
             hs.push(std::move(hj));
         }
         hb.set("haplotypes", std::move(hs));
@@ -343,6 +376,22 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
                                  .set("ambiguous_reads", Json::of((uint32_t)rescue_cat[1]))
                                  .set("incompatible_reads", Json::of((uint32_t)rescue_cat[2]))
                                  .set("uninformative_reads", Json::of((uint32_t)rescue_cat[3])));
+        if (R.absorbed) {
+            Json ab = Json::object();
+            ab.set("max_distance", Json::of(R.absorb_distance)).set("min_positions", Json::of(R.absorb_min));
+            static const char *kinds[2] = {"insufficient", "damaged"};
+            for (uint32_t kind = 0; kind < 2u; ++kind) {
+                Json by = Json::array();
+                for (uint64_t c : absorb_by_distance[kind]) by.push(Json::of((uint32_t)c));
+                ab.set(kinds[kind], Json::object()
+                                        .set("assigned_reads", Json::of((uint32_t)absorb_cat[kind][0]))
+                                        .set("ambiguous_reads", Json::of((uint32_t)absorb_cat[kind][1]))
+                                        .set("distant_reads", Json::of((uint32_t)absorb_cat[kind][2]))
+                                        .set("uninformative_reads", Json::of((uint32_t)absorb_cat[kind][3]))
+                                        .set("assigned_by_distance", std::move(by)));
+            }
+            hb.set("absorb", std::move(ab));
+        }
         root.set("haplotype", std::move(hb));
     }
     if (R.linked) {   // --linkage (docs/SPEC.md §15): one entry per pair of rows v < w at different positions that some read covers both of

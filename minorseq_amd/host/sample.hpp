@@ -51,6 +51,12 @@ struct Results {
     bool rescued = false;
     uint32_t rescue_min = 0;
     std::vector<uint16_t> rescue;
+    // --absorb-distance (docs/SPEC.md §22): nearest[i] and dist[i] of every read by the run's own positions and haplotypes; empty
+    // when no call was made (no reported haplotype, or more positions asked for than the run has: every read is uninformative then)
+    bool absorbed = false;
+    uint32_t absorb_distance = 0, absorb_min = 0;
+    std::vector<uint16_t> nearest;
+    std::vector<uint8_t> nearest_dist;
     // --linkage (docs/SPEC.md §15): the three tables of ONE call over the table's distinct columns and its rows; link_var[k] = the
     // row of `var` that is variant k of the call (the rows by column: var_pos must not decrease, and genes may overlap)
     bool linked = false, link_skipped = false;
@@ -244,6 +250,24 @@ const char *fetch_rescue(jl_ctx *ctx, uint32_t min_positions, Results &R)
         return "rescue";
     R.rescue.resize(R.read_hap.size());
     if (jl_phase_rescue_fetch(ctx, R.rescue.data(), nullptr, nullptr) != JL_OK) return "rescue fetch";
+    return nullptr;
+}
+
+// --absorb-distance, after fetch_phase: one call of the rule of docs/SPEC.md §22 with the run's own positions and haplotypes.
+const char *fetch_absorb(jl_ctx *ctx, uint32_t min_positions, uint32_t max_distance, Results &R)
+{
+    R.absorbed = true;
+    R.absorb_min = min_positions;
+    R.absorb_distance = max_distance;
+    R.nearest.clear();
+    R.nearest_dist.clear();
+    if (R.ps.n_haplotypes == 0 || min_positions > R.ps.n_positions) return nullptr;
+    if (jl_phase_nearest_async(ctx, R.pos_cols.data(), R.ps.n_positions, R.hap_pattern.data(), (uint32_t)R.pat_stride, R.ps.n_haplotypes,
+                               min_positions, max_distance) != JL_OK)
+        return "absorb";
+    R.nearest.resize(R.read_hap.size());
+    R.nearest_dist.resize(R.read_hap.size());
+    if (jl_phase_nearest_fetch(ctx, R.nearest.data(), R.nearest_dist.data(), nullptr, nullptr) != JL_OK) return "absorb fetch";
     return nullptr;
 }
 
