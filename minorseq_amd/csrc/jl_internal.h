@@ -260,6 +260,17 @@ struct jl_call_group_args { jl_win_call w[JL_GROUP_MAX]; };
 struct jl_compact_group_args { jl_win_compact w[JL_GROUP_MAX]; };
 struct jl_phase_group_args { jl_win_phase w[JL_GROUP_MAX]; };
 struct jl_pileup_group_args { jl_win_pileup w[JL_GROUP_WINDOWS_MAX]; };
+// a window counted from its deviation index (deviation_index.h; kernels_pileup.hip pileup_index_body): one workgroup per plain chunk
+struct jl_win_index {
+    const uint8_t *msa;          // the planes: a plain chunk over the density bound is still counted from them
+    uint64_t plane_stride;
+    uint32_t n_reads, n_plain;   // n_plain = workgroups of the window's own grid
+    const uint4 *tab;            // [n_plain] {first column, first entry, entries (all ones: not indexed), -}
+    const uint32_t *entries;
+    const uint8_t *seed;         // [n_cols] the index seed
+    uint32_t *counts, *hist;
+};
+struct jl_index_group_args { jl_win_index w[JL_GROUP_MAX]; };
 // the Fisher stage of a window, evaluated by the pileup workgroup that counted the codon (one workgroup per chunk): the call
 // stage's own argument block + the positions by column
 struct jl_win_fold {
@@ -267,6 +278,7 @@ struct jl_win_fold {
     const uint32_t *col_head, *pos_next;
 };
 struct jl_pileup_fold_group_args { jl_win_pileup w[JL_GROUP_MAX]; jl_win_fold f[JL_GROUP_MAX]; };
+struct jl_index_fold_group_args { jl_win_index w[JL_GROUP_MAX]; jl_win_fold f[JL_GROUP_MAX]; };
 
 // exchange: the heads of the result blocks of up to JL_GATHER_MAX windows copied next to each other (one send buffer,
 // one all-gather for the launch)
@@ -883,6 +895,26 @@ struct jl_ctx {
     // of their own), jl_run_pileup_clock (the clock nodes come or go).
     uint64_t alloc_version = 0;
     uint64_t plan_version = 0;
+
+    // ---- the deviation index (deviation_index.h, capi_index.hip): a structure DERIVED from the planes, owned here, dropped in
+    // one place (jl_msa_touched) and by a new chunk table (build_plan).  Never built for a matrix that is analysed once.
+    uint64_t msa_gen = 1;              // the matrix generation: bumped by jl_msa_touched
+    uint32_t ix_runs = 0;              // runs enqueued on this generation and chunk table
+    bool ix_reserved = false;          // the buffers below are made for this generation and chunk table
+    bool ix_build_due = false;         // the run being enqueued is the second: the build goes behind its last node
+    bool ix_enqueued = false;          // ... and is on a stream (or done): the pinned record says which
+    uint32_t ix_last_form = 0;         // 1: the last enqueued run counted from the index
+    uint32_t ix_builds = 0;            // builds enqueued over the context's life
+    hipStream_t ix_stream = nullptr;   // where the build was enqueued
+    uint32_t ix_n_plain = 0, ix_n_rest = 0;
+    std::vector<uint64_t> h_chunks;    // host copy of the chunk table (build_plan)
+    jl_dev_array<uint4> d_ix_tab;      // [ix_n_plain] jl_win_index::tab
+    jl_dev_array<uint64_t> d_ix_rest;  // [ix_n_rest] chunk records of the chunks that are not plain: the plane kernel's table of an index-form run
+    jl_dev_array<uint32_t> d_ix_entries;
+    jl_dev_array<uint8_t> d_ix_seed;   // [n_cols]
+    jl_dev_array<uint32_t> d_ix_rec;   // [8] the build's record on the device; [4..] cursors of the build
+    event_slot ix_ev;                  // behind the build's last kernel: whoever drops the index waits for it
+    jl_pinned_array<volatile uint32_t> h_ix;   // [8] {state, entries, indexed chunks, generation (low word)}: stored by the build's last kernel
     int pileup_blocks_per_cu[16] = {0};  // occupancy per kernel variant, queried once
 
     // ---- timing
@@ -929,6 +961,17 @@ void jl_launch_call(jl_ctx *ctx, hipStream_t st, const jl_params *prm, double n_
 void jl_launch_compact(jl_ctx *ctx, hipStream_t st, bool plan, bool pack, bool signal);
 bool jl_launch_phase(jl_ctx *ctx, hipStream_t st, uint32_t min_reads, jl_phase_plan plan, bool signal);
 void jl_fill_call_args(jl_ctx *ctx, const jl_params *prm, double n_tests, jl_call_args *A);
+// the deviation index (capi_index.hip, kernels_index.hip, kernels_pileup.hip)
+void jl_msa_touched(jl_ctx *ctx);                    // the one invalidation point: every writer of d_msa reaches it
+void jl_index_drop(jl_ctx *ctx);                     // a new chunk table: the index and its run counter go, the generation stays
+int jl_index_count_run(jl_ctx *ctx);                 // a run is about to be enqueued: counts it; the second reserves the buffers (may wait)
+void jl_index_after_run(jl_ctx *ctx, hipStream_t st);    // ... it is enqueued: the build behind its last node, if due
+bool jl_index_usable(const jl_ctx *ctx);             // the pinned record says "built" for the current generation: no HIP call
+void jl_launch_index_build(jl_ctx *ctx, hipStream_t st);   // kernels_index.hip: the five launches of a build
+void jl_fill_win_index(jl_ctx *ctx, jl_win_index *w);
+void jl_fill_win_pileup_rest(jl_ctx *ctx, bool grouped, jl_win_pileup *w);   // the plane kernel's block over the chunks that are not plain
+void jl_launch_pileup_index(jl_ctx *ctx, hipStream_t st, const jl_win_call *call);   // one window: index kernel (+ plane kernel over the rest); call != null: folded
+int jl_launch_pileup_index_group(jl_ctx *const *ctxs, uint32_t n_win, const jl_win_index *h_wins, const jl_win_fold *h_fold, uint32_t max_plain, hipStream_t st);
 // group runs: fill one window's argument block / launch a stage once for `n_win` <= JL_GROUP_MAX windows (the blocks
 // travel by value in the kernel arguments)
 void jl_fill_win_pileup(jl_ctx *ctx, jl_win_pileup *w);

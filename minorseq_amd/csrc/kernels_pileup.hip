@@ -28,6 +28,7 @@
 #include <string.h>
 
 #include "call_eval.h"
+#include "deviation_index.h"
 #include "jl_internal.h"
 
 namespace {
@@ -222,6 +223,60 @@ __device__ __forceinline__ void pileup_planes_stream(const uint8_t JL_AS1 *plane
     }
 }
 
+// The end of a chunk's workgroup, behind the barrier that closes its counting: store (or add) the column counts, put the seed codon's
+// reads into their bin, store the histogram, and (FOLD) the Fisher stage from the histogram still in LDS.  Shared by the plane
+// kernels and the index kernels (pileup_index_body): what is downstream of the counters is one piece of code.
+template <int W, bool FOLD>
+__device__ __forceinline__ void pileup_tail(uint32_t (*s_hist)[64], uint32_t (*s_col)[6], uint32_t *s_match, const uint32_t (&g)[W + 2],
+                                            uint32_t c0, uint32_t ncols, uint32_t startf, uint32_t JL_AS1 *counts, uint32_t JL_AS1 *hist,
+                                            const jl_win_fold *fold)
+{
+    const uint32_t tid = threadIdx.x;
+    const bool excl = gridDim.y == 1;
+    if (tid < W * 6) {
+        const uint32_t j = tid / 6u, k = tid - j * 6u;
+        const uint32_t v = s_col[j][k];
+        if (j < ncols) {
+            if (excl) counts[(uint64_t)(c0 + j) * 6u + k] = v;
+            else if (v) atomicAdd((uint32_t *)(counts + (uint64_t)(c0 + j) * 6u + k), v);
+        }
+    }
+    if (tid < W && (startf & (1u << tid))) {
+        const uint32_t j = tid;
+        const uint32_t seed = (g[j] << 4) | (g[j + 1] << 2) | g[j + 2];
+        s_hist[j][seed] += s_match[j];   // reads equal to the seed codon were only counted, never binned
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < W * 64; i += 256) {
+        const uint32_t j = i >> 6;
+        const uint32_t v = s_hist[j][i & 63u];
+        if (startf & (1u << j)) {
+            if (excl) hist[(uint64_t)(c0 + j) * 64u + (i & 63u)] = v;
+            else if (v) atomicAdd((uint32_t *)(hist + (uint64_t)(c0 + j) * 64u + (i & 63u)), v);
+        }
+    }
+    if (FOLD) {
+        const jl_win_call &c = fold->c;
+        if (blockIdx.x == 0 && tid == 0 && c.meta) {   // counters of the phasing launch that follows on the stream (call_kernel's first block did this)
+            // (an index-form run of a window with a rest table does this twice, in the index launch and in the plane launch over the
+            // rest: harmless, nothing between the two writes these counters — the phasing launch comes behind both)
+            c.meta->n_occupied = 0;
+            c.meta->overflow = 0;
+            jl_phase_summary z = {0, 0, 0, 0, 0, 0, 0, 0};
+            c.meta->summary = z;
+        }
+        const uint32_t wid = tid >> 6, lane = tid & 63u;
+#pragma unroll
+        for (int j = 0; j < W; ++j) {
+            if (((uint32_t)j & 3u) != wid || !(startf & (1u << j))) continue;      // (wave-uniform)
+            const uint32_t col = c0 + (uint32_t)j;
+            const uint32_t h = s_hist[j][lane];
+            for (uint32_t p = fold->col_head[col]; p != 0xFFFFFFFFu; p = fold->pos_next[p])
+                jl_call_position<false>(c.A, p, col, h, c.pos_refcfg[p], c.pos_gene[p], c.pos_codon[p], c.drm, c.called, c.staged);
+        }
+    }
+}
+
 // FOLD (round 6): the Fisher stage of the chunk's codons in the workgroup that has just counted them — the histogram is still in
 // LDS — instead of a call launch that reads it back from HBM (8 us of a 64 us window, 20 of the 72 us an eight-window launch's
 // tail exposes).  Only where ONE workgroup counts a chunk (gridDim.y = 1).  Wave j & 3 takes the codon that begins at the chunk's
@@ -266,47 +321,7 @@ __device__ __forceinline__ void pileup_planes_body(const uint8_t JL_AS1 *planes,
     else
         pileup_planes_stream<W, NQ, false>(planes, plane_stride, n_cols, n_tiles, c0, ncols, startf, need_halo, g, s_hist, s_col, s_match);
     __syncthreads();
-    const bool excl = gridDim.y == 1;
-    if (tid < W * 6) {
-        const uint32_t j = tid / 6u, k = tid - j * 6u;
-        const uint32_t v = s_col[j][k];
-        if (j < ncols) {
-            if (excl) counts[(uint64_t)(c0 + j) * 6u + k] = v;
-            else if (v) atomicAdd((uint32_t *)(counts + (uint64_t)(c0 + j) * 6u + k), v);
-        }
-    }
-    if (tid < W && (startf & (1u << tid))) {
-        const uint32_t j = tid;
-        const uint32_t seed = (g[j] << 4) | (g[j + 1] << 2) | g[j + 2];
-        s_hist[j][seed] += s_match[j];   // reads equal to the seed codon were only counted, never binned
-    }
-    __syncthreads();
-    for (uint32_t i = tid; i < W * 64; i += 256) {
-        const uint32_t j = i >> 6;
-        const uint32_t v = s_hist[j][i & 63u];
-        if (startf & (1u << j)) {
-            if (excl) hist[(uint64_t)(c0 + j) * 64u + (i & 63u)] = v;
-            else if (v) atomicAdd((uint32_t *)(hist + (uint64_t)(c0 + j) * 64u + (i & 63u)), v);
-        }
-    }
-    if (FOLD) {
-        const jl_win_call &c = fold->c;
-        if (blockIdx.x == 0 && tid == 0 && c.meta) {   // counters of the phasing launch that follows on the stream (call_kernel's first block did this)
-            c.meta->n_occupied = 0;
-            c.meta->overflow = 0;
-            jl_phase_summary z = {0, 0, 0, 0, 0, 0, 0, 0};
-            c.meta->summary = z;
-        }
-        const uint32_t wid = tid >> 6, lane = tid & 63u;
-#pragma unroll
-        for (int j = 0; j < W; ++j) {
-            if (((uint32_t)j & 3u) != wid || !(startf & (1u << j))) continue;      // (wave-uniform)
-            const uint32_t col = c0 + (uint32_t)j;
-            const uint32_t h = s_hist[j][lane];
-            for (uint32_t p = fold->col_head[col]; p != 0xFFFFFFFFu; p = fold->pos_next[p])
-                jl_call_position<false>(c.A, p, col, h, c.pos_refcfg[p], c.pos_gene[p], c.pos_codon[p], c.drm, c.called, c.staged);
-        }
-    }
+    pileup_tail<W, FOLD>(s_hist, s_col, s_match, g, c0, ncols, startf, counts, hist, fold);
 }
 
 template <int W, int NQ>
@@ -344,6 +359,181 @@ __global__ __launch_bounds__(256) void pileup_fold_group_kernel(jl_pileup_fold_g
     pileup_planes_body<W, NQ, true>((const uint8_t JL_AS1 *)w.msa, w.plane_stride, w.n_cols, w.n_tiles, (const uint2 JL_AS1 *)w.chunks,
                                     (const uint32_t JL_AS1 *)w.guess32, (uint32_t JL_AS1 *)w.counts, (uint32_t JL_AS1 *)w.hist, &args.f[blockIdx.z]);
 }
+
+// ------------------------------------------------------------------------------- counting from the deviation index
+// A resident window that is run again and again keeps, per plain codon chunk, the list of the reads that differ from the chunk's
+// index seed anywhere in its three columns (deviation_index.h; built by kernels_index.hip behind the window's second run): about
+// 6 % of the reads of a CCS sample, 4 bytes each, against nine plane rows.  One workgroup per plain chunk:
+//   * a lane streams four entries per round with one 16-byte non-temporal load, the next round's in flight meanwhile;
+//   * column counts: per lane one 64-bit accumulator per column with a 9-bit field per code 0..6 — at most JL_IX_FLUSH_ROUNDS
+//     rounds x 4 entries = 508 <= 511 per field between flushes; a flush unpacks them two to a register (64 lanes x 508 < 2^16),
+//     sums over the wave by DPP and adds to LDS, as the plane kernel does;
+//   * an entry whose three codes are all bases is a valid codon other than the seed codon (it differs somewhere): one LDS atomic;
+//     an entry with a code >= 4 is outside the coverage, as `inv` says in the plane kernel;
+//   * the n_reads - E reads that are not in the list carry the seed base in every column: added to those bins and to the seed
+//     codon's count (s_match), from where pileup_tail takes over unchanged.  Padding reads are never in a list.
+// A plain chunk over the density bound has no list (tab[].z all ones): its workgroup counts it from the planes with a simple
+// walk — few registers, no prefetch: the path is rare and must not cost the common one its occupancy.
+// Registers: 58 VGPRs unfolded (eight waves per SIMD), 132 folded (the Fisher epilogue's); the plane path's 154 are why the two are
+// separate kernels.
+__device__ __forceinline__ void index_stream(const uint32_t JL_AS1 *list, uint32_t E, uint32_t (*s_hist)[64], uint32_t (*s_col)[6])
+{
+    const uint32_t tid = threadIdx.x;
+    const bool last_lane = (tid & 63u) == 63u;
+    const u32x4 JL_AS1 *src = (const u32x4 JL_AS1 *)list;
+    const uint32_t n_rounds = (E + 4u * 256u - 1u) / (4u * 256u);
+    u32x4 nxt = {0u, 0u, 0u, 0u};
+    if (tid * 4u < E) nxt = __builtin_nontemporal_load(src + tid);
+    uint32_t r = 0;
+    while (r < n_rounds) {
+        // (codes are 0..6: every producer of an OWNED matrix writes or validates them — jl_msa_upload and jl_msa_pack_rows refuse a
+        // matrix with a code outside 0..6, ingest, synth fill, take and the assemblies write none — and an adopted matrix, the only
+        // way caller-made planes get in, is never indexed: no field 7, which would sit at bit 63)
+        unsigned long long acc[3] = {0ull, 0ull, 0ull};
+        for (uint32_t it = 0; it < JL_IX_FLUSH_ROUNDS && r < n_rounds; ++it, ++r) {
+            const u32x4 cur = nxt;
+            const uint32_t first = (r * 256u + tid) * 4u;           // this lane's first entry of the round
+            const uint32_t nfirst = first + 4u * 256u;
+            if (nfirst < E) nxt = __builtin_nontemporal_load(src + (size_t)(r + 1u) * 256u + tid);
+            const uint32_t e4[4] = {cur.x, cur.y, cur.z, cur.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (first + (uint32_t)i >= E) continue;
+                const uint32_t e = e4[i];
+                const uint32_t a = (e >> 6) & 7u, b = (e >> 3) & 7u, c = e & 7u;
+                acc[0] += 1ull << (JL_IX_FIELD_BITS * a);
+                acc[1] += 1ull << (JL_IX_FIELD_BITS * b);
+                acc[2] += 1ull << (JL_IX_FIELD_BITS * c);
+                if ((e & 0x124u) == 0u) atomicAdd(&s_hist[0][(a << 4) | (b << 2) | c], 1u);   // no code >= 4: a valid codon
+            }
+        }
+        // ---- flush: codes 0..5 of each column (code 6, uncovered, is not reported), two 9-bit fields to a DPP sum
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const uint32_t m = (1u << JL_IX_FIELD_BITS) - 1u;
+            uint32_t p[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                p[k] = wave_sum(((uint32_t)(acc[j] >> (JL_IX_FIELD_BITS * 2u * k)) & m) | (((uint32_t)(acc[j] >> (JL_IX_FIELD_BITS * (2u * k + 1u))) & m) << 16));
+            if (last_lane) {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    if (p[k] & 0xFFFFu) atomicAdd(&s_col[j][2 * k], p[k] & 0xFFFFu);
+                    if (p[k] >> 16) atomicAdd(&s_col[j][2 * k + 1], p[k] >> 16);
+                }
+            }
+        }
+    }
+}
+
+// a plain chunk that has no list, from its nine plane rows: a lane takes 32 reads of every row per step
+__device__ __forceinline__ void index_dense_stream(const uint8_t JL_AS1 *planes, uint64_t plane_stride, uint32_t c0, const uint32_t (&g)[5],
+                                                   uint32_t (*s_hist)[64], uint32_t (*s_col)[6], uint32_t *s_match)
+{
+    const uint32_t tid = threadIdx.x;
+    const bool last_lane = (tid & 63u) == 63u;
+    const uint32_t n_words = (uint32_t)(plane_stride / 4u);
+    const uint32_t JL_AS1 *base = (const uint32_t JL_AS1 *)(planes + (uint64_t)c0 * 3u * plane_stride);
+    const uint64_t row = plane_stride / 4u;
+    uint32_t acc[3][6], match = 0, reads = 0;
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int k = 0; k < 6; ++k) acc[j][k] = 0;
+    for (uint32_t w = tid; w < n_words; w += 256u) {
+        uint32_t d[3][3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) d[j][k] = base[(uint64_t)(3 * j + k) * row + w];
+        reads += 32u;
+        uint32_t inv = 0, x = 0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const uint32_t b0 = d[j][0], b1 = d[j][1], b2 = d[j][2];
+            acc[j][0] += __popc(b0);
+            acc[j][1] += __popc(b1);
+            acc[j][2] += __popc(b2);
+            acc[j][3] += __popc(b0 & b1);
+            acc[j][4] += __popc(b0 & b2);
+            acc[j][5] += __popc(b1 & b2);
+            inv |= b2;
+            x |= (b1 ^ ((g[j] & 2u) ? 0xFFFFFFFFu : 0u)) | (b0 ^ ((g[j] & 1u) ? 0xFFFFFFFFu : 0u));
+        }
+        match += __popc(~(x | inv));
+        uint32_t rest = x & ~inv;
+        while (rest) {
+            const int b = __ffs((int)rest) - 1;
+            rest &= rest - 1;
+            const uint32_t idx = (((d[0][1] >> b) & 1u) << 5) | (((d[0][0] >> b) & 1u) << 4) | (((d[1][1] >> b) & 1u) << 3) |
+                                 (((d[1][0] >> b) & 1u) << 2) | (((d[2][1] >> b) & 1u) << 1) | ((d[2][0] >> b) & 1u);
+            atomicAdd(&s_hist[0][idx], 1u);
+        }
+    }
+    // (a lane's sums reach 2^15 at 2^23 reads: whole registers through the wave sums here, no packing)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const uint32_t nT = acc[j][3], nN = acc[j][4], nU = acc[j][5];
+        const uint32_t nC = acc[j][0] - nT - nN, nG = acc[j][1] - nT - nU, nD = acc[j][2] - nN - nU;
+        const uint32_t nA = reads - (nC + nG + nT + nD + nN + nU);
+        const uint32_t v[6] = {wave_sum(nA), wave_sum(nC), wave_sum(nG), wave_sum(nT), wave_sum(nD), wave_sum(nN)};
+        if (last_lane) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k)
+                if (v[k]) atomicAdd(&s_col[j][k], v[k]);
+        }
+    }
+    const uint32_t ms = wave_sum(match);
+    if (last_lane && ms) atomicAdd(&s_match[0], ms);
+}
+
+template <bool FOLD>
+__device__ __forceinline__ void pileup_index_body(const uint8_t JL_AS1 *planes, uint64_t plane_stride, uint32_t n_reads, const uint4 JL_AS1 *tab,
+                                                  const uint32_t JL_AS1 *entries, const uint8_t JL_AS1 *seed, uint32_t JL_AS1 *counts,
+                                                  uint32_t JL_AS1 *hist, const jl_win_fold *fold)
+{
+    __shared__ uint32_t s_hist[3][64];
+    __shared__ uint32_t s_col[3][6];   // A C G T - N
+    __shared__ uint32_t s_match[3];
+    const uint32_t tid = threadIdx.x;
+    const uint4 rec = tab[blockIdx.x];   // {first column, first entry, entries or all ones, -}
+    const uint32_t c0 = rec.x;
+    const uint32_t g[5] = {seed[c0] & 3u, seed[c0 + 1u] & 3u, seed[c0 + 2u] & 3u, 0u, 0u};   // (a plain chunk: c0 + 2 < n_cols)
+    for (uint32_t i = tid; i < 3 * 64; i += 256) (&s_hist[0][0])[i] = 0;
+    if (tid < 3 * 6) (&s_col[0][0])[tid] = 0;
+    if (tid < 3) s_match[tid] = 0;
+    __syncthreads();
+    if (rec.z != 0xFFFFFFFFu) {
+        index_stream(entries + rec.y, rec.z, s_hist, s_col);
+        if (tid < 3) atomicAdd(&s_col[tid][g[tid]], n_reads - rec.z);   // the reads not in the list: the seed base in every column
+        if (tid == 3) s_match[0] = n_reads - rec.z;                     // ... and the seed codon
+    } else {
+        index_dense_stream(planes, plane_stride, c0, g, s_hist, s_col, s_match);
+    }
+    __syncthreads();
+    pileup_tail<3, FOLD>(s_hist, s_col, s_match, g, c0, 3u, 1u, counts, hist, fold);
+}
+
+#define JL_INDEX_BODY(FOLD, w, f)                                                                                                     \
+    pileup_index_body<FOLD>((const uint8_t JL_AS1 *)(w).msa, (w).plane_stride, (w).n_reads, (const uint4 JL_AS1 *)(w).tab,            \
+                            (const uint32_t JL_AS1 *)(w).entries, (const uint8_t JL_AS1 *)(w).seed, (uint32_t JL_AS1 *)(w).counts,     \
+                            (uint32_t JL_AS1 *)(w).hist, f)
+
+__global__ __launch_bounds__(256) void pileup_index_kernel(jl_win_index w) { JL_INDEX_BODY(false, w, nullptr); }
+__global__ __launch_bounds__(256) void pileup_index_fold_kernel(jl_win_index w, jl_win_fold f) { JL_INDEX_BODY(true, w, &f); }
+__global__ __launch_bounds__(256) void pileup_index_group_kernel(jl_index_group_args args)
+{
+    const jl_win_index &w = args.w[blockIdx.z];
+    if (blockIdx.x >= w.n_plain) return;
+    JL_INDEX_BODY(false, w, nullptr);
+}
+__global__ __launch_bounds__(256) void pileup_index_fold_group_kernel(jl_index_fold_group_args args)
+{
+    const jl_win_index &w = args.w[blockIdx.z];
+    if (blockIdx.x >= w.n_plain) return;
+    JL_INDEX_BODY(true, w, &args.f[blockIdx.z]);
+}
+#undef JL_INDEX_BODY
 
 // Seed base per column for majority-codon mode: majority base among the first 2048 reads of the column.
 // (Any value is correct; a good seed keeps the codon compare on its fast path.)
@@ -513,6 +703,72 @@ int jl_launch_pileup_group(jl_ctx *const *ctxs, uint32_t n_win, const jl_win_pil
     memcpy(args.w, h_wins, sizeof(jl_win_pileup) * n_win);
     if (ctxs[0]->pileup_w == 3) hipLaunchKernelGGL((pileup_planes_group_kernel<3, 4>), dim3(max_chunks, 1, n_win), dim3(256), 0, st, args);
     else hipLaunchKernelGGL((pileup_planes_group_kernel<6, 2>), dim3(max_chunks, 1, n_win), dim3(256), 0, st, args);
+    return JL_OK;
+}
+
+// ---- runs that count from the deviation index: the index kernel over the plain chunks, the plane kernel over the rest (if any)
+void jl_fill_win_index(jl_ctx *ctx, jl_win_index *w)
+{
+    w->msa = ctx->d_msa;
+    w->plane_stride = ctx->plane_stride;
+    w->n_reads = (uint32_t)ctx->n_reads;
+    w->n_plain = ctx->ix_n_plain;
+    w->tab = ctx->d_ix_tab;
+    w->entries = ctx->d_ix_entries;
+    w->seed = ctx->d_ix_seed;
+    w->counts = ctx->d_counts;
+    w->hist = ctx->d_hist;
+}
+
+void jl_fill_win_pileup_rest(jl_ctx *ctx, bool grouped, jl_win_pileup *w)
+{
+    jl_fill_win_pileup(ctx, w);
+    w->n_tiles = planes_tiles(ctx, grouped);
+    w->n_chunks = ctx->ix_n_rest;
+    w->chunks = ctx->d_ix_rest.as<const uint2>();
+}
+
+// one window; `call` non-null: the Fisher stage in the epilogue (the caller has checked jl_pileup_can_fold).  The rest keeps the
+// single run's launch shape (read splits, load width), so whoever zeroes the counters for it still does.
+void jl_launch_pileup_index(jl_ctx *ctx, hipStream_t st, const jl_win_call *call)
+{
+    jl_win_index wi;
+    jl_win_pileup w;
+    jl_win_fold f;
+    jl_fill_win_index(ctx, &wi);
+    jl_fill_win_pileup_rest(ctx, false, &w);
+    if (call) jl_fill_win_fold(ctx, call, &f);
+    if (call) hipLaunchKernelGGL(pileup_index_fold_kernel, dim3(wi.n_plain), dim3(256), 0, st, wi, f);
+    else hipLaunchKernelGGL(pileup_index_kernel, dim3(wi.n_plain), dim3(256), 0, st, wi);
+    if (!w.n_chunks) return;
+    const int nq = planes_nq(ctx, false);   // (an indexed window's chunk table is three columns wide)
+    if (call) {
+        if (nq == 4) hipLaunchKernelGGL((pileup_fold_kernel<3, 4>), dim3(w.n_chunks, 1), dim3(256), 0, st, w, f);
+        else hipLaunchKernelGGL((pileup_fold_kernel<3, 2>), dim3(w.n_chunks, 1), dim3(256), 0, st, w, f);
+    } else {
+        const uint32_t rsplit = jl_pileup_rsplit(ctx);
+        if (nq == 4) hipLaunchKernelGGL((pileup_planes_kernel<3, 4>), dim3(w.n_chunks, rsplit), dim3(256), 0, st, w.msa, w.plane_stride, w.n_cols, w.n_tiles, w.chunks, w.guess32, w.counts, w.hist);
+        else hipLaunchKernelGGL((pileup_planes_kernel<3, 2>), dim3(w.n_chunks, rsplit), dim3(256), 0, st, w.msa, w.plane_stride, w.n_cols, w.n_tiles, w.chunks, w.guess32, w.counts, w.hist);
+    }
+}
+
+// the index kernel for the windows of one chunk of a group (h_fold non-null: folded); the plane launch over their rest tables is the caller's
+int jl_launch_pileup_index_group(jl_ctx *const *ctxs, uint32_t n_win, const jl_win_index *h_wins, const jl_win_fold *h_fold, uint32_t max_plain, hipStream_t st)
+{
+    (void)ctxs;
+    if (n_win == 0 || n_win > JL_GROUP_MAX || max_plain == 0) return JL_ERR_ARG;
+    if (h_fold) {
+        jl_index_fold_group_args args;
+        memset(&args, 0, sizeof args);
+        memcpy(args.w, h_wins, sizeof(jl_win_index) * n_win);
+        memcpy(args.f, h_fold, sizeof(jl_win_fold) * n_win);
+        hipLaunchKernelGGL(pileup_index_fold_group_kernel, dim3(max_plain, 1, n_win), dim3(256), 0, st, args);
+    } else {
+        jl_index_group_args args;
+        memset(&args, 0, sizeof args);
+        memcpy(args.w, h_wins, sizeof(jl_win_index) * n_win);
+        hipLaunchKernelGGL(pileup_index_group_kernel, dim3(max_plain, 1, n_win), dim3(256), 0, st, args);
+    }
     return JL_OK;
 }
 

@@ -13,7 +13,7 @@ import csv
 import statistics
 import sys
 
-KINDS = (("pileup", ("pileup_fold_group_kernel", "pileup_planes_group_kernel")), ("call", ("call_group_kernel",)),
+KINDS = (("pileup", ("pileup_fold_group_kernel", "pileup_planes_group_kernel", "pileup_index_fold_group_kernel", "pileup_index_group_kernel")), ("call", ("call_group_kernel",)),
          ("phase", ("phase_group_run_kernel",)), ("assign", ("phase_assign_group_kernel",)), ("done", ("done_group_kernel",)))
 
 
