@@ -16,10 +16,10 @@
 // Results are per window, exactly those of jl_run_async on each context: every context keeps its own result block,
 // per-read ids and completion word, so jl_run_wait / jl_run_view_get / jl_call_fetch / jl_phase_fetch work unchanged.
 //
-// Two forms, chosen per launch (group_pick_form).  FOLDED: the Fisher stage rides in the pileup launch's epilogue — one launch
-// and one read-back of the histograms less in the tail, which is what a launch whose tail is exposed gains from.  UNFOLDED: plain
-// pileup + call_group_kernel — the pileup's workgroups leave as soon as they have counted, which is what a launch gains from
-// whose tail runs beside other launches' pileups anyway (the epilogue then only holds workgroup slots those pileups want).
+// Two forms, chosen per launch (group_pick_form -> group_form.h).  FOLDED: the Fisher stage rides in the counting launch's epilogue —
+// one launch and one read-back of the histograms less in the tail, which is what a launch whose tail is exposed gains from.
+// UNFOLDED: plain pileup + call_group_kernel — the pileup's workgroups leave as soon as they have counted, which is what a launch
+// gains from whose tail runs beside other launches' pileups anyway (the epilogue then only holds workgroup slots those pileups want).
 // Which of the two a tail is going to be is read off the completion words of the device's other group launches at enqueue
 // time: a few loads from pinned host memory, no HIP call.  Both forms share call_eval.h and give the same bits; a group
 // captures a graph per form (and exchange parity): both with the first launch of a configuration where both can be taken.
@@ -27,7 +27,10 @@
 // Independently of that, the counting stage of a launch reads the planes or — every window of the group having a built deviation
 // index (kernels_index.hip) — the windows' entry lists (pileup_index_(fold_)group_kernel over the plain chunks, the plane kernel over
 // the rest tables where a window has one).  That choice is per launch and at enqueue time as well (group_pick_index); it is the
-// second bit of a graph's index.  The index-form graphs are captured in the launch that enqueues the builds: see there.
+// second bit of a graph's index, and it is made FIRST: the form's threshold is the counting form's.  A launch from the planes is
+// folded while fewer than JL_GROUP_FOLD_BELOW = 3 other group launches of the device are incomplete; a launch from the index while
+// fewer than JL_GROUP_FOLD_BELOW_INDEX = 1 are, i.e. only when it is alone (group_form.h says why).  The index-form graphs are
+// captured in the launch that enqueues the builds: see there.
 #include <string.h>
 
 #include <algorithm>
@@ -38,6 +41,7 @@
 
 #include <chrono>
 
+#include "group_form.h"
 #include "jl_comm_internal.h"
 #include "jl_internal.h"
 
@@ -45,13 +49,6 @@
 #ifndef JL_COMM_TIMEOUT_S
 #define JL_COMM_TIMEOUT_S 60
 #endif
-// A group launch is FOLDED while fewer than this many other group launches of its device are incomplete at enqueue time
-// (0: never, a large value: always).  Measured, not guessed: the sweep is in profiles/ (DESIGN.md "What bounds a step").
-#ifndef JL_GROUP_FOLD_BELOW
-#define JL_GROUP_FOLD_BELOW 3u
-#endif
-enum { JL_FORM_FOLDED = 0, JL_FORM_UNFOLDED = 1 };
-
 struct jl_group {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -115,6 +112,7 @@ static std::mutex &g_live_mu = *new std::mutex();
 static std::vector<jl_group *> &g_live = *new std::vector<jl_group *>();
 #ifdef JL_TUNING
 static uint64_t g_form_taken[2] = {0, 0};
+static uint64_t g_form_by_count[4] = {0, 0, 0, 0};   // [form | 2 x counting from the deviation index]
 #endif
 
 // Group launches of g's device, other than g's own, that were incomplete a moment ago.  A launch is complete when every window's
@@ -133,17 +131,20 @@ static uint32_t group_others_in_flight(const jl_group *g)
     return busy;
 }
 
-// FOLDED while this launch's tail is likely to be exposed: few other launches to run beside.  JL_NO_FOLD_CALL: never.
-// *other_reachable: the form not taken now is one a later launch of this group can take (enough other groups on the device).
-static int group_pick_form(const jl_group *g, bool *other_reachable)
+// The form of a launch of g that counts from the planes (ix false) or from the deviation index (ix true), from what is in flight
+// on g's device now: FOLDED while the launch's tail is likely to be exposed.  JL_NO_FOLD_CALL: never.  *index_choice: the same
+// decision for an index-form launch, whatever this one counts from — what the launch that enqueues the builds captures by.
+static jl_group_form_choice group_pick_form(const jl_group *g, bool ix, jl_group_form_choice *index_choice)
 {
-    *other_reachable = false;
-    if (!jl_fold_enabled()) return JL_FORM_UNFOLDED;
-    std::lock_guard<std::mutex> lk(g_live_mu);
-    uint32_t others = 0;
-    for (const jl_group *o : g_live) others += o != g && o->device == g->device;
-    *other_reachable = JL_GROUP_FOLD_BELOW > 0u && others >= JL_GROUP_FOLD_BELOW;
-    return group_others_in_flight(g) < JL_GROUP_FOLD_BELOW ? JL_FORM_FOLDED : JL_FORM_UNFOLDED;
+    const bool fold = jl_fold_enabled();
+    uint32_t others = 0, busy = 0;
+    if (fold) {
+        std::lock_guard<std::mutex> lk(g_live_mu);
+        for (const jl_group *o : g_live) others += o != g && o->device == g->device;
+        busy = group_others_in_flight(g);
+    }
+    *index_choice = jl_group_form_decide(busy, others, true, fold);
+    return ix ? *index_choice : jl_group_form_decide(busy, others, false, fold);
 }
 
 void jl_group_forget_ctx(const jl_ctx *ctx)
@@ -437,14 +438,17 @@ int jl_group_run_masked_async(jl_group *g, const jl_gene *genes, uint32_t n_gene
         g->h_phase[k].S.xhead = xh;
         g->h_compact[k].xhead = xh;
     }
-    // the form of THIS launch, from what is in flight now (the argument blocks above hold both forms' arguments)
-    bool other_reachable = false;
-    const int form = group_pick_form(g, &other_reachable);
+    // where THIS launch counts from: the index iff every window's pinned record says "built" NOW; a launch never waits for a build
+    const bool ix = group_pick_index(g);
+    // ... and its form, from what is in flight now and by the threshold of that counting form (the argument blocks above hold both
+    // forms' arguments)
+    jl_group_form_choice ix_choice;
+    const jl_group_form_choice choice = group_pick_form(g, ix, &ix_choice);
+    const int form = choice.form;
 #ifdef JL_TUNING
     __atomic_fetch_add(&g_form_taken[form], 1, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&g_form_by_count[form | (ix ? 2 : 0)], 1, __ATOMIC_RELAXED);
 #endif
-    // ... and where it counts from: the index iff every window's pinned record says "built" NOW; a launch never waits for a build
-    const bool ix = group_pick_index(g);
     const int gi = form | (ix ? 2 : 0);
     const bool graphs_on = !jl_env().no_graph;
     auto ensure_graph = [&](int f) {
@@ -455,18 +459,21 @@ int jl_group_run_masked_async(jl_group *g, const jl_gene *genes, uint32_t n_gene
     ensure_graph(gi);
     // The other form's graph too, with the first launch of a configuration rather than in the middle of a stream of launches
     // (a capture and its instantiation cost milliseconds) — where this group can ever take that form: the unfolded one needs
-    // JL_GROUP_FOLD_BELOW other groups on the device.  A group whose neighbours are created later captures it at first use.
-    if (other_reachable) ensure_graph(gi ^ 1);
+    // the counting form's threshold of other groups on the device.  A group whose neighbours are created later captures it at
+    // first use.
+    if (choice.other_reachable) ensure_graph(gi ^ 1);
     // The index-form graphs are captured by the launch that enqueues the builds (a window's second run), not by the first launch
     // that uses them: their pointers are known — the buffers were reserved at their bound in jl_run_prepare — and that launch is
-    // set-up in every caller that has one, while the first use may fall into a stream of launches.  bench.py --steps 20
-    // --warmup 5: set-up runs every window alone (run 1), then every full group once (run 2 of all its windows: build + this
-    // capture, collected with a stream sync); the next use of unit 0's full group is inside the timed region.
+    // set-up in every caller that has one, while the first use may fall into a stream of launches.  This launch counts from the
+    // planes, so the graphs go by what an INDEX-form launch would take now and could take later (ix_choice): the unfolded index
+    // graph as soon as ONE other group lives on the device.  bench.py --steps 20 --warmup 5: set-up runs every window alone
+    // (run 1), then every full group once (run 2 of all its windows: build + this capture of both index graphs — the other
+    // units' groups exist by then —, collected with a stream sync); the next use of unit 0's full group is inside the timed region.
     bool builds_due = false;
     for (const jl_ctx *c : g->ctxs) builds_due = builds_due || c->ix_build_due;
     if (builds_due && g->index_blocks) {
-        ensure_graph(form | 2);
-        if (other_reachable) ensure_graph((form ^ 1) | 2);
+        ensure_graph(ix_choice.form | 2);
+        if (ix_choice.other_reachable) ensure_graph((ix_choice.form ^ 1) | 2);
     }
     bool launched = g->graph_exec[par][gi] && hipGraphLaunch(g->graph_exec[par][gi], g->stream) == hipSuccess;
     if (!launched) {
@@ -663,6 +670,12 @@ __attribute__((visibility("default"))) void jl_tuning_group_forms(uint64_t *fold
 {
     if (folded) *folded = __atomic_load_n(&g_form_taken[JL_FORM_FOLDED], __ATOMIC_RELAXED);
     if (unfolded) *unfolded = __atomic_load_n(&g_form_taken[JL_FORM_UNFOLDED], __ATOMIC_RELAXED);
+}
+// ... and the same by what the launch counted from: out[0..3] = folded from the planes, unfolded from the planes, folded from the
+// deviation index, unfolded from the deviation index
+__attribute__((visibility("default"))) void jl_tuning_group_forms_by_count(uint64_t out[4])
+{
+    for (int i = 0; i < 4; ++i) out[i] = __atomic_load_n(&g_form_by_count[i], __ATOMIC_RELAXED);
 }
 // ... and the device-resident scalars of a context's last phasing run (jl_phase_meta: run counters, overflow bits, summary) as
 // bytes, behind everything on the run's stream: what a test compares before and after a call that must not touch them.

@@ -364,47 +364,73 @@ __global__ __launch_bounds__(256) void pileup_fold_group_kernel(jl_pileup_fold_g
 // A resident window that is run again and again keeps, per plain codon chunk, the list of the reads that differ from the chunk's
 // index seed anywhere in its three columns (deviation_index.h; built by kernels_index.hip behind the window's second run): about
 // 6 % of the reads of a CCS sample, 4 bytes each, against nine plane rows.  One workgroup per plain chunk:
-//   * a lane streams four entries per round with one 16-byte non-temporal load, the next round's in flight meanwhile;
+//   * a lane streams four entries per round with one 16-byte non-temporal load, DEPTH rounds held in registers: the loads of the
+//     first DEPTH rounds all go out before the first is consumed, and each register is loaded with round r + DEPTH as round r
+//     leaves it.  DEPTH = 1 in the unfolded kernels, which hide the chain of round trips behind eight workgroups per CU and must
+//     keep the registers for that; DEPTH = JL_IX_FOLD_DEPTH = 8 in the folded ones, whose Fisher epilogue leaves three workgroups
+//     per CU whatever the walk needs: 32 KB per workgroup in flight, a benchmark chunk's whole list (25 KB) in one round trip;
 //   * column counts: per lane one 64-bit accumulator per column with a 9-bit field per code 0..6 — at most JL_IX_FLUSH_ROUNDS
-//     rounds x 4 entries = 508 <= 511 per field between flushes; a flush unpacks them two to a register (64 lanes x 508 < 2^16),
-//     sums over the wave by DPP and adds to LDS, as the plane kernel does;
+//     rounds x 4 entries = 508 <= 511 per field between flushes (whole batches of DEPTH rounds: 127 rounds at depth 1, 120 at
+//     depth 8); a flush unpacks them two to a register (64 lanes x 508 < 2^16), sums over the wave by DPP and adds to LDS, as the
+//     plane kernel does;
 //   * an entry whose three codes are all bases is a valid codon other than the seed codon (it differs somewhere): one LDS atomic;
 //     an entry with a code >= 4 is outside the coverage, as `inv` says in the plane kernel;
 //   * the n_reads - E reads that are not in the list carry the seed base in every column: added to those bins and to the seed
 //     codon's count (s_match), from where pileup_tail takes over unchanged.  Padding reads are never in a list.
 // A plain chunk over the density bound has no list (tab[].z all ones): its workgroup counts it from the planes with a simple
 // walk — few registers, no prefetch: the path is rare and must not cost the common one its occupancy.
-// Registers: 58 VGPRs unfolded (eight waves per SIMD), 132 folded (the Fisher epilogue's); the plane path's 154 are why the two are
-// separate kernels.
+// Registers (gfx950, the compiler's kernel-resource-usage remarks; no scratch in any of the four): pileup_index_kernel and
+// pileup_index_group_kernel 58 VGPRs, eight waves per SIMD, as before the depth; pileup_index_fold_kernel and
+// pileup_index_fold_group_kernel 132 VGPRs, three waves per SIMD, at depth 8 as at depth 1 — the epilogue's live range sets the
+// figure, the walk's 32 registers of entries fit under it (a kernel stays at three waves up to 168).  The plane path's 154 are why
+// index and plane counting are separate kernels.
+#ifndef JL_IX_FOLD_DEPTH
+#define JL_IX_FOLD_DEPTH 8
+#endif
+template <int DEPTH>
 __device__ __forceinline__ void index_stream(const uint32_t JL_AS1 *list, uint32_t E, uint32_t (*s_hist)[64], uint32_t (*s_col)[6])
 {
+    static_assert(DEPTH >= 1 && DEPTH <= 8, "rounds held in registers");
+    // rounds between two flushes: whole batches, at most JL_IX_FLUSH_ROUNDS (127 at depth 1, 120 at depth 8: 480 <= 511 per field)
+    constexpr uint32_t FLUSH_BATCHES = JL_IX_FLUSH_ROUNDS / (uint32_t)DEPTH;
+    static_assert(FLUSH_BATCHES >= 1u && FLUSH_BATCHES * (uint32_t)DEPTH <= JL_IX_FLUSH_ROUNDS, "a 9-bit field never above 511");
     const uint32_t tid = threadIdx.x;
     const bool last_lane = (tid & 63u) == 63u;
     const u32x4 JL_AS1 *src = (const u32x4 JL_AS1 *)list;
     const uint32_t n_rounds = (E + 4u * 256u - 1u) / (4u * 256u);
-    u32x4 nxt = {0u, 0u, 0u, 0u};
-    if (tid * 4u < E) nxt = __builtin_nontemporal_load(src + tid);
+    // buf[k]: this lane's four entries of round r + k — the first batch's loads all go out before the first is consumed
+    u32x4 buf[DEPTH];
+#pragma unroll
+    for (int k = 0; k < DEPTH; ++k) {
+        buf[k] = u32x4{0u, 0u, 0u, 0u};
+        if (((uint32_t)k * 256u + tid) * 4u < E) buf[k] = __builtin_nontemporal_load(src + (size_t)k * 256u + tid);
+    }
     uint32_t r = 0;
     while (r < n_rounds) {
         // (codes are 0..6: every producer of an OWNED matrix writes or validates them — jl_msa_upload and jl_msa_pack_rows refuse a
         // matrix with a code outside 0..6, ingest, synth fill, take and the assemblies write none — and an adopted matrix, the only
         // way caller-made planes get in, is never indexed: no field 7, which would sit at bit 63)
         unsigned long long acc[3] = {0ull, 0ull, 0ull};
-        for (uint32_t it = 0; it < JL_IX_FLUSH_ROUNDS && r < n_rounds; ++it, ++r) {
-            const u32x4 cur = nxt;
-            const uint32_t first = (r * 256u + tid) * 4u;           // this lane's first entry of the round
-            const uint32_t nfirst = first + 4u * 256u;
-            if (nfirst < E) nxt = __builtin_nontemporal_load(src + (size_t)(r + 1u) * 256u + tid);
-            const uint32_t e4[4] = {cur.x, cur.y, cur.z, cur.w};
+        for (uint32_t it = 0; it < FLUSH_BATCHES && r < n_rounds; ++it, r += (uint32_t)DEPTH) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (first + (uint32_t)i >= E) continue;
-                const uint32_t e = e4[i];
-                const uint32_t a = (e >> 6) & 7u, b = (e >> 3) & 7u, c = e & 7u;
-                acc[0] += 1ull << (JL_IX_FIELD_BITS * a);
-                acc[1] += 1ull << (JL_IX_FIELD_BITS * b);
-                acc[2] += 1ull << (JL_IX_FIELD_BITS * c);
-                if ((e & 0x124u) == 0u) atomicAdd(&s_hist[0][(a << 4) | (b << 2) | c], 1u);   // no code >= 4: a valid codon
+            for (int k = 0; k < DEPTH; ++k) {
+                if (r + (uint32_t)k >= n_rounds) break;                  // (uniform: the batch's later rounds are past the list too)
+                const u32x4 cur = buf[k];
+                const uint32_t first = ((r + (uint32_t)k) * 256u + tid) * 4u;   // this lane's first entry of the round
+                // the register is free: round r + k + DEPTH goes out into it, DEPTH - 1 younger loads still in flight
+                const uint32_t nfirst = first + (uint32_t)DEPTH * 4u * 256u;
+                if (nfirst < E) buf[k] = __builtin_nontemporal_load(src + (size_t)(r + (uint32_t)k + (uint32_t)DEPTH) * 256u + tid);
+                const uint32_t e4[4] = {cur.x, cur.y, cur.z, cur.w};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    if (first + (uint32_t)i >= E) continue;
+                    const uint32_t e = e4[i];
+                    const uint32_t a = (e >> 6) & 7u, b = (e >> 3) & 7u, c = e & 7u;
+                    acc[0] += 1ull << (JL_IX_FIELD_BITS * a);
+                    acc[1] += 1ull << (JL_IX_FIELD_BITS * b);
+                    acc[2] += 1ull << (JL_IX_FIELD_BITS * c);
+                    if ((e & 0x124u) == 0u) atomicAdd(&s_hist[0][(a << 4) | (b << 2) | c], 1u);   // no code >= 4: a valid codon
+                }
             }
         }
         // ---- flush: codes 0..5 of each column (code 6, uncovered, is not reported), two 9-bit fields to a DPP sum
@@ -504,7 +530,7 @@ __device__ __forceinline__ void pileup_index_body(const uint8_t JL_AS1 *planes, 
     if (tid < 3) s_match[tid] = 0;
     __syncthreads();
     if (rec.z != 0xFFFFFFFFu) {
-        index_stream(entries + rec.y, rec.z, s_hist, s_col);
+        index_stream<FOLD ? JL_IX_FOLD_DEPTH : 1>(entries + rec.y, rec.z, s_hist, s_col);
         if (tid < 3) atomicAdd(&s_col[tid][g[tid]], n_reads - rec.z);   // the reads not in the list: the seed base in every column
         if (tid == 3) s_match[0] = n_reads - rec.z;                     // ... and the seed codon
     } else {
