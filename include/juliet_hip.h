@@ -372,6 +372,47 @@ int jl_phase_nearest_async(jl_ctx *ctx, const uint32_t *pos_cols, uint32_t n_pos
 int jl_phase_nearest_fetch(jl_ctx *ctx, uint16_t *nearest, uint8_t *dist, uint32_t *hap_reads /* [n_hap][D+1] */,
                            uint64_t *tally /* [4] */);
 /*
+ * Which reads are RECOMBINANTS of two reported haplotypes (docs/SPEC.md §23): PCR-mediated recombination (template switching) gives
+ * a molecule the codons of one clone at the left variant positions and of another at the right.  The rescue asks whether one
+ * haplotype agrees with the read everywhere and the nearest call counts differences wherever they lie; this call is sensitive to
+ * ORDER.  pos_cols, pattern, pattern_stride, n_hap and min_positions are jl_phase_rescue_async's, as are INFORMATIVE and k_i.
+ * Per read i and haplotype h: agree(i, h, p) iff p is open for the read or its codon there equals pattern[h][p];
+ * pre(i, h) = the smallest p with !agree, n_pos when there is none; suf(i, h) = n_pos - 1 - the largest p with !agree, n_pos when
+ * there is none; P_i = max over h of pre, S_i = max over h of suf, nP_i and nS_i = the haplotypes attaining each maximum.
+ * prefix[i] = P_i and suffix[i] = S_i, always.  The first line that holds decides left[i] and right[i]:
+ *   k_i < min_positions      JL_RESCUE_UNINFORMATIVE, both
+ *   P_i == n_pos             JL_RECOMB_WHOLE, both (some haplotype agrees with the whole read; then S_i == n_pos too)
+ *   P_i + S_i < n_pos        JL_RESCUE_NONE, both (no single breakpoint explains the read)
+ *   otherwise                left = the h at P_i if nP_i == 1, else JL_RESCUE_AMBIGUOUS; right likewise by S_i and nS_i
+ * The last line is a recombinant: every b in [n_pos - S_i, P_i] is a possible breakpoint, in front of position b.
+ * The contract is jl_phase_nearest_async's: the inputs are copied before the call returns; it enqueues on the context's stream
+ * into buffers of its own and touches nothing else — the matrix, earlier stage results, the captured graph, the last rescue's and
+ * the last nearest call's results stay as they are.  JL_ERR_STATE: no resident matrix.  JL_ERR_ARG (jl_last_error says which):
+ * what jl_phase_rescue_async refuses.  A refused call changes nothing: what an earlier call enqueued can still be fetched.
+ */
+enum { JL_RECOMB_WHOLE = 0xFFFA };
+int jl_phase_recombinants_async(jl_ctx *ctx, const uint32_t *pos_cols, uint32_t n_pos, const uint8_t *pattern,
+                                uint32_t pattern_stride, uint32_t n_hap, uint32_t min_positions);
+/* Wait and copy out, all of the last jl_phase_recombinants_async: left, right, prefix, suffix [n_reads] each;
+ * parent_reads[n_hap][2] = the reads with left == h (column 0) and right == h (column 1) among the recombinants with BOTH parents
+ * unique; tally[5] = reads {recombinant (both parents unique), ambiguous_parent, whole, none, uninformative}, summing to n_reads.
+ * Any pointer may be NULL.  JL_ERR_STATE: none was enqueued. */
+int jl_phase_recombinants_fetch(jl_ctx *ctx, uint16_t *left, uint16_t *right, uint16_t *prefix, uint16_t *suffix,
+                                uint32_t *parent_reads /* [n_hap][2] */, uint64_t *tally /* [5] */);
+/* Is a reported haplotype itself a recombinant of two more frequent ones (docs/SPEC.md §23)?  prefix / suffix are the largest
+ * common prefix / suffix length of row h with a candidate parent's row, left / right the lowest candidate attaining each. */
+typedef struct {
+    uint32_t flagged;        /* 1: candidates exist and prefix + suffix >= n_pos */
+    uint32_t left, right;    /* candidate parents (0 when there is no candidate) */
+    uint32_t prefix, suffix; /* (0 when there is no candidate) */
+} jl_hap_recombinant;
+/* Host only (no device, no context): out[n_hap] from pattern[n_hap] rows of n_pos codons, pattern_stride bytes apart, and
+ * hap_count[n_hap].  The candidate parents of h are the a != h with hap_count[a] >= min_parent_ratio * hap_count[h] (the product
+ * in IEEE double).  JL_ERR_ARG (jl_last_error(NULL) says which): a NULL array; min_parent_ratio < 1 (or NaN); n_pos 0 or above
+ * 4096; n_hap 0 or above JL_MAX_HAPLOTYPES; pattern_stride < n_pos. */
+int jl_haplotype_recombinants(const uint8_t *pattern, uint32_t pattern_stride, uint32_t n_hap, uint32_t n_pos,
+                              const uint32_t *hap_count, double min_parent_ratio, jl_hap_recombinant *out);
+/*
  * Pairwise linkage of called variants over EVERY READ COVERING BOTH (docs/SPEC.md §15): do variant v and variant w occur on the
  * same molecules?  The co-occurrence of jl_phase_fetch counts the reads of the reported haplotypes only — reads that can be read
  * at all Vp positions, in groups of min_reads; a pair needs only the reads that can be read at its TWO positions.

@@ -17,6 +17,7 @@ MAX_HAPLOTYPES = 702
 HAP_INSUFFICIENT = 0xFFFE
 HAP_DAMAGED = 0xFFFF
 RESCUE_UNINFORMATIVE, RESCUE_NONE, RESCUE_AMBIGUOUS = 0xFFFB, 0xFFFC, 0xFFFD   # jl_phase_rescue_async (docs/SPEC.md §14)
+RECOMB_WHOLE = 0xFFFA   # jl_phase_recombinants_async (docs/SPEC.md §23): some haplotype agrees with the whole read
 NEAREST_MAX_DISTANCE = 7   # jl_phase_nearest_async (docs/SPEC.md §22): the largest mismatch budget
 LINK_MAX = 1024   # jl_variant_linkage_async (docs/SPEC.md §15): positions, and variants, of one call
 VARIANT_CAP = 4096
@@ -41,7 +42,7 @@ SITE_INS_NONE, SITE_INS_OTHER, SITE_INS_MAX_ALLELES = 0, 63, 62
 EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", "jl_ctx_destroy", "jl_last_error",
            "jl_sync", "jl_col_stride", "jl_plane_stride", "jl_msa_upload", "jl_msa_alloc", "jl_msa_adopt", "jl_msa_pack_rows",
            "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_take", "jl_msa_take_async", "jl_sample_reads", "jl_mix_counts", "jl_msa_download", "jl_msa_download_planes", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
-           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_phase_nearest_async", "jl_phase_nearest_fetch", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_read_stats_async", "jl_read_stats_fetch", "jl_read_filter", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_msa_track_insertion_reads", "jl_insertion_reads_fetch", "jl_sites_assemble_alleles", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_control_call_async", "jl_control_call_fetch", "jl_control_test", "jl_phase_async", "jl_phase_fetch",
+           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_phase_nearest_async", "jl_phase_nearest_fetch", "jl_phase_recombinants_async", "jl_phase_recombinants_fetch", "jl_haplotype_recombinants", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_read_stats_async", "jl_read_stats_fetch", "jl_read_filter", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_msa_track_insertion_reads", "jl_insertion_reads_fetch", "jl_sites_assemble_alleles", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_control_call_async", "jl_control_call_fetch", "jl_control_test", "jl_phase_async", "jl_phase_fetch",
            "jl_ctx_stream", "jl_run_async", "jl_run_wait", "jl_run_done", "jl_run_view_get", "jl_group_create", "jl_group_destroy",
            "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_msa_index_info", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
            "jl_allgather_variants", "jl_allgather_variants_async", "jl_allgather_variants_async_many", "jl_allgather_variants_many", "jl_group_exchange_bind", "jl_group_exchange_collect", "jl_xwin_plan", "jl_xwin_assemble_local",
@@ -238,6 +239,9 @@ def load_library(path=LIB_PATH):
     lib.jl_phase_rescue_fetch.argtypes = [vp, vp, vp, vp]
     lib.jl_phase_nearest_async.argtypes = [vp, vp, u32, vp, u32, u32, u32, u32]
     lib.jl_phase_nearest_fetch.argtypes = [vp, vp, vp, vp, vp]
+    lib.jl_phase_recombinants_async.argtypes = [vp, vp, u32, vp, u32, u32, u32]
+    lib.jl_phase_recombinants_fetch.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    lib.jl_haplotype_recombinants.argtypes = [vp, u32, u32, u32, vp, C.c_double, vp]
     lib.jl_consensus_of_counts.argtypes = [vp, u32, vp]
     lib.jl_variant_linkage_async.argtypes = [vp, vp, u32, vp, vp, u32]
     lib.jl_variant_linkage_fetch.argtypes = [vp, vp, vp, vp]
@@ -668,6 +672,30 @@ class Juliet:
         tally = np.zeros(4, dtype=np.uint64)
         self._chk(self.lib.jl_phase_nearest_fetch(self.h, _p(nearest), _p(dist), _p(hap_reads), _p(tally)))
         return dict(nearest=nearest, dist=dist, hap_reads=hap_reads, tally=tally)
+
+    def phase_recombinants(self, pos_cols, hap_pattern, min_positions=1, wait=True):
+        """jl_phase_recombinants_async (docs/SPEC.md §23): which reads of the resident matrix are recombinants of two haplotypes of
+        hap_pattern[H, Vp] — one agrees with the read from the first position up to a breakpoint, another from there to the last.
+        Returns dict(left[n_reads], right[n_reads] uint16: h, RESCUE_UNINFORMATIVE, RECOMB_WHOLE, RESCUE_NONE or RESCUE_AMBIGUOUS;
+        prefix[n_reads], suffix[n_reads] uint16; parent_reads[H, 2]; tally[5] = recombinant, ambiguous_parent, whole, none,
+        uninformative); wait=False only enqueues on this context's stream and returns None (phase_recombinants_fetch brings the
+        arrays)."""
+        pos_cols = np.ascontiguousarray(pos_cols, dtype=np.uint32)
+        hap_pattern = np.ascontiguousarray(hap_pattern, dtype=np.uint8)
+        assert hap_pattern.ndim == 2 and hap_pattern.shape[1] == len(pos_cols)
+        self._chk(self.lib.jl_phase_recombinants_async(self.h, _p(pos_cols), len(pos_cols), _p(hap_pattern), hap_pattern.shape[1],
+                                                       hap_pattern.shape[0], int(min_positions)))
+        self._recomb_shape = (self.n_reads, hap_pattern.shape[0])
+        return self.phase_recombinants_fetch() if wait else None
+
+    def phase_recombinants_fetch(self):
+        n, h = getattr(self, "_recomb_shape", (0, 0))
+        per_read = {key: np.zeros(n, dtype=np.uint16) for key in ("left", "right", "prefix", "suffix")}
+        parent_reads = np.zeros((h, 2), dtype=np.uint32)
+        tally = np.zeros(5, dtype=np.uint64)
+        self._chk(self.lib.jl_phase_recombinants_fetch(self.h, *(_p(per_read[key]) for key in ("left", "right", "prefix", "suffix")),
+                                                       _p(parent_reads), _p(tally)))
+        return dict(per_read, parent_reads=parent_reads, tally=tally)
 
     def variant_linkage(self, pos_cols, var_pos, var_codon, wait=True):
         """jl_variant_linkage_async (docs/SPEC.md §15): pairwise linkage of variants over every read covering both.  pos_cols[P]
@@ -1117,6 +1145,26 @@ def linkage_stats(both, carry, joint, var_pos, v, w):
     if rc:
         raise JulietError(rc, "jl_linkage_stats: " + lib.jl_last_error(None).decode())
     return {name: getattr(out, name) for name, _ in LinkPair._fields_ if name != "pad_"}
+
+
+class HapRecombinant(C.Structure):
+    _fields_ = [("flagged", C.c_uint32), ("left", C.c_uint32), ("right", C.c_uint32), ("prefix", C.c_uint32), ("suffix", C.c_uint32)]
+
+
+def haplotype_recombinants(hap_pattern, hap_count, min_parent_ratio=2.0):
+    """jl_haplotype_recombinants (host only, docs/SPEC.md §23): for every row h of hap_pattern[H, Vp], whether it is a common prefix
+    of one row and a common suffix of another that together cover it, both among the rows with hap_count >= min_parent_ratio *
+    hap_count[h]: a list of dict(flagged, left, right, prefix, suffix)."""
+    lib = load_library()
+    hap_pattern = np.ascontiguousarray(hap_pattern, dtype=np.uint8)
+    hap_count = np.ascontiguousarray(hap_count, dtype=np.uint32)
+    assert hap_pattern.ndim == 2 and len(hap_count) == hap_pattern.shape[0]
+    out = (HapRecombinant * max(1, hap_pattern.shape[0]))()
+    rc = lib.jl_haplotype_recombinants(_p(hap_pattern), hap_pattern.shape[1], hap_pattern.shape[0], hap_pattern.shape[1], _p(hap_count),
+                                       float(min_parent_ratio), C.byref(out))
+    if rc:
+        raise JulietError(rc, "jl_haplotype_recombinants: " + lib.jl_last_error(None).decode())
+    return [dict(flagged=bool(o.flagged), left=o.left, right=o.right, prefix=o.prefix, suffix=o.suffix) for o in out[: hap_pattern.shape[0]]]
 
 
 class DeletionCall(C.Structure):

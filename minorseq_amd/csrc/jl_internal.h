@@ -390,6 +390,26 @@ struct jl_nearest_args {
 };
 void jl_launch_phase_nearest(const jl_nearest_args *a, hipStream_t st);
 
+// ---- which reads are recombinants of two reported haplotypes (kernels_recomb.hip, capi_recomb.hip; docs/SPEC.md §23)
+// positions, haplotypes and the packed pattern are the rescue's (JL_RESCUE_POS_MAX, JL_RESCUE_HAP_PAD, pat4); the second
+// direction walks the positions from the last to the first, and gets its own copy of both in that order
+#define JL_RECOMB_HIST_WORDS (JL_RESCUE_HAP_PAD * 2u)   // parent_reads at its largest: [704][2]
+struct jl_recomb_args {
+    const uint8_t *msa;        // the window's bit planes
+    uint64_t plane_stride;     // ... and their stride (an adopted matrix brings its own)
+    uint64_t n_reads;
+    uint32_t n_runs;           // runs of 64 reads: ceil(n_reads / 64); 8 (n_runs) <= plane_stride
+    uint32_t n_pos, n_hap, min_positions;
+    uint32_t hap_pad, pad_;    // n_hap in whole chunks of 64
+    const uint32_t *pos_cols[2];  // [n_pos], each + 2 < n_cols: [0] ascending, [1] the same descending
+    const uint32_t *pat4[2];      // [ceil(n_pos / 4)][hap_pad], as jl_rescue_args: [0] of pattern, [1] of pattern with every row reversed
+    uint16_t *left, *right;    // [n_reads] each
+    uint16_t *prefix, *suffix; // [n_reads] each
+    uint32_t *parent_reads;    // [n_hap][2], zeroed
+    unsigned long long *tally; // [5] recombinant, ambiguous_parent, whole, none, uninformative; zeroed
+};
+void jl_launch_phase_recombinants(const jl_recomb_args *a, hipStream_t st);
+
 // ---- pairwise linkage of variants over every read covering both (kernels_link.hip, capi_link.hip; docs/SPEC.md §15)
 #define JL_LINK_TILE 8u                    // rows of a wave's tile side: 8 x 8 pairs in the registers of every lane
 #define JL_LINK_BLOCK_TILE 16u             // ... and of a workgroup's: four waves, 2 x 2 wave tiles
@@ -748,6 +768,12 @@ struct jl_ctx {
     jl_dev_array<uint32_t> nearest_out;  // tally [4] as 8 words, hap_reads [JL_NEAREST_HIST_WORDS], nearest [nearest_n] 16 bits each, dist [nearest_n] bytes
     uint64_t nearest_n = 0;              // reads of the last call enqueued (0: none)
     uint32_t nearest_h = 0, nearest_d = 0;   // ... its haplotypes and its budget D
+
+    // ---- jl_phase_recombinants_async: buffers of its own, grown on demand (capi_recomb.hip); no stage, no run, no rescue and no nearest call touches them
+    jl_upload_staging<uint32_t> recomb_in;   // pos_cols [n_pos] and pat4, then both again in descending order (jl_recomb_args)
+    jl_dev_array<uint32_t> recomb_out;   // tally [5] as 12 words, parent_reads [JL_RECOMB_HIST_WORDS], left, right, prefix, suffix [recomb_n] 16 bits each
+    uint64_t recomb_n = 0;               // reads of the last call enqueued (0: none)
+    uint32_t recomb_h = 0;               // ... and its haplotypes
 
     // ---- jl_variant_linkage_async: buffers of its own, grown on demand (capi_link.hip); no stage and no run touches them
     jl_upload_staging<uint32_t> link_in;   // pos_cols [n_pos], var_first [n_pos + 1], var_codon [n_var] (jl_link_args)

@@ -317,6 +317,31 @@ inline std::string render_html(const Json &root)
                 }
             h += "</table>\n";
         }
+        if (const Json *rc = hb->get("recombinants")) {   // --flag-recombinants (docs/SPEC.md §23): reads and haplotypes that are one haplotype, then another
+            h += "\n<table id=\"hap-recombinants\" data-min-positions=\"" + num_str(rc->get("min_positions")) + "\" data-parent-ratio=\"" +
+                 num_str(rc->get("parent_ratio")) + "\"><tr><th>Reads as recombinants of two haplotypes (at least " + num_str(rc->get("min_positions")) +
+                 " informative positions)</th><th>#Insufficient</th><th>#Damaged</th></tr>\n";
+            static const char *cc[5][2] = {{"recombinant_reads", "Recombinant (both parents unique)"}, {"ambiguous_parent_reads", "Recombinant, a parent ambiguous"},
+                                           {"whole_reads", "Whole (a haplotype agrees throughout)"}, {"unexplained_reads", "Unexplained by one breakpoint"},
+                                           {"uninformative_reads", "Uninformative"}};
+            const Json *ins = rc->get("insufficient"), *dam = rc->get("damaged");
+            for (auto &c : cc)
+                h += "<tr data-key=\"" + std::string(c[0]) + "\"><th>" + c[1] + "</th>" + td(num_str(ins->get(c[0]))) + td(num_str(dam->get(c[0]))) + "</tr>\n";
+            h += "</table>\n<table id=\"hap-recombinant-pairs\"><tr><th>Left</th><th>Right</th><th>#Reads</th><th>#Insufficient</th><th>#Damaged</th>"
+                 "<th>Breakpoint from</th><th>Breakpoint to</th></tr>\n";
+            for (const Json &pr : rc->get("pairs")->arr)
+                h += "<tr>" + td(pr.get_str("left")) + td(pr.get_str("right")) + td(num_str(pr.get("reads"))) + td(num_str(pr.get("insufficient_reads"))) +
+                     td(num_str(pr.get("damaged_reads"))) + td(num_str(pr.get("breakpoint_min"))) + td(num_str(pr.get("breakpoint_max"))) + "</tr>\n";
+            h += "</table>\n<table id=\"hap-putative-recombinants\"><tr><th>Haplotype</th><th>Putative recombinant</th><th>Left</th><th>Right</th>"
+                 "<th>Prefix</th><th>Suffix</th></tr>\n";
+            if (haps)
+                for (const Json &hp : haps->arr) {
+                    const Json *of = hp.get("recombinant_of");
+                    h += "<tr>" + td(hp.get_str("name")) + td(of ? "yes" : "no") + td(of ? of->get_str("left") : "") + td(of ? of->get_str("right") : "") +
+                         td(of ? num_str(of->get("prefix")) : "") + td(of ? num_str(of->get("suffix")) : "") + "</tr>\n";
+                }
+            h += "</table>\n";
+        }
         h += "</details>\n";
     }
     // ---- --linkage (docs/SPEC.md §15): every pair of variants over the reads covering both; doubles as the JSON prints them

@@ -151,6 +151,10 @@ int run_one_window(Run &run)
         if (const char *what = fetch_absorb(ctx, opt.absorb_min, opt.absorb_distance, R)) die_jl(ctx, what);
         tick("absorb");
     }
+    if (opt.flag_recombinants) {
+        if (const char *what = fetch_recombinants(ctx, opt.recomb_min, opt.recomb_ratio, R)) die_jl(ctx, what);
+        tick("recombinants");
+    }
     if (opt.linkage) {
         if (const char *what = fetch_linkage(ctx, R)) die_jl(ctx, what);
         tick("linkage");

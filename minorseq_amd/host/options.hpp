@@ -44,6 +44,11 @@ struct Options {
     bool have_absorb = false;
     uint32_t absorb_min = 0;         // --absorb-min-positions K: informative positions a read needs to be judged at all (default D + 1)
     bool have_absorb_min = false;
+    bool flag_recombinants = false;  // --flag-recombinants: reads and haplotypes that are one haplotype up to a breakpoint and another from there on (docs/SPEC.md §23)
+    uint32_t recomb_min = 2;         // --recombinant-min-positions K: informative positions a read needs to be judged at all
+    bool have_recomb_min = false;
+    double recomb_ratio = 2.0;       // --recombinant-parent-ratio r: a parent of a haplotype has r times its reads at least
+    bool have_recomb_ratio = false;
     bool linkage = false;            // --linkage: every pair of called variants over the reads covering both (docs/SPEC.md §15)
     bool call_deletions = false;     // --call-deletions: in-frame codon deletions at every evaluated position (docs/SPEC.md §16)
     bool phase_deletions = false;    // --phase-deletions: the called deletions as sites of the haplotypes (docs/SPEC.md §18)
@@ -127,6 +132,16 @@ struct Options {
         "                                      absorbed_read_names and frequency_with_absorbed.  Independent of --rescue-damaged.\n"
         "                                      Follows --downsample / --mix.  Not with --windows, --devices a,b, --batch,\n"
         "                                      --phase-deletions, --phase-insertions or as fuse\n"
+        "      --flag-recombinants [--recombinant-min-positions K] [--recombinant-parent-ratio r]  with --mode-phasing: flags the\n"
+        "                                      products of PCR recombination (docs/SPEC.md section 23).  Every read phasing leaves\n"
+        "                                      out that can be read at K positions at least (default 2) is a recombinant when one\n"
+        "                                      reported haplotype agrees with it from the first position up to a breakpoint and\n"
+        "                                      another from there to the last, and none agrees throughout; a reported haplotype is\n"
+        "                                      a putative recombinant when two others with r times its reads at least (default 2)\n"
+        "                                      cover it in that way.  The haplotype block gains `recombinants`, every haplotype\n"
+        "                                      putative_recombinant (and recombinant_of).  Nothing is filtered.  Independent of\n"
+        "                                      --rescue-damaged and --absorb-distance.  Follows --downsample / --mix.  Not with\n"
+        "                                      --windows, --devices a,b, --batch, --phase-deletions, --phase-insertions or as fuse\n"
         "      --linkage                       pairwise linkage of the called variants over every read covering both (docs/SPEC.md\n"
         "                                      section 15), with and without --mode-phasing: read i is informative at a position iff\n"
         "                                      its three codes there are all < 4; it carries a variant iff it is informative at its\n"
@@ -354,6 +369,9 @@ Options parse(int argc, char **argv)
         }
         else if (a == "--rescue-min-positions") { o.rescue_min = (uint32_t)std::stoul(need(i)); o.have_rescue_min = true; }
         else if (a == "--absorb-distance") { o.absorb_distance = (uint32_t)std::stoul(need(i)); o.have_absorb = true; }
+        else if (a == "--flag-recombinants") o.flag_recombinants = true;
+        else if (a == "--recombinant-min-positions") { o.recomb_min = (uint32_t)std::stoul(need(i)); o.have_recomb_min = true; }
+        else if (a == "--recombinant-parent-ratio") { o.recomb_ratio = std::stod(need(i)); o.have_recomb_ratio = true; }
         else if (a == "--absorb-min-positions") { o.absorb_min = (uint32_t)std::stoul(need(i)); o.have_absorb_min = true; }
         else if (a == "--ins-min-frac") o.ins_min_frac = std::stod(need(i));
         else if (a == "--ins-min-distance") o.ins_min_distance = (uint32_t)std::stoul(need(i));
@@ -419,6 +437,20 @@ Options parse(int argc, char **argv)
         if (!o.batch.empty()) refuse("is not part of a batch (not with --batch)");
         if (o.phase_deletions || o.phase_insertions) refuse("measures distances in codons; the sites of --phase-deletions / --phase-insertions are none (drop them)");
         if (!o.have_absorb_min) o.absorb_min = o.absorb_distance + 1u;
+    }
+    if (o.flag_recombinants || o.have_recomb_min || o.have_recomb_ratio) {   // refused here, before any file is read or any GPU work
+        auto refuse = [](const char *why) {
+            std::cerr << "juliet: --flag-recombinants [--recombinant-min-positions K] [--recombinant-parent-ratio r] " << why << "\n";
+            std::exit(1);
+        };
+        if (!o.flag_recombinants) refuse("--recombinant-min-positions and --recombinant-parent-ratio set thresholds of --flag-recombinants (add it)");
+        if (o.recomb_min == 0) refuse("wants at least one informative position (--recombinant-min-positions 0)");
+        if (!(o.recomb_ratio >= 1.0)) refuse("wants a parent with as many reads as the haplotype at least (--recombinant-parent-ratio below 1)");
+        if (as_fuse) refuse("are not options of fuse");
+        if (!o.phasing) refuse("looks for recombinants of the haplotypes of a phasing run (add --mode-phasing)");
+        if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
+        if (!o.batch.empty()) refuse("is not part of a batch (not with --batch)");
+        if (o.phase_deletions || o.phase_insertions) refuse("compares codons; the sites of --phase-deletions / --phase-insertions are none (drop them)");
     }
     if (o.linkage) {   // refused here, before any file is read or any GPU work
         auto refuse = [](const char *why) { std::cerr << "juliet: --linkage " << why << "\n"; std::exit(1); };

@@ -4,6 +4,7 @@
 #include <chrono>
 #include <ctime>
 #include <fstream>
+#include <map>
 
 #include "fuse.hpp"
 #include "html.hpp"
@@ -290,6 +291,37 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
                 }
             for (uint32_t h = 0; h < H; ++h) with_absorbed_total += (uint64_t)hap_count[h] + absorbed_members[h].size();
         }
+        // --flag-recombinants: the insufficient and the damaged reads by what the rule of docs/SPEC.md §23 says of them, and the
+        // (left, right) pairs of those with both parents unique
+        struct RecombPair { uint32_t left, right, reads[2], bp_min, bp_max; };
+        uint64_t recomb_cat[2][5] = {{0, 0, 0, 0, 0}, {0, 0, 0, 0, 0}};   // [insufficient, damaged][recombinant, ambiguous parent, whole, unexplained, uninformative]
+        std::vector<RecombPair> recomb_pairs;
+        if (R.recomb && ps.n_positions) {   // (no variant position: nothing was phased, no read is insufficient or damaged, §8)
+            std::map<std::pair<uint32_t, uint32_t>, size_t> at;
+            for (uint64_t i = 0; i < n_reads; ++i) {
+                if (read_hap[i] != (uint16_t)JL_HAP_INSUFFICIENT && read_hap[i] != (uint16_t)JL_HAP_DAMAGED) continue;
+                const uint32_t kind = read_hap[i] == (uint16_t)JL_HAP_DAMAGED ? 1u : 0u;
+                const uint32_t l = R.recomb_left.empty() ? (uint32_t)JL_RESCUE_UNINFORMATIVE : R.recomb_left[i];
+                const uint32_t r = R.recomb_left.empty() ? (uint32_t)JL_RESCUE_UNINFORMATIVE : R.recomb_right[i];
+                if (l < H && r < H) {
+                    recomb_cat[kind][0]++;
+                    const uint32_t lo = ps.n_positions - R.recomb_suffix[i], hi = R.recomb_prefix[i];
+                    auto it = at.find({l, r});
+                    if (it == at.end()) {
+                        it = at.emplace(std::make_pair(l, r), recomb_pairs.size()).first;
+                        recomb_pairs.push_back({l, r, {0u, 0u}, lo, hi});
+                    }
+                    RecombPair &pr = recomb_pairs[it->second];
+                    pr.reads[kind]++;
+                    pr.bp_min = std::min(pr.bp_min, lo), pr.bp_max = std::max(pr.bp_max, hi);
+                } else
+                    recomb_cat[kind][l == (uint32_t)JL_RECOMB_WHOLE ? 2 : l == (uint32_t)JL_RESCUE_NONE ? 3 : l == (uint32_t)JL_RESCUE_UNINFORMATIVE ? 4 : 1]++;
+            }
+            std::sort(recomb_pairs.begin(), recomb_pairs.end(), [](const RecombPair &a, const RecombPair &b) {
+                const uint32_t ra = a.reads[0] + a.reads[1], rb = b.reads[0] + b.reads[1];
+                return ra != rb ? ra > rb : a.left != b.left ? a.left < b.left : a.right < b.right;
+            });
+        }
         // --phase-deletions / --phase-insertions with at least one site (docs/SPEC.md §18, §19): position p of the run is site p
         const bool with_sites = R.sites_phased && !R.sites.empty();
         Json hs = Json::array();
@@ -339,6 +371,16 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
                 for (uint32_t i : absorbed_members[h]) ar.push(Json::of(names[i]));
                 hj.set("absorbed_read_names", std::move(ar));
                 hj.set("frequency_with_absorbed", Json::of(with_absorbed_total ? (double)with / (double)with_absorbed_total : 0.0));
+            }
+            if (R.recomb) {
+                const jl_hap_recombinant *hr = h < R.recomb_haps.size() ? &R.recomb_haps[h] : nullptr;
+                hj.set("putative_recombinant", Json::of(hr && hr->flagged != 0u));
+                if (hr && hr->flagged)
+                    hj.set("recombinant_of", Json::object()
+                                                 .set("left", Json::of(haplotype_name(hr->left)))
+                                                 .set("right", Json::of(haplotype_name(hr->right)))
+                                                 .set("prefix", Json::of(hr->prefix))
+                                                 .set("suffix", Json::of(hr->suffix)));
             }
             hs.push(std::move(hj));
         }
@@ -391,6 +433,30 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
                                         .set("assigned_by_distance", std::move(by)));
             }
             hb.set("absorb", std::move(ab));
+        }
+        if (R.recomb) {
+            Json rb = Json::object();
+            rb.set("min_positions", Json::of(R.recomb_min)).set("parent_ratio", Json::of(R.recomb_ratio));
+            static const char *kinds[2] = {"insufficient", "damaged"};
+            for (uint32_t kind = 0; kind < 2u; ++kind)
+                rb.set(kinds[kind], Json::object()
+                                        .set("recombinant_reads", Json::of((uint32_t)recomb_cat[kind][0]))
+                                        .set("ambiguous_parent_reads", Json::of((uint32_t)recomb_cat[kind][1]))
+                                        .set("whole_reads", Json::of((uint32_t)recomb_cat[kind][2]))
+                                        .set("unexplained_reads", Json::of((uint32_t)recomb_cat[kind][3]))
+                                        .set("uninformative_reads", Json::of((uint32_t)recomb_cat[kind][4])));
+            Json pairs = Json::array();
+            for (const auto &pr : recomb_pairs)
+                pairs.push(Json::object()
+                               .set("left", Json::of(haplotype_name(pr.left)))
+                               .set("right", Json::of(haplotype_name(pr.right)))
+                               .set("reads", Json::of(pr.reads[0] + pr.reads[1]))
+                               .set("insufficient_reads", Json::of(pr.reads[0]))
+                               .set("damaged_reads", Json::of(pr.reads[1]))
+                               .set("breakpoint_min", Json::of(pr.bp_min))
+                               .set("breakpoint_max", Json::of(pr.bp_max)));
+            rb.set("pairs", std::move(pairs));
+            hb.set("recombinants", std::move(rb));
         }
         root.set("haplotype", std::move(hb));
     }

@@ -57,6 +57,14 @@ struct Results {
     uint32_t absorb_distance = 0, absorb_min = 0;
     std::vector<uint16_t> nearest;
     std::vector<uint8_t> nearest_dist;
+    // --flag-recombinants (docs/SPEC.md §23): left, right, prefix and suffix of every read by the run's own positions and haplotypes
+    // (empty when no device call was made: no reported haplotype, or more positions asked for than the run has — every read is
+    // uninformative then), and the haplotype-level verdicts (one per reported haplotype)
+    bool recomb = false;
+    uint32_t recomb_min = 0;
+    double recomb_ratio = 0.0;
+    std::vector<uint16_t> recomb_left, recomb_right, recomb_prefix, recomb_suffix;
+    std::vector<jl_hap_recombinant> recomb_haps;
     // --linkage (docs/SPEC.md §15): the three tables of ONE call over the table's distinct columns and its rows; link_var[k] = the
     // row of `var` that is variant k of the call (the rows by column: var_pos must not decrease, and genes may overlap)
     bool linked = false, link_skipped = false;
@@ -268,6 +276,33 @@ const char *fetch_absorb(jl_ctx *ctx, uint32_t min_positions, uint32_t max_dista
     R.nearest.resize(R.read_hap.size());
     R.nearest_dist.resize(R.read_hap.size());
     if (jl_phase_nearest_fetch(ctx, R.nearest.data(), R.nearest_dist.data(), nullptr, nullptr) != JL_OK) return "absorb fetch";
+    return nullptr;
+}
+
+// --flag-recombinants, after fetch_phase: one device call of the rule of docs/SPEC.md §23 with the run's own positions and
+// haplotypes, then the haplotype-level rule on the host with the run's own counts.
+const char *fetch_recombinants(jl_ctx *ctx, uint32_t min_positions, double parent_ratio, Results &R)
+{
+    R.recomb = true;
+    R.recomb_min = min_positions;
+    R.recomb_ratio = parent_ratio;
+    for (auto *v : {&R.recomb_left, &R.recomb_right, &R.recomb_prefix, &R.recomb_suffix}) v->clear();
+    R.recomb_haps.clear();
+    if (R.ps.n_haplotypes == 0) return nullptr;
+    if (R.ps.n_positions) {
+        R.recomb_haps.resize(R.ps.n_haplotypes);
+        if (jl_haplotype_recombinants(R.hap_pattern.data(), (uint32_t)R.pat_stride, R.ps.n_haplotypes, R.ps.n_positions, R.hap_count.data(), parent_ratio,
+                                      R.recomb_haps.data()) != JL_OK)
+            return "haplotype recombinants";
+    }
+    if (min_positions > R.ps.n_positions) return nullptr;
+    if (jl_phase_recombinants_async(ctx, R.pos_cols.data(), R.ps.n_positions, R.hap_pattern.data(), (uint32_t)R.pat_stride, R.ps.n_haplotypes,
+                                    min_positions) != JL_OK)
+        return "recombinants";
+    for (auto *v : {&R.recomb_left, &R.recomb_right, &R.recomb_prefix, &R.recomb_suffix}) v->resize(R.read_hap.size());
+    if (jl_phase_recombinants_fetch(ctx, R.recomb_left.data(), R.recomb_right.data(), R.recomb_prefix.data(), R.recomb_suffix.data(), nullptr,
+                                    nullptr) != JL_OK)
+        return "recombinants fetch";
     return nullptr;
 }
 
