@@ -322,6 +322,33 @@ int jl_class_pileup_fetch(jl_ctx *ctx, uint32_t *counts, uint32_t *class_reads);
  * covers the column. */
 int jl_consensus_of_counts(const uint32_t *col_counts, uint32_t n_cols, uint8_t *out);
 /*
+ * Codon histograms of the resident matrix BY CLASS OF READS at chosen codon starts (docs/SPEC.md §24): the codon counterpart of
+ * jl_class_pileup_async — a column majority is not a codon majority — in one pass over the planes for up to 16 classes.
+ * label[n_reads] and n_classes are jl_class_pileup_async's, word for word: read i belongs to class label[i] when label[i] <
+ * n_classes and to no class otherwise (the ids of jl_phase_fetch can be passed as they are); n_classes is 1 .. JL_CLASS_MAX.
+ * col[n_pos]: window columns of codon starts, strictly ascending, each + 2 < n_cols; positions of different frames may overlap
+ * (c, c + 1, c + 2 can all be starts).  A read of class k whose three codes at col[p], col[p] + 1, col[p] + 2 are all < 4 adds
+ * one to hist[k][p][codon], codon = 16 * first + 4 * second + third as in hist of jl_pileup_fetch; a read with a '-', an N or
+ * an uncovered cell there counts nowhere, so the sum over codons of hist[k][p] is class k's coverage at p, and with every read
+ * in one class hist[0] is jl_pileup_fetch's hist at the same columns.  32 bits, exact, independent of launch shape and order
+ * and of the seed codon the kernel counts by popcount.  Reads past n_reads count nowhere: the padding, and whatever an adopted
+ * matrix holds behind the last read of a plane row.
+ * The contract is jl_class_pileup_async's: the inputs are copied before the call returns; it enqueues on the context's stream
+ * into buffers of its own (grown on demand, released with the context) and touches nothing else — the matrix, the insertion
+ * counters, earlier stage results, the class pileup's buffers and the captured graph stay as they are.  Every kind of resident
+ * matrix is accepted, an adopted one with its own plane stride included.
+ * JL_ERR_STATE: no resident matrix.  JL_ERR_ARG (jl_last_error says which): label == NULL; col == NULL; n_classes 0 or above
+ * JL_CLASS_MAX; n_pos 0; n_classes * n_pos above JL_CLASS_CODONS_CELLS (256 MiB of counters); a column with c + 2 >= n_cols;
+ * columns not strictly ascending.  A refused call changes nothing: what an earlier call enqueued can still be fetched.
+ * A call that fails later, in the runtime (JL_ERR_MEMORY, JL_ERR_DEVICE: its buffers could not grow, an upload or a launch
+ * failed), leaves NOTHING fetchable: the table of the call before it lives in the buffer this one was about to overwrite.
+ */
+enum { JL_CLASS_CODONS_CELLS = 1 << 20 };
+int jl_class_codons_async(jl_ctx *ctx, const uint16_t *label, uint32_t n_classes, const uint32_t *col, uint32_t n_pos);
+/* Wait and copy out: hist[n_classes][n_pos][64] and class_reads[n_classes] (reads per class), both of the last
+ * jl_class_codons_async.  Either pointer may be NULL.  JL_ERR_STATE: none was enqueued. */
+int jl_class_codons_fetch(jl_ctx *ctx, uint32_t *hist /* [n_classes][n_pos][64] */, uint32_t *class_reads /* [n_classes] */);
+/*
  * Which reported haplotype a read agrees with WHERE IT CAN BE READ (docs/SPEC.md §14): phasing drops a read with a deletion, a
  * filtered N or an uncovered cell at any variant position (JL_HAP_DAMAGED); most such reads are clean at the other positions and
  * match exactly one reported haplotype there.  pos_cols[n_pos]: window columns of codon starts, strictly ascending, each + 2 <

@@ -42,7 +42,7 @@ SITE_INS_NONE, SITE_INS_OTHER, SITE_INS_MAX_ALLELES = 0, 63, 62
 EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", "jl_ctx_destroy", "jl_last_error",
            "jl_sync", "jl_col_stride", "jl_plane_stride", "jl_msa_upload", "jl_msa_alloc", "jl_msa_adopt", "jl_msa_pack_rows",
            "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_take", "jl_msa_take_async", "jl_sample_reads", "jl_mix_counts", "jl_msa_download", "jl_msa_download_planes", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
-           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_phase_nearest_async", "jl_phase_nearest_fetch", "jl_phase_recombinants_async", "jl_phase_recombinants_fetch", "jl_haplotype_recombinants", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_read_stats_async", "jl_read_stats_fetch", "jl_read_filter", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_msa_track_insertion_reads", "jl_insertion_reads_fetch", "jl_sites_assemble_alleles", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_control_call_async", "jl_control_call_fetch", "jl_control_test", "jl_phase_async", "jl_phase_fetch",
+           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_class_codons_async", "jl_class_codons_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_phase_nearest_async", "jl_phase_nearest_fetch", "jl_phase_recombinants_async", "jl_phase_recombinants_fetch", "jl_haplotype_recombinants", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_read_stats_async", "jl_read_stats_fetch", "jl_read_filter", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_msa_track_insertion_reads", "jl_insertion_reads_fetch", "jl_sites_assemble_alleles", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_control_call_async", "jl_control_call_fetch", "jl_control_test", "jl_phase_async", "jl_phase_fetch",
            "jl_ctx_stream", "jl_run_async", "jl_run_wait", "jl_run_done", "jl_run_view_get", "jl_group_create", "jl_group_destroy",
            "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_msa_index_info", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
            "jl_allgather_variants", "jl_allgather_variants_async", "jl_allgather_variants_async_many", "jl_allgather_variants_many", "jl_group_exchange_bind", "jl_group_exchange_collect", "jl_xwin_plan", "jl_xwin_assemble_local",
@@ -235,6 +235,8 @@ def load_library(path=LIB_PATH):
     lib.jl_consensus_fetch.argtypes = [vp, vp]
     lib.jl_class_pileup_async.argtypes = [vp, vp, u32]
     lib.jl_class_pileup_fetch.argtypes = [vp, vp, vp]
+    lib.jl_class_codons_async.argtypes = [vp, vp, u32, vp, u32]
+    lib.jl_class_codons_fetch.argtypes = [vp, vp, vp]
     lib.jl_phase_rescue_async.argtypes = [vp, vp, u32, vp, u32, u32, u32]
     lib.jl_phase_rescue_fetch.argtypes = [vp, vp, vp, vp]
     lib.jl_phase_nearest_async.argtypes = [vp, vp, u32, vp, u32, u32, u32, u32]
@@ -626,6 +628,25 @@ class Juliet:
         reads = np.zeros(k, dtype=np.uint32)
         self._chk(self.lib.jl_class_pileup_fetch(self.h, _p(counts), _p(reads)))
         return counts, reads
+
+    def class_codons(self, labels, n_classes, cols, wait=True):
+        """jl_class_codons_async (docs/SPEC.md §24): the codon histograms of the resident matrix by class of reads at the codon
+        starts cols[n_pos] (window columns, strictly ascending) — the labels are class_pileup's.  Returns
+        (hist[n_classes, n_pos, 64], class_reads[n_classes]); wait=False only enqueues on this context's stream and returns
+        None (class_codons_fetch brings the arrays)."""
+        labels = np.ascontiguousarray(labels, dtype=np.uint16)
+        cols = np.ascontiguousarray(cols, dtype=np.uint32)
+        assert len(labels) == self.n_reads and cols.ndim == 1
+        self._chk(self.lib.jl_class_codons_async(self.h, _p(labels), int(n_classes), _p(cols), len(cols)))
+        self._class_codons_shape = (int(n_classes), len(cols))
+        return self.class_codons_fetch() if wait else None
+
+    def class_codons_fetch(self):
+        k, p = getattr(self, "_class_codons_shape", (0, 0))
+        hist = np.zeros((k, p, 64), dtype=np.uint32)
+        reads = np.zeros(k, dtype=np.uint32)
+        self._chk(self.lib.jl_class_codons_fetch(self.h, _p(hist), _p(reads)))
+        return hist, reads
 
     def phase_rescue(self, pos_cols, hap_pattern, min_positions=1, wait=True):
         """jl_phase_rescue_async (docs/SPEC.md §14): which haplotype of hap_pattern[H, Vp] (codon indices at the codon starts

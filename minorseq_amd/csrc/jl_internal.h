@@ -351,6 +351,23 @@ struct jl_class_args {
     uint32_t k_first;          // first class of the counting launch's pass 0
 };
 void jl_launch_class_pileup(const jl_class_args *a, hipStream_t st);
+void jl_launch_class_masks(const jl_class_args *a, hipStream_t st);   // its first step alone: mask rows and class_reads
+
+// ---- codon histograms by class of reads at chosen codon starts (kernels_class_codons.hip, capi_class_codons.hip; docs/SPEC.md §24)
+struct jl_class_codons_args {
+    const uint8_t *msa;        // the window's bit planes
+    uint64_t plane_stride;     // ... and their stride (an adopted matrix brings its own)
+    uint64_t n_reads;
+    uint32_t n_pos, n_classes;
+    const uint32_t *col;       // [n_pos] codon starts, strictly ascending, each + 2 < n_cols
+    const uint16_t *label;     // [n_reads]
+    const uint8_t *mask;       // [n_classes][mask_stride]: the rows of jl_launch_class_masks
+    uint64_t mask_stride;      // jl_plane_stride(n_reads)
+    uint32_t *hist;            // [n_classes][n_pos][64], zeroed
+    uint32_t seg_tiles;        // tiles of 512 reads a workgroup walks (set by the launcher, as is:)
+    uint32_t k_first;          // first class of the launch's pass 0
+};
+void jl_launch_class_codons(const jl_class_codons_args *a, hipStream_t st);
 
 // ---- which reported haplotype a read agrees with (kernels_rescue.hip, capi_rescue.hip; docs/SPEC.md §14)
 #define JL_RESCUE_POS_MAX JL_VARIANT_CAP   // variant positions of one call: the variant table's capacity
@@ -756,6 +773,13 @@ struct jl_ctx {
     jl_dev_array<uint8_t> class_mask;
     jl_dev_array<uint32_t> class_out;   // counts [class_k][class_cols][6], then class_reads [class_k]
     uint32_t class_k = 0, class_cols = 0;   // shape of the last class pileup enqueued (class_k = 0: none)
+
+    // ---- jl_class_codons_async: buffers of its own, grown on demand (capi_class_codons.hip); no stage, no run and no class pileup touches them
+    jl_upload_staging<uint16_t> cc_label;
+    jl_upload_staging<uint32_t> cc_col;
+    jl_dev_array<uint8_t> cc_mask;
+    jl_dev_array<uint32_t> cc_out;      // hist [cc_k][cc_pos][64], then class_reads [cc_k]
+    uint32_t cc_k = 0, cc_pos = 0;      // shape of the last call enqueued (cc_k = 0: none)
 
     // ---- jl_phase_rescue_async: buffers of its own, grown on demand (capi_rescue.hip); no stage and no run touches them
     jl_upload_staging<uint32_t> rescue_in;   // pos_cols [n_pos], then pat4 (jl_rescue_args)

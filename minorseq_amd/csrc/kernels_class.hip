@@ -131,13 +131,20 @@ constexpr auto kCounting = counting_table(std::make_index_sequence<16>{});
 
 }  // namespace
 
-// masks and class_reads from the labels, then ceil(n_classes / 16) passes of the counting; a->counts and a->class_reads are zero
+// masks and class_reads from the labels (the per-class codon tables of kernels_class_codons.hip count under the same rows);
+// a->class_reads is zero, a->msa, a->counts and the columns are not looked at
+void jl_launch_class_masks(const jl_class_args *a, hipStream_t st)
+{
+    const uint32_t n_lines = (uint32_t)((a->n_reads + 1023u) / 1024u);
+    const uint32_t class_chunks = (a->n_classes + kMaskWaves - 1u) / kMaskWaves;
+    hipLaunchKernelGGL(class_masks_kernel, dim3(n_lines, class_chunks), dim3(64 * kMaskWaves), 0, st, *a);
+}
+
+// the masks, then ceil(n_classes / 16) passes of the counting; a->counts and a->class_reads are zero
 void jl_launch_class_pileup(const jl_class_args *a, hipStream_t st)
 {
     jl_class_args A = *a;
-    const uint32_t n_lines = (uint32_t)((A.n_reads + 1023u) / 1024u);
-    const uint32_t class_chunks = (A.n_classes + kMaskWaves - 1u) / kMaskWaves;
-    hipLaunchKernelGGL(class_masks_kernel, dim3(n_lines, class_chunks), dim3(64 * kMaskWaves), 0, st, A);
+    jl_launch_class_masks(&A, st);
     const uint32_t n_groups = (A.n_cols + 63u) / 64u;
     const jl_walk_shape shape = jl_walk_shape_for(A.n_reads, n_groups);
     A.seg_tiles = shape.seg_tiles;

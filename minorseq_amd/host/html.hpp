@@ -135,8 +135,13 @@ inline std::string render_html(const Json &root)
                                  td(vp.get_str("ref_codon")) + td(vp.get_str("ref_amino_acid")) + td(num_str(vp.get("ref_position"))) +
                                  td(aa.get_str("amino_acid")) + td(vc.get_str("codon")) + td(format_percent(100.0 * vc.get("frequency")->num)) +
                                  td(num_str(vp.get("coverage"))) + td(vc.get_str("known_drm"));
+                            const Json *hcnt = vc.get("haplotype_count"), *hcov = vc.get("haplotype_coverage");   // --haplotype-mutations (docs/SPEC.md §24)
                             if (const Json *hh = vc.get("haplotype_hit"))
-                                for (const Json &x : hh->arr) h += x.b ? "<td class=\"hit\">x</td>" : "<td class=\"nohit\"></td>";
+                                for (size_t x = 0; x < hh->arr.size(); ++x) {
+                                    if (!hcnt || x >= hcnt->arr.size()) { h += hh->arr[x].b ? "<td class=\"hit\">x</td>" : "<td class=\"nohit\"></td>"; continue; }
+                                    h += std::string("<td class=\"") + (hh->arr[x].b ? "hit" : "nohit") + "\" data-count=\"" + num_str(&hcnt->arr[x]) +
+                                         "\" data-coverage=\"" + num_str(&hcov->arr[x]) + "\">" + (hh->arr[x].b ? "x" : "") + "</td>";
+                                }
                             h += "</tr>\n";
                         }
                     // "Clicking the row will show counts of the multiple-sequence alignment counts of the -3 to +3 context positions"
@@ -274,6 +279,38 @@ inline std::string render_html(const Json &root)
                 h += "</details></td></tr>\n";
             }
         h += "</table>";
+        if (const Json *dp = hb->get("drug_profile")) {   // --haplotype-mutations (docs/SPEC.md §24); doubles as the JSON prints them
+            h += "\n<table id=\"hap-mutations\"><tr><th>Haplotype</th><th>Gene</th><th>Pos</th><th>Ref codon</th><th>Ref AA</th><th>Codon</th><th>AA</th>"
+                 "<th>#Reads</th><th>Coverage</th><th>Frequency</th><th>Affected Drugs</th></tr>\n";
+            if (haps)
+                for (const Json &hp : haps->arr)
+                    if (const Json *ms = hp.get("mutations"))
+                        for (const Json &m : ms->arr) {
+                            h += "<tr data-haplotype=\"" + html_escape(hp.get_str("name")) + "\">" + td(hp.get_str("name")) + td(m.get_str("gene")) +
+                                 td(num_str(m.get("position"))) + td(m.get_str("ref_codon")) + td(m.get_str("ref_amino_acid")) + td(m.get_str("codon")) +
+                                 td(m.get_str("amino_acid")) + td(num_str(m.get("count"))) + td(num_str(m.get("coverage"))) + td(num_str(m.get("frequency"))) + "<td>";
+                            for (const Json &d : m.get("drms")->arr) h += "<span class=\"drm-name\">" + html_escape(d.str) + "</span> ";
+                            h += "</td></tr>\n";
+                        }
+            h += "</table>\n<table id=\"hap-drugs\"><tr><th>Haplotype</th><th>Drugs</th></tr>\n";
+            if (haps)
+                for (const Json &hp : haps->arr) {
+                    h += "<tr>" + td(hp.get_str("name")) + "<td>";
+                    if (const Json *ds = hp.get("drugs"))
+                        for (const Json &d : ds->arr) h += "<span class=\"drm-name\">" + html_escape(d.str) + "</span> ";
+                    h += "</td></tr>\n";
+                }
+            h += "</table>\n<table id=\"hap-drug-profile\"><tr><th>Drug</th>";
+            if (haps)
+                for (const Json &hp : haps->arr) h += "<th class=\"hapname\">" + html_escape(hp.get_str("name")) + "</th>";
+            h += "<th>#Reads</th><th>Frequency</th></tr>\n";
+            for (const Json &d : dp->arr) {
+                h += "<tr>" + td(d.get_str("drug"));
+                for (const Json &x : d.get("haplotypes")->arr) h += x.b ? "<td class=\"hit\">x</td>" : "<td class=\"nohit\"></td>";
+                h += td(num_str(d.get("reads"))) + td(num_str(d.get("frequency"))) + "</tr>\n";
+            }
+            h += "</table>\n";
+        }
         if (const Json *rs = hb->get("rescue")) {   // --rescue-damaged (docs/SPEC.md §14): the damaged reads, judged where they can be read
             h += "\n<table id=\"hap-rescue\"><tr><th>Damaged reads, rescued (at least " + num_str(rs->get("min_positions")) +
                  " informative positions)</th><th>#Reads</th></tr>\n";

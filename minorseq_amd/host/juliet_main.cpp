@@ -172,6 +172,10 @@ int run_one_window(Run &run)
         if (const char *what = fetch_sites_phase(ctx, opt.device, opt.min_reads, n_reads, opt.phase_deletions, opt.phase_insertions, R, &pc)) die_jl(pc ? pc : ctx, what);
         tick("sites");
     }
+    if (opt.hap_mutations) {
+        if (const char *what = fetch_haplotype_mutations(ctx, smp.refcodes, win_begin, R)) die_jl(ctx, what);
+        tick("class_codons");
+    }
     if (!opt.hap_fasta.empty()) {
         if (const int code = write_haplotype_fasta(opt, ctx, R, win_begin, n_cols)) return code;
         tick("haplotype fasta");

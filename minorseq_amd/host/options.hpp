@@ -37,6 +37,7 @@ struct Options {
     std::vector<int> devices;        // --devices a,b,...: one rank (thread) per device, consecutive windows each
     std::string dump_msa, dump_config, consensus;
     std::string hap_fasta;           // --haplotype-fasta: one consensus per reported haplotype (docs/SPEC.md §13)
+    bool hap_mutations = false;      // --haplotype-mutations: per-haplotype codon tables and drug profile (docs/SPEC.md §24)
     bool rescue = false;             // --rescue-damaged: which reported haplotype each damaged read agrees with (docs/SPEC.md §14)
     uint32_t rescue_min = 1;         // --rescue-min-positions K: informative positions a read needs to be judged at all
     bool have_rescue_min = false;
@@ -108,6 +109,10 @@ struct Options {
         "      --consensus <out.fasta>         also write the window's consensus as `fuse` would (doc/FUSE.md:17-20):\n"
         "                                      majority base, major deletions removed, in-frame majority insertions kept\n"
         "      --ins-min-frac 0.5  --ins-min-distance 10   when an insertion enters the consensus\n"
+        "      --haplotype-mutations           with --mode-phasing: per reported haplotype every evaluated codon whose majority\n"
+        "                                      within the haplotype differs from the reference (mutations[], drugs[]), a\n"
+        "                                      drug_profile over the haplotypes, and per-haplotype counts on every variant codon\n"
+        "                                      (docs/SPEC.md section 24).  Allowed and refused as --haplotype-fasta is\n"
         "      --haplotype-fasta <out.fasta>   with --mode-phasing: one consensus record per reported haplotype, in the JSON's\n"
         "                                      order, from the column pileup of that haplotype's reads alone (docs/SPEC.md section\n"
         "                                      13): majority base, major deletions removed, N where none of its reads covers the\n"
@@ -351,6 +356,7 @@ Options parse(int argc, char **argv)
         }
         else if (a == "--consensus") o.consensus = need(i);
         else if (a == "--haplotype-fasta") o.hap_fasta = need(i);
+        else if (a == "--haplotype-mutations") o.hap_mutations = true;
         else if (a == "--rescue-damaged") o.rescue = true;
         else if (a == "--linkage") o.linkage = true;
         else if (a == "--call-deletions") o.call_deletions = true;
@@ -416,6 +422,13 @@ Options parse(int argc, char **argv)
         if (!o.phasing) refuse("writes the haplotypes of a phasing run (add --mode-phasing)");
         if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
         if (!o.batch.empty()) refuse("writes one file for one sample (not with --batch)");
+    }
+    if (o.hap_mutations) {   // refused as --haplotype-fasta is, before any file is read or any GPU work
+        auto refuse = [](const char *why) { std::cerr << "juliet: --haplotype-mutations " << why << "\n"; std::exit(1); };
+        if (as_fuse) refuse("is not an option of fuse");
+        if (!o.phasing) refuse("describes the haplotypes of a phasing run (add --mode-phasing)");
+        if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
+        if (!o.batch.empty()) refuse("describes one sample (not with --batch)");
     }
     if (o.rescue || o.have_rescue_min) {   // refused here, before any file is read or any GPU work
         auto refuse = [](const char *why) { std::cerr << "juliet: --rescue-damaged [--rescue-min-positions K] " << why << "\n"; std::exit(1); };

@@ -136,6 +136,18 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
                         for (uint32_t h = 0; h < H; ++h) hh.push(Json::of(hit[row * R.hit_stride + h] != 0));
                         cj.set("haplotype_hit", hh);  // doc/JULIET.md:207-209
                     }
+                    if (R.hap_mutations) {   // §24: the codon's count and the coverage within each reported haplotype
+                        Json hc = Json::array(), hv = Json::array();
+                        const int entry = R.hm_entry(var[k].col);
+                        for (uint32_t h = 0; h < H && entry >= 0 && !R.hm_hist.empty(); ++h) {
+                            const uint32_t *row = &R.hm_hist[((size_t)h * R.hm_cols.size() + (size_t)entry) * 64];
+                            uint32_t cov = 0;
+                            for (uint32_t q = 0; q < 64; ++q) cov += row[q];
+                            hc.push(Json::of(row[var[k].codon]));
+                            hv.push(Json::of(cov));
+                        }
+                        cj.set("haplotype_count", std::move(hc)).set("haplotype_coverage", std::move(hv));
+                    }
                     cods.push(cj);
                 }
                 aj.set("variant_codons", cods);
@@ -325,8 +337,45 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
         // --phase-deletions / --phase-insertions with at least one site (docs/SPEC.md §18, §19): position p of the run is site p
         const bool with_sites = R.sites_phased && !R.sites.empty();
         Json hs = Json::array();
+        std::vector<std::vector<std::string>> hap_drugs(H);   // --haplotype-mutations (docs/SPEC.md §24)
         for (uint32_t h = 0; h < H; ++h) {
             Json hj = Json::object();
+            Json muts = Json::array();
+            if (R.hap_mutations) {   // every evaluated position whose majority codon within the haplotype is not the position's ref
+                for (const Results::HapMutPos &q : R.hm_pos) {
+                    if (q.ref < 0 || R.hm_hist.empty()) continue;
+                    const uint32_t *row = &R.hm_hist[((size_t)h * R.hm_cols.size() + q.entry) * 64];
+                    uint32_t best = 0, cov = 0;
+                    for (uint32_t k = 0; k < 64; ++k) {
+                        cov += row[k];
+                        if (row[k] > row[best]) best = k;   // (ties: the lowest index)
+                    }
+                    if (cov == 0 || best == (uint32_t)q.ref) continue;
+                    const GeneCfg &g = cfg.genes[q.gene];
+                    const uint32_t aa_pos = q.codon_pos + g.first_codon;
+                    const char aa = translate(best);
+                    Json drms = Json::array();
+                    for (const Drm &d : g.drms) {
+                        bool hit_drm = false;
+                        for (const DrmPosition &dp : d.positions) hit_drm = hit_drm || dp.matches(aa_pos, aa);
+                        if (!hit_drm) continue;
+                        drms.push(Json::of(d.name));
+                        if (std::find(hap_drugs[h].begin(), hap_drugs[h].end(), d.name) == hap_drugs[h].end()) hap_drugs[h].push_back(d.name);
+                    }
+                    muts.push(Json::object()
+                                  .set("gene", Json::of(g.name))
+                                  .set("position", Json::of(aa_pos))
+                                  .set("ref_codon", Json::of(codon_string((unsigned)q.ref)))
+                                  .set("ref_amino_acid", Json::of(std::string(1, translate((unsigned)q.ref))))
+                                  .set("codon", Json::of(codon_string(best)))
+                                  .set("amino_acid", Json::of(std::string(1, aa)))
+                                  .set("count", Json::of(row[best]))
+                                  .set("coverage", Json::of(cov))
+                                  .set("frequency", Json::of((double)row[best] / (double)cov))
+                                  .set("drms", std::move(drms)));
+                }
+                std::sort(hap_drugs[h].begin(), hap_drugs[h].end());
+            }
             hj.set("name", Json::of(haplotype_name(h))).set("reads", Json::of(hap_count[h]));
             hj.set("frequency", Json::of(ps.reported_reads ? (double)hap_count[h] / (double)ps.reported_reads : 0.0));
             Json cods = Json::array();
@@ -382,9 +431,36 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
                                                  .set("prefix", Json::of(hr->prefix))
                                                  .set("suffix", Json::of(hr->suffix)));
             }
+            if (R.hap_mutations) {
+                Json dj = Json::array();
+                for (const std::string &d : hap_drugs[h]) dj.push(Json::of(d));
+                hj.set("mutations", std::move(muts)).set("drugs", std::move(dj));
+            }
             hs.push(std::move(hj));
         }
         hb.set("haplotypes", std::move(hs));
+        if (R.hap_mutations) {   // one entry per drug that any haplotype carries, ascending by name
+            std::vector<std::string> all;
+            for (const auto &v : hap_drugs) all.insert(all.end(), v.begin(), v.end());
+            std::sort(all.begin(), all.end());
+            all.erase(std::unique(all.begin(), all.end()), all.end());
+            Json dp = Json::array();
+            for (const std::string &drug : all) {
+                Json flags = Json::array();
+                uint64_t reads = 0;
+                double freq = 0.0;
+                for (uint32_t h = 0; h < H; ++h) {
+                    const bool has = std::find(hap_drugs[h].begin(), hap_drugs[h].end(), drug) != hap_drugs[h].end();
+                    flags.push(Json::of(has));
+                    if (!has) continue;
+                    reads += hap_count[h];
+                    freq += ps.reported_reads ? (double)hap_count[h] / (double)ps.reported_reads : 0.0;
+                }
+                dp.push(Json::object().set("drug", Json::of(drug)).set("haplotypes", std::move(flags)).set("reads", Json::of((uint32_t)reads))
+                            .set("frequency", Json::of(freq)));
+            }
+            hb.set("drug_profile", std::move(dp));
+        }
         Json pc = Json::array();
         if (!with_sites)
             for (uint32_t p = 0; p < ps.n_positions; ++p) pc.push(Json::of(win_begin + pos_cols[p] + 1));

@@ -73,6 +73,19 @@ struct Results {
     // var[k], and var[k].expected the control's count of the codon
     bool controlled = false;
     std::vector<uint32_t> control_cov;
+    // --haplotype-mutations (docs/SPEC.md §24): the evaluated positions of every gene in (gene, codon) order with their §4
+    // reference codon (ref < 0: none exists at the position) and their entry of hm_cols; hm_cols: their distinct columns,
+    // ascending; hm_hist[h][entry][64]: ONE per-class codon table with the run's per-read ids as labels (empty: no haplotype)
+    struct HapMutPos { uint32_t gene, codon_pos, col; int ref; uint32_t entry; };
+    bool hap_mutations = false;
+    std::vector<HapMutPos> hm_pos;
+    std::vector<uint32_t> hm_cols, hm_hist;
+    // the entry of hm_cols that window column `col` is, or -1
+    int hm_entry(uint32_t col) const
+    {
+        const auto it = std::lower_bound(hm_cols.begin(), hm_cols.end(), col);
+        return it != hm_cols.end() && *it == col ? (int)(it - hm_cols.begin()) : -1;
+    }
     // --call-deletions (docs/SPEC.md §16): the called positions in (gene, codon) order; ref_codon < 0: none exists at the position
     struct Deletion { uint32_t gene, codon_pos, col; int ref_codon; jl_deletion_call call; };
     bool deletions = false;
@@ -380,6 +393,46 @@ const char *fetch_deletions(jl_ctx *ctx, const Options &opt, const jl_params &pr
         }
         R.del_rows.push_back({pg[p], pk[p], pc[p], ref, dc});
     }
+    return nullptr;
+}
+
+// --haplotype-mutations, after fetch_phase (and after the site matrix's phasing, whose ids are the labels then): the evaluated
+// positions of the run's plan on `ctx` with their §4 reference codon, and ONE jl_class_codons_async (docs/SPEC.md §24) at their
+// distinct columns with the plain per-read ids as labels and the reported haplotypes as classes.  No haplotype: no call.
+const char *fetch_haplotype_mutations(jl_ctx *ctx, const std::vector<uint8_t> &refcodes, uint32_t win_begin, Results &R)
+{
+    R.hap_mutations = true;
+    R.hm_pos.clear(), R.hm_cols.clear(), R.hm_hist.clear();
+    const uint32_t P = jl_n_positions(ctx), H = R.ps.n_haplotypes;
+    std::vector<uint32_t> pg(P), pk(P), pc(P), hist;
+    const bool majority = refcodes.empty();   // (§4: the reference codon is the sample's majority codon then)
+    if (majority) hist.resize((size_t)P * 64);
+    if (P && jl_pileup_fetch(ctx, nullptr, pg.data(), pk.data(), pc.data(), majority ? hist.data() : nullptr, nullptr) != JL_OK) return "positions";
+    R.hm_cols.assign(pc.begin(), pc.end());
+    std::sort(R.hm_cols.begin(), R.hm_cols.end());
+    R.hm_cols.erase(std::unique(R.hm_cols.begin(), R.hm_cols.end()), R.hm_cols.end());
+    for (uint32_t p = 0; p < P; ++p) {
+        int ref = -1;
+        if (majority) {
+            const uint32_t *h = &hist[(size_t)p * 64];
+            uint32_t best = 0;
+            for (uint32_t k = 1; k < 64; ++k)
+                if (h[k] > h[best]) best = k;
+            if (h[best]) ref = (int)best;
+        } else {
+            const size_t r = (size_t)win_begin + pc[p];
+            if (r + 2 < refcodes.size() && refcodes[r] < 4 && refcodes[r + 1] < 4 && refcodes[r + 2] < 4)
+                ref = 16 * refcodes[r] + 4 * refcodes[r + 1] + refcodes[r + 2];
+        }
+        R.hm_pos.push_back({pg[p], pk[p], pc[p], ref, (uint32_t)R.hm_entry(pc[p])});
+    }
+    std::stable_sort(R.hm_pos.begin(), R.hm_pos.end(), [](const Results::HapMutPos &a, const Results::HapMutPos &b) {
+        return a.gene != b.gene ? a.gene < b.gene : a.codon_pos < b.codon_pos;
+    });
+    if (H == 0 || R.hm_cols.empty()) return nullptr;
+    if (jl_class_codons_async(ctx, R.read_hap.data(), H, R.hm_cols.data(), (uint32_t)R.hm_cols.size()) != JL_OK) return "class codons";
+    R.hm_hist.resize((size_t)H * R.hm_cols.size() * 64);
+    if (jl_class_codons_fetch(ctx, R.hm_hist.data(), nullptr) != JL_OK) return "class codons fetch";
     return nullptr;
 }
 
