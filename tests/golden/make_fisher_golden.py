@@ -6,6 +6,10 @@ only names the test), so the pin is an independent 60-digit evaluation of the hy
 tail P(X >= a) for the 2x2 table [[a, b], [c, d]], cross-checked against scipy.stats.fisher_exact
 where scipy does not underflow (scipy itself is only good to ~1e-9 relative at 1e7 coverage, so the
 cross-check is loose; mpmath is the pin).  Nothing here travels to the GPU box; only the JSON does.
+
+The 60 tiny random tables mostly have unequal rows, and the tests of the device routine (equal rows only) skip
+those: small equal-row tables, and the rest of the routine's count domain, live in fisher_domain.json
+(make_fisher_domain_golden.py).
 """
 import json
 import random
