@@ -875,6 +875,14 @@ int jl_fisher_eval(jl_ctx *ctx, const uint32_t *a, const uint32_t *c, const uint
 /* The same with the tail of jl_params: 0 = P(X >= a), 1 = two-sided. */
 int jl_fisher_eval_tail(jl_ctx *ctx, const uint32_t *a, const uint32_t *c, const uint32_t *cov, uint32_t n, int tail,
                         double *p, double *log_p);
+/*
+ * The same for the general-margin routine of the control call (SPEC §21): `n` tables [[a, cov_s-a], [c, cov_c-c]] with both
+ * coverages above 0.  skipped == NULL: p[i] = P(X >= a[i]), log_p[i] = ln p, and n_tests, alpha are not read.  Otherwise the
+ * form the control call's kernel evaluates: skipped[i] = 1 and p[i] = 1 where the point mass alone, times n_tests, reaches
+ * alpha (n_tests > 0, alpha > 0), the plain value everywhere else.
+ */
+int jl_control_eval(jl_ctx *ctx, const uint32_t *a, const uint32_t *cov_s, const uint32_t *c, const uint32_t *cov_c, uint32_t n,
+                    double n_tests, double alpha, double *p, double *log_p, uint32_t *skipped);
 
 /* ---------------------------------------------------------------- timing hooks (bench) */
 

@@ -44,7 +44,7 @@ EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", 
            "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_take", "jl_msa_take_async", "jl_sample_reads", "jl_mix_counts", "jl_msa_download", "jl_msa_download_planes", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
            "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_class_codons_async", "jl_class_codons_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_phase_nearest_async", "jl_phase_nearest_fetch", "jl_phase_recombinants_async", "jl_phase_recombinants_fetch", "jl_haplotype_recombinants", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_read_stats_async", "jl_read_stats_fetch", "jl_read_filter", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_msa_track_insertion_reads", "jl_insertion_reads_fetch", "jl_sites_assemble_alleles", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_control_call_async", "jl_control_call_fetch", "jl_control_test", "jl_phase_async", "jl_phase_fetch",
            "jl_ctx_stream", "jl_run_async", "jl_run_wait", "jl_run_done", "jl_run_view_get", "jl_group_create", "jl_group_destroy",
-           "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_msa_index_info", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
+           "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_msa_index_info", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_control_eval", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
            "jl_allgather_variants", "jl_allgather_variants_async", "jl_allgather_variants_async_many", "jl_allgather_variants_many", "jl_group_exchange_bind", "jl_group_exchange_collect", "jl_xwin_plan", "jl_xwin_assemble_local",
            "jl_xwin_assemble_rccl", "jl_xwin_assemble_slice_local", "jl_xwin_assemble_slice_rccl", "jl_phase_groups_async",
            "jl_phase_groups_fetch", "jl_phase_regroup", "jl_merge_tables", "jl_merge_groups", "jl_select_haplotypes",
@@ -285,6 +285,7 @@ def load_library(path=LIB_PATH):
     lib.jl_run_view_get.argtypes = [vp, C.POINTER(RunView)]
     lib.jl_fisher_eval.argtypes = [vp, vp, vp, vp, u32, vp, vp]
     lib.jl_fisher_eval_tail.argtypes = [vp, vp, vp, vp, u32, C.c_int, vp, vp]
+    lib.jl_control_eval.argtypes = [vp, vp, vp, vp, vp, u32, C.c_double, C.c_double, vp, vp, vp]
     lib.jl_expand_read_hap.argtypes = [vp, u32, u64, vp]
     lib.jl_time_pileup.argtypes = [vp, u32, C.POINTER(C.c_float)]
     lib.jl_time_pileup_set.argtypes = [vp, u32, u32, C.POINTER(C.c_float)]
@@ -927,6 +928,20 @@ class Juliet:
         lp = np.zeros(len(a), dtype=np.float64)
         self._chk(self.lib.jl_fisher_eval_tail(self.h, _p(a), _p(c), _p(cov), len(a), tail, _p(p), _p(lp)))
         return p, lp
+
+    def control_eval(self, a, cov_s, c, cov_c, n_tests=None, alpha=None):
+        """jl_control_eval: the general-margin routine of the control call on the device, one table [[a, cov_s - a],
+        [c, cov_c - c]] per element.  (p, log_p) of the plain form; with n_tests and alpha (p, log_p, skipped) of the gated one."""
+        a, cov_s, c, cov_c = (np.ascontiguousarray(x, dtype=np.uint32) for x in (a, cov_s, c, cov_c))
+        assert len(a) == len(cov_s) == len(c) == len(cov_c)
+        p = np.zeros(len(a), dtype=np.float64)
+        lp = np.zeros(len(a), dtype=np.float64)
+        if n_tests is None:
+            self._chk(self.lib.jl_control_eval(self.h, _p(a), _p(cov_s), _p(c), _p(cov_c), len(a), 0.0, 0.0, _p(p), _p(lp), None))
+            return p, lp
+        sk = np.zeros(len(a), dtype=np.uint32)
+        self._chk(self.lib.jl_control_eval(self.h, _p(a), _p(cov_s), _p(c), _p(cov_c), len(a), n_tests, alpha, _p(p), _p(lp), _p(sk)))
+        return p, lp, sk.astype(bool)
 
     def sync(self):
         self._chk(self.lib.jl_sync(self.h))

@@ -139,4 +139,40 @@ int jl_control_test(uint32_t a, uint32_t cov_s, uint32_t c, uint32_t cov_c, cons
     return JL_OK;
 }
 
+// the same header as the DEVICE evaluates it, one thread a table (a diagnostic, as jl_fisher_eval_tail is for jl_fisher.h)
+int jl_control_eval(jl_ctx *ctx, const uint32_t *a, const uint32_t *cov_s, const uint32_t *c, const uint32_t *cov_c, uint32_t n,
+                    double n_tests, double alpha, double *p, double *log_p, uint32_t *skipped)
+{
+    static const char *fn = "jl_control_eval";
+    if (!ctx) return JL_ERR_ARG;
+    if (!a || !cov_s || !c || !cov_c || !p || !log_p) return jl_fail(ctx, JL_ERR_ARG, "%s: a NULL array", fn);
+    if (skipped && !(n_tests > 0.0 && alpha > 0.0)) return jl_fail(ctx, JL_ERR_ARG, "%s: the gated form needs n_tests > 0 and alpha > 0", fn);
+    if (n == 0) return JL_OK;
+    for (uint32_t i = 0; i < n; ++i)
+        if (cov_s[i] == 0u || cov_c[i] == 0u || a[i] > cov_s[i] || c[i] > cov_c[i])
+            return jl_fail(ctx, JL_ERR_ARG, "%s: table %u: coverages above 0, a <= cov_s and c <= cov_c", fn, i);
+    JL_HIP(ctx, hipSetDevice(ctx->device));
+    uint32_t *d_in = nullptr;   // a | cov_s | c | cov_c | skipped
+    double *d_out = nullptr;    // p | log_p
+    JL_HIP(ctx, hipMalloc(&d_in, (size_t)n * 20));
+    if (hipMalloc(&d_out, (size_t)n * 16) != hipSuccess) { hipFree(d_in); return jl_fail(ctx, JL_ERR_MEMORY, "%s buffers", fn); }
+    hipStream_t st = ctx->stream;
+    const uint32_t *src[4] = {a, cov_s, c, cov_c};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipMemcpyAsync(d_in + k * (size_t)n, src[k], (size_t)n * 4, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        uint32_t *d_skip = skipped ? d_in + 4 * (size_t)n : nullptr;
+        jl_launch_control_eval(n, d_in, d_in + n, d_in + 2 * (size_t)n, d_in + 3 * (size_t)n, n_tests, alpha, d_out, d_out + n, d_skip, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(p, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(log_p, d_out + n, (size_t)n * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && skipped) e = hipMemcpyAsync(skipped, d_in + 4 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    hipFree(d_in);
+    hipFree(d_out);
+    if (e != hipSuccess) return jl_fail(ctx, JL_ERR_DEVICE, "%s: %s", fn, hipGetErrorString(e));
+    return JL_OK;
+}
+
 }  // extern "C"

@@ -6,47 +6,19 @@
 #include <math.h>
 #include <string.h>
 
-#include "jl_fisher.h"
+#include "jl_fisher_general.h"
 #include "jl_internal.h"
 
 namespace {
 
-// ln of the Binomial(n, p) mass at x in saddle-point (Loader) form, q = 1 - p, 0 < p < 1
-double log_binom_mass(double x, double n, double p, double q)
+// X ~ Hypergeometric(n, K marked, r drawn), max(0, r + K - n) < min(r, K): *ge = P(X >= x), *le = P(X <= x), each as the upper
+// tail of a 2 x 2 table under the general-margin routine of jl_fisher_general.h (the lower tail of X is the upper tail of K - X,
+// the marked among the n - r not drawn)
+void hypergeometric_tails(uint32_t x, uint32_t K, uint32_t r, uint32_t n, double *ge, double *le)
 {
-    const double TWO_PI = 6.283185307179586477;
-    if (n == 0.0) return 0.0;
-    if (x == 0.0) return n * log1p(-p);
-    if (x == n) return n * log1p(-q);
-    const double lc = stirlerr(n) - stirlerr(x) - stirlerr(n - x) - bd0(x, n * p) - bd0(n - x, n * q);
-    return lc - 0.5 * (log(TWO_PI * x) + log1p(-x / n));
-}
-
-// X ~ Hypergeometric(n, K marked, r drawn), max(0, r + K - n) < min(r, K): *ge = P(X >= x), *le = P(X <= x).  The tail that runs
-// away from the mean is summed by the ratio recurrence from the point mass, the other one is its complement plus the point mass.
-void hypergeometric_tails(double x, double K, double r, double n, double *ge, double *le)
-{
-    const double lo = r + K > n ? r + K - n : 0.0, hi = r < K ? r : K;
-    const double p = r / n, q = (n - r) / n;
-    const double mass = exp(log_binom_mass(x, K, p, q) + log_binom_mass(r - x, n - K, p, q) - log_binom_mass(r, n, p, q));
-    double term = 1.0, sum = 1.0;
-    const bool upper = x * n >= r * K;   // at or above the mean
-    if (upper) {
-        for (double t = x; t < hi; t += 1.0) {
-            term *= ((K - t) * (r - t)) / ((t + 1.0) * (n - K - r + t + 1.0));
-            sum += term;
-            if (term < sum * 1e-17) break;
-        }
-    } else {
-        for (double t = x; t > lo; t -= 1.0) {
-            term *= (t * (n - K - r + t)) / ((K - t + 1.0) * (r - t + 1.0));
-            sum += term;
-            if (term < sum * 1e-17) break;
-        }
-    }
-    const double tail = fmin(1.0, mass * sum), other = fmin(1.0, fmax(0.0, 1.0 - tail + mass));
-    *ge = upper ? tail : other;
-    *le = upper ? other : tail;
+    double lp;
+    *ge = jl_fisher_greater_general(x, r, K - x, n - r, &lp);
+    *le = jl_fisher_greater_general(K - x, n - r, x, r, &lp);
 }
 
 }  // namespace
@@ -159,7 +131,7 @@ int jl_linkage_stats(const uint32_t *both, const uint32_t *carry, const uint32_t
     out->r2 = (double)(d * d) / (double)((u128)(row1 * row0) * (u128)(col1 * col0));
     const uint64_t d_max = negative ? std::min(row1 * col1, row0 * col0) : std::min(row1 * col0, row0 * col1);
     out->d_prime = d_max ? (negative ? -1.0 : 1.0) * ((double)d / (double)d_max) : 0.0;
-    hypergeometric_tails((double)n11, (double)col1, (double)row1, (double)n, &out->p_positive, &out->p_negative);
+    hypergeometric_tails((uint32_t)n11, (uint32_t)col1, (uint32_t)row1, (uint32_t)n, &out->p_positive, &out->p_negative);
     return JL_OK;
 }
 

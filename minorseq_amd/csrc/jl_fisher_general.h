@@ -7,17 +7,18 @@
 // three binomial log-masses in saddle-point (Loader) form folded into one expression: the deviance terms of the third mass are
 // exactly zero, the square-root factors take one log.  jl_fisher.h is the p = 1/2 case of this, where the four means K/2, L/2
 // are exact; here they are K n / M and the like, rounded, and a deviance bd0(x, mu) moves by (1 - x/mu) d_mu when mu does.
-// At 1e7 coverage and p near 1e-300 that is 1e-11 of ln P, so every mean carries its rounding remainder (one fma: the product
-// K n is exact below 2^53) and the deviance its first-order correction.  The tail that runs away from the mean is summed by the
+// At 1e7 coverage and p near 1e-300 that is 1e-11 of ln P, so every mean carries its rounding remainder (two fmas: the product
+// K n, which rounds above 2^53, as an exact two-product) and the deviance its first-order correction.  Every count is a
+// uint32_t, so the bounds hold for every table the ABI can express (tests/fisher_general_domain.py, family `beyond`).  The tail that runs away from the mean is summed by the
 // ratio recurrence from the point mass, the other one is its complement.  Written once for device and host.
 #pragma once
 #include "jl_fisher.h"
 
-// mu = u v / M rounded, *d = the rest of the quotient (exact product: u v < 2^53)
+// mu = u v / M rounded, *d = the rest of the quotient; u v = uv + uv_lo exactly (uv_lo = 0 below 2^53)
 JL_FHD double jl_mean_with_rest(double u, double v, double M, double *d)
 {
-    const double uv = u * v, mu = uv / M;
-    *d = fma(-mu, M, uv) / M;
+    const double uv = u * v, uv_lo = fma(u, v, -uv), mu = uv / M;
+    *d = (fma(-mu, M, uv) + uv_lo) / M;
     return mu;
 }
 
@@ -83,7 +84,7 @@ JL_FHD double jl_fisher_greater_general_impl(uint32_t a_, uint32_t n_, uint32_t 
     const double hi = K < n ? K : n;
     const double lo = K > m ? K - m : 0.0;
     if (a <= lo) { *logp = 0.0; return 1.0; }
-    const bool upper = a * M >= n * K;   // at or above the mean (both products exact below 2^53)
+    const bool upper = (uint64_t)a_ * m_ >= (uint64_t)n_ * c_;   // a M >= n K, at or above the mean: in integers, both below 2^64
     const double gate = alpha * (1.0 + 1e-6);
     if (upper) {   // sum the decreasing upper tail
         double pm = 0.0, l0 = 0.0;

@@ -475,6 +475,9 @@ struct jl_control_args {
     uint32_t cap, pad_;
 };
 void jl_launch_control_call(const jl_control_args *a, hipStream_t st);
+// jl_control_eval: n tables [[a, cov_s - a], [c, cov_c - c]], one thread each; skipped == nullptr: the plain form
+void jl_launch_control_eval(uint32_t n, const uint32_t *a, const uint32_t *cov_s, const uint32_t *c, const uint32_t *cov_c,
+                            double n_tests, double alpha, double *p, double *lp, uint32_t *skipped, hipStream_t st);
 
 // ---- per-read counters over the whole window (kernels_readstats.hip, capi_readstats.hip; docs/SPEC.md §20)
 struct jl_readstats_shape;     // readstats_shape.h

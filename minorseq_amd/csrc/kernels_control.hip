@@ -76,7 +76,34 @@ __global__ __launch_bounds__(256) void control_compact_kernel(jl_control_args w)
     if (threadIdx.x == 0) w.n_rows[0] = n;
 }
 
+// jl_control_eval: the header's value for table i, nothing of the call stage around it (a diagnostic; not on any hot path)
+__global__ __launch_bounds__(256) void control_eval_kernel(uint32_t n, const uint32_t *__restrict__ a,
+                                                            const uint32_t *__restrict__ cov_s, const uint32_t *__restrict__ c,
+                                                            const uint32_t *__restrict__ cov_c, double n_tests, double alpha,
+                                                            double *__restrict__ p, double *__restrict__ lp,
+                                                            uint32_t *__restrict__ skipped)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    double l;
+    if (skipped) {
+        bool s;
+        p[i] = jl_fisher_greater_general_or_skip(a[i], cov_s[i], c[i], cov_c[i], n_tests, alpha, &l, &s);
+        skipped[i] = s ? 1u : 0u;
+    } else {
+        p[i] = jl_fisher_greater_general(a[i], cov_s[i], c[i], cov_c[i], &l);
+    }
+    lp[i] = l;
+}
+
 }  // namespace
+
+void jl_launch_control_eval(uint32_t n, const uint32_t *a, const uint32_t *cov_s, const uint32_t *c, const uint32_t *cov_c,
+                            double n_tests, double alpha, double *p, double *lp, uint32_t *skipped, hipStream_t st)
+{
+    hipLaunchKernelGGL(control_eval_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, n, a, cov_s, c, cov_c, n_tests, alpha, p, lp,
+                       skipped);
+}
 
 // every array of `a` holds what its comment in jl_internal.h says; a->A.P may be 0 (the table is then empty)
 void jl_launch_control_call(const jl_control_args *a, hipStream_t st)

@@ -67,3 +67,48 @@ def stats(n11, n10, n01, n00, p_values=True):
     if p_values:
         out["p_positive"], out["p_negative"] = hypergeometric_tails(n11, n10, n01, n00)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ designed tables for the tails
+TAIL_READS = (1, 2, 10, 3000, 10 ** 5, 10 ** 7, 2 * 10 ** 9, 2 ** 31 - 1)
+TAIL_SIGMAS = (1, 3, 6, 12, 20, 30, 38, 45)       # 38 sigma is about 1e-300 where the tail is Gaussian, 45 is beyond the doubles
+MAX_TAIL_TABLES = 1200
+
+
+def _isqrt_up(v):
+    r = math.isqrt(v)
+    return r if r * r == v else r + 1
+
+
+def tail_margins(n):
+    """(row1, col1) of n reads: rare x rare, rare x common, common x rare, common x common, both nearly everything."""
+    rare, common = min(30, max(1, n // 3)), max(1, n // 2)
+    out = [(rare, rare), (rare, common), (common, rare), (common, max(1, n // 3)), (n - rare, n - rare)]
+    return [m for k, m in enumerate(out) if 0 < m[0] < n and 0 < m[1] < n and m not in out[:k]]
+
+
+def tail_design():
+    """[(n11, n10, n01, n00)], each once, no random draw: for n = 1 .. 2^31 - 1 reads and the margins of `tail_margins`, n11 at
+    lo, lo + 1, either side of the mean, TAIL_SIGMAS standard deviations to either side of it, hi - 1 and hi (for equal margins
+    hi is perfect linkage, lo with n11 = 0 perfect exclusion, the counts next to them near-perfect), and perfect and near-perfect
+    linkage and exclusion of 10 reads, 1 % and half of 10^5, 10^7 and 2 10^9; the margins of n = 1 are 0."""
+    out = [(1, 0, 0, 0), (0, 1, 0, 0), (0, 0, 1, 0), (0, 0, 0, 1)]
+    for n in TAIL_READS[1:]:
+        for row1, col1 in tail_margins(n):
+            lo, hi = max(0, row1 + col1 - n), min(row1, col1)
+            mean = row1 * col1 // n
+            s = max(1, _isqrt_up(-(-row1 * (n - row1) * col1 * (n - col1) // (n * n * max(n - 1, 1)))))
+            xs = {lo, lo + 1, mean - 1, mean, mean + 1, mean + 2, hi - 1, hi}
+            xs |= {mean + z * s for z in TAIL_SIGMAS} | {mean - z * s for z in TAIL_SIGMAS}
+            for x in sorted({min(max(x, lo), hi) for x in xs}):
+                out.append((x, row1 - x, col1 - x, n - row1 - col1 + x))
+        if n >= 10 ** 5:
+            for k in (10, n // 100, n // 2):
+                out += [(k, 0, 0, n - k), (k, 1, 2, n - k - 3), (k - 1, 1, 0, n - k), (k, 0, 1, n - k - 1)]      # linkage
+                out += [(0, k, k, n - 2 * k), (1, k, k + 2, n - 2 * k - 3), (0, k, n - k, 0), (1, k - 1, n - k - 1, 1)]    # exclusion
+    seen, uniq = set(), []
+    for t in out:
+        if min(t) >= 0 and t not in seen:      # (half of the reads twice, and three more, do not fit)
+            seen.add(t)
+            uniq.append(t)
+    return uniq

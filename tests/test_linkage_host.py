@@ -3,6 +3,7 @@ statistics of a pair's 2 x 2 table (jl_linkage_stats) against the mirror's exact
 line refuses of --linkage before any file is read.  No GPU: the library only has to load."""
 import ctypes as C
 import fnmatch
+import json
 import os
 import re
 import subprocess
@@ -168,6 +169,56 @@ def test_linkage_stats_on_seeded_tables():
             if k % 4 == 0:
                 t = (t[1], t[0], t[3], t[2])
         check_table(*t)
+
+
+# ---------------------------------------------------------------------------------------------- the tails over the whole domain
+P_ABS_TOL, P_REL_TOL = 1e-10, 5e-12     # the project's p-value bounds (DESIGN.md "Numerics"; test_control_host.py)
+
+
+@pytest.fixture(scope="module")
+def tails():
+    with open(os.path.join(ROOT, "tests", "golden", "linkage_tails.json")) as f:
+        return json.load(f)["tables"]
+
+
+def test_tail_fixture_is_the_design(tails):
+    got = [(t["n11"], t["n10"], t["n01"], t["n00"]) for t in tails]
+    assert got == linkage_mirror.tail_design() and len(set(got)) == len(got) and 300 < len(got) <= linkage_mirror.MAX_TAIL_TABLES
+    assert {sum(t) for t in got} == set(linkage_mirror.TAIL_READS)
+    for n in (10 ** 5, 10 ** 7, 2 * 10 ** 9):
+        mine = [t for t in got if sum(t) == n]
+        assert sum(1 for t in mine if t[1] == t[2] == 0) >= 3 and sum(1 for t in mine if t[0] == 0 and t[3] == 0) >= 3   # perfect
+        assert sum(1 for t in mine if 0 < t[1] + t[2] <= 3 and t[0] >= 9) >= 3 and sum(1 for t in mine if t[0] == 1) >= 3      # nearly
+        for row1, col1 in linkage_mirror.tail_margins(n):
+            lo, hi, mean = max(0, row1 + col1 - n), min(row1, col1), row1 * col1 // n
+            xs = {t[0] for t in mine if (t[0] + t[1], t[0] + t[2]) == (row1, col1)}
+            assert {lo, lo + 1, hi, max(lo, mean - 1), min(hi, mean + 1)} <= xs, (n, row1, col1)
+    for side in ("p_positive", "p_negative"):        # p from about 1/2 down to below the doubles, at every depth from 1e5
+        for n in (10 ** 5, 10 ** 7, 2 * 10 ** 9, 2 ** 31 - 1):
+            ps = [float(t[side]) for t in tails if t["n11"] + t["n10"] + t["n01"] + t["n00"] == n]
+            for lo_, hi_ in ((0.3, 0.7), (1e-12, 1e-2), (1e-120, 1e-30), (1e-300, 1e-150), (0.0, 0.0)):
+                assert any(lo_ <= v <= hi_ for v in ps), (side, n, lo_, hi_)
+
+
+def test_linkage_tails_over_the_whole_domain(tails):
+    """p_positive and p_negative against exact arithmetic for n = 1 .. 2^31 - 1: absolute 1e-10, relative 5e-12 where the exact
+    value is above 1e-300, exactly 0 where it is below 2^-1075 (float() of the exact digits is then 0).  Measured: worst relative
+    error 2.9e-13 (the saddle-point routine this entry had before missed the bound from 10^7 reads on: 1.2e-12 there, 1.9e-11 at
+    2 10^9 within 12 sigma of the mean)."""
+    worst = (0.0, (), "")
+    for t in tails:
+        cells = (t["n11"], t["n10"], t["n01"], t["n00"])
+        got = capi.linkage_stats(*tables_of(*cells), [0, 1], 0, 1)
+        assert (got["n11"], got["n10"], got["n01"], got["n00"]) == cells
+        for side in ("p_positive", "p_negative"):
+            exact, p = float(t[side]), got[side]
+            assert abs(p - exact) <= P_ABS_TOL, (cells, side, p, exact)
+            if exact == 0.0:
+                assert p == 0.0, (cells, side, p)
+            elif exact > 1e-300:
+                assert abs(p - exact) <= P_REL_TOL * exact, (cells, side, p, exact, abs(p - exact) / exact)
+                worst = max(worst, (abs(p - exact) / exact, cells, side))
+    print("%d tables, worst relative error %.3g at %s (%s)" % (len(tails), *worst))
 
 
 def test_linkage_stats_refusals():
