@@ -37,15 +37,20 @@ public:
     explicit BamReader(const std::string &path) : in_(path)
     {
         char magic[4];
-        if (!in_.read(magic, 4) || memcmp(magic, "BAM\1", 4) != 0) throw std::runtime_error(path + ": not a BAM file");
-        int32_t l_text = rd<int32_t>();
-        text_.resize((size_t)l_text);
-        if (l_text) in_.read(&text_[0], (size_t)l_text);
+        // untrusted input: the lengths of the header are checked before anything is sized by them, and the bytes they announce
+        // are taken as they arrive (a length beyond the file ends as a truncated header, not as an allocation of 2 GiB)
+        header_bytes(magic, 4);
+        if (memcmp(magic, "BAM\1", 4) != 0) throw std::runtime_error(path + ": not a BAM file");
+        const int32_t l_text = rd<int32_t>();
+        if (l_text < 0) throw std::runtime_error("corrupt BAM header");
+        header_string(text_, (size_t)l_text);
         const int32_t n_ref = rd<int32_t>();
+        if (n_ref < 0) throw std::runtime_error("corrupt BAM header");
         for (int32_t i = 0; i < n_ref; ++i) {
             const int32_t l_name = rd<int32_t>();
-            std::string nm((size_t)l_name, '\0');
-            in_.read(&nm[0], (size_t)l_name);
+            if (l_name < 0) throw std::runtime_error("corrupt BAM header");
+            std::string nm;
+            header_string(nm, (size_t)l_name);
             if (!nm.empty() && nm.back() == '\0') nm.pop_back();
             BamRef r{nm, (uint32_t)rd<int32_t>()};
             refs_.push_back(r);
@@ -114,13 +119,22 @@ public:
     {
         int32_t block = 0;
         if (const uint8_t *q = in_.peek(4)) memcpy(&block, q, 4);
-        else if (!in_.read(&block, 4)) return false;
+        else if (!in_.read(&block, 4)) {
+            if (in_.ended_inside()) throw std::runtime_error("truncated BAM record");
+            return false;
+        }
         if (block < 32) throw std::runtime_error("corrupt BAM record");
         len = (size_t)block;
         p = in_.peek(len);
         if (!p) {
-            buf_.resize(len);
-            if (!in_.read(buf_.data(), len)) throw std::runtime_error("truncated BAM record");
+            // (a piece at a time: block_size is untrusted, and the bytes of a record beyond the file's end are never sized)
+            buf_.clear();
+            for (size_t have = 0; have < len;) {
+                const size_t take = std::min(len - have, kPiece);
+                buf_.resize(have + take);
+                if (!in_.read(buf_.data() + have, take)) throw std::runtime_error("truncated BAM record");
+                have += take;
+            }
             p = buf_.data();
         }
         return true;
@@ -149,7 +163,7 @@ public:
         r.name.assign((const char *)p + o, l_read_name ? l_read_name - 1 : 0);
         o += l_read_name;
         r.cigar.resize(n_cigar);
-        memcpy(r.cigar.data(), p + o, (size_t)n_cigar * 4);
+        if (n_cigar) memcpy(r.cigar.data(), p + o, (size_t)n_cigar * 4);
         o += (size_t)n_cigar * 4;
         static const uint8_t nt16[16] = {4, 0, 1, 4, 2, 4, 4, 4, 3, 4, 4, 4, 4, 4, 4, 4};  // =ACMGRSVTWYHKDBN
         r.seq.resize(unpack_seq ? l_seq : 0);
@@ -167,7 +181,19 @@ public:
     }
 
 private:
-    template <typename T> T rd() { T v; if (!in_.read(&v, sizeof v)) throw std::runtime_error("truncated BAM header"); return v; }
+    static constexpr size_t kPiece = (size_t)1 << 20;
+    void header_bytes(void *dst, size_t n) { if (!in_.read(dst, n)) throw std::runtime_error("truncated BAM header"); }
+    void header_string(std::string &s, size_t n)
+    {
+        s.clear();
+        for (size_t have = 0; have < n;) {
+            const size_t take = std::min(n - have, kPiece);
+            s.resize(have + take);
+            header_bytes(&s[have], take);
+            have += take;
+        }
+    }
+    template <typename T> T rd() { T v; header_bytes(&v, sizeof v); return v; }
     BgzfReader in_;
     std::string text_;
     std::vector<BamRef> refs_;

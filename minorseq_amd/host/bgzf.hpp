@@ -44,8 +44,10 @@ public:
         if (!block_mode_) inflateEnd(&z_);
         if (f_) fclose(f_);
     }
-    // read exactly n bytes; returns false on clean EOF at a record boundary (n bytes not started)
+    // read exactly n bytes; returns false when the stream ends first: at a boundary (n bytes not started), or inside the n
+    // bytes, which ended_inside() then tells (the caller knows what was cut short: the header or a record)
     bool read(void *dst, size_t n) { return block_mode_ ? read_blocks(dst, n) : read_stream(dst, n); }
+    bool ended_inside() const { return ended_inside_; }
     // the next n bytes in place when they lie inside the inflated batch at hand (valid until the next call), else
     // nullptr: the caller then copies them with read()
     const uint8_t *peek(size_t n)
@@ -154,8 +156,8 @@ private:
         while (got < n) {
             if (out_pos_ == out_.size()) {
                 if (!refill()) {
-                    if (got == 0) return false;
-                    throw std::runtime_error("truncated BGZF stream");
+                    ended_inside_ = got != 0;
+                    return false;
                 }
                 continue;
             }
@@ -179,8 +181,8 @@ private:
                 if (z_.avail_in == 0) eof_ = true;
             }
             if (z_.avail_in == 0 && eof_) {
-                if (got == 0) return false;
-                throw std::runtime_error("truncated BGZF stream");
+                ended_inside_ = got != 0;
+                return false;
             }
             z_.next_out = out + got;
             z_.avail_out = (uInt)std::min<size_t>(n - got, 1u << 30);
@@ -207,6 +209,7 @@ private:
     z_stream z_;
     std::vector<uint8_t> in_;
     bool eof_ = false;
+    bool ended_inside_ = false;
 };
 
 class BgzfWriter {

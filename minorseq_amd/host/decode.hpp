@@ -167,6 +167,7 @@ private:
         std::condition_variable cv;
         bool inflated = false, parsed = false, last = false;
         std::string error;
+        std::string split_error;   // what ended the splitter's walk inside this segment: reported after its whole records are parsed
     };
     using SegPtr = std::shared_ptr<Segment>;
 
@@ -309,7 +310,10 @@ private:
                     uint32_t block;
                     memcpy(&block, p, 4);
                     (void)n;
-                    if (rid >= 0) parse_record(p + 4, block, opt_, want_qual_, rid, s.chunk, s.extent);
+                    // (rid < 0: no kept record up to the end of this segment; its records are still checked like the sequential
+                    // reader checks them, and none of them is kept — BECAUSE note_first_kept below drops by the same rules as
+                    // parse_record: flags, ref_id, pos, rq.  Change one and change the other, or a segment picks a reference of its own)
+                    parse_record(p + 4, block, opt_, want_qual_, rid, s.chunk, s.extent);
                 };
                 if (!s.joined.empty()) one(s.joined.data(), s.joined.size());
                 size_t o = s.rec_begin;
@@ -319,6 +323,9 @@ private:
                     one(s.out.data() + o, 4 + (size_t)block);
                     o += 4 + (size_t)block;
                 }
+                // the first fault in stream order is the one reported, as by the sequential reader: a record in front of the place
+                // where the walk over the block_size words ended comes first
+                if (!s.split_error.empty()) throw std::runtime_error(s.split_error);
             }
             give_out(std::move(s.out));
             s.out = RawBuf();
@@ -392,8 +399,9 @@ private:
                 s->out.clear();
                 s->rec_begin = s->rec_end = 0;
             } else {
+                size_t o = 0;   // first byte of s->out not yet accounted for
+                bool walking = false;   // past the header and a joined record: [rec_begin, o) are whole records
                 try {
-                    size_t o = 0;   // first byte of s->out not yet accounted for
                     if (!header_done) {
                         carry.insert(carry.end(), s->out.data(), s->out.data() + s->out.size());
                         o = s->out.size();
@@ -415,7 +423,7 @@ private:
                             if (carry.size() >= 4) {
                                 uint32_t block;
                                 memcpy(&block, carry.data(), 4);
-                                if (block < 32) throw std::runtime_error("corrupt BAM record");
+                                if (block < 32 || block > 0x7FFFFFFFu) throw std::runtime_error("corrupt BAM record");
                                 const size_t want = 4 + (size_t)block, have = carry.size();
                                 const size_t take = std::min(want - have, b.size() - o);
                                 carry.insert(carry.end(), b.data() + o, b.data() + o + take);
@@ -428,11 +436,12 @@ private:
                             }
                         }
                         s->rec_begin = o;
+                        walking = true;
                         while (carry.empty() && o < b.size()) {
                             if (b.size() - o < 4) break;
                             uint32_t block;
                             memcpy(&block, b.data() + o, 4);
-                            if (block < 32) throw std::runtime_error("corrupt BAM record");
+                            if (block < 32 || block > 0x7FFFFFFFu) throw std::runtime_error("corrupt BAM record");   // (a signed word)
                             if (b.size() - o < 4 + (size_t)block) break;
                             note_first_kept(b.data() + o);
                             o += 4 + (size_t)block;
@@ -442,7 +451,14 @@ private:
                     }
                     s->ref_id = ref_id_;
                 } catch (const std::exception &ex) {
-                    s->error = err = ex.what();
+                    err = ex.what();
+                    if (walking) {   // the whole records in front of the fault are still parsed (parse_segment reports it after them)
+                        s->rec_end = o;
+                        s->ref_id = ref_id_;
+                        s->split_error = err;
+                    } else {
+                        s->error = err;
+                    }
                 }
             }
             Segment *raw = s.get();
@@ -452,14 +468,16 @@ private:
         }
         if (err.empty() && (!header_done || !carry.empty())) {   // the stream ended inside the header or a record
             SegPtr s = std::make_shared<Segment>();
-            s->error = header_done ? "truncated BAM record" : "not a BAM file (truncated header)";
+            s->error = header_done ? "truncated BAM record" : "truncated BAM header";
             s->inflated = s->parsed = true;
             to_consume_.push(std::move(s), max_inflight_, stop_);
         }
         to_consume_.close();
     }
 
-    // the reference of the first KEPT record decides which reference is read (ref_id < 0 on entry)
+    // the reference of the first KEPT record decides which reference is read (ref_id < 0 on entry).  "Kept" is parse_record's rule
+    // (msa_builder.hpp), restated: the two must stay the same, since parse_segment calls parse_record with no reference chosen for
+    // a segment in which this function found no kept record, and relies on it keeping none either
     void note_first_kept(const uint8_t *rec)
     {
         if (ref_id_ >= 0) return;
@@ -488,8 +506,9 @@ private:
         size_t o = 0;
         auto need = [&](size_t n) { return buf.size() - o >= n; };
         auto i32 = [&]() { int32_t v; memcpy(&v, buf.data() + o, 4); o += 4; return v; };
-        if (!need(8)) return false;
+        if (!need(4)) return false;
         if (memcmp(buf.data(), "BAM\1", 4) != 0) throw std::runtime_error(path_ + ": not a BAM file");
+        if (!need(8)) return false;
         o = 4;
         const int32_t l_text = i32();
         if (l_text < 0) throw std::runtime_error("corrupt BAM header");

@@ -89,9 +89,9 @@ inline bool keep_record(const BamRecord &r)
     return !(r.flag & 0x4) && !(r.flag & 0x100) && r.ref_id >= 0 && r.pos >= 0;
 }
 
-inline uint32_t ref_span(const BamRecord &r)
+inline uint64_t ref_span(const BamRecord &r)
 {
-    uint32_t n = 0;
+    uint64_t n = 0;   // (65535 ops of up to 2^28 - 1 columns: not a 32-bit sum)
     for (uint32_t c : r.cigar) {
         const uint32_t op = c & 15;
         if (op == CIG_D || op == CIG_N || op == CIG_EQ || op == CIG_X || op == CIG_M) n += c >> 4;
@@ -118,7 +118,7 @@ inline ReadExtent scan_extent(const std::string &bam, const IngestOptions &opt)
         if (r.ref_id != e.ref_id) continue;
         ++e.n_reads;
         e.min_pos = std::min<int64_t>(e.min_pos, r.pos);
-        e.max_end = std::max<int64_t>(e.max_end, (int64_t)r.pos + ref_span(r));
+        e.max_end = std::max<int64_t>(e.max_end, (int64_t)r.pos + (int64_t)ref_span(r));
     }
     return e;
 }
@@ -225,8 +225,12 @@ struct RecordSink {
     std::function<void(RecordArrays &)> give;   // swaps the full chunk for an empty one
 };
 
+constexpr uint64_t kMaxRefSpan = (uint64_t)1 << 30;   // reference bases a read may span: one more than cigar_rules.h kRunMask
+
 // One record of the stream -> the arrays the device ingests (shared by the sequential and the pipelined reader).
-// `ref_id`: -1 = not known yet (the first kept record decides; sequential reader only).  Returns whether it was kept.
+// `ref_id`: -1 = not known yet: the first kept record decides.  The sequential reader relies on that; the pipelined one chooses the
+// reference in its splitter (decode.hpp, note_first_kept, which restates the drop rules below: flags, ref_id, pos, rq — keep the two
+// the same) and passes -1 only for a segment without a kept record.  Returns whether it was kept.
 inline bool parse_record(const uint8_t *p, size_t len, const IngestOptions &opt, bool want_qual, int &ref_id, RecordArrays &out,
                          ReadExtent &e)
 {
@@ -250,9 +254,8 @@ inline bool parse_record(const uint8_t *p, size_t len, const IngestOptions &opt,
     if (rid != ref_id) return false;
     const size_t c_at = out.cigar.size();
     out.cigar.resize(c_at + n_cigar);
-    memcpy(out.cigar.data() + c_at, p + o_cig, (size_t)n_cigar * 4);
-    uint32_t span = 0;
-    uint64_t query = 0;
+    if (n_cigar) memcpy(out.cigar.data() + c_at, p + o_cig, (size_t)n_cigar * 4);   // (a read without a cigar into empty arrays: no null to memcpy)
+    uint64_t span = 0, query = 0;   // (65535 ops of up to 2^28 - 1 columns: a 32-bit sum wraps)
     for (size_t k = c_at; k < out.cigar.size(); ++k) {
         const uint32_t op = out.cigar[k] & 15;
         if (op == CIG_M) {
@@ -269,30 +272,37 @@ inline bool parse_record(const uint8_t *p, size_t len, const IngestOptions &opt,
         throw std::runtime_error("read " + name + ": cigar consumes " + std::to_string(query) + " bases, the record holds " +
                                  std::to_string(l_seq));
     }
+    // the device keeps a window column in 30 bits and refuses a read that spans more (cigar_rules.h, verdict 4): refused here, before
+    // the extent, which sizes the window, takes it in
+    if (span >= kMaxRefSpan) {
+        const std::string name((const char *)p + 32, l_name ? l_name - 1 : 0);
+        throw std::runtime_error("read " + name + ": cigar spans " + std::to_string(span) + " reference bases, the limit is " +
+                                 std::to_string(kMaxRefSpan - 1));
+    }
     ++e.n_reads;
     e.min_pos = std::min<int64_t>(e.min_pos, pos);
-    e.max_end = std::max<int64_t>(e.max_end, (int64_t)pos + span);
+    e.max_end = std::max<int64_t>(e.max_end, (int64_t)pos + (int64_t)span);
     out.pos.push_back(pos);
     out.cig_off.push_back(out.cigar.size());
     // (resize + memcpy: a range insert into a vector with an allocator of its own goes through construct(), element by element)
     const size_t s_at = out.seq4.size();
     out.seq4.resize(s_at + (o_qual - o_seq));
-    memcpy(out.seq4.data() + s_at, p + o_seq, o_qual - o_seq);
+    if (o_qual > o_seq) memcpy(out.seq4.data() + s_at, p + o_seq, o_qual - o_seq);
     out.seq_off.push_back(out.seq4.size());
     if (want_qual && opt.qv_mask) {
         // the effective qualities of this read only, folded as below, then one compare per sixteen bases: its bits of the mask
         out.qual.resize(l_seq);
-        memcpy(out.qual.data(), p + o_qual, l_seq);
+        if (l_seq) memcpy(out.qual.data(), p + o_qual, l_seq);
         for (int k = 0; k < 3; ++k) min_with_track(out.qual.data(), aux.track[k], std::min<size_t>(aux.len[k], l_seq));
         const size_t m_at = out.qmask.size(), m_end = (out.seq4.size() + 3) / 4;
         out.qmask.resize(m_end);
-        memset(out.qmask.data() + m_at, 0, m_end - m_at);
+        if (m_end > m_at) memset(out.qmask.data() + m_at, 0, m_end - m_at);
         mask_low_quals(out.qmask.data(), 2 * (uint64_t)s_at, out.qual.data(), l_seq, (uint8_t)std::min<uint32_t>(opt.min_qv, 127u));
         out.qual.clear();
     } else if (want_qual) {
         const size_t q_at = out.qual.size();
         out.qual.resize(q_at + l_seq);
-        memcpy(out.qual.data() + q_at, p + o_qual, l_seq);
+        if (l_seq) memcpy(out.qual.data() + q_at, p + o_qual, l_seq);
         for (int k = 0; k < 3; ++k) min_with_track(out.qual.data() + q_at, aux.track[k], std::min<size_t>(aux.len[k], l_seq));
         out.qual_off.push_back(out.qual.size());
     }

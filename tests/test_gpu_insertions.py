@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import bam_py
 import insertion_mirror as im
 import records_expand
 from minorseq_amd import capi, msa
@@ -349,34 +350,8 @@ PLANT_COL, SPLIT_COL, PLANT_LEN, PLANT_PERMILLE = 30, 46, 6, 20      # before ge
 
 
 def read_bam(path):
-    """The primary records of a BAM as the arrays the library takes (BGZF is a run of gzip members; SAM spec section 4.2)."""
-    import gzip
-    import struct
-    data = gzip.open(path, "rb").read()
-    assert data[:4] == b"BAM\x01"
-    l_text, = struct.unpack_from("<i", data, 4)
-    at = 8 + l_text
-    n_ref, = struct.unpack_from("<i", data, at)
-    at += 4
-    for _ in range(n_ref):
-        l_name, = struct.unpack_from("<i", data, at)
-        at += 8 + l_name
-    pos, cigar, cig_off, seq4, seq_off, qual, qual_off = [], [], [0], bytearray(), [0], bytearray(), [0]
-    while at < len(data):
-        size, _ref, p, l_name, _mapq, _bin, n_cig, _flag, l_seq = struct.unpack_from("<iiiBBHHHi", data, at)
-        body = at + 36
-        c0 = body + l_name
-        pos.append(p)
-        cigar += struct.unpack_from("<%dI" % n_cig, data, c0)
-        s0 = c0 + 4 * n_cig
-        seq4 += data[s0:s0 + (l_seq + 1) // 2]
-        q0 = s0 + (l_seq + 1) // 2
-        qual += data[q0:q0 + l_seq]
-        cig_off.append(len(cigar)), seq_off.append(len(seq4)), qual_off.append(len(qual))
-        at += 4 + size
-    return dict(pos=np.array(pos, dtype=np.int32), cigar=np.array(cigar, dtype=np.uint32), cig_off=np.array(cig_off, dtype=np.uint64),
-                seq4=np.frombuffer(bytes(seq4), dtype=np.uint8), seq_off=np.array(seq_off, dtype=np.uint64),
-                qual=np.frombuffer(bytes(qual), dtype=np.uint8), qual_off=np.array(qual_off, dtype=np.uint64))
+    """The records of a BAM as the arrays the library takes, through the suite's independent reader (tests/bam_py.py)."""
+    return bam_py.record_arrays(bam_py.read_bam(str(path))[2])
 
 
 def juliet(d, *args):
