@@ -521,6 +521,53 @@ typedef struct {
  * above 2^32 - 1. */
 int jl_deletion_test(const uint32_t cnt[4], const jl_params *prm, double n_tests, jl_deletion_call *out);
 /*
+ * Deletions BY EXTENT (docs/SPEC.md §25): the table above sees a deletion codon by codon; this call names it by where it starts
+ * and how long it is.  Per read i < n_reads a RUN is a maximal stretch [s, s + len) of columns whose cells are all code 4.  A run
+ * is BOUNDED iff s >= 1, s + len <= n_cols - 1 and the cells at s - 1 and at s + len are not code 6 (they are a base or an N
+ * then); any other run is OPEN: it touches the window's edge or an uncovered cell, its true extent is unknown, and it is never
+ * an allele.  Results, exact integers independent of launch shape and order:
+ *   runs[2]        {bounded, open}: the runs of each kind over all reads
+ *   open[n_cols]   reads whose cell at c is code 4 and lies in an open run
+ *   rows           one {col = s, len, count, flank} per distinct (s, len) among the bounded runs, ascending by (col, len):
+ *                  count = the reads with exactly that run, flank = the reads whose cells at s - 1 and s + len are both != 6
+ * Grouping is on the full key, never on a hash; the caller gives no capacity and no allele is ever dropped.  Reads past n_reads
+ * count nowhere: the padding, and whatever an adopted matrix holds past byte ceil(n_reads / 8) of a plane row or past the last
+ * read in its last byte.  Any n_cols >= 1 is accepted (below 3 columns no run is bounded and the table is empty).
+ * The contract is jl_codon_deletions_async's: buffers of its own on the context's stream, nothing else of the context is touched,
+ * every kind of resident matrix is accepted.  ONE WAIT: the table is sized from the number of runs of the matrix, so the call
+ * enqueues a kernel that counts them and waits for that single count on the context's stream; the walk over the runs, the flank
+ * counts and the rows are then enqueued, not waited for, and the matrix is not needed again at fetch time.
+ * JL_ERR_STATE: no resident matrix.  JL_ERR_MEMORY: no room for the table.  A refused call changes nothing.
+ */
+typedef struct {
+    uint32_t col;     /* s: the first deleted column */
+    uint32_t len;
+    uint32_t count;   /* reads with exactly this run */
+    uint32_t flank;   /* reads covered (code != 6) at s - 1 and at s + len */
+} jl_deletion_allele;
+int jl_deletion_alleles_async(jl_ctx *ctx);
+/* Wait and copy out the results of the last jl_deletion_alleles_async, in THAT call's n_cols, whatever was enqueued behind it and
+ * whatever matrix is resident now.  runs, open: NULL = not wanted.  *n_rows = the rows of the table; rows == NULL: the count
+ * only.  JL_ERR_STATE: none was enqueued.  JL_ERR_ARG: cap below the rows (nothing is lost: fetch again with room). */
+int jl_deletion_alleles_fetch(jl_ctx *ctx, uint64_t runs[2], uint32_t *open /* [n_cols] */, jl_deletion_allele *rows, uint32_t cap,
+                              uint32_t *n_rows);
+/* One allele tested against a rate of such deletions by error: coverage = flank, expected = round_mode(coverage * rate) clamped
+ * to [0, coverage] (prm->expected_round, the product in IEEE double), the table [[count, coverage - count], [expected, coverage -
+ * expected]], p by prm->tail from the routines of the codon test, p_value = min(1, p * n_tests), called = count > 0 and p_value <
+ * prm->alpha and the prm->min_perc / max_perc filters on 100 count / coverage (strict).  coverage == 0: not called, p_value 1. */
+typedef struct {
+    uint32_t count;
+    uint32_t coverage;  /* flank */
+    uint32_t expected;
+    uint32_t called;    /* 0 or 1 */
+    double p_value;     /* Bonferroni-adjusted, <= 1 */
+    double log_p;       /* ln of the unadjusted p */
+} jl_deletion_allele_call;
+/* Host only (no device, no context).  n_tests: the Bonferroni factor, RESOLVED.  JL_ERR_ARG (jl_last_error(NULL) says which): a
+ * NULL argument; n_tests <= 0; rate outside [0, 1]; count > flank. */
+int jl_deletion_allele_test(uint32_t count, uint32_t flank, const jl_params *prm, double rate, double n_tests,
+                            jl_deletion_allele_call *out);
+/*
  * PER-READ counters over the whole resident window (docs/SPEC.md §20): every other stage looks at the matrix by column; a read that
  * disagrees with the window at dozens of columns (off-target, chimeric, hypermutated, badly aligned at its ends) raises several
  * minor codons at once, and this is the call that shows it.  For read i, summed over all n_cols columns, with `code` its cell

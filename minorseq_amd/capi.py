@@ -36,13 +36,14 @@ SITE_NO_FILL, SITE_PRESENT, SITE_DELETED, SITES_MAX = 0xFF, 0, 1, 4096
 INSERTION_ALLELE = np.dtype([("col", "<u4"), ("len", "<u4"), ("seq", "<u8"), ("count", "<u4"), ("pad_", "<u4")])   # jl_insertion_allele
 INSERTION_EVENT = np.dtype([("read", "<u4"), ("col", "<u4"), ("len", "<u4"), ("kind", "<u4"), ("seq", "<u8")])       # jl_insertion_event
 SITE_INSERTION = 2
+DELETION_ALLELE = np.dtype([("col", "<u4"), ("len", "<u4"), ("count", "<u4"), ("flank", "<u4")])   # jl_deletion_allele
 SITE_INS_NONE, SITE_INS_OTHER, SITE_INS_MAX_ALLELES = 0, 63, 62
 
 # every symbol include/juliet_hip.h declares (checked by tests/test_capi_exports.py)
 EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", "jl_ctx_destroy", "jl_last_error",
            "jl_sync", "jl_col_stride", "jl_plane_stride", "jl_msa_upload", "jl_msa_alloc", "jl_msa_adopt", "jl_msa_pack_rows",
            "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_take", "jl_msa_take_async", "jl_sample_reads", "jl_mix_counts", "jl_msa_download", "jl_msa_download_planes", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
-           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_class_codons_async", "jl_class_codons_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_phase_nearest_async", "jl_phase_nearest_fetch", "jl_phase_recombinants_async", "jl_phase_recombinants_fetch", "jl_haplotype_recombinants", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_read_stats_async", "jl_read_stats_fetch", "jl_read_filter", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_msa_track_insertion_reads", "jl_insertion_reads_fetch", "jl_sites_assemble_alleles", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_control_call_async", "jl_control_call_fetch", "jl_control_test", "jl_phase_async", "jl_phase_fetch",
+           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_class_codons_async", "jl_class_codons_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_phase_nearest_async", "jl_phase_nearest_fetch", "jl_phase_recombinants_async", "jl_phase_recombinants_fetch", "jl_haplotype_recombinants", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_deletion_alleles_async", "jl_deletion_alleles_fetch", "jl_deletion_allele_test", "jl_read_stats_async", "jl_read_stats_fetch", "jl_read_filter", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_msa_track_insertion_reads", "jl_insertion_reads_fetch", "jl_sites_assemble_alleles", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_control_call_async", "jl_control_call_fetch", "jl_control_test", "jl_phase_async", "jl_phase_fetch",
            "jl_ctx_stream", "jl_run_async", "jl_run_wait", "jl_run_done", "jl_run_view_get", "jl_group_create", "jl_group_destroy",
            "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_msa_index_info", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_control_eval", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
            "jl_allgather_variants", "jl_allgather_variants_async", "jl_allgather_variants_async_many", "jl_allgather_variants_many", "jl_group_exchange_bind", "jl_group_exchange_collect", "jl_xwin_plan", "jl_xwin_assemble_local",
@@ -251,6 +252,9 @@ def load_library(path=LIB_PATH):
     lib.jl_codon_deletions_async.argtypes = [vp]
     lib.jl_codon_deletions_fetch.argtypes = [vp, vp]
     lib.jl_deletion_test.argtypes = [vp, vp, C.c_double, vp]
+    lib.jl_deletion_alleles_async.argtypes = [vp]
+    lib.jl_deletion_alleles_fetch.argtypes = [vp, vp, vp, vp, C.c_uint32, vp]
+    lib.jl_deletion_allele_test.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_double, C.c_double, vp]
     lib.jl_read_stats_async.argtypes = [vp, vp]
     lib.jl_read_stats_fetch.argtypes = [vp, vp]
     lib.jl_read_filter.argtypes = [vp, u64, C.POINTER(ReadRule), vp, C.POINTER(u64), vp]
@@ -756,6 +760,26 @@ class Juliet:
         self._chk(self.lib.jl_codon_deletions_fetch(self.h, _p(cnt) if cnt.size else None))
         return cnt
 
+    def deletion_alleles(self, wait=True):
+        """jl_deletion_alleles_async (docs/SPEC.md §25): every read's maximal runs of '-' in the resident matrix.  Returns
+        dict(runs = uint64[2] (bounded, open), open = uint32[n_cols] reads in an open run at each column, alleles =
+        DELETION_ALLELE rows (col, len, count, flank), one per distinct bounded (start, length), ascending by (col, len)), all
+        exact.  The call waits once, for the number of runs (the table is sized from it); wait=False then only enqueues the rest on
+        this context's stream and returns None (deletion_alleles_fetch brings the arrays, in this call's own n_cols)."""
+        self._chk(self.lib.jl_deletion_alleles_async(self.h))
+        self._dal_cols = self.n_cols
+        return self.deletion_alleles_fetch() if wait else None
+
+    def deletion_alleles_fetch(self):
+        runs = np.zeros(2, dtype=np.uint64)
+        open_ = np.zeros(max(1, getattr(self, "_dal_cols", 0)), dtype=np.uint32)
+        n = C.c_uint32(0)
+        self._chk(self.lib.jl_deletion_alleles_fetch(self.h, _p(runs), _p(open_), None, 0, C.byref(n)))
+        rows = np.zeros(n.value, dtype=DELETION_ALLELE)
+        if n.value:
+            self._chk(self.lib.jl_deletion_alleles_fetch(self.h, None, None, _p(rows), n.value, C.byref(n)))
+        return dict(runs=runs, open=open_[: getattr(self, "_dal_cols", 0)], alleles=rows)
+
     def read_stats(self, compare=None, wait=True):
         """jl_read_stats_async (docs/SPEC.md §20): per read of the resident matrix, over all columns, its bases, gaps, masked cells,
         bases in compared columns and mismatches among those.  compare[n_cols]: a code per column, 4 or above = not compared (the
@@ -1220,6 +1244,25 @@ def deletion_test(cnt, params, n_tests):
     if rc:
         raise JulietError(rc, "jl_deletion_test: " + lib.jl_last_error(None).decode())
     d = {name: getattr(out, name) for name, _ in DeletionCall._fields_ if name != "pad_"}
+    d["called"] = bool(d["called"])
+    return d
+
+
+class DeletionAlleleCall(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("coverage", C.c_uint32), ("expected", C.c_uint32), ("called", C.c_uint32),
+                ("p_value", C.c_double), ("log_p", C.c_double)]
+
+
+def deletion_allele_test(count, flank, params, rate, n_tests):
+    """jl_deletion_allele_test (host only, docs/SPEC.md §25): one row of Juliet.deletion_alleles against a rate of such deletions by
+    error, coverage = flank, with the codon test's resolved Bonferroni factor n_tests: dict(count, coverage, expected, called,
+    p_value = min(1, p * n_tests), log_p = ln p)."""
+    lib = load_library()
+    out = DeletionAlleleCall()
+    rc = lib.jl_deletion_allele_test(int(count), int(flank), C.byref(params), float(rate), float(n_tests), C.byref(out))
+    if rc:
+        raise JulietError(rc, "jl_deletion_allele_test: " + lib.jl_last_error(None).decode())
+    d = {name: getattr(out, name) for name, _ in DeletionAlleleCall._fields_}
     d["called"] = bool(d["called"])
     return d
 

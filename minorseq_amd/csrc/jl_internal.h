@@ -459,6 +459,28 @@ struct jl_del_args {
 };
 void jl_launch_codon_deletions(const jl_del_args *a, hipStream_t st);
 
+// ---- deletions by extent: (start, length) alleles (kernels_del_alleles.hip, capi_del_alleles.hip; docs/SPEC.md §25)
+struct jl_dal_args {
+    const uint8_t *msa;        // the window's bit planes
+    uint64_t plane_stride;     // ... and their stride (an adopted matrix brings its own)
+    uint64_t n_reads;
+    uint32_t n_cols;           // >= 1
+    uint32_t n_words;          // words of a row that hold reads: ceil(n_reads / 32); 4 n_words <= plane_stride
+    uint32_t seg_cols;         // columns a workgroup walks (set by the launcher)
+    uint32_t occ_cap;          // room in occ[] (and in the rows): no more distinct alleles can exist
+    unsigned long long *n_starts;   // [1] the runs of the matrix (the counting launch); zeroed
+    unsigned long long *runs;  // [2] bounded, open; zeroed
+    uint32_t *diff;            // [n_cols + 1]: + k where k open runs begin, - k where they end, modulo 2^32; zeroed
+    // the allele table: `slots` (a power of two, at least twice occ_cap) key words col << 32 | len, all ones = empty, and their
+    // read counts, zeroed; occ[] lists the slots in use, *n_occ (zeroed) how many
+    unsigned long long *keys;
+    uint32_t *count, *occ, *n_occ;
+    uint64_t slots_mask;
+};
+void jl_launch_deletion_starts(const jl_dal_args *a, hipStream_t st);
+void jl_launch_deletion_runs(const jl_dal_args *a, hipStream_t st);
+void jl_launch_deletion_rows(const jl_dal_args *a, jl_deletion_allele *rows, hipStream_t st);
+
 // ---- codon calls against a control's histograms (kernels_control.hip, capi_control.hip; docs/SPEC.md §21)
 struct jl_control_args {
     jl_call_args A;            // alpha, n_tests, min_perc, max_perc, P (the error model's fields are not read)
@@ -811,6 +833,14 @@ struct jl_ctx {
     // ---- jl_codon_deletions_async: a buffer of its own, grown on demand (capi_del.hip); no stage and no run touches it
     jl_dev_array<uint32_t> del_out;        // cnt [del_cols - 2][4]
     uint32_t del_cols = 0;                 // columns of the last call enqueued (0: none)
+
+    // ---- jl_deletion_alleles_async: buffers of its own, grown on demand (capi_del_alleles.hip); no stage and no run touches them
+    jl_dev_array<unsigned long long> dal_u64;   // n_starts [1], runs [2], a spare word, then the keys [dal_slots]
+    jl_dev_array<uint32_t> dal_u32;             // n_occ [1] and three spare words, diff [dal_cols + 1], count [dal_slots], occ [dal_cap]
+    jl_dev_array<jl_deletion_allele> dal_rows;  // [dal_cap], in the order in which the slots were claimed
+    uint64_t dal_slots = 0;                     // of the last call enqueued
+    uint32_t dal_cap = 0;                       // ... its bound on the distinct alleles
+    uint32_t dal_cols = 0;                      // ... and its columns (0: none)
 
     // ---- jl_control_call_async with this context as the SAMPLE: result buffers of its own, grown on demand (capi_control.hip); the
     // masks and the staged rows of the call stage (d_called, d_staged) are its scratch, no stage result and no run sees the rest

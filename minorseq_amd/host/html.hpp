@@ -400,6 +400,26 @@ inline std::string render_html(const Json &root)
             }
         h += "</table></details>\n";
     }
+    // ---- --call-deletion-alleles (docs/SPEC.md §25): the called deletions by extent, one table; doubles as the JSON prints them
+    if (const Json *db = root.get("deletion_alleles")) {
+        h += "<details open id=\"deletion-alleles\"><summary>Deletion alleles</summary><table id=\"deletion-alleles-summary\">\n";
+        for (const char *key : {"rate", "min_length", "bounded_runs", "open_runs", "n_alleles", "n_alleles_tested"})
+            h += "<tr data-key=\"" + std::string(key) + "\"><th>" + key + "</th>" + td(num_str(db->get(key))) + "</tr>\n";
+        h += "</table>\n<table id=\"deletion-alleles-table\"><tr><th>Begin</th><th>Length</th><th>#Reads</th><th>Coverage</th><th>Frequency</th>"
+             "<th>Expected</th><th>p</th><th>ln p</th><th>In frame</th><th>Genes</th></tr>\n";
+        if (const Json *al = db->get("alleles"))
+            for (const Json &a : al->arr) {
+                h += "<tr class=\"deletion-allele\">";
+                for (const char *key : {"begin_abs", "length", "count", "coverage", "frequency", "expected", "pValue", "log_pValue", "in_frame"}) h += td(num_str(a.get(key)));
+                std::string gs;   // name first-last aligned|unaligned, the genes separated by "; "
+                if (const Json *genes = a.get("genes"))
+                    for (const Json &g : genes->arr)
+                        gs += (gs.empty() ? "" : "; ") + g.get_str("name") + " " + num_str(g.get("first_position")) + "-" + num_str(g.get("last_position")) +
+                              (g.get("codon_aligned") && g.get("codon_aligned")->b ? " aligned" : " unaligned");
+                h += td(gs) + "</tr>\n";
+            }
+        h += "</table></details>\n";
+    }
     h += "</body></html>\n";
     return h;
 }

@@ -167,6 +167,10 @@ int run_one_window(Run &run)
         if (const char *what = fetch_insertions(ctx, opt, smp.prm, smp.genes, n_cols, R)) die_jl(ctx, what);
         tick("insertions");
     }
+    if (opt.call_deletion_alleles) {
+        if (const char *what = fetch_deletion_alleles(ctx, opt, smp.prm, smp.genes, R)) die_jl(ctx, what);
+        tick("deletion_alleles");
+    }
     if (opt.phase_deletions || opt.phase_insertions) {   // (the haplotypes, hit rows and per-read ids from here on are those of the site matrix)
         jl_ctx *pc = nullptr;
         if (const char *what = fetch_sites_phase(ctx, opt.device, opt.min_reads, n_reads, opt.phase_deletions, opt.phase_insertions, R, &pc)) die_jl(pc ? pc : ctx, what);

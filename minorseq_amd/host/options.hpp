@@ -57,6 +57,11 @@ struct Options {
     bool call_insertions = false;    // --call-insertions: in-frame insertion alleles before every evaluated position (docs/SPEC.md §17)
     bool have_insertion_rate = false;
     double insertion_rate = 0.0;     // --insertion-rate r: a read shows an in-frame insertion at a junction by error (default: the chemistry's deletion rate)
+    bool call_deletion_alleles = false;   // --call-deletion-alleles: deletions by (start, length) over the whole window (docs/SPEC.md §25)
+    bool have_deletion_allele_rate = false;
+    double deletion_allele_rate = 0.0;    // --deletion-allele-rate r: a read shows one given deletion by error (default: the chemistry's deletion rate)
+    bool have_min_deletion_length = false;
+    uint32_t min_deletion_length = 1;     // --min-deletion-length K: shorter alleles are neither tested nor listed
     bool fuse_only = false;        // invoked as `fuse in.bam out.fasta` (doc/FUSE.md:26-31): the consensus and nothing else
     double ins_min_frac = 0.5;     // an insertion enters the consensus when more than this share of the covering reads carries it
     uint32_t ins_min_distance = 10;  // ... and the previous included insertion lies at least this many columns back (UNPINNED)
@@ -197,6 +202,19 @@ struct Options {
         "                                      insertion_alleles (gene, after_position, inserted_codons) and every haplotype\n"
         "                                      `insertions`, a flag per allele; every insertion_positions entry gains haplotype_hit.\n"
         "                                      Not with --rescue-damaged, nor where --call-insertions is refused\n"
+        "      --call-deletion-alleles [--deletion-allele-rate r] [--min-deletion-length K]  deletions by extent (docs/SPEC.md\n"
+        "                                      section 25), with and without --mode-phasing: the device groups every read's maximal\n"
+        "                                      runs of deleted bases by (start, length) over the whole window.  A run that touches the\n"
+        "                                      window's edge or an uncovered base is open and is no allele.  Every allele of K bases\n"
+        "                                      or more (default 1) is tested by the codon test's own Fisher test, Bonferroni factor\n"
+        "                                      and --min-perc / --max-perc against r, the rate of one such deletion by error (default:\n"
+        "                                      the chemistry's deletion rate), over coverage = the reads covering the base before and\n"
+        "                                      the base after it.  The JSON root gains `deletion_alleles`: rate, min_length,\n"
+        "                                      bounded_runs, open_runs, n_alleles, n_alleles_tested (to correct with) and one entry\n"
+        "                                      per called allele: begin_abs, length, count, coverage, frequency, expected, pValue,\n"
+        "                                      log_pValue, in_frame and the genes it overlaps (first_position, last_position,\n"
+        "                                      codon_aligned).  Follows --downsample / --mix.  Not with --windows, --devices a,b,\n"
+        "                                      --batch, --control or as fuse\n"
         "      --downsample N [--sample-seed S]  call on N reads of the sample (\"downsample it to 6000x\", doc/JULIETFLOW.md:23-25):\n"
         "                                      the reads are chosen by docs/SPEC.md section 12 (seed default 0; samples of one seed are\n"
         "                                      nested) and gathered on the device; N at or above the read count changes nothing.\n"
@@ -373,6 +391,28 @@ Options parse(int argc, char **argv)
                 std::exit(1);
             }
         }
+        else if (a == "--call-deletion-alleles") o.call_deletion_alleles = true;
+        else if (a == "--deletion-allele-rate") {
+            const std::string v = need(i);
+            char *end = nullptr;
+            o.deletion_allele_rate = std::strtod(v.c_str(), &end);
+            o.have_deletion_allele_rate = true;
+            if (v.empty() || *end || !(o.deletion_allele_rate >= 0.0 && o.deletion_allele_rate <= 1.0)) {
+                std::cerr << "juliet: --deletion-allele-rate wants a probability in [0, 1], not '" << v << "'\n";
+                std::exit(1);
+            }
+        }
+        else if (a == "--min-deletion-length") {
+            const std::string v = need(i);
+            char *end = nullptr;
+            const unsigned long long k = std::strtoull(v.c_str(), &end, 10);
+            o.have_min_deletion_length = true;
+            if (v.empty() || *end || v[0] == '-' || k == 0 || k > 0xFFFFFFFFull) {
+                std::cerr << "juliet: --min-deletion-length wants a length of 1 base or more, not '" << v << "'\n";
+                std::exit(1);
+            }
+            o.min_deletion_length = (uint32_t)k;
+        }
         else if (a == "--rescue-min-positions") { o.rescue_min = (uint32_t)std::stoul(need(i)); o.have_rescue_min = true; }
         else if (a == "--absorb-distance") { o.absorb_distance = (uint32_t)std::stoul(need(i)); o.have_absorb = true; }
         else if (a == "--flag-recombinants") o.flag_recombinants = true;
@@ -499,6 +539,17 @@ Options parse(int argc, char **argv)
         if (!o.phasing) refuse("adds sites to the haplotypes of a phasing run (add --mode-phasing)");
         if (!o.call_insertions) refuse("phases the insertions that --call-insertions calls (add it)");
         if (o.rescue) refuse("leaves no insertion for --rescue-damaged to judge as damage (drop one of the two)");
+    }
+    if (o.call_deletion_alleles || o.have_deletion_allele_rate || o.have_min_deletion_length) {   // refused here, before any file is read or any GPU work
+        auto refuse = [](const char *why) {
+            std::cerr << "juliet: --call-deletion-alleles [--deletion-allele-rate r] [--min-deletion-length K] " << why << "\n";
+            std::exit(1);
+        };
+        if (!o.call_deletion_alleles) refuse("--deletion-allele-rate and --min-deletion-length set the test of --call-deletion-alleles (add it)");
+        if (as_fuse) refuse("are not options of fuse");
+        if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
+        if (!o.batch.empty()) refuse("is not part of a batch (not with --batch)");
+        if (!o.control.empty()) refuse("tests against the error model, not a control (drop --control)");
     }
     if (!o.control.empty()) {   // refused here, before any file is read or any GPU work
         auto refuse = [](const char *why) { std::cerr << "juliet: --control " << why << "\n"; std::exit(2); };

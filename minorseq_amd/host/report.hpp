@@ -567,6 +567,32 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
         if (R.link_skipped) lb.set("skipped", Json::of(true));
         root.set("linkage", std::move(lb));
     }
+    if (R.del_alleles) {   // --call-deletion-alleles (docs/SPEC.md §25): one entry per called allele, ascending by (begin_abs, length)
+        Json db = Json::object();
+        db.set("rate", Json::of(R.dal_rate)).set("min_length", Json::of(R.dal_min_length))
+            .set("bounded_runs", Json::of((int64_t)R.dal_runs[0])).set("open_runs", Json::of((int64_t)R.dal_runs[1]))
+            .set("n_alleles", Json::of(R.dal_n_alleles)).set("n_alleles_tested", Json::of(R.dal_n_tested));
+        Json alleles = Json::array();
+        for (const Results::DeletionAllele &d : R.dal_rows) {
+            const uint32_t begin_abs = win_begin + d.allele.col + 1, end_abs = begin_abs + d.allele.len;   // 1-based [begin_abs, end_abs)
+            Json gs = Json::array();
+            for (const GeneCfg &g : cfg.genes) {   // the part of the extent inside the gene: amino-acid positions count from the gene's begin
+                const uint32_t lo = std::max(begin_abs, g.begin_eff), hi = std::min(end_abs, g.end_eff);
+                if (lo >= hi) continue;
+                gs.push(Json::object().set("name", Json::of(g.name)).set("first_position", Json::of((lo - g.begin) / 3 + 1))
+                            .set("last_position", Json::of((hi - 1 - g.begin) / 3 + 1))
+                            .set("codon_aligned", Json::of((lo - g.begin) % 3 == 0 && (hi - g.begin) % 3 == 0)));
+            }
+            alleles.push(Json::object().set("begin_abs", Json::of(begin_abs)).set("length", Json::of(d.allele.len))
+                             .set("count", Json::of(d.call.count)).set("coverage", Json::of(d.call.coverage))
+                             .set("frequency", Json::of((double)d.call.count / (double)d.call.coverage))
+                             .set("expected", Json::of(d.call.expected)).set("pValue", Json::of(d.call.p_value))
+                             .set("log_pValue", Json::of(d.call.log_p)).set("in_frame", Json::of(d.allele.len % 3 == 0))
+                             .set("genes", std::move(gs)));
+        }
+        db.set("alleles", std::move(alleles));
+        root.set("deletion_alleles", std::move(db));
+    }
     return root;
 }
 

@@ -120,6 +120,13 @@ struct Results {
     struct Insertion { uint32_t gene, codon_pos; jl_insertion_allele allele; jl_insertion_call call; };
     bool insertions = false;
     std::vector<Insertion> ins_rows;
+    // --call-deletion-alleles (docs/SPEC.md §25): the called alleles, ascending by (col, len), and the totals of the one stage call
+    struct DeletionAllele { jl_deletion_allele allele; jl_deletion_allele_call call; };
+    bool del_alleles = false;
+    double dal_rate = 0.0;
+    uint32_t dal_min_length = 1, dal_n_alleles = 0, dal_n_tested = 0;
+    uint64_t dal_runs[2] = {0, 0};
+    std::vector<DeletionAllele> dal_rows;
     // the haplotype a damaged read was assigned to, or JL_HAP_DAMAGED; a read that is not damaged: its own id
     uint16_t hap_with_rescued(uint64_t i) const
     {
@@ -560,6 +567,37 @@ const char *fetch_insertions(jl_ctx *ctx, const Options &opt, const jl_params &p
             if (jl_insertion_test(it->count, &jcnt[(size_t)pc[p] * 4], &prm, rate, n_tests, &ic) != JL_OK) return "insertion test";
             if (ic.called) R.ins_rows.push_back({pg[p], pk[p], *it, ic});
         }
+    }
+    return nullptr;
+}
+
+// --call-deletion-alleles, after fetch_calls: ONE call of docs/SPEC.md §25 on the window that was called, then the test of every
+// allele of --min-deletion-length bases or more with the run's own parameters and resolved Bonferroni factor.
+const char *fetch_deletion_alleles(jl_ctx *ctx, const Options &opt, const jl_params &prm, const std::vector<jl_gene> &genes, Results &R)
+{
+    R.del_alleles = true;
+    R.dal_rows.clear();
+    R.dal_rate = opt.have_deletion_allele_rate ? opt.deletion_allele_rate : prm.err.deletion;
+    R.dal_min_length = opt.min_deletion_length;
+    if (jl_deletion_alleles_async(ctx) != JL_OK) return "deletion alleles";
+    uint32_t n = 0;
+    if (jl_deletion_alleles_fetch(ctx, R.dal_runs, nullptr, nullptr, 0, &n) != JL_OK) return "deletion alleles fetch";
+    std::vector<jl_deletion_allele> rows(n);
+    if (n && jl_deletion_alleles_fetch(ctx, nullptr, nullptr, rows.data(), n, &n) != JL_OK) return "deletion alleles fetch";
+    double n_tests = prm.n_tests;
+    if (!(n_tests > 0.0)) {   // §5: the codons of all genes
+        n_tests = 0.0;
+        for (const jl_gene &g : genes)
+            if (g.begin != 0 && g.end > g.begin) n_tests += (double)((g.end - g.begin) / 3);
+    }
+    if (!(n_tests > 0.0)) n_tests = 1.0;
+    R.dal_n_alleles = n, R.dal_n_tested = 0;
+    for (const jl_deletion_allele &a : rows) {
+        if (a.len < opt.min_deletion_length) continue;
+        jl_deletion_allele_call dc;
+        if (jl_deletion_allele_test(a.count, a.flank, &prm, R.dal_rate, n_tests, &dc) != JL_OK) return "deletion allele test";
+        R.dal_n_tested++;
+        if (dc.called) R.dal_rows.push_back({a, dc});
     }
     return nullptr;
 }
