@@ -5,8 +5,9 @@
 //   * the planes (JL_GROUP_FOLD_BELOW = 3): a 140 us stream whose epilogue is 1 % of it — the fold pays until three other
 //     launches' pileups want the workgroup slots the epilogue holds;
 //   * the deviation index (JL_GROUP_FOLD_BELOW_INDEX = 1): a 60 us latency-bound list walk that lives on eight waves per SIMD;
-//     the epilogue's registers leave it three, so the fold pays only where nothing else can fill the device: a launch that is
-//     ALONE, whose tail is exposed whole.  (Not 0: a lone launch's tail is one launch and one read-back shorter folded.)
+//     the epilogue's registers leave it five (JL_IX_FOLD_WAVES, kernels_pileup.hip; three before that budget), so the fold pays
+//     only where nothing else can fill the device: a launch that is ALONE, whose tail is exposed whole.  (Not 0: a lone launch's
+//     tail is one launch and one read-back shorter folded.)
 // Measured, not guessed: the sweeps are in profiles/ (DESIGN.md "What bounds a step", "With the deviation index").
 #pragma once
 #include <stdint.h>

@@ -272,7 +272,7 @@ __device__ __forceinline__ void pileup_tail(uint32_t (*s_hist)[64], uint32_t (*s
             const uint32_t col = c0 + (uint32_t)j;
             const uint32_t h = s_hist[j][lane];
             for (uint32_t p = fold->col_head[col]; p != 0xFFFFFFFFu; p = fold->pos_next[p])
-                jl_call_position<false>(c.A, p, col, h, c.pos_refcfg[p], c.pos_gene[p], c.pos_codon[p], c.drm, c.called, c.staged);
+                jl_call_position_at<false>(c.A, p, col, h, c.pos_refcfg[p], c.pos_gene, c.pos_codon, c.drm, c.called, c.staged);
         }
     }
 }
@@ -367,8 +367,9 @@ __global__ __launch_bounds__(256) void pileup_fold_group_kernel(jl_pileup_fold_g
 //   * a lane streams four entries per round with one 16-byte non-temporal load, DEPTH rounds held in registers: the loads of the
 //     first DEPTH rounds all go out before the first is consumed, and each register is loaded with round r + DEPTH as round r
 //     leaves it.  DEPTH = 1 in the unfolded kernels, which hide the chain of round trips behind eight workgroups per CU and must
-//     keep the registers for that; DEPTH = JL_IX_FOLD_DEPTH = 8 in the folded ones, whose Fisher epilogue leaves three workgroups
-//     per CU whatever the walk needs: 32 KB per workgroup in flight, a benchmark chunk's whole list (25 KB) in one round trip;
+//     keep the registers for that; DEPTH = JL_IX_FOLD_DEPTH = 8 in the folded ones, whose Fisher epilogue leaves five workgroups
+//     per CU (JL_IX_FOLD_WAVES) whatever the walk needs: 32 KB per workgroup in flight, a benchmark chunk's whole list (25 KB) in
+//     one round trip;
 //   * column counts: per lane one 64-bit accumulator per column with a 9-bit field per code 0..6 — at most JL_IX_FLUSH_ROUNDS
 //     rounds x 4 entries = 508 <= 511 per field between flushes (whole batches of DEPTH rounds: 127 rounds at depth 1, 120 at
 //     depth 8); a flush unpacks them two to a register (64 lanes x 508 < 2^16), sums over the wave by DPP and adds to LDS, as the
@@ -379,13 +380,20 @@ __global__ __launch_bounds__(256) void pileup_fold_group_kernel(jl_pileup_fold_g
 //     codon's count (s_match), from where pileup_tail takes over unchanged.  Padding reads are never in a list.
 // A plain chunk over the density bound has no list (tab[].z all ones): its workgroup counts it from the planes with a simple
 // walk — few registers, no prefetch: the path is rare and must not cost the common one its occupancy.
-// Registers (gfx950, the compiler's kernel-resource-usage remarks; no scratch in any of the four): pileup_index_kernel and
-// pileup_index_group_kernel 58 VGPRs, eight waves per SIMD, as before the depth; pileup_index_fold_kernel and
-// pileup_index_fold_group_kernel 132 VGPRs, three waves per SIMD, at depth 8 as at depth 1 — the epilogue's live range sets the
-// figure, the walk's 32 registers of entries fit under it (a kernel stays at three waves up to 168).  The plane path's 154 are why
-// index and plane counting are separate kernels.
+// Registers (gfx950, the compiler's kernel-resource-usage remarks): pileup_index_kernel and pileup_index_group_kernel 58 VGPRs,
+// eight waves per SIMD, no scratch; pileup_index_fold_kernel and pileup_index_fold_group_kernel 96 VGPRs, five waves per SIMD, 128
+// bytes of scratch a lane, at depth 8 as at depth 2 (without a bound: 132, three waves — the epilogue sets the figure, the walk
+// stays under 60).  tests/test_fold_budget_resources.py pins these.  The plane path's 154 are why index and plane counting are
+// separate kernels.
 #ifndef JL_IX_FOLD_DEPTH
 #define JL_IX_FOLD_DEPTH 8
+#endif
+// The folded index kernels' register budget, as waves per SIMD (__launch_bounds__): 5 = 96 VGPRs, five workgroups per CU.  What does
+// not fit is the Fisher stage's (its FP64 constants, which the compiler hoists out of the loop over a column's positions): the
+// spill's stores and loads all lie behind the barrier that closes the walk, in the one wave that evaluates.  The sweep of 3 / 4 / 5
+// waves against depth 8 / 4 / 2 is in profiles/fold_budget/: depth 8 is ahead at every budget, so the depth does not follow the budget.
+#ifndef JL_IX_FOLD_WAVES
+#define JL_IX_FOLD_WAVES 5
 #endif
 template <int DEPTH>
 __device__ __forceinline__ void index_stream(const uint32_t JL_AS1 *list, uint32_t E, uint32_t (*s_hist)[64], uint32_t (*s_col)[6])
@@ -546,14 +554,14 @@ __device__ __forceinline__ void pileup_index_body(const uint8_t JL_AS1 *planes, 
                             (uint32_t JL_AS1 *)(w).hist, f)
 
 __global__ __launch_bounds__(256) void pileup_index_kernel(jl_win_index w) { JL_INDEX_BODY(false, w, nullptr); }
-__global__ __launch_bounds__(256) void pileup_index_fold_kernel(jl_win_index w, jl_win_fold f) { JL_INDEX_BODY(true, w, &f); }
+__global__ __launch_bounds__(256, JL_IX_FOLD_WAVES) void pileup_index_fold_kernel(jl_win_index w, jl_win_fold f) { JL_INDEX_BODY(true, w, &f); }
 __global__ __launch_bounds__(256) void pileup_index_group_kernel(jl_index_group_args args)
 {
     const jl_win_index &w = args.w[blockIdx.z];
     if (blockIdx.x >= w.n_plain) return;
     JL_INDEX_BODY(false, w, nullptr);
 }
-__global__ __launch_bounds__(256) void pileup_index_fold_group_kernel(jl_index_fold_group_args args)
+__global__ __launch_bounds__(256, JL_IX_FOLD_WAVES) void pileup_index_fold_group_kernel(jl_index_fold_group_args args)
 {
     const jl_win_index &w = args.w[blockIdx.z];
     if (blockIdx.x >= w.n_plain) return;
