@@ -6,6 +6,8 @@
 
 #include "jl_internal.h"
 
+#include "hap_stage.h"
+
 extern "C" {
 
 int jl_class_codons_async(jl_ctx *ctx, const uint16_t *label, uint32_t n_classes, const uint32_t *col, uint32_t n_pos)
@@ -20,11 +22,7 @@ int jl_class_codons_async(jl_ctx *ctx, const uint16_t *label, uint32_t n_classes
     if (n_pos == 0) return jl_fail(ctx, JL_ERR_ARG, "%s: no positions", fn);
     if ((uint64_t)n_classes * n_pos > (uint64_t)JL_CLASS_CODONS_CELLS)
         return jl_fail(ctx, JL_ERR_ARG, "%s: %u classes x %u positions, at most %u cells", fn, n_classes, n_pos, (unsigned)JL_CLASS_CODONS_CELLS);
-    for (uint32_t p = 0; p < n_pos; ++p) {
-        if ((uint64_t)col[p] + 2u >= ctx->n_cols)
-            return jl_fail(ctx, JL_ERR_ARG, "%s: position %u: the codon at column %u ends beyond the window's %u columns", fn, p, col[p], ctx->n_cols);
-        if (p && col[p] <= col[p - 1]) return jl_fail(ctx, JL_ERR_ARG, "%s: position %u: columns not strictly ascending", fn, p);
-    }
+    if (int rc = jl_check_codon_columns(ctx, fn, col, n_pos)) return rc;
     JL_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const uint64_t n = ctx->n_reads;

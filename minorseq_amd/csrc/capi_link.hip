@@ -9,6 +9,8 @@
 #include "jl_fisher_general.h"
 #include "jl_internal.h"
 
+#include "hap_stage.h"
+
 namespace {
 
 // X ~ Hypergeometric(n, K marked, r drawn), max(0, r + K - n) < min(r, K): *ge = P(X >= x), *le = P(X <= x), each as the upper
@@ -36,11 +38,7 @@ int jl_variant_linkage_async(jl_ctx *ctx, const uint32_t *pos_cols, uint32_t n_p
     if (!var_codon) return jl_fail(ctx, JL_ERR_ARG, "%s: no variant codons array", fn);
     if (n_pos == 0 || n_pos > (uint32_t)JL_LINK_MAX) return jl_fail(ctx, JL_ERR_ARG, "%s: %u positions, 1 to %d", fn, n_pos, (int)JL_LINK_MAX);
     if (n_var == 0 || n_var > (uint32_t)JL_LINK_MAX) return jl_fail(ctx, JL_ERR_ARG, "%s: %u variants, 1 to %d", fn, n_var, (int)JL_LINK_MAX);
-    for (uint32_t p = 0; p < n_pos; ++p) {
-        if ((uint64_t)pos_cols[p] + 2u >= ctx->n_cols)
-            return jl_fail(ctx, JL_ERR_ARG, "%s: position %u: the codon at column %u ends beyond the window's %u columns", fn, p, pos_cols[p], ctx->n_cols);
-        if (p && pos_cols[p] <= pos_cols[p - 1]) return jl_fail(ctx, JL_ERR_ARG, "%s: position %u: columns not strictly ascending", fn, p);
-    }
+    if (int rc = jl_check_codon_columns(ctx, fn, pos_cols, n_pos)) return rc;
     for (uint32_t v = 0; v < n_var; ++v) {
         if (var_pos[v] >= n_pos) return jl_fail(ctx, JL_ERR_ARG, "%s: variant %u: position index %u beyond the %u positions", fn, v, var_pos[v], n_pos);
         if (v && var_pos[v] < var_pos[v - 1]) return jl_fail(ctx, JL_ERR_ARG, "%s: variant %u: position indices decreasing", fn, v);

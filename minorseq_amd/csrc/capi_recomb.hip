@@ -4,9 +4,9 @@
 // else of the context: no stage result, no plan, no captured graph, no rescue and no nearest result sees it.  Every size the
 // kernel (kernels_recomb.hip) forms an address from is checked here, and the pattern is packed into the form it streams, once in
 // the order of the positions and once reversed.
-#include <string.h>
-
 #include "jl_internal.h"
+
+#include "hap_stage.h"
 
 namespace {
 constexpr size_t kTallyWords = 12;                                  // tally [5], 64 bits each, and a pad to 16 bytes
@@ -20,42 +20,18 @@ int jl_phase_recombinants_async(jl_ctx *ctx, const uint32_t *pos_cols, uint32_t 
 {
     static const char *fn = "jl_phase_recombinants_async";
     if (!ctx) return JL_ERR_ARG;
-    if (!ctx->d_msa) return jl_fail(ctx, JL_ERR_STATE, "%s: no resident matrix", fn);
-    if (!pos_cols) return jl_fail(ctx, JL_ERR_ARG, "%s: no positions array", fn);
-    if (!pattern) return jl_fail(ctx, JL_ERR_ARG, "%s: no pattern array", fn);
-    if (n_pos == 0 || n_pos > JL_RESCUE_POS_MAX) return jl_fail(ctx, JL_ERR_ARG, "%s: %u positions, 1 to %u", fn, n_pos, JL_RESCUE_POS_MAX);
-    if (n_hap == 0 || n_hap > (uint32_t)JL_MAX_HAPLOTYPES)
-        return jl_fail(ctx, JL_ERR_ARG, "%s: %u haplotypes, 1 to %d", fn, n_hap, (int)JL_MAX_HAPLOTYPES);
-    if (pattern_stride < n_pos) return jl_fail(ctx, JL_ERR_ARG, "%s: pattern_stride %u below the %u positions of a row", fn, pattern_stride, n_pos);
-    if (min_positions == 0 || min_positions > n_pos)
-        return jl_fail(ctx, JL_ERR_ARG, "%s: min_positions %u, 1 to the %u positions", fn, min_positions, n_pos);
-    for (uint32_t p = 0; p < n_pos; ++p) {
-        if ((uint64_t)pos_cols[p] + 2u >= ctx->n_cols)
-            return jl_fail(ctx, JL_ERR_ARG, "%s: position %u: the codon at column %u ends beyond the window's %u columns", fn, p, pos_cols[p], ctx->n_cols);
-        if (p && pos_cols[p] <= pos_cols[p - 1]) return jl_fail(ctx, JL_ERR_ARG, "%s: position %u: columns not strictly ascending", fn, p);
-    }
-    for (uint32_t h = 0; h < n_hap; ++h)
-        for (uint32_t p = 0; p < n_pos; ++p)
-            if (pattern[(size_t)h * pattern_stride + p] > 63u)
-                return jl_fail(ctx, JL_ERR_ARG, "%s: pattern byte %u of haplotype %u at position %u is no codon (0..63)", fn,
-                               (unsigned)pattern[(size_t)h * pattern_stride + p], h, p);
+    if (int rc = jl_check_hap_table(ctx, fn, pos_cols, n_pos, pattern, pattern_stride, n_hap, min_positions)) return rc;
+    if (int rc = jl_check_hap_contents(ctx, fn, pos_cols, n_pos, pattern, pattern_stride, n_hap)) return rc;
     JL_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const uint64_t n = ctx->n_reads;
-    const uint32_t hap_pad = (n_hap + 63u) / 64u * 64u, groups = (n_pos + 3u) / 4u;
-    const size_t dir_words = (size_t)n_pos + (size_t)groups * hap_pad, in_words = 2u * dir_words;
+    const jl_pat4_shape shape = jl_pat4_shape_for(n_pos, n_hap);
+    const size_t dir_words = shape.dir_words, in_words = 2u * dir_words;
     // positions and packed pattern, ascending and then descending, into pinned staging (an upload of the last call may still read
     // it: wait for that)
     uint32_t *h_in = nullptr;
     JL_HIP(ctx, ctx->recomb_in.host(in_words, &h_in));
-    memset(h_in, 0, in_words * sizeof(uint32_t));
-    for (uint32_t dir = 0; dir < 2u; ++dir) {
-        uint32_t *cols = h_in + dir * dir_words, *pat4 = cols + n_pos;
-        for (uint32_t p = 0; p < n_pos; ++p) cols[p] = pos_cols[dir ? n_pos - 1u - p : p];
-        for (uint32_t h = 0; h < n_hap; ++h)
-            for (uint32_t p = 0; p < n_pos; ++p)
-                pat4[(size_t)(p / 4u) * hap_pad + h] |= (uint32_t)pattern[(size_t)h * pattern_stride + (dir ? n_pos - 1u - p : p)] << (8u * (p % 4u));
-    }
+    for (uint32_t dir = 0; dir < 2u; ++dir) jl_stage_hap_direction(h_in + dir * dir_words, shape, pos_cols, n_pos, pattern, pattern_stride, n_hap, dir != 0u);
     const size_t id_words = (size_t)((n + 1u) / 2u);
     const size_t out_words = kHeadWords + 4u * id_words;
     ctx->recomb_n = 0;   // (what was fetchable is gone as soon as a buffer may move)
@@ -66,7 +42,7 @@ int jl_phase_recombinants_async(jl_ctx *ctx, const uint32_t *pos_cols, uint32_t 
         jl_recomb_args A = {};
         A.msa = ctx->d_msa, A.plane_stride = ctx->plane_stride;
         A.n_reads = n, A.n_runs = (uint32_t)((n + 63u) / 64u);   // (8 n_runs <= plane_stride: a multiple of 16 and >= ceil(n / 8))
-        A.n_pos = n_pos, A.n_hap = n_hap, A.min_positions = min_positions, A.hap_pad = hap_pad;
+        A.n_pos = n_pos, A.n_hap = n_hap, A.min_positions = min_positions, A.hap_pad = shape.hap_pad;
         for (uint32_t dir = 0; dir < 2u; ++dir) {
             A.pos_cols[dir] = ctx->recomb_in.dev + dir * dir_words;
             A.pat4[dir] = A.pos_cols[dir] + n_pos;
@@ -111,10 +87,7 @@ int jl_haplotype_recombinants(const uint8_t *pattern, uint32_t pattern_stride, u
     static const char *fn = "jl_haplotype_recombinants";
     if (!pattern || !hap_count || !out) return jl_fail(nullptr, JL_ERR_ARG, "%s: a NULL array", fn);
     if (!(min_parent_ratio >= 1.0)) return jl_fail(nullptr, JL_ERR_ARG, "%s: min_parent_ratio %g, 1 at least", fn, min_parent_ratio);
-    if (n_pos == 0 || n_pos > JL_RESCUE_POS_MAX) return jl_fail(nullptr, JL_ERR_ARG, "%s: %u positions, 1 to %u", fn, n_pos, JL_RESCUE_POS_MAX);
-    if (n_hap == 0 || n_hap > (uint32_t)JL_MAX_HAPLOTYPES)
-        return jl_fail(nullptr, JL_ERR_ARG, "%s: %u haplotypes, 1 to %d", fn, n_hap, (int)JL_MAX_HAPLOTYPES);
-    if (pattern_stride < n_pos) return jl_fail(nullptr, JL_ERR_ARG, "%s: pattern_stride %u below the %u positions of a row", fn, pattern_stride, n_pos);
+    if (int rc = jl_check_hap_shape(nullptr, fn, n_pos, pattern_stride, n_hap)) return rc;
     for (uint32_t h = 0; h < n_hap; ++h) {
         const uint8_t *row = pattern + (size_t)h * pattern_stride;
         const double need = min_parent_ratio * (double)hap_count[h];

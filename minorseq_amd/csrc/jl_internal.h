@@ -380,7 +380,7 @@ struct jl_rescue_args {
     uint32_t n_pos, n_hap, min_positions;
     uint32_t hap_pad, pad_;    // n_hap in whole chunks of 64
     const uint32_t *pos_cols;  // [n_pos], each + 2 < n_cols
-    const uint32_t *pat4;      // [ceil(n_pos / 4)][hap_pad]: byte q of dword [g][h] = pattern[h][4 g + q] (0 where either does not exist)
+    const uint32_t *pat4;      // [ceil(n_pos / 4)][hap_pad]: the packed pattern (jl_pack_pat4, hap_stage.h)
     uint16_t *rescue;          // [n_reads]
     uint32_t *hap_reads;       // [n_hap], zeroed
     unsigned long long *tally; // [4] assigned, ambiguous, none, uninformative; zeroed
@@ -388,7 +388,7 @@ struct jl_rescue_args {
 void jl_launch_phase_rescue(const jl_rescue_args *a, hipStream_t st);
 
 // ---- which reported haplotype a read is nearest to, within a mismatch budget (kernels_nearest.hip, capi_nearest.hip; docs/SPEC.md §22)
-// positions, haplotypes and the packed pattern are the rescue's (JL_RESCUE_POS_MAX, JL_RESCUE_HAP_PAD, pat4)
+// positions and haplotypes are bounded as the rescue's (JL_RESCUE_POS_MAX, JL_RESCUE_HAP_PAD); the walk is shared: hap_walk.h
 #define JL_NEAREST_HIST_WORDS (JL_RESCUE_HAP_PAD * (JL_NEAREST_MAX_DISTANCE + 1u))   // hap_reads at its largest: [704][8]
 struct jl_nearest_args {
     const uint8_t *msa;        // the window's bit planes
@@ -399,7 +399,7 @@ struct jl_nearest_args {
     uint32_t hap_pad;          // n_hap in whole chunks of 64
     uint32_t max_distance;     // D <= JL_NEAREST_MAX_DISTANCE
     const uint32_t *pos_cols;  // [n_pos], each + 2 < n_cols
-    const uint32_t *pat4;      // [ceil(n_pos / 4)][hap_pad], as jl_rescue_args
+    const uint32_t *pat4;      // [ceil(n_pos / 4)][hap_pad]: the packed pattern (jl_pack_pat4, hap_stage.h)
     uint16_t *nearest;         // [n_reads]
     uint8_t *dist;             // [n_reads]
     uint32_t *hap_reads;       // [n_hap][D + 1], zeroed
@@ -408,7 +408,7 @@ struct jl_nearest_args {
 void jl_launch_phase_nearest(const jl_nearest_args *a, hipStream_t st);
 
 // ---- which reads are recombinants of two reported haplotypes (kernels_recomb.hip, capi_recomb.hip; docs/SPEC.md §23)
-// positions, haplotypes and the packed pattern are the rescue's (JL_RESCUE_POS_MAX, JL_RESCUE_HAP_PAD, pat4); the second
+// positions and haplotypes are bounded as the rescue's (JL_RESCUE_POS_MAX, JL_RESCUE_HAP_PAD); the walk is shared: hap_walk.h.  The second
 // direction walks the positions from the last to the first, and gets its own copy of both in that order
 #define JL_RECOMB_HIST_WORDS (JL_RESCUE_HAP_PAD * 2u)   // parent_reads at its largest: [704][2]
 struct jl_recomb_args {
@@ -419,7 +419,7 @@ struct jl_recomb_args {
     uint32_t n_pos, n_hap, min_positions;
     uint32_t hap_pad, pad_;    // n_hap in whole chunks of 64
     const uint32_t *pos_cols[2];  // [n_pos], each + 2 < n_cols: [0] ascending, [1] the same descending
-    const uint32_t *pat4[2];      // [ceil(n_pos / 4)][hap_pad], as jl_rescue_args: [0] of pattern, [1] of pattern with every row reversed
+    const uint32_t *pat4[2];      // [ceil(n_pos / 4)][hap_pad] (jl_pack_pat4, hap_stage.h): [0] of pattern, [1] of pattern with every row reversed
     uint16_t *left, *right;    // [n_reads] each
     uint16_t *prefix, *suffix; // [n_reads] each
     uint32_t *parent_reads;    // [n_hap][2], zeroed
@@ -807,13 +807,13 @@ struct jl_ctx {
     uint32_t cc_k = 0, cc_pos = 0;      // shape of the last call enqueued (cc_k = 0: none)
 
     // ---- jl_phase_rescue_async: buffers of its own, grown on demand (capi_rescue.hip); no stage and no run touches them
-    jl_upload_staging<uint32_t> rescue_in;   // pos_cols [n_pos], then pat4 (jl_rescue_args)
+    jl_upload_staging<uint32_t> rescue_in;   // pos_cols [n_pos], then pat4 (jl_stage_hap_direction, hap_stage.h)
     jl_dev_array<uint32_t> rescue_out;   // tally [4] as 8 words, hap_reads [JL_RESCUE_HAP_PAD], then rescue [rescue_n] 16 bits each
     uint64_t rescue_n = 0;               // reads of the last rescue enqueued (0: none)
     uint32_t rescue_h = 0;               // ... and its haplotypes
 
     // ---- jl_phase_nearest_async: buffers of its own, grown on demand (capi_nearest.hip); no stage, no run and no rescue touches them
-    jl_upload_staging<uint32_t> nearest_in;   // pos_cols [n_pos], then pat4 (jl_nearest_args)
+    jl_upload_staging<uint32_t> nearest_in;   // pos_cols [n_pos], then pat4 (jl_stage_hap_direction, hap_stage.h)
     jl_dev_array<uint32_t> nearest_out;  // tally [4] as 8 words, hap_reads [JL_NEAREST_HIST_WORDS], nearest [nearest_n] 16 bits each, dist [nearest_n] bytes
     uint64_t nearest_n = 0;              // reads of the last call enqueued (0: none)
     uint32_t nearest_h = 0, nearest_d = 0;   // ... its haplotypes and its budget D
