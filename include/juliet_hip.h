@@ -609,6 +609,42 @@ typedef struct {
 int jl_read_filter(const uint32_t *stats, uint64_t n_reads, const jl_read_rule *rule, uint32_t *idx, uint64_t *n_kept,
                    uint64_t failed[5]);
 /*
+ * PER-READ APOBEC hypermutation counters and their exact test (docs/SPEC.md §26).  APOBEC3G/F turns G into A where the two bases
+ * downstream are R and D; a read edited that way passes any mismatch bound a clean minority haplotype must also pass, and is found
+ * as Hypermut 2.0 finds it: G->A in the target context GRD against G->A in the control contexts GYN / GRC, one-sided Fisher test.
+ * For read i and column c with c + 2 < n_cols, x, y, z its cells at c, c + 1, c + 2 (alignment columns; codes as above): the
+ * column is a SITE of the read when ref[c] == 2 (G), x is A or G, y < 4 and z < 4.  The context is the READ's own y and z:
+ *   target   y in {A, G} and z != C          control   every other site (y in {C, T}; or y in {A, G} and z == C)
+ * A gap, N or uncovered cell in y or z: no site; the last two columns of the window are never sites.  Summed over the window:
+ *   JL_HM_TARGET_SITES    target-context sites          JL_HM_TARGET_MUT     of those, x == A
+ *   JL_HM_CONTROL_SITES   control-context sites         JL_HM_CONTROL_MUT    of those, x == A
+ * counts[JL_HM_COUNTERS][n_reads], struct of arrays as jl_read_stats_async's, 32 bits, exact, independent of launch shape and
+ * order; reads past n_reads count nowhere.  A ref[c] of 4 or above (and any other than 2) makes column c no site.
+ * p[i] = P(X >= a) of the table [[a, n - a], [c, m - c]] with a = target mutations, n = target sites, c = control mutations, m =
+ * control sites (the routine of jl_control_test), log_p[i] = ln p; n == 0 or m == 0: p = 1, log_p = 0.  No multiple-test
+ * correction.
+ * The contract is jl_read_stats_async's: ref[n_cols] is copied before the call returns; both kernels are enqueued on the
+ * context's stream into buffers of its own and nothing else of the context is touched; every kind of resident matrix is accepted.
+ * JL_ERR_ARG: ref == NULL.  JL_ERR_STATE: no resident matrix.  A refused call changes nothing.
+ */
+enum { JL_HM_TARGET_SITES = 0, JL_HM_TARGET_MUT = 1, JL_HM_CONTROL_SITES = 2, JL_HM_CONTROL_MUT = 3, JL_HM_COUNTERS = 4 };
+int jl_read_hypermut_async(jl_ctx *ctx, const uint8_t *ref /* [n_cols] */);
+/* Wait and copy out what the last jl_read_hypermut_async computed; any pointer may be NULL (all NULL: only wait).
+ * JL_ERR_STATE: none was enqueued. */
+int jl_read_hypermut_fetch(jl_ctx *ctx, uint32_t *counts /* [JL_HM_COUNTERS][n_reads] */, double *p /* [n_reads] */,
+                           double *log_p /* [n_reads] */);
+/* The test kernel alone over `n` tables the caller supplies (host arrays in and out), as jl_control_eval is for the control call.
+ * JL_ERR_ARG: a NULL array, or a mutation count above its site count. */
+int jl_hypermut_eval(jl_ctx *ctx, const uint32_t *counts /* [JL_HM_COUNTERS][n] */, uint64_t n, double *p, double *log_p);
+/* Host only (no device, no context): the same expressions for one read.  JL_ERR_ARG: a NULL pointer, a mutation count above its
+ * site count. */
+int jl_hypermut_test(uint32_t target_mut, uint32_t target_sites, uint32_t control_mut, uint32_t control_sites, double *p,
+                     double *log_p);
+/* Host only.  A read is hypermutated when p < alpha (strict) and is dropped; idx[0 .. *n_kept): the kept reads, ascending — what
+ * jl_msa_take takes; room for n_reads.  *n_flagged = n_reads - *n_kept.  JL_ERR_ARG (jl_last_error(NULL) says which): a NULL
+ * argument; alpha outside (0, 1]; n_reads above 2^32 - 1. */
+int jl_hypermut_filter(const double *p, uint64_t n_reads, double alpha, uint32_t *idx, uint64_t *n_kept, uint64_t *n_flagged);
+/*
  * The SITE MATRIX (docs/SPEC.md §18): called codon deletions as sites of a haplotype.  Phasing groups reads by their codons at the
  * variant positions, and a deleted codon is no codon: its carriers are GAP-damaged where the position is a variant position and
  * invisible where it is not.  This call builds, as jl_xwin_assemble_local does, a compact matrix of chosen codon starts of `src`

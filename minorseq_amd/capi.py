@@ -43,7 +43,7 @@ SITE_INS_NONE, SITE_INS_OTHER, SITE_INS_MAX_ALLELES = 0, 63, 62
 EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", "jl_ctx_destroy", "jl_last_error",
            "jl_sync", "jl_col_stride", "jl_plane_stride", "jl_msa_upload", "jl_msa_alloc", "jl_msa_adopt", "jl_msa_pack_rows",
            "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_take", "jl_msa_take_async", "jl_sample_reads", "jl_mix_counts", "jl_msa_download", "jl_msa_download_planes", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
-           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_class_codons_async", "jl_class_codons_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_phase_nearest_async", "jl_phase_nearest_fetch", "jl_phase_recombinants_async", "jl_phase_recombinants_fetch", "jl_haplotype_recombinants", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_deletion_alleles_async", "jl_deletion_alleles_fetch", "jl_deletion_allele_test", "jl_read_stats_async", "jl_read_stats_fetch", "jl_read_filter", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_msa_track_insertion_reads", "jl_insertion_reads_fetch", "jl_sites_assemble_alleles", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_control_call_async", "jl_control_call_fetch", "jl_control_test", "jl_phase_async", "jl_phase_fetch",
+           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_class_codons_async", "jl_class_codons_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_phase_nearest_async", "jl_phase_nearest_fetch", "jl_phase_recombinants_async", "jl_phase_recombinants_fetch", "jl_haplotype_recombinants", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_deletion_alleles_async", "jl_deletion_alleles_fetch", "jl_deletion_allele_test", "jl_read_stats_async", "jl_read_stats_fetch", "jl_read_filter", "jl_read_hypermut_async", "jl_read_hypermut_fetch", "jl_hypermut_eval", "jl_hypermut_test", "jl_hypermut_filter", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_msa_track_insertion_reads", "jl_insertion_reads_fetch", "jl_sites_assemble_alleles", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_control_call_async", "jl_control_call_fetch", "jl_control_test", "jl_phase_async", "jl_phase_fetch",
            "jl_ctx_stream", "jl_run_async", "jl_run_wait", "jl_run_done", "jl_run_view_get", "jl_group_create", "jl_group_destroy",
            "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_msa_index_info", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_control_eval", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
            "jl_allgather_variants", "jl_allgather_variants_async", "jl_allgather_variants_async_many", "jl_allgather_variants_many", "jl_group_exchange_bind", "jl_group_exchange_collect", "jl_xwin_plan", "jl_xwin_assemble_local",
@@ -55,6 +55,7 @@ EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", 
 
 READ_BASES, READ_GAPS, READ_MASKED, READ_COMPARED, READ_MISMATCHES, READ_STATS = range(6)   # jl_read_stats_async (docs/SPEC.md §20)
 READ_RULES = ("min_bases", "mismatches", "mismatch_perc", "gap_perc", "n_perc")   # the order of jl_read_filter's failed[5]
+HM_TARGET_SITES, HM_TARGET_MUT, HM_CONTROL_SITES, HM_CONTROL_MUT, HM_COUNTERS = range(5)   # jl_read_hypermut_async (docs/SPEC.md §26)
 
 
 class ReadRule(C.Structure):   # jl_read_rule
@@ -258,6 +259,11 @@ def load_library(path=LIB_PATH):
     lib.jl_read_stats_async.argtypes = [vp, vp]
     lib.jl_read_stats_fetch.argtypes = [vp, vp]
     lib.jl_read_filter.argtypes = [vp, u64, C.POINTER(ReadRule), vp, C.POINTER(u64), vp]
+    lib.jl_read_hypermut_async.argtypes = [vp, vp]
+    lib.jl_read_hypermut_fetch.argtypes = [vp, vp, vp, vp]
+    lib.jl_hypermut_eval.argtypes = [vp, vp, u64, vp, vp]
+    lib.jl_hypermut_test.argtypes = [u32, u32, u32, u32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    lib.jl_hypermut_filter.argtypes = [vp, u64, C.c_double, vp, C.POINTER(u64), C.POINTER(u64)]
     lib.jl_sites_assemble.argtypes = [vp, vp, vp, u32]
     lib.jl_msa_track_insertion_alleles.argtypes = [vp, C.c_int]
     lib.jl_insertion_alleles_fetch.argtypes = [vp, vp, vp, u32, vp]
@@ -798,6 +804,34 @@ class Juliet:
         self._chk(self.lib.jl_read_stats_fetch(self.h, _p(stats) if stats.size else None))
         return stats
 
+    def read_hypermut(self, ref, wait=True):
+        """jl_read_hypermut_async (docs/SPEC.md §26): per read of the resident matrix its G->A sites in APOBEC's target context GRD
+        and in the control contexts, the mutated ones of each, and the one-sided exact test of the two.  ref[n_cols]: a code per
+        column, only G (2) makes a site.  Returns (counts[4, n_reads] uint32 (HM_TARGET_SITES .. HM_CONTROL_MUT), p[n_reads],
+        log_p[n_reads]); wait=False only enqueues on this context's stream and returns None (read_hypermut_fetch brings them)."""
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        assert ref.shape == (self.n_cols,)
+        self._chk(self.lib.jl_read_hypermut_async(self.h, _p(ref)))
+        self._hm_reads = self.n_reads
+        return self.read_hypermut_fetch() if wait else None
+
+    def read_hypermut_fetch(self):
+        n = getattr(self, "_hm_reads", 0)
+        counts = np.zeros((HM_COUNTERS, n), dtype=np.uint32)
+        p, lp = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
+        self._chk(self.lib.jl_read_hypermut_fetch(self.h, *((_p(counts), _p(p), _p(lp)) if n else (None, None, None))))
+        return counts, p, lp
+
+    def hypermut_eval(self, counts):
+        """jl_hypermut_eval: the test kernel of jl_read_hypermut_async over counts[4, n] of the caller; (p, log_p)."""
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        assert counts.ndim == 2 and counts.shape[0] == HM_COUNTERS
+        n = counts.shape[1]
+        p, lp = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
+        if n:
+            self._chk(self.lib.jl_hypermut_eval(self.h, _p(counts), n, _p(p), _p(lp)))
+        return p, lp
+
     def sites_assemble(self, src, sites):
         """jl_sites_assemble (docs/SPEC.md §18): this context becomes the site matrix of `src` — its reads x 3 len(sites) columns,
         site k = (col, kind, fill) at columns 3k..3k+2: the three columns at `col` of `src`, the del3 reads of a SITE_DELETION site
@@ -1307,6 +1341,30 @@ def read_filter(stats, **rule):
     if rc:
         raise JulietError(rc, "jl_read_filter: " + lib.jl_last_error(None).decode())
     return idx[: kept.value].copy(), failed
+
+
+def hypermut_test(target_mut, target_sites, control_mut, control_sites):
+    """jl_hypermut_test (host only, docs/SPEC.md §26): (p, log_p) of one read's table, P(X >= target_mut) one-sided."""
+    lib = load_library()
+    p, lp = C.c_double(), C.c_double()
+    rc = lib.jl_hypermut_test(int(target_mut), int(target_sites), int(control_mut), int(control_sites), C.byref(p), C.byref(lp))
+    if rc:
+        raise JulietError(rc, "jl_hypermut_test: " + lib.jl_last_error(None).decode())
+    return p.value, lp.value
+
+
+def hypermut_filter(p, alpha=0.05):
+    """jl_hypermut_filter (host only, docs/SPEC.md §26): (idx, n_flagged) — the reads with p >= alpha, ascending uint32 indices, what
+    Juliet.take takes, and how many reads were flagged as hypermutated (p < alpha)."""
+    lib = load_library()
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    assert p.ndim == 1
+    idx = np.zeros(max(1, len(p)), dtype=np.uint32)
+    kept, flagged = C.c_uint64(), C.c_uint64()
+    rc = lib.jl_hypermut_filter(_p(p), len(p), float(alpha), _p(idx), C.byref(kept), C.byref(flagged))
+    if rc:
+        raise JulietError(rc, "jl_hypermut_filter: " + lib.jl_last_error(None).decode())
+    return idx[: kept.value].copy(), flagged.value
 
 
 class InsertionCall(C.Structure):

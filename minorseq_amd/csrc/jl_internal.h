@@ -517,6 +517,23 @@ struct jl_readstats_args {
 void jl_launch_read_stats(const jl_readstats_args *a, const jl_readstats_shape *shape, hipStream_t st);
 size_t jl_readstats_part_words(const jl_readstats_shape *shape);
 
+// ---- per-read hypermutation counters and their exact test (kernels_hypermut.hip, capi_hypermut.hip; docs/SPEC.md §26)
+struct jl_hypermut_args {
+    const uint8_t *msa;        // the window's bit planes
+    uint64_t plane_stride;     // ... and their stride (an adopted matrix brings its own)
+    uint64_t n_reads;
+    uint32_t n_cols;
+    uint32_t n_words;          // words of a row that hold reads: ceil(n_reads / 32); 4 n_words <= plane_stride
+    uint32_t n_chunks, seg_cols;   // of the launch shape (set by the launcher)
+    const uint8_t *ref;        // [n_cols]
+    uint32_t *part;            // the segments' byte counters (jl_hypermut_part_words), or null when the shape combines by atomics
+    uint32_t *counts;          // [JL_HM_COUNTERS][n_reads]
+};
+void jl_launch_hypermut_counts(const jl_hypermut_args *a, const jl_readstats_shape *shape, hipStream_t st);
+size_t jl_hypermut_part_words(const jl_readstats_shape *shape);
+// one thread a read: p[i], lp[i] of the table counts[.][i] (n > 0; ceil(n / 256) workgroups fit a launch)
+void jl_launch_hypermut_test(const uint32_t *counts, uint64_t n, double *p, double *lp, hipStream_t st);
+
 // ---- the site matrix: chosen codon starts of a matrix, deletion sites recoded (kernels_sites.hip, capi_sites.hip; docs/SPEC.md §18)
 struct jl_sites_args {
     const uint8_t *src;        // the source's bit planes
@@ -859,6 +876,13 @@ struct jl_ctx {
     jl_dev_array<uint32_t> rs_part;        // the column segments' byte counters, when a second kernel combines them
     jl_dev_array<uint32_t> rs_out;         // stats [JL_READ_STATS][rs_reads]
     uint64_t rs_reads = 0;                 // reads of the last call enqueued (0: none)
+
+    // ---- jl_read_hypermut_async: buffers of its own, grown on demand (capi_hypermut.hip); no stage and no run touches them
+    jl_upload_staging<uint8_t> hm_ref;     // the reference row on its way to the device
+    jl_dev_array<uint32_t> hm_part;        // the column segments' byte counters, when a second kernel combines them
+    jl_dev_array<uint32_t> hm_out;         // counts [JL_HM_COUNTERS][hm_reads]
+    jl_dev_array<double> hm_p;             // p [hm_reads], then log_p [hm_reads]
+    uint64_t hm_reads = 0;                 // reads of the last call enqueued (0: none)
 
     // ---- jl_sites_assemble INTO this context: the site table on its way to the device (capi_sites.hip)
     jl_upload_staging<jl_site> sites_in;

@@ -77,6 +77,7 @@ private:
         jl_ctx *run = nullptr;       // the window that is called: ctx, or — downsampled — the pool context's companion (taken_)
         SamplingInfo sampling;
         ReadFilterInfo read_filter;
+        HypermutInfo hypermut;
         SampleSetup s;
         std::vector<std::string> names;
         uint64_t n_reads = 0;
@@ -217,6 +218,14 @@ private:
             if (rf.outcome != Outcome::ok) return rf.text();
             if (acted) smp.run = kept;
         }
+        if (opt_.hypermut()) {   // (every sample of the list at the same level; docs/SPEC.md §26)
+            jl_ctx *kept = companion_of(smp.run);
+            bool acted = false;
+            const Status hs = hypermut_window(opt_, smp.s, smp.run, kept, &smp.read_filter, smp.names, smp.n_reads, smp.hypermut, &acted);
+            if (hs.outcome == Outcome::device) gpu_error(hs.text());
+            if (hs.outcome != Outcome::ok) return hs.text();
+            if (acted) smp.run = kept;
+        }
         if (opt_.have_downsample && smp.n_reads > opt_.downsample) {   // (every sample of the list goes to the same depth)
             jl_ctx *taken = companion_of(smp.run);
             bool acted = false;
@@ -337,7 +346,7 @@ private:
     void write(Sample &x)
     {
         try {
-            const Json root = build_json(opt_, x.s, x.line->bam, cmdline_, x.names, x.n_reads, x.R, &x.sampling, &x.read_filter);
+            const Json root = build_json(opt_, x.s, x.line->bam, cmdline_, x.names, x.n_reads, x.R, &x.sampling, &x.read_filter, nullptr, &x.hypermut);
             std::lock_guard<std::mutex> lk(io_m_);
             const std::string failed = write_outputs(x.line->outputs, root);
             if (!failed.empty()) sample_failed(*x.line, "cannot write " + failed);

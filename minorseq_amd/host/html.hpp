@@ -50,7 +50,7 @@ inline std::string render_html(const Json &root)
     if (const Json *in = root.get("input")) {
         h += "<details open id=\"input\"><summary>Input data</summary><table id=\"input-table\">\n";
         for (auto &kv : in->obj)
-            if (kv.first != "sampling" && kv.first != "read_filter" && kv.first != "control") h += "<tr><th>" + html_escape(kv.first) + "</th>" + td(num_str(&kv.second)) + "</tr>\n";
+            if (kv.first != "sampling" && kv.first != "read_filter" && kv.first != "hypermutation" && kv.first != "control") h += "<tr><th>" + html_escape(kv.first) + "</th>" + td(num_str(&kv.second)) + "</tr>\n";
         h += "</table>\n";
         // --downsample / --mix: the seed and, per source, its file, its reads and how many of them were kept (docs/SPEC.md section 12)
         if (const Json *sp = in->get("sampling")) {
@@ -75,6 +75,14 @@ inline std::string render_html(const Json &root)
             if (const Json *failed = rf->get("failed"))
                 for (auto &kv : failed->obj)
                     h += "<tr class=\"rule\">" + td(kv.first) + td(rule ? num_str(rule->get(kv.first)) : "") + td(num_str(&kv.second)) + "</tr>\n";
+            h += "</table>\n";
+        }
+        // the hypermutation filter: its reference row, its level, and the reads it flagged and kept (docs/SPEC.md section 26)
+        if (const Json *hj = in->get("hypermutation")) {
+            h += "<table id=\"hypermutation-table\" data-reference=\"" + html_escape(hj->get_str("reference")) + "\">\n<tr><th>hypermutation filter (G of: " +
+                 html_escape(hj->get_str("reference")) + ")</th><th>value</th></tr>\n";
+            for (const char *leaf : {"alpha", "reads", "flagged", "kept", "dropped"})
+                h += std::string("<tr class=\"") + leaf + "\">" + td(leaf) + td(num_str(hj->get(leaf))) + "</tr>\n";
             h += "</table>\n";
         }
         h += "</details>\n";

@@ -58,13 +58,14 @@ struct Run {
     Results R;
     SamplingInfo sampling;
     ReadFilterInfo read_filter;
+    HypermutInfo hypermut;
     ControlInfo control;
 };
 
 // JSON / HTML (doc/JULIET.md:61-107, 207-211), and the end of the process
 int write_run(Run &run)
 {
-    const Json root = build_json(run.opt, run.smp, run.opt.bam, run.cmdline, run.load.names, run.load.n_reads, run.R, &run.sampling, &run.read_filter, &run.control);
+    const Json root = build_json(run.opt, run.smp, run.opt.bam, run.cmdline, run.load.names, run.load.n_reads, run.R, &run.sampling, &run.read_filter, &run.control, &run.hypermut);
     const std::string failed = write_outputs(run.opt.outputs, root);
     if (!failed.empty()) { std::cerr << "juliet: cannot write " << failed << "\n"; return 2; }
     run.tick("json / html");
@@ -85,7 +86,7 @@ int run_fuse(Run &run, jl_ctx *ctx)
     return 0;
 }
 
-// One window on one device: ingest, the read filter, --downsample / --mix, the run, its results, the outputs.
+// One window on one device: ingest, the read filter, the hypermutation filter, --downsample / --mix, the run, its results, the outputs.
 int run_one_window(Run &run)
 {
     const Options &opt = run.opt;
@@ -106,6 +107,14 @@ int run_one_window(Run &run)
         if (const int code = exit_code_of(read_filter_window(opt, smp, ctx, kept, names, n_reads, run.read_filter, &acted), opt.bam)) return code;
         if (acted) ctx = kept;
         tick("read filter");
+    }
+    if (opt.hypermut()) {   // the reads that are not hypermutated, of those the read filter kept (docs/SPEC.md §26)
+        jl_ctx *kept = nullptr;
+        if (jl_ctx_create(opt.device, jl_ctx_stream(ctx), &kept) != JL_OK) die_jl(nullptr, "context of the kept reads");
+        bool acted = false;
+        if (const int code = exit_code_of(hypermut_window(opt, smp, ctx, kept, &run.read_filter, names, n_reads, run.hypermut, &acted), opt.bam)) return code;
+        if (acted) ctx = kept;
+        tick("hypermutation filter");
     }
     if (opt.sampling()) {   // the window to call is made of chosen reads, in a second context on the same device and stream
         jl_ctx *taken = nullptr;

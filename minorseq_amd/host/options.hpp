@@ -80,6 +80,11 @@ struct Options {
     uint32_t read_rule_set = 0;      // bit r: rule r (the order of jl_read_filter's failed[]) was given
     std::string read_stats_out;      // --read-stats out.tsv: the counters of every read of the loaded sample
     bool read_filter() const { return read_rule_set != 0 || !read_stats_out.empty(); }
+    bool drop_hypermutated = false;  // --drop-hypermutated: drop the reads whose G->A test gives p < hypermut_alpha (docs/SPEC.md §26)
+    bool have_hypermut_alpha = false;
+    double hypermut_alpha = 0.05;    // Hypermut's
+    std::string hypermut_report;     // --hypermut-report out.tsv: the counters and p of every read of the loaded sample
+    bool hypermut() const { return drop_hypermutated || !hypermut_report.empty(); }
     std::string control;             // --control control.bam: the codons are called against this sample's counts, not the error model (docs/SPEC.md §21)
     std::string batch;               // --batch samples.tsv: one `in.bam<TAB>out1[<TAB>out2]` per line, every other option for all of them
     struct BatchLine { unsigned line; std::string bam; std::vector<std::string> outputs; };
@@ -232,6 +237,16 @@ struct Options {
         "      --read-stats <out.tsv>          name, bases, gaps, masked, compared, mismatches of every read of the loaded sample,\n"
         "                                      tab-separated, in input order, before any filter; needs no rule.  Refused where the\n"
         "                                      read filter is, and with --batch\n"
+        "      --drop-hypermutated [--hypermut-alpha a]  drop APOBEC-hypermutated reads (docs/SPEC.md section 26): the device counts,\n"
+        "                                      per read, its G->A sites in the target context GRD and in the control contexts\n"
+        "                                      GYN / GRC, taken from the read's own two cells downstream, and tests the two one-sided\n"
+        "                                      (Fisher, as Hypermut 2.0); a read with p < a (default 0.05) is dropped.  G is the\n"
+        "                                      config's referenceSequence over the window, else the majority consensus.  After the\n"
+        "                                      read filter, before --downsample.  The JSON gains input.hypermutation.  No read kept is\n"
+        "                                      an input error (2).  With --batch: every sample.  Refused where the read filter is\n"
+        "      --hypermut-report <out.tsv>     name, target_sites, target_mut, control_sites, control_mut, p of every read of the\n"
+        "                                      loaded sample, tab-separated, in input order; needs no --drop-hypermutated.  Refused\n"
+        "                                      where the read filter is, and with --batch\n"
         "      --mix b.bam[,c.bam...] [--mix-perc P]  a mixture as mixdata makes it (doc/MIXDATA.md): in.bam is the major clone, every\n"
         "                                      listed BAM a minor clone with P percent (default 1) of --downsample C reads (default\n"
         "                                      3000); source m is sampled with seed S + m.  A source with too few reads is an input\n"
@@ -449,6 +464,15 @@ Options parse(int argc, char **argv)
             else o.read_rule.max_masked_perc = x, o.read_rule_set |= 16u;
         }
         else if (a == "--read-stats") o.read_stats_out = need(i);
+        else if (a == "--drop-hypermutated") o.drop_hypermutated = true;
+        else if (a == "--hypermut-alpha") {
+            const std::string v = need(i);
+            char *end = nullptr;
+            const double x = std::strtod(v.c_str(), &end);
+            if (v.empty() || *end || !(x > 0.0 && x <= 1.0)) { std::cerr << "juliet: --hypermut-alpha wants a level in (0, 1], not '" << v << "'\n"; std::exit(1); }
+            o.hypermut_alpha = x, o.have_hypermut_alpha = true;
+        }
+        else if (a == "--hypermut-report") o.hypermut_report = need(i);
         else if (a == "--control") o.control = need(i);
         else if (!a.empty() && a[0] == '-') { std::cerr << "juliet: unknown option " << a << "\n"; usage(1); }
         else pos.push_back(a);
@@ -532,6 +556,7 @@ Options parse(int argc, char **argv)
         if (!o.batch.empty()) refuse("is not part of a batch (not with --batch)");
         if (o.sampling()) refuse("reads the insertions of the records that were ingested, not of a sample of them (drop --downsample / --mix)");
         if (o.read_filter()) refuse("reads the insertions of the records that were ingested, not of the reads a filter keeps (drop the read filter / --read-stats)");
+        if (o.hypermut() || o.have_hypermut_alpha) refuse("reads the insertions of the records that were ingested, not of the reads a filter keeps (drop --drop-hypermutated / --hypermut-report)");
     }
     if (o.phase_insertions) {   // refused here, before any file is read or any GPU work (what --call-insertions refuses: above)
         auto refuse = [](const char *why) { std::cerr << "juliet: --phase-insertions " << why << "\n"; std::exit(1); };
@@ -567,6 +592,15 @@ Options parse(int argc, char **argv)
         if (!o.consensus.empty()) refuse("carries no insertion counters into the kept reads: no consensus (drop --consensus)");
         if (!o.mix.empty()) refuse("filters one sample, not the sources of a mixture (drop --mix)");
         if (!o.batch.empty() && !o.read_stats_out.empty()) refuse("writes one --read-stats file for one sample (not with --batch)");
+    }
+    if (o.hypermut() || o.have_hypermut_alpha) {   // refused here, before any file is read or any GPU work: what the read filter refuses
+        auto refuse = [](const char *why) { std::cerr << "juliet: the hypermutation filter (--drop-hypermutated, --hypermut-alpha, --hypermut-report) " << why << "\n"; std::exit(1); };
+        if (!o.drop_hypermutated && o.have_hypermut_alpha) refuse("--hypermut-alpha sets the level of --drop-hypermutated (add it)");
+        if (as_fuse) refuse("is not an option of fuse");
+        if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
+        if (!o.consensus.empty()) refuse("carries no insertion counters into the kept reads: no consensus (drop --consensus)");
+        if (!o.mix.empty()) refuse("filters one sample, not the sources of a mixture (drop --mix)");
+        if (!o.batch.empty() && !o.hypermut_report.empty()) refuse("writes one --hypermut-report file for one sample (not with --batch)");
     }
     if (o.sampling()) {   // what sampling cannot be combined with is refused here, before any file is read or any GPU work
         auto refuse = [&](const char *why) { std::cerr << "juliet: " << (o.mix.empty() ? "--downsample " : "--mix ") << why << "\n"; std::exit(1); };

@@ -37,7 +37,7 @@ std::string haplotype_name(uint32_t h)  // [A-Z]{1}[a-z]?  (doc/JULIET.md:198)
 // The JSON document of one sample (doc/JULIET.md:61-107, 207-211); the HTML output is its rendering.
 Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam, const std::string &cmdline,
                 const std::vector<std::string> &names, uint64_t n_reads, const Results &R, const SamplingInfo *sampling = nullptr,
-                const ReadFilterInfo *read_filter = nullptr, const ControlInfo *control = nullptr)
+                const ReadFilterInfo *read_filter = nullptr, const ControlInfo *control = nullptr, const HypermutInfo *hypermut = nullptr)
 {
     const TargetConfig &cfg = s.cfg;
     const uint32_t win_begin = s.win_begin, n_cols = s.n_cols;
@@ -76,6 +76,13 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
         rf.set("compare", Json::of(std::string(read_filter->reference ? "reference" : "majority"))).set("rule", std::move(rule));
         rf.set("reads", Json::of((int64_t)read_filter->reads)).set("kept", Json::of((int64_t)read_filter->kept)).set("failed", std::move(failed));
         root.obj.back().second.set("read_filter", std::move(rf));
+    }
+    if (hypermut && hypermut->ran) {   // (only with --drop-hypermutated or --hypermut-report: docs/SPEC.md section 26)
+        Json hj = Json::object();
+        hj.set("reference", Json::of(std::string(hypermut->reference ? "reference" : "majority"))).set("alpha", Json::of(hypermut->alpha));
+        hj.set("reads", Json::of((int64_t)hypermut->reads)).set("flagged", Json::of((int64_t)hypermut->flagged)).set("kept", Json::of((int64_t)hypermut->kept));
+        hj.set("dropped", Json::of(hypermut->dropped));
+        root.obj.back().second.set("hypermutation", std::move(hj));
     }
     if (control && control->used)   // (only with --control: docs/SPEC.md section 21)
         root.obj.back().second.set("control", Json::object().set("file", Json::of(control->file)).set("reads", Json::of((int64_t)control->reads)));

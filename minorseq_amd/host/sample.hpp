@@ -745,7 +745,26 @@ struct ReadFilterInfo {
     bool reference = false;      // the compare row: the config's referenceSequence over the window, or the majority consensus
     uint64_t reads = 0, kept = 0;
     uint64_t failed[5] = {0, 0, 0, 0, 0};
+    std::vector<uint8_t> compare;   // the compare row it used, of the window as ingested (the hypermutation filter takes it over)
 };
+
+// The row a per-read stage compares with (docs/SPEC.md §20, §26): the config's referenceSequence over the window when it covers it
+// (*reference), else the majority consensus of the window resident on `ctx`: a plain pileup, then its consensus.  JL_OK, or the
+// status of the call that failed (*what says which).
+int window_compare_row(const SampleSetup &smp, jl_ctx *ctx, std::vector<uint8_t> &compare, bool *reference, const char **what)
+{
+    const uint32_t n_cols = smp.n_cols;
+    compare.resize(n_cols);
+    *reference = smp.refcodes.size() >= (size_t)smp.win_begin + n_cols;
+    if (*reference) {
+        std::copy_n(smp.refcodes.begin() + smp.win_begin, n_cols, compare.begin());
+        return JL_OK;
+    }
+    *what = "pileup of the compare row";
+    if (const int rc = jl_pileup_async(ctx, smp.genes.data(), (uint32_t)smp.genes.size(), smp.refp(), (uint32_t)smp.refcodes.size())) return rc;
+    *what = "consensus of the compare row";
+    return jl_consensus_fetch(ctx, compare.data());
+}
 
 // The read filter on a window that is resident on `ctx` (its reads' names in `names`): the compare row, the per-read counters
 // (jl_read_stats_async), --read-stats, the rule (jl_read_filter), and — when it drops a read — the kept reads gathered into `taken`,
@@ -760,14 +779,9 @@ Status read_filter_window(const Options &opt, const SampleSetup &smp, jl_ctx *ct
         st.outcome = Outcome::device, st.what = what, st.ctx = c, st.rc = rc;
         return st;
     };
-    const uint32_t n_cols = smp.n_cols;
-    std::vector<uint8_t> compare(n_cols);
-    info.reference = smp.refcodes.size() >= (size_t)smp.win_begin + n_cols;
-    if (info.reference) std::copy_n(smp.refcodes.begin() + smp.win_begin, n_cols, compare.begin());
-    else {   // the majority of the window as ingested: a plain pileup, then its consensus
-        if (const int rc = jl_pileup_async(ctx, smp.genes.data(), (uint32_t)smp.genes.size(), smp.refp(), (uint32_t)smp.refcodes.size())) return device("pileup of the read filter", ctx, rc);
-        if (const int rc = jl_consensus_fetch(ctx, compare.data())) return device("consensus of the read filter", ctx, rc);
-    }
+    std::vector<uint8_t> &compare = info.compare;
+    const char *what = "";
+    if (const int rc = window_compare_row(smp, ctx, compare, &info.reference, &what)) return device(what, ctx, rc);
     std::vector<uint32_t> stats((size_t)JL_READ_STATS * n_reads);
     if (const int rc = jl_read_stats_async(ctx, compare.data())) return device("read stats", ctx, rc);
     if (const int rc = jl_read_stats_fetch(ctx, stats.data())) return device("read stats fetch", ctx, rc);
@@ -803,6 +817,82 @@ Status read_filter_window(const Options &opt, const SampleSetup &smp, jl_ctx *ct
     if (kept == n_reads) return st;
     const jl_take_part part = {ctx, idx.data(), kept};
     if (const int rc = jl_msa_take(taken, &part, 1)) return device("take of the read filter", taken, rc);
+    std::vector<std::string> chosen((size_t)kept);
+    for (uint64_t j = 0; j < kept; ++j) chosen[(size_t)j].swap(names[idx[(size_t)j]]);
+    names.swap(chosen);
+    n_reads = kept;
+    *acted = true;
+    return st;
+}
+
+// What the hypermutation filter did to a sample (docs/SPEC.md §26): the `hypermutation` block of the JSON's input section, present
+// when --drop-hypermutated or --hypermut-report was given.
+struct HypermutInfo {
+    bool ran = false;
+    bool reference = false;      // the row whose G are the sites: the config's referenceSequence over the window, or the majority consensus
+    bool dropped = false;        // --drop-hypermutated was given
+    double alpha = 0.05;
+    uint64_t reads = 0, flagged = 0, kept = 0;
+};
+
+// The hypermutation filter on a window that is resident on `ctx` (its reads' names in `names`) — what the read filter kept, when
+// there is one: the reference row (`row`: the read filter's, when it ran; else chosen as the read filter chooses), the per-read
+// counters and their test (jl_read_hypermut_async), --hypermut-report, the rule (jl_hypermut_filter) and — when it drops a read —
+// the kept reads gathered into `taken`, a second context of the device on the same stream; names / n_reads follow the indices.
+// *acted: the window to run is `taken` now.  An input failure: no read is kept, or the report cannot be written.
+Status hypermut_window(const Options &opt, const SampleSetup &smp, jl_ctx *ctx, jl_ctx *taken, const ReadFilterInfo *row,
+                       std::vector<std::string> &names, uint64_t &n_reads, HypermutInfo &info, bool *acted)
+{
+    Status st;
+    *acted = false;
+    auto device = [&](const char *what, jl_ctx *c, int rc) {
+        st.outcome = Outcome::device, st.what = what, st.ctx = c, st.rc = rc;
+        return st;
+    };
+    std::vector<uint8_t> ref;
+    if (row && row->ran) ref = row->compare, info.reference = row->reference;
+    else {
+        const char *what = "";
+        if (const int rc = window_compare_row(smp, ctx, ref, &info.reference, &what)) return device(what, ctx, rc);
+    }
+    std::vector<uint32_t> counts((size_t)JL_HM_COUNTERS * n_reads);
+    std::vector<double> p((size_t)n_reads);
+    if (const int rc = jl_read_hypermut_async(ctx, ref.data())) return device("hypermutation counters", ctx, rc);
+    if (const int rc = jl_read_hypermut_fetch(ctx, counts.data(), p.data(), nullptr)) return device("hypermutation counters fetch", ctx, rc);
+    info.ran = true;
+    info.dropped = opt.drop_hypermutated;
+    info.alpha = opt.hypermut_alpha;
+    info.reads = info.kept = n_reads;
+    std::vector<uint32_t> idx((size_t)n_reads);
+    uint64_t kept = 0;
+    if (const int rc = jl_hypermut_filter(p.data(), n_reads, opt.hypermut_alpha, idx.data(), &kept, &info.flagged)) return device("hypermutation filter", nullptr, rc);
+    if (!opt.hypermut_report.empty()) {
+        std::string text;
+        char num[40];
+        for (uint64_t i = 0; i < n_reads; ++i) {
+            text += names[(size_t)i];
+            for (uint32_t k = 0; k < JL_HM_COUNTERS; ++k) text += "\t" + std::to_string(counts[(size_t)(k * n_reads + i)]);
+            snprintf(num, sizeof num, "\t%.17g\n", p[(size_t)i]);
+            text += num;
+        }
+        std::ofstream f(opt.hypermut_report, std::ios::binary);
+        f << text;
+        f.close();
+        if (!f) {
+            st.outcome = Outcome::input, st.what = "cannot write " + opt.hypermut_report + " for the reads";
+            return st;
+        }
+    }
+    if (!opt.drop_hypermutated) return st;
+    info.kept = kept;
+    if (kept == 0) {
+        st.outcome = Outcome::input;
+        st.what = "the hypermutation filter keeps none of " + std::to_string(n_reads) + " reads (p below " + std::to_string(opt.hypermut_alpha) + " in every one)";
+        return st;
+    }
+    if (kept == n_reads) return st;
+    const jl_take_part part = {ctx, idx.data(), kept};
+    if (const int rc = jl_msa_take(taken, &part, 1)) return device("take of the hypermutation filter", taken, rc);
     std::vector<std::string> chosen((size_t)kept);
     for (uint64_t j = 0; j < kept; ++j) chosen[(size_t)j].swap(names[idx[(size_t)j]]);
     names.swap(chosen);
@@ -884,6 +974,16 @@ int control_window(const Options &opt, const IngestOptions &io, const SampleSetu
         ReadFilterInfo rf;
         bool acted = false;
         if (const int code = exit_code_of(read_filter_window(rules, smp, c, kept, load.names, n_reads, rf, &acted), opt.control)) return code;
+        if (acted) c = kept;
+    }
+    if (opt.drop_hypermutated) {   // (and the sample's hypermutation filter, on a reference row of the control's own choosing)
+        Options rules = opt;
+        rules.hypermut_report.clear();
+        jl_ctx *kept = nullptr;
+        if (jl_ctx_create(opt.device, jl_ctx_stream(sample), &kept) != JL_OK) die_jl(nullptr, "context of the control's kept reads");
+        HypermutInfo hm;
+        bool acted = false;
+        if (const int code = exit_code_of(hypermut_window(rules, smp, c, kept, nullptr, load.names, n_reads, hm, &acted), opt.control)) return code;
         if (acted) c = kept;
     }
     info.used = true;
