@@ -645,6 +645,59 @@ int jl_hypermut_test(uint32_t target_mut, uint32_t target_sites, uint32_t contro
  * argument; alpha outside (0, 1]; n_reads above 2^32 - 1. */
 int jl_hypermut_filter(const double *p, uint64_t n_reads, double alpha, uint32_t *idx, uint64_t *n_kept, uint64_t *n_flagged);
 /*
+ * PER-READ reading-frame integrity per open reading frame (docs/SPEC.md §27): which reads carry a premature stop, are out of frame
+ * or lack a large piece, in which gene — the second half of the proviral intactness screen after hypermutation.  A SPAN is an open
+ * reading frame in window columns: codon k of span g is the columns col + 3 k .. col + 3 k + 2.  1 <= n_spans <= JL_ORF_MAX_SPANS,
+ * n_codons >= 1 and col + 3 n_codons <= n_cols (summed in 64 bits); spans may overlap in any frame and need no order.  Per (span
+ * g, read i), over the span's 3 n_codons columns only (codes as above):
+ *   JL_ORF_COVERED      cells != 6                     JL_ORF_GAP_CELLS   cells == 4
+ *   JL_ORF_CODONS_READ  codons whose three cells are all < 4
+ *   JL_ORF_STOPS        of those, the read's codon is TAA, TAG or TGA and the codon of ref at the same three columns is none of
+ *                       the three (a ref codon with any code >= 4 is no stop)
+ * An N cell (5) is covered, no gap, and makes its codon unread.  first_stop[g][i]: the lowest codon index k counted in
+ * JL_ORF_STOPS, or JL_ORF_NO_STOP.  counts[JL_ORF_COUNTERS][n_spans][n_reads] and first_stop[n_spans][n_reads], 32 bits, exact,
+ * independent of launch shape and order; reads past n_reads count nowhere.  ref[n_cols] follows jl_read_stats_async's compare
+ * convention.
+ * The contract is jl_read_hypermut_async's: spans and ref are copied before the call returns; the kernels are enqueued on the
+ * context's stream into buffers of its own and nothing else of the context is touched; every kind of resident matrix is accepted.
+ * JL_ERR_ARG: spans or ref NULL, n_spans outside 1 .. 64, a span outside the window.  JL_ERR_STATE: no resident matrix.  A refused
+ * call changes nothing.
+ */
+typedef struct {
+    uint32_t col;
+    uint32_t n_codons;
+} jl_orf_span;
+enum { JL_ORF_MAX_SPANS = 64 };
+enum { JL_ORF_COVERED = 0, JL_ORF_GAP_CELLS = 1, JL_ORF_CODONS_READ = 2, JL_ORF_STOPS = 3, JL_ORF_COUNTERS = 4 };
+#define JL_ORF_NO_STOP 0xFFFFFFFFu
+int jl_read_orf_async(jl_ctx *ctx, const jl_orf_span *spans, uint32_t n_spans, const uint8_t *ref /* [n_cols] */);
+/* Wait and copy out what the last jl_read_orf_async computed, for its n_spans and the n_reads it saw; any pointer may be NULL (both
+ * NULL: only wait).  JL_ERR_STATE: none was enqueued. */
+int jl_read_orf_fetch(jl_ctx *ctx, uint32_t *counts /* [JL_ORF_COUNTERS][n_spans][n_reads] */,
+                      uint32_t *first_stop /* [n_spans][n_reads] */);
+/* Host only (no device, no context): the flags of every (span, read) from the counters.  With n = n_codons of the span:
+ *   JL_ORF_PARTIAL      covered < 3 n
+ *   JL_ORF_STOP         first_stop < n - min(tail_codons, n): a stop before the last tail_codons codons (the first stop in the
+ *                       tail: all are)
+ *   JL_ORF_FRAMESHIFT   gap_cells % 3 != 0: the NET frame of the read's deletions inside the span (a -1 and a -2 deletion cancel;
+ *                       insertions never enter the matrix)
+ *   JL_ORF_DELETION     max_gap_cells > 0 and gap_cells >= max_gap_cells
+ * A partial read keeps every other flag it earns.  rule {0, 0}: DELETION off, no tail.  JL_ERR_ARG (jl_last_error(NULL) says
+ * which): a NULL argument; n_spans outside 1 .. 64; n_reads above 2^32 - 1; a counter that contradicts its span — covered > 3 n,
+ * gap_cells > covered, stops > codons_read, a first_stop that is neither JL_ORF_NO_STOP nor < n.  A refused call writes nothing. */
+typedef struct {
+    uint32_t max_gap_cells;
+    uint32_t tail_codons;
+} jl_orf_rule;
+enum { JL_ORF_PARTIAL = 1, JL_ORF_STOP = 2, JL_ORF_FRAMESHIFT = 4, JL_ORF_DELETION = 8 };
+int jl_orf_classify(const uint32_t *counts, const uint32_t *first_stop, const jl_orf_span *spans, uint32_t n_spans,
+                    uint64_t n_reads, const jl_orf_rule *rule, uint8_t *flags /* [n_spans][n_reads] */);
+/* Host only.  A read is defective when the flags of any span meet `mask`, a non-empty subset of JL_ORF_STOP | JL_ORF_FRAMESHIFT |
+ * JL_ORF_DELETION, and is dropped; idx[0 .. *n_kept): the kept reads, ascending — what jl_msa_take takes; room for n_reads.
+ * *n_flagged = n_reads - *n_kept.  JL_ERR_ARG: a NULL argument; n_spans outside 1 .. 64; such a mask; n_reads above 2^32 - 1. */
+int jl_orf_filter(const uint8_t *flags, uint32_t n_spans, uint64_t n_reads, uint32_t mask, uint32_t *idx, uint64_t *n_kept,
+                  uint64_t *n_flagged);
+/*
  * The SITE MATRIX (docs/SPEC.md §18): called codon deletions as sites of a haplotype.  Phasing groups reads by their codons at the
  * variant positions, and a deleted codon is no codon: its carriers are GAP-damaged where the position is a variant position and
  * invisible where it is not.  This call builds, as jl_xwin_assemble_local does, a compact matrix of chosen codon starts of `src`

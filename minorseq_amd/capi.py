@@ -43,7 +43,7 @@ SITE_INS_NONE, SITE_INS_OTHER, SITE_INS_MAX_ALLELES = 0, 63, 62
 EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", "jl_ctx_destroy", "jl_last_error",
            "jl_sync", "jl_col_stride", "jl_plane_stride", "jl_msa_upload", "jl_msa_alloc", "jl_msa_adopt", "jl_msa_pack_rows",
            "jl_msa_ingest_records", "jl_records_begin", "jl_records_append", "jl_records_finish", "jl_records_window", "jl_records_window_async", "jl_records_drop", "jl_records_append_masked", "jl_msa_ingest_records_masked", "jl_qmask_bytes", "jl_qmask_from_quals", "jl_msa_track_insertions", "jl_insertions_fetch", "jl_msa_take", "jl_msa_take_async", "jl_sample_reads", "jl_mix_counts", "jl_msa_download", "jl_msa_download_planes", "jl_synth_fill", "jl_synth_fill_window", "jl_pileup_async", "jl_n_positions", "jl_pileup_fetch",
-           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_class_codons_async", "jl_class_codons_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_phase_nearest_async", "jl_phase_nearest_fetch", "jl_phase_recombinants_async", "jl_phase_recombinants_fetch", "jl_haplotype_recombinants", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_deletion_alleles_async", "jl_deletion_alleles_fetch", "jl_deletion_allele_test", "jl_read_stats_async", "jl_read_stats_fetch", "jl_read_filter", "jl_read_hypermut_async", "jl_read_hypermut_fetch", "jl_hypermut_eval", "jl_hypermut_test", "jl_hypermut_filter", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_msa_track_insertion_reads", "jl_insertion_reads_fetch", "jl_sites_assemble_alleles", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_control_call_async", "jl_control_call_fetch", "jl_control_test", "jl_phase_async", "jl_phase_fetch",
+           "jl_consensus_fetch", "jl_class_pileup_async", "jl_class_pileup_fetch", "jl_class_codons_async", "jl_class_codons_fetch", "jl_consensus_of_counts", "jl_phase_rescue_async", "jl_phase_rescue_fetch", "jl_phase_nearest_async", "jl_phase_nearest_fetch", "jl_phase_recombinants_async", "jl_phase_recombinants_fetch", "jl_haplotype_recombinants", "jl_variant_linkage_async", "jl_variant_linkage_fetch", "jl_linkage_stats", "jl_codon_deletions_async", "jl_codon_deletions_fetch", "jl_deletion_test", "jl_deletion_alleles_async", "jl_deletion_alleles_fetch", "jl_deletion_allele_test", "jl_read_stats_async", "jl_read_stats_fetch", "jl_read_filter", "jl_read_hypermut_async", "jl_read_hypermut_fetch", "jl_hypermut_eval", "jl_hypermut_test", "jl_hypermut_filter", "jl_read_orf_async", "jl_read_orf_fetch", "jl_orf_classify", "jl_orf_filter", "jl_sites_assemble", "jl_msa_track_insertion_alleles", "jl_insertion_alleles_fetch", "jl_insertion_test", "jl_msa_track_insertion_reads", "jl_insertion_reads_fetch", "jl_sites_assemble_alleles", "jl_call_async", "jl_call_fetch", "jl_variant_table_device", "jl_control_call_async", "jl_control_call_fetch", "jl_control_test", "jl_phase_async", "jl_phase_fetch",
            "jl_ctx_stream", "jl_run_async", "jl_run_wait", "jl_run_done", "jl_run_view_get", "jl_group_create", "jl_group_destroy",
            "jl_group_last_error", "jl_group_run_async", "jl_group_run_masked_async", "jl_group_views", "jl_group_time_pileup", "jl_msa_index_info", "jl_fisher_eval", "jl_fisher_eval_tail", "jl_control_eval", "jl_expand_read_hap", "jl_time_run", "jl_time_pileup", "jl_time_pileup_set", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_pileup_kernel_name", "jl_comm_unique_id", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
            "jl_allgather_variants", "jl_allgather_variants_async", "jl_allgather_variants_async_many", "jl_allgather_variants_many", "jl_group_exchange_bind", "jl_group_exchange_collect", "jl_xwin_plan", "jl_xwin_assemble_local",
@@ -56,6 +56,14 @@ EXPORTS = ("jl_abi_version", "jl_strerror", "jl_device_count", "jl_ctx_create", 
 READ_BASES, READ_GAPS, READ_MASKED, READ_COMPARED, READ_MISMATCHES, READ_STATS = range(6)   # jl_read_stats_async (docs/SPEC.md §20)
 READ_RULES = ("min_bases", "mismatches", "mismatch_perc", "gap_perc", "n_perc")   # the order of jl_read_filter's failed[5]
 HM_TARGET_SITES, HM_TARGET_MUT, HM_CONTROL_SITES, HM_CONTROL_MUT, HM_COUNTERS = range(5)   # jl_read_hypermut_async (docs/SPEC.md §26)
+ORF_COVERED, ORF_GAP_CELLS, ORF_CODONS_READ, ORF_STOPS, ORF_COUNTERS = range(5)            # jl_read_orf_async (docs/SPEC.md §27)
+ORF_MAX_SPANS, ORF_NO_STOP = 64, 0xFFFFFFFF
+ORF_PARTIAL, ORF_STOP, ORF_FRAMESHIFT, ORF_DELETION = 1, 2, 4, 8                            # the flags of jl_orf_classify
+ORF_SPAN = np.dtype([("col", np.uint32), ("n_codons", np.uint32)])                          # jl_orf_span
+
+
+class OrfRule(C.Structure):   # jl_orf_rule
+    _fields_ = [("max_gap_cells", C.c_uint32), ("tail_codons", C.c_uint32)]
 
 
 class ReadRule(C.Structure):   # jl_read_rule
@@ -264,6 +272,10 @@ def load_library(path=LIB_PATH):
     lib.jl_hypermut_eval.argtypes = [vp, vp, u64, vp, vp]
     lib.jl_hypermut_test.argtypes = [u32, u32, u32, u32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     lib.jl_hypermut_filter.argtypes = [vp, u64, C.c_double, vp, C.POINTER(u64), C.POINTER(u64)]
+    lib.jl_read_orf_async.argtypes = [vp, vp, u32, vp]
+    lib.jl_read_orf_fetch.argtypes = [vp, vp, vp]
+    lib.jl_orf_classify.argtypes = [vp, vp, vp, u32, u64, C.POINTER(OrfRule), vp]
+    lib.jl_orf_filter.argtypes = [vp, u32, u64, u32, vp, C.POINTER(u64), C.POINTER(u64)]
     lib.jl_sites_assemble.argtypes = [vp, vp, vp, u32]
     lib.jl_msa_track_insertion_alleles.argtypes = [vp, C.c_int]
     lib.jl_insertion_alleles_fetch.argtypes = [vp, vp, vp, u32, vp]
@@ -822,6 +834,26 @@ class Juliet:
         self._chk(self.lib.jl_read_hypermut_fetch(self.h, *((_p(counts), _p(p), _p(lp)) if n else (None, None, None))))
         return counts, p, lp
 
+    def read_orf(self, spans, ref, wait=True):
+        """jl_read_orf_async (docs/SPEC.md §27): per (span, read) of the resident matrix the covered cells, the gap cells, the codons
+        read in full, the stops the reference does not have, and the first of them.  spans: ORF_SPAN rows or (col, n_codons) pairs;
+        ref[n_cols]: a code per column.  Returns (counts[4, n_spans, n_reads] uint32 (ORF_COVERED .. ORF_STOPS), first_stop[n_spans,
+        n_reads] uint32, ORF_NO_STOP for none); wait=False only enqueues on this context's stream and returns None (read_orf_fetch
+        brings them)."""
+        spans = orf_spans(spans)
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        assert ref.shape == (self.n_cols,)
+        self._chk(self.lib.jl_read_orf_async(self.h, _p(spans), len(spans), _p(ref)))
+        self._orf_shape = (len(spans), self.n_reads)
+        return self.read_orf_fetch() if wait else None
+
+    def read_orf_fetch(self):
+        s, n = getattr(self, "_orf_shape", (0, 0))
+        counts = np.zeros((ORF_COUNTERS, s, n), dtype=np.uint32)
+        first = np.zeros((s, n), dtype=np.uint32)
+        self._chk(self.lib.jl_read_orf_fetch(self.h, *((_p(counts), _p(first)) if s * n else (None, None))))
+        return counts, first
+
     def hypermut_eval(self, counts):
         """jl_hypermut_eval: the test kernel of jl_read_hypermut_async over counts[4, n] of the caller; (p, log_p)."""
         counts = np.ascontiguousarray(counts, dtype=np.uint32)
@@ -1364,6 +1396,43 @@ def hypermut_filter(p, alpha=0.05):
     rc = lib.jl_hypermut_filter(_p(p), len(p), float(alpha), _p(idx), C.byref(kept), C.byref(flagged))
     if rc:
         raise JulietError(rc, "jl_hypermut_filter: " + lib.jl_last_error(None).decode())
+    return idx[: kept.value].copy(), flagged.value
+
+
+def orf_spans(spans):
+    """ORF_SPAN rows of (col, n_codons) pairs, or of an ORF_SPAN array as it stands."""
+    if isinstance(spans, np.ndarray) and spans.dtype == ORF_SPAN:
+        return np.ascontiguousarray(spans)
+    return np.array([tuple(int(x) for x in s) for s in spans], dtype=ORF_SPAN)
+
+
+def orf_classify(counts, first_stop, spans, max_gap_cells=0, tail_codons=0):
+    """jl_orf_classify (host only, docs/SPEC.md §27): flags[n_spans, n_reads] uint8 of ORF_PARTIAL | ORF_STOP | ORF_FRAMESHIFT |
+    ORF_DELETION from counts[4, n_spans, n_reads] and first_stop[n_spans, n_reads]."""
+    lib = load_library()
+    spans = orf_spans(spans)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    first_stop = np.ascontiguousarray(first_stop, dtype=np.uint32)
+    assert counts.ndim == 3 and counts.shape[:2] == (ORF_COUNTERS, len(spans)) and first_stop.shape == counts.shape[1:]
+    flags = np.zeros(first_stop.shape, dtype=np.uint8)
+    rule = OrfRule(int(max_gap_cells), int(tail_codons))
+    rc = lib.jl_orf_classify(_p(counts), _p(first_stop), _p(spans), len(spans), first_stop.shape[1], C.byref(rule), _p(flags))
+    if rc:
+        raise JulietError(rc, "jl_orf_classify: " + lib.jl_last_error(None).decode())
+    return flags
+
+
+def orf_filter(flags, mask=ORF_STOP | ORF_FRAMESHIFT):
+    """jl_orf_filter (host only, docs/SPEC.md §27): (idx, n_flagged) — the reads none of whose spans' flags meets `mask`, ascending
+    uint32 indices, what Juliet.take takes, and how many reads were defective."""
+    lib = load_library()
+    flags = np.ascontiguousarray(flags, dtype=np.uint8)
+    assert flags.ndim == 2
+    idx = np.zeros(max(1, flags.shape[1]), dtype=np.uint32)
+    kept, flagged = C.c_uint64(), C.c_uint64()
+    rc = lib.jl_orf_filter(_p(flags), flags.shape[0], flags.shape[1], int(mask), _p(idx), C.byref(kept), C.byref(flagged))
+    if rc:
+        raise JulietError(rc, "jl_orf_filter: " + lib.jl_last_error(None).decode())
     return idx[: kept.value].copy(), flagged.value
 
 

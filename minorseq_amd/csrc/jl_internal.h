@@ -534,6 +534,32 @@ size_t jl_hypermut_part_words(const jl_readstats_shape *shape);
 // one thread a read: p[i], lp[i] of the table counts[.][i] (n > 0; ceil(n / 256) workgroups fit a launch)
 void jl_launch_hypermut_test(const uint32_t *counts, uint64_t n, double *p, double *lp, hipStream_t st);
 
+// ---- per-read reading-frame counters per span (kernels_orf.hip, capi_orf.hip; docs/SPEC.md §27)
+struct jl_orf_shape;           // orf_shape.h
+struct jl_orf_seg {            // one workgroup's walk: whole codons of one span (the table capi_orf.hip builds from the shape)
+    uint32_t col;              // window column of its first codon
+    uint32_t n_codons;         // 1 .. 85
+    uint32_t span;
+    uint32_t first_codon;      // ... of the span that is codon 0 here
+};
+struct jl_orf_args {
+    const uint8_t *msa;        // the window's bit planes
+    uint64_t plane_stride;     // ... and their stride (an adopted matrix brings its own)
+    uint64_t n_reads;
+    uint32_t n_cols;
+    uint32_t n_words;          // words of a row that hold reads: ceil(n_reads / 32); 4 n_words <= plane_stride
+    uint32_t n_chunks;         // of the launch shape (set by the launcher)
+    uint32_t n_spans, n_segs;
+    const uint8_t *ref;        // [n_cols]
+    const jl_orf_seg *segs;    // [n_segs], the segments of span 0 first, each span's in codon order
+    const uint32_t *span_seg0; // [n_spans + 1]: the first segment of every span, and n_segs
+    uint32_t *part;            // the segments' byte counters (jl_orf_part_words)
+    uint32_t *counts;          // [JL_ORF_COUNTERS][n_spans][n_reads]
+    uint32_t *first_stop;      // [n_spans][n_reads]
+};
+void jl_launch_orf_counts(const jl_orf_args *a, const jl_orf_shape *shape, hipStream_t st);
+size_t jl_orf_part_words(const jl_orf_shape *shape);
+
 // ---- the site matrix: chosen codon starts of a matrix, deletion sites recoded (kernels_sites.hip, capi_sites.hip; docs/SPEC.md §18)
 struct jl_sites_args {
     const uint8_t *src;        // the source's bit planes
@@ -883,6 +909,14 @@ struct jl_ctx {
     jl_dev_array<uint32_t> hm_out;         // counts [JL_HM_COUNTERS][hm_reads]
     jl_dev_array<double> hm_p;             // p [hm_reads], then log_p [hm_reads]
     uint64_t hm_reads = 0;                 // reads of the last call enqueued (0: none)
+
+    // ---- jl_read_orf_async: buffers of its own, grown on demand (capi_orf.hip); no stage and no run touches them
+    jl_upload_staging<uint8_t> orf_ref;    // the reference row on its way to the device
+    jl_upload_staging<uint32_t> orf_tab;   // the segment table (jl_orf_seg [n_segs]), then the spans' first segments [n_spans + 1]
+    jl_dev_array<uint32_t> orf_part;       // the segments' byte counters
+    jl_dev_array<uint32_t> orf_out;        // counts [JL_ORF_COUNTERS][orf_spans][orf_reads], then first_stop [orf_spans][orf_reads]
+    uint64_t orf_reads = 0;                // reads of the last call enqueued (0: none)
+    uint32_t orf_spans = 0;                // ... and its spans
 
     // ---- jl_sites_assemble INTO this context: the site table on its way to the device (capi_sites.hip)
     jl_upload_staging<jl_site> sites_in;

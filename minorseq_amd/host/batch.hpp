@@ -78,6 +78,7 @@ private:
         SamplingInfo sampling;
         ReadFilterInfo read_filter;
         HypermutInfo hypermut;
+        OrfInfo orf;
         SampleSetup s;
         std::vector<std::string> names;
         uint64_t n_reads = 0;
@@ -226,6 +227,15 @@ private:
             if (hs.outcome != Outcome::ok) return hs.text();
             if (acted) smp.run = kept;
         }
+        if (opt_.orf()) {   // (every sample of the list under the same rule; docs/SPEC.md §27)
+            jl_ctx *kept = companion_of(smp.run);
+            bool acted = false, reference = false;
+            const std::vector<uint8_t> *row = earlier_row(smp.read_filter, smp.hypermut, &reference);
+            const Status os = orf_window(opt_, smp.s, smp.run, kept, row, reference, smp.names, smp.n_reads, smp.orf, &acted);
+            if (os.outcome == Outcome::device) gpu_error(os.text());
+            if (os.outcome != Outcome::ok) return os.text();
+            if (acted) smp.run = kept;
+        }
         if (opt_.have_downsample && smp.n_reads > opt_.downsample) {   // (every sample of the list goes to the same depth)
             jl_ctx *taken = companion_of(smp.run);
             bool acted = false;
@@ -346,7 +356,7 @@ private:
     void write(Sample &x)
     {
         try {
-            const Json root = build_json(opt_, x.s, x.line->bam, cmdline_, x.names, x.n_reads, x.R, &x.sampling, &x.read_filter, nullptr, &x.hypermut);
+            const Json root = build_json(opt_, x.s, x.line->bam, cmdline_, x.names, x.n_reads, x.R, &x.sampling, &x.read_filter, nullptr, &x.hypermut, &x.orf);
             std::lock_guard<std::mutex> lk(io_m_);
             const std::string failed = write_outputs(x.line->outputs, root);
             if (!failed.empty()) sample_failed(*x.line, "cannot write " + failed);

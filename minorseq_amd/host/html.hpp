@@ -50,7 +50,7 @@ inline std::string render_html(const Json &root)
     if (const Json *in = root.get("input")) {
         h += "<details open id=\"input\"><summary>Input data</summary><table id=\"input-table\">\n";
         for (auto &kv : in->obj)
-            if (kv.first != "sampling" && kv.first != "read_filter" && kv.first != "hypermutation" && kv.first != "control") h += "<tr><th>" + html_escape(kv.first) + "</th>" + td(num_str(&kv.second)) + "</tr>\n";
+            if (kv.first != "sampling" && kv.first != "read_filter" && kv.first != "hypermutation" && kv.first != "orf_integrity" && kv.first != "control") h += "<tr><th>" + html_escape(kv.first) + "</th>" + td(num_str(&kv.second)) + "</tr>\n";
         h += "</table>\n";
         // --downsample / --mix: the seed and, per source, its file, its reads and how many of them were kept (docs/SPEC.md section 12)
         if (const Json *sp = in->get("sampling")) {
@@ -83,6 +83,21 @@ inline std::string render_html(const Json &root)
                  html_escape(hj->get_str("reference")) + ")</th><th>value</th></tr>\n";
             for (const char *leaf : {"alpha", "reads", "flagged", "kept", "dropped"})
                 h += std::string("<tr class=\"") + leaf + "\">" + td(leaf) + td(num_str(hj->get(leaf))) + "</tr>\n";
+            h += "</table>\n";
+        }
+        // the reading-frame filter: its reference row, its rule, the reads it found defective and kept, and per gene the reads of every flag (docs/SPEC.md section 27)
+        if (const Json *oj = in->get("orf_integrity")) {
+            h += "<table id=\"orf-integrity-table\" data-reference=\"" + html_escape(oj->get_str("reference")) + "\">\n<tr><th>reading-frame filter (stops of: " +
+                 html_escape(oj->get_str("reference")) + ")</th><th>value</th></tr>\n";
+            for (const char *leaf : {"kinds", "max_deletion", "tail_codons", "reads", "defective", "kept", "dropped"})
+                h += std::string("<tr class=\"") + leaf + "\">" + td(leaf) + td(num_str(oj->get(leaf))) + "</tr>\n";
+            h += "</table>\n<table id=\"orf-integrity-genes\">\n<tr><th>gene</th><th>partial</th><th>stop</th><th>frameshift</th><th>deletion</th></tr>\n";
+            if (const Json *genes = oj->get("genes"))
+                for (const Json &g : genes->arr) {
+                    h += "<tr class=\"gene\">" + td(html_escape(g.get_str("name")));
+                    for (const char *leaf : {"partial", "stop", "frameshift", "deletion"}) h += td(num_str(g.get(leaf)));
+                    h += "</tr>\n";
+                }
             h += "</table>\n";
         }
         h += "</details>\n";

@@ -59,13 +59,14 @@ struct Run {
     SamplingInfo sampling;
     ReadFilterInfo read_filter;
     HypermutInfo hypermut;
+    OrfInfo orf;
     ControlInfo control;
 };
 
 // JSON / HTML (doc/JULIET.md:61-107, 207-211), and the end of the process
 int write_run(Run &run)
 {
-    const Json root = build_json(run.opt, run.smp, run.opt.bam, run.cmdline, run.load.names, run.load.n_reads, run.R, &run.sampling, &run.read_filter, &run.control, &run.hypermut);
+    const Json root = build_json(run.opt, run.smp, run.opt.bam, run.cmdline, run.load.names, run.load.n_reads, run.R, &run.sampling, &run.read_filter, &run.control, &run.hypermut, &run.orf);
     const std::string failed = write_outputs(run.opt.outputs, root);
     if (!failed.empty()) { std::cerr << "juliet: cannot write " << failed << "\n"; return 2; }
     run.tick("json / html");
@@ -86,7 +87,7 @@ int run_fuse(Run &run, jl_ctx *ctx)
     return 0;
 }
 
-// One window on one device: ingest, the read filter, the hypermutation filter, --downsample / --mix, the run, its results, the outputs.
+// One window on one device: ingest, the read filter, the hypermutation filter, the reading-frame filter, --downsample / --mix, the run, its results, the outputs.
 int run_one_window(Run &run)
 {
     const Options &opt = run.opt;
@@ -115,6 +116,15 @@ int run_one_window(Run &run)
         if (const int code = exit_code_of(hypermut_window(opt, smp, ctx, kept, &run.read_filter, names, n_reads, run.hypermut, &acted), opt.bam)) return code;
         if (acted) ctx = kept;
         tick("hypermutation filter");
+    }
+    if (opt.orf()) {   // the reads whose reading frames are whole, of those the two filters before kept (docs/SPEC.md §27)
+        jl_ctx *kept = nullptr;
+        if (jl_ctx_create(opt.device, jl_ctx_stream(ctx), &kept) != JL_OK) die_jl(nullptr, "context of the kept reads");
+        bool acted = false, reference = false;
+        const std::vector<uint8_t> *row = earlier_row(run.read_filter, run.hypermut, &reference);
+        if (const int code = exit_code_of(orf_window(opt, smp, ctx, kept, row, reference, names, n_reads, run.orf, &acted), opt.bam)) return code;
+        if (acted) ctx = kept;
+        tick("reading-frame filter");
     }
     if (opt.sampling()) {   // the window to call is made of chosen reads, in a second context on the same device and stream
         jl_ctx *taken = nullptr;
@@ -201,7 +211,7 @@ int run_one_window(Run &run)
 // `juliet in.bam out...`: the sample onto the device(s) — its setup and --dump-msa while the contexts come up — then the mode
 int run_sample(const Options &opt, const TargetConfig &cfg, const std::string &cmdline, const Tick &tick)
 {
-    Run run{opt, cmdline, tick, ingest_options(opt), {}, {}, {}, {}, {}, {}};
+    Run run{opt, cmdline, tick, ingest_options(opt), {}, {}, {}, {}, {}, {}, {}, {}};
     // the GPU context comes up (runtime start, stream, pinned blocks) while the host reads the BAM
     const bool need_gpu = !opt.outputs.empty() || opt.fuse_only;
     std::vector<CtxFuture> ctx_ups;

@@ -85,6 +85,13 @@ struct Options {
     double hypermut_alpha = 0.05;    // Hypermut's
     std::string hypermut_report;     // --hypermut-report out.tsv: the counters and p of every read of the loaded sample
     bool hypermut() const { return drop_hypermutated || !hypermut_report.empty(); }
+    bool drop_defective = false;     // --drop-defective: drop the reads with a premature stop, a frameshift or a large deletion in a gene (docs/SPEC.md §27)
+    bool have_defect_option = false; // any --defect-* option was given
+    uint32_t defect_kinds = 2u | 4u; // JL_ORF_STOP | JL_ORF_FRAMESHIFT: --defect-kinds
+    uint32_t defect_max_deletion = 0;// --defect-max-deletion K: gap cells of a gene from which a read has the DELETION flag (0: off)
+    uint32_t defect_tail_codons = 0; // --defect-tail-codons T: a stop in the last T codons of a gene is none
+    std::string orf_report;          // --orf-report out.tsv: the counters and flags of every (read, gene) of the loaded sample
+    bool orf() const { return drop_defective || !orf_report.empty(); }
     std::string control;             // --control control.bam: the codons are called against this sample's counts, not the error model (docs/SPEC.md §21)
     std::string batch;               // --batch samples.tsv: one `in.bam<TAB>out1[<TAB>out2]` per line, every other option for all of them
     struct BatchLine { unsigned line; std::string bam; std::vector<std::string> outputs; };
@@ -247,6 +254,17 @@ struct Options {
         "      --hypermut-report <out.tsv>     name, target_sites, target_mut, control_sites, control_mut, p of every read of the\n"
         "                                      loaded sample, tab-separated, in input order; needs no --drop-hypermutated.  Refused\n"
         "                                      where the read filter is, and with --batch\n"
+        "      --drop-defective [--defect-kinds stop,frameshift,deletion] [--defect-max-deletion K] [--defect-tail-codons T]\n"
+        "                                      drop reads whose reading frame is broken in any gene (docs/SPEC.md section 27): the device\n"
+        "                                      counts, per read and gene of the config (without one: the one `unknown` gene), covered\n"
+        "                                      cells, gap cells, codons read and stop codons the reference row does not have.  stop: a\n"
+        "                                      stop before the gene's last T codons (default 0); frameshift: gap cells not a multiple\n"
+        "                                      of 3; deletion: K gap cells or more (needs K).  Default kinds: stop,frameshift.  After\n"
+        "                                      --drop-hypermutated, before --downsample.  The JSON gains input.orf_integrity.  No read\n"
+        "                                      kept is an input error (2).  With --batch: every sample.  Refused where the read filter is\n"
+        "      --orf-report <out.tsv>          name, gene, covered, gap_cells, codons_read, stops, first_stop, flags (P S F D) of every\n"
+        "                                      read and gene of the loaded sample, tab-separated, reads in input order, genes in config\n"
+        "                                      order; needs no --drop-defective.  Refused where the read filter is, and with --batch\n"
         "      --mix b.bam[,c.bam...] [--mix-perc P]  a mixture as mixdata makes it (doc/MIXDATA.md): in.bam is the major clone, every\n"
         "                                      listed BAM a minor clone with P percent (default 1) of --downsample C reads (default\n"
         "                                      3000); source m is sampled with seed S + m.  A source with too few reads is an input\n"
@@ -473,6 +491,33 @@ Options parse(int argc, char **argv)
             o.hypermut_alpha = x, o.have_hypermut_alpha = true;
         }
         else if (a == "--hypermut-report") o.hypermut_report = need(i);
+        else if (a == "--drop-defective") o.drop_defective = true;
+        else if (a == "--orf-report") o.orf_report = need(i);
+        else if (a == "--defect-kinds") {
+            const std::string v = need(i);
+            o.have_defect_option = true;
+            o.defect_kinds = 0;
+            for (size_t b = 0; b <= v.size();) {
+                const size_t e = std::min(v.find(',', b), v.size());
+                const std::string kind = v.substr(b, e - b);
+                const uint32_t bit = kind == "stop" ? 2u : kind == "frameshift" ? 4u : kind == "deletion" ? 8u : 0u;   // JL_ORF_STOP, _FRAMESHIFT, _DELETION
+                if (!bit) { std::cerr << "juliet: --defect-kinds wants a list of stop, frameshift, deletion, not '" << v << "'\n"; std::exit(1); }
+                o.defect_kinds |= bit;
+                b = e + 1;
+            }
+        }
+        else if (a == "--defect-max-deletion" || a == "--defect-tail-codons") {
+            const bool tail = a == "--defect-tail-codons";
+            const std::string v = need(i);
+            char *end = nullptr;
+            const unsigned long long k = std::strtoull(v.c_str(), &end, 10);
+            o.have_defect_option = true;
+            if (v.empty() || *end || v[0] == '-' || (!tail && k == 0) || k > 0xFFFFFFFFull) {
+                std::cerr << "juliet: " << a << (tail ? " wants a number of codons, not '" : " wants 1 gap cell or more, not '") << v << "'\n";
+                std::exit(1);
+            }
+            (tail ? o.defect_tail_codons : o.defect_max_deletion) = (uint32_t)k;
+        }
         else if (a == "--control") o.control = need(i);
         else if (!a.empty() && a[0] == '-') { std::cerr << "juliet: unknown option " << a << "\n"; usage(1); }
         else pos.push_back(a);
@@ -557,6 +602,7 @@ Options parse(int argc, char **argv)
         if (o.sampling()) refuse("reads the insertions of the records that were ingested, not of a sample of them (drop --downsample / --mix)");
         if (o.read_filter()) refuse("reads the insertions of the records that were ingested, not of the reads a filter keeps (drop the read filter / --read-stats)");
         if (o.hypermut() || o.have_hypermut_alpha) refuse("reads the insertions of the records that were ingested, not of the reads a filter keeps (drop --drop-hypermutated / --hypermut-report)");
+        if (o.orf() || o.have_defect_option) refuse("reads the insertions of the records that were ingested, not of the reads a filter keeps (drop --drop-defective / --orf-report)");
     }
     if (o.phase_insertions) {   // refused here, before any file is read or any GPU work (what --call-insertions refuses: above)
         auto refuse = [](const char *why) { std::cerr << "juliet: --phase-insertions " << why << "\n"; std::exit(1); };
@@ -601,6 +647,16 @@ Options parse(int argc, char **argv)
         if (!o.consensus.empty()) refuse("carries no insertion counters into the kept reads: no consensus (drop --consensus)");
         if (!o.mix.empty()) refuse("filters one sample, not the sources of a mixture (drop --mix)");
         if (!o.batch.empty() && !o.hypermut_report.empty()) refuse("writes one --hypermut-report file for one sample (not with --batch)");
+    }
+    if (o.orf() || o.have_defect_option) {   // refused here, before any file is read or any GPU work: what the hypermutation filter refuses
+        auto refuse = [](const char *why) { std::cerr << "juliet: the reading-frame filter (--drop-defective, --defect-*, --orf-report) " << why << "\n"; std::exit(1); };
+        if (!o.drop_defective && o.have_defect_option) refuse("--defect-kinds, --defect-max-deletion and --defect-tail-codons are the rule of --drop-defective (add it)");
+        if ((o.defect_kinds & 8u) && o.defect_max_deletion == 0) refuse("kind deletion needs its bound (add --defect-max-deletion K)");
+        if (as_fuse) refuse("is not an option of fuse");
+        if (o.windows > 1 || o.devices.size() > 1) refuse("works on one window of one device (drop --windows / --devices a,b)");
+        if (!o.consensus.empty()) refuse("carries no insertion counters into the kept reads: no consensus (drop --consensus)");
+        if (!o.mix.empty()) refuse("filters one sample, not the sources of a mixture (drop --mix)");
+        if (!o.batch.empty() && !o.orf_report.empty()) refuse("writes one --orf-report file for one sample (not with --batch)");
     }
     if (o.sampling()) {   // what sampling cannot be combined with is refused here, before any file is read or any GPU work
         auto refuse = [&](const char *why) { std::cerr << "juliet: " << (o.mix.empty() ? "--downsample " : "--mix ") << why << "\n"; std::exit(1); };

@@ -37,7 +37,8 @@ std::string haplotype_name(uint32_t h)  // [A-Z]{1}[a-z]?  (doc/JULIET.md:198)
 // The JSON document of one sample (doc/JULIET.md:61-107, 207-211); the HTML output is its rendering.
 Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam, const std::string &cmdline,
                 const std::vector<std::string> &names, uint64_t n_reads, const Results &R, const SamplingInfo *sampling = nullptr,
-                const ReadFilterInfo *read_filter = nullptr, const ControlInfo *control = nullptr, const HypermutInfo *hypermut = nullptr)
+                const ReadFilterInfo *read_filter = nullptr, const ControlInfo *control = nullptr, const HypermutInfo *hypermut = nullptr,
+                const OrfInfo *orf = nullptr)
 {
     const TargetConfig &cfg = s.cfg;
     const uint32_t win_begin = s.win_begin, n_cols = s.n_cols;
@@ -83,6 +84,19 @@ Json build_json(const Options &opt, const SampleSetup &s, const std::string &bam
         hj.set("reads", Json::of((int64_t)hypermut->reads)).set("flagged", Json::of((int64_t)hypermut->flagged)).set("kept", Json::of((int64_t)hypermut->kept));
         hj.set("dropped", Json::of(hypermut->dropped));
         root.obj.back().second.set("hypermutation", std::move(hj));
+    }
+    if (orf && orf->ran) {   // (only with --drop-defective or --orf-report: docs/SPEC.md section 27)
+        Json oj = Json::object();
+        oj.set("reference", Json::of(std::string(orf->reference ? "reference" : "majority"))).set("kinds", Json::of(orf_kinds_text(orf->kinds)));
+        oj.set("max_deletion", Json::of((int64_t)orf->max_deletion)).set("tail_codons", Json::of((int64_t)orf->tail_codons));
+        oj.set("reads", Json::of((int64_t)orf->reads)).set("defective", Json::of((int64_t)orf->defective)).set("kept", Json::of((int64_t)orf->kept));
+        oj.set("dropped", Json::of(orf->dropped));
+        Json genes = Json::array();
+        for (const OrfInfo::Gene &g : orf->genes)
+            genes.push(Json::object().set("name", Json::of(g.name)).set("partial", Json::of((int64_t)g.partial)).set("stop", Json::of((int64_t)g.stop))
+                           .set("frameshift", Json::of((int64_t)g.frameshift)).set("deletion", Json::of((int64_t)g.deletion)));
+        oj.set("genes", std::move(genes));
+        root.obj.back().second.set("orf_integrity", std::move(oj));
     }
     if (control && control->used)   // (only with --control: docs/SPEC.md section 21)
         root.obj.back().second.set("control", Json::object().set("file", Json::of(control->file)).set("reads", Json::of((int64_t)control->reads)));

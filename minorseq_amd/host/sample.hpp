@@ -833,6 +833,7 @@ struct HypermutInfo {
     bool dropped = false;        // --drop-hypermutated was given
     double alpha = 0.05;
     uint64_t reads = 0, flagged = 0, kept = 0;
+    std::vector<uint8_t> ref;    // the row it used (the reading-frame filter takes it over)
 };
 
 // The hypermutation filter on a window that is resident on `ctx` (its reads' names in `names`) — what the read filter kept, when
@@ -849,7 +850,7 @@ Status hypermut_window(const Options &opt, const SampleSetup &smp, jl_ctx *ctx, 
         st.outcome = Outcome::device, st.what = what, st.ctx = c, st.rc = rc;
         return st;
     };
-    std::vector<uint8_t> ref;
+    std::vector<uint8_t> &ref = info.ref;
     if (row && row->ran) ref = row->compare, info.reference = row->reference;
     else {
         const char *what = "";
@@ -899,6 +900,134 @@ Status hypermut_window(const Options &opt, const SampleSetup &smp, jl_ctx *ctx, 
     n_reads = kept;
     *acted = true;
     return st;
+}
+
+// What the reading-frame filter did to a sample (docs/SPEC.md §27): the `orf_integrity` block of the JSON's input section, present
+// when --drop-defective or --orf-report was given.
+struct OrfInfo {
+    bool ran = false;
+    bool reference = false;      // the row whose stops are no stops of a read: the config's referenceSequence over the window, or the majority consensus
+    bool dropped = false;        // --drop-defective was given
+    uint32_t kinds = 0, max_deletion = 0, tail_codons = 0;
+    uint64_t reads = 0, defective = 0, kept = 0;
+    struct Gene { std::string name; uint64_t partial = 0, stop = 0, frameshift = 0, deletion = 0; };
+    std::vector<Gene> genes;     // reads per flag, in config order
+};
+
+// "stop,frameshift,deletion" of a mask of JL_ORF_STOP | JL_ORF_FRAMESHIFT | JL_ORF_DELETION
+inline std::string orf_kinds_text(uint32_t kinds)
+{
+    std::string s;
+    for (const auto &k : {std::make_pair((uint32_t)JL_ORF_STOP, "stop"), std::make_pair((uint32_t)JL_ORF_FRAMESHIFT, "frameshift"), std::make_pair((uint32_t)JL_ORF_DELETION, "deletion")})
+        if (kinds & k.first) s += (s.empty() ? "" : ",") + std::string(k.second);
+    return s;
+}
+
+// The reading-frame filter on a window that is resident on `ctx` (its reads' names in `names`) — what the read filter and the
+// hypermutation filter kept, when there are any: the spans (the sample's genes as the pileup maps their codons to window columns,
+// docs/SPEC.md §3), the reference row (`ref`: an earlier filter's, when one ran; else chosen as the read filter chooses), the
+// per-read counters (jl_read_orf_async), the flags (jl_orf_classify), --orf-report, the rule (jl_orf_filter) and — when it drops a
+// read — the kept reads gathered into `taken`, a second context of the device on the same stream; names / n_reads follow the
+// indices.  *acted: the window to run is `taken` now.  An input failure: more than 64 genes, a gene without a codon in the window,
+// no read kept, or a report that cannot be written.
+Status orf_window(const Options &opt, const SampleSetup &smp, jl_ctx *ctx, jl_ctx *taken, const std::vector<uint8_t> *ref_row, bool ref_is_reference,
+                  std::vector<std::string> &names, uint64_t &n_reads, OrfInfo &info, bool *acted)
+{
+    Status st;
+    *acted = false;
+    auto device = [&](const char *what, jl_ctx *c, int rc) {
+        st.outcome = Outcome::device, st.what = what, st.ctx = c, st.rc = rc;
+        return st;
+    };
+    auto input = [&](const std::string &what) {
+        st.outcome = Outcome::input, st.what = what;
+        return st;
+    };
+    const std::vector<GeneCfg> &genes = smp.cfg.genes;
+    if (genes.size() > (size_t)JL_ORF_MAX_SPANS) return input("the reading-frame filter takes at most " + std::to_string((int)JL_ORF_MAX_SPANS) + " genes, the config has " + std::to_string(genes.size()));
+    std::vector<jl_orf_span> spans;
+    for (const GeneCfg &g : genes) {   // codon k of the gene: window column begin - 1 + 3 k - win_begin, evaluated while c + 2 < n_cols
+        const uint64_t col = (uint64_t)g.begin_eff - 1u - smp.win_begin;
+        const uint64_t fit = col + 3u <= smp.n_cols ? (smp.n_cols - col) / 3u : 0u;
+        const uint64_t n = std::min<uint64_t>((g.end_eff - g.begin_eff) / 3u, fit);
+        if (n == 0) return input("gene '" + g.name + "' has no codon in the window: nothing for the reading-frame filter to read");
+        spans.push_back({(uint32_t)col, (uint32_t)n});
+    }
+    const uint32_t n_spans = (uint32_t)spans.size();
+    std::vector<uint8_t> own;
+    if (ref_row && !ref_row->empty()) info.reference = ref_is_reference;
+    else {
+        const char *what = "";
+        if (const int rc = window_compare_row(smp, ctx, own, &info.reference, &what)) return device(what, ctx, rc);
+        ref_row = &own;
+    }
+    const size_t per_kind = (size_t)n_spans * n_reads;
+    std::vector<uint32_t> counts((size_t)JL_ORF_COUNTERS * per_kind), first(per_kind);
+    std::vector<uint8_t> flags(per_kind);
+    if (const int rc = jl_read_orf_async(ctx, spans.data(), n_spans, ref_row->data())) return device("reading-frame counters", ctx, rc);
+    if (const int rc = jl_read_orf_fetch(ctx, counts.data(), first.data())) return device("reading-frame counters fetch", ctx, rc);
+    const jl_orf_rule rule = {opt.defect_max_deletion, opt.defect_tail_codons};
+    if (const int rc = jl_orf_classify(counts.data(), first.data(), spans.data(), n_spans, n_reads, &rule, flags.data())) return device("reading-frame flags", nullptr, rc);
+    info.ran = true;
+    info.dropped = opt.drop_defective;
+    info.kinds = opt.defect_kinds, info.max_deletion = opt.defect_max_deletion, info.tail_codons = opt.defect_tail_codons;
+    info.reads = info.kept = n_reads;
+    info.genes.clear();
+    for (uint32_t g = 0; g < n_spans; ++g) {
+        OrfInfo::Gene gi;
+        gi.name = genes[g].name;
+        for (uint64_t i = 0; i < n_reads; ++i) {
+            const uint8_t f = flags[(size_t)(g * n_reads + i)];
+            gi.partial += (f & JL_ORF_PARTIAL) != 0, gi.stop += (f & JL_ORF_STOP) != 0;
+            gi.frameshift += (f & JL_ORF_FRAMESHIFT) != 0, gi.deletion += (f & JL_ORF_DELETION) != 0;
+        }
+        info.genes.push_back(std::move(gi));
+    }
+    std::vector<uint32_t> idx((size_t)n_reads);
+    uint64_t kept = 0;
+    if (const int rc = jl_orf_filter(flags.data(), n_spans, n_reads, opt.defect_kinds, idx.data(), &kept, &info.defective)) return device("reading-frame filter", nullptr, rc);
+    if (!opt.orf_report.empty()) {
+        std::string text;
+        for (uint64_t i = 0; i < n_reads; ++i)
+            for (uint32_t g = 0; g < n_spans; ++g) {
+                const size_t e = (size_t)(g * n_reads + i);
+                text += names[(size_t)i] + "\t" + genes[g].name;
+                for (uint32_t k = 0; k < JL_ORF_COUNTERS; ++k) text += "\t" + std::to_string(counts[k * per_kind + e]);
+                text += "\t" + (first[e] == JL_ORF_NO_STOP ? std::string("-") : std::to_string((uint64_t)genes[g].first_codon + first[e] + 1u)) + "\t";
+                std::string letters;
+                for (const auto &b : {std::make_pair((int)JL_ORF_PARTIAL, 'P'), std::make_pair((int)JL_ORF_STOP, 'S'), std::make_pair((int)JL_ORF_FRAMESHIFT, 'F'), std::make_pair((int)JL_ORF_DELETION, 'D')})
+                    if (flags[e] & b.first) letters += b.second;
+                text += (letters.empty() ? "-" : letters) + "\n";
+            }
+        std::ofstream f(opt.orf_report, std::ios::binary);
+        f << text;
+        f.close();
+        if (!f) return input("cannot write " + opt.orf_report + " for the reads");
+    }
+    if (!opt.drop_defective) {
+        info.kept = n_reads;
+        return st;
+    }
+    info.kept = kept;
+    if (kept == 0) return input("the reading-frame filter keeps none of " + std::to_string(n_reads) + " reads (" + orf_kinds_text(opt.defect_kinds) + " in every one)");
+    if (kept == n_reads) return st;
+    const jl_take_part part = {ctx, idx.data(), kept};
+    if (const int rc = jl_msa_take(taken, &part, 1)) return device("take of the reading-frame filter", taken, rc);
+    std::vector<std::string> chosen((size_t)kept);
+    for (uint64_t j = 0; j < kept; ++j) chosen[(size_t)j].swap(names[idx[(size_t)j]]);
+    names.swap(chosen);
+    n_reads = kept;
+    *acted = true;
+    return st;
+}
+
+// the row an earlier filter of the sample used, for the reading-frame filter: the read filter's, else the hypermutation filter's, else none
+inline const std::vector<uint8_t> *earlier_row(const ReadFilterInfo &rf, const HypermutInfo &hm, bool *reference)
+{
+    if (rf.ran) { *reference = rf.reference; return &rf.compare; }
+    if (hm.ran) { *reference = hm.reference; return &hm.ref; }
+    *reference = false;
+    return nullptr;
 }
 
 // --mix: the mixture of doc/MIXDATA.md in `taken`.  `major` holds the positional BAM's window; every BAM of the list is decoded and
@@ -984,6 +1113,16 @@ int control_window(const Options &opt, const IngestOptions &io, const SampleSetu
         HypermutInfo hm;
         bool acted = false;
         if (const int code = exit_code_of(hypermut_window(rules, smp, c, kept, nullptr, load.names, n_reads, hm, &acted), opt.control)) return code;
+        if (acted) c = kept;
+    }
+    if (opt.drop_defective) {   // (and the sample's reading-frame filter, on a reference row of the control's own choosing)
+        Options rules = opt;
+        rules.orf_report.clear();
+        jl_ctx *kept = nullptr;
+        if (jl_ctx_create(opt.device, jl_ctx_stream(sample), &kept) != JL_OK) die_jl(nullptr, "context of the control's kept reads");
+        OrfInfo oi;
+        bool acted = false;
+        if (const int code = exit_code_of(orf_window(rules, smp, c, kept, nullptr, false, load.names, n_reads, oi, &acted), opt.control)) return code;
         if (acted) c = kept;
     }
     info.used = true;
