@@ -150,7 +150,7 @@ int jl_msa_upload(jl_ctx *ctx, const uint8_t *colpacked, uint64_t n_reads, uint3
 /* Allocate an uninitialised resident matrix (for jl_synth_fill / jl_msa_pack_rows). */
 int jl_msa_alloc(jl_ctx *ctx, uint64_t n_reads, uint32_t n_cols, uint32_t win_begin);
 /* Use caller-owned device memory (e.g. a torch tensor) holding the resident format — [n_cols][3][plane_stride] bytes,
- * 16-byte aligned, plane_stride a multiple of 16 and >= ceil(n_reads / 8), padding reads = code 6 — as the resident
+ * 16-byte aligned, plane_stride a multiple of 16, >= ceil(n_reads / 8) and below 4 GiB, padding reads = code 6 — as the resident
  * matrix; never copied, not freed by the ctx, and the caller may rewrite it between runs. */
 int jl_msa_adopt(jl_ctx *ctx, void *d_planes, uint64_t n_reads, uint32_t n_cols, uint64_t plane_stride,
                  uint32_t win_begin);

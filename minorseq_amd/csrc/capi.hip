@@ -173,6 +173,10 @@ static int set_shape(jl_ctx *ctx, uint64_t n_reads, uint32_t n_cols, uint64_t pl
     if (n_reads > 0x7FFFFFFFull) return jl_fail(ctx, JL_ERR_ARG, "more than 2^31-1 reads per context");
     if (plane_stride % 16 != 0 || plane_stride < (n_reads + 7) / 8)
         return jl_fail(ctx, JL_ERR_ARG, "plane_stride %llu must be a multiple of 16 and >= ceil(n_reads/8)", (unsigned long long)plane_stride);
+    // Several launchers keep the stride, or the stride divided by 4 or 16, in a uint32_t (kernels_phase.hip, kernels_pileup.hip,
+    // kernels_index.hip, capi_group.hip, capi_take.hip): below 4 GiB all of them fit.  2^31 - 1 reads need 2^28 bytes a plane.
+    if (plane_stride > 0xFFFFFFFFull)
+        return jl_fail(ctx, JL_ERR_ARG, "plane_stride %llu: a plane stride of 4 GiB or more is not supported", (unsigned long long)plane_stride);
     if (n_reads != ctx->n_reads || n_cols != ctx->n_cols || plane_stride != ctx->plane_stride || win_begin != ctx->win_begin)
         ctx->plan_valid = false;
     ctx->n_reads = n_reads;

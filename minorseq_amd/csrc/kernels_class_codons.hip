@@ -29,6 +29,7 @@ constexpr uint32_t kWaves = 4;                      // waves of a workgroup: a q
 constexpr uint32_t kThreads = 64 * kWaves;
 constexpr uint32_t kRows = 9u * kStarts;            // plane rows staged: nine a position
 constexpr uint32_t kLoads = kRows * 4u / kThreads;  // 16-byte loads of a thread per tile
+static_assert(kStarts == 64, "jl_class_codons_shape_for (plane_walk.h) groups the positions by 64");
 static_assert(kLoads * kThreads == kRows * 4u && kWaves * 4u == kTileWords, "a tile is four 16-byte units a row, one a wave");
 
 // grid: x = group of 64 positions, y = read segment of `seg_tiles` tiles, z = pass; NK = classes of a pass, from class
@@ -169,12 +170,10 @@ void jl_launch_class_codons(const jl_class_codons_args *a, hipStream_t st)
     jl_class_codons_args A = *a;
     const uint32_t n_groups = (A.n_pos + kStarts - 1u) / kStarts;
     const uint32_t full = A.n_classes / 16u, rest = A.n_classes % 16u;
-    // segments x groups x passes fill the chip twice over: 256 CUs x 3 workgroups (46 KB of LDS each)
-    const uint32_t n_tiles = jl_walk_tiles(A.n_reads);
-    if (!n_tiles) return;   // no read: the zeroed table is the answer
-    const uint32_t segs = std::max(1u, std::min(n_tiles, 1536u / std::max(1u, n_groups * std::max(1u, full))));
-    A.seg_tiles = (n_tiles + segs - 1u) / segs;
-    const uint32_t n_segs = (n_tiles + A.seg_tiles - 1u) / A.seg_tiles;
+    if (!jl_walk_tiles(A.n_reads)) return;   // no read: the zeroed table is the answer
+    const jl_walk_shape shape = jl_class_codons_shape_for(A.n_reads, A.n_pos, A.n_classes);
+    A.seg_tiles = shape.seg_tiles;
+    const uint32_t n_segs = shape.n_segs;
     A.k_first = 0u;
     if (full) kCounting[15](A, dim3(n_groups, n_segs, full), st);
     A.k_first = 16u * full;

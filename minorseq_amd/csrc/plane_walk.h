@@ -40,6 +40,19 @@ static inline jl_walk_shape jl_walk_shape_for(uint64_t n_reads, uint32_t n_group
     return s;
 }
 
+// the class-codon kernel's shape (kernels_class_codons.hip: groups of 64 positions, ceil(n_classes / 16) passes): segments x groups x
+// passes fill the chip twice over, 256 CUs x 3 workgroups (46 KB of LDS each).  n_reads > 0.
+static inline jl_walk_shape jl_class_codons_shape_for(uint64_t n_reads, uint32_t n_pos, uint32_t n_classes)
+{
+    const uint32_t n_groups = (n_pos + 63u) / 64u, full = n_classes / 16u;
+    const uint32_t n_tiles = jl_walk_tiles(n_reads);
+    const uint32_t segs = std::max(1u, std::min(n_tiles, 1536u / std::max(1u, n_groups * std::max(1u, full))));
+    jl_walk_shape s;
+    s.seg_tiles = (n_tiles + segs - 1u) / segs;
+    s.n_segs = (n_tiles + s.seg_tiles - 1u) / s.seg_tiles;
+    return s;
+}
+
 #if defined(__HIPCC__)
 #include "jl_internal.h"
 

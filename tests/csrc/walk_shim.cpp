@@ -14,3 +14,8 @@ extern "C" void shim_walk_shape(uint64_t n_reads, uint32_t n_groups, uint32_t *s
     const jl_walk_shape s = jl_walk_shape_for(n_reads, n_groups);
     *seg_tiles = s.seg_tiles, *n_segs = s.n_segs;
 }
+extern "C" void shim_class_codons_shape(uint64_t n_reads, uint32_t n_pos, uint32_t n_classes, uint32_t *seg_tiles, uint32_t *n_segs)
+{
+    const jl_walk_shape s = jl_class_codons_shape_for(n_reads, n_pos, n_classes);
+    *seg_tiles = s.seg_tiles, *n_segs = s.n_segs;
+}

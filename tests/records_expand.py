@@ -108,3 +108,39 @@ def expand_reference(rec, n_cols, win_begin=0, min_qv=0):
                 elif op in (1, 4):
                     q += 1
     return out
+
+
+def covered_pairs(rec, n_cols, win_begin=0):
+    """int64[n_cols]: at c >= 1 the reads whose cells at c - 1 and c are both covered (not code 6), from the cigars alone — no
+    matrix, so a deep window costs its ops, not its cells.  A read covers the columns of its D, = and X ops; they follow each
+    other without a hole unless an N op lies between.  So: pairs[c] = reads that cover c - reads of which a covered run BEGINS at c,
+    and a run begins at an op that covers something and is the read's first such op or follows an N.  (test_insertion_host.py
+    pins it against the matrix of expand_reference.)"""
+    pos, cigar, cig_off = (np.asarray(rec[k]) for k in ("pos", "cigar", "cig_off"))
+    words = cigar.astype(np.int64)
+    op, ln = words & 15, words >> 4
+    if (op == 0).any():
+        raise ValueError("cigar M")
+    n_ops = np.diff(cig_off.astype(np.int64))
+    rd = np.repeat(np.arange(len(pos)), n_ops)
+    keep = _REF_OPS[op] & (ln > 0)                                      # the ops that move along the reference
+    op, ln, rd = op[keep], ln[keep], rd[keep]
+    end = np.cumsum(ln)
+    first = np.ones(len(op), dtype=bool)
+    first[1:] = rd[1:] != rd[:-1]
+    base = np.maximum.accumulate(np.where(first, end - ln, 0))          # the cumulated length in front of the read's first op
+    a = end - ln - base + pos[rd].astype(np.int64) - win_begin
+    b = a + ln
+    covers = op != 3
+    begins = covers & (first | np.concatenate([[False], op[:-1] == 3]))
+    diff = np.zeros(n_cols + 1, dtype=np.int64)
+    lo, hi = np.clip(a[covers], 0, n_cols), np.clip(b[covers], 0, n_cols)
+    np.add.at(diff, lo, 1)
+    np.add.at(diff, hi, -1)
+    cov = np.cumsum(diff)[:n_cols]
+    starts = np.zeros(n_cols, dtype=np.int64)
+    at = a[begins & (b > a)]
+    np.add.at(starts, at[(at >= 1) & (at < n_cols)], 1)
+    out = cov - starts
+    out[0] = 0
+    return out

@@ -164,3 +164,81 @@ def test_merge_and_schedule_from_c99(tmp_path):
     out = subprocess.run([str(exe)], capture_output=True, text=True)
     assert out.returncode == 0, (out.returncode, out.stdout, out.stderr)
     assert out.stdout.strip() == "0:0:2304 1:1:2304 2:1:1152"
+
+
+# ---------------------------------------------------------------------------------------------- who reads the resident matrix
+# Every exported function is in exactly one of three lists.  A stage added later has to be classified here before the suite passes;
+# one that reads the resident matrix gets a test in tests/test_gpu_high_rows.py, where the matrix has plane rows on both sides of
+# 4 GiB, or a reason why it cannot take that matrix.
+READS_MATRIX = {                      # function -> the test of tests/test_gpu_high_rows.py that runs it on the tensor
+    "jl_run_async": "test_run_with_phasing", "jl_run_wait": "test_run_with_phasing", "jl_run_done": "test_run_with_phasing",
+    "jl_run_view_get": "test_run_with_phasing",
+    "jl_pileup_async": "test_stage_api_pileup_call_phase", "jl_pileup_fetch": "test_stage_api_pileup_call_phase",
+    "jl_consensus_fetch": "test_stage_api_pileup_call_phase", "jl_call_async": "test_stage_api_pileup_call_phase",
+    "jl_call_fetch": "test_stage_api_pileup_call_phase", "jl_phase_async": "test_stage_api_pileup_call_phase",
+    "jl_phase_fetch": "test_stage_api_pileup_call_phase", "jl_n_positions": "test_stage_api_pileup_call_phase",
+    "jl_pileup_kernel_name": "test_run_with_phasing",
+    "jl_control_call_async": "test_control_call", "jl_control_call_fetch": "test_control_call",
+    "jl_class_pileup_async": "test_class_pileup_and_consensus", "jl_class_pileup_fetch": "test_class_pileup_and_consensus",
+    "jl_class_codons_async": "test_class_codons", "jl_class_codons_fetch": "test_class_codons",
+    "jl_codon_deletions_async": "test_codon_deletions", "jl_codon_deletions_fetch": "test_codon_deletions",
+    "jl_deletion_alleles_async": "test_deletion_alleles", "jl_deletion_alleles_fetch": "test_deletion_alleles",
+    "jl_sites_assemble": "test_sites_assemble",
+    "jl_variant_linkage_async": "test_variant_linkage", "jl_variant_linkage_fetch": "test_variant_linkage",
+    "jl_phase_rescue_async": "test_rescue", "jl_phase_rescue_fetch": "test_rescue",
+    "jl_phase_nearest_async": "test_nearest", "jl_phase_nearest_fetch": "test_nearest",
+    "jl_phase_recombinants_async": "test_recombinant", "jl_phase_recombinants_fetch": "test_recombinant",
+    "jl_read_stats_async": "test_read_stats", "jl_read_stats_fetch": "test_read_stats",
+    "jl_read_hypermut_async": "test_read_hypermut", "jl_read_hypermut_fetch": "test_read_hypermut",
+    "jl_read_orf_async": "test_read_orf", "jl_read_orf_fetch": "test_read_orf",
+    "jl_msa_take": "test_take", "jl_msa_take_async": "test_take",
+    "jl_msa_download": "test_download",
+    "jl_msa_adopt": "test_a_plane_stride_of_4_gib_is_refused",
+    "jl_xwin_assemble_slice_local": "test_cross_window_pack_and_session",
+    "jl_xwin_create": "test_cross_window_pack_and_session", "jl_xwin_phase_sharded": "test_cross_window_pack_and_session",
+    "jl_xwin_read_hap_fetch": "test_cross_window_pack_and_session", "jl_xwin_destroy": "test_cross_window_pack_and_session",
+}
+READS_MATRIX_NOT_ON_THE_TENSOR = {    # function -> why tests/test_gpu_high_rows.py does not run it
+    "jl_msa_index_info": "an adopted matrix is never indexed (test_gpu_deviation_index.test_adopted_matrix_is_never_indexed)",
+    "jl_msa_download_planes": "one hipMemcpy of the whole allocation, no kernel and no row offset",
+    "jl_group_run_async": "the kernels of jl_run_async, launched for several contexts",
+    "jl_group_run_masked_async": "the kernels of jl_run_async, launched for several contexts",
+    "jl_group_time_pileup": "the pileup of jl_run_async in a timing loop", "jl_time_pileup": "the pileup of jl_run_async in a timing loop",
+    "jl_time_pileup_set": "the pileup of jl_run_async in a timing loop", "jl_time_run": "jl_run_async in a timing loop",
+    "jl_sites_assemble_alleles": "its source is a record build (the insertion events), which is never adopted",
+    "jl_xwin_assemble_local": "the pack kernel of jl_xwin_assemble_slice_local with whole columns at the windows' stride",
+    "jl_xwin_assemble_rccl": "the pack kernel of the local assembly; needs a communicator",
+    "jl_xwin_assemble_slice_rccl": "the pack kernel of the local assembly; needs a communicator",
+    "jl_phase_groups_async": "the key and grouping kernels of jl_phase_async over a slice", "jl_phase_groups_fetch": "fetch of the former",
+    "jl_phase_regroup": "reads the keys of jl_phase_groups_async, not the matrix rows by offset of its own",
+    "jl_insertions_fetch": "counters of a record build", "jl_insertion_alleles_fetch": "counters of a record build",
+    "jl_insertion_reads_fetch": "events of a record build",
+}
+READS_NO_MATRIX = [
+    "jl_abi_version", "jl_allgather_groups", "jl_allgather_variants", "jl_allgather_variants_async", "jl_allgather_variants_async_many",
+    "jl_allgather_variants_many", "jl_col_stride", "jl_comm_create", "jl_comm_create_inproc", "jl_comm_destroy", "jl_comm_info",
+    "jl_comm_unique_id", "jl_consensus_of_counts", "jl_control_eval", "jl_control_test", "jl_ctx_create", "jl_ctx_destroy", "jl_ctx_stream",
+    "jl_deletion_allele_test", "jl_deletion_test", "jl_device_count", "jl_expand_read_hap", "jl_fisher_eval", "jl_fisher_eval_tail",
+    "jl_group_create", "jl_group_destroy", "jl_group_exchange_bind", "jl_group_exchange_collect", "jl_group_last_error", "jl_group_views",
+    "jl_haplotype_recombinants", "jl_hypermut_eval", "jl_hypermut_filter", "jl_hypermut_test", "jl_insertion_test", "jl_last_error",
+    "jl_linkage_stats", "jl_merge_groups", "jl_merge_tables", "jl_mix_counts", "jl_orf_classify", "jl_orf_filter", "jl_plane_stride",
+    "jl_qmask_bytes", "jl_qmask_from_quals", "jl_read_filter", "jl_run_pileup_clock", "jl_run_pileup_ms", "jl_sample_reads",
+    "jl_select_haplotypes", "jl_strerror", "jl_sync", "jl_variant_table_device", "jl_xwin_last_error", "jl_xwin_plan", "jl_xwin_slice_plan",
+    "jl_xwin_stage_us",
+    # producers: they write the resident matrix and read none
+    "jl_msa_alloc", "jl_msa_upload", "jl_msa_pack_rows", "jl_msa_ingest_records", "jl_msa_ingest_records_masked", "jl_msa_track_insertions",
+    "jl_msa_track_insertion_alleles", "jl_msa_track_insertion_reads", "jl_records_begin", "jl_records_append", "jl_records_append_masked",
+    "jl_records_finish", "jl_records_drop", "jl_records_window", "jl_records_window_async", "jl_synth_fill", "jl_synth_fill_window",
+]
+
+
+def test_every_export_is_classified_as_a_reader_of_the_matrix_or_not():
+    lists = [list(READS_MATRIX), list(READS_MATRIX_NOT_ON_THE_TENSOR), READS_NO_MATRIX]
+    everything = [name for lst in lists for name in lst]
+    assert len(everything) == len(set(everything)), sorted(n for n in set(everything) if everything.count(n) > 1)
+    declared = _declared()
+    assert sorted(everything) == declared, (sorted(set(declared) - set(everything)), sorted(set(everything) - set(declared)))
+    text = open(os.path.join(ROOT, "tests", "test_gpu_high_rows.py")).read()
+    defined = set(re.findall(r"^def (test_[a-z0-9_]+)\(", text, flags=re.M))
+    assert set(READS_MATRIX.values()) <= defined, sorted(set(READS_MATRIX.values()) - defined)
+    assert all(reason for reason in READS_MATRIX_NOT_ON_THE_TENSOR.values())

@@ -114,6 +114,32 @@ def test_class_pileup_equals_numpy(ctx, n, l, k, name):
     assert (msa.unpack_columns(ctx.download_columns(), n) == rows).all()     # the matrix is untouched
 
 
+def test_segments_of_four_tiles():
+    """The smallest window at which a workgroup walks four tiles (jl_walk_shape_for: n_tiles * n_groups > 8192): 65 columns — two
+    groups, the second of one column — and 4097 tiles in 1025 segments, the last of one tile that ends inside it.  The rows
+    are a 1536-read block — three tiles, so that tiles t and t + 2 differ — repeated with a tail, the labels too; the counts are the block's times the repeats plus the
+    tail's (tests/test_walk_host.py holds that property)."""
+    import second_turn
+    import walk_shape
+    l, k = 65, 3
+    n, seg_tiles, n_segs = walk_shape.deep_case(lambda n: walk_shape.walk(n, (l + 63) // 64))
+    assert seg_tiles >= 4 and n_segs >= 2 and -(-n // 512) % seg_tiles != 0 and n % 512 == 300
+    block, lab = code_rows(1536, l, 11), labels("mixed", 1536, k, 5)
+    reps, tail = second_turn.split(n, 1536)
+    c, r = expected(block, lab, k)
+    tc, tr = expected(block[:tail], lab[:tail], k)
+    exp_counts, exp_reads = reps * c + tc, reps * r + tr
+    assert exp_counts[:, :, :6].any(axis=(0, 1)).all() and (exp_reads > 0).all() and tc.any()
+    j = capi.Juliet(0)
+    try:
+        second_turn.adopt_tiled(j, block, n)
+        counts, reads = j.class_pileup(second_turn.tiled(lab, n), k)
+        assert (reads == exp_reads).all()
+        assert (counts == exp_counts).all(), np.argwhere(counts != exp_counts)[:8]
+    finally:
+        j.close()
+
+
 def test_padding_behind_the_last_read_counts_nowhere(ctx):
     """1025 reads: 1023 read positions of padding in the second line of every plane row.  With every read in class 0 the
     counts are the whole-matrix counts and not one more."""

@@ -197,6 +197,33 @@ def test_record_build():
     j.close()
 
 
+def test_segments_of_four_tiles():
+    """The smallest window at which a workgroup of this kernel's own shape (jl_class_codons_shape_for) walks four tiles, so that the
+    prefetching schedule has an iteration with a tile before and a tile after: 4609 tiles in 1153 segments, the last of one tile that
+    ends inside it.  The rows are a 1536-read block — three tiles, so that tiles t and t + 2 differ — repeated with a tail, the labels too; the histograms are the block's
+    times the repeats plus the tail's (tests/test_walk_host.py holds that property)."""
+    import second_turn
+    import walk_shape
+    l, k = 12, 3
+    cols = starts(l)
+    n, seg_tiles, n_segs = walk_shape.deep_case(lambda n: walk_shape.class_codons(n, len(cols), k))
+    assert seg_tiles >= 4 and n_segs >= 2 and -(-n // 512) % seg_tiles != 0 and n % 512 == 300
+    block, lab = code_rows(1536, l, 11), labels("mixed", 1536, k, 5)
+    reps, tail = second_turn.split(n, 1536)
+    h, r = mirror.class_codons(block, lab, k, cols)
+    th, tr = mirror.class_codons(block[:tail], lab[:tail], k, cols)
+    exp_hist, exp_reads = (reps * h.astype(np.uint64) + th).astype(np.uint32), (reps * r.astype(np.uint64) + tr).astype(np.uint32)
+    assert int((reps * h.astype(np.uint64) + th).max()) < 2 ** 32 and (exp_hist.sum(axis=(1, 2)) > 0).all() and th.any()
+    j = capi.Juliet(0)
+    try:
+        second_turn.adopt_tiled(j, block, n)
+        hist, reads = j.class_codons(second_turn.tiled(lab, n), k, cols)
+        assert (reads == exp_reads).all()
+        assert (hist == exp_hist).all(), np.argwhere(hist != exp_hist)[:8]
+    finally:
+        j.close()
+
+
 def test_adopted_matrix_with_its_own_stride():
     """A torch tensor as the matrix: 2049 reads in planes of 272 bytes (the library's own stride, and that of the mask rows, is
     384), all ones in the bytes past the last read of every plane row — code 7 there, and bases once plane 2 is looked at alone.

@@ -14,7 +14,7 @@ import pytest
 import bam_py
 import insertion_mirror as im
 import records_expand
-from minorseq_amd import capi, msa
+from minorseq_amd import capi, msa, synth
 from test_insertion_host import HAND_ALLELES, HAND_FRAMESHIFT, HAND_READS, HAND_UNREAD
 
 pytestmark = pytest.mark.gpu
@@ -216,6 +216,39 @@ def test_counts_and_table_equal_mirror(ctx, n, n_cols):
     check(ctx, rec, n_cols)
     # the matrix is what a build without tracking makes
     assert (msa.unpack_columns(ctx.download_columns(), n) == records_expand.expand_reference(rec, n_cols, WB, 20)).all()
+
+
+def test_span_with_segments_of_four_tiles():
+    """The smallest read count at 3000 columns at which a workgroup of the span pass walks four tiles (jl_walk_shape_for with 47 groups
+    of 64 junctions: more than 174 tiles), so that its prefetching schedule has an iteration with a tile before and a tile after:
+    the last segment is shorter than the others and its last tile ragged.  Generated records with insertions, one read in three
+    partial; SPAN is the reads covered at c - 1 and at c, counted from the cigars (records_expand.covered_pairs, pinned against the
+    mirror's own statement of it in tests/test_insertion_host.py), compared for equality at every junction."""
+    import walk_shape
+    l = 3000
+    n_groups = (l - 1 + 63) // 64
+    n, seg_tiles, n_segs = walk_shape.deep_case(lambda n: walk_shape.walk(n, n_groups))
+    n_tiles = -(-n // 512)
+    assert n_groups == 47 and seg_tiles >= 4 and n_segs >= 2 and n_tiles % seg_tiles != 0 and n % 512 == 300
+    assert walk_shape.walk(n - 512, n_groups)[0] < 4                      # ... and one tile fewer has shorter segments
+    rec = synth.raw_records(9, n, l, extra=("--ins-ppm", "2500", "--partial", "0.3"))
+    exp_span = records_expand.covered_pairs(rec, l)                      # (from the cigars: the expected matrix never exists)
+    r0 = n - 600                                                          # ... and over the last two tiles from the matrix itself
+    cov = records_expand.expand(rec, l, 0, 0, read_begin=r0, read_end=n) != 6
+    tail = {k: rec[k] for k in ("seq4", "seq_off")}
+    tail.update(pos=rec["pos"][r0:], cig_off=rec["cig_off"][r0:] - rec["cig_off"][r0], cigar=rec["cigar"][int(rec["cig_off"][r0]):])
+    assert (records_expand.covered_pairs(tail, l)[1:] == (cov[:, :-1] & cov[:, 1:]).sum(axis=0)).all()
+    assert exp_span[0] == 0 and exp_span[1:].min() > 0 and len(np.unique(exp_span[1:])) > 100      # partial reads: the junctions differ
+    j = capi.Juliet(0)
+    try:
+        j.track_insertion_alleles()
+        j.ingest_records(l, 0, rec["pos"], rec["cigar"], rec["cig_off"], rec["seq4"], rec["seq_off"])
+        jcnt, rows = j.insertion_alleles()
+        assert jcnt.shape == (l, 4) and (jcnt[:, im.SPAN] == exp_span).all(), np.flatnonzero(jcnt[:, im.SPAN] != exp_span)[:8]
+        assert jcnt[:, im.INFRAME].any() and jcnt[:, im.FRAMESHIFT].any()
+        assert (jcnt[:, 1:].astype(np.int64).sum(axis=1) <= jcnt[:, im.SPAN]).all()
+    finally:
+        j.close()
 
 
 @pytest.mark.parametrize("form,min_qv", [("bytes", 0), ("bytes", 20), ("mask", 0), ("mask", 20), ("chunks", 20)])

@@ -12,6 +12,7 @@ import pytest
 
 import nearest_mirror
 import rescue_mirror
+import second_turn as st
 from minorseq_amd import capi, msa, synth
 
 pytestmark = pytest.mark.gpu
@@ -170,6 +171,48 @@ def test_nearest_equals_mirror(ctx, n, vp, n_hap, d_budget, min_positions, held)
     ctx.upload_rows(rows, win_begin=3)
     check(ctx, rows, pos_cols, pattern, k, d_budget, exp)
     assert (msa.unpack_columns(ctx.download_columns(), n) == rows).all()     # the matrix is untouched
+
+
+# (positions, haplotypes): two chunks of haplotypes at few positions, two tiles of positions at few haplotypes; D = 3
+SECOND_TURN_SHAPES = [(5, 65), (65, 2)]
+SECOND_TURN_D = 3
+
+
+def second_turn_block(vp, n_hap):
+    """The 2049-read case of this file's builder at the shape, cut to the block of st.BLOCK reads; (block, pos_cols, pattern)."""
+    rows, pos_cols, pattern = make_case(2049, vp, n_hap, SECOND_TURN_D, seed_of(2049, vp, n_hap, SECOND_TURN_D))
+    return rows[:st.BLOCK], pos_cols, pattern
+
+
+def second_turn_expectation(block, pos_cols, pattern, n):
+    """(nearest, dist, hap_reads, tally) of the n tiled reads from the mirror over the block and over the tail."""
+    whole = nearest_mirror.nearest(block, pos_cols, pattern, 1, SECOND_TURN_D)
+    tail = nearest_mirror.nearest(block[:st.split(n)[1]], pos_cols, pattern, 1, SECOND_TURN_D)
+    return st.tiled(whole[0], n), st.tiled(whole[1], n), st.summed(whole[2], tail[2], n, st.BLOCK), st.summed(whole[3], tail[3], n, st.BLOCK)
+
+
+@pytest.mark.parametrize("vp,n_hap", SECOND_TURN_SHAPES)
+@pytest.mark.parametrize("n,what", st.COUNTS)
+def test_a_workgroups_second_turn(n, what, vp, n_hap):
+    """More than 4096 runs: a workgroup walks a second run — its distances and `informative` start again, its histogram and tallies
+    are carried into one flush.  The rows are the block repeated (tests/second_turn.py)."""
+    block, pos_cols, pattern = second_turn_block(vp, n_hap)
+    exp = second_turn_expectation(block, pos_cols, pattern, n)
+    assert int(exp[3].sum()) == n
+    if n - st.ONE_TURN > 1:                                 # all four categories and every distance among the reads of the second turns
+        late, late_d = exp[0][st.second_turn_reads(n)], exp[1][st.second_turn_reads(n)]
+        assert (late < n_hap).any() and (late == AMB).any() and (late == NONE).any() and (late == U).any()
+        assert set(late_d[late < n_hap].tolist()) == set(range(SECOND_TURN_D + 1))
+    j = capi.Juliet(0)
+    try:
+        st.adopt_tiled(j, block, n)
+        out = j.phase_nearest(pos_cols, pattern, 1, SECOND_TURN_D)
+        assert out["nearest"].shape == (n,) and (out["nearest"] == exp[0]).all(), np.flatnonzero(out["nearest"] != exp[0])[:8]
+        assert (out["dist"] == exp[1]).all(), np.flatnonzero(out["dist"] != exp[1])[:8]
+        assert (out["hap_reads"] == exp[2]).all() and (out["tally"] == exp[3]).all()
+        assert int(out["tally"].sum()) == n
+    finally:
+        j.close()
 
 
 def test_the_counter_saturates(ctx):

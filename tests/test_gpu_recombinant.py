@@ -13,6 +13,7 @@ import pytest
 import nearest_mirror
 import recombinant_mirror as rm
 import rescue_mirror
+import second_turn as st
 from minorseq_amd import capi, msa, synth
 
 pytestmark = pytest.mark.gpu
@@ -183,6 +184,47 @@ def test_recombinants_equal_mirror(ctx, n, vp, n_hap, min_positions, held):
     ctx.upload_rows(rows, win_begin=3)
     check(ctx, rows, pos_cols, pattern, k, exp)
     assert (msa.unpack_columns(ctx.download_columns(), n) == rows).all()     # the matrix is untouched
+
+
+# (positions, haplotypes): two chunks of haplotypes at few positions, two tiles of positions at few haplotypes
+SECOND_TURN_SHAPES = [(5, 65), (65, 2)]
+
+
+def second_turn_block(vp, n_hap):
+    """The 2049-read case of this file's builder at the shape, cut to the block of st.BLOCK reads; (block, pos_cols, pattern)."""
+    rows, pos_cols, pattern = make_case(2049, vp, n_hap, 1000 * 2049 + 7 * vp + n_hap)
+    return rows[:st.BLOCK], pos_cols, pattern
+
+
+def second_turn_expectation(block, pos_cols, pattern, n):
+    """The dict of the n tiled reads from the mirror over the block and over the tail."""
+    whole = rm.recombinants(block, pos_cols, pattern, 1)
+    tail = rm.recombinants(block[:st.split(n)[1]], pos_cols, pattern, 1)
+    exp = {key: st.tiled(whole[key], n) for key in ("left", "right", "prefix", "suffix")}
+    exp.update({key: st.summed(whole[key], tail[key], n, st.BLOCK) for key in ("parent_reads", "tally")})
+    return exp
+
+
+@pytest.mark.parametrize("vp,n_hap", SECOND_TURN_SHAPES)
+@pytest.mark.parametrize("n,what", st.COUNTS)
+def test_a_workgroups_second_turn(n, what, vp, n_hap):
+    """More than 4096 runs: a workgroup walks a second run — both walks' verdicts and `informative` start again, its parent counts and
+    tallies are carried into one flush.  The rows are the block repeated (tests/second_turn.py)."""
+    block, pos_cols, pattern = second_turn_block(vp, n_hap)
+    exp = second_turn_expectation(block, pos_cols, pattern, n)
+    assert int(exp["tally"].sum()) == n
+    if n - st.ONE_TURN > 1:                                 # every outcome the shape can hold among the reads of the second turns
+        late = {key: exp[key][st.second_turn_reads(n)] for key in ("left", "right")}
+        assert all(o in outcomes(late, n_hap) for o in "BWNU"), outcomes(late, n_hap)
+    j = capi.Juliet(0)
+    try:
+        st.adopt_tiled(j, block, n)
+        out = j.phase_recombinants(pos_cols, pattern, 1)
+        for key in KEYS:
+            assert out[key].shape == exp[key].shape and (out[key] == exp[key]).all(), key
+        assert int(out["tally"].sum()) == n
+    finally:
+        j.close()
 
 
 def test_the_index_does_not_wrap_or_truncate(ctx):

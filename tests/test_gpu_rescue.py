@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import rescue_mirror
+import second_turn as st
 from minorseq_amd import capi, msa, synth
 
 pytestmark = pytest.mark.gpu
@@ -128,6 +129,45 @@ def test_adopted_matrix_with_its_own_stride():
     check(j, rows, pos_cols, pattern, 1, all_four=True)
     check(j, rows, pos_cols[:3], pattern[:2, :3], 3)
     j.close()
+
+
+# (positions, haplotypes): two chunks of haplotypes at few positions, two tiles of positions at few haplotypes
+SECOND_TURN_SHAPES = [(5, 65), (65, 2)]
+
+
+def second_turn_block(vp, n_hap):
+    """The 2049-read case of this file's builder at the shape, cut to the block of st.BLOCK reads; (block, pos_cols, pattern)."""
+    rows, pos_cols, pattern = make_case(2049, vp, n_hap, 1000 * 2049 + 7 * vp + n_hap)
+    return rows[:st.BLOCK], pos_cols, pattern
+
+
+def second_turn_expectation(block, pos_cols, pattern, n):
+    """(rescue, hap_reads, tally) of the n tiled reads from the mirror over the block and over the tail."""
+    whole = rescue_mirror.rescue(block, pos_cols, pattern, 1)
+    tail = rescue_mirror.rescue(block[:st.split(n)[1]], pos_cols, pattern, 1)
+    return st.tiled(whole[0], n), st.summed(whole[1], tail[1], n, st.BLOCK), st.summed(whole[2], tail[2], n, st.BLOCK)
+
+
+@pytest.mark.parametrize("vp,n_hap", SECOND_TURN_SHAPES)
+@pytest.mark.parametrize("n,what", st.COUNTS)
+def test_a_workgroups_second_turn(n, what, vp, n_hap):
+    """More than 4096 runs: a workgroup walks a second run — its verdicts and `informative` start again, its histogram and tallies
+    are carried into one flush.  The rows are the block repeated (tests/second_turn.py)."""
+    block, pos_cols, pattern = second_turn_block(vp, n_hap)
+    exp_rescue, exp_reads, exp_tally = second_turn_expectation(block, pos_cols, pattern, n)
+    assert int(exp_tally.sum()) == n
+    if n - st.ONE_TURN > 1:                                 # all four categories among the reads of the second turns
+        late = exp_rescue[st.second_turn_reads(n)]
+        assert (late < n_hap).any() and (late == rescue_mirror.AMBIGUOUS).any() and (late == rescue_mirror.NONE).any() and (late == rescue_mirror.UNINFORMATIVE).any()
+    j = capi.Juliet(0)
+    try:
+        st.adopt_tiled(j, block, n)
+        out = j.phase_rescue(pos_cols, pattern, 1)
+        assert out["rescue"].shape == (n,) and (out["rescue"] == exp_rescue).all(), np.flatnonzero(out["rescue"] != exp_rescue)[:8]
+        assert (out["hap_reads"] == exp_reads).all() and (out["tally"] == exp_tally).all()
+        assert int(out["tally"].sum()) == n
+    finally:
+        j.close()
 
 
 def test_repeat_on_one_context(ctx):

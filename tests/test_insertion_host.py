@@ -234,3 +234,18 @@ def test_cli_refused_with_batch_as_fuse_and_the_rate_alone(tmp_path):
         r = juliet(tmp_path, "--call-insertions", "--insertion-rate", bad, "no_such.bam", "o.json")
         assert r.returncode == 1 and "--insertion-rate" in r.stderr
     assert sorted(p.name for p in tmp_path.iterdir()) == ["l.tsv"]
+
+
+def test_covered_pairs_from_the_cigars_are_the_matrix_own():
+    """records_expand.covered_pairs — what the deep span case of tests/test_gpu_insertions.py expects — against SPAN as the mirror
+    states it on the expanded matrix: generated reads with every kind of op (N beside an insertion, D, clips, reads that begin
+    before the window and end behind it), windows that begin inside the reads."""
+    import records_expand
+    from test_gpu_insertions import WB, make_reads
+    for n, n_cols, wb in ((300, 40, WB), (257, 130, WB), (64, 2, WB), (500, 25, WB + 9), (33, 64, WB - 2)):
+        rec = im.records(make_reads(n, max(n_cols, 5), 7 * n + n_cols), with_qual=True)
+        m = records_expand.expand_reference(rec, n_cols, wb, 0)
+        exp = np.zeros(n_cols, dtype=np.int64)
+        exp[1:] = ((m[:, :-1] != 6) & (m[:, 1:] != 6)).sum(axis=0)
+        assert (records_expand.covered_pairs(rec, n_cols, wb) == exp).all(), (n, n_cols, wb)
+        assert exp.any() == (n_cols > 1) and (n_cols < 5 or len(set(exp[1:].tolist())) > 1)

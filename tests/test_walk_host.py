@@ -5,7 +5,11 @@ import ctypes as C
 import os
 import subprocess
 
+import numpy as np
 import pytest
+
+import class_codons_mirror
+import walk_shape
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -66,3 +70,54 @@ def test_walk_shape(shim):
     # 2049 reads are five tiles in three segments
     shim.shim_walk_shape(2049, 1, C.byref(seg_tiles), C.byref(n_segs))
     assert (seg_tiles.value, n_segs.value) == (2, 3)
+
+
+# ---------------------------------------------------------------------------------------------- segments of four tiles and more
+def class_codons_rule(n_reads, n_pos, n_classes):
+    """The shape as kernels_class_codons.hip had it inline."""
+    n_tiles = -(-n_reads // 512)
+    n_groups, full = (n_pos + 63) // 64, n_classes // 16
+    segs = max(1, min(n_tiles, 1536 // max(1, n_groups * max(1, full))))
+    seg_tiles = (n_tiles + segs - 1) // segs
+    return seg_tiles, (n_tiles + seg_tiles - 1) // seg_tiles
+
+
+def test_class_codons_shape():
+    for n_reads in (1, 512, 513, 2049, 100000, 2359596, 2**31 - 1):
+        for n_pos, n_classes in ((1, 1), (10, 3), (64, 15), (65, 16), (130, 704), (4096, 33)):
+            st, ns = walk_shape.class_codons(n_reads, n_pos, n_classes)
+            n_tiles = -(-n_reads // 512)
+            assert st >= 1 and ns * st >= n_tiles and (ns - 1) * st < n_tiles
+            assert (st, ns) == class_codons_rule(n_reads, n_pos, n_classes)
+
+
+def test_the_deep_cases_are_the_smallest_with_segments_of_four_tiles():
+    """What tests/test_gpu_class.py and tests/test_gpu_class_codons.py run: n_tiles * n_groups > 8192 for the shared shape, n_tiles >
+    3 * 1536 for the class codons' own; the last segment shorter than the others, the last tile ragged."""
+    n, st, ns = walk_shape.deep_case(lambda n: walk_shape.walk(n, 2))
+    n_tiles = -(-n // 512)
+    assert (st, ns) == (4, 1025) and n_tiles == 4097 and n_tiles * 2 > 8192 and n % 512 == 300 and n_tiles % st == 1
+    assert walk_shape.walk(n - 512, 2)[0] == 2                                   # one tile fewer: segments of two
+    n, st, ns = walk_shape.deep_case(lambda n: walk_shape.class_codons(n, 10, 3))
+    n_tiles = -(-n // 512)
+    assert (st, ns) == (4, 1153) and n_tiles == 4609 and n % 512 == 300 and n_tiles % st == 1
+    assert walk_shape.class_codons(n - 512, 10, 3)[0] == 3
+
+
+def test_counts_are_additive_over_reads():
+    """The expectation of the deep cases: for rows that are a block repeated with a tail, and labels repeated the same way, the class
+    pileup and the class codons are the block's counts times the repeats plus the tail's — against the numpy rules run in full."""
+    from test_gpu_class import code_rows, expected, labels
+    import second_turn
+    block, lab = code_rows(1536, 65, 11), labels("mixed", 1536, 3, 5)
+    n = 3 * 1536 + 300
+    rows, labs = second_turn.tiled_rows(block, n), second_turn.tiled(lab, n)
+    full_c, full_r = expected(rows, labs, 3)
+    c, r = expected(block, lab, 3)
+    tc, tr = expected(block[:300], lab[:300], 3)
+    assert (full_c == 3 * c + tc).all() and (full_r == 3 * r + tr).all() and full_c.any()
+    cols = np.arange(63, dtype=np.uint32)
+    full_h, full_r = class_codons_mirror.class_codons(rows, labs, 3, cols)
+    h, r = class_codons_mirror.class_codons(block, lab, 3, cols)
+    th, tr = class_codons_mirror.class_codons(block[:300], lab[:300], 3, cols)
+    assert (full_h == 3 * h + th).all() and (full_r == 3 * r + tr).all() and full_h.any()
