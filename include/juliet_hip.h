@@ -978,16 +978,17 @@ int jl_group_time_pileup(jl_group *const *groups, uint32_t n_groups, uint32_t re
 /* The deviation index of a context's resident matrix: a structure the library derives from the planes of a window that is run
  * again and again — per plain codon chunk, the reads that differ from the column majority — and counts from instead of the planes
  * from the third run on.  Results never depend on it (docs/SPEC.md); this call only observes it.
- *   state           0 none, 1 a build is enqueued, 2 built, 3 refused (no chunk's list would take at most half of the chunk's
- *                   plane bytes: every chunk is counted faster from the planes)
+ *   state           0 none, 1 a build is enqueued, 2 built, 3 refused (no chunk's list would have at most 9 plane_stride / 8
+ *                   entries, one per eight of the chunk's plane bytes: every chunk is counted from the planes)
  *   generation      of the matrix: every producer that rewrites the matrix starts a new one, with no index and run counter 0
  *   runs            runs enqueued on this generation and chunk table (jl_run_async, jl_group_run(_masked)_async, jl_pileup_async)
  *   builds          index builds this context has enqueued over its life
  *   last_form       1: the last enqueued run counted from the index, 0: from the planes
  *   plain_chunks    chunks the index covers at most; indexed_chunks: those that have a list; entries: reads in all lists
- *   bytes           device memory of the entry buffer (allocated at its bound before the build)
+ *   bytes           device memory of the entry buffer (allocated at its bound before the build; an entry is 2 bytes: a deviating
+ *                   read's three codes, not its number)
  * Cost: a window's SECOND run on a matrix and chunk table allocates the entry buffer at its bound (9 plane_stride / 8 entries per
- * plain chunk: 56 MB for 100 000 reads x 3 000 columns) and uploads two small tables with one stream synchronisation before it is
+ * plain chunk: 28 MB for 100 000 reads x 3 000 columns) and uploads two small tables with one stream synchronisation before it is
  * enqueued — once per matrix generation; a caller whose second run is latency-critical sees that run some hundred microseconds late.
  * wait != 0: a build that is enqueued is waited for first.  chunk_flags (optional, room for cap_chunks >= the chunk table's length;
  * implies wait): per chunk of the pileup's chunk table 0 = counted from the planes (not a plain chunk, or no index), 1 = has a

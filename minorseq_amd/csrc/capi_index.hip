@@ -132,7 +132,7 @@ extern "C" int jl_msa_index_info(jl_ctx *ctx, jl_index_info *info, int wait, uin
         info->entries = ctx->h_ix[1];
         info->indexed_chunks = ctx->h_ix[2];
     }
-    info->bytes = ctx->ix_reserved ? (uint64_t)ctx->d_ix_entries.cap * 4u : 0u;
+    info->bytes = ctx->ix_reserved ? (uint64_t)ctx->d_ix_entries.cap * JL_IX_ENTRY_BYTES : 0u;
     if (chunk_flags) {
         if (!ctx->plan_valid || cap_chunks < ctx->n_chunks) return jl_fail(ctx, JL_ERR_ARG, "jl_msa_index_info: %u chunks, room for %u", ctx->n_chunks, cap_chunks);
         memset(chunk_flags, 0, ctx->n_chunks);

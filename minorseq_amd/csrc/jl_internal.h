@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/juliet_hip.h"
+#include "deviation_index.h"
 #include "jl_synth.h"
 
 // The environment: the library reads these four switches and no other, each once (jl_env, kernels_util.hip).
@@ -266,7 +267,7 @@ struct jl_win_index {
     uint64_t plane_stride;
     uint32_t n_reads, n_plain;   // n_plain = workgroups of the window's own grid
     const uint4 *tab;            // [n_plain] {first column, first entry, entries (all ones: not indexed), -}
-    const uint32_t *entries;
+    const jl_ix_stored_t *entries;   // 16-bit stored entries; tab[].y counts in entries
     const uint8_t *seed;         // [n_cols] the index seed
     uint32_t *counts, *hist;
 };
@@ -1051,7 +1052,7 @@ struct jl_ctx {
     std::vector<uint64_t> h_chunks;    // host copy of the chunk table (build_plan)
     jl_dev_array<uint4> d_ix_tab;      // [ix_n_plain] jl_win_index::tab
     jl_dev_array<uint64_t> d_ix_rest;  // [ix_n_rest] chunk records of the chunks that are not plain: the plane kernel's table of an index-form run
-    jl_dev_array<uint32_t> d_ix_entries;
+    jl_dev_array<jl_ix_stored_t> d_ix_entries;   // jl_ix_alloc_entries(...) stored entries, JL_IX_ENTRY_BYTES each
     jl_dev_array<uint8_t> d_ix_seed;   // [n_cols]
     jl_dev_array<uint32_t> d_ix_rec;   // [8] the build's record on the device; [4..] cursors of the build
     event_slot ix_ev;                  // behind the build's last kernel: whoever drops the index waits for it

@@ -6,8 +6,9 @@
 // matrix generation in force.  The build is five launches on the stream of the run it follows, no host round trip in between:
 //   seed     the exact majority base among A C G T of every column (ties: the lowest code) — a property of the cells alone
 //   count    per plain chunk, the reads that differ from the seed in some column: popcount of x | inv, as the plane kernel forms them
-//   scan     which chunks stay under the density bound, their offsets (a list begins on 16 bytes), the total against its bound
-//   fill     the entries: a wave's lanes take consecutive positions (prefix over the lanes), one atomic per wave and step for the place
+//   scan     which chunks stay under the density bound, their offsets in entries (a list begins on four entries = 8 bytes), the
+//            total against its bound
+//   fill     the entries, stored as their 16 code bits (jl_ix_stored): a wave's lanes take consecutive positions (prefix over the lanes), one atomic per wave and step for the place
 //   publish  the record into the pinned block: state, entries, indexed chunks, generation
 // The buffer is allocated before the build at the bound (jl_ix_alloc_entries), so the pointers a captured graph bakes in are known
 // when the build is enqueued.
@@ -146,7 +147,7 @@ __global__ __launch_bounds__(256) void ix_scan_kernel(uint4 *__restrict__ tab, u
 // grid (plain chunks, read splits): the entries of every indexed chunk
 __global__ __launch_bounds__(256) void ix_fill_kernel(const uint8_t *__restrict__ planes, uint64_t plane_stride, uint64_t n_reads,
                                                       const uint8_t *__restrict__ seed, uint4 *__restrict__ tab, const uint32_t *__restrict__ rec,
-                                                      uint32_t *__restrict__ entries)
+                                                      jl_ix_stored_t *__restrict__ entries)
 {
     const uint32_t p = blockIdx.x, tid = threadIdx.x, lane = tid & 63u;
     if (rec[0] != JL_IX_BUILT) return;
@@ -186,7 +187,8 @@ __global__ __launch_bounds__(256) void ix_fill_kernel(const uint8_t *__restrict_
 #pragma unroll
                 for (int j = 0; j < 3; ++j)
                     code[j] = (((t.d[j][2][q] >> b) & 1u) << 2) | (((t.d[j][1][q] >> b) & 1u) << 1) | ((t.d[j][0][q] >> b) & 1u);
-                if (at < end) entries[at] = jl_ix_encode((u * 4u + (uint32_t)q) * 32u + b, code[0], code[1], code[2]);
+                // (the entry names its read while it is formed; what is stored is its codes: deviation_index.h)
+                if (at < end) entries[at] = jl_ix_stored(jl_ix_encode((u * 4u + (uint32_t)q) * 32u + b, code[0], code[1], code[2]));
                 ++at;
             }
         }

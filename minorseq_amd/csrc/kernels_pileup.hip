@@ -363,16 +363,18 @@ __global__ __launch_bounds__(256) void pileup_fold_group_kernel(jl_pileup_fold_g
 // ------------------------------------------------------------------------------- counting from the deviation index
 // A resident window that is run again and again keeps, per plain codon chunk, the list of the reads that differ from the chunk's
 // index seed anywhere in its three columns (deviation_index.h; built by kernels_index.hip behind the window's second run): about
-// 6 % of the reads of a CCS sample, 4 bytes each, against nine plane rows.  One workgroup per plain chunk:
-//   * a lane streams four entries per round with one 16-byte non-temporal load, DEPTH rounds held in registers: the loads of the
-//     first DEPTH rounds all go out before the first is consumed, and each register is loaded with round r + DEPTH as round r
-//     leaves it.  DEPTH = 1 in the unfolded kernels, which hide the chain of round trips behind eight workgroups per CU and must
-//     keep the registers for that; DEPTH = JL_IX_FOLD_DEPTH = 8 in the folded ones, whose Fisher epilogue leaves five workgroups
-//     per CU (JL_IX_FOLD_WAVES) whatever the walk needs: 32 KB per workgroup in flight, a benchmark chunk's whole list (25 KB) in
-//     one round trip;
+// 6 % of the reads of a CCS sample, 2 bytes each (the three codes; the read number is not stored), against nine plane rows.  One
+// workgroup per plain chunk:
+//   * a lane streams four entries per round with one 8-byte non-temporal load, two entries to a dword, DEPTH rounds held in
+//     registers: the loads of the first DEPTH rounds all go out before the first is consumed, and each register is loaded with
+//     round r + DEPTH as round r leaves it.  DEPTH = JL_IX_DEPTH = 2 in the unfolded kernels, which hide the chain of round trips
+//     behind eight workgroups per CU and must keep the registers for that: 4 KB per workgroup in flight, a benchmark chunk's list
+//     (12.6 KB) in 3.1 dependent round trips; DEPTH = JL_IX_FOLD_DEPTH = 16 in the folded ones, whose Fisher epilogue leaves five
+//     workgroups per CU (JL_IX_FOLD_WAVES) whatever the walk needs: 32 KB per workgroup in flight, a benchmark chunk's whole list
+//     in one round trip;
 //   * column counts: per lane one 64-bit accumulator per column with a 9-bit field per code 0..6 — at most JL_IX_FLUSH_ROUNDS
-//     rounds x 4 entries = 508 <= 511 per field between flushes (whole batches of DEPTH rounds: 127 rounds at depth 1, 120 at
-//     depth 8); a flush unpacks them two to a register (64 lanes x 508 < 2^16), sums over the wave by DPP and adds to LDS, as the
+//     rounds x 4 entries = 508 <= 511 per field between flushes (whole batches of DEPTH rounds: 126 rounds at depth 2, 112 at
+//     depth 16); a flush unpacks them two to a register (64 lanes x 508 < 2^16), sums over the wave by DPP and adds to LDS, as the
 //     plane kernel does;
 //   * an entry whose three codes are all bases is a valid codon other than the seed codon (it differs somewhere): one LDS atomic;
 //     an entry with a code >= 4 is outside the coverage, as `inv` says in the plane kernel;
@@ -382,35 +384,34 @@ __global__ __launch_bounds__(256) void pileup_fold_group_kernel(jl_pileup_fold_g
 // walk — few registers, no prefetch: the path is rare and must not cost the common one its occupancy.
 // Registers (gfx950, the compiler's kernel-resource-usage remarks): pileup_index_kernel and pileup_index_group_kernel 58 VGPRs,
 // eight waves per SIMD, no scratch; pileup_index_fold_kernel and pileup_index_fold_group_kernel 96 VGPRs, five waves per SIMD, 128
-// bytes of scratch a lane, at depth 8 as at depth 2 (without a bound: 132, three waves — the epilogue sets the figure, the walk
-// stays under 60).  tests/test_fold_budget_resources.py pins these.  The plane path's 154 are why index and plane counting are
+// bytes of scratch a lane, at depth 16 as at depth 8, and the unfolded ones' 58 at depth 1, 2 and 4 alike (without a bound the
+// folded ones take 132, three waves — the epilogue sets the figure, the walk stays under 60).  tests/test_fold_budget_resources.py pins these.  The plane path's 154 are why index and plane counting are
 // separate kernels.
-#ifndef JL_IX_FOLD_DEPTH
-#define JL_IX_FOLD_DEPTH 8
-#endif
 // The folded index kernels' register budget, as waves per SIMD (__launch_bounds__): 5 = 96 VGPRs, five workgroups per CU.  What does
 // not fit is the Fisher stage's (its FP64 constants, which the compiler hoists out of the loop over a column's positions): the
 // spill's stores and loads all lie behind the barrier that closes the walk, in the one wave that evaluates.  The sweep of 3 / 4 / 5
-// waves against depth 8 / 4 / 2 is in profiles/fold_budget/: depth 8 is ahead at every budget, so the depth does not follow the budget.
+// waves against depth 8 / 4 / 2 (of 16-byte rounds, the 4-byte entry of the day) is in profiles/fold_budget/: the deepest is ahead at
+// every budget, so the depth does not follow the budget.  The depths of the 8-byte rounds: profiles/narrow_index/.
 #ifndef JL_IX_FOLD_WAVES
 #define JL_IX_FOLD_WAVES 5
 #endif
 template <int DEPTH>
-__device__ __forceinline__ void index_stream(const uint32_t JL_AS1 *list, uint32_t E, uint32_t (*s_hist)[64], uint32_t (*s_col)[6])
+__device__ __forceinline__ void index_stream(const jl_ix_stored_t JL_AS1 *list, uint32_t E, uint32_t (*s_hist)[64], uint32_t (*s_col)[6])
 {
-    static_assert(DEPTH >= 1 && DEPTH <= 8, "rounds held in registers");
-    // rounds between two flushes: whole batches, at most JL_IX_FLUSH_ROUNDS (127 at depth 1, 120 at depth 8: 480 <= 511 per field)
-    constexpr uint32_t FLUSH_BATCHES = JL_IX_FLUSH_ROUNDS / (uint32_t)DEPTH;
+    static_assert(DEPTH >= 1 && DEPTH <= (int)JL_IX_MAX_DEPTH, "rounds held in registers");
+    // rounds between two flushes: whole batches, at most JL_IX_FLUSH_ROUNDS (126 at depth 2, 112 at depth 16: 448 <= 511 per field)
+    constexpr uint32_t FLUSH_BATCHES = jl_ix_flush_rounds_at((uint32_t)DEPTH) / (uint32_t)DEPTH;
     static_assert(FLUSH_BATCHES >= 1u && FLUSH_BATCHES * (uint32_t)DEPTH <= JL_IX_FLUSH_ROUNDS, "a 9-bit field never above 511");
+    static_assert(sizeof(jl_ix_stored_t) * JL_IX_ROUND_ENTRIES == sizeof(u32x2), "a lane's round is one 8-byte load");
     const uint32_t tid = threadIdx.x;
     const bool last_lane = (tid & 63u) == 63u;
-    const u32x4 JL_AS1 *src = (const u32x4 JL_AS1 *)list;
+    const u32x2 JL_AS1 *src = (const u32x2 JL_AS1 *)list;   // (a list begins on four entries: jl_ix_padded)
     const uint32_t n_rounds = (E + 4u * 256u - 1u) / (4u * 256u);
-    // buf[k]: this lane's four entries of round r + k — the first batch's loads all go out before the first is consumed
-    u32x4 buf[DEPTH];
+    // buf[k]: this lane's four entries of round r + k, two to a dword — the first batch's loads all go out before the first is consumed
+    u32x2 buf[DEPTH];
 #pragma unroll
     for (int k = 0; k < DEPTH; ++k) {
-        buf[k] = u32x4{0u, 0u, 0u, 0u};
+        buf[k] = u32x2{0u, 0u};
         if (((uint32_t)k * 256u + tid) * 4u < E) buf[k] = __builtin_nontemporal_load(src + (size_t)k * 256u + tid);
     }
     uint32_t r = 0;
@@ -423,12 +424,13 @@ __device__ __forceinline__ void index_stream(const uint32_t JL_AS1 *list, uint32
 #pragma unroll
             for (int k = 0; k < DEPTH; ++k) {
                 if (r + (uint32_t)k >= n_rounds) break;                  // (uniform: the batch's later rounds are past the list too)
-                const u32x4 cur = buf[k];
+                const u32x2 cur = buf[k];
                 const uint32_t first = ((r + (uint32_t)k) * 256u + tid) * 4u;   // this lane's first entry of the round
                 // the register is free: round r + k + DEPTH goes out into it, DEPTH - 1 younger loads still in flight
                 const uint32_t nfirst = first + (uint32_t)DEPTH * 4u * 256u;
                 if (nfirst < E) buf[k] = __builtin_nontemporal_load(src + (size_t)(r + (uint32_t)k + (uint32_t)DEPTH) * 256u + tid);
-                const uint32_t e4[4] = {cur.x, cur.y, cur.z, cur.w};
+                // (a stored entry's upper seven bits are zero: the high half of a dword needs no mask)
+                const uint32_t e4[4] = {cur.x & 0xFFFFu, cur.x >> 16, cur.y & 0xFFFFu, cur.y >> 16};
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     if (first + (uint32_t)i >= E) continue;
@@ -523,7 +525,7 @@ __device__ __forceinline__ void index_dense_stream(const uint8_t JL_AS1 *planes,
 
 template <bool FOLD>
 __device__ __forceinline__ void pileup_index_body(const uint8_t JL_AS1 *planes, uint64_t plane_stride, uint32_t n_reads, const uint4 JL_AS1 *tab,
-                                                  const uint32_t JL_AS1 *entries, const uint8_t JL_AS1 *seed, uint32_t JL_AS1 *counts,
+                                                  const jl_ix_stored_t JL_AS1 *entries, const uint8_t JL_AS1 *seed, uint32_t JL_AS1 *counts,
                                                   uint32_t JL_AS1 *hist, const jl_win_fold *fold)
 {
     __shared__ uint32_t s_hist[3][64];
@@ -538,7 +540,7 @@ __device__ __forceinline__ void pileup_index_body(const uint8_t JL_AS1 *planes, 
     if (tid < 3) s_match[tid] = 0;
     __syncthreads();
     if (rec.z != 0xFFFFFFFFu) {
-        index_stream<FOLD ? JL_IX_FOLD_DEPTH : 1>(entries + rec.y, rec.z, s_hist, s_col);
+        index_stream<FOLD ? JL_IX_FOLD_DEPTH : JL_IX_DEPTH>(entries + rec.y, rec.z, s_hist, s_col);
         if (tid < 3) atomicAdd(&s_col[tid][g[tid]], n_reads - rec.z);   // the reads not in the list: the seed base in every column
         if (tid == 3) s_match[0] = n_reads - rec.z;                     // ... and the seed codon
     } else {
@@ -550,7 +552,7 @@ __device__ __forceinline__ void pileup_index_body(const uint8_t JL_AS1 *planes, 
 
 #define JL_INDEX_BODY(FOLD, w, f)                                                                                                     \
     pileup_index_body<FOLD>((const uint8_t JL_AS1 *)(w).msa, (w).plane_stride, (w).n_reads, (const uint4 JL_AS1 *)(w).tab,            \
-                            (const uint32_t JL_AS1 *)(w).entries, (const uint8_t JL_AS1 *)(w).seed, (uint32_t JL_AS1 *)(w).counts,     \
+                            (const jl_ix_stored_t JL_AS1 *)(w).entries, (const uint8_t JL_AS1 *)(w).seed, (uint32_t JL_AS1 *)(w).counts,     \
                             (uint32_t JL_AS1 *)(w).hist, f)
 
 __global__ __launch_bounds__(256) void pileup_index_kernel(jl_win_index w) { JL_INDEX_BODY(false, w, nullptr); }
